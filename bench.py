@@ -15,6 +15,11 @@ next step. torch.distributed only carries the 128-byte RCCL id, the barrier and 
   `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) starts its N ranks itself through torch.distributed.run.
   --workload s100k BASELINE configs[3]: 100 000 paths at 8192x8192 split over the ranks (strong)
 
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, ...). --full adds everything else the line
+has carried: HIP-event marks in the timed block with per-kernel times and rooflines, spread, latency, the animated / recount / reupload /
+other-workload side blocks, the multi-GPU weak and tile-split figures, the frame checks against the oracle's CRC and the CPU baseline.
+--dump-outputs DIR writes the frame of the last timed step (see dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -218,6 +223,22 @@ def _frame_crc(workload, image):
     return zlib.crc32(image.tobytes()), (expected["crc32"] if expected else None)
 
 
+DUMP_SAMPLE_PIXELS = 1 << 20
+DUMP_SEED = 20261015
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: what a caller of the timed step receives — the RGBA8 frame [H, W, 4] of the last timed step — as float32 / float64 .npy
+    files, 16 MB at most: frame_sample.npy [2^20, 4] float32 = the pixels at a fixed set of indices (seeded: the same for every run at this
+    frame size, sorted row-major), frame_row_sums.npy [H, 4] float64 = every row's channel sums, so that every pixel of the frame counts."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    pixels = np.ascontiguousarray(image).reshape(-1, image.shape[-1])
+    index = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels.shape[0], size=min(DUMP_SAMPLE_PIXELS, pixels.shape[0]), replace=False))
+    np.save(os.path.join(directory, "frame_sample.npy"), pixels[index].astype(np.float32))
+    np.save(os.path.join(directory, "frame_row_sums.npy"), image.sum(axis=1, dtype=np.float64))
+
+
 def side_workload(name, device, steps, warmup):
     """The step of one of the other BASELINE configs at N = 1, through the same loop as `value` (tessellate + clear + render of resident inputs, 20 set-up steps
     + warm-up in front, barrier-free: one GPU) — a side block of the default line, never `value`: glyphs = configs[2], dashed = configs[4], s100k = configs[3] whole."""
@@ -359,6 +380,8 @@ def run_loopback(args, size, scaling, np):
     for c in comms:
         c.last_timing()  # waits for the communicator's stream: the tail of the last exchange is inside the clock
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result.download())
     # the exchange alone: layers final, nothing else on the GPU
     wall, phases = [], []
     for _ in range(5):
@@ -460,18 +483,22 @@ def main():
     ap.add_argument("--paths", type=int, default=10000, help="shapes of the scene: per GPU (weak) or in total (strong); configs[1] = 10000")
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--scaling", default=None, choices=("weak", "strong"), help="default: strong at N > 1 (the metric's scene split N ways) with the weak figure in a side block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-animated", action="store_true", help="N = 1: skip the `animated` side block (new instance transforms every step)")
-    ap.add_argument("--repeats", type=int, default=5, help="blocks of --steps steps timed again behind the timed region (never `value`): their min / median / max ms per step go to `spread`")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: timing marks and per-kernel / roofline figures, spread, latency, the side "
+                    "blocks, the frame checks and the CPU baseline (the options below marked --full tune it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: the frame of the last one as DIR/frame_sample.npy + "
+                    "DIR/frame_row_sums.npy (float32 / float64, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-animated", action="store_true", help="--full, N = 1: skip the `animated` and `recount` side blocks (new instance transforms every step)")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: blocks of --steps steps timed again behind the timed region (never `value`): their min / median / max ms per step go to `spread`")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"), help="torch.distributed backend for the barrier / id broadcast (nccl = RCCL)")
     ap.add_argument("--exchange", default="cabi", choices=("cabi", "torch"), help="cabi: crh_frame_exchange over RCCL (the product path); torch: the "
                     "torch.distributed statement of the same exchange (contrast_renderer_amd/distributed.py), dense slabs — validation only")
     ap.add_argument("--same-device", action="store_true", help="all ranks use cuda:0 (validation only; implies --exchange torch)")
-    ap.add_argument("--check", action="store_true", help="N > 1: rank 0 also renders every shard itself and compares the composite of those layers with the gathered image "
-                    "(N = 1 always checks: CRC-32 of the downloaded frame against tests/golden/bench_frame_crc.json, the oracle's frame of the same scene)")
-    ap.add_argument("--no-check", action="store_true", help="N = 1: skip the frame CRC")
-    ap.add_argument("--no-side-workloads", action="store_true", help="N = 1, default invocation: skip the `other_workloads` (glyphs, dashed, s100k) and `reupload` side blocks")
-    ap.add_argument("--side-budget-s", type=float, default=150.0, help="the side blocks stop starting new workloads once the run has taken this long (the line says which were left out)")
+    ap.add_argument("--check", action="store_true", help="--full, N > 1: rank 0 also renders every shard itself and compares the composite of those layers with the gathered image "
+                    "(--full at N = 1 always checks: CRC-32 of the downloaded frame against tests/golden/bench_frame_crc.json, the oracle's frame of the same scene)")
+    ap.add_argument("--no-check", action="store_true", help="--full, N = 1: skip the frame CRC")
+    ap.add_argument("--no-side-workloads", action="store_true", help="--full, N = 1, default invocation: skip the `other_workloads` (glyphs, dashed, s100k) and `reupload` side blocks")
+    ap.add_argument("--side-budget-s", type=float, default=150.0, help="--full: the side blocks stop starting new workloads once the run has taken this long (the line says which were left out)")
     ap.add_argument("--reupload", action="store_true", help="every step uploads the paths again into the existing Scene before it tessellates and renders — the "
                     "reference's animated-path use (new geometry every frame, Shape::from_paths with existing_shape): host marshalling + PCIe are inside the "
                     "step, so this is a host-inclusive figure, reported as such and never as the metric's `value`")
@@ -487,6 +514,11 @@ def main():
     ap.add_argument("--workload", default="cubic", choices=("cubic", "glyphs", "dashed", "s100k"),
                     help="cubic = BASELINE configs[1] (the metric's configuration); glyphs = configs[2]; dashed = configs[4]; s100k = configs[3] (100k paths @ 8192^2, split over the ranks)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.check and not args.full:
+        ap.error("--check is part of --full")
+    full = args.full
     t_process = time.perf_counter()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started bare: this process becomes the launcher of its own N ranks (one per GPU, rendezvous on the loopback address)
@@ -723,8 +755,9 @@ def main():
         watchdog.cancel()
     # The timing marks of the timed region (below) take their HIP events from a pool the library grows on first use: one untimed pass of the same
     # length with the marks on creates them here, outside the clock (until round 5 the first timed block created its forty events itself: it was
-    # 2 - 3 % slower than the blocks behind it — `spread` showed it).
-    if os.environ.get("CRH_BENCH_NO_MARKS") is None:
+    # 2 - 3 % slower than the blocks behind it — `spread` showed it). A plain run (no --full) reports no kernel times and runs without marks.
+    marks = full and os.environ.get("CRH_BENCH_NO_MARKS") is None
+    if marks:
         renderer.enable_timing(2)
         run(args.steps)
         sync()
@@ -736,12 +769,12 @@ def main():
     # HIP events around the raster lane's kernels — the dominant kernel's launches — inside the timed region, drained once after it. (Events
     # around EVERY kernel of a step, a dozen per step on three streams, cost the loop 4 %: 0.437 against 0.415 ms per step. The other
     # kernels' times in the run come from a second loop of the same length right after, outside the clock.)
-    renderer.enable_timing(0 if os.environ.get("CRH_BENCH_NO_MARKS") is not None else 2)
+    renderer.enable_timing(2 if marks else 0)
     sync()
     if os.environ.get("CRH_PASS_VERBOSE"):
         sys.stderr.write("[bench] the timed block begins\n")
     t0 = time.perf_counter()
-    run(args.steps)
+    gathered = run(args.steps)  # (N > 1: the image the last step gathered on rank 0)
     sync()
     elapsed = time.perf_counter() - t0
     if os.environ.get("CRH_PASS_VERBOSE"):
@@ -752,6 +785,53 @@ def main():
         elapsed = float(t.item())
     if os.environ.get("CRH_BENCH_NO_MARKS") is not None:  # (measurement of the measurement: what do the timing marks cost the timed region?)
         raise SystemExit(f"[bench] without timing marks: {elapsed / args.steps * 1e3:.4f} ms/step")
+    if args.dump_outputs and rank == 0:  # before anything else draws into the frames
+        if world == 1:
+            last = frames[(reupload_steps[0] - 1) % len(frames)] if args.reupload else frames[(args.steps - 1) % len(frames)]
+            dump_outputs(args.dump_outputs, last.download())
+        else:
+            dump_outputs(args.dump_outputs, gathered.download() if comm is not None else gathered.cpu().numpy())
+    step_s = elapsed / args.steps
+    total_paths = args.paths * world if scaling == "weak" else args.paths
+    ms_per_step = step_s * 1e3
+    out = {
+        "metric": "paths/sec, 10k mixed-Bezier paths @ 4096^2 (tessellate + tile raster)" + (" — HOST-INCLUSIVE: new geometry uploaded every step (--reupload)" if args.reupload else ""),
+        "value": total_paths / step_s,
+        "unit": "paths/s",
+        "mpixel_per_s": size[0] * size[1] / step_s / 1e6,
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "full": full,
+        "config": {
+            "workload": workload + "; step = tessellate (count/scan/emit/hull) + bin + tile raster, inputs resident in HBM",
+            "paths_per_gpu": int(batch.n_shapes),
+            "paths_total": int(total_paths),
+            "segments_per_gpu": int(batch.n_segments),
+            "parallelism": "single GPU" if world == 1 else ((f"TILE split x{world}: every rank holds all paths and draws its slab of tile rows" if tile_split else f"path-index sharding x{world} ({scaling})")
+                                                               + f"; {exchange_note}; the exchange of step i overlaps the rendering of step i + 1"),
+        },
+        "setup": "20 untimed steps before the warm-up: the library times its raster formulations (boundary edges per sample / strip triangles / boundary edges as row spans: same pixels) on this scene and keeps the fastest",
+        "steady_state": "`value` is the steady state of IDENTICAL frames (an animation that re-tessellates and re-draws the same geometry): the tile lists keep the "
+                        "places the verified first passes left them, no read-back; `latency_ms_per_step` (--full) is one host-synchronised step, `bench.py --reupload` new geometry every step",
+        "pipelining": "ms_per_step: up to three steps in flight on three HIP streams (tessellate / bin / raster); latency_ms_per_step (--full): one step, host synchronised before and after",
+        # the boundary hands over host buffers once per scene (crh_scene_upload); never part of `value`
+        "host_inclusive": {"upload_ms": upload_s * 1e3, "paths_per_s_first_frame": batch.n_shapes / (upload_s + step_s),
+                           "input_bytes": int(batch.input_bytes())},
+    }
+    if not full:  # the headline and nothing else
+        scene.check()
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     kernel_times = renderer.kernel_times()  # the raster lane of the timed steps
     # the spread of the timed region: the same block of K steps again, R times, each bracketed like the timed one (never `value`)
     blocks = []
@@ -1031,9 +1111,6 @@ def main():
     triangle_pass = launches_of("raster_prim_setup") > launches_of("raster_bin")
     traffic, traffic_source = measured_traffic(dominant, args.workload, triangle_pass) if default_workload else (None, None)
 
-    step_s = elapsed / args.steps
-    total_paths = args.paths * world if scaling == "weak" else args.paths
-    ms_per_step = step_s * 1e3
     # whole-step algorithmic bytes: the tessellation reads the control data and writes the emitted bytes, the raster reads the
     # emitted bytes and writes the frame (the raster mark already carries emitted + 80 B / shape + W * H * 4); binning has none
     # (every mark of the tessellation lane carries what its kernels emit — tess_fused / tess_emit the vertex and index streams, tess_hull the hull vertices —; the
@@ -1041,38 +1118,13 @@ def main():
     # sets, and silently dropped the tessellation's bytes: VERDICT r05)
     tess_bytes = sum(v.get("algorithmic_bytes", 0) for k, v in kernels.items() if k.startswith("tess_"))
     step_bytes = int(batch.input_bytes()) + tess_bytes + max(kernels.get("raster_tiles", {}).get("algorithmic_bytes", 0), kernels.get("raster_rows", {}).get("algorithmic_bytes", 0))
-    out = {
-        "metric": "paths/sec, 10k mixed-Bezier paths @ 4096^2 (tessellate + tile raster)" + (" — HOST-INCLUSIVE: new geometry uploaded every step (--reupload)" if args.reupload else ""),
-        "value": total_paths / step_s,
-        "unit": "paths/s",
-        "mpixel_per_s": size[0] * size[1] / step_s / 1e6,
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
+    out["config"]["covered_fraction"] = covered
+    out.update({
         "latency_ms_per_step": latency_ms,
         "spread": None if not blocks else {"blocks": len(blocks), "steps_per_block": args.steps,
                                            "ms_per_step_min": min(blocks) / args.steps * 1e3, "ms_per_step_median": sorted(blocks)[len(blocks) // 2] / args.steps * 1e3,
                                            "ms_per_step_max": max(blocks) / args.steps * 1e3,
                                            "note": "the timed block of K steps run again R times behind the timed region, each between barrier + synchronize (max over ranks); `value` is the first block alone"},
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": workload + "; step = tessellate (count/scan/emit/hull) + bin + tile raster, inputs resident in HBM",
-            "paths_per_gpu": int(batch.n_shapes),
-            "paths_total": int(total_paths),
-            "segments_per_gpu": int(batch.n_segments),
-            "parallelism": "single GPU" if world == 1 else ((f"TILE split x{world}: every rank holds all paths and draws its slab of tile rows" if tile_split else f"path-index sharding x{world} ({scaling})")
-                                                               + f"; {exchange_note}; the exchange of step i overlaps the rendering of step i + 1"),
-            "covered_fraction": covered,
-        },
-        "setup": "20 untimed steps before the warm-up: the library times its raster formulations (boundary edges per sample / strip triangles / boundary edges as row spans: same pixels) on this scene and keeps the fastest",
-        "steady_state": "`value` is the steady state of IDENTICAL frames (an animation that re-tessellates and re-draws the same geometry): the tile lists keep the "
-                        "places the verified first passes left them, no read-back; `latency_ms_per_step` is one host-synchronised step, `bench.py --reupload` new geometry every step",
-        "pipelining": "ms_per_step: up to three steps in flight on three HIP streams (tessellate / bin / raster); latency_ms_per_step: one step, host synchronised before and after",
         "roofline": {
             "kernel": dominant,
             "bound": "hbm",
@@ -1109,10 +1161,7 @@ def main():
         "animated": animated,
         "recount": recount,
         "check": check,
-        # the boundary hands over host buffers once per scene (crh_scene_upload); never part of `value`
-        "host_inclusive": {"upload_ms": upload_s * 1e3, "paths_per_s_first_frame": batch.n_shapes / (upload_s + step_s),
-                           "input_bytes": int(batch.input_bytes())},
-    }
+    })
     if traffic_sent is not None:
         out["exchange"] = {"bytes_sent_by_rank0_last_step": traffic_sent[0], "dense_slabs_would_be": traffic_sent[1]}
         out["exchange"].update(exchange_stats or {})

@@ -314,7 +314,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_metrics_scene():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "3", "--paths", "2000", "--size", "1024"],
+    done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "3", "--paths", "2000", "--size", "1024", "--full"],
                           capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [l for l in done.stdout.splitlines() if l.startswith("{")]

@@ -2,7 +2,7 @@
 # GPU box: rebuild everything with each flag set (flags reach all .hip files) and print the tessellation kernel times.
 for flags in "$@"; do
   CRH_EXTRA_FLAGS="$flags" python contrast_renderer_amd/build.py --force > /dev/null 2>&1
-  python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+  python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernels']

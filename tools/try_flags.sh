@@ -5,6 +5,6 @@ fmt='import json,sys; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step
 for flags in "$@"; do
   echo "== flags: $flags"
   CRH_EXTRA_FLAGS="$flags" python contrast_renderer_amd/build.py --force > /dev/null 2>&1 || echo BUILD FAILED
-  for w in ${WORKLOADS:-cubic}; do CRH_NO_PIPELINE=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload $w 2>&1 | tail -1 | python -c "$fmt"; done
+  for w in ${WORKLOADS:-cubic}; do CRH_NO_PIPELINE=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload $w 2>&1 | tail -1 | python -c "$fmt"; done
 done
 python contrast_renderer_amd/build.py --force > /dev/null 2>&1

@@ -6,7 +6,7 @@ for b in ${BATCHES:-4 8 16 32}; do
   CRH_EXTRA_FLAGS=-DCRH_HULL_BATCH=$b python contrast_renderer_amd/build.py --force > /dev/null 2>&1
   for w in glyphs cubic; do
     echo "== CRH_HULL_BATCH=$b $w"
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload $w 2>&1 | tail -1 | python -c "$fmt"
+    python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload $w 2>&1 | tail -1 | python -c "$fmt"
   done
 done
 python contrast_renderer_amd/build.py --force > /dev/null 2>&1

@@ -5,6 +5,6 @@ fmt='import json,sys; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step
 for w in 5 4 3; do
   CRH_EXTRA_FLAGS=-DCRH_STROKE_TILE_WAVES=$w python contrast_renderer_amd/build.py --force > /dev/null 2>&1
   echo "== CRH_STROKE_TILE_WAVES=$w"
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --workload dashed 2>&1 | tail -1 | python -c "$fmt"
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --workload dashed 2>&1 | tail -1 | python -c "$fmt"
 done
 python contrast_renderer_amd/build.py --force > /dev/null 2>&1

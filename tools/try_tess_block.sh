@@ -6,7 +6,7 @@ for b in 256 128 64; do
   CRH_EXTRA_FLAGS=-DCRH_TESS_BLOCK=$b python contrast_renderer_amd/build.py --force > /dev/null 2>&1
   for w in ${WORKLOADS:-cubic glyphs}; do
     echo "== CRH_TESS_BLOCK=$b $w (ms/step pipelined, latency; tess kernels in-run / alone)"
-    python bench.py --steps 30 --warmup 5 --no-cpu-baseline --workload $w 2>&1 | tail -1 | python -c "$fmt"
+    python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --workload $w 2>&1 | tail -1 | python -c "$fmt"
   done
 done
 python contrast_renderer_amd/build.py --force > /dev/null 2>&1
