@@ -24,13 +24,13 @@ void launch_build_elements(const UploadBuild& u, hipStream_t stream);
 void launch_prim_ranges(const SceneDev& s, uint32_t* shape_ncand, uint32_t* shape_prim_begin, uint32_t* scratch, hipStream_t stream);
 void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup);
 void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_fill);
-void launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke);
+uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke); // -> RasterVariant
 void launch_item_ranges(const SceneDev& s, const RasterParams& r, uint32_t* item_ncand, uint32_t* item_prim_begin, uint32_t* scratch, hipStream_t stream);
 void launch_composite(const uint8_t* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, uint8_t* dst, hipStream_t stream);
 void launch_state_colors_from_image(const RasterParams& r, uint32_t samples, hipStream_t stream);
 // raster_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop, binned in one traversal
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);
-void launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin);
+uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin); // -> BinRoute | items per workgroup << 16
 void launch_scatter(const RasterParams& r, hipStream_t stream, MarkFn mark, void* ctx);
 void launch_shape_bounds(const SceneDev& s, float* bounds, hipStream_t stream);
 void launch_slab_items(const RasterParams& r, uint8_t* elsewhere, hipStream_t stream);
@@ -39,7 +39,7 @@ bool bin_itemwise(const RasterParams& r);
 void flat_batches(const uint32_t* cost, uint32_t n_items, std::vector<uint32_t>& runs);
 void flat_batch_limits(uint32_t n_items, uint32_t limits[4]);
 void launch_tile_bases(const uint32_t* tile_count, uint32_t* caps, uint32_t* tile_base, uint32_t* scratch, uint32_t n_tiles, uint32_t tiles_x, uint32_t radius, hipStream_t stream);
-void launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke);
+uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke); // -> RasterVariant
 void launch_fmath(int fn, const float* a, const float* b, float* out, uint64_t n, hipStream_t stream);
 } // namespace crh
 
@@ -330,6 +330,11 @@ struct crh_frame {
     bool carry = false;            // the frame keeps its pass state in HBM
     bool carry_valid = false;      // ... and the planes hold what the earlier passes left (false: to be initialised in front of the next pass)
     bool carry_recolor = false;    // the exchange wrote the frame's pixels behind the planes' back: the sample colours start from the image again
+    // What the frame's last pass ran (crh_debug_frame_last_pass; the tests that pin a path check that they reached it): the formulation
+    // (choose_pass' 1 / 2 / 3, + 256 when it is the Scene's measured choice), whether it was the general one, RasterVariant, and BinRoute
+    // + 256 with the lists in place (direct), + 512 in the heavy-first tile order, + items per binning workgroup << 16 (0: measured runs).
+    // All zero for a pass that launched nothing (forget_last_pass).
+    uint32_t last_formulation = 0, last_general = 0, last_raster = 0, last_bin = 0;
     bool cleared = true;
     bool pairs_known = false;
     // Direct tile lists (RasterParams::direct): once a pass of a Scene into this frame has been verified, the places of its lists are kept
@@ -878,8 +883,8 @@ size_t grown_pair_bytes(const crh_frame* f, const uint32_t ov[8]) {
 // The pass of this plain frame — 1: boundary edges, per-sample raster kernel; 2: strip triangles; 3: boundary edges, row-span raster kernel
 // (k_raster_rows: msaa 1, no strokes) — and, through `timed`, which trial (candidate 0 edges, 1 triangles, 2 rows) its events belong to, or -1.
 constexpr uint32_t kMovingListRadius = 3u;
-int choose_pass(crh_scene* sc, const crh_frame* f, int* timed) {
-    *timed = -1;
+int choose_pass(crh_scene* sc, const crh_frame* f, int* timed, bool* measured) {
+    *timed = -1, *measured = false;
     const bool rows_eligible = sc->renderer->config.msaa_sample_count == 1 && !sc->has_stroke && getenv("CRH_NO_ROWS") == nullptr;
     if (f->triangle_pass_for == sc && f->triangle_pass_generation == sc->generation) return 2;
     if (getenv("CRH_TRIANGLE_PASS")) return 2;
@@ -894,6 +899,7 @@ int choose_pass(crh_scene* sc, const crh_frame* f, int* timed) {
         for (crh_scene::PassTrial& t : sc->pass_trial) t.started = t.recorded = false;
     }
     if (sc->pass_choice == 3 && !rows_eligible) return 1;
+    *measured = sc->pass_choice != 0;
     if (sc->pass_choice) return sc->pass_choice;
     const uint32_t candidates = rows_eligible ? 3u : 2u;
     static const int code_of[3] = {1, 2, 3};
@@ -921,6 +927,7 @@ int choose_pass(crh_scene* sc, const crh_frame* f, int* timed) {
             }
             sc->pass_choice = code_of[best];
             sc->pass_known[sc->pass_class] = (uint8_t)sc->pass_choice;
+            *measured = true;
             if (getenv("CRH_PASS_VERBOSE"))
                 std::fprintf(stderr, "[contrast-hip] pass trial: edges %.3f ms, triangles %.3f ms, edges as row spans %.3f ms per frame -> %s\n", sc->pass_ms[0], sc->pass_ms[1],
                              candidates == 3u ? sc->pass_ms[2] : 0.0f, best == 0u ? "edges" : (best == 1u ? "triangles" : "row spans"));
@@ -1080,8 +1087,10 @@ crh_status settle_frames_of(crh_scene* sc, bool forget) {
 }
 
 // `again`: the remedy of settle_frame — the frame's last pass once more, from the instance buffer it used
+void forget_last_pass(crh_frame* f) { f->last_formulation = f->last_general = f->last_raster = f->last_bin = 0u; }
 crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     crh_renderer* r = sc->renderer;
+    forget_last_pass(f); // (until the kernels of this pass are launched: an early exit reports nothing rather than the pass before)
     if (!f->cleared && f->check_pending) { // rendering over existing content: that content has to be final
         const crh_status st = settle_frame(f);
         if (st != CRH_OK) return st;
@@ -1221,7 +1230,8 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         p.state_load = f->carry_valid ? 1u : 0u;
     }
     int timed = -1;
-    const int pass = p.general == 0u ? choose_pass(sc, f, &timed) : 2;
+    bool measured = false;
+    const int pass = p.general == 0u ? choose_pass(sc, f, &timed, &measured) : 2;
     const bool edges = pass != 2;
     // k_raster_rows keeps fill + 65536 * hull in one cell: exact below 2^15 entries per tile. Lists in place grow by half at most between two
     // verified passes, so a frame that has ever shown a list of 16 384 entries keeps the per-sample kernel.
@@ -1303,9 +1313,11 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
                 launch_slab_items(p, set.item_elsewhere.as<uint8_t>(), bin);
                 p.item_elsewhere = set.item_elsewhere.as<uint8_t>();
             }
-            launch_bin_edges(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
-        } else
-        launch_bin(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
+            f->last_bin = launch_bin_edges(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
+        } else {
+            launch_bin(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
+            f->last_bin = kBinTriangles;
+        }
         if (f->pairs_known) break;
         uint32_t ov[8];
         HIP_TRY(hipMemcpyAsync(ov, p.overflow, 32, hipMemcpyDeviceToHost, bin));
@@ -1415,9 +1427,12 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         p.state_load = 1u; // (the planes now hold the frame's state: zero counters, the image's colours)
     }
     if (edges)
-        launch_raster_edges(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke);
+        f->last_raster = launch_raster_edges(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke);
     else
-        launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke);
+        f->last_raster = launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke);
+    f->last_formulation = (uint32_t)pass | (measured ? 256u : 0u), f->last_general = p.general | (r->pipeline ? 0u : 256u);
+    if (direct) f->last_bin |= 256u;
+    if (p.tile_order) f->last_bin |= 512u;
     HIP_TRY(hipEventRecord(set.raster_done, r->stream));
     HIP_TRY(hipEventRecord(sc->rec_raster_done[rec], r->stream));
     HIP_TRY(hipStreamWaitEvent(r->aux_stream, set.raster_done, 0));
@@ -2388,6 +2403,7 @@ crh_status crh_scene_render_draws(crh_scene* sc, crh_frame* f, const float* tran
     }
     if (items.empty()) { // an empty pass still resolves a cleared frame
         f->n_items = 0;
+        forget_last_pass(f);
         if (f->cleared) {
             HIP_TRY(order_after_external(f, r->stream));
             HIP_TRY(hipMemsetAsync(f->rgba8.p, 0, f->image_bytes(), r->stream));
@@ -2480,6 +2496,11 @@ extern "C" crh_status crh_debug_frame_counters16(crh_frame* f, uint32_t out[16])
     HIP_TRY(f->renderer->sync());
     HIP_TRY(hipMemcpy(out, f->sets[f->last_set].overflow_p, 64, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemset(static_cast<uint8_t*>(f->sets[f->last_set].overflow_p) + 32, 0, 32));
+    return CRH_OK;
+}
+extern "C" crh_status crh_debug_frame_last_pass(crh_frame* f, uint32_t out[4]) { // tests only (host fields, no device): what the frame's last pass ran
+    if (!f || !out) return CRH_ERR_INVALID_ARGUMENT;
+    out[0] = f->last_formulation, out[1] = f->last_general, out[2] = f->last_raster, out[3] = f->last_bin;
     return CRH_OK;
 }
 extern "C" crh_status crh_debug_frame_words(crh_frame* f, uint32_t out[128]) { // tools only: the whole 512-byte flag / counter block of the last set
@@ -2590,6 +2611,7 @@ crh_status crh_frame_set_tile_rows(crh_frame* f, uint32_t row_begin, uint32_t ro
     HIP_TRY(hipMemsetAsync(f->rgba8.p, 0, f->image_bytes(), r->stream));
     f->slab_ty0 = (row_begin + 15u) / 16u, f->slab_ty1 = (row_begin == 0u && row_end == f->height) ? 0xFFFFFFFFu : (row_end + 15u) / 16u;
     f->cleared = true, f->counts_describe_pixels = false, f->check_pending = false, f->last_scene = nullptr;
+    f->carry = f->carry_valid = f->carry_recolor = false; // (the stencil and alpha layers go with the pixels, as in crh_frame_clear: a kept plane would bring back the colours from before)
     f->pairs_known = false, f->tile_order_ready = false; // (the next pass is a verified one: it orders the slab's tiles)
     return CRH_OK;
 }

@@ -1180,7 +1180,7 @@ void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hip
     if (after_fill) (void)hipEventRecord(after_fill, stream);
     if (mark) mark(ctx, "raster_tile_fill", 0);
 }
-void launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
+uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
                    uint64_t raster_bytes, bool has_stroke) {
     // 8x8-tile blocks, an equal number per XCD (k_raster_tile's tile order)
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;
@@ -1203,6 +1203,7 @@ void launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, h
     }
 #undef CRH_LAUNCH_TILE
     if (mark) mark(ctx, "raster_tiles", raster_bytes);
+    return r.general ? kRasterOps : kRasterTile;
 }
 // exported to raster_edges.hip
 void launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t* block_sum, uint32_t n, hipStream_t stream) {

@@ -3868,7 +3868,7 @@ void flat_batch_limits(uint32_t n_items, uint32_t limits[4]) {
     const FlatShape shape = flat_shape(flat_threads_for(n_items));
     limits[0] = shape.batch, limits[1] = shape.tris, limits[2] = shape.edges, limits[3] = shape.pool;
 }
-void launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_bin) {
+uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_bin) {
     // tile_count and, right behind it, the overflow words (overflow[8 ...] are the cursors of the pair sub-streams): one memset (tile_cursor, in front, is the triangle pass')
     (void)hipMemsetAsync(r.tile_count, 0, sizeof(uint32_t) * r.n_tiles + 32 + 4 * kSubStreams + 32, stream); // (... and kExtraTurnsWord behind them)
     // Items per workgroup. One is best while the grid is small (S10k: 0.169 ms; two: 0.189, four: 0.21 — an item is a chain of dependent
@@ -3878,8 +3878,10 @@ void launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples
     // k_bin_edges for every item: CRH_BIN_ITEMWISE (A/B runs, tests), or a pass whose AVERAGE item is beyond what a batch of k_bin_flat holds
     // (the dashed strokes of config 5: a thousand line triangles per Shape) — every item would be queued anyway
     const bool itemwise = bin_itemwise(r);
+    uint32_t route = r.n_items == 0u ? 0u : (itemwise ? kBinItemwise : (r.bin_batches ? kBinFlatBatches : kBinFlatItems)); // (0: no item, nothing launched)
     if (r.n_items && itemwise) {
         const uint32_t items_per_group = pinned ? pinned : min(8u, max(1u, (r.n_items + 12287u) / 12288u));
+        route |= min(items_per_group, 255u) << 16;
         const uint32_t bin_grid = (r.n_items + items_per_group - 1u) / items_per_group;
         if (samples == 4)
             hipLaunchKernelGGL((k_bin_edges<4, false>), dim3(bin_grid), dim3(128), 0, stream, s, r);
@@ -3898,6 +3900,7 @@ void launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples
         const uint32_t fitting = max(1u, min(shape.batch, min(by_tris, by_edges)));
         const uint32_t items_per_group = pinned ? min(pinned, shape.batch) : min(fitting, max(1u, (r.n_items + resident - 1u) / resident));
         const uint32_t flat_grid = r.bin_batches ? r.n_bin_batches : (r.n_items + items_per_group - 1u) / items_per_group, queue_grid = min(r.n_items, 4096u);
+        if (!r.bin_batches) route |= min(items_per_group, 255u) << 16;
         if (samples == 4) {
             if (shape.threads == 64u) hipLaunchKernelGGL((k_bin_flat<4, 64u>), dim3(flat_grid), dim3(64), 0, stream, s, r, items_per_group);
             else hipLaunchKernelGGL((k_bin_flat<4, kFlatThreads>), dim3(flat_grid), dim3(kFlatThreads), 0, stream, s, r, items_per_group);
@@ -3912,6 +3915,7 @@ void launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples
     if (mark) mark(ctx, "raster_bin", 0);
     if (!r.direct) launch_scan_tiles(r, stream);
     if (mark) mark(ctx, "raster_tile_scan", 0);
+    return route;
 }
 void launch_scatter(const RasterParams& r, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx) {
     if (r.pair_capacity && !r.direct) hipLaunchKernelGGL(k_scatter, dim3((r.pair_capacity + 255u) / 256u), dim3(256), 0, stream, r);
@@ -3981,7 +3985,7 @@ void launch_tile_bases(const uint32_t* tile_count, uint32_t* caps, uint32_t* til
     hipLaunchKernelGGL(k_tile_base_local, dim3(blocks), dim3(64), 0, stream, caps, tile_base, scratch, n_tiles);
     hipLaunchKernelGGL(k_tile_base_add, dim3(blocks), dim3(64), 0, stream, tile_base, scratch, n_tiles, blocks);
 }
-void launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
+uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
                          uint64_t raster_bytes, bool has_stroke) {
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;
     const uint32_t blocks = ((r.tiles_x + kBlock - 1u) / kBlock) * ((r.tiles_y + kBlock - 1u) / kBlock);
@@ -3991,7 +3995,9 @@ void launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samp
     const bool fill_kernel = !(fill_env && fill_env[0] == '0') && r.winding_mask <= 0xFFFFu && r.fill_cells != 0u;
 #define CRH_LAUNCH_EDGES(S_, ROWS_, STROKES_, LONG_) \
     hipLaunchKernelGGL((k_raster_edges<S_, ROWS_, STROKES_, LONG_>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r)
-    if (samples == 1 && !has_stroke && r.rows) { // the row-span kernel: winding numbers accumulated in LDS, lanes over (entry, sample row)
+    uint32_t variant = kRasterEdges;
+    if (samples == 1 && !has_stroke && r.rows) {
+        variant = r.long_lists ? kRasterRowsLong : kRasterRows; // the row-span kernel: winding numbers accumulated in LDS, lanes over (entry, sample row)
         if (r.long_lists)
             hipLaunchKernelGGL((k_raster_rows<true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
         else
@@ -4005,13 +4011,16 @@ void launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samp
         // beyond one chunk — it is as fast as the one without, 0.1655 against 0.168 ms, and it is the build without scratch memory)
         // (... and ONE build for every frame: round 5's six-wave build for frames of long lists is gone with its reason, see CRH_FILL_TILE_WAVES)
         hipLaunchKernelGGL((k_raster_fill<true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
+        variant = kRasterFill;
     } else if (r.long_lists) {
         CRH_LAUNCH_EDGES(1, 4, false, true);
+        variant = kRasterEdgesLong;
     } else {
         CRH_LAUNCH_EDGES(1, 4, false, false);
     }
 #undef CRH_LAUNCH_EDGES
     if (mark) mark(ctx, (samples == 1 && !has_stroke && r.rows) ? "raster_rows" : "raster_tiles", raster_bytes);
+    return variant;
 }
 
 } // namespace crh

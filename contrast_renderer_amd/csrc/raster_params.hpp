@@ -20,6 +20,12 @@ struct DrawItem {
     uint32_t refs; // bits 0-7 clip depth of the stencil phase, 8-15 clip depth of the cover phase, 16-23 alpha layer
 };
 
+// What the launch functions report they launched (crh_debug_frame_last_pass): the raster kernel of a pass ...
+enum RasterVariant : uint32_t { kRasterFill = 1, kRasterEdges = 2, kRasterEdgesLong = 3, kRasterRows = 4, kRasterRowsLong = 5, kRasterTile = 6, kRasterOps = 7 };
+// ... and its binning route (the triangle pass' k_prim_setup / k_tile_walk, k_bin_flat over a count of items per workgroup or over the runs
+// a verified pass measured, k_bin_edges item by item)
+enum BinRoute : uint32_t { kBinTriangles = 1, kBinFlatItems = 2, kBinFlatBatches = 3, kBinItemwise = 4 };
+
 constexpr uint32_t kTessStatusWord = 126; // ... the status word of the optimistic tessellation a pass drew (api.hip: crh_scene::optimistic), copied in by the host side
 constexpr uint32_t kExtraTurnsWord = 76; // of RasterParams::overflow: behind the 8 flag words and the 64 cursors of the pair sub-streams
 struct RasterParams {

@@ -293,9 +293,10 @@ def scene_dashed_strokes(n_paths=2000, size=(4096, 4096), config_index=5, angle_
     return dict(batch=batch, transforms=transforms, colors=colors, width=size[0], height=size[1], msaa=msaa, winding_bits=4, name="Sdash")
 
 
-def scene_mixed(n_shapes=64, size=(512, 512), seed=7):
+def scene_mixed(n_shapes=64, size=(512, 512), seed=7, fills_only=False):
     """A small everything-scene for parity tests: every segment type, filled and stroked paths in the same Shape,
-    open / closed strokes, both curve approximations, solid and dashed groups, all joins and caps."""
+    open / closed strokes, both curve approximations, solid and dashed groups, all joins and caps. `fills_only`: the same outlines
+    (the same random draws), every path filled and no stroke options — the scenes the fill-only raster kernels take."""
     rng = np.random.RandomState(seed)
     from .path import Path, batch_from_shapes
     shapes, colors, centres, radii = [], [], [], []
@@ -348,8 +349,10 @@ def scene_mixed(n_shapes=64, size=(512, 512), seed=7):
                     dyn.append(DynamicStrokeOptions.Solid(Join(s % 3), Cap(int(rng.randint(0, 7))), Cap(int(rng.randint(0, 7)))))
                 approx = CurveApproximation.UniformTangentAngle(rng.uniform(0.08, 0.3)) if s % 2 else CurveApproximation.UniformlySpacedParameters(int(rng.randint(1, 9)))
                 path.stroke_options = StrokeOptions(rng.uniform(1.0, 9.0) / radii[-1], rng.uniform(-0.5, 0.5) if s % 5 == 0 else 0.0, rng.uniform(0.6, 4.0), bool((s + p) % 2), group, approx)
+            if fills_only:
+                path.stroke_options = None
             paths.append(path)
-        shapes.append((dyn, paths))
+        shapes.append(([] if fills_only else dyn, paths))
         a = 1.0 if s % 2 else rng.uniform(0.3, 1.0)
         colors.append((rng.uniform(), rng.uniform(), rng.uniform(), a))
     batch = batch_from_shapes(shapes)

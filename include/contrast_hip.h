@@ -401,7 +401,8 @@ crh_status crh_frame_exchange(crh_comm* comm, crh_frame* layer, crh_frame* resul
  * [row_begin, row_end) only (multiples of 16, or the frame's height; crh_comm_slab_rows gives rank g's), the rest of the frame is and stays
  * transparent. Every rank uploads, tessellates and bins ALL paths and draws 1 / world of the tiles; crh_frame_exchange of such layers
  * moves nothing in its all-to-all, composites nothing, and gathers an image that is bit-equal to a single GPU's (path sharding with RGBA8
- * layers: <= 2/255). (0, height) gives the whole frame back. Waits for the frame's last pass. */
+ * layers: <= 2/255). (0, height) gives the whole frame back. Waits for the frame's last pass. A LoadOp::Clear of the pixels, the stencil
+ * attachment and the alpha layers: the frame keeps no pass state afterwards (as after crh_frame_clear); the depth attachment is left alone. */
 crh_status crh_frame_set_tile_rows(crh_frame* frame, uint32_t row_begin, uint32_t row_end);
 /* collective, the tile split's own exchange: every rank's `layer` holds its slab of rows (crh_frame_set_tile_rows with crh_comm_slab_rows' rows)
  * and the slabs travel straight from the layers' pixel rows into rank 0's `result` frame (NULL elsewhere): one grouped ncclSend / ncclRecv
