@@ -9,69 +9,9 @@ import pytest
 
 from contrast_renderer_amd import Cap, CurveApproximation, DynamicStrokeOptions, Join, Path, SegmentType, StrokeOptions, batch_from_shapes, scenes
 
+from ground_truth_util import distance_to_polyline, flatten, pixel_centres, to_pixels, winding_numbers
+
 SIZE = 96
-
-
-def flatten(path, samples=400, closed=True):
-    """-> [n, 2] points along the exact curve in path coordinates."""
-    t = np.linspace(0.0, 1.0, samples, endpoint=False)[:, None]
-    out = []
-    p0 = np.asarray(path.start, dtype=np.float64)
-    for kind, rec in zip(path.segment_types, path.records):
-        r = np.asarray(rec, dtype=np.float64)
-        if kind == SegmentType.Line:
-            pts, w = [p0, r[0:2]], [1.0, 1.0]
-        elif kind == SegmentType.IntegralQuadraticCurve:
-            pts, w = [p0, r[0:2], r[2:4]], [1.0, 1.0, 1.0]
-        elif kind == SegmentType.IntegralCubicCurve:
-            pts, w = [p0, r[0:2], r[2:4], r[4:6]], [1.0] * 4
-        elif kind == SegmentType.RationalQuadraticCurve:
-            pts, w = [p0, r[1:3], r[3:5]], [1.0, r[0], 1.0]
-        else:
-            pts, w = [p0, r[4:6], r[6:8], r[8:10]], list(r[0:4])
-        n = len(pts) - 1
-        binom = [1, n, n * (n - 1) // 2, 1][:n] + [1] if n == 3 else ([1, 2, 1] if n == 2 else [1, 1])
-        basis = [b * t ** k * (1 - t) ** (n - k) * wk for k, (b, wk) in enumerate(zip(binom, w))]
-        den = sum(basis)
-        out.append(sum(bk * np.asarray(pk)[None, :] for bk, pk in zip(basis, pts)) / den)
-        p0 = np.asarray(pts[-1], dtype=np.float64)
-    out.append(p0[None, :] if not closed else np.asarray(path.start, dtype=np.float64)[None, :])
-    return np.concatenate(out)
-
-
-def to_pixels(points, transform, size):
-    m = np.asarray(transform, dtype=np.float64)
-    x = (m[0] * points[:, 0] + m[4] * points[:, 1] + m[12]) * 0.5 + 0.5
-    y = 0.5 - (m[1] * points[:, 0] + m[5] * points[:, 1] + m[13]) * 0.5
-    return np.stack([x * size, y * size], axis=1)
-
-
-def pixel_centres(size):
-    c = np.arange(size) + 0.5
-    return np.stack(np.meshgrid(c, c), axis=-1).reshape(-1, 2)  # row-major: y outer, x inner
-
-
-def winding_numbers(polygon, centres):
-    a, b = polygon[:-1], polygon[1:]
-    px, py = centres[:, 0:1], centres[:, 1:2]
-    upward = (a[None, :, 1] <= py) & (b[None, :, 1] > py)
-    downward = (a[None, :, 1] > py) & (b[None, :, 1] <= py)
-    cross = (b[None, :, 0] - a[None, :, 0]) * (py - a[None, :, 1]) - (px - a[None, :, 0]) * (b[None, :, 1] - a[None, :, 1])
-    return (upward & (cross > 0)).sum(axis=1) - (downward & (cross < 0)).sum(axis=1)
-
-
-def distance_to_polyline(polyline, centres):
-    a, b = polyline[:-1], polyline[1:]
-    d = b - a
-    length2 = np.maximum((d * d).sum(axis=1), 1e-30)
-    best = np.full(len(centres), np.inf)
-    for chunk in range(0, len(a), 512):
-        aa, dd, ll = a[chunk:chunk + 512], d[chunk:chunk + 512], length2[chunk:chunk + 512]
-        rel = centres[:, None, :] - aa[None, :, :]
-        t = np.clip((rel * dd[None]).sum(axis=2) / ll[None], 0.0, 1.0)
-        diff = rel - t[..., None] * dd[None]
-        best = np.minimum(best, np.sqrt((diff * diff).sum(axis=2)).min(axis=1))
-    return best
 
 
 def test_filled_cubic_paths_cover_exactly_the_pixels_with_nonzero_winding(oracle_lib):
