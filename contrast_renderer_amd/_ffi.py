@@ -115,6 +115,20 @@ class ConfigC(C.Structure):
     ]
 
 
+class BlendComponentC(C.Structure):  # crh_blend_component = wgpu::BlendComponent
+    _fields_ = [("src_factor", C.c_uint32), ("dst_factor", C.c_uint32), ("operation", C.c_uint32)]
+
+
+class ColorTargetStateC(C.Structure):  # crh_color_target_state = wgpu::ColorTargetState without the format (+ the blend constant)
+    _fields_ = [
+        ("blend_enabled", C.c_uint32),
+        ("color", BlendComponentC),
+        ("alpha", BlendComponentC),
+        ("write_mask", C.c_uint32),
+        ("constant", C.c_float * 4),
+    ]
+
+
 class KernelTimeC(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_float), ("algorithmic_bytes", C.c_uint64)]
 
@@ -233,6 +247,8 @@ def load_library():
         "crh_renderer_create": (C.c_int, [C.POINTER(ConfigC), C.c_int, C.POINTER(V)]),
         "crh_renderer_destroy": (None, [V]),
         "crh_renderer_get_config": (C.c_int, [V, C.POINTER(ConfigC)]),
+        "crh_renderer_create_blended": (C.c_int, [C.POINTER(ConfigC), C.POINTER(ColorTargetStateC), C.c_int, C.POINTER(V)]),
+        "crh_renderer_get_blending": (C.c_int, [V, C.POINTER(ColorTargetStateC)]),
         "crh_convert_dynamic_stroke_options": (C.c_int, [C.POINTER(DynamicStrokeOptionsC), C.POINTER(DynamicStrokeDescriptorC)]),
         "crh_scene_upload": (C.c_int, [V, C.POINTER(PathBatchC), V, C.POINTER(V)]),
         "crh_scene_tessellate": (C.c_int, [V]),
@@ -260,6 +276,7 @@ def load_library():
         "crh_scene_set_instances": (C.c_int, [V, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "crh_scene_render_resident": (C.c_int, [V, V]),
         "crh_scene_render_draws": (C.c_int, [V, V, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(DrawC), C.c_uint32]),
+        "crh_frame_upload": (C.c_int, [V, V]),
         "crh_frame_download": (C.c_int, [V, V]),
         "crh_frame_download_f16": (C.c_int, [V, V]),
         "crh_frame_device_pointer": (C.c_int, [V, C.POINTER(V)]),

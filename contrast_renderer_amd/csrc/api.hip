@@ -24,7 +24,8 @@ void launch_build_elements(const UploadBuild& u, hipStream_t stream);
 void launch_prim_ranges(const SceneDev& s, uint32_t* shape_ncand, uint32_t* shape_prim_begin, uint32_t* scratch, hipStream_t stream);
 void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup);
 void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_fill);
-uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke); // -> RasterVariant
+uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke,
+                       const BlendForm* blend); // -> RasterVariant; blend: nullptr = premultiplied "over", otherwise k_raster_blend
 void launch_item_ranges(const SceneDev& s, const RasterParams& r, uint32_t* item_ncand, uint32_t* item_prim_begin, uint32_t* scratch, hipStream_t stream);
 void launch_composite(const uint8_t* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, uint8_t* dst, hipStream_t stream);
 void launch_state_colors_from_image(const RasterParams& r, uint32_t samples, hipStream_t stream);
@@ -173,6 +174,9 @@ struct Mark {
 struct crh_renderer {
     int n_cus = 256; // compute units of the device (sizes the resident raster grid)
     crh_config config;
+    crh_color_target_state blending;  // Configuration::blending of the colour cover (crh_renderer_create_blended)
+    bool blend_over = true;           // ... is the showcase's premultiplied "over": the passes take the paths they took before blending was configurable
+    BlendForm blend_form = {};       // ... otherwise: what k_raster_blend evaluates (blend_form)
     int device;
     hipStream_t stream;       // raster kernel, copies
     hipStream_t bin_stream;   // primitive setup + tile binning: frame N + 1's overlap frame N's raster kernel (double-buffered records / lists)
@@ -1217,7 +1221,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     p.cull_mode = r->config.cull_mode;
     // The general pass keeps the reference's triangle strips (raster.hip): clip nesting / alpha contexts, perspective, depth, and face
     // culling (a cull decision is per strip triangle). Everything else is the edge pass (raster_edges.hip).
-    p.general = (projective || p.depth || r->config.cull_mode != CRH_CULL_NONE || (recorded && f->items_need_ops) || f->carry) ? 1u : 0u;
+    p.general = (projective || p.depth || r->config.cull_mode != CRH_CULL_NONE || (recorded && f->items_need_ops) || f->carry || !r->blend_over) ? 1u : 0u;
     p.state_stencil = nullptr, p.state_alpha = nullptr, p.state_color = nullptr, p.state_load = 0u, p.state_layers = 0u;
     p.winding_bits = r->config.winding_counter_bits;
     if (f->carry) { // the frame keeps clip counters, winding counters, saved alphas and sample colours from pass to pass
@@ -1256,7 +1260,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     p.rgba8 = f->rgba8.as<uint8_t>();
     p.format = f->format;
     p.debug = getenv("CRH_RASTER_DEBUG") ? (uint32_t)atoi(getenv("CRH_RASTER_DEBUG")) : 0u;
-    p.occlude = tame_colors ? 1u : 0u;
+    p.occlude = (tame_colors && r->blend_over) ? 1u : 0u; // (an opaque cover hides what is below it under "over" only)
     r->begin_marks(2);
     // Rendering over existing content is not repeatable (the target is read and overwritten), so the optimistic tile-list capacity with a
     // transparent re-run after the fact is only used for cleared frames; otherwise the pair count is checked before the raster kernel runs.
@@ -1429,7 +1433,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     if (edges)
         f->last_raster = launch_raster_edges(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke);
     else
-        f->last_raster = launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke);
+        f->last_raster = launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke, r->blend_over ? nullptr : &r->blend_form);
     f->last_formulation = (uint32_t)pass | (measured ? 256u : 0u), f->last_general = p.general | (r->pipeline ? 0u : 256u);
     if (direct) f->last_bin |= 256u;
     if (p.tile_order) f->last_bin |= 512u;
@@ -1562,6 +1566,76 @@ crh_status settle_frame_cheaply(crh_frame* f) {
     f->check_pending = false;
     return CRH_OK;
 }
+// ---- Configuration::blending (renderer.rs:380-382): the showcase's state, its validation and the form k_raster_blend evaluates
+crh_color_target_state over_state() { // examples/showcase/main.rs:32-43
+    crh_color_target_state b = {};
+    b.blend_enabled = 1u;
+    b.color = b.alpha = crh_blend_component{CRH_BLEND_ONE, CRH_BLEND_ONE_MINUS_SRC_ALPHA, CRH_BLEND_OP_ADD};
+    b.write_mask = CRH_COLOR_WRITE_ALL;
+    return b;
+}
+bool is_over(const crh_color_target_state& b) { // (the constant does not matter: no Constant factor is used)
+    auto over = [](const crh_blend_component& c) { return c.src_factor == CRH_BLEND_ONE && c.dst_factor == CRH_BLEND_ONE_MINUS_SRC_ALPHA && c.operation == CRH_BLEND_OP_ADD; };
+    return b.blend_enabled != 0u && over(b.color) && over(b.alpha) && b.write_mask == CRH_COLOR_WRITE_ALL;
+}
+crh_status validate_blending(const crh_color_target_state& b) {
+    if (b.blend_enabled > 1u || b.write_mask > CRH_COLOR_WRITE_ALL) return CRH_ERR_INVALID_ARGUMENT;
+    for (float c : b.constant)
+        if (!std::isfinite(c)) return CRH_ERR_INVALID_ARGUMENT;
+    bool dual_source = false;
+    for (const crh_blend_component* c : {&b.color, &b.alpha}) {
+        if (c->src_factor > CRH_BLEND_ONE_MINUS_SRC1_ALPHA || c->dst_factor > CRH_BLEND_ONE_MINUS_SRC1_ALPHA || c->operation > CRH_BLEND_OP_MAX) return CRH_ERR_INVALID_ARGUMENT;
+        // WebGPU's pipeline validation: Min and Max take no factors (both must be One)
+        if ((c->operation == CRH_BLEND_OP_MIN || c->operation == CRH_BLEND_OP_MAX) && (c->src_factor != CRH_BLEND_ONE || c->dst_factor != CRH_BLEND_ONE)) return CRH_ERR_INVALID_ARGUMENT;
+        dual_source = dual_source || c->src_factor >= CRH_BLEND_SRC1 || c->dst_factor >= CRH_BLEND_SRC1;
+    }
+    return dual_source ? CRH_ERR_UNSUPPORTED : CRH_OK; // (the colour cover has one output)
+}
+// One factor of component c (0: rgb, 1: alpha) as the linear form of raster_params.hpp BlendFactorForm, for the channels [ch0, ch1)
+void factor_form(BlendFactorForm& f, uint32_t factor, int c, const float constant[4], int ch0, int ch1) {
+    const float inf = INFINITY;
+    f.s[c] = f.sa[c] = f.d[c] = f.da[c] = 0.0f;
+    f.cap0[c] = inf, f.cap1[c] = 0.0f;
+    float c0 = 0.0f;
+    bool from_constant = false, one_minus_constant = false;
+    switch (factor) {
+    case CRH_BLEND_ZERO: break;
+    case CRH_BLEND_ONE: c0 = 1.0f; break;
+    case CRH_BLEND_SRC: f.s[c] = 1.0f; break;
+    case CRH_BLEND_ONE_MINUS_SRC: c0 = 1.0f, f.s[c] = -1.0f; break;
+    case CRH_BLEND_SRC_ALPHA: f.sa[c] = 1.0f; break;
+    case CRH_BLEND_ONE_MINUS_SRC_ALPHA: c0 = 1.0f, f.sa[c] = -1.0f; break;
+    case CRH_BLEND_DST: f.d[c] = 1.0f; break;
+    case CRH_BLEND_ONE_MINUS_DST: c0 = 1.0f, f.d[c] = -1.0f; break;
+    case CRH_BLEND_DST_ALPHA: f.da[c] = 1.0f; break;
+    case CRH_BLEND_ONE_MINUS_DST_ALPHA: c0 = 1.0f, f.da[c] = -1.0f; break;
+    case CRH_BLEND_SRC_ALPHA_SATURATED: // min(As, 1 - Ad) for rgb, 1 for alpha
+        if (c == 0) f.sa[c] = 1.0f, f.cap0[c] = 1.0f, f.cap1[c] = -1.0f;
+        else c0 = 1.0f;
+        break;
+    case CRH_BLEND_CONSTANT: from_constant = true; break;
+    default: from_constant = one_minus_constant = true; break; // CRH_BLEND_ONE_MINUS_CONSTANT (validated)
+    }
+    for (int ch = ch0; ch < ch1; ++ch) {
+        const float k = std::min(std::max(constant[ch], 0.0f), 1.0f); // the constant is clamped like the source (finite: validated)
+        f.c0[ch] = from_constant ? (one_minus_constant ? 1.0f - k : k) : c0;
+    }
+}
+BlendForm blend_form(const crh_color_target_state& b) {
+    BlendForm out = {};
+    const crh_blend_component replace = {CRH_BLEND_ONE, CRH_BLEND_ZERO, CRH_BLEND_OP_ADD}; // (factors of `blend: None`; kind 3 takes the source as it is)
+    for (int c = 0; c < 2; ++c) {
+        const crh_blend_component& comp = b.blend_enabled ? (c == 0 ? b.color : b.alpha) : replace;
+        const int ch0 = c == 0 ? 0 : 3, ch1 = c == 0 ? 3 : 4;
+        factor_form(out.src, comp.src_factor, c, b.constant, ch0, ch1);
+        factor_form(out.dst, comp.dst_factor, c, b.constant, ch0, ch1);
+        out.os[c] = comp.operation == CRH_BLEND_OP_REVERSE_SUBTRACT ? -1.0f : 1.0f;
+        out.od[c] = comp.operation == CRH_BLEND_OP_SUBTRACT ? -1.0f : 1.0f;
+        out.kind[c] = !b.blend_enabled ? 3u : (comp.operation == CRH_BLEND_OP_MIN ? 1u : (comp.operation == CRH_BLEND_OP_MAX ? 2u : 0u));
+    }
+    out.write_mask = b.write_mask;
+    return out;
+}
 } // namespace
 
 namespace crh {
@@ -1574,12 +1648,18 @@ const char* crh_last_error(void) { return g_error.c_str(); }
 
 const char* crh_version(void) { return "contrast_hip 0.1 (gfx950)"; }
 
-crh_status crh_renderer_create(const crh_config* config, int device_ordinal, crh_renderer** out) {
+crh_status crh_renderer_create(const crh_config* config, int device_ordinal, crh_renderer** out) { return crh_renderer_create_blended(config, nullptr, device_ordinal, out); }
+crh_status crh_renderer_create_blended(const crh_config* config, const crh_color_target_state* blending, int device_ordinal, crh_renderer** out) {
     if (!config || !out) return CRH_ERR_INVALID_ARGUMENT;
     // renderer.rs:433-435
     if (config->winding_counter_bits == 0 || config->clip_nesting_counter_bits + config->winding_counter_bits > 8) return CRH_ERR_NUMBER_OF_STENCIL_BITS_IS_UNSUPPORTED;
     if (!(config->msaa_sample_count == 1 || config->msaa_sample_count == 4)) return CRH_ERR_UNSUPPORTED;
     if (config->cull_mode > CRH_CULL_BACK || config->depth_compare > CRH_COMPARE_GREATER_EQUAL || config->depth_write_enabled > 1) return CRH_ERR_INVALID_ARGUMENT;
+    const crh_color_target_state blend_state = blending ? *blending : over_state();
+    {
+        const crh_status valid = validate_blending(blend_state); // (before any device is touched, as the checks above)
+        if (valid != CRH_OK) return valid;
+    }
     int count = 0;
     HIP_TRY(hipGetDeviceCount(&count));
     if (count <= 0) {
@@ -1590,6 +1670,9 @@ crh_status crh_renderer_create(const crh_config* config, int device_ordinal, crh
     HIP_TRY(hipSetDevice(device_ordinal));
     crh_renderer* r = new crh_renderer;
     r->config = *config;
+    r->blending = blend_state;
+    r->blend_over = is_over(blend_state);
+    r->blend_form = blend_form(blend_state);
     r->device = device_ordinal;
     r->pipeline = getenv("CRH_NO_PIPELINE") == nullptr;
     // CRH_CU_SPLIT=n (experiment): the tessellation and binning lanes get n of the device's compute units, the raster
@@ -1660,6 +1743,11 @@ void crh_renderer_destroy(crh_renderer* r) {
 crh_status crh_renderer_get_config(const crh_renderer* r, crh_config* out) {
     if (!r || !out) return CRH_ERR_INVALID_ARGUMENT;
     *out = r->config;
+    return CRH_OK;
+}
+crh_status crh_renderer_get_blending(const crh_renderer* r, crh_color_target_state* out) {
+    if (!r || !out) return CRH_ERR_INVALID_ARGUMENT;
+    *out = r->blending;
     return CRH_OK;
 }
 crh_status crh_convert_dynamic_stroke_options(const crh_dynamic_stroke_options* o, crh_dynamic_stroke_descriptor* out) {
@@ -2241,6 +2329,21 @@ crh_status crh_frame_keep_pass_state(crh_frame* f) {
     f->carry = true; // (the planes are allocated and initialised — from the image, if the frame shows one — in front of the next pass: render_impl)
     return CRH_OK;
 }
+crh_status crh_frame_upload(crh_frame* f, const void* rgba8) {
+    if (!f || !f->renderer || !rgba8 || f->format == CRH_FORMAT_RGBA16F || f->slab_ty0 != 0u || f->slab_ty1 != 0xFFFFFFFFu) return CRH_ERR_INVALID_ARGUMENT;
+    crh_renderer* r = f->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    const crh_status st = settle_frame(f); // (a pass drawn again after the fact would draw over the new pixels)
+    if (st != CRH_OK) return st;
+    HIP_TRY(order_after_external(f, r->stream)); // behind the exchange's last read and write of the pixels
+    // on the raster stream: behind the last pass into the frame, in front of the next one
+    HIP_TRY(hipMemcpyAsync(f->rgba8.p, rgba8, f->image_bytes(), hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream)); // (the caller's bytes are copied when the call returns)
+    f->cleared = false; // LoadOp::Load: the next pass reads these pixels
+    f->carry = f->carry_valid = f->carry_recolor = false; // the stencil attachment and the alpha layers start from zero, as after crh_frame_clear
+    f->counts_describe_pixels = false, f->check_pending = false, f->last_scene = nullptr;
+    return CRH_OK;
+}
 crh_status crh_frame_clear_depth(crh_frame* f, float value) {
     if (!f || !f->depth.p || !std::isfinite(value)) return CRH_ERR_INVALID_ARGUMENT;
     crh_renderer* r = f->renderer;
@@ -2616,6 +2719,8 @@ crh_status crh_frame_set_tile_rows(crh_frame* f, uint32_t row_begin, uint32_t ro
     return CRH_OK;
 }
 int crh_internal_renderer_device(crh_renderer* r) { return r ? r->device : -1; }
+// 1: the frame's renderer blends the colour cover with premultiplied "over", the composite of crh_frame_exchange (csrc/comm.hip)
+int crh_internal_frame_blends_over(crh_frame* f) { return (f && f->renderer && f->renderer->blend_over) ? 1 : 0; }
 
 crh_status crh_composite_over(crh_renderer* r, const void* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, void* dst_dev) {
     if (!r || !layers_dev || !dst_dev || n_layers == 0) return CRH_ERR_INVALID_ARGUMENT;

@@ -42,6 +42,7 @@ extern "C" crh_status crh_internal_frame_touched(crh_frame* f, void* stream, int
 extern "C" crh_status crh_internal_frame_slab(crh_frame* f, uint32_t* row_begin, uint32_t* row_end);
 extern "C" crh_status crh_internal_frame_tile_counts(crh_frame* f, const uint32_t** counts, uint32_t* n_tiles, uint32_t* first_tile, uint32_t* end_tile);
 extern "C" int crh_internal_renderer_device(crh_renderer* r);
+extern "C" int crh_internal_frame_blends_over(crh_frame* f);
 
 namespace {
 using crh::set_last_error;
@@ -484,7 +485,11 @@ crh_status phase_pack(crh_comm* c, crh_frame* layer) {
     set_geometry(c, w, h, format);
     if ((st = ensure_buffers(c)) != CRH_OK) return st;
     void* pixels = nullptr;
-    const crh_status layer_status = crh_internal_frame_info(layer, &pixels, &w, &h, &device); // settles the frame: its pixels are final and visible
+    crh_status layer_status = crh_internal_frame_info(layer, &pixels, &w, &h, &device); // settles the frame: its pixels are final and visible
+    if (layer_status == CRH_OK && !crh_internal_frame_blends_over(layer)) { // the composite is "over": a layer drawn with another blend state cannot be composited so
+        layer_status = CRH_ERR_UNSUPPORTED; // (the status travels in the header: the rank takes part, and every rank returns it from phase_plan)
+        set_last_error("crh_frame_exchange: the layer of rank " + std::to_string(c->rank) + " was drawn with a blend state other than premultiplied \"over\"");
+    }
     HIP_TRY(hipSetDevice(c->device));
     begin_phase(c, kPack);
     uint32_t* header = c->host_header.as<uint32_t>(); // (the previous exchange's copy of it was waited for with its bitmaps)

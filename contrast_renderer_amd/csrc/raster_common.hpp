@@ -51,6 +51,11 @@ CRH_D float attachment_unorm8(float v) {
 #endif
     return (float)(uint32_t)(int)(x * 255.0f + 0.5f) * (1.0f / 255.0f);
 }
+// [0, 1], NaN -> 0 (what an Rgba8Unorm attachment's blender does to its inputs and its result; the blend states other than "over")
+CRH_D float clamp_unit(float v) {
+    const float x = v > 0.0f ? v : 0.0f;
+    return x < 1.0f ? x : 1.0f;
+}
 // The target's pixel (gx, gy): the resolved premultiplied colour, clamped to [0, 1] (NaN -> 0) and stored as RGBA8 unorm or — the layers
 // of the multi-GPU exchange — as four binary16 values (round to nearest even; the clamp is the same, so a 16F layer holds what the RGBA8
 // target would have quantised).

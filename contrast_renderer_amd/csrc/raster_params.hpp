@@ -26,6 +26,25 @@ enum RasterVariant : uint32_t { kRasterFill = 1, kRasterEdges = 2, kRasterEdgesL
 // a verified pass measured, k_bin_edges item by item)
 enum BinRoute : uint32_t { kBinTriangles = 1, kBinFlatItems = 2, kBinFlatBatches = 3, kBinItemwise = 4 };
 
+// Configuration::blending of the colour cover (renderer.rs:380-382, :736-754) when it is not premultiplied "over": a kernel argument of its own
+// behind RasterParams, read by k_raster_blend only (api.hip blend_form builds it; a larger RasterParams changed the code of the existing kernels).
+// A crh_color_target_state as the kernel evaluates it, per channel ch (0-2: the `color` component c = 0, 3: the `alpha` component c = 1), with
+// S / D the clamped source / the target's sample, As / Ad their alphas:
+//   factor = min((((c0[ch] + s[c] * S) + sa[c] * As) + d[c] * D) + da[c] * Ad, cap0[c] + cap1[c] * Ad)
+// Every WebGPU factor but SrcAlphaSaturated has at most one term besides c0, with a coefficient of +-1, so the sum rounds once, as 1 - x does
+// (the zero terms add exactly); SrcAlphaSaturated = min(As, 1 - Ad) through the cap, which is +inf for every other factor.
+//   result = kind 0: os[c] * (S * f_src) + od[c] * (D * f_dst) (Add / Subtract / ReverseSubtract), 1: min(S, D), 2: max(S, D), 3: S (blend: None)
+struct BlendFactorForm {
+    float c0[4];
+    float s[2], sa[2], d[2], da[2], cap0[2], cap1[2];
+};
+struct BlendForm {
+    BlendFactorForm src, dst;
+    float os[2], od[2];
+    uint32_t kind[2];
+    uint32_t write_mask; // wgpu::ColorWrites: bit ch set = channel ch is written
+};
+
 constexpr uint32_t kTessStatusWord = 126; // ... the status word of the optimistic tessellation a pass drew (api.hip: crh_scene::optimistic), copied in by the host side
 constexpr uint32_t kExtraTurnsWord = 76; // of RasterParams::overflow: behind the 8 flag words and the 64 cursors of the pair sub-streams
 struct RasterParams {

@@ -5,7 +5,8 @@ All arithmetic runs in libcontrast_hip.so on the GPU; this module only marshals 
 """
 import ctypes as C
 from dataclasses import dataclass
-from enum import IntEnum
+from enum import IntEnum, IntFlag
+from typing import ClassVar, Optional, Tuple
 
 import numpy as np
 
@@ -41,6 +42,93 @@ class Compare(IntEnum):  # wgpu::CompareFunction of Configuration::depth_compare
     GreaterEqual = 7
 
 
+class BlendFactor(IntEnum):  # wgpu::BlendFactor, same order (crh_blend_factor)
+    Zero = 0
+    One = 1
+    Src = 2
+    OneMinusSrc = 3
+    SrcAlpha = 4
+    OneMinusSrcAlpha = 5
+    Dst = 6
+    OneMinusDst = 7
+    DstAlpha = 8
+    OneMinusDstAlpha = 9
+    SrcAlphaSaturated = 10
+    Constant = 11
+    OneMinusConstant = 12
+    Src1 = 13  # 13-16: dual-source factors; the colour cover has one output, so the renderer refuses them (Unsupported)
+    OneMinusSrc1 = 14
+    Src1Alpha = 15
+    OneMinusSrc1Alpha = 16
+
+
+class BlendOperation(IntEnum):  # wgpu::BlendOperation (crh_blend_operation)
+    Add = 0
+    Subtract = 1
+    ReverseSubtract = 2
+    Min = 3
+    Max = 4
+
+
+@dataclass(frozen=True)
+class BlendComponent:  # wgpu::BlendComponent; the default is BlendComponent::REPLACE
+    src_factor: int = BlendFactor.One
+    dst_factor: int = BlendFactor.Zero
+    operation: int = BlendOperation.Add
+    REPLACE: ClassVar["BlendComponent"]
+    OVER: ClassVar["BlendComponent"]
+
+    def to_c(self):
+        return _ffi.BlendComponentC(int(self.src_factor), int(self.dst_factor), int(self.operation))
+
+
+BlendComponent.REPLACE = BlendComponent(BlendFactor.One, BlendFactor.Zero, BlendOperation.Add)
+BlendComponent.OVER = BlendComponent(BlendFactor.One, BlendFactor.OneMinusSrcAlpha, BlendOperation.Add)
+
+
+@dataclass(frozen=True)
+class BlendState:  # wgpu::BlendState
+    color: BlendComponent = BlendComponent.REPLACE
+    alpha: BlendComponent = BlendComponent.REPLACE
+    REPLACE: ClassVar["BlendState"]
+    ALPHA_BLENDING: ClassVar["BlendState"]
+    PREMULTIPLIED_ALPHA_BLENDING: ClassVar["BlendState"]
+
+
+BlendState.REPLACE = BlendState(BlendComponent.REPLACE, BlendComponent.REPLACE)
+BlendState.ALPHA_BLENDING = BlendState(BlendComponent(BlendFactor.SrcAlpha, BlendFactor.OneMinusSrcAlpha, BlendOperation.Add), BlendComponent.OVER)
+BlendState.PREMULTIPLIED_ALPHA_BLENDING = BlendState(BlendComponent.OVER, BlendComponent.OVER)
+
+
+class ColorWrites(IntFlag):  # wgpu::ColorWrites
+    RED = 1
+    GREEN = 2
+    BLUE = 4
+    ALPHA = 8
+    COLOR = 7
+    ALL = 15
+
+
+@dataclass(frozen=True)
+class ColorTargetState:
+    """wgpu::ColorTargetState of the colour cover without the format (renderer.rs:380-382): `blend` None = the source replaces the target.
+    `constant` stands for RenderPass::set_blend_constant, which this library keeps with the renderer."""
+    blend: Optional[BlendState] = None
+    write_mask: int = ColorWrites.ALL
+    constant: Tuple[float, float, float, float] = (0.0, 0.0, 0.0, 0.0)
+
+    def to_c(self):
+        b = self.blend or BlendState.REPLACE
+        return _ffi.ColorTargetStateC(1 if self.blend is not None else 0, b.color.to_c(), b.alpha.to_c(), int(self.write_mask),
+                                      (C.c_float * 4)(*[float(v) for v in self.constant]))
+
+    @staticmethod
+    def from_c(c):
+        comp = lambda x: BlendComponent(BlendFactor(x.src_factor), BlendFactor(x.dst_factor), BlendOperation(x.operation))
+        blend = BlendState(comp(c.color), comp(c.alpha)) if c.blend_enabled else None
+        return ColorTargetState(blend, ColorWrites(c.write_mask), tuple(float(v) for v in c.constant))
+
+
 @dataclass
 class Configuration:  # renderer.rs:380-405 (fields that change results on this path)
     msaa_sample_count: int = 1
@@ -50,6 +138,7 @@ class Configuration:  # renderer.rs:380-405 (fields that change results on this 
     cull_mode: int = Cull.Disabled          # the three depth / cull fields act on the colour cover only (renderer.rs:743-745)
     depth_compare: int = Compare.Always
     depth_write_enabled: bool = False
+    blending: Optional[ColorTargetState] = None  # the colour cover's blend state (renderer.rs:380-382); None = the showcase's premultiplied "over"
 
 
 class Renderer:
@@ -61,13 +150,20 @@ class Renderer:
         c = _ffi.ConfigC(config.msaa_sample_count, config.clip_nesting_counter_bits, config.winding_counter_bits, config.alpha_layer_count,
                          int(config.cull_mode), int(config.depth_compare), 1 if config.depth_write_enabled else 0)
         handle = C.c_void_p()
-        check(self.lib.crh_renderer_create(C.byref(c), device, C.byref(handle)))
+        blending = C.byref(config.blending.to_c()) if config.blending is not None else None
+        check(self.lib.crh_renderer_create_blended(C.byref(c), blending, device, C.byref(handle)))
         self.handle = handle
         self.config = config
         self.device = device
 
     def get_config(self):
         return self.config
+
+    def get_blending(self) -> ColorTargetState:
+        """The colour cover's blend state the renderer was created with (the "over" state when Configuration.blending is None)."""
+        out = _ffi.ColorTargetStateC()
+        check(self.lib.crh_renderer_get_blending(self.handle, C.byref(out)))
+        return ColorTargetState.from_c(out)
 
     def synchronize(self):
         check(self.lib.crh_renderer_synchronize(self.handle))
@@ -143,6 +239,16 @@ class Frame:
         out = np.zeros((self.height, self.width, self.renderer.config.msaa_sample_count), dtype=np.float32)
         check(self.lib.crh_frame_download_depth(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def upload(self, image):
+        """LoadOp::Load of caller content: [height, width, 4] premultiplied RGBA8 replaces the pixels, stencil, alpha layers and pass state are
+        reset as by clear(), depth is left alone; the next pass loads the pixels. An RGBA16F frame, a frame restricted by set_tile_rows() and an
+        image of another size are refused (InvalidArgument)."""
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.shape != (self.height, self.width, 4):
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"an upload takes a ({self.height}, {self.width}, 4) uint8 image, not {image.shape} {image.dtype}")
+        data = np.ascontiguousarray(image)
+        check(self.lib.crh_frame_upload(self.handle, data.ctypes.data))
 
     def download(self):
         """-> [height, width, 4] uint8 (an RGBA8 frame) or float16 (an RGBA16F frame)."""

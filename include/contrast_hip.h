@@ -121,8 +121,10 @@ typedef struct crh_path_batch {
 /* ---- Renderer (renderer.rs:380-435) --------------------------------------------------------------- */
 
 /* Configuration, renderer.rs:380-405. The fields that change results on this path:
- * blending is fixed to premultiplied "over" (One, OneMinusSrcAlpha — examples/showcase/main.rs:32-43), the depth attachment is
- * f32 per sample (depth_stencil_format is a wgpu detail), color_attachment_in_stencil_pass has no meaning in a compute rasterizer.
+ * `blending` (the colour cover's wgpu::ColorTargetState, renderer.rs:380-382, :736-754) is not a member of crh_config: it is given to
+ * crh_renderer_create_blended below (crh_renderer_create = premultiplied "over", One / OneMinusSrcAlpha, examples/showcase/main.rs:32-43);
+ * the depth attachment is f32 per sample (depth_stencil_format is a wgpu detail), color_attachment_in_stencil_pass has no meaning in a
+ * compute rasterizer.
  * The three depth / cull fields act on the colour cover only, as in the reference (renderer.rs:743-745: every other pipeline is
  * built with cull None, CompareFunction::Always and no depth write). Zero-initialised = no culling, Always, no write. */
 typedef enum crh_cull { CRH_CULL_NONE = 0, CRH_CULL_FRONT = 1, CRH_CULL_BACK = 2 } crh_cull; /* Option<wgpu::Face>; front = counter-clockwise on screen (renderer.rs:477) */
@@ -166,6 +168,62 @@ crh_status crh_renderer_create(const crh_config* config, int device_ordinal, crh
 void crh_renderer_destroy(crh_renderer* renderer);
 /* Renderer::get_config, renderer.rs:887 */
 crh_status crh_renderer_get_config(const crh_renderer* renderer, crh_config* out);
+
+/* Configuration::blending, renderer.rs:380-382: the blend state of the Color operation's pipeline (color_cover, renderer.rs:736-754).
+ * Stencil, Clip / UnClip and the alpha-context covers keep their fixed states (renderer.rs:761-861), as in the reference.
+ * crh_blend_factor has the order of wgpu::BlendFactor, crh_blend_operation that of wgpu::BlendOperation. */
+typedef enum crh_blend_factor {
+    CRH_BLEND_ZERO = 0,
+    CRH_BLEND_ONE = 1,
+    CRH_BLEND_SRC = 2,
+    CRH_BLEND_ONE_MINUS_SRC = 3,
+    CRH_BLEND_SRC_ALPHA = 4,
+    CRH_BLEND_ONE_MINUS_SRC_ALPHA = 5,
+    CRH_BLEND_DST = 6,
+    CRH_BLEND_ONE_MINUS_DST = 7,
+    CRH_BLEND_DST_ALPHA = 8,
+    CRH_BLEND_ONE_MINUS_DST_ALPHA = 9,
+    CRH_BLEND_SRC_ALPHA_SATURATED = 10, /* min(As, 1 - Ad) for rgb, 1 for alpha */
+    CRH_BLEND_CONSTANT = 11,
+    CRH_BLEND_ONE_MINUS_CONSTANT = 12,
+    CRH_BLEND_SRC1 = 13, /* 13-16: the dual-source factors; the colour cover has one output: CRH_ERR_UNSUPPORTED */
+    CRH_BLEND_ONE_MINUS_SRC1 = 14,
+    CRH_BLEND_SRC1_ALPHA = 15,
+    CRH_BLEND_ONE_MINUS_SRC1_ALPHA = 16
+} crh_blend_factor;
+typedef enum crh_blend_operation {
+    CRH_BLEND_OP_ADD = 0,
+    CRH_BLEND_OP_SUBTRACT = 1,          /* src * src_factor - dst * dst_factor */
+    CRH_BLEND_OP_REVERSE_SUBTRACT = 2,  /* dst * dst_factor - src * src_factor */
+    CRH_BLEND_OP_MIN = 3,               /* min(src, dst): both factors must be One (WebGPU validation) */
+    CRH_BLEND_OP_MAX = 4
+} crh_blend_operation;
+typedef struct crh_blend_component { /* wgpu::BlendComponent */
+    uint32_t src_factor; /* crh_blend_factor */
+    uint32_t dst_factor; /* crh_blend_factor */
+    uint32_t operation;  /* crh_blend_operation */
+} crh_blend_component;
+enum { CRH_COLOR_WRITE_RED = 1, CRH_COLOR_WRITE_GREEN = 2, CRH_COLOR_WRITE_BLUE = 4, CRH_COLOR_WRITE_ALPHA = 8, CRH_COLOR_WRITE_ALL = 15 }; /* wgpu::ColorWrites */
+typedef struct crh_color_target_state { /* wgpu::ColorTargetState without the format */
+    uint32_t blend_enabled;    /* 0 = `blend: None`: the source replaces the target */
+    crh_blend_component color; /* rgb channels */
+    crh_blend_component alpha; /* alpha channel */
+    uint32_t write_mask;       /* CRH_COLOR_WRITE_*: channels outside the mask keep the target's value */
+    float constant[4];         /* RenderPass::set_blend_constant — kept with the renderer here (a deviation: wgpu sets it per pass) */
+} crh_color_target_state;
+/* Renderer::new with Configuration::blending. `blending` NULL = the showcase's premultiplied "over" (blend enabled, both components
+ * One / OneMinusSrcAlpha / Add, write mask 15), exactly crh_renderer_create. Validated before any device is touched: a factor > 16, an
+ * operation > 4, a write mask > 15, a non-finite constant, or Min / Max with a factor other than One -> CRH_ERR_INVALID_ARGUMENT; a
+ * dual-source factor -> CRH_ERR_UNSUPPORTED.
+ * Per sample of the Color operation, where today's stencil and depth tests let it blend: the source is color_cover's premultiplied
+ * (rgb * a, a) (shaders.wgsl:304-309); factors follow WebGPU's table. A state other than "over" treats the target as an Rgba8Unorm
+ * attachment on every frame format: source and constant are clamped to [0, 1] (NaN -> 0) before the blend, the result after it, and a
+ * CRH_FORMAT_RGBA8_ATTACHMENT frame rounds every written value to 8 bits. Products and the operation round separately (no fused
+ * multiply-add). Such passes are drawn by the general (triangle) formulation, and crh_frame_exchange refuses their layers
+ * (CRH_ERR_UNSUPPORTED on every rank: its composite is "over"); crh_frame_gather_slabs works with any state. */
+crh_status crh_renderer_create_blended(const crh_config* config, const crh_color_target_state* blending, int device_ordinal, crh_renderer** out);
+/* the state the renderer was created with (the "over" state for crh_renderer_create) */
+crh_status crh_renderer_get_blending(const crh_renderer* renderer, crh_color_target_state* out);
 
 /* convert_dynamic_stroke_options, renderer.rs:29-60 (host-side, pure) */
 crh_status crh_convert_dynamic_stroke_options(const crh_dynamic_stroke_options* options, crh_dynamic_stroke_descriptor* out);
@@ -275,6 +333,12 @@ typedef struct crh_draw {
 crh_status crh_scene_render_draws(crh_scene* scene, crh_frame* frame, const float* transforms, const float* colors, uint32_t n_instances,
                                   const crh_draw* draws, uint32_t n_draws);
 
+/* LoadOp::Load of caller content: `rgba8` = width*height*4 bytes of premultiplied RGBA8, row 0 = top, replace the frame's pixels; every
+ * sample of a pixel starts from its value. The stencil attachment, the saved alpha layers and the pass state are reset as by
+ * crh_frame_clear, the depth attachment is left alone. The frame is NOT cleared afterwards: the next pass loads these pixels. Ordered
+ * behind the last pass into the frame; the host bytes are copied before the call returns. CRH_ERR_INVALID_ARGUMENT for a
+ * CRH_FORMAT_RGBA16F frame and for a frame restricted by crh_frame_set_tile_rows. */
+crh_status crh_frame_upload(crh_frame* frame, const void* rgba8);
 /* MSAA resolve (box average, examples/showcase/main.rs:215) + copy to host, `rgba8` = width*height*4 bytes, row 0 = top. */
 crh_status crh_frame_download(crh_frame* frame, void* rgba8);
 /* The same for a CRH_FORMAT_RGBA16F frame: width*height*8 bytes (four IEEE binary16 per pixel). Each entry point refuses the other format. */

@@ -401,12 +401,57 @@ class PathBatch {
 // ---------------------------------------------------------------------------------------------- renderer.rs
 enum class RenderOperation : uint32_t { Stencil = 0, Clip = 1, UnClip = 2, Color = 3, SaveAlphaContext = 4, ScaleAlphaContext = 5, RestoreAlphaContext = 6 }; // :145-160
 
+// Configuration::blending (renderer.rs:380-382): wgpu's blend types, as the C ABI's crh_color_target_state carries them
+enum class BlendFactor : uint32_t { // wgpu::BlendFactor, same order; 13-16 (dual source) are refused: the colour cover has one output
+    Zero = 0, One = 1, Src = 2, OneMinusSrc = 3, SrcAlpha = 4, OneMinusSrcAlpha = 5, Dst = 6, OneMinusDst = 7, DstAlpha = 8, OneMinusDstAlpha = 9,
+    SrcAlphaSaturated = 10, Constant = 11, OneMinusConstant = 12, Src1 = 13, OneMinusSrc1 = 14, Src1Alpha = 15, OneMinusSrc1Alpha = 16
+};
+enum class BlendOperation : uint32_t { Add = 0, Subtract = 1, ReverseSubtract = 2, Min = 3, Max = 4 }; // wgpu::BlendOperation
+struct BlendComponent { // wgpu::BlendComponent (the default is REPLACE)
+    BlendFactor src_factor = BlendFactor::One;
+    BlendFactor dst_factor = BlendFactor::Zero;
+    BlendOperation operation = BlendOperation::Add;
+    static const BlendComponent REPLACE, OVER;
+    crh_blend_component to_c() const { return crh_blend_component{(uint32_t)src_factor, (uint32_t)dst_factor, (uint32_t)operation}; }
+    static BlendComponent from_c(const crh_blend_component& c) { return BlendComponent{(BlendFactor)c.src_factor, (BlendFactor)c.dst_factor, (BlendOperation)c.operation}; }
+};
+inline const BlendComponent BlendComponent::REPLACE{BlendFactor::One, BlendFactor::Zero, BlendOperation::Add};
+inline const BlendComponent BlendComponent::OVER{BlendFactor::One, BlendFactor::OneMinusSrcAlpha, BlendOperation::Add};
+struct BlendState { // wgpu::BlendState
+    BlendComponent color, alpha;
+    static const BlendState REPLACE, ALPHA_BLENDING, PREMULTIPLIED_ALPHA_BLENDING;
+};
+inline const BlendState BlendState::REPLACE{BlendComponent::REPLACE, BlendComponent::REPLACE};
+inline const BlendState BlendState::ALPHA_BLENDING{BlendComponent{BlendFactor::SrcAlpha, BlendFactor::OneMinusSrcAlpha, BlendOperation::Add}, BlendComponent::OVER};
+inline const BlendState BlendState::PREMULTIPLIED_ALPHA_BLENDING{BlendComponent::OVER, BlendComponent::OVER};
+namespace ColorWrites { // wgpu::ColorWrites
+constexpr uint32_t RED = CRH_COLOR_WRITE_RED, GREEN = CRH_COLOR_WRITE_GREEN, BLUE = CRH_COLOR_WRITE_BLUE, ALPHA = CRH_COLOR_WRITE_ALPHA, COLOR = 7, ALL = CRH_COLOR_WRITE_ALL;
+}
+// wgpu::ColorTargetState without the format; `constant` stands for RenderPass::set_blend_constant, kept with the renderer here
+struct ColorTargetState {
+    std::optional<BlendState> blend = std::nullopt; // None: the source replaces the target
+    uint32_t write_mask = ColorWrites::ALL;
+    std::array<float, 4> constant = {0.0f, 0.0f, 0.0f, 0.0f};
+    crh_color_target_state to_c() const {
+        const BlendState b = blend.value_or(BlendState::REPLACE);
+        return crh_color_target_state{blend ? 1u : 0u, b.color.to_c(), b.alpha.to_c(), write_mask, {constant[0], constant[1], constant[2], constant[3]}};
+    }
+    static ColorTargetState from_c(const crh_color_target_state& c) {
+        ColorTargetState out;
+        if (c.blend_enabled) out.blend = BlendState{BlendComponent::from_c(c.color), BlendComponent::from_c(c.alpha)};
+        out.write_mask = c.write_mask;
+        for (int i = 0; i < 4; ++i) out.constant[(size_t)i] = c.constant[i];
+        return out;
+    }
+};
+
 struct Configuration { // renderer.rs:380-405, the fields that change results on this path
     uint32_t msaa_sample_count = 1, clip_nesting_counter_bits = 4, winding_counter_bits = 4, alpha_layer_count = 0;
     // of the colour cover only, as in the reference (renderer.rs:743-745)
     crh_cull cull_mode = CRH_CULL_NONE;              // Option<wgpu::Face>
     crh_compare depth_compare = CRH_COMPARE_ALWAYS;  // wgpu::CompareFunction
     bool depth_write_enabled = false;
+    std::optional<ColorTargetState> blending = std::nullopt; // the colour cover's blend state (renderer.rs:380-382); nullopt = the showcase's premultiplied "over"
 };
 
 class Renderer { // renderer.rs:408-435
@@ -414,7 +459,8 @@ class Renderer { // renderer.rs:408-435
     Renderer(int device, const Configuration& config) { // Renderer::new(&device, config) -> Result<Renderer, Error>
         const crh_config c = {config.msaa_sample_count, config.clip_nesting_counter_bits, config.winding_counter_bits, config.alpha_layer_count,
                               (uint32_t)config.cull_mode,  (uint32_t)config.depth_compare,      config.depth_write_enabled ? 1u : 0u};
-        check(crh_renderer_create(&c, device, &handle_));
+        const std::optional<crh_color_target_state> blending = config.blending ? std::optional<crh_color_target_state>(config.blending->to_c()) : std::nullopt;
+        check(crh_renderer_create_blended(&c, blending ? &*blending : nullptr, device, &handle_));
         samples_ = config.msaa_sample_count;
     }
     ~Renderer() { crh_renderer_destroy(handle_); }
@@ -424,7 +470,12 @@ class Renderer { // renderer.rs:408-435
         crh_config c;
         check(crh_renderer_get_config(handle_, &c));
         return Configuration{c.msaa_sample_count, c.clip_nesting_counter_bits, c.winding_counter_bits, c.alpha_layer_count,
-                             (crh_cull)c.cull_mode, (crh_compare)c.depth_compare, c.depth_write_enabled != 0};
+                             (crh_cull)c.cull_mode, (crh_compare)c.depth_compare, c.depth_write_enabled != 0, get_blending()};
+    }
+    ColorTargetState get_blending() const { // the state the renderer was created with (the "over" state for a Configuration without one)
+        crh_color_target_state b;
+        check(crh_renderer_get_blending(handle_, &b));
+        return ColorTargetState::from_c(b);
     }
     void synchronize() { check(crh_renderer_synchronize(handle_)); }
     crh_renderer* raw() const { return handle_; }
@@ -460,6 +511,11 @@ class Frame {
         std::vector<float> out((size_t)width_ * height_ * samples_);
         check(crh_frame_download_depth(handle_, out.data()));
         return out;
+    }
+    // LoadOp::Load of caller content: premultiplied RGBA8, row 0 = top; stencil, alpha layers and pass state reset as by clear(), depth kept
+    void upload(const std::vector<uint8_t>& rgba8) {
+        if (rgba8.size() != (size_t)width_ * height_ * 4) throw Error(CRH_ERR_INVALID_ARGUMENT);
+        check(crh_frame_upload(handle_, rgba8.data()));
     }
     std::vector<uint8_t> download() {                 // MSAA resolve + read back: premultiplied RGBA8, row 0 = top
         std::vector<uint8_t> out((size_t)width_ * height_ * 4);

@@ -351,8 +351,91 @@ pub enum CompareFunction {
     GreaterEqual = 7,
 }
 
-/// renderer.rs:380-405. `blending` is fixed to premultiplied "over" (examples/showcase/main.rs:32-43), `depth_stencil_format` and
-/// `color_attachment_in_stencil_pass` are wgpu details without meaning for a compute rasterizer.
+/// `wgpu::BlendFactor`, same order (= crh_blend_factor); `Renderer::new` refuses the dual-source factors (status 8, a panic: no reference variant)
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum BlendFactor {
+    Zero = 0,
+    One = 1,
+    Src = 2,
+    OneMinusSrc = 3,
+    SrcAlpha = 4,
+    OneMinusSrcAlpha = 5,
+    Dst = 6,
+    OneMinusDst = 7,
+    DstAlpha = 8,
+    OneMinusDstAlpha = 9,
+    SrcAlphaSaturated = 10,
+    Constant = 11,
+    OneMinusConstant = 12,
+    Src1 = 13,
+    OneMinusSrc1 = 14,
+    Src1Alpha = 15,
+    OneMinusSrc1Alpha = 16,
+}
+/// `wgpu::BlendOperation` (= crh_blend_operation)
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum BlendOperation {
+    Add = 0,
+    Subtract = 1,
+    ReverseSubtract = 2,
+    Min = 3,
+    Max = 4,
+}
+/// `wgpu::BlendComponent`
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub struct BlendComponent {
+    pub src_factor: BlendFactor,
+    pub dst_factor: BlendFactor,
+    pub operation: BlendOperation,
+}
+impl BlendComponent {
+    pub const REPLACE: Self = Self { src_factor: BlendFactor::One, dst_factor: BlendFactor::Zero, operation: BlendOperation::Add };
+    pub const OVER: Self = Self { src_factor: BlendFactor::One, dst_factor: BlendFactor::OneMinusSrcAlpha, operation: BlendOperation::Add };
+    fn raw(&self) -> ffi::crh_blend_component {
+        ffi::crh_blend_component { src_factor: self.src_factor as u32, dst_factor: self.dst_factor as u32, operation: self.operation as u32 }
+    }
+}
+/// `wgpu::BlendState`
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub struct BlendState {
+    pub color: BlendComponent,
+    pub alpha: BlendComponent,
+}
+impl BlendState {
+    pub const REPLACE: Self = Self { color: BlendComponent::REPLACE, alpha: BlendComponent::REPLACE };
+    pub const ALPHA_BLENDING: Self = Self {
+        color: BlendComponent { src_factor: BlendFactor::SrcAlpha, dst_factor: BlendFactor::OneMinusSrcAlpha, operation: BlendOperation::Add },
+        alpha: BlendComponent::OVER,
+    };
+    pub const PREMULTIPLIED_ALPHA_BLENDING: Self = Self { color: BlendComponent::OVER, alpha: BlendComponent::OVER };
+}
+/// `wgpu::ColorWrites` bits
+pub struct ColorWrites;
+impl ColorWrites {
+    pub const RED: u32 = 1;
+    pub const GREEN: u32 = 2;
+    pub const BLUE: u32 = 4;
+    pub const ALPHA: u32 = 8;
+    pub const COLOR: u32 = 7;
+    pub const ALL: u32 = 15;
+}
+/// `wgpu::ColorTargetState` without the format (`blend: None` = replace). `constant` stands for `RenderPass::set_blend_constant`, which this
+/// library keeps with the renderer.
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub struct ColorTargetState {
+    pub blend: Option<BlendState>,
+    pub write_mask: u32,
+    pub constant: [f32; 4],
+}
+impl ColorTargetState {
+    fn raw(&self) -> ffi::crh_color_target_state {
+        let b = self.blend.unwrap_or(BlendState::REPLACE);
+        ffi::crh_color_target_state { blend_enabled: self.blend.is_some() as u32, color: b.color.raw(), alpha: b.alpha.raw(), write_mask: self.write_mask, constant: self.constant }
+    }
+}
+
+/// renderer.rs:380-405. `blending` = the colour cover's blend state (None: the premultiplied "over" of examples/showcase/main.rs:32-43);
+/// `depth_stencil_format` and `color_attachment_in_stencil_pass` are wgpu details without meaning for a compute rasterizer.
 #[derive(Clone, Copy, Debug)]
 pub struct Configuration {
     pub cull_mode: Option<Face>,
@@ -362,11 +445,21 @@ pub struct Configuration {
     pub clip_nesting_counter_bits: usize,
     pub winding_counter_bits: usize,
     pub alpha_layer_count: usize,
+    pub blending: Option<ColorTargetState>,
 }
 impl Default for Configuration {
     /// examples/showcase/main.rs:45-56
     fn default() -> Self {
-        Self { cull_mode: None, depth_compare: CompareFunction::Always, depth_write_enabled: false, msaa_sample_count: 4, clip_nesting_counter_bits: 4, winding_counter_bits: 4, alpha_layer_count: 0 }
+        Self {
+            cull_mode: None,
+            depth_compare: CompareFunction::Always,
+            depth_write_enabled: false,
+            msaa_sample_count: 4,
+            clip_nesting_counter_bits: 4,
+            winding_counter_bits: 4,
+            alpha_layer_count: 0,
+            blending: None,
+        }
     }
 }
 
@@ -388,7 +481,9 @@ impl Renderer {
             depth_write_enabled: config.depth_write_enabled as u32,
         };
         let mut raw = ptr::null_mut();
-        status(unsafe { ffi::crh_renderer_create(&c, device, &mut raw) })?;
+        let blending = config.blending.map(|b| b.raw());
+        let blending_ptr = blending.as_ref().map_or(ptr::null(), |b| b as *const ffi::crh_color_target_state);
+        status(unsafe { ffi::crh_renderer_create_blended(&c, blending_ptr, device, &mut raw) })?;
         Ok(Self { raw, config })
     }
     /// renderer.rs:887
@@ -432,6 +527,11 @@ impl Frame {
     pub fn upload_depth(&mut self, depth: &[f32]) {
         assert_eq!(depth.len(), (self.width * self.height) as usize);
         status(unsafe { ffi::crh_frame_upload_depth(self.raw, depth.as_ptr()) }).unwrap()
+    }
+    /// `LoadOp::Load` of caller content: premultiplied RGBA8, row 0 = top. Stencil, alpha layers and pass state are reset as by `clear`, depth is kept.
+    pub fn upload(&mut self, rgba8: &[u8]) {
+        assert_eq!(rgba8.len(), (self.width * self.height * 4) as usize);
+        status(unsafe { ffi::crh_frame_upload(self.raw, rgba8.as_ptr() as *const _) }).unwrap()
     }
     /// Premultiplied RGBA8, row 0 = top
     pub fn download(&mut self) -> Vec<u8> {
