@@ -300,6 +300,7 @@ def load_library():
         "crh_renderer_enable_timing": (C.c_int, [V, C.c_int]),
         "crh_renderer_kernel_times": (C.c_int, [V, C.POINTER(KernelTimeC), C.c_uint32, C.POINTER(C.c_uint32)]),
         "crh_selftest_fmath": (C.c_int, [V, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]),
+        "crh_selftest_srgb": (C.c_int, [V, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_float)]),
         "crh_font_create": (C.c_int, [V, C.c_size_t, C.POINTER(V)]),
         "crh_font_destroy": (None, [V]),
         "crh_font_get_metrics": (C.c_int, [V, C.POINTER(FontMetricsC)]),

@@ -42,6 +42,7 @@ void flat_batch_limits(uint32_t n_items, uint32_t limits[4]);
 void launch_tile_bases(const uint32_t* tile_count, uint32_t* caps, uint32_t* tile_base, uint32_t* scratch, uint32_t n_tiles, uint32_t tiles_x, uint32_t radius, hipStream_t stream);
 uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke); // -> RasterVariant
 void launch_fmath(int fn, const float* a, const float* b, float* out, uint64_t n, hipStream_t stream);
+void launch_selftest_srgb(const float* x, uint8_t* codes, uint64_t n, float* decoded, hipStream_t stream); // raster.hip
 } // namespace crh
 
 using namespace crh;
@@ -2242,7 +2243,7 @@ crh_status crh_frame_format(const crh_frame* f, uint32_t* format) {
 }
 crh_status crh_frame_create_format(crh_renderer* r, uint32_t width, uint32_t height, uint32_t format, crh_frame** out) {
     // pixel boxes are 16-bit (0xFFFF = nothing to draw), so a frame is at most 65 535 pixels wide and high
-    if (!r || !out || width == 0 || height == 0 || width > 65535u || height > 65535u || format > CRH_FORMAT_RGBA8_ATTACHMENT) return CRH_ERR_INVALID_ARGUMENT;
+    if (!r || !out || width == 0 || height == 0 || width > 65535u || height > 65535u || format > CRH_FORMAT_BGRA8_SRGB_ATTACHMENT) return CRH_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(r->device));
     crh_frame* f = new crh_frame;
     f->renderer = r;
@@ -2571,7 +2572,7 @@ crh_status crh_scene_render(crh_scene* sc, crh_frame* f, const float* transforms
 }
 namespace {
 crh_status download_pixels(crh_frame* f, void* out, uint32_t format) {
-    if (!f || !out || (f->format == CRH_FORMAT_RGBA16F) != (format == CRH_FORMAT_RGBA16F)) return CRH_ERR_INVALID_ARGUMENT; // (both RGBA8 formats store RGBA8)
+    if (!f || !out || (f->format == CRH_FORMAT_RGBA16F) != (format == CRH_FORMAT_RGBA16F)) return CRH_ERR_INVALID_ARGUMENT; // (every other format stores 4 bytes)
     crh_renderer* r = f->renderer;
     HIP_TRY(hipSetDevice(r->device));
     crh_status st = settle_frame(f);
@@ -2766,6 +2767,25 @@ crh_status crh_selftest_fmath(crh_renderer* r, int fn, const float* a, const flo
     da.release();
     db.release();
     dout.release();
+    return rc;
+}
+
+crh_status crh_selftest_srgb(crh_renderer* r, const float* x, uint8_t* codes, uint64_t n, float* decoded) {
+    if (!r || (n && (!x || !codes)) || !decoded) return CRH_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(r->device));
+    DevBuf dx, dcodes, ddecoded;
+    crh_status rc = CRH_OK;
+    if (!hip_ok(dx.ensure(n * 4 + 4), "hipMalloc") || !hip_ok(dcodes.ensure(n + 4), "hipMalloc") || !hip_ok(ddecoded.ensure(256 * 4), "hipMalloc")) rc = CRH_ERR_HIP;
+    if (rc == CRH_OK && n && !hip_ok(hipMemcpyAsync(dx.p, x, n * 4, hipMemcpyHostToDevice, r->stream), "memcpy")) rc = CRH_ERR_HIP;
+    if (rc == CRH_OK) {
+        launch_selftest_srgb(dx.as<float>(), dcodes.as<uint8_t>(), n, ddecoded.as<float>(), r->stream);
+        if ((n && !hip_ok(hipMemcpyAsync(codes, dcodes.p, n, hipMemcpyDeviceToHost, r->stream), "memcpy")) ||
+            !hip_ok(hipMemcpyAsync(decoded, ddecoded.p, 256 * 4, hipMemcpyDeviceToHost, r->stream), "memcpy") || !hip_ok(r->sync(), "sync"))
+            rc = CRH_ERR_HIP;
+    }
+    dx.release();
+    dcodes.release();
+    ddecoded.release();
     return rc;
 }
 

@@ -473,10 +473,20 @@ enum Phase { kPack = 0, kPlan, kAllToAll, kComposite, kGather, kUnpack };
 void begin_phase(crh_comm* c, Phase k) { (void)hipEventRecord(c->phase_begin[k], c->stream); }
 void end_phase(crh_comm* c, Phase k) { (void)hipEventRecord(c->phase_end[k], c->stream); }
 
+// The bytes a frame format stores: 0 RGBA unorm8 (CRH_FORMAT_RGBA8, _ATTACHMENT), 1 BGRA, 2 RGBA sRGB, 3 BGRA sRGB (X and X_ATTACHMENT store
+// the same encoding); slab gathers move bytes, so layers and result must agree on it
+uint32_t byte_encoding(uint32_t format) {
+    switch (format) {
+        case CRH_FORMAT_BGRA8: case CRH_FORMAT_BGRA8_ATTACHMENT: return 1u;
+        case CRH_FORMAT_RGBA8_SRGB: case CRH_FORMAT_RGBA8_SRGB_ATTACHMENT: return 2u;
+        case CRH_FORMAT_BGRA8_SRGB: case CRH_FORMAT_BGRA8_SRGB_ATTACHMENT: return 3u;
+        default: return 0u;
+    }
+}
 // phase 1: [header | occupancy bitmap], its prefix sums and the packed tiles of this rank's layer (all on the communicator's stream).
 // A layer that cannot be read (its pass failed) leaves an empty bitmap and its status in the header: the rank still takes part in the
 // collectives, and every rank learns of it from the gathered headers.
-crh_status phase_pack(crh_comm* c, crh_frame* layer) {
+crh_status phase_pack(crh_comm* c, crh_frame* layer, crh_frame* result) {
     uint32_t w = 0, h = 0, format = 0;
     int device = 0;
     crh_status st = crh_internal_frame_geometry(layer, &w, &h, &format, &device);
@@ -489,6 +499,13 @@ crh_status phase_pack(crh_comm* c, crh_frame* layer) {
     if (layer_status == CRH_OK && !crh_internal_frame_blends_over(layer)) { // the composite is "over": a layer drawn with another blend state cannot be composited so
         layer_status = CRH_ERR_UNSUPPORTED; // (the status travels in the header: the rank takes part, and every rank returns it from phase_plan)
         set_last_error("crh_frame_exchange: the layer of rank " + std::to_string(c->rank) + " was drawn with a blend state other than premultiplied \"over\"");
+    }
+    uint32_t rw = 0, rh = 0, rformat = 0;
+    int rdevice = 0;
+    if (layer_status == CRH_OK && (format > CRH_FORMAT_RGBA8_ATTACHMENT || (result && crh_internal_frame_geometry(result, &rw, &rh, &rformat, &rdevice) == CRH_OK &&
+                                                                             rformat > CRH_FORMAT_RGBA8_ATTACHMENT))) {
+        layer_status = CRH_ERR_UNSUPPORTED; // the composite is unorm RGBA "over": BGRA / sRGB layers and results are not composited (every rank returns it, as above)
+        set_last_error("crh_frame_exchange: rank " + std::to_string(c->rank) + " exchanges a BGRA or sRGB frame");
     }
     HIP_TRY(hipSetDevice(c->device));
     begin_phase(c, kPack);
@@ -783,7 +800,7 @@ crh_status crh_frame_exchange(crh_comm* c, crh_frame* layer, crh_frame* result) 
     if (!c || !layer || !c->nccl || (c->rank == 0) != (result != nullptr)) return CRH_ERR_INVALID_ARGUMENT;
     Rccl* api = rccl();
     c->timed = false;
-    crh_status st = phase_pack(c, layer);
+    crh_status st = phase_pack(c, layer, result);
     if (st != CRH_OK) return st; // (only argument errors end here: a layer that cannot be read still takes part)
     // Sizes of the collectives follow from the frame geometry, which therefore has to be the same on every rank BEFORE a count is derived
     // from it. Two rules keep the ranks' collectives matched whatever one of them does to its layer:
@@ -892,6 +909,10 @@ crh_status crh_frame_gather_slabs(crh_comm* c, crh_frame* layer, crh_frame* resu
     if (mine == CRH_OK && result) {
         mine = crh_internal_frame_geometry(result, &rw, &rh, &rformat, &device);
         if (mine == CRH_OK && (rw != w || rh != h || rformat == CRH_FORMAT_RGBA16F || device != c->device)) mine = CRH_ERR_INVALID_ARGUMENT;
+        if (mine == CRH_OK && byte_encoding(rformat) != byte_encoding(format)) {
+            set_last_error("crh_frame_gather_slabs: the result frame has another byte encoding than rank 0's layer");
+            mine = CRH_ERR_INVALID_ARGUMENT;
+        }
     }
     HIP_TRY(hipSetDevice(c->device));
     void *pixels = nullptr, *out = nullptr;
@@ -913,7 +934,7 @@ crh_status crh_frame_gather_slabs(crh_comm* c, crh_frame* layer, crh_frame* resu
     HIP_TRY(c->headers_all.ensure((size_t)c->world * kHeaderWords * 4));
     HIP_TRY(c->host_headers.ensure((size_t)c->world * kHeaderWords * 4));
     uint32_t* header = c->host_header.as<uint32_t>();
-    header[0] = kMagic, header[1] = w, header[2] = h, header[3] = (uint32_t)mine;
+    header[0] = kMagic, header[1] = w, header[2] = h | (byte_encoding(format) << 24), header[3] = (uint32_t)mine; // (h < 65536)
     HIP_TRY(hipMemcpyAsync(c->bitmap.p, header, kHeaderWords * 4, hipMemcpyHostToDevice, c->stream));
     mark_all_phases(c);
     NCCL_TRY(api->AllGather(c->bitmap.p, c->headers_all.p, kHeaderWords * 4, ncclUint8, c->nccl, c->stream));
@@ -927,8 +948,12 @@ crh_status crh_frame_gather_slabs(crh_comm* c, crh_frame* layer, crh_frame* resu
             set_last_error("crh_frame_gather_slabs: rank " + std::to_string(k) + " cannot take part (status " + std::to_string(hd[3]) + ")");
             return (crh_status)hd[3]; // on every rank
         }
-        if (hd[0] != kMagic || hd[1] != w || hd[2] != h) {
+        if (hd[0] != kMagic || hd[1] != w || (hd[2] & 0xFFFFFFu) != h) {
             set_last_error("crh_frame_gather_slabs: rank " + std::to_string(k) + " gathers a layer of another size");
+            return CRH_ERR_INVALID_ARGUMENT; // on every rank
+        }
+        if ((hd[2] >> 24) != byte_encoding(format)) {
+            set_last_error("crh_frame_gather_slabs: rank " + std::to_string(k) + " gathers a layer of another byte encoding");
             return CRH_ERR_INVALID_ARGUMENT; // on every rank
         }
     }
@@ -975,7 +1000,7 @@ crh_status crh_comm_local_gather_slabs(crh_comm* rank0, crh_frame* const* layers
         if (!g[k] || !layers[k]) return CRH_ERR_INVALID_ARGUMENT;
         uint32_t w = 0, h = 0, format = 0;
         if ((st = crh_internal_frame_geometry(layers[k], &w, &h, &format, &device)) != CRH_OK) return st;
-        if (w != rw || h != rh || format == CRH_FORMAT_RGBA16F) {
+        if (w != rw || h != rh || format == CRH_FORMAT_RGBA16F || byte_encoding(format) != byte_encoding(rformat)) {
             set_last_error("crh_comm_local_gather_slabs: rank " + std::to_string(k) + " gathers a layer of another size or format");
             return CRH_ERR_INVALID_ARGUMENT;
         }
@@ -1020,7 +1045,7 @@ crh_status crh_comm_local_exchange(crh_comm* rank0, crh_frame* const* layers, cr
     for (uint32_t k = 0; k < world; ++k) {
         g[k]->timed = false;
         if (serial && k) HIP_TRY(hipStreamSynchronize(g[k - 1]->stream));
-        if ((st = phase_pack(g[k], layers[k])) != CRH_OK) return st;
+        if ((st = phase_pack(g[k], layers[k], k == 0 ? result : nullptr)) != CRH_OK) return st;
         HIP_TRY(hipEventRecord(g[k]->packed, g[k]->stream));
     }
     CRH_SERIAL_POINT(world - 1);

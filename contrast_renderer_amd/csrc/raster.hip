@@ -555,14 +555,14 @@ constexpr int kMaxAlphaLayers = 4;
 //                walk reserves) are compiled out: fewer VGPRs, more waves per SIMD.
 //   BLEND == true (with OPS only): the colour cover blends with the renderer's Configuration::blending (`bf`) instead of premultiplied
 //                "over": the kernel k_raster_blend. Both kernels include the one body, csrc/raster_tile_body.inc.
-template <int S, int ROWS, bool OPS, bool STROKES>
+template <int S, int ROWS, bool OPS, bool STROKES, bool XFMT = false> // XFMT: the frame formats 3-8 (raster_common.hpp store_px)
 __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu((OPS || STROKES || S == 4) ? 1 : CRH_TILE_WAVES))) void k_raster_tile(SceneDev s, RasterParams r) {
     constexpr bool BLEND = false;
     const BlendForm bf = {}; // (not read: the blend block is compiled out)
 #include "raster_tile_body.inc"
 }
 // The general variant with the renderer's blend state in place of "over" (Configuration::blending; msaa 1: ROWS 4, msaa 4: ROWS 1)
-template <int S, bool STROKES>
+template <int S, bool STROKES, bool XFMT = false>
 __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_blend(SceneDev s, RasterParams r, BlendForm bf) {
     constexpr int ROWS = 4 / S;
     constexpr bool OPS = true, BLEND = true;
@@ -592,8 +592,15 @@ __global__ __launch_bounds__(256) void k_state_colors_from_image(RasterParams r,
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= (uint64_t)r.width * r.height) return;
     const uint32_t gy = (uint32_t)(i / r.width), gx = (uint32_t)(i - (uint64_t)gy * r.width);
-    const float4 c = load_pixel(r, gx, gy);
+    const float4 c = r.format > CRH_FORMAT_RGBA8_ATTACHMENT ? load_px<true>(r, gx, gy) : load_pixel(r, gx, gy);
     for (uint32_t k = 0; k < samples; ++k) reinterpret_cast<float4*>(r.state_color)[i * samples + k] = c;
+}
+
+// crh_selftest_srgb: the kernels' encode on x[0, n), their decode on the 256 codes
+__global__ __launch_bounds__(256) void k_selftest_srgb(const float* x, uint8_t* codes, uint64_t n, float* decoded) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) codes[i] = (uint8_t)srgb_encode(x[i]);
+    if (i < 256u) decoded[i] = srgb_decode((uint32_t)i);
 }
 
 // ---------------------------------------------------------------------------------------------- launchers
@@ -670,9 +677,21 @@ uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t sample
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;
     const uint32_t blocks = ((r.tiles_x + kBlock - 1u) / kBlock) * ((r.tiles_y + kBlock - 1u) / kBlock);
     const dim3 grid((r.tile_order && r.order_places) ? r.order_places : ((blocks + 7u) / 8u) * kBlock * kBlock * 8u);
-#define CRH_LAUNCH_TILE(S_, ROWS_, OPS_, STROKES_) \
-    hipLaunchKernelGGL((k_raster_tile<S_, ROWS_, OPS_, STROKES_>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r)
-#define CRH_LAUNCH_BLEND(S_, STROKES_) hipLaunchKernelGGL((k_raster_blend<S_, STROKES_>), grid, dim3(64 * S_), S_ * r.sort_capacity * 4u, stream, s, r, *blend)
+    const bool xfmt = r.format > CRH_FORMAT_RGBA8_ATTACHMENT; // BGRA / sRGB targets: the XFMT instantiations
+#define CRH_LAUNCH_TILE(S_, ROWS_, OPS_, STROKES_)                                                                                                   \
+    do {                                                                                                                                           \
+        if (xfmt)                                                                                                                                  \
+            hipLaunchKernelGGL((k_raster_tile<S_, ROWS_, OPS_, STROKES_, true>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r); \
+        else                                                                                                                                       \
+            hipLaunchKernelGGL((k_raster_tile<S_, ROWS_, OPS_, STROKES_>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r); \
+    } while (0)
+#define CRH_LAUNCH_BLEND(S_, STROKES_)                                                                                                   \
+    do {                                                                                                                               \
+        if (xfmt)                                                                                                                      \
+            hipLaunchKernelGGL((k_raster_blend<S_, STROKES_, true>), grid, dim3(64 * S_), S_ * r.sort_capacity * 4u, stream, s, r, *blend); \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((k_raster_blend<S_, STROKES_>), grid, dim3(64 * S_), S_ * r.sort_capacity * 4u, stream, s, r, *blend); \
+    } while (0)
     if (blend) { // a blend state other than "over" (r.general is set with it)
         if (samples == 4) {
             if (has_stroke) CRH_LAUNCH_BLEND(4, true); else CRH_LAUNCH_BLEND(4, false);
@@ -719,6 +738,10 @@ void launch_scan_tiles(const RasterParams& r, hipStream_t stream) { // tile_coun
 void launch_state_colors_from_image(const RasterParams& r, uint32_t samples, hipStream_t stream) {
     const uint64_t n = (uint64_t)r.width * r.height;
     hipLaunchKernelGGL(k_state_colors_from_image, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, r, samples);
+}
+void launch_selftest_srgb(const float* x, uint8_t* codes, uint64_t n, float* decoded, hipStream_t stream) {
+    const uint64_t threads = n > 256u ? n : 256u;
+    hipLaunchKernelGGL(k_selftest_srgb, dim3((uint32_t)((threads + 255u) / 256u)), dim3(256), 0, stream, x, codes, n, decoded);
 }
 void launch_composite(const uint8_t* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, uint8_t* dst, hipStream_t stream) {
     hipLaunchKernelGGL(k_composite, dim3((uint32_t)((n_pixels + 255) / 256)), dim3(256), 0, stream, layers_dev, n_layers, n_pixels, dst);

@@ -6,6 +6,7 @@
 #include "ga.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
+#include "srgb_tables.h"
 
 #ifndef CRH_TILE_WAVES
 #define CRH_TILE_WAVES 6
@@ -85,6 +86,70 @@ CRH_D float4 load_pixel(const RasterParams& r, uint32_t gx, uint32_t gy) {
     }
     const uchar4 d = reinterpret_cast<const uchar4*>(r.rgba8)[at];
     return make_float4((float)d.x * (1.0f / 255.0f), (float)d.y * (1.0f / 255.0f), (float)d.z * (1.0f / 255.0f), (float)d.w * (1.0f / 255.0f));
+}
+
+// ---- The formats CRH_FORMAT_BGRA8 .. CRH_FORMAT_BGRA8_SRGB_ATTACHMENT (3-8): byte order B G R A and / or sRGB-encoded rgb. The raster kernels draw
+//      them in instantiations of their own (template argument XFMT = true), which read the format from r.format; the XFMT = false kernels are the
+//      RGBA8 / RGBA16F kernels exactly as they were (a branch on r.format inside the shared helpers changed their register allocation).
+//      format - 3 = k: bit 0 set = every write is rounded (*_ATTACHMENT), k in 2..5 = sRGB, k in 2..3 = RGBA byte order.
+// The codec is correctly rounded (csrc/srgb_tables.h, tools/gen_srgb_tables.py): decode = a table of 256 floats; encode = a first guess from
+// the sRGB curve, within one code of the answer, corrected against the two thresholds around it.
+static __constant__ float kSrgbDecode[256] = CRH_SRGB_DECODE_INIT;
+static __constant__ float kSrgbThreshold[257] = CRH_SRGB_THRESHOLD_INIT;
+__device__ __forceinline__ bool format_srgb(uint32_t format) { return format - 5u <= 3u; }
+__device__ __forceinline__ bool format_bgra(uint32_t format) { return format - 5u > 1u; }   // (for format >= 3)
+__device__ __forceinline__ bool format_rounds(uint32_t format) { return ((format - 3u) & 1u) != 0u; } // (for format >= 3)
+__device__ __forceinline__ float srgb_decode(uint32_t code) { return kSrgbDecode[code]; }
+// the number of k in 1..255 with x >= T[k]; NaN -> 0
+__device__ __forceinline__ uint32_t srgb_encode(float v) {
+    const float x = __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f); // NaN -> 0
+    const float s = x <= 0.0031308f ? x * 12.92f : 1.055f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.0f / 2.4f)) - 0.055f;
+    const int c = (int)__builtin_amdgcn_fmed3f(s * 255.0f + 0.5f, 0.0f, 255.0f); // within one code of the answer
+    return (uint32_t)(c + (int)(x >= kSrgbThreshold[c + 1]) - (int)(x < kSrgbThreshold[c]));
+}
+__device__ __forceinline__ uint32_t unorm8(float v) { return (uint32_t)(int)(__builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) * 255.0f + 0.5f); } // (pack_unorm8's channel)
+__device__ __forceinline__ uint32_t pack_pixel_x(uint32_t format, float c0, float c1, float c2, float c3) {
+    const bool srgb = format_srgb(format);
+    const uint32_t r = srgb ? srgb_encode(c0) : unorm8(c0), g = srgb ? srgb_encode(c1) : unorm8(c1), b = srgb ? srgb_encode(c2) : unorm8(c2);
+    const uint32_t a = unorm8(c3) << 24;
+    return format_bgra(format) ? (b | g << 8 | r << 16 | a) : (r | g << 8 | b << 16 | a);
+}
+__device__ __forceinline__ float4 unpack_pixel_x(uint32_t format, uint32_t bits) {
+    const uint32_t lo = bits & 255u, mid = (bits >> 8) & 255u, hi = (bits >> 16) & 255u;
+    const uint32_t r = format_bgra(format) ? hi : lo, g = mid, b = format_bgra(format) ? lo : hi;
+    const float a = (float)(bits >> 24) * (1.0f / 255.0f);
+    if (format_srgb(format)) return make_float4(srgb_decode(r), srgb_decode(g), srgb_decode(b), a);
+    return make_float4((float)r * (1.0f / 255.0f), (float)g * (1.0f / 255.0f), (float)b * (1.0f / 255.0f), a);
+}
+// What a *_SRGB_ATTACHMENT keeps of a colour component ch a blend wrote: encoded to 8 bits and read back decoded (alpha: attachment_unorm8)
+__device__ __forceinline__ float attachment_x(uint32_t format, int ch, float v) {
+    return (ch < 3 && format_srgb(format)) ? srgb_decode(srgb_encode(v)) : attachment_unorm8(v);
+}
+// The kernels' view of the target: XFMT = false is the code of the RGBA8 / RGBA16F kernels, XFMT = true that of formats 3-8.
+template <bool XFMT>
+__device__ __forceinline__ void store_px(const RasterParams& r, uint32_t gx, uint32_t gy, float c0, float c1, float c2, float c3) {
+    if constexpr (XFMT) reinterpret_cast<uint32_t*>(r.rgba8)[(size_t)gy * r.width + gx] = pack_pixel_x(r.format, c0, c1, c2, c3);
+    else store_pixel(r, gx, gy, c0, c1, c2, c3);
+}
+template <bool XFMT>
+__device__ __forceinline__ float4 load_px(const RasterParams& r, uint32_t gx, uint32_t gy) {
+    if constexpr (XFMT) return unpack_pixel_x(r.format, reinterpret_cast<const uint32_t*>(r.rgba8)[(size_t)gy * r.width + gx]);
+    else return load_pixel(r, gx, gy);
+}
+template <bool XFMT>
+__device__ __forceinline__ uint32_t pack_px(const RasterParams& r, float c0, float c1, float c2, float c3) {
+    if constexpr (XFMT) return pack_pixel_x(r.format, c0, c1, c2, c3);
+    else return pack_unorm8(c0, c1, c2, c3);
+}
+template <bool XFMT>
+__device__ __forceinline__ bool rounds_writes(const RasterParams& r) { // the target is an attachment: every colour write of a cover is rounded where it happens
+    if constexpr (XFMT) return format_rounds(r.format);
+    else return r.format == CRH_FORMAT_RGBA8_ATTACHMENT;
+}
+template <bool XFMT>
+__device__ __forceinline__ float attachment(const RasterParams& r, int ch, float v) {
+    if constexpr (XFMT) return attachment_x(r.format, ch, v);
+    else return attachment_unorm8(v);
 }
 
 enum : uint32_t { KIND_SOLID = 0, KIND_IQ = 1, KIND_IC = 2, KIND_RQ = 3, KIND_RC = 4, KIND_LINE = 5, KIND_JOINT = 6, KIND_COVER = 7 };

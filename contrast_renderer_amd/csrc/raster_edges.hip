@@ -1691,7 +1691,7 @@ CRH_D SlotMasks slot_masks(uint32_t rows16) {
 // msaa 4 = four wavefronts, one pixel row x four samples per lane. Per sample the lane keeps the winding counter, the hull winding of
 // the item being drawn and the colour; entries are walked in key order (= draw order).
 // LONG: the late start also for lists of several chunks (selected by the host for frames whose tiles hold many entries on average).
-template <int S, int ROWS, bool STROKES, bool LONG>
+template <int S, int ROWS, bool STROKES, bool LONG, bool XFMT = false> // XFMT: the frame formats 3-8 (raster_common.hpp store_px)
 __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu((STROKES || S == 4) ? CRH_STROKE_TILE_WAVES : CRH_EDGE_TILE_WAVES))) void k_raster_edges(SceneDev s, RasterParams r) {
     const uint32_t bid = blockIdx.x; // the workgroup's place in the frame's tile order
     extern __shared__ uint32_t sort_buffer[];
@@ -1754,7 +1754,7 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
         for (int b = 0; b < ROWS; ++b) {
             const uint32_t gy = ty * kTile + first_row + 4u * b + rq;
             if (gx < r.width && gy < r.height) {
-                const float4 d = load_pixel(r, gx, gy);
+                const float4 d = load_px<XFMT>(r, gx, gy);
 #pragma unroll
                 for (int q = 0; q < S; ++q) col[b][q][0] = d.x, col[b][q][1] = d.y, col[b][q][2] = d.z, col[b][q][3] = d.w;
             }
@@ -2336,13 +2336,13 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
                     col[b][q][3] = blend[b][q] ? n3 : col[b][q][3];
                 }
             }
-            if (r.format == CRH_FORMAT_RGBA8_ATTACHMENT) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
+            if (rounds_writes<XFMT>(r)) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
 #pragma unroll
                 for (int b = 0; b < ROWS; ++b)
 #pragma unroll
                     for (int q = 0; q < S; ++q)
 #pragma unroll
-                        for (int ch = 0; ch < 4; ++ch) col[b][q][ch] = attachment_unorm8(col[b][q][ch]);
+                        for (int ch = 0; ch < 4; ++ch) col[b][q][ch] = attachment<XFMT>(r, ch, col[b][q][ch]);
             }
             col_keep();
         }
@@ -2367,7 +2367,7 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
                 for (int q = 0; q < S; ++q) sum = sum + col[b][q][ch];
                 avg[ch] = sum * inv;
             }
-            store_pixel(r, gx, gy, avg[0], avg[1], avg[2], avg[3]);
+            store_px<XFMT>(r, gx, gy, avg[0], avg[1], avg[2], avg[3]);
         }
     }
 }
@@ -2567,7 +2567,7 @@ CRH_D int reject_unless_row(int x, uint32_t not_rows, int bit) { return (int)(((
 #ifndef CRH_FILL_TILE_WAVES
 #define CRH_FILL_TILE_WAVES 7
 #endif
-template <bool LONG, int WAVES = CRH_FILL_TILE_WAVES>
+template <bool LONG, int WAVES = CRH_FILL_TILE_WAVES, bool XFMT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) void k_raster_fill(SceneDev s, RasterParams r) {
     constexpr int ROWS = 4;
     const uint32_t bid = blockIdx.x; // the workgroup's place in the frame's tile order
@@ -2603,7 +2603,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
         for (int b = 0; b < ROWS; ++b) {
             const uint32_t gy = ty * kTile + 4u * b + rq;
             if (gx < r.width && gy < r.height) {
-                const float4 d = load_pixel(r, gx, gy);
+                const float4 d = load_px<XFMT>(r, gx, gy);
                 col[b][0] = d.x, col[b][1] = d.y, col[b][2] = d.z, col[b][3] = d.w;
             }
         }
@@ -3027,11 +3027,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
             }
             const float one_minus_a = 1.0f - cs3;
             blend_rows(col, blend, cs0, cs1, cs2, cs3, one_minus_a, replace);
-            if (r.format == CRH_FORMAT_RGBA8_ATTACHMENT) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
+            if (rounds_writes<XFMT>(r)) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
 #pragma unroll
                 for (int b = 0; b < ROWS; ++b)
 #pragma unroll
-                    for (int ch = 0; ch < 4; ++ch) col[b][ch] = attachment_unorm8(col[b][ch]);
+                    for (int ch = 0; ch < 4; ++ch) col[b][ch] = attachment<XFMT>(r, ch, col[b][ch]);
             }
         } // groups of the chunk
         if (LONG && again_from_the_top) { // (X of the late start did not overwrite every sample: the whole list, chunk 0 first)
@@ -3052,7 +3052,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 #pragma unroll
     for (int b = 0; b < ROWS; ++b) {
         const uint32_t gy = ty * kTile + 4u * b + rq;
-        if (gx_end < r.width && gy < r.height) store_pixel(r, gx_end, gy, col[b][0], col[b][1], col[b][2], col[b][3]);
+        if (gx_end < r.width && gy < r.height) store_px<XFMT>(r, gx_end, gy, col[b][0], col[b][1], col[b][2], col[b][3]);
     }
 }
 
@@ -3122,7 +3122,7 @@ CRH_D uint32_t first_of_16(P holds) {
     for (int step = 8; step >= 1; step >>= 1) lo = holds(lo + (float)(step - 1)) ? lo : lo + (float)step;
     return (lo == 15.0f && !holds(15.0f)) ? 16u : (uint32_t)(int)lo;
 }
-template <bool LONG>
+template <bool LONG, bool XFMT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE_WAVES))) void k_raster_rows(SceneDev s, RasterParams r) {
     const uint32_t bid = blockIdx.x;
     extern __shared__ uint32_t sort_buffer[];
@@ -3164,7 +3164,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (gx0 + (uint32_t)i < r.width) {
-                const float4 d = load_pixel(r, gx0 + (uint32_t)i, gy);
+                const float4 d = load_px<XFMT>(r, gx0 + (uint32_t)i, gy);
                 col[i][0] = d.x, col[i][1] = d.y, col[i][2] = d.z, col[i][3] = d.w;
             }
     }
@@ -3592,11 +3592,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
                             col[i][0] = replace ? cs0 : cs0 + col[i][0] * one_minus_a, col[i][1] = replace ? cs1 : cs1 + col[i][1] * one_minus_a;
                             col[i][2] = replace ? cs2 : cs2 + col[i][2] * one_minus_a, col[i][3] = replace ? cs3 : cs3 + col[i][3] * one_minus_a;
                         }
-                        if (r.format == CRH_FORMAT_RGBA8_ATTACHMENT) {
+                        if (rounds_writes<XFMT>(r)) {
 #pragma unroll
                             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                                for (int ch = 0; ch < 4; ++ch) col[i][ch] = attachment_unorm8(col[i][ch]);
+                                for (int ch = 0; ch < 4; ++ch) col[i][ch] = attachment<XFMT>(r, ch, col[i][ch]);
                         }
                         continue;
                     }
@@ -3678,11 +3678,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
                             col[i][3] = blend[i] ? n3 : col[i][3];
                         }
                     }
-                    if (r.format == CRH_FORMAT_RGBA8_ATTACHMENT) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
+                    if (rounds_writes<XFMT>(r)) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
-                            for (int ch = 0; ch < 4; ++ch) col[i][ch] = attachment_unorm8(col[i][ch]);
+                            for (int ch = 0; ch < 4; ++ch) col[i][ch] = attachment<XFMT>(r, ch, col[i][ch]);
                     }
                 }
                 if (restart) { // (X of the late start did not overwrite every sample: everything again, from cleared state, the shortcut off)
@@ -3724,13 +3724,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
     if (gy < r.height) {
         if (r.format != CRH_FORMAT_RGBA16F && gx0 + 3u < r.width) {
             uint4 px;
-            px.x = pack_unorm8(col[0][0], col[0][1], col[0][2], col[0][3]), px.y = pack_unorm8(col[1][0], col[1][1], col[1][2], col[1][3]);
-            px.z = pack_unorm8(col[2][0], col[2][1], col[2][2], col[2][3]), px.w = pack_unorm8(col[3][0], col[3][1], col[3][2], col[3][3]);
+            px.x = pack_px<XFMT>(r, col[0][0], col[0][1], col[0][2], col[0][3]), px.y = pack_px<XFMT>(r, col[1][0], col[1][1], col[1][2], col[1][3]);
+            px.z = pack_px<XFMT>(r, col[2][0], col[2][1], col[2][2], col[2][3]), px.w = pack_px<XFMT>(r, col[3][0], col[3][1], col[3][2], col[3][3]);
             *reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(r.rgba8) + (size_t)gy * r.width + gx0) = px;
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (gx0 + (uint32_t)i < r.width) store_pixel(r, gx0 + (uint32_t)i, gy, col[i][0], col[i][1], col[i][2], col[i][3]);
+                if (gx0 + (uint32_t)i < r.width) store_px<XFMT>(r, gx0 + (uint32_t)i, gy, col[i][0], col[i][1], col[i][2], col[i][3]);
         }
     }
 }
@@ -3993,13 +3993,23 @@ uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t 
     // fill scenes at msaa 1: the class-batched walk with packed counters (k_raster_fill); CRH_FILL_KERNEL=0 keeps k_raster_edges<1, 4, false, *> (A/B runs, tests: the two are bit-equal)
     const char* fill_env = getenv("CRH_FILL_KERNEL"); // (read per launch: tests switch it inside one process)
     const bool fill_kernel = !(fill_env && fill_env[0] == '0') && r.winding_mask <= 0xFFFFu && r.fill_cells != 0u;
-#define CRH_LAUNCH_EDGES(S_, ROWS_, STROKES_, LONG_) \
-    hipLaunchKernelGGL((k_raster_edges<S_, ROWS_, STROKES_, LONG_>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r)
+    const bool xfmt = r.format > CRH_FORMAT_RGBA8_ATTACHMENT; // BGRA / sRGB targets: the XFMT instantiations (the same formulation)
+#define CRH_LAUNCH_EDGES(S_, ROWS_, STROKES_, LONG_)                                                                                                    \
+    do {                                                                                                                                              \
+        if (xfmt)                                                                                                                                     \
+            hipLaunchKernelGGL((k_raster_edges<S_, ROWS_, STROKES_, LONG_, true>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r); \
+        else                                                                                                                                          \
+            hipLaunchKernelGGL((k_raster_edges<S_, ROWS_, STROKES_, LONG_>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r); \
+    } while (0)
     uint32_t variant = kRasterEdges;
     if (samples == 1 && !has_stroke && r.rows) {
         variant = r.long_lists ? kRasterRowsLong : kRasterRows; // the row-span kernel: winding numbers accumulated in LDS, lanes over (entry, sample row)
-        if (r.long_lists)
+        if (r.long_lists && xfmt)
+            hipLaunchKernelGGL((k_raster_rows<true, true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
+        else if (r.long_lists)
             hipLaunchKernelGGL((k_raster_rows<true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
+        else if (xfmt)
+            hipLaunchKernelGGL((k_raster_rows<false, true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
         else
             hipLaunchKernelGGL((k_raster_rows<false>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
     } else if (samples == 4) {
@@ -4010,7 +4020,10 @@ uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t 
         // (always the variant that looks for its late start across the chunks of a long list: measured on the 10 000 path scene — few lists
         // beyond one chunk — it is as fast as the one without, 0.1655 against 0.168 ms, and it is the build without scratch memory)
         // (... and ONE build for every frame: round 5's six-wave build for frames of long lists is gone with its reason, see CRH_FILL_TILE_WAVES)
-        hipLaunchKernelGGL((k_raster_fill<true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
+        if (xfmt)
+            hipLaunchKernelGGL((k_raster_fill<true, CRH_FILL_TILE_WAVES, true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
+        else
+            hipLaunchKernelGGL((k_raster_fill<true>), grid, dim3(64), r.sort_capacity * 4u, stream, s, r);
         variant = kRasterFill;
     } else if (r.long_lists) {
         CRH_LAUNCH_EDGES(1, 4, false, true);

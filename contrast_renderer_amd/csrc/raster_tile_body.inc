@@ -75,7 +75,7 @@
         for (int b = 0; b < ROWS; ++b) {
             const uint32_t gy = ty * kTile + first_row + 4u * b + rq;
             if (gx < r.width && gy < r.height) {
-                const float4 d = load_pixel(r, gx, gy);
+                const float4 d = load_px<XFMT>(r, gx, gy);
 #pragma unroll
                 for (int k = 0; k < S; ++k) col[b][k][0] = d.x, col[b][k][1] = d.y, col[b][k][2] = d.z, col[b][k][3] = d.w;
             }
@@ -373,7 +373,7 @@
                             const float scaled = scale_src + alpha * (1.0f - scale_src);      // alpha' = src.a * One + dst.a * (1 - src.a), renderer.rs:803-828
                             const float restored = alpha - (1.0f - mine) * (1.0f - ca);        // alpha' = dst.a - (1 - saved)(1 - a), renderer.rs:829-861
                             float next = is_scale ? scaled : (is_restore ? restored : alpha);
-                            if (r.format == CRH_FORMAT_RGBA8_ATTACHMENT) next = attachment_unorm8(next); // an Rgba8Unorm attachment keeps 8 bits of what the blender writes
+                            if (rounds_writes<XFMT>(r)) next = attachment<XFMT>(r, 3, next); // an Rgba8Unorm attachment keeps 8 bits of what the blender writes
                             col[b][k][3] = pass ? next : alpha;
 #pragma unroll
                             for (int l = 0; l < kMaxAlphaLayers; ++l) // save_alpha_context_cover: the layer receives the frame's alpha, shaders.wgsl:326-331
@@ -486,7 +486,7 @@
                             const uint32_t kind = bf.kind[c]; // wave uniform
                             float v = kind == 0u ? lin : (kind == 1u ? fminf(src[ch], dc) : (kind == 2u ? fmaxf(src[ch], dc) : src[ch]));
                             v = clamp_unit(v);
-                            if (r.format == CRH_FORMAT_RGBA8_ATTACHMENT) v = attachment_unorm8(v);
+                            if (rounds_writes<XFMT>(r)) v = attachment<XFMT>(r, ch, v);
                             col[b][k][ch] = (blend[b][k] && ((bf.write_mask >> ch) & 1u) != 0u) ? v : dc; // a masked channel keeps the target's value
                         }
                     }
@@ -504,13 +504,13 @@
                         col[b][k][2] = blend[b][k] ? n2 : col[b][k][2];
                         col[b][k][3] = blend[b][k] ? n3 : col[b][k][3];
                     }
-                if (r.format == CRH_FORMAT_RGBA8_ATTACHMENT) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
+                if (rounds_writes<XFMT>(r)) { // an Rgba8Unorm attachment keeps 8 bits of what the blender writes (idempotent on the others)
 #pragma unroll
                     for (int b = 0; b < ROWS; ++b)
 #pragma unroll
                         for (int k = 0; k < S; ++k)
 #pragma unroll
-                            for (int ch = 0; ch < 4; ++ch) col[b][k][ch] = attachment_unorm8(col[b][k][ch]);
+                            for (int ch = 0; ch < 4; ++ch) col[b][k][ch] = attachment<XFMT>(r, ch, col[b][k][ch]);
                 }
             }
         }
@@ -556,6 +556,6 @@
                 for (int k = 0; k < S; ++k) sum = sum + col[b][k][ch];
                 avg[ch] = sum * inv;
             }
-            store_pixel(r, gx, gy, avg[0], avg[1], avg[2], avg[3]);
+            store_px<XFMT>(r, gx, gy, avg[0], avg[1], avg[2], avg[3]);
         }
     }

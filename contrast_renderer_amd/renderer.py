@@ -4,6 +4,7 @@ batch forms (Scene = many Shapes built and rendered together, Frame = the render
 All arithmetic runs in libcontrast_hip.so on the GPU; this module only marshals arguments.
 """
 import ctypes as C
+import dataclasses
 from dataclasses import dataclass
 from enum import IntEnum, IntFlag
 from typing import ClassVar, Optional, Tuple
@@ -109,13 +110,28 @@ class ColorWrites(IntFlag):  # wgpu::ColorWrites
     ALL = 15
 
 
+class TextureFormat(IntEnum):
+    """wgpu::TextureFormat of the colour target (renderer.rs:380-382). The value is the frame format that keeps f32 colours within a pass
+    (FORMAT_*); `attachment` is the one that rounds every write, as a hardware blender does."""
+    Rgba8Unorm = 0
+    Bgra8Unorm = 3
+    Rgba8UnormSrgb = 5
+    Bgra8UnormSrgb = 7
+
+    @property
+    def attachment(self):
+        return FORMAT_RGBA8_ATTACHMENT if self == TextureFormat.Rgba8Unorm else int(self) + 1
+
+
 @dataclass(frozen=True)
 class ColorTargetState:
-    """wgpu::ColorTargetState of the colour cover without the format (renderer.rs:380-382): `blend` None = the source replaces the target.
-    `constant` stands for RenderPass::set_blend_constant, which this library keeps with the renderer."""
+    """wgpu::ColorTargetState of the colour cover (renderer.rs:380-382): `blend` None = the source replaces the target.
+    `constant` stands for RenderPass::set_blend_constant, which this library keeps with the renderer. `format` is kept host-side: it is
+    the format Frame(renderer, ...) creates by default (the C ABI names a frame's format at crh_frame_create_format)."""
     blend: Optional[BlendState] = None
     write_mask: int = ColorWrites.ALL
     constant: Tuple[float, float, float, float] = (0.0, 0.0, 0.0, 0.0)
+    format: TextureFormat = TextureFormat.Rgba8Unorm
 
     def to_c(self):
         b = self.blend or BlendState.REPLACE
@@ -163,7 +179,10 @@ class Renderer:
         """The colour cover's blend state the renderer was created with (the "over" state when Configuration.blending is None)."""
         out = _ffi.ColorTargetStateC()
         check(self.lib.crh_renderer_get_blending(self.handle, C.byref(out)))
-        return ColorTargetState.from_c(out)
+        state = ColorTargetState.from_c(out)
+        if self.config.blending is not None:
+            state = dataclasses.replace(state, format=self.config.blending.format)
+        return state
 
     def synchronize(self):
         check(self.lib.crh_renderer_synchronize(self.handle))
@@ -188,6 +207,15 @@ class Renderer:
         check(self.lib.crh_selftest_fmath(self.handle, fn, a.ctypes.data_as(fp), b.ctypes.data_as(fp), out.ctypes.data_as(fp), a.size))
         return out
 
+    def selftest_srgb(self, x):
+        """The raster kernels' sRGB codec run on the GPU: -> (encode(x) as uint8, decode of the 256 codes as float32)."""
+        x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+        codes = np.zeros(x.size, dtype=np.uint8)
+        decoded = np.zeros(256, dtype=np.float32)
+        check(self.lib.crh_selftest_srgb(self.handle, x.ctypes.data_as(C.POINTER(C.c_float)), codes.ctypes.data_as(C.POINTER(C.c_uint8)), x.size,
+                                         decoded.ctypes.data_as(C.POINTER(C.c_float))))
+        return codes, decoded
+
     def __del__(self):
         if getattr(self, "handle", None) and self.lib is not None:
             self.lib.crh_renderer_destroy(self.handle)
@@ -195,12 +223,19 @@ class Renderer:
 
 
 FORMAT_RGBA8, FORMAT_RGBA16F, FORMAT_RGBA8_ATTACHMENT = 0, 1, 2  # (2: RGBA8 storage, every blend rounded to 8 bits like an Rgba8Unorm attachment)
+# the other colour targets (include/contrast_hip.h): B G R A byte order and / or sRGB-encoded rgb; *_ATTACHMENT rounds every write
+FORMAT_BGRA8, FORMAT_BGRA8_ATTACHMENT, FORMAT_RGBA8_SRGB, FORMAT_RGBA8_SRGB_ATTACHMENT, FORMAT_BGRA8_SRGB, FORMAT_BGRA8_SRGB_ATTACHMENT = 3, 4, 5, 6, 7, 8
 
 
 class Frame:
-    """The colour attachment (premultiplied; RGBA8, or RGBA16F for the layers of the multi-GPU exchange) and per-sample winding state of one render pass."""
+    """The colour attachment (premultiplied; RGBA8, BGRA8, their sRGB forms, or RGBA16F for the layers of the multi-GPU exchange) and
+    per-sample winding state of one render pass. `format` None = the renderer's Configuration.blending.format (FORMAT_RGBA8 without one)."""
 
-    def __init__(self, renderer: Renderer, width: int, height: int, format: int = FORMAT_RGBA8):
+    def __init__(self, renderer: Renderer, width: int, height: int, format: Optional[int] = None):
+        if format is None:
+            blending = renderer.config.blending
+            format = int(blending.format) if blending is not None else FORMAT_RGBA8
+        format = int(format)
         self.renderer = renderer
         self.lib = renderer.lib
         self.width, self.height, self.format = width, height, format
@@ -241,7 +276,8 @@ class Frame:
         return out
 
     def upload(self, image):
-        """LoadOp::Load of caller content: [height, width, 4] premultiplied RGBA8 replaces the pixels, stencil, alpha layers and pass state are
+        """LoadOp::Load of caller content: [height, width, 4] premultiplied 8-bit pixels in the frame's storage order (B G R A for a BGRA
+        format; sRGB-encoded rgb for an sRGB one) replace the pixels, stencil, alpha layers and pass state are
         reset as by clear(), depth is left alone; the next pass loads the pixels. An RGBA16F frame, a frame restricted by set_tile_rows() and an
         image of another size are refused (InvalidArgument)."""
         image = np.asarray(image)
@@ -251,7 +287,7 @@ class Frame:
         check(self.lib.crh_frame_upload(self.handle, data.ctypes.data))
 
     def download(self):
-        """-> [height, width, 4] uint8 (an RGBA8 frame) or float16 (an RGBA16F frame)."""
+        """-> [height, width, 4] uint8 in the frame's storage order (R G B A, or B G R A for a BGRA format) or float16 (an RGBA16F frame)."""
         if self.format == FORMAT_RGBA16F:
             out = np.zeros((self.height, self.width, 4), dtype=np.float16)
             check(self.lib.crh_frame_download_f16(self.handle, out.ctypes.data))

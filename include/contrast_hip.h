@@ -204,7 +204,7 @@ typedef struct crh_blend_component { /* wgpu::BlendComponent */
     uint32_t operation;  /* crh_blend_operation */
 } crh_blend_component;
 enum { CRH_COLOR_WRITE_RED = 1, CRH_COLOR_WRITE_GREEN = 2, CRH_COLOR_WRITE_BLUE = 4, CRH_COLOR_WRITE_ALPHA = 8, CRH_COLOR_WRITE_ALL = 15 }; /* wgpu::ColorWrites */
-typedef struct crh_color_target_state { /* wgpu::ColorTargetState without the format */
+typedef struct crh_color_target_state { /* wgpu::ColorTargetState without the format (the frame's: crh_frame_create_format) */
     uint32_t blend_enabled;    /* 0 = `blend: None`: the source replaces the target */
     crh_blend_component color; /* rgb channels */
     crh_blend_component alpha; /* alpha channel */
@@ -275,12 +275,37 @@ crh_status crh_frame_create(crh_renderer* renderer, uint32_t width, uint32_t hei
 /* The same with the storage format of the resolved image named. CRH_FORMAT_RGBA8 is the reference's target (main.rs:205-215 renders to
  * the surface format, 8 bits per channel). CRH_FORMAT_RGBA16F keeps four binary16 values per pixel — the per-rank LAYERS of the multi-GPU
  * exchange (layers exchanged as RGBA16F keep the composite within 1/255 of a single-GPU render, RGBA8 layers within 2/255). */
-enum { CRH_FORMAT_RGBA8 = 0, CRH_FORMAT_RGBA16F = 1, CRH_FORMAT_RGBA8_ATTACHMENT = 2 };
+enum {
+    CRH_FORMAT_RGBA8 = 0,
+    CRH_FORMAT_RGBA16F = 1,
+    CRH_FORMAT_RGBA8_ATTACHMENT = 2,
+    CRH_FORMAT_BGRA8 = 3,                     /* wgpu Bgra8Unorm, f32 colours within a pass (as CRH_FORMAT_RGBA8) */
+    CRH_FORMAT_BGRA8_ATTACHMENT = 4,          /* wgpu Bgra8Unorm, every write rounded (as CRH_FORMAT_RGBA8_ATTACHMENT) */
+    CRH_FORMAT_RGBA8_SRGB = 5,                /* wgpu Rgba8UnormSrgb, f32 linear colours within a pass, encoded once at the end */
+    CRH_FORMAT_RGBA8_SRGB_ATTACHMENT = 6,     /* wgpu Rgba8UnormSrgb, every write encoded to sRGB8 and read back decoded */
+    CRH_FORMAT_BGRA8_SRGB = 7,                /* wgpu Bgra8UnormSrgb, as CRH_FORMAT_RGBA8_SRGB */
+    CRH_FORMAT_BGRA8_SRGB_ATTACHMENT = 8      /* wgpu Bgra8UnormSrgb, as CRH_FORMAT_RGBA8_SRGB_ATTACHMENT */
+};
 /* CRH_FORMAT_RGBA8_ATTACHMENT: RGBA8 storage like CRH_FORMAT_RGBA8, and the frame behaves like the wgpu::TextureFormat::Rgba8Unorm colour
  * ATTACHMENT the reference blends into (renderer.rs:736-754, examples/showcase/main.rs:32-43,205-215): every colour write of a cover — the
  * premultiplied "over" of Color, the alpha writes of Scale / RestoreAlphaContext — is rounded to 8 bits per channel where it happens, as a
  * hardware blender reads and writes the texture. CRH_FORMAT_RGBA8 keeps f32 colours for the whole pass and rounds once at the end: up to a
- * few 1/255 closer to the exact composite where many translucent Shapes overlap. Same download / upload entry points as CRH_FORMAT_RGBA8. */
+ * few 1/255 closer to the exact composite where many translucent Shapes overlap. Same download / upload entry points as CRH_FORMAT_RGBA8.
+ *
+ * Formats 3-8 are the other colour targets of Configuration::blending's `format` (renderer.rs:380-382). All store 4 bytes per pixel:
+ *   BGRA byte order: B G R A in memory — crh_frame_download / crh_frame_device_pointer hand out, and crh_frame_upload takes, bytes in the
+ *       frame's storage order; nothing else differs from the RGBA formats (a Bgra8Unorm swapchain image is the frame's bytes as they are).
+ *   sRGB (*_SRGB): as a wgpu *Srgb attachment, colours are linear within a pass — the MSAA resolve averages linear samples — and rgb is
+ *       encoded at the store; loads (a pass over existing content, crh_frame_upload) decode rgb. Alpha is never converted (unorm8 as RGBA8).
+ *       *_SRGB_ATTACHMENT encodes and decodes rgb at every write where CRH_FORMAT_RGBA8_ATTACHMENT rounds. A blend state other than "over"
+ *       blends the decoded (linear) target. The codec is correctly rounded — hardware blenders are allowed a tolerance here, so no GPU
+ *       gives a bit-exact answer to copy; this library defines its contract as: linear(s) = s / 12.92 (s <= 0.04045) or
+ *       ((s + 0.055) / 1.055)^2.4 in float64 (utils.rs:203-226); decode D[c] = float32 round-to-nearest of linear(c / 255); encode of a
+ *       float32 x = the number of k in 1..255 with x >= T[k], T[k] = the smallest float32 not below linear((k - 0.5) / 255), NaN -> 0.
+ *   crh_frame_clear, crh_frame_set_tile_rows, crh_frame_download, crh_frame_device_pointer and crh_frame_gather_slabs move bytes and work on
+ *   every 8-bit format (gathered layers and the result share one byte encoding: X and X_ATTACHMENT count as one; a mismatch is
+ *   CRH_ERR_INVALID_ARGUMENT on every rank); crh_frame_download_f16 refuses them; crh_frame_exchange returns CRH_ERR_UNSUPPORTED on every
+ *   rank for a BGRA or sRGB layer or result (its composite is unorm RGBA "over"). Passes take the formulation an RGBA8 frame would. */
 crh_status crh_frame_create_format(crh_renderer* renderer, uint32_t width, uint32_t height, uint32_t format, crh_frame** out);
 crh_status crh_frame_format(const crh_frame* frame, uint32_t* format);
 void crh_frame_destroy(crh_frame* frame);
@@ -370,6 +395,9 @@ crh_status crh_renderer_kernel_times(crh_renderer* renderer, crh_kernel_time* ou
 /* Self-test tap: evaluates include/crh_fmath.h ON THE GPU (fn 0 atan2(a,b), 1 acos(a), 2 sin(a), 3 cos(a), 4 pow(a,b), 5 wgsl_mod(a,b))
  * so that tests can check device results bit for bit against the host evaluation of the same header. Host pointers. */
 crh_status crh_selftest_fmath(crh_renderer* renderer, int fn, const float* a, const float* b, float* out, uint64_t n);
+/* Self-test tap of the sRGB codec of the *_SRGB formats, run ON THE GPU by the functions the raster kernels use: codes[i] = encode(x[i]) for
+ * i < n, decoded[c] = decode(c) for the 256 codes (both as defined at CRH_FORMAT_RGBA8_SRGB above). Host pointers. */
+crh_status crh_selftest_srgb(crh_renderer* renderer, const float* x, uint8_t* codes, uint64_t n, float* decoded);
 /* ---- glyph producer: text.rs (config 3 input) ----------------------------------------------------
  * Host-side code (the reference's is host-side too). The TrueType reading is done by the crate
  * ttf-parser 0.14.0 in the reference (Cargo.toml:20, not vendored); src/csrc/text.cpp restates the

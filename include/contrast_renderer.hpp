@@ -427,11 +427,22 @@ inline const BlendState BlendState::PREMULTIPLIED_ALPHA_BLENDING{BlendComponent:
 namespace ColorWrites { // wgpu::ColorWrites
 constexpr uint32_t RED = CRH_COLOR_WRITE_RED, GREEN = CRH_COLOR_WRITE_GREEN, BLUE = CRH_COLOR_WRITE_BLUE, ALPHA = CRH_COLOR_WRITE_ALPHA, COLOR = 7, ALL = CRH_COLOR_WRITE_ALL;
 }
-// wgpu::ColorTargetState without the format; `constant` stands for RenderPass::set_blend_constant, kept with the renderer here
+// wgpu::TextureFormat of the colour target. The value is the frame format that keeps f32 colours within a pass; attachment_format() the one
+// that rounds every write, as a hardware blender does
+enum class TextureFormat : uint32_t {
+    Rgba8Unorm = CRH_FORMAT_RGBA8,
+    Bgra8Unorm = CRH_FORMAT_BGRA8,
+    Rgba8UnormSrgb = CRH_FORMAT_RGBA8_SRGB,
+    Bgra8UnormSrgb = CRH_FORMAT_BGRA8_SRGB
+};
+inline uint32_t attachment_format(TextureFormat f) { return f == TextureFormat::Rgba8Unorm ? (uint32_t)CRH_FORMAT_RGBA8_ATTACHMENT : (uint32_t)f + 1u; }
+// wgpu::ColorTargetState; `constant` stands for RenderPass::set_blend_constant, kept with the renderer here. `format` is kept host-side: the
+// format a Frame created without one gets (the C ABI names a frame's format at crh_frame_create_format)
 struct ColorTargetState {
     std::optional<BlendState> blend = std::nullopt; // None: the source replaces the target
     uint32_t write_mask = ColorWrites::ALL;
     std::array<float, 4> constant = {0.0f, 0.0f, 0.0f, 0.0f};
+    TextureFormat format = TextureFormat::Rgba8Unorm;
     crh_color_target_state to_c() const {
         const BlendState b = blend.value_or(BlendState::REPLACE);
         return crh_color_target_state{blend ? 1u : 0u, b.color.to_c(), b.alpha.to_c(), write_mask, {constant[0], constant[1], constant[2], constant[3]}};
@@ -462,6 +473,7 @@ class Renderer { // renderer.rs:408-435
         const std::optional<crh_color_target_state> blending = config.blending ? std::optional<crh_color_target_state>(config.blending->to_c()) : std::nullopt;
         check(crh_renderer_create_blended(&c, blending ? &*blending : nullptr, device, &handle_));
         samples_ = config.msaa_sample_count;
+        format_ = config.blending ? config.blending->format : TextureFormat::Rgba8Unorm;
     }
     ~Renderer() { crh_renderer_destroy(handle_); }
     Renderer(const Renderer&) = delete;
@@ -475,25 +487,31 @@ class Renderer { // renderer.rs:408-435
     ColorTargetState get_blending() const { // the state the renderer was created with (the "over" state for a Configuration without one)
         crh_color_target_state b;
         check(crh_renderer_get_blending(handle_, &b));
-        return ColorTargetState::from_c(b);
+        ColorTargetState out = ColorTargetState::from_c(b);
+        out.format = format_;
+        return out;
     }
     void synchronize() { check(crh_renderer_synchronize(handle_)); }
     crh_renderer* raw() const { return handle_; }
     uint32_t msaa_sample_count() const { return samples_; }
+    TextureFormat format() const { return format_; } // Configuration::blending's format (Rgba8Unorm without one)
 
   private:
     crh_renderer* handle_ = nullptr;
     uint32_t samples_ = 1;
+    TextureFormat format_ = TextureFormat::Rgba8Unorm;
 };
 
 // The caller-owned colour + depth/stencil attachments of the render pass (examples/showcase/main.rs:217-230).
 class Frame {
   public:
     // `format`: CRH_FORMAT_RGBA8 (f32 colours during a pass, one rounding at the end) or CRH_FORMAT_RGBA8_ATTACHMENT (every blend rounded to 8 bits, as
-    // the wgpu Rgba8Unorm attachment of main.rs:205-215 would)
-    Frame(Renderer& renderer, uint32_t width, uint32_t height, uint32_t format = CRH_FORMAT_RGBA8) : width_(width), height_(height), samples_(renderer.msaa_sample_count()) {
+    // the wgpu Rgba8Unorm attachment of main.rs:205-215 would), or one of the BGRA / sRGB formats (include/contrast_hip.h)
+    Frame(Renderer& renderer, uint32_t width, uint32_t height, uint32_t format) : width_(width), height_(height), samples_(renderer.msaa_sample_count()) {
         check(crh_frame_create_format(renderer.raw(), width, height, format, &handle_));
     }
+    // ... in the format of the renderer's Configuration::blending (CRH_FORMAT_RGBA8 without one)
+    Frame(Renderer& renderer, uint32_t width, uint32_t height) : Frame(renderer, width, height, (uint32_t)renderer.format()) {}
     ~Frame() { crh_frame_destroy(handle_); }
     Frame(const Frame&) = delete;
     Frame& operator=(const Frame&) = delete;
@@ -512,12 +530,13 @@ class Frame {
         check(crh_frame_download_depth(handle_, out.data()));
         return out;
     }
-    // LoadOp::Load of caller content: premultiplied RGBA8, row 0 = top; stencil, alpha layers and pass state reset as by clear(), depth kept
+    // LoadOp::Load of caller content: premultiplied 8-bit pixels in the frame's storage order (B G R A for a BGRA format, sRGB rgb for an sRGB one),
+    // row 0 = top; stencil, alpha layers and pass state reset as by clear(), depth kept
     void upload(const std::vector<uint8_t>& rgba8) {
         if (rgba8.size() != (size_t)width_ * height_ * 4) throw Error(CRH_ERR_INVALID_ARGUMENT);
         check(crh_frame_upload(handle_, rgba8.data()));
     }
-    std::vector<uint8_t> download() {                 // MSAA resolve + read back: premultiplied RGBA8, row 0 = top
+    std::vector<uint8_t> download() {                 // MSAA resolve + read back: premultiplied 8-bit pixels in the frame's storage order, row 0 = top
         std::vector<uint8_t> out((size_t)width_ * height_ * 4);
         check(crh_frame_download(handle_, out.data()));
         return out;

@@ -419,13 +419,32 @@ impl ColorWrites {
     pub const COLOR: u32 = 7;
     pub const ALL: u32 = 15;
 }
-/// `wgpu::ColorTargetState` without the format (`blend: None` = replace). `constant` stands for `RenderPass::set_blend_constant`, which this
-/// library keeps with the renderer.
+/// `wgpu::TextureFormat` of the colour target. The value is the frame format that keeps f32 colours within a pass; [`TextureFormat::attachment`]
+/// is the one that rounds every write, as a hardware blender does.
+#[repr(u32)]
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum TextureFormat {
+    Rgba8Unorm = ffi::CRH_FORMAT_RGBA8,
+    Bgra8Unorm = ffi::CRH_FORMAT_BGRA8,
+    Rgba8UnormSrgb = ffi::CRH_FORMAT_RGBA8_SRGB,
+    Bgra8UnormSrgb = ffi::CRH_FORMAT_BGRA8_SRGB,
+}
+impl TextureFormat {
+    pub fn attachment(self) -> u32 {
+        match self {
+            TextureFormat::Rgba8Unorm => ffi::CRH_FORMAT_RGBA8_ATTACHMENT,
+            other => other as u32 + 1,
+        }
+    }
+}
+/// `wgpu::ColorTargetState` (`blend: None` = replace). `constant` stands for `RenderPass::set_blend_constant`, which this library keeps with
+/// the renderer. `format` is kept host-side: the format [`Frame::new`] creates (the C ABI names a frame's format at `crh_frame_create_format`).
 #[derive(Clone, Copy, PartialEq, Debug)]
 pub struct ColorTargetState {
     pub blend: Option<BlendState>,
     pub write_mask: u32,
     pub constant: [f32; 4],
+    pub format: TextureFormat,
 }
 impl ColorTargetState {
     fn raw(&self) -> ffi::crh_color_target_state {
@@ -500,17 +519,23 @@ impl Drop for Renderer {
     }
 }
 
-/// The colour attachment (RGBA8, premultiplied) plus the depth / stencil attachments of a render pass: caller-owned in the reference
-/// (`wgpu::TextureView`s handed to `begin_render_pass`), an object of the library here.
+/// The colour attachment (premultiplied; RGBA8, BGRA8 or their sRGB forms) plus the depth / stencil attachments of a render pass: caller-owned in
+/// the reference (`wgpu::TextureView`s handed to `begin_render_pass`), an object of the library here.
 pub struct Frame {
     raw: *mut ffi::crh_frame,
     width: u32,
     height: u32,
 }
 impl Frame {
+    /// In the format of the renderer's `Configuration::blending` (`Rgba8Unorm` without one)
     pub fn new(renderer: &Renderer, width: u32, height: u32) -> Result<Self, Error> {
+        let format = renderer.config.blending.map_or(TextureFormat::Rgba8Unorm, |b| b.format);
+        Self::with_format(renderer, width, height, format as u32)
+    }
+    /// `format`: a `CRH_FORMAT_*` value (`TextureFormat as u32`, `TextureFormat::attachment`, ...)
+    pub fn with_format(renderer: &Renderer, width: u32, height: u32, format: u32) -> Result<Self, Error> {
         let mut raw = ptr::null_mut();
-        status(unsafe { ffi::crh_frame_create(renderer.raw, width, height, &mut raw) })?;
+        status(unsafe { ffi::crh_frame_create_format(renderer.raw, width, height, format, &mut raw) })?;
         Ok(Self { raw, width, height })
     }
     /// `LoadOp::Clear` of colour, depth (1.0) and stencil (examples/showcase/main.rs:217-230)
@@ -528,12 +553,12 @@ impl Frame {
         assert_eq!(depth.len(), (self.width * self.height) as usize);
         status(unsafe { ffi::crh_frame_upload_depth(self.raw, depth.as_ptr()) }).unwrap()
     }
-    /// `LoadOp::Load` of caller content: premultiplied RGBA8, row 0 = top. Stencil, alpha layers and pass state are reset as by `clear`, depth is kept.
+    /// `LoadOp::Load` of caller content: premultiplied 8-bit pixels in the frame's storage order (B G R A for a BGRA format), row 0 = top. Stencil, alpha layers and pass state are reset as by `clear`, depth is kept.
     pub fn upload(&mut self, rgba8: &[u8]) {
         assert_eq!(rgba8.len(), (self.width * self.height * 4) as usize);
         status(unsafe { ffi::crh_frame_upload(self.raw, rgba8.as_ptr() as *const _) }).unwrap()
     }
-    /// Premultiplied RGBA8, row 0 = top
+    /// Premultiplied 8-bit pixels in the frame's storage order, row 0 = top
     pub fn download(&mut self) -> Vec<u8> {
         let mut pixels = vec![0u8; (self.width * self.height * 4) as usize];
         status(unsafe { ffi::crh_frame_download(self.raw, pixels.as_mut_ptr() as *mut _) }).unwrap();
