@@ -888,8 +888,10 @@ size_t grown_pair_bytes(const crh_frame* f, const uint32_t ov[8]) {
 // The pass of this plain frame — 1: boundary edges, per-sample raster kernel; 2: strip triangles; 3: boundary edges, row-span raster kernel
 // (k_raster_rows: msaa 1, no strokes) — and, through `timed`, which trial (candidate 0 edges, 1 triangles, 2 rows) its events belong to, or -1.
 constexpr uint32_t kMovingListRadius = 3u;
+// msaa 2 and 8: always the triangle pass (the edge pass draws 1 and 4 only), whatever the pins ask for — no trial, no shortcut.
 int choose_pass(crh_scene* sc, const crh_frame* f, int* timed, bool* measured) {
     *timed = -1, *measured = false;
+    if (!edge_pass_samples(sc->renderer->config.msaa_sample_count)) return 2;
     const bool rows_eligible = sc->renderer->config.msaa_sample_count == 1 && !sc->has_stroke && getenv("CRH_NO_ROWS") == nullptr;
     if (f->triangle_pass_for == sc && f->triangle_pass_generation == sc->generation) return 2;
     if (getenv("CRH_TRIANGLE_PASS")) return 2;
@@ -1015,11 +1017,14 @@ uint32_t long_lists(const crh_frame* f) {
     return pinned >= 0 ? (uint32_t)(pinned != 0) : (uint32_t)(f->mean_list >= 40u && f->opaque_covers >= n_tiles / 2u);
 }
 
+// The longest tile list the raster kernels sort in LDS: 32 KiB of dynamic LDS per workgroup (kSortBytesMax), a wavefront-private buffer
+// for each of the workgroup's wavefronts (msaa 1: one, 2: two, 4 and 8: four; the edge pass' kernels have the same layouts at 1 and 4)
+uint32_t sort_capacity_limit(uint32_t samples) { return 32768u / (4u * tile_waves(samples)); }
 // the raster kernel sorts a tile's list in LDS: size that buffer (a power of two) from the longest list seen; true when it had to grow
 bool grow_sort_capacity(crh_frame* f, uint32_t longest_list) {
     f->longest_list = std::max(f->longest_list, longest_list);
     if (longest_list <= f->sort_capacity) return false;
-    const uint32_t limit = 32768u / (4u * (f->renderer->config.msaa_sample_count == 4 ? 4u : 1u)); // 32 KiB of dynamic LDS per workgroup (kSortBytesMax)
+    const uint32_t limit = sort_capacity_limit(f->renderer->config.msaa_sample_count);
     uint32_t capacity = f->sort_capacity;
     while (capacity < longest_list && capacity < limit) capacity <<= 1;
     const bool grew = capacity != f->sort_capacity;
@@ -1238,6 +1243,10 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     bool measured = false;
     const int pass = p.general == 0u ? choose_pass(sc, f, &timed, &measured) : 2;
     const bool edges = pass != 2;
+    if (edges ? !edge_pass_samples(r->config.msaa_sample_count) : !triangle_pass_samples(r->config.msaa_sample_count)) { // (cannot happen: choose_pass, crh_renderer_create)
+        g_error = "no raster pass draws this sample count";
+        return CRH_ERR_UNSUPPORTED;
+    }
     // k_raster_rows keeps fill + 65536 * hull in one cell: exact below 2^15 entries per tile. Lists in place grow by half at most between two
     // verified passes, so a frame that has ever shown a list of 16 384 entries keeps the per-sample kernel.
     p.rows = (pass == 3 && f->longest_list < 16384u) ? 1u : 0u;
@@ -1557,7 +1566,7 @@ crh_status settle_frame_cheaply(crh_frame* f) {
     if (set.used) HIP_TRY(hipEventSynchronize(set.flags_ready)); // (behind raster_done: the pixels are written, the pass' flag words are on the host)
     if (!f->check_pending) return CRH_OK;
     const uint32_t* ov = set.flags_host;
-    const uint32_t limit = 32768u / (4u * (r->config.msaa_sample_count == 4 ? 4u : 1u));
+    const uint32_t limit = sort_capacity_limit(r->config.msaa_sample_count);
     const bool sort_too_small = ov[3] > f->sort_capacity && f->sort_capacity < limit;
     if (ov[0] != 0 || ov[5] != 0 || ov[2] != 0 || ov[7] != 0 || sort_too_small || (ov[6] != 0 && f->last_skipped_queue) || (f->last_tess_optimistic && tess_status_overflowed(ov[kTessStatusWord])))
         return settle_frame(f);
@@ -1654,7 +1663,7 @@ crh_status crh_renderer_create_blended(const crh_config* config, const crh_color
     if (!config || !out) return CRH_ERR_INVALID_ARGUMENT;
     // renderer.rs:433-435
     if (config->winding_counter_bits == 0 || config->clip_nesting_counter_bits + config->winding_counter_bits > 8) return CRH_ERR_NUMBER_OF_STENCIL_BITS_IS_UNSUPPORTED;
-    if (!(config->msaa_sample_count == 1 || config->msaa_sample_count == 4)) return CRH_ERR_UNSUPPORTED;
+    if (!triangle_pass_samples(config->msaa_sample_count)) return CRH_ERR_UNSUPPORTED; // 1, 2, 4 and 8 (renderer.rs:490-494: MultisampleState::count)
     if (config->cull_mode > CRH_CULL_BACK || config->depth_compare > CRH_COMPARE_GREATER_EQUAL || config->depth_write_enabled > 1) return CRH_ERR_INVALID_ARGUMENT;
     const crh_color_target_state blend_state = blending ? *blending : over_state();
     {

@@ -499,7 +499,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_tile_walk(SceneDev s, Raste
         // result is bit-identical): the best corner of every edge, the row term of the edge constants, the row half of the box test
         float best_x[3], best_y[3];
         {
-            const float lo = S == 1 ? 0.5f : 0.125f, hi = (float)(kTile - 1) + (S == 1 ? 0.5f : 0.875f);
+            const float lo = sample_lo(S), hi = (float)(kTile - 1) + sample_hi(S); // the extreme sample offsets of the pattern
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 best_x[i] = cov.nay[i] > 0.0f ? hi : lo;
@@ -543,11 +543,14 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_tile_walk(SceneDev s, Raste
 
 // ---------------------------------------------------------------------------------------------- k_raster_tile
 
-// One workgroup per 16x16 tile, lane = (column px, row group rq), ROWS pixel rows per lane:
+// One workgroup per 16x16 tile, lane = (column px, row group rq), ROWS = tile_rows(S) pixel rows per lane:
 //   ROWS == 4 (msaa 1): ONE wavefront per tile; the lane owns the pixels (px, 4b + rq), b = 0..3, so a primitive's entry setup, tile
 //                       constants and kind dispatch are paid once per (tile, primitive) and only the per-sample arithmetic repeats;
+//   ROWS == 2 (msaa 2): two wavefronts per tile, wavefront w owns rows 8w..8w+7 — 2 samples x 2 rows per lane, the same four sample
+//                       states per lane as msaa 1 and 4;
 //   ROWS == 1 (msaa 4): four wavefronts per tile, wavefront w owns rows 4w..4w+3 — 4 samples x 1 row per lane keeps the per-lane state
-//                       (winding + colour of every sample) at the same 20 registers instead of 80.
+//                       (winding + colour of every sample) at the same 20 registers instead of 80;
+//   ROWS == 1 (msaa 8): the msaa 4 layout with eight samples per lane (twice the per-lane state; DESIGN.md §7 has its registers).
 //   OPS == true: the full RenderOperation set — every sample also carries the clip nesting counter and up to kMaxAlphaLayers saved
 //                alphas; OPS == false is the plain Stencil + Color pass at clip depth 0 (what the benchmark runs).
 constexpr int kMaxAlphaLayers = 4;
@@ -556,15 +559,15 @@ constexpr int kMaxAlphaLayers = 4;
 //   BLEND == true (with OPS only): the colour cover blends with the renderer's Configuration::blending (`bf`) instead of premultiplied
 //                "over": the kernel k_raster_blend. Both kernels include the one body, csrc/raster_tile_body.inc.
 template <int S, int ROWS, bool OPS, bool STROKES, bool XFMT = false> // XFMT: the frame formats 3-8 (raster_common.hpp store_px)
-__global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu((OPS || STROKES || S == 4) ? 1 : CRH_TILE_WAVES))) void k_raster_tile(SceneDev s, RasterParams r) {
+__global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu((OPS || STROKES || S >= 4) ? 1 : CRH_TILE_WAVES))) void k_raster_tile(SceneDev s, RasterParams r) {
     constexpr bool BLEND = false;
     const BlendForm bf = {}; // (not read: the blend block is compiled out)
 #include "raster_tile_body.inc"
 }
-// The general variant with the renderer's blend state in place of "over" (Configuration::blending; msaa 1: ROWS 4, msaa 4: ROWS 1)
+// The general variant with the renderer's blend state in place of "over" (Configuration::blending; ROWS = tile_rows(S) as above)
 template <int S, bool STROKES, bool XFMT = false>
-__global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_blend(SceneDev s, RasterParams r, BlendForm bf) {
-    constexpr int ROWS = 4 / S;
+__global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_blend(SceneDev s, RasterParams r, BlendForm bf) {
+    constexpr int ROWS = tile_rows(S);
     constexpr bool OPS = true, BLEND = true;
 #include "raster_tile_body.inc"
 }
@@ -628,30 +631,29 @@ void launch_item_ranges(const SceneDev& s, const RasterParams& r, uint32_t* item
     hipLaunchKernelGGL(k_scan_local, dim3(j.blocks), dim3(256), 0, stream, j);
     hipLaunchKernelGGL(k_scan_add, dim3(j.blocks), dim3(256), 0, stream, j, unused, 0);
 }
-// `after_setup` (optional) is recorded when k_prim_setup, the last reader of the tessellated vertex streams, has been enqueued
-void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_setup) {
-    // tile_cursor, tile_count and the overflow words are adjacent: one memset ([5] belongs to the edge pass (raster_edges.hip); cleared so that the host never sees a stale flag)
-    (void)hipMemsetAsync(r.tile_cursor, 0, sizeof(uint32_t) * 2u * r.n_tiles + 32, stream);
+template <int S>
+static void launch_prim_setup_walk(const SceneDev& s, const RasterParams& r, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_setup) {
     if (r.n_items) {
-        if (samples == 4) {
-            if (r.prim_proj)
-                hipLaunchKernelGGL((k_prim_setup<4, true>), dim3(r.n_items), dim3(64), 0, stream, s, r);
-            else
-                hipLaunchKernelGGL((k_prim_setup<4, false>), dim3(r.n_items), dim3(64), 0, stream, s, r);
-        } else {
-            if (r.prim_proj)
-                hipLaunchKernelGGL((k_prim_setup<1, true>), dim3(r.n_items), dim3(64), 0, stream, s, r);
-            else
-                hipLaunchKernelGGL((k_prim_setup<1, false>), dim3(r.n_items), dim3(64), 0, stream, s, r);
-        }
+        if (r.prim_proj)
+            hipLaunchKernelGGL((k_prim_setup<S, true>), dim3(r.n_items), dim3(64), 0, stream, s, r);
+        else
+            hipLaunchKernelGGL((k_prim_setup<S, false>), dim3(r.n_items), dim3(64), 0, stream, s, r);
     }
     if (after_setup) (void)hipEventRecord(after_setup, stream);
     if (mark) mark(ctx, "raster_prim_setup", 0);
-    if (r.n_items) {
-        if (samples == 4)
-            hipLaunchKernelGGL((k_tile_walk<4, false>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r);
-        else
-            hipLaunchKernelGGL((k_tile_walk<1, false>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r);
+    if (r.n_items) hipLaunchKernelGGL((k_tile_walk<S, false>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r);
+}
+// `after_setup` (optional) is recorded when k_prim_setup, the last reader of the tessellated vertex streams, has been enqueued. The three
+// launchers of the triangle pass launch nothing for a sample count it does not draw (api.hip render_impl refuses such a pass up front).
+void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_setup) {
+    if (!triangle_pass_samples(samples)) return;
+    // tile_cursor, tile_count and the overflow words are adjacent: one memset ([5] belongs to the edge pass (raster_edges.hip); cleared so that the host never sees a stale flag)
+    (void)hipMemsetAsync(r.tile_cursor, 0, sizeof(uint32_t) * 2u * r.n_tiles + 32, stream);
+    switch (samples) {
+        case 1: launch_prim_setup_walk<1>(s, r, stream, mark, ctx, after_setup); break;
+        case 2: launch_prim_setup_walk<2>(s, r, stream, mark, ctx, after_setup); break;
+        case 4: launch_prim_setup_walk<4>(s, r, stream, mark, ctx, after_setup); break;
+        case 8: launch_prim_setup_walk<8>(s, r, stream, mark, ctx, after_setup); break;
     }
     if (mark) mark(ctx, "raster_tile_count", 0);
     const ScanJob j = scan_job(r.tile_count, r.tile_offset, r.scan_scratch, r.n_tiles, r.overflow + 3); // overflow[3] = longest tile list
@@ -663,56 +665,62 @@ void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipS
 void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
                  hipEvent_t after_fill) {
     if (r.n_items) {
-        if (samples == 4)
-            hipLaunchKernelGGL((k_tile_walk<4, true>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r);
-        else
-            hipLaunchKernelGGL((k_tile_walk<1, true>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r);
+        switch (samples) {
+            case 1: hipLaunchKernelGGL((k_tile_walk<1, true>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r); break;
+            case 2: hipLaunchKernelGGL((k_tile_walk<2, true>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r); break;
+            case 4: hipLaunchKernelGGL((k_tile_walk<4, true>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r); break;
+            case 8: hipLaunchKernelGGL((k_tile_walk<8, true>), dim3(r.n_items), dim3(64 * kWalkWaves), 0, stream, s, r); break;
+        }
     }
     if (after_fill) (void)hipEventRecord(after_fill, stream);
     if (mark) mark(ctx, "raster_tile_fill", 0);
 }
+// The raster kernel of msaa S: k_raster_blend for a blend state other than "over" (r.general is set with it), else k_raster_tile, OPS for
+// clip nesting / alpha contexts / depth / projective instances
+template <int S>
+static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_t stream, dim3 grid, bool has_stroke, const BlendForm* blend) {
+    constexpr int ROWS = tile_rows(S);
+    const dim3 block(64u * tile_waves(S));
+    const uint32_t lds = tile_waves(S) * r.sort_capacity * 4u;
+    const bool xfmt = r.format > CRH_FORMAT_RGBA8_ATTACHMENT; // BGRA / sRGB targets: the XFMT instantiations
+#define CRH_LAUNCH_TILE(OPS_, STROKES_)                                                                                   \
+    do {                                                                                                                \
+        if (xfmt)                                                                                                       \
+            hipLaunchKernelGGL((k_raster_tile<S, ROWS, OPS_, STROKES_, true>), grid, block, lds, stream, s, r);        \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_raster_tile<S, ROWS, OPS_, STROKES_>), grid, block, lds, stream, s, r);              \
+    } while (0)
+#define CRH_LAUNCH_BLEND(STROKES_)                                                                                        \
+    do {                                                                                                                \
+        if (xfmt)                                                                                                       \
+            hipLaunchKernelGGL((k_raster_blend<S, STROKES_, true>), grid, block, lds, stream, s, r, *blend);           \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_raster_blend<S, STROKES_>), grid, block, lds, stream, s, r, *blend);                 \
+    } while (0)
+    if (blend) {
+        if (has_stroke) CRH_LAUNCH_BLEND(true); else CRH_LAUNCH_BLEND(false);
+    } else if (r.general) {
+        if (has_stroke) CRH_LAUNCH_TILE(true, true); else CRH_LAUNCH_TILE(true, false);
+    } else {
+        if (has_stroke) CRH_LAUNCH_TILE(false, true); else CRH_LAUNCH_TILE(false, false);
+    }
+#undef CRH_LAUNCH_TILE
+#undef CRH_LAUNCH_BLEND
+}
+// -> RasterVariant (0: nothing launched)
 uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
                    uint64_t raster_bytes, bool has_stroke, const BlendForm* blend) {
     // 8x8-tile blocks, an equal number per XCD (k_raster_tile's tile order)
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;
     const uint32_t blocks = ((r.tiles_x + kBlock - 1u) / kBlock) * ((r.tiles_y + kBlock - 1u) / kBlock);
     const dim3 grid((r.tile_order && r.order_places) ? r.order_places : ((blocks + 7u) / 8u) * kBlock * kBlock * 8u);
-    const bool xfmt = r.format > CRH_FORMAT_RGBA8_ATTACHMENT; // BGRA / sRGB targets: the XFMT instantiations
-#define CRH_LAUNCH_TILE(S_, ROWS_, OPS_, STROKES_)                                                                                                   \
-    do {                                                                                                                                           \
-        if (xfmt)                                                                                                                                  \
-            hipLaunchKernelGGL((k_raster_tile<S_, ROWS_, OPS_, STROKES_, true>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r); \
-        else                                                                                                                                       \
-            hipLaunchKernelGGL((k_raster_tile<S_, ROWS_, OPS_, STROKES_>), grid, dim3(64 * (4 / ROWS_)), (4 / ROWS_) * r.sort_capacity * 4u, stream, s, r); \
-    } while (0)
-#define CRH_LAUNCH_BLEND(S_, STROKES_)                                                                                                   \
-    do {                                                                                                                               \
-        if (xfmt)                                                                                                                      \
-            hipLaunchKernelGGL((k_raster_blend<S_, STROKES_, true>), grid, dim3(64 * S_), S_ * r.sort_capacity * 4u, stream, s, r, *blend); \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((k_raster_blend<S_, STROKES_>), grid, dim3(64 * S_), S_ * r.sort_capacity * 4u, stream, s, r, *blend); \
-    } while (0)
-    if (blend) { // a blend state other than "over" (r.general is set with it)
-        if (samples == 4) {
-            if (has_stroke) CRH_LAUNCH_BLEND(4, true); else CRH_LAUNCH_BLEND(4, false);
-        } else {
-            if (has_stroke) CRH_LAUNCH_BLEND(1, true); else CRH_LAUNCH_BLEND(1, false);
-        }
-    } else if (samples == 4) {
-        if (r.general) { // clip nesting / alpha contexts / depth / projective instances: the OPS variant
-            if (has_stroke) CRH_LAUNCH_TILE(4, 1, true, true); else CRH_LAUNCH_TILE(4, 1, true, false);
-        } else {
-            if (has_stroke) CRH_LAUNCH_TILE(4, 1, false, true); else CRH_LAUNCH_TILE(4, 1, false, false);
-        }
-    } else {
-        if (r.general) { // clip nesting / alpha contexts / depth / projective instances: the OPS variant
-            if (has_stroke) CRH_LAUNCH_TILE(1, 4, true, true); else CRH_LAUNCH_TILE(1, 4, true, false);
-        } else {
-            if (has_stroke) CRH_LAUNCH_TILE(1, 4, false, true); else CRH_LAUNCH_TILE(1, 4, false, false);
-        }
+    switch (samples) {
+        case 1: launch_raster_s<1>(s, r, stream, grid, has_stroke, blend); break;
+        case 2: launch_raster_s<2>(s, r, stream, grid, has_stroke, blend); break;
+        case 4: launch_raster_s<4>(s, r, stream, grid, has_stroke, blend); break;
+        case 8: launch_raster_s<8>(s, r, stream, grid, has_stroke, blend); break;
+        default: return 0u;
     }
-#undef CRH_LAUNCH_TILE
-#undef CRH_LAUNCH_BLEND
     if (mark) mark(ctx, "raster_tiles", raster_bytes);
     return (r.general || blend) ? kRasterOps : kRasterTile;
 }

@@ -19,7 +19,20 @@
 namespace crh {
 
 constexpr int kTile = 16;
-constexpr uint32_t kSortBytesMax = 32u * 1024u; // dynamic LDS per workgroup for the tile sort: 8 192 primitives per tile at msaa 1, 2 048 at msaa 4
+constexpr uint32_t kSortBytesMax = 32u * 1024u; // dynamic LDS per workgroup for the tile sort: 8 192 primitives per tile at msaa 1, 4 096 at msaa 2, 2 048 at msaa 4 / 8
+
+// The standard sample locations (Vulkan standardSampleLocations, the same as D3D's) in 1/16 pixel, x right and y down, in sample-index order
+// (include/contrast_hip.h msaa_sample_count states the table):
+//   msaa 1: (8, 8)   msaa 2: (12, 12), (4, 4)   msaa 4: (6, 2), (14, 6), (2, 10), (10, 14)
+//   msaa 8: (9, 5), (7, 11), (13, 9), (5, 3), (3, 13), (1, 7), (11, 15), (15, 1)
+// Packed four bits per sample, sample k in bits 4k..4k+3 (folds to constants in the unrolled loops over k).
+CRH_D constexpr uint32_t sample_pattern_x(int samples) { return samples == 2 ? 0x4Cu : (samples == 4 ? 0xA2E6u : (samples == 8 ? 0xFB135D79u : 0x8u)); }
+CRH_D constexpr uint32_t sample_pattern_y(int samples) { return samples == 2 ? 0x4Cu : (samples == 4 ? 0xEA62u : (samples == 8 ? 0x1F7D39B5u : 0x8u)); }
+CRH_D constexpr float sample_dx(int samples, int k) { return (float)((sample_pattern_x(samples) >> (4 * k)) & 15u) * 0.0625f; }
+CRH_D constexpr float sample_dy(int samples, int k) { return (float)((sample_pattern_y(samples) >> (4 * k)) & 15u) * 0.0625f; }
+// The extreme offsets of the pattern (both axes alike): the corners of a tile's sample box in the tile tests
+CRH_D constexpr float sample_lo(int samples) { return samples == 2 ? 0.25f : (samples == 4 ? 0.125f : (samples == 8 ? 0.0625f : 0.5f)); }
+CRH_D constexpr float sample_hi(int samples) { return samples == 2 ? 0.75f : (samples == 4 ? 0.875f : (samples == 8 ? 0.9375f : 0.5f)); }
 
 CRH_D float2 to_framebuffer(const float* m, float w, float h, float x, float y) { // oracle/raster.hpp to_framebuffer
     const float cx = (m[0] * x + m[4] * y) + m[12];

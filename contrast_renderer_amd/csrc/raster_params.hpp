@@ -12,6 +12,15 @@ namespace crh {
 struct PrimRec;
 struct PrimProj;
 
+// The sample counts the triangle pass draws (Configuration::msaa_sample_count). The edge pass (raster_edges.hip) draws 1 and 4 only: its
+// 16-bit row masks and 4x4 sample transposes are built for those two layouts.
+constexpr bool triangle_pass_samples(uint32_t samples) { return samples == 1u || samples == 2u || samples == 4u || samples == 8u; }
+constexpr bool edge_pass_samples(uint32_t samples) { return samples == 1u || samples == 4u; }
+// Pixel rows per lane of the triangle pass' raster kernels, whose workgroup is 4 / ROWS wavefronts per 16x16 tile. msaa 1: four rows x one
+// sample, msaa 2: two rows x two samples, msaa 4: one row x four samples, msaa 8: one row x eight samples.
+constexpr int tile_rows(int samples) { return samples >= 4 ? 1 : 4 / samples; }
+constexpr uint32_t tile_waves(uint32_t samples) { return 4u / (uint32_t)tile_rows((int)samples); }
+
 // One Shape::render(Stencil) optionally followed by one cover operation of the same Shape and instance (the host merges adjacent
 // draws of a recorded pass); the unit the setup and binning kernels are launched over.
 struct DrawItem {

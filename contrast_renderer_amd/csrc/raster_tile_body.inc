@@ -22,20 +22,20 @@
     uint32_t* __restrict__ keys = sort_buffer + wave * r.sort_capacity;
     const uint32_t px = lane & 15u, rq = lane >> 4;
     const uint32_t first_row = 4u * ROWS * wave; // local row b of this lane is pixel row first_row + 4b + rq (ROWS == 4: one wavefront, wave == 0)
+    static_assert(ROWS == tile_rows(S), "the lane layout of msaa S");
     const uint32_t gx = tx * kTile + px;
     const float tx0 = (float)(tx * kTile), ty0 = (float)(ty * kTile);
     const int tpx = (int)(tx * kTile), tpy = (int)(ty * kTile);
 
-    float sx[S], sy0[S]; // sample positions of the lane's first row; local row b adds 4b (exact in f32)
-    if (S == 1) {
-        sx[0] = (float)px + 0.5f;
-        sy0[0] = (float)(first_row + rq) + 0.5f;
+    float sx[S], sy0[S]; // sample positions of the lane's first row (the pattern of msaa S, raster_common.hpp); local row b adds 4b (exact in f32)
+    if (S == 1) { // (written out: the one-trip loop lets the msaa 1 kernels schedule these two adds the other way round)
+        sx[0] = (float)px + sample_dx(S, 0);
+        sy0[0] = (float)(first_row + rq) + sample_dy(S, 0);
     } else {
-        const float ox[4] = {0.375f, 0.875f, 0.125f, 0.625f}, oy[4] = {0.125f, 0.375f, 0.625f, 0.875f};
 #pragma unroll
         for (int k = 0; k < S; ++k) {
-            sx[k] = (float)px + ox[k & 3];
-            sy0[k] = (float)(first_row + rq) + oy[k & 3];
+            sx[k] = (float)px + sample_dx(S, k);
+            sy0[k] = (float)(first_row + rq) + sample_dy(S, k);
         }
     }
     const uint32_t row_shift = first_row + rq; // the lane's row b is bit row_shift + 4b of a 16-bit row mask

@@ -147,7 +147,7 @@ class ColorTargetState:
 
 @dataclass
 class Configuration:  # renderer.rs:380-405 (fields that change results on this path)
-    msaa_sample_count: int = 1
+    msaa_sample_count: int = 1  # 1, 2, 4 or 8, standard sample locations (include/contrast_hip.h); any other count: ContrastError (CRH_ERR_UNSUPPORTED)
     clip_nesting_counter_bits: int = 4
     winding_counter_bits: int = 4
     alpha_layer_count: int = 0

@@ -138,8 +138,16 @@ typedef enum crh_compare { /* wgpu::CompareFunction of `fragment depth  OP  stor
     CRH_COMPARE_NOT_EQUAL = 6,
     CRH_COMPARE_GREATER_EQUAL = 7
 } crh_compare;
+/* msaa_sample_count: 1, 2, 4 or 8 (wgpu::MultisampleState::count, renderer.rs:490-494); anything else is CRH_ERR_UNSUPPORTED. The sample
+ * locations are the standard ones (Vulkan standardSampleLocations = D3D), in 1/16 pixel, x right and y down, in sample-index order — the order
+ * of the per-sample data, e.g. crh_frame_download_depth's [height][width][msaa]:
+ *   1: (8, 8)
+ *   2: (12, 12), (4, 4)
+ *   4: (6, 2), (14, 6), (2, 10), (10, 14)
+ *   8: (9, 5), (7, 11), (13, 9), (5, 3), (3, 13), (1, 7), (11, 15), (15, 1)
+ * The resolve is the box average of a pixel's samples, summed in sample-index order. */
 typedef struct crh_config {
-    uint32_t msaa_sample_count;         /* 1 or 4 */
+    uint32_t msaa_sample_count;         /* 1, 2, 4 or 8 (the table above) */
     uint32_t clip_nesting_counter_bits; /* validated as in renderer.rs:433 */
     uint32_t winding_counter_bits;      /* >= 1, sum <= 8 */
     uint32_t alpha_layer_count;         /* <= 4; layers of the alpha-context operations (renderer.rs:403-404) */

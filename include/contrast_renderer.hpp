@@ -457,6 +457,7 @@ struct ColorTargetState {
 };
 
 struct Configuration { // renderer.rs:380-405, the fields that change results on this path
+    // msaa_sample_count: 1, 2, 4 or 8 with the standard sample locations (contrast_hip.h crh_config); any other count: CRH_ERR_UNSUPPORTED
     uint32_t msaa_sample_count = 1, clip_nesting_counter_bits = 4, winding_counter_bits = 4, alpha_layer_count = 0;
     // of the colour cover only, as in the reference (renderer.rs:743-745)
     crh_cull cull_mode = CRH_CULL_NONE;              // Option<wgpu::Face>

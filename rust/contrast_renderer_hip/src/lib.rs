@@ -455,6 +455,8 @@ impl ColorTargetState {
 
 /// renderer.rs:380-405. `blending` = the colour cover's blend state (None: the premultiplied "over" of examples/showcase/main.rs:32-43);
 /// `depth_stencil_format` and `color_attachment_in_stencil_pass` are wgpu details without meaning for a compute rasterizer.
+/// `msaa_sample_count`: 1, 2, 4 or 8, at the standard sample locations (Vulkan / D3D, listed in include/contrast_hip.h); the library
+/// reports CRH_ERR_UNSUPPORTED for any other count (a panic here, as for every status that is not a reference error).
 #[derive(Clone, Copy, Debug)]
 pub struct Configuration {
     pub cull_mode: Option<Face>,
