@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ("tessellate.hip", "raster.hip", "raster_edges.hip", "api.hip", "comm.hip", "text.cpp", "path.cpp")  # text.cpp / path.cpp: host-only (text.rs, path.rs:639-708)
-HEADERS = ("ga.hpp", "fill.hpp", "stroke.hpp", "scene.hpp", "raster_params.hpp", "raster_common.hpp", "raster_tile_body.inc", "srgb_tables.h", "../../include/contrast_hip.h", "../../include/crh_fmath.h")
+HEADERS = ("ga.hpp", "fill.hpp", "stroke.hpp", "scene.hpp", "raster_params.hpp", "raster_common.hpp", "raster_tile_list.hpp", "raster_tile_body.inc", "launch.hpp", "srgb_tables.h", "../../include/contrast_hip.h", "../../include/crh_fmath.h")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical"]
 # Per-file flags. raster_edges.hip without LLVM's SLP vectorizer (round 6): it packs pairs of independent f32 operations of the per-sample code into
 # v_pk_* instructions, whose operands are register PAIRS — lane-invariant values (sample positions, the tile's origin) end up duplicated in pairs that live

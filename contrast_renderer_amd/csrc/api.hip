@@ -13,37 +13,9 @@
 #include <string>
 #include <vector>
 
+#include "launch.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
-
-namespace crh {
-typedef void (*MarkFn)(void*, const char*, uint64_t);
-void launch_tessellate(const SceneDev& s, hipStream_t stream, MarkFn mark, void* ctx, const uint64_t bytes[4], bool has_stroke, bool need_totals);
-void launch_emit(const SceneDev& s, hipStream_t stream, MarkFn mark, void* ctx, const uint64_t bytes[4], bool has_stroke, bool big_shapes, const uint32_t* hull_queued);
-void launch_build_elements(const UploadBuild& u, hipStream_t stream);
-void launch_prim_ranges(const SceneDev& s, uint32_t* shape_ncand, uint32_t* shape_prim_begin, uint32_t* scratch, hipStream_t stream);
-void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup);
-void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_fill);
-uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke,
-                       const BlendForm* blend); // -> RasterVariant; blend: nullptr = premultiplied "over", otherwise k_raster_blend
-void launch_item_ranges(const SceneDev& s, const RasterParams& r, uint32_t* item_ncand, uint32_t* item_prim_begin, uint32_t* scratch, hipStream_t stream);
-void launch_composite(const uint8_t* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, uint8_t* dst, hipStream_t stream);
-void launch_state_colors_from_image(const RasterParams& r, uint32_t samples, hipStream_t stream);
-// raster_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop, binned in one traversal
-void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);
-uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin); // -> BinRoute | items per workgroup << 16
-void launch_scatter(const RasterParams& r, hipStream_t stream, MarkFn mark, void* ctx);
-void launch_shape_bounds(const SceneDev& s, float* bounds, hipStream_t stream);
-void launch_slab_items(const RasterParams& r, uint8_t* elsewhere, hipStream_t stream);
-void launch_plain_ranges(const SceneDev& s, uint32_t* shape_ncand, uint32_t* shape_prim_begin, uint32_t* shape_nslots, uint32_t* shape_slot_begin, uint32_t* scratch0, uint32_t* scratch1, hipStream_t stream);
-bool bin_itemwise(const RasterParams& r);
-void flat_batches(const uint32_t* cost, uint32_t n_items, std::vector<uint32_t>& runs);
-void flat_batch_limits(uint32_t n_items, uint32_t limits[4]);
-void launch_tile_bases(const uint32_t* tile_count, uint32_t* caps, uint32_t* tile_base, uint32_t* scratch, uint32_t n_tiles, uint32_t tiles_x, uint32_t radius, hipStream_t stream);
-uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke); // -> RasterVariant
-void launch_fmath(int fn, const float* a, const float* b, float* out, uint64_t n, hipStream_t stream);
-void launch_selftest_srgb(const float* x, uint8_t* codes, uint64_t n, float* decoded, hipStream_t stream); // raster.hip
-} // namespace crh
 
 using namespace crh;
 

@@ -21,7 +21,8 @@
 //
 // Roofline note: algorithmic traffic = emitted vertices read once + W*H*4 bytes written once; the raster kernel is VALU-issue bound
 // (edge functions per sample), the others latency bound; there is no GEMM shape for MFMA anywhere.
-#include "raster_common.hpp"
+#include "launch.hpp"
+#include "raster_tile_list.hpp"
 
 namespace crh {
 
@@ -632,7 +633,7 @@ void launch_item_ranges(const SceneDev& s, const RasterParams& r, uint32_t* item
     hipLaunchKernelGGL(k_scan_add, dim3(j.blocks), dim3(256), 0, stream, j, unused, 0);
 }
 template <int S>
-static void launch_prim_setup_walk(const SceneDev& s, const RasterParams& r, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_setup) {
+static void launch_prim_setup_walk(const SceneDev& s, const RasterParams& r, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup) {
     if (r.n_items) {
         if (r.prim_proj)
             hipLaunchKernelGGL((k_prim_setup<S, true>), dim3(r.n_items), dim3(64), 0, stream, s, r);
@@ -645,7 +646,7 @@ static void launch_prim_setup_walk(const SceneDev& s, const RasterParams& r, hip
 }
 // `after_setup` (optional) is recorded when k_prim_setup, the last reader of the tessellated vertex streams, has been enqueued. The three
 // launchers of the triangle pass launch nothing for a sample count it does not draw (api.hip render_impl refuses such a pass up front).
-void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_setup) {
+void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup) {
     if (!triangle_pass_samples(samples)) return;
     // tile_cursor, tile_count and the overflow words are adjacent: one memset ([5] belongs to the edge pass (raster_edges.hip); cleared so that the host never sees a stale flag)
     (void)hipMemsetAsync(r.tile_cursor, 0, sizeof(uint32_t) * 2u * r.n_tiles + 32, stream);
@@ -662,7 +663,7 @@ void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipS
     if (mark) mark(ctx, "raster_tile_scan", 0);
 }
 // `after_fill` (optional) is recorded when the fill pass, the last reader of the per-item primitive ranges, has been enqueued
-void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
+void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx,
                  hipEvent_t after_fill) {
     if (r.n_items) {
         switch (samples) {
@@ -708,7 +709,7 @@ static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_
 #undef CRH_LAUNCH_BLEND
 }
 // -> RasterVariant (0: nothing launched)
-uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
+uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx,
                    uint64_t raster_bytes, bool has_stroke, const BlendForm* blend) {
     // 8x8-tile blocks, an equal number per XCD (k_raster_tile's tile order)
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;

@@ -28,11 +28,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "raster_common.hpp"
+#include "launch.hpp"
+#include "raster_tile_list.hpp"
 
 namespace crh {
-
-void launch_scan_tiles(const RasterParams& r, hipStream_t stream); // raster.hip: exclusive scan of tile_count -> tile_offset, pair total, longest list
 
 constexpr uint32_t EK_EDGE = 0, EK_SYNTH = 7, EK_COVER_TRI = 8; // kinds 1..6 = KIND_IQ .. KIND_JOINT as in raster_common.hpp (flags bits 4-7)
 // Two refinements of a COVER entry's code, decided by the bin kernel per (item, tile):
@@ -1647,6 +1646,50 @@ __global__ __launch_bounds__(256) void k_scatter(RasterParams r) {
     r.tile_list[r.tile_offset[r.pair_tile[i]] + r.pair_pos[i]] = r.pair_key[i];
 }
 
+// The late start (see "Occlusion" in k_raster_edges) of a list longer than one chunk is found before the walk: the chunks' keys and the first word
+// of their slots from the END of the list — X, the last opaque cover over the whole tile none of whose item's triangles are in the
+// list (keys ascend: a binary search), then R, the last cover before X that resets the whole tile. The walk begins behind R: walk_from,
+// and checks at X that it overwrote every sample: verify_entry (absolute positions in the list; unchanged when there is no such pair).
+// The sorted keys are in `keys` (LDS) or — sorted_in_place — in `segment`. (Device only, not CRH_D: ballots and lane reads have no host form.)
+__device__ __forceinline__ void find_late_start(const uint8_t* slots, const uint32_t* segment, const uint32_t* keys, bool sorted_in_place, uint32_t n, uint32_t lane, uint32_t& walk_from, uint32_t& verify_entry) {
+    auto key_of = [&](uint32_t i) -> uint32_t { return sorted_in_place ? __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : keys[i]; };
+    uint32_t x_at = 0xFFFFFFFFu;
+    for (uint32_t c0 = ((n - 1u) >> 6) << 6;; c0 -= 64u) {
+        const uint32_t k = c0 + lane < n ? key_of(c0 + lane) : 0xFFFFFFFFu;
+        uint32_t code = 0;
+        if (c0 + lane < n) {
+            const uint32_t flags = *reinterpret_cast<const uint32_t*>(slots + (size_t)k * 32u);
+            code = ((flags >> 4) & 15u) == EK_SYNTH ? (flags >> 8) & 31u : 0u;
+        }
+        unsigned long long resets = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverHull);
+        if (x_at == 0xFFFFFFFFu) {
+            unsigned long long candidates = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverOpaque);
+            while (candidates) {
+                const uint32_t at = 63u - (uint32_t)__builtin_clzll(candidates);
+                const SynthRec sr = load_uniform(reinterpret_cast<const SynthRec*>(slots + (size_t)__builtin_amdgcn_readlane(k, at) * 32u));
+                uint32_t lo = 0, hi = n; // the number of keys below the item's synthetic slots
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (key_of(mid) < sr.synth_a) lo = mid + 1u;
+                    else hi = mid;
+                }
+                if (lo == 0u || key_of(lo - 1u) < sr.first_slot) {
+                    x_at = c0 + at;
+                    resets &= (1ull << at) - 1ull;
+                    break;
+                }
+                candidates &= ~(1ull << at);
+            }
+        }
+        if (x_at != 0xFFFFFFFFu && resets) {
+            walk_from = c0 + 64u - (uint32_t)__builtin_clzll(resets); // behind the last whole-tile reset before X
+            verify_entry = x_at;
+            break;
+        }
+        if (c0 == 0u) break;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- k_raster_edges
 // A 16-bit row mask -> the lane masks of the lane's sample slots. Lane (px, rq) owns row bit rq + 4b in slot b (msaa 1) or 4 rq + q in
 // slot q (msaa 4); a slot's lane mask repeats each of its four row bits over a 16-lane group. Scalar unit only: s_bitreplicate doubles
@@ -1706,16 +1749,8 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
     constexpr bool kColLds = S == 4;
     constexpr int kColLdsSamples = CRH_COL_LDS_SAMPLES;
     __shared__ float4 col_lds[kColLds ? 4 / ROWS : 1][kColLds ? ROWS * kColLdsSamples * 64 : 1];
-    constexpr uint32_t kB = CRH_XCD_BLOCK_LOG2, kBlock = 1u << kB;
-    const uint32_t turn = bid >> 3;
-    const uint32_t blocks_x = (r.tiles_x + kBlock - 1u) >> kB, block = (turn >> (2u * kB)) * 8u + (bid & 7u);
-    uint32_t tx = (block % blocks_x) * kBlock + (turn & (kBlock - 1u)), ty = (block / blocks_x) * kBlock + ((turn >> kB) & (kBlock - 1u));
-    if (r.tile_order) { // the host's order for this frame: every XCD's heavy tiles first (api.hip order_tiles_heavy_first)
-        const uint32_t mine = r.tile_order[bid];
-        if (mine == 0xFFFFFFFFu) return;
-        ty = mine / r.tiles_x, tx = mine - ty * r.tiles_x;
-    }
-    if (tx >= r.tiles_x || ty >= r.tiles_y || ty < r.slab_ty0 || ty >= r.slab_ty1) return; // (beyond the frame, or not in this pass' slab of tile rows)
+    uint32_t tx, ty;
+    if (!tile_of_place(r, bid, tx, ty)) return;
     const uint32_t tile = ty * r.tiles_x + tx;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t* __restrict__ keys = sort_buffer + wave * r.sort_capacity;
@@ -1780,15 +1815,9 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
         }
     };
     col_keep();
-    const uint32_t list_begin = r.direct ? r.tile_base[tile] : r.tile_offset[tile];
-    uint32_t n = (r.overflow[0] | r.overflow[5]) ? 0u : (r.direct ? r.tile_count[tile] : r.tile_offset[tile + 1] - list_begin);
     constexpr uint32_t kLdsSortMax = kSortBytesMax / (4u * (4u / ROWS));
-    if (n > r.sort_capacity && n <= kLdsSortMax) { // the host grows the sort buffer (overflow[3] = the longest list) and runs the frame again
-        if (r.direct && threadIdx.x == 0u) atomicMax(&r.overflow[3], n); // (otherwise the scan of the counts has published it)
-        n = 0;
-    } else if (n > kLdsSortMax && r.direct && threadIdx.x == 0u) {
-        atomicMax(&r.overflow[3], n); // (sorted in place below; the host keeps the longest list it has heard of: crh_frame::longest_list)
-    }
+    uint32_t list_begin, n;
+    tile_list_range(r, tile, kLdsSortMax, list_begin, n);
 #ifdef CRH_ABLATE
     if (r.debug & 64u) n = 0;
     if ((r.debug & 524288u) && n > 64u) n = 0;   // only the lists that fit one chunk
@@ -1797,73 +1826,13 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
     uint32_t my_key = 0xFFFFFFFFu;
     const bool sorted_in_place = n > kLdsSortMax;
     uint32_t* const segment = r.tile_list + list_begin;
-    if (sorted_in_place) { // as raster.hip: a normalised bitonic network over the tile's segment of the list, in global memory
-        const uint32_t tid = threadIdx.x, n_threads = 64u * (4u / ROWS);
-        uint32_t padded = 1;
-        while (padded < n) padded <<= 1;
-        auto exchange = [&](uint32_t i, uint32_t partner) {
-            if (partner < n) {
-                const uint32_t a = __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t b = __hip_atomic_load(segment + partner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (a > b) {
-                    __hip_atomic_store(segment + i, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(segment + partner, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        };
-        for (uint32_t kk = 2; kk <= padded; kk <<= 1) {
-            const uint32_t half = kk >> 1;
-            for (uint32_t p = tid; p < (padded >> 1); p += n_threads) {
-                const uint32_t blk = p / half, t = p - blk * half;
-                exchange(blk * kk + t, blk * kk + kk - 1u - t);
-            }
-            __threadfence();
-            __syncthreads();
-            for (uint32_t j = half >> 1; j > 0; j >>= 1) {
-                for (uint32_t p = tid; p < (padded >> 1); p += n_threads) {
-                    const uint32_t i = 2u * j * (p / j) + (p % j);
-                    exchange(i, i + j);
-                }
-                __threadfence();
-                __syncthreads();
-            }
-        }
+    if (sorted_in_place) {
+        sort_list_in_place(segment, n, threadIdx.x, 64u * (4u / ROWS));
     } else if (n <= 64u) {
         if (lane < n) my_key = r.tile_list[list_begin + lane];
-        if (n > 1u) {
-            const uint32_t depth = n <= 8u ? 8u : (n <= 16u ? 16u : (n <= 32u ? 32u : 64u)); // a network as deep as the list needs (the keys sit in the leading lanes)
-#pragma unroll
-            for (uint32_t kk = 2; kk <= 64u; kk <<= 1) {
-                if (kk > depth) break;
-#pragma unroll
-                for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-                    const uint32_t other = __shfl_xor(my_key, j, 64);
-                    const bool keep_min = ((lane & j) == 0) == ((lane & kk) == 0);
-                    my_key = keep_min ? min(my_key, other) : max(my_key, other);
-                }
-            }
-        }
+        if (n > 1u) my_key = sort_keys_in_lanes(my_key, lane, n <= 8u ? 8u : (n <= 16u ? 16u : (n <= 32u ? 32u : 64u))); // a network as deep as the list needs (the keys sit in the leading lanes)
     } else {
-        uint32_t padded = 128;
-        while (padded < n) padded <<= 1;
-        for (uint32_t i = lane; i < padded; i += 64u) keys[i] = i < n ? r.tile_list[list_begin + i] : 0xFFFFFFFFu;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t kk = 2; kk <= padded; kk <<= 1)
-            for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-                for (uint32_t i = lane; i < padded; i += 64u) {
-                    const uint32_t partner = i ^ j;
-                    if (partner > i) {
-                        const uint32_t a = keys[i], b = keys[partner];
-                        if (((i & kk) == 0) ? (a > b) : (a < b)) {
-                            keys[i] = b;
-                            keys[partner] = a;
-                        }
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
+        sort_list_in_lds(keys, segment, n, lane);
     }
 
     const uint8_t* slots = r.slots;
@@ -1874,49 +1843,9 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
     const float ry_row = lane == 16u ? (S == 1 ? 0.5f : 0.125f)
                                      : (S == 1 ? (float)row_j + 0.5f : (float)(first_row + (row_j >> 2)) + ((float)(row_j & 3u) * 0.25f + 0.125f));
     const float sy_row = ty0 + ry_row;
-    // The late start (see "Occlusion" below) of a list longer than one chunk is found before the walk: the chunks' keys and the first word
-    // of their slots from the END of the list — X, the last opaque cover over the whole tile none of whose item's triangles are in the
-    // list (keys ascend: a binary search), then R, the last cover before X that resets the whole tile. The walk begins behind R.
-    auto key_of = [&](uint32_t i) -> uint32_t { return sorted_in_place ? __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : keys[i]; };
     uint32_t walk_from = 0, verify_entry = 0xFFFFFFFFu; // absolute positions in the list
     constexpr bool kLongLateStart = LONG; // (a variant of its own: compiled into the kernel of the 10 000 path scene — few tiles beyond one chunk — it cost 8 %: 0.234 -> 0.255 ms)
-    if (kLongLateStart && n > 64u && !r.load_existing) {
-        uint32_t x_at = 0xFFFFFFFFu;
-        for (uint32_t c0 = ((n - 1u) >> 6) << 6;; c0 -= 64u) {
-            const uint32_t k = c0 + lane < n ? key_of(c0 + lane) : 0xFFFFFFFFu;
-            uint32_t code = 0;
-            if (c0 + lane < n) {
-                const uint32_t flags = *reinterpret_cast<const uint32_t*>(slots + (size_t)k * 32u);
-                code = ((flags >> 4) & 15u) == EK_SYNTH ? (flags >> 8) & 31u : 0u;
-            }
-            unsigned long long resets = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverHull);
-            if (x_at == 0xFFFFFFFFu) {
-                unsigned long long candidates = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverOpaque);
-                while (candidates) {
-                    const uint32_t at = 63u - (uint32_t)__builtin_clzll(candidates);
-                    const SynthRec sr = load_uniform(reinterpret_cast<const SynthRec*>(slots + (size_t)__builtin_amdgcn_readlane(k, at) * 32u));
-                    uint32_t lo = 0, hi = n; // the number of keys below the item's synthetic slots
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (key_of(mid) < sr.synth_a) lo = mid + 1u;
-                        else hi = mid;
-                    }
-                    if (lo == 0u || key_of(lo - 1u) < sr.first_slot) {
-                        x_at = c0 + at;
-                        resets &= (1ull << at) - 1ull;
-                        break;
-                    }
-                    candidates &= ~(1ull << at);
-                }
-            }
-            if (x_at != 0xFFFFFFFFu && resets) {
-                walk_from = c0 + 64u - (uint32_t)__builtin_clzll(resets); // behind the last whole-tile reset before X
-                verify_entry = x_at;
-                break;
-            }
-            if (c0 == 0u) break;
-        }
-    }
+    if (kLongLateStart && n > 64u && !r.load_existing) find_late_start(slots, segment, keys, sorted_in_place, n, lane, walk_from, verify_entry);
     uint32_t first_j = walk_from & 63u;
     bool again_from_the_top = false;
     for (uint32_t q0 = kLongLateStart ? walk_from & ~63u : 0u; q0 < n; q0 += 64u) {
@@ -2407,77 +2336,6 @@ CRH_D int sub_lane_bit(int v, unsigned long long mask) { // v - (this lane's bit
 #endif
     return v;
 }
-// One compare-exchange step of a sorting network on the 64 lanes' u32 keys, partner inside the 16-lane row: the partner's key comes in as a DPP
-// operand of v_min_u32 / v_max_u32 themselves (no LDS permute, no address arithmetic); keep_min: the lanes that keep the smaller key.
-// (s_nop 1: a DPP operand written by the VALU instruction in front needs two wait states, and the assembler does not see into the asm.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define CRH_CX_DPP(key_, keep_min_, ctrl_)                                                                                                  \
-    {                                                                                                                                       \
-        uint32_t lo_, hi_;                                                                                                                  \
-        asm("s_nop 1\n\tv_min_u32_dpp %0, %2, %2 " ctrl_ " row_mask:0xf bank_mask:0xf\n\tv_max_u32_dpp %1, %2, %2 " ctrl_ " row_mask:0xf bank_mask:0xf" \
-            : "=&v"(lo_), "=&v"(hi_)                                                                                                        \
-            : "v"(key_));                                                                                                                   \
-        key_ = __builtin_amdgcn_inverse_ballot_w64(keep_min_) ? lo_ : hi_;                                                                   \
-    }
-#else
-#define CRH_CX_DPP(key_, keep_min_, ctrl_) { (void)(keep_min_); }
-#endif
-// ... partner = lane ^ 4 = quad mirror of the half-row mirror: one DPP move, then as above
-CRH_D uint32_t cx_xor4(uint32_t key, unsigned long long keep_min) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)key, 0x141, 0xF, 0xF, false); // row_half_mirror
-    uint32_t lo, hi;
-    asm("s_nop 1\n\tv_min_u32_dpp %0, %2, %3 quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf\n\tv_max_u32_dpp %1, %2, %3 quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf"
-        : "=&v"(lo), "=&v"(hi)
-        : "v"(t), "v"(key));
-    return __builtin_amdgcn_inverse_ballot_w64(keep_min) ? lo : hi;
-#else
-    return key;
-#endif
-}
-// ... partner in another row (lane ^ 16, ^ 31, ^ 32, ^ 63): through the LDS crossbar
-CRH_D uint32_t cx_far(uint32_t key, uint32_t lane, uint32_t xor_mask, unsigned long long keep_min) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t other = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane ^ xor_mask) << 2), (int)key);
-    return __builtin_amdgcn_inverse_ballot_w64(keep_min) ? min(key, other) : max(key, other);
-#else
-    return key;
-#endif
-}
-// The normalised bitonic network (every merge begins with a mirror step, so all exchanges keep the minimum in the lower lane) over the first
-// `depth` lanes — 8, 16, 32 or 64 (wave uniform) —, ascending; lanes without a key hold 0xFFFFFFFF.
-CRH_D uint32_t sort_keys_in_lanes(uint32_t key, uint32_t lane, uint32_t depth) {
-    constexpr unsigned long long kBit0 = 0x5555555555555555ull, kBit1 = 0x3333333333333333ull, kBit2 = 0x0F0F0F0F0F0F0F0Full, kBit3 = 0x00FF00FF00FF00FFull,
-                                 kBit4 = 0x0000FFFF0000FFFFull, kBit5 = 0x00000000FFFFFFFFull; // lanes whose bit b is clear
-    CRH_CX_DPP(key, kBit0, "quad_perm:[1,0,3,2]") // kk = 2
-    CRH_CX_DPP(key, kBit1, "quad_perm:[3,2,1,0]") // kk = 4: mirror, 1
-    CRH_CX_DPP(key, kBit0, "quad_perm:[1,0,3,2]")
-    CRH_CX_DPP(key, kBit2, "row_half_mirror")     // kk = 8: mirror, 2, 1
-    CRH_CX_DPP(key, kBit1, "quad_perm:[2,3,0,1]")
-    CRH_CX_DPP(key, kBit0, "quad_perm:[1,0,3,2]")
-    if (depth > 8u) {
-        CRH_CX_DPP(key, kBit3, "row_mirror")      // kk = 16: mirror, 4, 2, 1
-        key = cx_xor4(key, kBit2);
-        CRH_CX_DPP(key, kBit1, "quad_perm:[2,3,0,1]")
-        CRH_CX_DPP(key, kBit0, "quad_perm:[1,0,3,2]")
-    }
-    if (depth > 16u) {
-        key = cx_far(key, lane, 31u, kBit4);      // kk = 32: mirror, 8, 4, 2, 1
-        CRH_CX_DPP(key, kBit3, "row_ror:8")
-        key = cx_xor4(key, kBit2);
-        CRH_CX_DPP(key, kBit1, "quad_perm:[2,3,0,1]")
-        CRH_CX_DPP(key, kBit0, "quad_perm:[1,0,3,2]")
-    }
-    if (depth > 32u) {
-        key = cx_far(key, lane, 63u, kBit5);      // kk = 64: mirror, 16, 8, 4, 2, 1
-        key = cx_far(key, lane, 16u, kBit4);
-        CRH_CX_DPP(key, kBit3, "row_ror:8")
-        key = cx_xor4(key, kBit2);
-        CRH_CX_DPP(key, kBit1, "quad_perm:[2,3,0,1]")
-        CRH_CX_DPP(key, kBit0, "quad_perm:[1,0,3,2]")
-    }
-    return key;
-}
 // "over" on the lanes of mask[b] only (sample row b), the others keep their colour: the blends run under the masks as the EXEC mask — no
 // select per channel —, dst = src + dst * (1 - alpha) as a multiply and an add (Rust does not contract), or dst = src for an opaque source.
 // One asm statement for the four rows: the colour registers are updated in place (per row, the compiler moved them to temporaries and back).
@@ -2573,16 +2431,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
     const uint32_t bid = blockIdx.x; // the workgroup's place in the frame's tile order
     extern __shared__ uint32_t sort_buffer[];
     __shared__ float4 entry_buffer[64 * 3];
-    constexpr uint32_t kB = CRH_XCD_BLOCK_LOG2, kBlock = 1u << kB;
-    const uint32_t turn = bid >> 3;
-    const uint32_t blocks_x = (r.tiles_x + kBlock - 1u) >> kB, block = (turn >> (2u * kB)) * 8u + (bid & 7u);
-    uint32_t tx = (block % blocks_x) * kBlock + (turn & (kBlock - 1u)), ty = (block / blocks_x) * kBlock + ((turn >> kB) & (kBlock - 1u));
-    if (r.tile_order) { // the host's order for this frame: every XCD's heavy tiles first (api.hip order_tiles_heavy_first)
-        const uint32_t mine = r.tile_order[bid];
-        if (mine == 0xFFFFFFFFu) return;
-        ty = mine / r.tiles_x, tx = mine - ty * r.tiles_x;
-    }
-    if (tx >= r.tiles_x || ty >= r.tiles_y || ty < r.slab_ty0 || ty >= r.slab_ty1) return; // (beyond the frame, or not in this pass' slab of tile rows)
+    uint32_t tx, ty;
+    if (!tile_of_place(r, bid, tx, ty)) return;
     const uint32_t tile = ty * r.tiles_x + tx;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t* __restrict__ keys = sort_buffer;
@@ -2608,76 +2458,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
             }
         }
     }
-    const uint32_t list_begin = r.direct ? r.tile_base[tile] : r.tile_offset[tile];
-    uint32_t n = (r.overflow[0] | r.overflow[5]) ? 0u : (r.direct ? r.tile_count[tile] : r.tile_offset[tile + 1] - list_begin);
     constexpr uint32_t kLdsSortMax = kSortBytesMax / 4u;
-    {   // a list the sort buffer cannot hold: the host grows the buffer (overflow[3] = the longest list; without lists in place the scan of the
-        // counts has published it) and runs the frame again. (n is decided by selects on scalars only, and pinned to a scalar register: joined
-        // behind the lane-0 branch of the report, the compiler took it — and with it every branch of the walk — for lane dependent.)
-        const bool too_long = n > r.sort_capacity && n <= kLdsSortMax;
-        if (r.direct != 0u && (too_long || n > kLdsSortMax) && threadIdx.x == 0u) atomicMax(&r.overflow[3], n);
-        n = __builtin_amdgcn_readfirstlane(too_long ? 0u : n);
-    }
+    uint32_t list_begin, n;
+    tile_list_range(r, tile, kLdsSortMax, list_begin, n);
 #ifdef CRH_ABLATE
     if (r.debug & 64u) n = 0;
 #endif
     uint32_t my_key = 0xFFFFFFFFu;
     const bool sorted_in_place = n > kLdsSortMax;
     uint32_t* const segment = r.tile_list + list_begin;
-    if (sorted_in_place) { // as k_raster_edges: a normalised bitonic network over the tile's segment of the list, in global memory
-        uint32_t padded = 1;
-        while (padded < n) padded <<= 1;
-        auto exchange = [&](uint32_t i, uint32_t partner) {
-            if (partner < n) {
-                const uint32_t a = __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t b = __hip_atomic_load(segment + partner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (a > b) {
-                    __hip_atomic_store(segment + i, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(segment + partner, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        };
-        for (uint32_t kk = 2; kk <= padded; kk <<= 1) {
-            const uint32_t half = kk >> 1;
-            for (uint32_t p = lane; p < (padded >> 1); p += 64u) {
-                const uint32_t blk = p / half, t = p - blk * half;
-                exchange(blk * kk + t, blk * kk + kk - 1u - t);
-            }
-            __threadfence();
-            __syncthreads();
-            for (uint32_t j = half >> 1; j > 0; j >>= 1) {
-                for (uint32_t p = lane; p < (padded >> 1); p += 64u) {
-                    const uint32_t i = 2u * j * (p / j) + (p % j);
-                    exchange(i, i + j);
-                }
-                __threadfence();
-                __syncthreads();
-            }
-        }
+    if (sorted_in_place) {
+        sort_list_in_place(segment, n, lane, 64u);
     } else if (n <= 64u) {
         if (lane < n) my_key = r.tile_list[list_begin + lane];
         if (n > 1u) my_key = sort_keys_in_lanes(my_key, lane, n <= 8u ? 8u : (n <= 16u ? 16u : (n <= 32u ? 32u : 64u))); // a network as deep as the list needs (the keys sit in the leading lanes)
     } else {
-        uint32_t padded = 128;
-        while (padded < n) padded <<= 1;
-        for (uint32_t i = lane; i < padded; i += 64u) keys[i] = i < n ? r.tile_list[list_begin + i] : 0xFFFFFFFFu;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t kk = 2; kk <= padded; kk <<= 1)
-            for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-                for (uint32_t i = lane; i < padded; i += 64u) {
-                    const uint32_t partner = i ^ j;
-                    if (partner > i) {
-                        const uint32_t a = keys[i], b = keys[partner];
-                        if (((i & kk) == 0) ? (a > b) : (a < b)) {
-                            keys[i] = b;
-                            keys[partner] = a;
-                        }
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
+        sort_list_in_lds(keys, segment, n, lane);
     }
 
     const uint8_t* slots = r.slots;
@@ -2686,45 +2482,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
     const uint32_t row_j = lane & 15u;
     const float ry_row = lane == 16u ? 0.5f : (float)row_j + 0.5f;
     const float sy_row = tile_y0 + ry_row;
-    auto key_of = [&](uint32_t i) -> uint32_t { return sorted_in_place ? __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : keys[i]; };
     uint32_t walk_from = 0, verify_entry = 0xFFFFFFFFu; // absolute positions in the list
-    if (LONG && n > 64u && !r.load_existing) { // the late start of a list of several chunks (k_raster_edges: X, the last opaque whole-tile cover; R, the last whole-tile reset before it)
-        uint32_t x_at = 0xFFFFFFFFu;
-        for (uint32_t c0 = ((n - 1u) >> 6) << 6;; c0 -= 64u) {
-            const uint32_t k = c0 + lane < n ? key_of(c0 + lane) : 0xFFFFFFFFu;
-            uint32_t code = 0;
-            if (c0 + lane < n) {
-                const uint32_t flags = *reinterpret_cast<const uint32_t*>(slots + (size_t)k * 32u);
-                code = ((flags >> 4) & 15u) == EK_SYNTH ? (flags >> 8) & 31u : 0u;
-            }
-            unsigned long long resets = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverHull);
-            if (x_at == 0xFFFFFFFFu) {
-                unsigned long long candidates = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverOpaque);
-                while (candidates) {
-                    const uint32_t at = 63u - (uint32_t)__builtin_clzll(candidates);
-                    const SynthRec sr = load_uniform(reinterpret_cast<const SynthRec*>(slots + (size_t)__builtin_amdgcn_readlane(k, at) * 32u));
-                    uint32_t lo = 0, hi = n; // the number of keys below the item's synthetic slots
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (key_of(mid) < sr.synth_a) lo = mid + 1u;
-                        else hi = mid;
-                    }
-                    if (lo == 0u || key_of(lo - 1u) < sr.first_slot) {
-                        x_at = c0 + at;
-                        resets &= (1ull << at) - 1ull;
-                        break;
-                    }
-                    candidates &= ~(1ull << at);
-                }
-            }
-            if (x_at != 0xFFFFFFFFu && resets) {
-                walk_from = c0 + 64u - (uint32_t)__builtin_clzll(resets); // behind the last whole-tile reset before X
-                verify_entry = x_at;
-                break;
-            }
-            if (c0 == 0u) break;
-        }
-    }
+    if (LONG && n > 64u && !r.load_existing) find_late_start(slots, segment, keys, sorted_in_place, n, lane, walk_from, verify_entry);
     uint32_t first_j = walk_from & 63u;
     bool again_from_the_top = false;
     for (uint32_t q0 = LONG ? walk_from & ~63u : 0u; q0 < n; q0 += 64u) {
@@ -3133,16 +2892,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
     __shared__ uint16_t pair_start[66];          // [rank of a triangle in the chunk] its first (triangle, row) pair; [number of triangles] all pairs
     __shared__ uint16_t edge_pair_start[66];     // the same for the boundary edges: their (edge, row) pairs — the rows of the edge's half-open y range
     __shared__ uint32_t vgrid[kRowSlots][16];    // [group slot][sample row] what begins at that row and holds for every column of it and of the rows below (delta form down the tile)
-    constexpr uint32_t kB = CRH_XCD_BLOCK_LOG2, kBlock = 1u << kB;
-    const uint32_t turn = bid >> 3;
-    const uint32_t blocks_x = (r.tiles_x + kBlock - 1u) >> kB, block = (turn >> (2u * kB)) * 8u + (bid & 7u);
-    uint32_t tx = (block % blocks_x) * kBlock + (turn & (kBlock - 1u)), ty = (block / blocks_x) * kBlock + ((turn >> kB) & (kBlock - 1u));
-    if (r.tile_order) { // the host's order for this frame: every XCD's heavy tiles first (api.hip order_tiles_heavy_first)
-        const uint32_t mine = r.tile_order[bid];
-        if (mine == 0xFFFFFFFFu) return;
-        ty = mine / r.tiles_x, tx = mine - ty * r.tiles_x;
-    }
-    if (tx >= r.tiles_x || ty >= r.tiles_y || ty < r.slab_ty0 || ty >= r.slab_ty1) return; // (beyond the frame, or not in this pass' slab of tile rows)
+    uint32_t tx, ty;
+    if (!tile_of_place(r, bid, tx, ty)) return;
     const uint32_t tile = ty * r.tiles_x + tx;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t* __restrict__ keys = sort_buffer;
@@ -3172,6 +2923,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
 #pragma unroll
     for (uint32_t g = 0; g < kRowSlots; ++g) my_cells[g * 64u] = make_uint4(0u, 0u, 0u, 0u);
     if (lane < kRowSlots * 16u) (&vgrid[0][0])[lane] = 0u;
+    // tile_list_range (raster_tile_list.hpp) written out, without its scalar pin: with the helper three of the four instantiations take one register less (99, 98, 99 for 100, 99, 100)
     const uint32_t list_begin = r.direct ? r.tile_base[tile] : r.tile_offset[tile];
     uint32_t n = (r.overflow[0] | r.overflow[5]) ? 0u : (r.direct ? r.tile_count[tile] : r.tile_offset[tile + 1] - list_begin);
     constexpr uint32_t kLdsSortMax = kSortBytesMax / 4u;
@@ -3184,40 +2936,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
     uint32_t my_key = 0xFFFFFFFFu;
     const bool sorted_in_place = n > kLdsSortMax;
     uint32_t* const segment = r.tile_list + list_begin;
-    if (sorted_in_place) { // as k_raster_edges: a normalised bitonic network over the tile's segment of the list, in global memory
-        const uint32_t tid = threadIdx.x, n_threads = 64u;
-        uint32_t padded = 1;
-        while (padded < n) padded <<= 1;
-        auto exchange = [&](uint32_t i, uint32_t partner) {
-            if (partner < n) {
-                const uint32_t a = __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t b = __hip_atomic_load(segment + partner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (a > b) {
-                    __hip_atomic_store(segment + i, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(segment + partner, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        };
-        for (uint32_t kk = 2; kk <= padded; kk <<= 1) {
-            const uint32_t half = kk >> 1;
-            for (uint32_t p = tid; p < (padded >> 1); p += n_threads) {
-                const uint32_t blk = p / half, t = p - blk * half;
-                exchange(blk * kk + t, blk * kk + kk - 1u - t);
-            }
-            __threadfence();
-            __syncthreads();
-            for (uint32_t j = half >> 1; j > 0; j >>= 1) {
-                for (uint32_t p = tid; p < (padded >> 1); p += n_threads) {
-                    const uint32_t i = 2u * j * (p / j) + (p % j);
-                    exchange(i, i + j);
-                }
-                __threadfence();
-                __syncthreads();
-            }
-        }
+    if (sorted_in_place) {
+        sort_list_in_place(segment, n, threadIdx.x, 64u);
     } else if (n <= 64u) {
         if (lane < n) my_key = r.tile_list[list_begin + lane];
-        // (a network as deep as the list needs: most tiles hold fewer than 32 entries)
+        // (a network as deep as the list needs: most tiles hold fewer than 32 entries — and many fewer than 8, the least sort_keys_in_lanes
+        // (raster_tile_list.hpp) runs: with it the glyph scene's step measured a median of 0.615 ms against the parent's 0.603 - 0.612, same resource rows: profiles/tile_list_helpers.txt §3)
         const uint32_t depth = n <= 2u ? 2u : (n <= 4u ? 4u : (n <= 8u ? 8u : (n <= 16u ? 16u : (n <= 32u ? 32u : 64u))));
         if (n > 1u) {
 #pragma unroll
@@ -3232,70 +2956,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
             }
         }
     } else {
-        uint32_t padded = 128;
-        while (padded < n) padded <<= 1;
-        for (uint32_t i = lane; i < padded; i += 64u) keys[i] = i < n ? r.tile_list[list_begin + i] : 0xFFFFFFFFu;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t kk = 2; kk <= padded; kk <<= 1)
-            for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-                for (uint32_t i = lane; i < padded; i += 64u) {
-                    const uint32_t partner = i ^ j;
-                    if (partner > i) {
-                        const uint32_t a = keys[i], b = keys[partner];
-                        if (((i & kk) == 0) ? (a > b) : (a < b)) {
-                            keys[i] = b;
-                            keys[partner] = a;
-                        }
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
+        sort_list_in_lds(keys, segment, n, lane);
     }
 
     const uint8_t* slots = r.slots;
     const int wmask = (int)r.winding_mask;
-    auto key_of = [&](uint32_t i) -> uint32_t { return sorted_in_place ? __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : keys[i]; };
-    // the late start of a list of several chunks: as k_raster_edges<.., LONG>
     uint32_t walk_from = 0, verify_entry = 0xFFFFFFFFu;
-    if (LONG && n > 64u && !r.load_existing) {
-        uint32_t x_at = 0xFFFFFFFFu;
-        for (uint32_t c0 = ((n - 1u) >> 6) << 6;; c0 -= 64u) {
-            const uint32_t k = c0 + lane < n ? key_of(c0 + lane) : 0xFFFFFFFFu;
-            uint32_t code = 0;
-            if (c0 + lane < n) {
-                const uint32_t flags = *reinterpret_cast<const uint32_t*>(slots + (size_t)k * 32u);
-                code = ((flags >> 4) & 15u) == EK_SYNTH ? (flags >> 8) & 31u : 0u;
-            }
-            unsigned long long resets = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverHull);
-            if (x_at == 0xFFFFFFFFu) {
-                unsigned long long candidates = __builtin_amdgcn_ballot_w64(code >= 4u + kCoverOpaque);
-                while (candidates) {
-                    const uint32_t at = 63u - (uint32_t)__builtin_clzll(candidates);
-                    const SynthRec sr = load_uniform(reinterpret_cast<const SynthRec*>(slots + (size_t)__builtin_amdgcn_readlane(k, at) * 32u));
-                    uint32_t lo = 0, hi = n;
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (key_of(mid) < sr.synth_a) lo = mid + 1u;
-                        else hi = mid;
-                    }
-                    if (lo == 0u || key_of(lo - 1u) < sr.first_slot) {
-                        x_at = c0 + at;
-                        resets &= (1ull << at) - 1ull;
-                        break;
-                    }
-                    candidates &= ~(1ull << at);
-                }
-            }
-            if (x_at != 0xFFFFFFFFu && resets) {
-                walk_from = c0 + 64u - (uint32_t)__builtin_clzll(resets);
-                verify_entry = x_at;
-                break;
-            }
-            if (c0 == 0u) break;
-        }
-    }
+    if (LONG && n > 64u && !r.load_existing) find_late_start(slots, segment, keys, sorted_in_place, n, lane, walk_from, verify_entry);
     uint32_t first_j = walk_from & 63u;
     bool again_from_the_top = false;
     bool prev_cover = true; // the entry in front of the chunk's first one was a cover (or there was none): the first entry opens a group
@@ -3735,8 +3402,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
     }
 }
 // ---------------------------------------------------------------------------------------------- launchers
-void launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t* block_sum, uint32_t n, hipStream_t stream); // raster.hip
-
 // slots per draw item (shapes in the plain pass) and their exclusive scan: slot_begin[n_items + 1]
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream) {
     if (n_items == 0) {
@@ -3760,7 +3425,7 @@ __global__ __launch_bounds__(64) void k_shape_counts(SceneDev s, uint32_t* shape
     RasterParams plain = {}; // items == nullptr: item i is Shape i, Stencil + Color
     shape_nslots[shape] = item_slots(s, item_of(plain, shape)).total;
 }
-// two exclusive prefixes of n items each (blockIdx.y picks the pair), 512 items per single-wave workgroup; out[n] = the total
+// two exclusive prefixes of n items each (blockIdx.y picks the job; a grid of (blocks, 1) runs job a alone), 512 items per single-wave workgroup; out[n] = the total
 struct WaveScan {
     const uint32_t* in;
     uint32_t* out;
@@ -3870,7 +3535,7 @@ void flat_batch_limits(uint32_t n_items, uint32_t limits[4]) {
 }
 // The edge pass draws msaa 1 and 4 only (edge_pass_samples): for any other count its launchers launch nothing and return 0 (api.hip
 // render_impl refuses such a pass before it gets here; choose_pass sends msaa 2 and 8 to the triangle pass).
-uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, hipEvent_t after_bin) {
+uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin) {
     if (!edge_pass_samples(samples)) return 0u;
     // tile_count and, right behind it, the overflow words (overflow[8 ...] are the cursors of the pair sub-streams): one memset (tile_cursor, in front, is the triangle pass')
     (void)hipMemsetAsync(r.tile_count, 0, sizeof(uint32_t) * r.n_tiles + 32 + 4 * kSubStreams + 32, stream); // (... and kExtraTurnsWord behind them)
@@ -3920,7 +3585,7 @@ uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t sam
     if (mark) mark(ctx, "raster_tile_scan", 0);
     return route;
 }
-void launch_scatter(const RasterParams& r, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx) {
+void launch_scatter(const RasterParams& r, hipStream_t stream, MarkFn mark, void* ctx) {
     if (r.pair_capacity && !r.direct) hipLaunchKernelGGL(k_scatter, dim3((r.pair_capacity + 255u) / 256u), dim3(256), 0, stream, r);
     if (mark) mark(ctx, "raster_scatter", 0);
 }
@@ -3948,47 +3613,15 @@ __global__ __launch_bounds__(64) void k_tile_caps(const uint32_t* count, uint32_
     }
     caps[t] = longest + (longest >> 1) + kListSlack;
 }
-// exclusive prefix of caps -> tile_base[0 .. n], tile_base[n] = the total: 512 items per single-wave workgroup (eight a lane), then every workgroup adds the sums in front of it
-constexpr uint32_t kBaseItems = 8, kBaseBlock = 64 * kBaseItems;
-__global__ __launch_bounds__(64) void k_tile_base_local(const uint32_t* caps, uint32_t* base, uint32_t* block_sum, uint32_t n) {
-    const uint32_t lane = threadIdx.x, i0 = blockIdx.x * kBaseBlock + lane * kBaseItems;
-    uint32_t v[kBaseItems], mine = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kBaseItems; ++k) v[k] = i0 + k < n ? caps[i0 + k] : 0u, mine += v[k];
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += up;
-    }
-    uint32_t run = incl - mine;
-#pragma unroll
-    for (uint32_t k = 0; k < kBaseItems; ++k) {
-        if (i0 + k < n) base[i0 + k] = run;
-        run += v[k];
-    }
-    if (lane == 63u) block_sum[blockIdx.x] = incl;
-}
-__global__ __launch_bounds__(64) void k_tile_base_add(uint32_t* base, const uint32_t* block_sum, uint32_t n, uint32_t blocks) {
-    const uint32_t lane = threadIdx.x;
-    uint32_t sum = 0;
-    for (uint32_t k = lane; k < blockIdx.x; k += 64u) sum += block_sum[k];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, 64);
-    const uint32_t i0 = blockIdx.x * kBaseBlock + lane * kBaseItems;
-#pragma unroll
-    for (uint32_t k = 0; k < kBaseItems; ++k)
-        if (i0 + k < n) base[i0 + k] += sum;
-    if (blockIdx.x + 1u == blocks && lane == 0u) base[n] = sum + block_sum[blockIdx.x];
-}
-// (scratch: (n_tiles + 511) / 512 block sums)
+// exclusive prefix of caps -> tile_base[0 .. n_tiles], tile_base[n_tiles] = the total: the single-wave scan of launch_plain_ranges with one job (scratch: (n_tiles + 511) / 512 block sums)
 void launch_tile_bases(const uint32_t* tile_count, uint32_t* caps, uint32_t* tile_base, uint32_t* scratch, uint32_t n_tiles, uint32_t tiles_x, uint32_t radius, hipStream_t stream) {
-    const uint32_t blocks = (n_tiles + kBaseBlock - 1u) / kBaseBlock;
+    const uint32_t blocks = (n_tiles + kWaveScanBlock - 1u) / kWaveScanBlock;
+    const WaveScan job = {caps, tile_base, scratch};
     hipLaunchKernelGGL(k_tile_caps, dim3((n_tiles + 63u) / 64u), dim3(64), 0, stream, tile_count, caps, n_tiles, tiles_x, radius);
-    hipLaunchKernelGGL(k_tile_base_local, dim3(blocks), dim3(64), 0, stream, caps, tile_base, scratch, n_tiles);
-    hipLaunchKernelGGL(k_tile_base_add, dim3(blocks), dim3(64), 0, stream, tile_base, scratch, n_tiles, blocks);
+    hipLaunchKernelGGL(k_wave_scan_local2, dim3(blocks, 1), dim3(64), 0, stream, job, job, n_tiles);
+    hipLaunchKernelGGL(k_wave_scan_add2, dim3(blocks, 1), dim3(64), 0, stream, job, job, n_tiles, blocks);
 }
-uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx,
+uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx,
                          uint64_t raster_bytes, bool has_stroke) {
     if (!edge_pass_samples(samples)) return 0u;
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;

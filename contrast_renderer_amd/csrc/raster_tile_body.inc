@@ -1,22 +1,12 @@
 // csrc/raster_tile_body.inc — the body of k_raster_tile<S, ROWS, OPS, STROKES> and k_raster_blend<S, STROKES> (raster.hip), included into
 // both kernels with S, ROWS, OPS, STROKES, BLEND and the blend form `bf` in scope. Included rather than shared as a __device__ function:
-// the instruction stream of k_raster_tile stays what it was (an inlined body changed its register allocation and scheduling).
+// the instruction stream of k_raster_tile stays what it was (an inlined body changed its register allocation and scheduling). The steps in
+// front of the walk that every tile kernel takes — the tile of the workgroup's place, the sort of a list in place — are the helpers of
+// raster_tile_list.hpp: tools/resource_usage.py shows the same registers, scratch, occupancy and LDS for every instantiation with them.
     extern __shared__ uint32_t sort_buffer[]; // [waves][r.sort_capacity], wave-private; only used by tiles with more than 64 primitives
     __shared__ float4 entry_buffer[4 / ROWS][64 * 3];        // wave-private: the set-up values of the current chunk's 64 entries
-
-    // XCD-aware tile order: workgroup b runs on XCD b % 8 (each XCD has its own L2). The frame is cut into 8x8-tile blocks dealt to the
-    // XCDs in turn (spatially interleaved, so an unevenly filled frame still loads all eight), and an XCD walks a block's 64 tiles back to
-    // back: a primitive record shared by neighbouring tiles is fetched into one L2 instead of up to eight. launch_raster pads the grid.
-    constexpr uint32_t kB = CRH_XCD_BLOCK_LOG2, kBlock = 1u << kB;
-    const uint32_t turn = blockIdx.x >> 3;
-    const uint32_t blocks_x = (r.tiles_x + kBlock - 1u) >> kB, block = (turn >> (2u * kB)) * 8u + (blockIdx.x & 7u);
-    uint32_t tx = (block % blocks_x) * kBlock + (turn & (kBlock - 1u)), ty = (block / blocks_x) * kBlock + ((turn >> kB) & (kBlock - 1u));
-    if (r.tile_order) { // the host's order for this frame: every XCD's heavy tiles first (api.hip order_tiles_heavy_first)
-        const uint32_t mine = r.tile_order[blockIdx.x];
-        if (mine == 0xFFFFFFFFu) return;
-        ty = mine / r.tiles_x, tx = mine - ty * r.tiles_x;
-    }
-    if (tx >= r.tiles_x || ty >= r.tiles_y || ty < r.slab_ty0 || ty >= r.slab_ty1) return; // (beyond the frame, or not in this pass' slab of tile rows)
+    uint32_t tx, ty;
+    if (!tile_of_place(r, blockIdx.x, tx, ty)) return;
     const uint32_t tile = ty * r.tiles_x + tx;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t* __restrict__ keys = sort_buffer + wave * r.sort_capacity;
@@ -117,40 +107,7 @@
     const bool sorted_in_place = n > kLdsSortMax;
     uint32_t* const segment = r.tile_list + list_begin;
     if (sorted_in_place) {
-        // Thousands of primitives over one tile (one Shape with 10^4 slivers through a point, hundreds of Shapes stacked): rare, so simple.
-        // A normalised bitonic network — every compare-exchange leaves the smaller key at the lower index — sorts any length: positions
-        // beyond n behave as +inf and are skipped. All wavefronts of the tile's workgroup take part; keys move through L2 (agent-scope
-        // atomics) so that every lane sees what the others wrote.
-        const uint32_t tid = threadIdx.x, n_threads = 64u * (4u / ROWS);
-        uint32_t padded = 1;
-        while (padded < n) padded <<= 1;
-        auto exchange = [&](uint32_t i, uint32_t partner) {
-            if (partner < n) {
-                const uint32_t a = __hip_atomic_load(segment + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t b = __hip_atomic_load(segment + partner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (a > b) {
-                    __hip_atomic_store(segment + i, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(segment + partner, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        };
-        for (uint32_t k = 2; k <= padded; k <<= 1) {
-            const uint32_t half = k >> 1;
-            for (uint32_t p = tid; p < (padded >> 1); p += n_threads) { // the mirror step of the block of k
-                const uint32_t block = p / half, t = p - block * half;
-                exchange(block * k + t, block * k + k - 1u - t);
-            }
-            __threadfence();
-            __syncthreads();
-            for (uint32_t j = half >> 1; j > 0; j >>= 1) {
-                for (uint32_t p = tid; p < (padded >> 1); p += n_threads) {
-                    const uint32_t i = 2u * j * (p / j) + (p % j);
-                    exchange(i, i + j);
-                }
-                __threadfence();
-                __syncthreads();
-            }
-        }
+        sort_list_in_place(segment, n, threadIdx.x, 64u * (4u / ROWS));
     } else if (n <= 64u) {
         if (lane < n) my_key = r.tile_list[list_begin + lane];
 #pragma unroll
@@ -163,6 +120,7 @@
             }
         }
     } else {
+        // sort_list_in_lds (raster_tile_list.hpp) written out: with the helper k_raster_tile<1, 4, false, false, true> takes 78 registers instead of 80
         uint32_t padded = 128;
         while (padded < n) padded <<= 1;
         for (uint32_t i = lane; i < padded; i += 64u) keys[i] = i < n ? r.tile_list[list_begin + i] : 0xFFFFFFFFu;

@@ -13,6 +13,7 @@
 //                 Shape-aligned workgroups (a run of consecutive Shapes each), the ten-channel scan in LDS, the runs' bases and every
 //                 element's counts kept from the first tessellation of the paths — see "k_tess_runs" below.
 #include "fill.hpp"
+#include "launch.hpp"
 #include "scene.hpp"
 #include "stroke.hpp"
 
@@ -933,7 +934,7 @@ void launch_fmath(int fn, const float* a, const float* b, float* out, uint64_t n
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-void launch_stroke_records(const SceneDev& s, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx) {
+void launch_stroke_records(const SceneDev& s, hipStream_t stream, MarkFn mark, void* ctx) {
     if (s.n_elems == 0) return;
     hipLaunchKernelGGL(k_stroke_records, dim3((s.n_paths + 63) / 64), dim3(64), 0, stream, s);
     if (mark) mark(ctx, "stroke_records", 0);
@@ -989,7 +990,7 @@ void launch_build_elements(const UploadBuild& u, hipStream_t stream) {
     hipLaunchKernelGGL(k_upload_build, dim3((lanes + 255u) / 256u), dim3(256), 0, stream, u);
 }
 
-void launch_tessellate(const SceneDev& s, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, const uint64_t bytes[4], bool has_stroke, bool need_totals) {
+void launch_tessellate(const SceneDev& s, hipStream_t stream, MarkFn mark, void* ctx, const uint64_t bytes[4], bool has_stroke, bool need_totals) {
     if (s.n_elems == 0) return;
     if (has_stroke) launch_stroke_records(s, stream, mark, ctx);
     if (s.n_runs) {
@@ -1014,7 +1015,7 @@ void launch_tessellate(const SceneDev& s, hipStream_t stream, void (*mark)(void*
     if (mark) mark(ctx, "tess_scan", bytes[1]);
 }
 // hull_queued: what the three queues behind k_hull_small held when these paths were tessellated before ([0] <= 256 candidates, [1] <= 2048, [2] beyond), or nullptr: not known yet
-void launch_emit(const SceneDev& s, hipStream_t stream, void (*mark)(void*, const char*, uint64_t), void* ctx, const uint64_t bytes[4], bool has_stroke, bool big_shapes, const uint32_t* hull_queued) {
+void launch_emit(const SceneDev& s, hipStream_t stream, MarkFn mark, void* ctx, const uint64_t bytes[4], bool has_stroke, bool big_shapes, const uint32_t* hull_queued) {
     if (s.n_elems == 0) return;
     if (s.n_runs) {
         if (s.run_block == 128u) {
