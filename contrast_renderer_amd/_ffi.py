@@ -209,6 +209,18 @@ class DrawC(C.Structure):
     _fields_ = [("shape", C.c_uint32), ("instance", C.c_uint32), ("op", C.c_uint32), ("clip_depth", C.c_uint32), ("alpha_layer", C.c_uint32)]
 
 
+MAX_GRADIENT_STOPS = 8  # CRH_MAX_GRADIENT_STOPS
+
+
+class GradientStopC(C.Structure):  # crh_gradient_stop
+    _fields_ = [("offset", C.c_float), ("color", C.c_float * 4)]
+
+
+class PaintC(C.Structure):  # crh_paint
+    _fields_ = [("kind", C.c_uint32), ("spread", C.c_uint32), ("p0", C.c_float * 2), ("p1", C.c_float * 2), ("n_stops", C.c_uint32),
+                ("stops", GradientStopC * MAX_GRADIENT_STOPS)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -276,6 +288,8 @@ def load_library():
         "crh_scene_set_instances": (C.c_int, [V, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "crh_scene_render_resident": (C.c_int, [V, V]),
         "crh_scene_render_draws": (C.c_int, [V, V, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(DrawC), C.c_uint32]),
+        "crh_paint_validate": (C.c_int, [C.POINTER(PaintC)]),
+        "crh_scene_set_paints": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),
         "crh_frame_download": (C.c_int, [V, V]),
         "crh_frame_download_f16": (C.c_int, [V, V]),

@@ -437,6 +437,12 @@ struct crh_scene {
     bool rec_used_ever[kPipelineDepth] = {}; // rec_raster_done[k] has been recorded (crh_scene_upload orders its copy behind them: rec_used is reset by every upload)
     int next_rec = 0;
     bool instances_set = false;
+    // gradient paints (crh_scene_set_paints): the association on the host (which passes draw a painted instance) and the kernels' tables
+    std::vector<int32_t> instance_paint;
+    uint32_t n_paints = 0;
+    uint32_t first_painted = 0xFFFFFFFFu; // the lowest instance with a paint: the plain pass (instance i = Shape i) is a painted one when it is below n_shapes
+    DevBuf paint_heads, paint_stops, paint_instance;
+    DevBuf paint_items[kPipelineDepth];  // [n_items] PaintItem, written per pass (k_paint_items) beside the set-up triangles of prim_rec
     // frame pipelining: tessellation runs on its own stream; these events order it against the raster stream
     hipEvent_t tess_done = nullptr;     // recorded on the tessellation stream after the last tessellation kernel
     hipEvent_t vertices_free = nullptr; // recorded on the raster stream after k_prim_setup (last reader of the vertex streams and hulls)
@@ -495,6 +501,8 @@ struct crh_scene {
         shadow.allocated = false;
         for (DevBuf& b : prim_rec) b.release();
         for (DevBuf& b : prim_proj) b.release();
+        for (DevBuf& b : paint_items) b.release();
+        paint_heads.release(), paint_stops.release(), paint_instance.release();
         upload_t.release();
         upload_c.release();
         geometry_stage.release();
@@ -1199,7 +1207,18 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     p.cull_mode = r->config.cull_mode;
     // The general pass keeps the reference's triangle strips (raster.hip): clip nesting / alpha contexts, perspective, depth, and face
     // culling (a cull decision is per strip triangle). Everything else is the edge pass (raster_edges.hip).
-    p.general = (projective || p.depth || r->config.cull_mode != CRH_CULL_NONE || (recorded && f->items_need_ops) || f->carry || !r->blend_over) ? 1u : 0u;
+    // a pass that draws a painted instance with a Color cover (crh_scene_set_paints); a Scene without paints asks nothing
+    bool painted = false;
+    if (sc->n_paints != 0u) {
+        if (!recorded) painted = sc->first_painted < sc->d.n_shapes;
+        else
+            for (const DrawItem& it : f->items_host)
+                if ((it.ops >> 4) == (uint32_t)CRH_OP_COLOR + 1u && it.instance < sc->instance_paint.size() && sc->instance_paint[it.instance] >= 0) {
+                    painted = true;
+                    break;
+                }
+    }
+    p.general = (projective || p.depth || r->config.cull_mode != CRH_CULL_NONE || (recorded && f->items_need_ops) || f->carry || !r->blend_over || painted) ? 1u : 0u;
     p.state_stencil = nullptr, p.state_alpha = nullptr, p.state_color = nullptr, p.state_load = 0u, p.state_layers = 0u;
     p.winding_bits = r->config.winding_counter_bits;
     if (f->carry) { // the frame keeps clip counters, winding counters, saved alphas and sample colours from pass to pass
@@ -1242,7 +1261,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     p.rgba8 = f->rgba8.as<uint8_t>();
     p.format = f->format;
     p.debug = getenv("CRH_RASTER_DEBUG") ? (uint32_t)atoi(getenv("CRH_RASTER_DEBUG")) : 0u;
-    p.occlude = (tame_colors && r->blend_over) ? 1u : 0u; // (an opaque cover hides what is below it under "over" only)
+    p.occlude = (tame_colors && r->blend_over && !painted) ? 1u : 0u; // (an opaque cover hides what is below it under "over" only; a paint's alpha is not the instance colour's)
     r->begin_marks(2);
     // Rendering over existing content is not repeatable (the target is read and overwritten), so the optimistic tile-list capacity with a
     // transparent re-run after the fact is only used for cleared frames; otherwise the pair count is checked before the raster kernel runs.
@@ -1302,6 +1321,10 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
             f->last_bin = launch_bin_edges(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
         } else {
             launch_bin(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
+            if (painted) { // behind k_prim_setup, in front of the event that says the instance data has been read
+                HIP_TRY(sc->paint_items[rec].ensure((size_t)p.n_items * sizeof(PaintItem) + 64));
+                launch_paint_items(p, PaintTable{sc->paint_items[rec].as<PaintItem>(), sc->paint_instance.as<int32_t>(), (uint32_t)sc->instance_paint.size()}, bin);
+            }
             f->last_bin = kBinTriangles;
         }
         if (f->pairs_known) break;
@@ -1415,7 +1438,11 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     if (edges)
         f->last_raster = launch_raster_edges(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke);
     else
-        f->last_raster = launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke, r->blend_over ? nullptr : &r->blend_form);
+    {
+        const PaintArgs paint_args = {sc->paint_items[rec].as<PaintItem>(), sc->paint_heads.as<PaintHead>(), sc->paint_stops.as<PaintStop>()};
+        f->last_raster = launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke, (r->blend_over && !painted) ? nullptr : &r->blend_form,
+                                       painted ? &paint_args : nullptr);
+    }
     f->last_formulation = (uint32_t)pass | (measured ? 256u : 0u), f->last_general = p.general | (r->pipeline ? 0u : 256u);
     if (direct) f->last_bin |= 256u;
     if (p.tile_order) f->last_bin |= 512u;
@@ -2400,6 +2427,98 @@ crh_status crh_scene_set_instances(crh_scene* sc, const float* transforms, const
     sc->instances_tame_of[next] = all_colors_tame(colors, sc->d.n_shapes);
     sc->instances_projective = sc->instances_projective_of[next];
     sc->instances_set = true;
+    return CRH_OK;
+}
+namespace {
+crh_status paint_error(const char* what) {
+    g_error = std::string("crh_paint: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+} // namespace
+crh_status crh_paint_validate(const crh_paint* paint) {
+    if (!paint) return paint_error("null paint");
+    const float fields[4] = {paint->p0[0], paint->p0[1], paint->p1[0], paint->p1[1]};
+    for (float v : fields)
+        if (!std::isfinite(v)) return CRH_ERR_NON_FINITE;
+    if (paint->n_stops == 0u || paint->n_stops > CRH_MAX_GRADIENT_STOPS) return paint_error("n_stops must be 1..CRH_MAX_GRADIENT_STOPS");
+    for (uint32_t i = 0; i < paint->n_stops; ++i) {
+        if (!std::isfinite(paint->stops[i].offset)) return CRH_ERR_NON_FINITE;
+        for (float v : paint->stops[i].color)
+            if (!std::isfinite(v)) return CRH_ERR_NON_FINITE;
+    }
+    if (paint->kind != CRH_PAINT_LINEAR && paint->kind != CRH_PAINT_RADIAL) return paint_error("unknown kind");
+    if (paint->spread > CRH_SPREAD_REFLECT) return paint_error("unknown spread");
+    for (uint32_t i = 0; i < paint->n_stops; ++i) {
+        const float o = paint->stops[i].offset;
+        if (o < 0.0f || o > 1.0f) return paint_error("a stop offset outside [0, 1]");
+        if (i != 0u && o < paint->stops[i - 1u].offset) return paint_error("stop offsets decrease");
+    }
+    if (paint->kind == CRH_PAINT_LINEAR) {
+        const float dx = paint->p1[0] - paint->p0[0], dy = paint->p1[1] - paint->p0[1];
+        const float dd = dx * dx + dy * dy;
+        if (!(dd > 0.0f) || !std::isfinite(dd)) return paint_error("a linear paint needs p0 != p1");
+    } else if (!(paint->p1[0] > 0.0f)) {
+        return paint_error("a radial paint needs a radius > 0");
+    }
+    return CRH_OK;
+}
+crh_status crh_scene_set_paints(crh_scene* sc, const crh_paint* paints, uint32_t n_paints, const int32_t* instance_paint, uint32_t n_instances) {
+    if (!sc || !sc->renderer || (n_paints && !paints) || (n_paints && n_instances && !instance_paint)) return paint_error("null argument");
+    crh_renderer* r = sc->renderer;
+    // everything is checked and built on the host first: a failed call leaves the previous table in force
+    std::vector<PaintHead> heads;
+    std::vector<PaintStop> stops;
+    std::vector<int32_t> assoc;
+    uint32_t first_painted = 0xFFFFFFFFu;
+    if (n_paints) {
+        for (uint32_t k = 0; k < n_paints; ++k) {
+            const crh_status st = crh_paint_validate(&paints[k]);
+            if (st != CRH_OK) return st;
+            const crh_paint& q = paints[k];
+            PaintHead h = {};
+            h.kind = q.kind, h.spread = q.spread, h.n_stops = q.n_stops, h.first_stop = (uint32_t)stops.size();
+            h.p0[0] = q.p0[0], h.p0[1] = q.p0[1];
+            if (q.kind == CRH_PAINT_LINEAR) {
+                h.d[0] = q.p1[0] - q.p0[0], h.d[1] = q.p1[1] - q.p0[1];
+                h.dd = h.d[0] * h.d[0] + h.d[1] * h.d[1];
+            } else {
+                h.d[0] = q.p1[0], h.d[1] = 0.0f, h.dd = 1.0f;
+            }
+            heads.push_back(h);
+            for (uint32_t i = 0; i < q.n_stops; ++i) {
+                PaintStop st = {};
+                st.o = q.stops[i].offset;
+                const bool ramp = i + 1u < q.n_stops && q.stops[i + 1u].offset > st.o;
+                st.inv = ramp ? 1.0f / (q.stops[i + 1u].offset - st.o) : 0.0f;
+                for (int ch = 0; ch < 4; ++ch) {
+                    st.c[ch] = q.stops[i].color[ch];
+                    st.dc[ch] = ramp ? q.stops[i + 1u].color[ch] - st.c[ch] : 0.0f;
+                }
+                stops.push_back(st);
+            }
+        }
+        assoc.assign(instance_paint, instance_paint + n_instances);
+        for (uint32_t i = 0; i < n_instances; ++i) {
+            if (assoc[i] < -1 || assoc[i] >= (int32_t)n_paints) return paint_error("an instance_paint entry is neither -1 nor an index into paints");
+            if (assoc[i] >= 0 && first_painted == 0xFFFFFFFFu) first_painted = i;
+        }
+    }
+    HIP_TRY(hipSetDevice(r->device));
+    // the frames drawn from this Scene become final (a pass drawn again would read the new tables), and no kernel in flight reads the old ones
+    const crh_status settled = settle_frames_of(sc, false);
+    if (settled != CRH_OK) return settled;
+    HIP_TRY(r->sync());
+    if (n_paints) {
+        HIP_TRY(sc->paint_heads.ensure(heads.size() * sizeof(PaintHead)));
+        HIP_TRY(sc->paint_stops.ensure(stops.size() * sizeof(PaintStop)));
+        HIP_TRY(sc->paint_instance.ensure(assoc.size() * 4 + 4));
+        HIP_TRY(hipMemcpy(sc->paint_heads.p, heads.data(), heads.size() * sizeof(PaintHead), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(sc->paint_stops.p, stops.data(), stops.size() * sizeof(PaintStop), hipMemcpyHostToDevice));
+        if (!assoc.empty()) HIP_TRY(hipMemcpy(sc->paint_instance.p, assoc.data(), assoc.size() * 4, hipMemcpyHostToDevice));
+    }
+    sc->n_paints = n_paints;
+    sc->instance_paint = std::move(assoc);
+    sc->first_painted = first_painted;
     return CRH_OK;
 }
 crh_status crh_scene_render_resident(crh_scene* sc, crh_frame* f) {

@@ -561,16 +561,77 @@ constexpr int kMaxAlphaLayers = 4;
 //                "over": the kernel k_raster_blend. Both kernels include the one body, csrc/raster_tile_body.inc.
 template <int S, int ROWS, bool OPS, bool STROKES, bool XFMT = false> // XFMT: the frame formats 3-8 (raster_common.hpp store_px)
 __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu((OPS || STROKES || S >= 4) ? 1 : CRH_TILE_WAVES))) void k_raster_tile(SceneDev s, RasterParams r) {
-    constexpr bool BLEND = false;
+    constexpr bool BLEND = false, PAINT = false;
     const BlendForm bf = {}; // (not read: the blend block is compiled out)
+    const PaintArgs pa = {}; // (nor this: the paint block is)
 #include "raster_tile_body.inc"
 }
 // The general variant with the renderer's blend state in place of "over" (Configuration::blending; ROWS = tile_rows(S) as above)
 template <int S, bool STROKES, bool XFMT = false>
 __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_blend(SceneDev s, RasterParams r, BlendForm bf) {
     constexpr int ROWS = tile_rows(S);
-    constexpr bool OPS = true, BLEND = true;
+    constexpr bool OPS = true, BLEND = true, PAINT = false;
+    const PaintArgs pa = {};
 #include "raster_tile_body.inc"
+}
+// k_raster_blend with gradient paints (crh_scene_set_paints): the colour cover of a painted item takes its source per sample from the paint
+// tables `pa`; every other primitive, an unpainted item's cover included, is drawn as k_raster_blend draws it. The pass of a Scene that draws a
+// painted instance runs this kernel whatever the blend state — under "over" with the blend form of "over".
+template <int S, bool STROKES, bool XFMT = false>
+__global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_paint(SceneDev s, RasterParams r, BlendForm bf, PaintArgs pa) {
+    constexpr int ROWS = tile_rows(S);
+    constexpr bool OPS = true, BLEND = true, PAINT = true;
+#include "raster_tile_body.inc"
+}
+
+// One wavefront per draw item of a painted pass, behind k_prim_setup: an item whose instance has a paint and whose cover is Color gets its
+// PaintItem record and its cover primitives the tag item + 1 (frag.flat_u, which k_prim_setup leaves 0 on every cover).
+// The record holds the inverse of the item's path -> pixel homography. A Shape lies in z = 0, so clip = M (x, y, 0, 1) takes columns 0, 1, 3 and
+// rows x, y, w of the instance transform; the clip -> pixel map of to_framebuffer follows, and the product is inverted in float64 (adjugate / scale).
+// Evaluated here rather than on the host: the instance data is double buffered on the device and a pass that is drawn again reads the older set,
+// so the record follows the very buffer k_prim_setup read.
+__global__ __launch_bounds__(64) void k_paint_items(RasterParams r, PaintTable t) {
+    const uint32_t item = blockIdx.x, lane = threadIdx.x;
+    const DrawItem it = item_of(r, item);
+    const int32_t paint = it.instance < t.n_instances ? t.instance_paint[it.instance] : -1;
+    if (paint < 0 || (it.ops >> 4) != (uint32_t)CRH_OP_COLOR + 1u) return;
+    const uint32_t prim0 = r.shape_prim_begin[item], prim1 = r.shape_prim_begin[item + 1];
+    if (prim1 > r.prim_capacity) return; // (as k_prim_setup: cannot happen)
+    if (lane == 0) {
+        const float* m = r.transforms + 16u * it.instance;
+        const double W = (double)r.width, H = (double)r.height;
+        const double a[3][3] = {{0.5 * W * ((double)m[0] + (double)m[3]), 0.5 * W * ((double)m[4] + (double)m[7]), 0.5 * W * ((double)m[12] + (double)m[15])},
+                                {0.5 * H * ((double)m[3] - (double)m[1]), 0.5 * H * ((double)m[7] - (double)m[5]), 0.5 * H * ((double)m[15] - (double)m[13])},
+                                {(double)m[3], (double)m[7], (double)m[15]}};
+        double inv[9] = {a[1][1] * a[2][2] - a[1][2] * a[2][1], a[0][2] * a[2][1] - a[0][1] * a[2][2], a[0][1] * a[1][2] - a[0][2] * a[1][1],
+                         a[1][2] * a[2][0] - a[1][0] * a[2][2], a[0][0] * a[2][2] - a[0][2] * a[2][0], a[0][2] * a[1][0] - a[0][0] * a[1][2],
+                         a[1][0] * a[2][1] - a[1][1] * a[2][0], a[0][1] * a[2][0] - a[0][0] * a[2][1], a[0][0] * a[1][1] - a[0][1] * a[1][0]};
+        const bool affine = m[3] == 0.0f && m[7] == 0.0f;
+        // a homography is defined up to scale: an affine one is scaled to W == 1 (the kernel skips the division), any other to a largest entry of 1
+        double scale = inv[8];
+        if (!affine) {
+            scale = 0.0;
+            for (int i = 0; i < 9; ++i) scale = fmax(scale, fabs(inv[i]));
+        }
+        PaintItem out;
+        bool finite = scale != 0.0;
+        for (int i = 0; i < 9; ++i) {
+            out.h[i] = (float)(inv[i] / scale);
+            finite = finite && is_finite(out.h[i]);
+        }
+        if (affine) out.h[6] = 0.0f, out.h[7] = 0.0f, out.h[8] = 1.0f;
+        if (!finite) // a singular transform draws nothing; the record stays harmless
+            for (int i = 0; i < 9; ++i) out.h[i] = 0.0f;
+        out.affine = (affine || !finite) ? 1u : 0u;
+        out.paint = (uint32_t)paint;
+        out.pad = 0u;
+        for (int ch = 0; ch < 4; ++ch) out.tint[ch] = r.colors[4u * it.instance + ch];
+        t.items[item] = out;
+    }
+    for (uint32_t p = prim0 + lane; p < prim1; p += 64u) {
+        const PrimCoverage& cov = r.prim_rec[p].cov;
+        if (cov.box.x != 0xFFFFu && ((cov.flags >> 4) & 7u) == KIND_COVER) r.prim_rec[p].frag.flat_u = item + 1u;
+    }
 }
 
 // ordered premultiplied "over" of n RGBA8 layers: dst = L0 under L1 under ...
@@ -676,10 +737,11 @@ void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hip
     if (after_fill) (void)hipEventRecord(after_fill, stream);
     if (mark) mark(ctx, "raster_tile_fill", 0);
 }
-// The raster kernel of msaa S: k_raster_blend for a blend state other than "over" (r.general is set with it), else k_raster_tile, OPS for
+// The raster kernel of msaa S: k_raster_paint for a pass that draws a painted instance, k_raster_blend for a blend state other than "over"
+// (r.general is set with both), else k_raster_tile, OPS for
 // clip nesting / alpha contexts / depth / projective instances
 template <int S>
-static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_t stream, dim3 grid, bool has_stroke, const BlendForm* blend) {
+static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_t stream, dim3 grid, bool has_stroke, const BlendForm* blend, const PaintArgs* paint) {
     constexpr int ROWS = tile_rows(S);
     const dim3 block(64u * tile_waves(S));
     const uint32_t lds = tile_waves(S) * r.sort_capacity * 4u;
@@ -698,7 +760,16 @@ static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_
         else                                                                                                            \
             hipLaunchKernelGGL((k_raster_blend<S, STROKES_>), grid, block, lds, stream, s, r, *blend);                 \
     } while (0)
-    if (blend) {
+#define CRH_LAUNCH_PAINT(STROKES_)                                                                                        \
+    do {                                                                                                                \
+        if (xfmt)                                                                                                       \
+            hipLaunchKernelGGL((k_raster_paint<S, STROKES_, true>), grid, block, lds, stream, s, r, *blend, *paint);   \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_raster_paint<S, STROKES_>), grid, block, lds, stream, s, r, *blend, *paint);         \
+    } while (0)
+    if (blend && paint) {
+        if (has_stroke) CRH_LAUNCH_PAINT(true); else CRH_LAUNCH_PAINT(false);
+    } else if (blend) {
         if (has_stroke) CRH_LAUNCH_BLEND(true); else CRH_LAUNCH_BLEND(false);
     } else if (r.general) {
         if (has_stroke) CRH_LAUNCH_TILE(true, true); else CRH_LAUNCH_TILE(true, false);
@@ -707,19 +778,23 @@ static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_
     }
 #undef CRH_LAUNCH_TILE
 #undef CRH_LAUNCH_BLEND
+#undef CRH_LAUNCH_PAINT
+}
+void launch_paint_items(const RasterParams& r, const PaintTable& t, hipStream_t stream) {
+    if (r.n_items) hipLaunchKernelGGL(k_paint_items, dim3(r.n_items), dim3(64), 0, stream, r, t);
 }
 // -> RasterVariant (0: nothing launched)
 uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx,
-                   uint64_t raster_bytes, bool has_stroke, const BlendForm* blend) {
+                   uint64_t raster_bytes, bool has_stroke, const BlendForm* blend, const PaintArgs* paint) {
     // 8x8-tile blocks, an equal number per XCD (k_raster_tile's tile order)
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;
     const uint32_t blocks = ((r.tiles_x + kBlock - 1u) / kBlock) * ((r.tiles_y + kBlock - 1u) / kBlock);
     const dim3 grid((r.tile_order && r.order_places) ? r.order_places : ((blocks + 7u) / 8u) * kBlock * kBlock * 8u);
     switch (samples) {
-        case 1: launch_raster_s<1>(s, r, stream, grid, has_stroke, blend); break;
-        case 2: launch_raster_s<2>(s, r, stream, grid, has_stroke, blend); break;
-        case 4: launch_raster_s<4>(s, r, stream, grid, has_stroke, blend); break;
-        case 8: launch_raster_s<8>(s, r, stream, grid, has_stroke, blend); break;
+        case 1: launch_raster_s<1>(s, r, stream, grid, has_stroke, blend, paint); break;
+        case 2: launch_raster_s<2>(s, r, stream, grid, has_stroke, blend, paint); break;
+        case 4: launch_raster_s<4>(s, r, stream, grid, has_stroke, blend, paint); break;
+        case 8: launch_raster_s<8>(s, r, stream, grid, has_stroke, blend, paint); break;
         default: return 0u;
     }
     if (mark) mark(ctx, "raster_tiles", raster_bytes);

@@ -54,6 +54,44 @@ struct BlendForm {
     uint32_t write_mask; // wgpu::ColorWrites: bit ch set = channel ch is written
 };
 
+// Gradient paints of the colour cover (crh_scene_set_paints): like BlendForm a kernel argument of its own, read by k_raster_paint only.
+//   PaintItem  per draw item of a painted pass (k_paint_items writes it, in front of the raster kernel): the inverse of the item's
+//              path -> pixel homography (rows X, Y, W; inverted in float64, stored as f32; an affine instance has the row W = (0, 0, 1) exactly),
+//              the instance colour (straight alpha) and the paint's index. The item's cover primitives carry item + 1 in frag.flat_u.
+//   PaintHead  per paint: kind, spread, p0, and d = p1 - p0 with dd = dot(d, d) (linear) or d[0] = the radius (radial)
+//   PaintStop  per stop i: the offset o_i, 1 / (o_{i+1} - o_i) (0 for a hard edge and behind the last stop), the colour c_i and c_{i+1} - c_i
+//              (0 behind the last stop), so that colour(t) = c_i + max((t - o_i) * inv, 0) * dc for the last i with t >= o_i (i = 0 if there is none)
+struct PaintItem {
+    float h[9];
+    uint32_t affine;
+    uint32_t paint;
+    uint32_t pad;
+    float tint[4];
+};
+struct PaintHead {
+    uint32_t kind, spread, n_stops, first_stop;
+    float p0[2], d[2];
+    float dd;
+    uint32_t pad[3];
+};
+struct PaintStop {
+    float o, inv;
+    float c[4], dc[4];
+    float pad[2];
+};
+static_assert(sizeof(PaintItem) == 64 && sizeof(PaintHead) == 48 && sizeof(PaintStop) == 48, "load_uniform takes 16-byte multiples");
+struct PaintArgs {
+    const PaintItem* items;
+    const PaintHead* heads;
+    const PaintStop* stops;
+};
+// what k_paint_items reads besides: the Scene's association of instances with paints
+struct PaintTable {
+    PaintItem* items;             // [n_items]
+    const int32_t* instance_paint; // [n_instances] index into the paints, or -1: the solid colour
+    uint32_t n_instances;
+};
+
 constexpr uint32_t kTessStatusWord = 126; // ... the status word of the optimistic tessellation a pass drew (api.hip: crh_scene::optimistic), copied in by the host side
 constexpr uint32_t kExtraTurnsWord = 76; // of RasterParams::overflow: behind the 8 flag words and the 64 cursors of the pair sub-streams
 struct RasterParams {

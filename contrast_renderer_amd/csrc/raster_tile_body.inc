@@ -1,5 +1,5 @@
-// csrc/raster_tile_body.inc — the body of k_raster_tile<S, ROWS, OPS, STROKES> and k_raster_blend<S, STROKES> (raster.hip), included into
-// both kernels with S, ROWS, OPS, STROKES, BLEND and the blend form `bf` in scope. Included rather than shared as a __device__ function:
+// csrc/raster_tile_body.inc — the body of k_raster_tile<S, ROWS, OPS, STROKES>, k_raster_blend<S, STROKES> and k_raster_paint<S, STROKES>
+// (raster.hip), included into the three kernels with S, ROWS, OPS, STROKES, BLEND, the blend form `bf`, PAINT and the paint tables `pa` in scope. Included rather than shared as a __device__ function:
 // the instruction stream of k_raster_tile stays what it was (an inlined body changed its register allocation and scheduling). The steps in
 // front of the walk that every tile kernel takes — the tile of the workgroup's place, the sort of a list in place — are the helpers of
 // raster_tile_list.hpp: tools/resource_usage.py shows the same registers, scratch, occupancy and LDS for every instantiation with them.
@@ -418,7 +418,83 @@
             for (int b = 0; b < ROWS; ++b)
 #pragma unroll
                 for (int k = 0; k < S; ++k) winding[b][k] += dw[b][k];
-            if (BLEND && color_cover) { // color_cover with the renderer's blend state (api.hip blend_form; the target stands for an Rgba8Unorm attachment)
+            if (PAINT && BLEND && color_cover && frag.flat_u != 0u) {
+                // color_cover of a painted item (k_paint_items left item + 1 in flat_u; wave uniform): the source is paint(t) * instance colour per
+                // SAMPLE (include/contrast_hip.h crh_scene_set_paints states the model), premultiplied and blended as the block below blends its
+                // wave-uniform one. Four samples at a time — msaa 8 takes two turns — so that t and the paint's colour of four samples are live at once.
+                const PaintItem pi = load_uniform(&pa.items[frag.flat_u - 1u]);
+                const PaintHead ph = load_uniform(&pa.heads[pi.paint]);
+#pragma unroll
+                for (int g = 0; g < ROWS * S; g += 4) {
+                    int any_blend = 0;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) any_blend |= (int)blend[(g + c) / S][(g + c) % S];
+                    if (!__any(any_blend)) continue;
+                    float t[4], pc[4][4] = {};
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int b = (g + c) / S, k = (g + c) % S;
+                        const float fx = tx0 + sx[k], fy = ty0 + (sy0[k] + (float)(4 * b)); // the sample's place on the frame (exact)
+                        float X = fmaf(fy, pi.h[1], fmaf(fx, pi.h[0], pi.h[2])), Y = fmaf(fy, pi.h[4], fmaf(fx, pi.h[3], pi.h[5]));
+                        if (!pi.affine) { // wave uniform
+                            const float W = fmaf(fy, pi.h[7], fmaf(fx, pi.h[6], pi.h[8]));
+                            X = X / W;
+                            Y = Y / W;
+                        }
+                        const float ux = X - ph.p0[0], uy = Y - ph.p0[1];
+                        float v = ph.kind == CRH_PAINT_LINEAR ? fmaf(ux, ph.d[0], uy * ph.d[1]) / ph.dd : sqrtf(fmaf(ux, ux, uy * uy)) / ph.d[0];
+                        if (ph.spread == CRH_SPREAD_REPEAT) {
+                            v = v - floorf(v);
+                        } else if (ph.spread == CRH_SPREAD_REFLECT) {
+                            const float u = v - 2.0f * floorf(v * 0.5f);
+                            v = u <= 1.0f ? u : 2.0f - u;
+                        } else {
+                            v = clamp_unit(v);
+                        }
+                        t[c] = v;
+                    }
+                    for (uint32_t i = 0; i < ph.n_stops; ++i) { // wave uniform: the stop's record in scalar registers, a select per sample
+                        const PaintStop st = load_uniform(&pa.stops[ph.first_stop + i]);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            const bool here = i == 0u || t[c] >= st.o;
+                            const float f = fmaxf((t[c] - st.o) * st.inv, 0.0f);
+#pragma unroll
+                            for (int ch = 0; ch < 4; ++ch) pc[c][ch] = here ? fmaf(f, st.dc[ch], st.c[ch]) : pc[c][ch];
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int b = (g + c) / S, k = (g + c) % S;
+                        float src[4], us[4], ud[4];
+                        const float sa = pc[c][3] * pi.tint[3];
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch) src[ch] = clamp_unit((pc[c][ch] * pi.tint[ch]) * sa); // (rgb * a, a) as k_prim_setup premultiplies the solid colour
+                        src[3] = clamp_unit(sa);
+#pragma unroll
+                        for (int ch = 0; ch < 4; ++ch) {
+                            const int cc = ch == 3 ? 1 : 0;
+                            us[ch] = (bf.src.c0[ch] + bf.src.s[cc] * src[ch]) + bf.src.sa[cc] * src[3];
+                            ud[ch] = (bf.dst.c0[ch] + bf.dst.s[cc] * src[ch]) + bf.dst.sa[cc] * src[3];
+                        }
+                        const float ad = col[b][k][3];
+#pragma unroll
+                        for (int ch = 0; ch < 4; ++ch) {
+                            const int cc = ch == 3 ? 1 : 0;
+                            const float dc = col[b][k][ch];
+                            const float fs = fminf((us[ch] + bf.src.d[cc] * dc) + bf.src.da[cc] * ad, bf.src.cap0[cc] + bf.src.cap1[cc] * ad);
+                            const float fd = fminf((ud[ch] + bf.dst.d[cc] * dc) + bf.dst.da[cc] * ad, bf.dst.cap0[cc] + bf.dst.cap1[cc] * ad);
+                            const float ps = src[ch] * fs, qd = dc * fd;
+                            const float lin = bf.os[cc] * ps + bf.od[cc] * qd;
+                            const uint32_t bkind = bf.kind[cc]; // wave uniform
+                            float v = bkind == 0u ? lin : (bkind == 1u ? fminf(src[ch], dc) : (bkind == 2u ? fmaxf(src[ch], dc) : src[ch]));
+                            v = clamp_unit(v);
+                            if (rounds_writes<XFMT>(r)) v = attachment<XFMT>(r, ch, v);
+                            col[b][k][ch] = (blend[b][k] && ((bf.write_mask >> ch) & 1u) != 0u) ? v : dc;
+                        }
+                    }
+                }
+            } else if (BLEND && color_cover) { // color_cover with the renderer's blend state (api.hip blend_form; the target stands for an Rgba8Unorm attachment)
                 float src[4], us[4], ud[4];
 #pragma unroll
                 for (int ch = 0; ch < 4; ++ch) src[ch] = clamp_unit(frag.a0[ch]);

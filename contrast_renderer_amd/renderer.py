@@ -145,6 +145,64 @@ class ColorTargetState:
         return ColorTargetState(blend, ColorWrites(c.write_mask), tuple(float(v) for v in c.constant))
 
 
+class Spread(IntEnum):  # crh_spread: what a gradient does outside [0, 1]
+    Pad = 0
+    Repeat = 1
+    Reflect = 2
+
+
+class PaintKind(IntEnum):  # crh_paint_kind
+    Linear = 1
+    Radial = 2
+
+
+@dataclass(frozen=True)
+class GradientStop:  # crh_gradient_stop: offset in [0, 1], straight RGBA
+    offset: float
+    color: Tuple[float, float, float, float]
+
+
+@dataclass(frozen=True)
+class Paint:
+    """crh_paint: a linear or radial gradient in the Shape's path coordinates, the source of a Color cover in place of the instance's one
+    colour (include/contrast_hip.h crh_scene_set_paints states the model). Stops: GradientStop or (offset, (r, g, b, a)) pairs, at most 8."""
+    kind: int
+    spread: int
+    p0: Tuple[float, float]
+    p1: Tuple[float, float]
+    stops: Tuple[GradientStop, ...]
+
+    @staticmethod
+    def _stops(stops):
+        return tuple(s if isinstance(s, GradientStop) else GradientStop(float(s[0]), tuple(float(v) for v in s[1])) for s in stops)
+
+    @staticmethod
+    def linear(p0, p1, stops, spread=Spread.Pad):
+        """t = 0 at p0, t = 1 at p1."""
+        return Paint(PaintKind.Linear, spread, (float(p0[0]), float(p0[1])), (float(p1[0]), float(p1[1])), Paint._stops(stops))
+
+    @staticmethod
+    def radial(center, radius, stops, spread=Spread.Pad):
+        """t = distance from `center` / radius."""
+        return Paint(PaintKind.Radial, spread, (float(center[0]), float(center[1])), (float(radius), 0.0), Paint._stops(stops))
+
+    def to_c(self):
+        if not 0 < len(self.stops) <= _ffi.MAX_GRADIENT_STOPS:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"a paint has 1..{_ffi.MAX_GRADIENT_STOPS} stops, not {len(self.stops)}")
+        c = _ffi.PaintC()
+        c.kind, c.spread, c.n_stops = int(self.kind), int(self.spread), len(self.stops)
+        c.p0[0], c.p0[1], c.p1[0], c.p1[1] = self.p0[0], self.p0[1], self.p1[0], self.p1[1]
+        for i, s in enumerate(self.stops):
+            c.stops[i].offset = s.offset
+            for ch in range(4):
+                c.stops[i].color[ch] = s.color[ch]
+        return c
+
+    def validate(self):
+        """crh_paint_validate (host only): raises ContrastError for what crh_scene_set_paints would refuse."""
+        check(_ffi.load_library().crh_paint_validate(C.byref(self.to_c())))
+
+
 @dataclass
 class Configuration:  # renderer.rs:380-405 (fields that change results on this path)
     msaa_sample_count: int = 1  # 1, 2, 4 or 8, standard sample locations (include/contrast_hip.h); any other count: ContrastError (CRH_ERR_UNSUPPORTED)
@@ -408,6 +466,7 @@ class Scene:
         if existing is not None:
             existing.handle = None  # moved in, as `existing_shape` is in renderer.rs:182
         self.handle = handle
+        self._pass_paints = getattr(existing, "_pass_paints", None)  # the paint table a RenderPass installed stays with the C scene
         self.n_shapes = batch.n_shapes
         if tessellate:
             self.tessellate()
@@ -451,16 +510,43 @@ class Scene:
         fp = C.POINTER(C.c_float)
         check(self.lib.crh_scene_set_instances(self.handle, t.ctypes.data_as(fp), c.ctypes.data_as(fp)))
 
+    def set_paints(self, paints, instance_paint):
+        """crh_scene_set_paints: `paints` = [Paint], `instance_paint[i]` = the index of instance i's paint or -1 for its solid colour (instances
+        beyond the list are solid). Stays with the Scene until the next call; an empty `paints` clears it. The call waits for the renderer's
+        work in flight (the kernels of a pass read the table): set it when it changes, not per frame."""
+        self._install_paints(paints, instance_paint)
+        self._pass_paints = None  # the caller's own table: passes without paints leave it alone
+
+    def _install_paints(self, paints, instance_paint):
+        table = (_ffi.PaintC * max(1, len(paints)))(*[p.to_c() for p in paints])
+        which = np.ascontiguousarray(instance_paint, dtype=np.int32).ravel()
+        check(self.lib.crh_scene_set_paints(self.handle, table if len(paints) else None, len(paints), which.ctypes.data_as(C.POINTER(C.c_int32)) if len(which) else None, len(which)))
+
+    def _paints_of_pass(self, paints, instance_paint):
+        """What RenderPass.submit asks for in front of its draws: the pass's table (None: the pass has no paints). A table an earlier pass put here
+        belongs to that pass's instance numbering, so it is replaced or removed; the call is skipped when the Scene already holds this very table."""
+        key = (tuple(paints), tuple(instance_paint)) if paints else None
+        if key == getattr(self, "_pass_paints", None):
+            return
+        if key is None:
+            self._install_paints([], [])
+        else:
+            self._install_paints(paints, instance_paint)
+        self._pass_paints = key
+
     def render(self, frame: Frame, transforms=None, colors=None):
         """Stencil + Color of every shape in index order (the loop of examples/showcase/main.rs:236-250)."""
+        self._paints_of_pass(None, None)  # (a table a RenderPass left belongs to that pass's instances)
         if transforms is not None:
             self.set_instances(transforms, colors)
         check(self.lib.crh_scene_render_resident(self.handle, frame.handle))
 
-    def render_draws(self, frame: Frame, transforms, colors, draws):
+    def render_draws(self, frame: Frame, transforms, colors, draws, _from_pass=False):
         """A recorded render pass: draws = [(shape, instance, RenderOperation, clip_depth, alpha_layer), ...] — one tuple per
         Shape::render call (renderer.rs:267-273) with the clip depth (Renderer::set_clip_depth, renderer.rs:932-938) and alpha layer
         (save/restore_alpha_context, renderer.rs:941-985) in effect. `instance` indexes transforms / colors (instancing)."""
+        if not _from_pass:
+            self._paints_of_pass(None, None)  # (a table a RenderPass left belongs to that pass's instances; the caller's own table stays)
         t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 16)
         c = np.ascontiguousarray(colors, dtype=np.float32).reshape(-1, 4)
         assert len(t) == len(c)
@@ -522,12 +608,20 @@ class RenderPass:
     def __init__(self, renderer: Renderer, frame: Frame):
         self.renderer, self.frame = renderer, frame
         self.transforms, self.colors, self.draws = [], [], []  # draws: (scene, shape, instance, op, clip_depth, alpha_layer)
+        self.paints, self.instance_paint = [], []  # the pass's paints and, per instance, the index of its paint or -1
         self.clip_depth = self.alpha_layer = 0
 
-    def push_instance(self, transform, color):
-        """Instance data of the pass (the instance buffers bound at slots 0 / 2, renderer.rs:462-466): returns the instance index."""
+    def push_instance(self, transform, color, paint=None):
+        """Instance data of the pass (the instance buffers bound at slots 0 / 2, renderer.rs:462-466): returns the instance index.
+        `paint`: a Paint that takes the place of `color` as the source of the instance's Color covers (times `color`)."""
         self.transforms.append(np.asarray(transform, dtype=np.float32).reshape(16))
         self.colors.append(np.asarray(color, dtype=np.float32).reshape(4))
+        if paint is None:
+            self.instance_paint.append(-1)
+        else:
+            if paint not in self.paints:
+                self.paints.append(paint)
+            self.instance_paint.append(self.paints.index(paint))
         return len(self.colors) - 1
 
     def set_clip_depth(self, clip_depth):  # Renderer::set_clip_depth, renderer.rs:932-938
@@ -553,7 +647,10 @@ class RenderPass:
             end = begin
             while end < len(self.draws) and self.draws[end][0] is self.draws[begin][0]:
                 end += 1
-            self.draws[begin][0].render_draws(self.frame, np.stack(self.transforms), np.stack(self.colors), [d[1:] for d in self.draws[begin:end]])
+            # every Scene of the pass draws with the pass's paints; a pass without any removes what an earlier pass installed (whose instance
+            # indices are not this pass's) and leaves a table the caller set with Scene.set_paints alone
+            self.draws[begin][0]._paints_of_pass(self.paints, self.instance_paint)
+            self.draws[begin][0].render_draws(self.frame, np.stack(self.transforms), np.stack(self.colors), [d[1:] for d in self.draws[begin:end]], _from_pass=True)
             begin = end
         self.draws = []
 

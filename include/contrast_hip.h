@@ -366,6 +366,47 @@ typedef struct crh_draw {
 crh_status crh_scene_render_draws(crh_scene* scene, crh_frame* frame, const float* transforms, const float* colors, uint32_t n_instances,
                                   const crh_draw* draws, uint32_t n_draws);
 
+/* Gradient paints: the source of a Color cover, per sample, in place of the instance's one colour (what a user of the reference does with a
+ * cover pipeline of their own). The model, which the tests check against float64:
+ *   coordinates  a paint lives in the Shape's path coordinates: it moves, scales and tilts with the instance transform. p is the sample's
+ *                position in those coordinates (Shapes lie in z = 0: the sample's place on the frame through the inverse of the
+ *                3x3 homography made of columns 0, 1, 3 and rows x, y, w of the transform and the clip -> pixel map).
+ *   linear       t = dot(p - p0, p1 - p0) / dot(p1 - p0, p1 - p0)
+ *   radial       t = |p - p0| / radius         (p0 the centre, radius = p1[0] > 0, p1[1] = 0)
+ *   spread       PAD: t = clamp(t, 0, 1); REPEAT: t = t - floor(t); REFLECT: u = t - 2 floor(t / 2), t = u <= 1 ? u : 2 - u
+ *   stops        offsets non-decreasing in [0, 1]. In front of the first stop its colour, behind the last stop its colour; between stops i and
+ *                i + 1 with o_i < o_i+1: c_i + f (c_i+1 - c_i), f = (t - o_i) / (o_i+1 - o_i), per straight-alpha channel — equal stop colours
+ *                give that colour back exactly. Two stops with one offset make a hard edge; at t equal to it the later stop wins.
+ *   source       paint(t) * instance colour per channel (straight alpha), premultiplied as the solid colour is (rgb * a, a), then blended with
+ *                the renderer's blend state as crh_renderer_create_blended describes: source clamped to [0, 1], the frame format's rounding of
+ *                writes, the write mask. Under the default "over" state a painted pass evaluates "over" in that same form: a painted cover is
+ *                always the Rgba8Unorm-attachment model (clamped source and result), never the unclamped float arithmetic of the solid fast path.
+ * `instance_paint[i]` is the index into `paints` of instance i's paint, or -1 for its solid colour; instances at index n_instances and beyond are
+ * solid. The table is copied and stays with the Scene until the next call; n_paints == 0 clears it. It applies to crh_scene_render,
+ * _render_resident (instance i = Shape i) and _render_draws, and to the Color operation only — the other six ignore it. A pass that draws a
+ * painted instance runs the general triangle kernel (as a blend state other than "over" does); every other pass is launched as before.
+ * Errors: a non-finite field CRH_ERR_NON_FINITE; an unknown kind or spread, n_stops 0 or > CRH_MAX_GRADIENT_STOPS, decreasing offsets or one outside
+ * [0, 1], a linear paint with p0 == p1 (precisely: whose dot(p1 - p0, p1 - p0), evaluated in f32, is not a positive finite number — it may
+ * underflow or overflow for p0 != p1), a radial one with radius <= 0, an instance_paint entry >= n_paints or < -1: CRH_ERR_INVALID_ARGUMENT with a
+ * crh_last_error text. A failed call leaves the Scene's previous table in place.
+ * The table's p1 - p0 and dot(p1 - p0, p1 - p0) are evaluated once, in f32, when the call builds the table. The call settles the frames drawn
+ * from the Scene and waits for the renderer's work in flight (kernels read the table): set a table when it changes, not once per frame. */
+#define CRH_MAX_GRADIENT_STOPS 8
+typedef enum crh_paint_kind { CRH_PAINT_LINEAR = 1, CRH_PAINT_RADIAL = 2 } crh_paint_kind;
+typedef enum crh_spread { CRH_SPREAD_PAD = 0, CRH_SPREAD_REPEAT = 1, CRH_SPREAD_REFLECT = 2 } crh_spread;
+typedef struct crh_gradient_stop {
+    float offset;
+    float color[4]; /* straight RGBA */
+} crh_gradient_stop;
+typedef struct crh_paint {
+    uint32_t kind, spread; /* crh_paint_kind, crh_spread */
+    float p0[2], p1[2];    /* linear: t = 0 at p0, t = 1 at p1; radial: centre p0, radius p1[0] (> 0), p1[1] = 0 */
+    uint32_t n_stops;      /* 1..CRH_MAX_GRADIENT_STOPS */
+    crh_gradient_stop stops[CRH_MAX_GRADIENT_STOPS];
+} crh_paint;
+crh_status crh_paint_validate(const crh_paint* paint); /* host only: needs no renderer and no device */
+crh_status crh_scene_set_paints(crh_scene* scene, const crh_paint* paints, uint32_t n_paints, const int32_t* instance_paint, uint32_t n_instances);
+
 /* LoadOp::Load of caller content: `rgba8` = width*height*4 bytes of premultiplied RGBA8, row 0 = top, replace the frame's pixels; every
  * sample of a pixel starts from its value. The stencil attachment, the saved alpha layers and the pass state are reset as by
  * crh_frame_clear, the depth attachment is left alone. The frame is NOT cleared afterwards: the next pass loads these pixels. Ordered

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -558,6 +559,39 @@ struct ShapeBuffers { // the byte image Shape::from_paths uploads (renderer.rs:1
 
 class RenderPass;
 
+// Gradient paints: the source of a Color cover in place of the instance's one colour (include/contrast_hip.h crh_scene_set_paints states the model)
+enum class Spread : uint32_t { Pad = CRH_SPREAD_PAD, Repeat = CRH_SPREAD_REPEAT, Reflect = CRH_SPREAD_REFLECT };
+struct GradientStop {
+    float offset;               // in [0, 1], non-decreasing along the stops
+    std::array<float, 4> color; // straight RGBA
+};
+class Paint {
+  public:
+    // t = 0 at p0, t = 1 at p1
+    static Paint linear(const std::array<float, 2>& p0, const std::array<float, 2>& p1, const std::vector<GradientStop>& stops, Spread spread = Spread::Pad) {
+        return Paint(CRH_PAINT_LINEAR, spread, p0, p1, stops);
+    }
+    // t = distance from `center` / radius
+    static Paint radial(const std::array<float, 2>& center, float radius, const std::vector<GradientStop>& stops, Spread spread = Spread::Pad) {
+        return Paint(CRH_PAINT_RADIAL, spread, center, {radius, 0.0f}, stops);
+    }
+    void validate() const { check(crh_paint_validate(&c_)); } // host only: throws what Scene::set_paints would
+    const crh_paint& to_c() const { return c_; }
+
+  private:
+    Paint(uint32_t kind, Spread spread, const std::array<float, 2>& p0, const std::array<float, 2>& p1, const std::vector<GradientStop>& stops) {
+        if (stops.empty() || stops.size() > CRH_MAX_GRADIENT_STOPS) throw Error(CRH_ERR_INVALID_ARGUMENT);
+        c_ = crh_paint{};
+        c_.kind = kind, c_.spread = (uint32_t)spread, c_.n_stops = (uint32_t)stops.size();
+        c_.p0[0] = p0[0], c_.p0[1] = p0[1], c_.p1[0] = p1[0], c_.p1[1] = p1[1];
+        for (size_t i = 0; i < stops.size(); ++i) {
+            c_.stops[i].offset = stops[i].offset;
+            for (int ch = 0; ch < 4; ++ch) c_.stops[i].color[ch] = stops[i].color[(size_t)ch];
+        }
+    }
+    crh_paint c_;
+};
+
 // A batch of Shapes built together (one launch tessellates all of them). Shape below is the n == 1 case with the reference's signature.
 class Scene {
   public:
@@ -565,7 +599,10 @@ class Scene {
         const crh_path_batch view = batch.view();
         // `existing` is given up only once the upload has taken it over: a batch that fails validation leaves it with its owner
         check(crh_scene_upload(renderer.raw(), &view, existing ? existing->raw() : nullptr, &handle_));
-        if (existing) existing->release();
+        if (existing) {
+            existing->release();
+            pass_table_ = std::move(existing->pass_table_), pass_assoc_ = std::move(existing->pass_assoc_), holds_pass_table_ = existing->holds_pass_table_; // (the C scene keeps its table)
+        }
         crh_status st = crh_scene_tessellate(handle_);
         if (st == CRH_OK) st = crh_scene_status(handle_); // surfaces the reference's panics at the call site, like the reference
         if (st != CRH_OK) { // a constructor that throws runs no destructor: free the handle here
@@ -577,7 +614,8 @@ class Scene {
     ~Scene() {
         if (handle_) crh_scene_destroy(handle_);
     }
-    Scene(Scene&& other) noexcept : handle_(other.release()), n_shapes_(other.n_shapes_) {}
+    Scene(Scene&& other) noexcept
+        : handle_(other.release()), n_shapes_(other.n_shapes_), pass_table_(std::move(other.pass_table_)), pass_assoc_(std::move(other.pass_assoc_)), holds_pass_table_(other.holds_pass_table_) {}
     Scene(const Scene&) = delete;
     Scene& operator=(const Scene&) = delete;
     uint32_t n_shapes() const { return n_shapes_; }
@@ -597,7 +635,31 @@ class Scene {
     // Stencil + Color of every Shape in index order, instance i = Shape i (the loop of examples/showcase/main.rs:236-250)
     void render(Frame& frame, const std::vector<float>& transforms, const std::vector<float>& colors) {
         if (transforms.size() != (size_t)n_shapes_ * 16 || colors.size() != (size_t)n_shapes_ * 4) throw Error(CRH_ERR_INVALID_ARGUMENT);
+        paints_of_pass({}, {}); // (a table a RenderPass left belongs to that pass's instances)
         check(crh_scene_render(handle_, frame.raw(), transforms.data(), colors.data()));
+    }
+    // crh_scene_set_paints: instance_paint[i] = the index into `paints` of instance i's paint, or -1 for its solid colour; stays until the next call,
+    // no paints clears it. The call waits for the renderer's work in flight: set the table when it changes, not per frame.
+    void set_paints(const std::vector<Paint>& paints, const std::vector<int32_t>& instance_paint) const {
+        install_paints(paints, instance_paint);
+        holds_pass_table_ = false; // the caller's own table: passes without paints leave it alone
+    }
+    // What RenderPass::submit asks for in front of its draws: the pass's table (none: the pass has no paints). A table an earlier pass put here
+    // belongs to that pass's instance numbering, so it is replaced or removed; the call is skipped when the Scene already holds this very table.
+    void paints_of_pass(const std::vector<Paint>& paints, const std::vector<int32_t>& instance_paint) const {
+        if (paints.empty()) {
+            if (holds_pass_table_) install_paints({}, {});
+            holds_pass_table_ = false;
+            return;
+        }
+        bool same = holds_pass_table_ && pass_table_.size() == paints.size() && pass_assoc_ == instance_paint;
+        for (size_t i = 0; same && i < paints.size(); ++i) same = std::memcmp(&pass_table_[i], &paints[i].to_c(), sizeof(crh_paint)) == 0;
+        if (same) return;
+        install_paints(paints, instance_paint);
+        pass_table_.clear();
+        for (const Paint& p : paints) pass_table_.push_back(p.to_c());
+        pass_assoc_ = instance_paint;
+        holds_pass_table_ = true;
     }
     crh_scene* raw() const { return handle_; }
     crh_scene* release() {
@@ -607,8 +669,17 @@ class Scene {
     }
 
   private:
+    void install_paints(const std::vector<Paint>& paints, const std::vector<int32_t>& instance_paint) const {
+        std::vector<crh_paint> table;
+        for (const Paint& p : paints) table.push_back(p.to_c());
+        check(crh_scene_set_paints(handle_, table.data(), (uint32_t)table.size(), instance_paint.data(), (uint32_t)instance_paint.size()));
+    }
     crh_scene* handle_ = nullptr;
     uint32_t n_shapes_ = 0;
+    // the paint table a RenderPass installed (none: the Scene holds the caller's own table, or nothing)
+    mutable std::vector<crh_paint> pass_table_;
+    mutable std::vector<int32_t> pass_assoc_;
+    mutable bool holds_pass_table_ = false;
 };
 
 // wgpu::RenderPass stand-in: records Shape::render calls with the pass state they see and submits them as one draw list.
@@ -619,7 +690,15 @@ class RenderPass {
     uint32_t push_instance(const float (&transform)[16], const float (&color)[4]) {
         transforms_.insert(transforms_.end(), transform, transform + 16);
         colors_.insert(colors_.end(), color, color + 4);
+        instance_paint_.push_back(-1);
         return (uint32_t)(colors_.size() / 4 - 1);
+    }
+    // ... with a paint as the source of the instance's Color covers (times `color`); the pass hands its paints to every Scene it submits to
+    uint32_t push_instance(const float (&transform)[16], const float (&color)[4], const Paint& paint) {
+        const uint32_t index = push_instance(transform, color);
+        instance_paint_.back() = (int32_t)paints_.size();
+        paints_.push_back(paint);
+        return index;
     }
     // Renderer::set_clip_depth (renderer.rs:932-938)
     void set_clip_depth(size_t clip_depth) {
@@ -650,6 +729,7 @@ class RenderPass {
         for (size_t begin = 0; begin < draws_.size();) {
             size_t end = begin;
             while (end < draws_.size() && scenes_[end] == scenes_[begin]) ++end;
+            scenes_[begin]->paints_of_pass(paints_, instance_paint_); // (a pass without paints removes what an earlier pass installed)
             check(crh_scene_render_draws(scenes_[begin]->raw(), frame_.raw(), transforms_.data(), colors_.data(), (uint32_t)(colors_.size() / 4), draws_.data() + begin, (uint32_t)(end - begin)));
             begin = end;
         }
@@ -661,6 +741,8 @@ class RenderPass {
     Configuration config_;
     Frame& frame_;
     std::vector<float> transforms_, colors_;
+    std::vector<Paint> paints_;
+    std::vector<int32_t> instance_paint_; // per instance: index into paints_, or -1
     std::vector<crh_draw> draws_;
     std::vector<const Scene*> scenes_; // the object every draw belongs to
     uint32_t clip_depth_ = 0, alpha_layer_ = 0;

@@ -687,6 +687,47 @@ impl Scene {
         })
     }
 }
+/// What a gradient does outside [0, 1] (`crh_spread`)
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum Spread {
+    Pad = 0,
+    Repeat = 1,
+    Reflect = 2,
+}
+/// A linear or radial gradient in the Shape's path coordinates: the source of a Color cover in place of the instance's one colour
+/// (include/contrast_hip.h, `crh_scene_set_paints`, states the model). Stops are (offset, straight RGBA), at most 8.
+#[derive(Clone, Copy)]
+pub struct Paint(pub ffi::crh_paint);
+impl Paint {
+    fn with(kind: u32, spread: Spread, p0: [f32; 2], p1: [f32; 2], stops: &[(f32, [f32; 4])]) -> Self {
+        assert!(!stops.is_empty() && stops.len() <= 8);
+        let mut table = [ffi::crh_gradient_stop { offset: 0.0, color: [0.0; 4] }; 8];
+        for (slot, &(offset, color)) in table.iter_mut().zip(stops) {
+            *slot = ffi::crh_gradient_stop { offset, color };
+        }
+        Paint(ffi::crh_paint { kind, spread: spread as u32, p0, p1, n_stops: stops.len() as u32, stops: table })
+    }
+    /// t = 0 at `p0`, t = 1 at `p1`
+    pub fn linear(p0: [f32; 2], p1: [f32; 2], stops: &[(f32, [f32; 4])], spread: Spread) -> Self {
+        Self::with(1, spread, p0, p1, stops)
+    }
+    /// t = distance from `center` / `radius`
+    pub fn radial(center: [f32; 2], radius: f32, stops: &[(f32, [f32; 4])], spread: Spread) -> Self {
+        Self::with(2, spread, center, [radius, 0.0], stops)
+    }
+    /// Host only: what `Scene::set_paints` would refuse
+    pub fn validate(&self) -> Result<(), Error> {
+        status(unsafe { ffi::crh_paint_validate(&self.0) })
+    }
+}
+impl Scene {
+    /// `instance_paint[i]` = the index into `paints` of instance i's paint, or -1 for its solid colour. Stays with the Scene until the next
+    /// call; no paints clears it.
+    pub fn set_paints(&self, paints: &[Paint], instance_paint: &[i32]) -> Result<(), Error> {
+        let table: Vec<ffi::crh_paint> = paints.iter().map(|p| p.0).collect();
+        status(unsafe { ffi::crh_scene_set_paints(self.raw, table.as_ptr(), table.len() as u32, instance_paint.as_ptr(), instance_paint.len() as u32) })
+    }
+}
 impl Drop for Scene {
     fn drop(&mut self) {
         unsafe { ffi::crh_scene_destroy(self.raw) }
