@@ -8,15 +8,14 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ("tessellate.hip", "raster.hip", "raster_edges.hip", "api.hip", "comm.hip", "text.cpp", "path.cpp")  # text.cpp / path.cpp: host-only (text.rs, path.rs:639-708)
-HEADERS = ("ga.hpp", "fill.hpp", "stroke.hpp", "scene.hpp", "raster_params.hpp", "raster_common.hpp", "raster_tile_list.hpp", "raster_tile_body.inc", "launch.hpp", "srgb_tables.h", "../../include/contrast_hip.h", "../../include/crh_fmath.h")
+SOURCES = ("tessellate.hip", "raster.hip", "bin_edges.hip", "raster_edges.hip", "api.hip", "comm.hip", "text.cpp", "path.cpp")  # text.cpp / path.cpp: host-only (text.rs, path.rs:639-708)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical"]
-# Per-file flags. raster_edges.hip without LLVM's SLP vectorizer (round 6): it packs pairs of independent f32 operations of the per-sample code into
+# Per-file flags. raster_edges.hip and bin_edges.hip (one file when this was measured) without LLVM's SLP vectorizer (round 6): it packs pairs of independent f32 operations of the per-sample code into
 # v_pk_* instructions, whose operands are register PAIRS — lane-invariant values (sample positions, the tile's origin) end up duplicated in pairs that live
 # for the whole kernel, and the raster kernels spilled exactly those (k_raster_edges<4,1,true,false>: 100 B of scratch per lane -> 12, 96 -> 95 registers;
 # k_raster_fill 94 -> 76 registers; k_raster_rows 112 -> 95). Same results bit for bit (no contraction either way); S10k raster kernel 0.166 -> 0.151 ms alone,
 # dashed scene 1.557 -> 1.481 (profiles/r06_experiments.txt). CRH_FILE_FLAGS="file.hip:-flag,-flag;..." replaces the table (A/B runs).
-FILE_FLAGS = {"raster_edges.hip": ["-fno-slp-vectorize"], "raster.hip": ["-fno-slp-vectorize"], "tessellate.hip": ["-fno-slp-vectorize"]}  # (raster.hip: k_raster_tile<4,1,true,true> 150 -> 127 registers; tessellate.hip: k_tess_runs<true> 182 -> 146)
+FILE_FLAGS = {"raster_edges.hip": ["-fno-slp-vectorize"], "bin_edges.hip": ["-fno-slp-vectorize"], "raster.hip": ["-fno-slp-vectorize"], "tessellate.hip": ["-fno-slp-vectorize"]}  # (raster.hip: k_raster_tile<4,1,true,true> 150 -> 127 registers; tessellate.hip: k_tess_runs<true> 182 -> 146)
 OUT = os.path.join(HERE, "libcontrast_hip.so")
 
 
@@ -25,6 +24,13 @@ def _newer(target, deps):
         return False
     t = os.path.getmtime(target)
     return all(os.path.getmtime(d) <= t for d in deps if os.path.exists(d))
+
+
+def header_deps():
+    """What every object is rebuilt after: each header csrc/ holds and the two public ones the sources include. Listed from the directory, so that a
+    new header cannot be forgotten (a missing one made _newer reuse a stale object silently)."""
+    own = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h", ".inc")))
+    return own + [os.path.join(HERE, "..", "include", h) for h in ("contrast_hip.h", "crh_fmath.h")]
 
 
 def file_flags():
@@ -40,7 +46,7 @@ def file_flags():
 
 def build_library(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, h) for h in HEADERS]
+    headers = header_deps()
     objects = []
     procs = []
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
@@ -84,6 +90,7 @@ def write_export_map():
     """build/exports.map: a linker version script listing exactly the header's entry points. Everything else — the C++ internals shared by
     the translation units (crh::launch_*), the crh_internal_* accessors comm.hip uses, HIP's kernel stubs — stays local to the library."""
     path = os.path.join(HERE, "build", "exports.map")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
     text = "{\n  global:\n" + "".join(f"    {name};\n" for name in declared_entry_points() + list(DEBUG_TAPS)) + "  local:\n    *;\n};\n"
     if not os.path.exists(path) or open(path).read() != text:
         with open(path, "w") as f:

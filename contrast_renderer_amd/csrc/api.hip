@@ -460,7 +460,7 @@ struct crh_scene {
         uint64_t emitted_bytes = 0;
     } shadow;
     bool tessellated_once = false;
-    // Which formulation draws this Scene's plain passes — boundary edges + backdrops (raster_edges.hip) or the reference's strip triangles
+    // Which formulation draws this Scene's plain passes — boundary edges + backdrops (bin_edges.hip, raster_edges.hip) or the reference's strip triangles
     // (raster.hip) — is decided by MEASUREMENT: both give the same pixels, and which is faster depends on the content (long strips
     // across many tiles favour the edges, tens of thousands of glyph-sized Shapes the triangles: the edge pass pays per item and per
     // (item, tile)). Frames 0-5 after an upload run the edge pass, frames 6-11 the triangle pass. The first frame of each is the verified
@@ -1206,7 +1206,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     p.depth_write = r->config.depth_write_enabled;
     p.cull_mode = r->config.cull_mode;
     // The general pass keeps the reference's triangle strips (raster.hip): clip nesting / alpha contexts, perspective, depth, and face
-    // culling (a cull decision is per strip triangle). Everything else is the edge pass (raster_edges.hip).
+    // culling (a cull decision is per strip triangle). Everything else is the edge pass (bin_edges.hip, raster_edges.hip).
     // a pass that draws a painted instance with a Color cover (crh_scene_set_paints); a Scene without paints asks nothing
     bool painted = false;
     if (sc->n_paints != 0u) {

@@ -1,4 +1,4 @@
-// csrc/launch.hpp — the interface between the translation units: what api.hip calls in tessellate.hip, raster.hip and raster_edges.hip, and
+// csrc/launch.hpp — the interface between the translation units: what api.hip calls in tessellate.hip, raster.hip, bin_edges.hip and raster_edges.hip, and
 // what those call in each other. Included by the callers AND by every file that defines one of these, so that the compiler checks each
 // definition against its declaration.
 #pragma once
@@ -34,7 +34,7 @@ void launch_state_colors_from_image(const RasterParams& r, uint32_t samples, hip
 void launch_selftest_srgb(const float* x, uint8_t* codes, uint64_t n, float* decoded, hipStream_t stream);
 void launch_composite(const uint8_t* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, uint8_t* dst, hipStream_t stream);
 
-// raster_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop, binned in one traversal
+// bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);
 uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin); // -> BinRoute | items per workgroup << 16
 void launch_scatter(const RasterParams& r, hipStream_t stream, MarkFn mark, void* ctx);
@@ -45,6 +45,8 @@ bool bin_itemwise(const RasterParams& r);
 void flat_batches(const uint32_t* cost, uint32_t n_items, std::vector<uint32_t>& runs);
 void flat_batch_limits(uint32_t n_items, uint32_t limits[4]);
 void launch_tile_bases(const uint32_t* tile_count, uint32_t* caps, uint32_t* tile_base, uint32_t* scratch, uint32_t n_tiles, uint32_t tiles_x, uint32_t radius, hipStream_t stream);
+
+// raster_edges.hip: the per-tile raster kernels of that pass
 uint32_t launch_raster_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke); // -> RasterVariant
 
 } // namespace crh

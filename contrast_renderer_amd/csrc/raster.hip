@@ -709,7 +709,7 @@ static void launch_prim_setup_walk(const SceneDev& s, const RasterParams& r, hip
 // launchers of the triangle pass launch nothing for a sample count it does not draw (api.hip render_impl refuses such a pass up front).
 void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup) {
     if (!triangle_pass_samples(samples)) return;
-    // tile_cursor, tile_count and the overflow words are adjacent: one memset ([5] belongs to the edge pass (raster_edges.hip); cleared so that the host never sees a stale flag)
+    // tile_cursor, tile_count and the overflow words are adjacent: one memset ([5] belongs to the edge pass (bin_edges.hip); cleared so that the host never sees a stale flag)
     (void)hipMemsetAsync(r.tile_cursor, 0, sizeof(uint32_t) * 2u * r.n_tiles + 32, stream);
     switch (samples) {
         case 1: launch_prim_setup_walk<1>(s, r, stream, mark, ctx, after_setup); break;
@@ -800,7 +800,7 @@ uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t sample
     if (mark) mark(ctx, "raster_tiles", raster_bytes);
     return (r.general || blend) ? kRasterOps : kRasterTile;
 }
-// exported to raster_edges.hip
+// exported to bin_edges.hip
 void launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t* block_sum, uint32_t n, hipStream_t stream) {
     const ScanJob j = scan_job(in, out, block_sum, n);
     RasterParams unused = {};

@@ -1,7 +1,7 @@
 // csrc/raster_common.hpp — what the two raster paths share: the set-up triangle records, candidate numbering of a Shape, the vertex
 // stage and the stroke fragment stages of shaders.wgsl:165-231. raster.hip is the general path (recorded passes with clip nesting / alpha
-// contexts, perspective instances, depth, culling: triangle strips exactly as the reference draws them); raster_edges.hip is the plain
-// Stencil + Color pass (boundary edges + backdrop for the polygon interiors, one binning traversal).
+// contexts, perspective instances, depth, culling: triangle strips exactly as the reference draws them); bin_edges.hip and raster_edges.hip
+// are the plain Stencil + Color pass (boundary edges + backdrop for the polygon interiors: one binning traversal, then the per-tile kernels).
 #pragma once
 #include "ga.hpp"
 #include "raster_params.hpp"

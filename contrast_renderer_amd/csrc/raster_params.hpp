@@ -12,7 +12,7 @@ namespace crh {
 struct PrimRec;
 struct PrimProj;
 
-// The sample counts the triangle pass draws (Configuration::msaa_sample_count). The edge pass (raster_edges.hip) draws 1 and 4 only: its
+// The sample counts the triangle pass draws (Configuration::msaa_sample_count). The edge pass (bin_edges.hip, raster_edges.hip) draws 1 and 4 only: its
 // 16-bit row masks and 4x4 sample transposes are built for those two layouts.
 constexpr bool triangle_pass_samples(uint32_t samples) { return samples == 1u || samples == 2u || samples == 4u || samples == 8u; }
 constexpr bool edge_pass_samples(uint32_t samples) { return samples == 1u || samples == 4u; }
@@ -127,7 +127,7 @@ struct RasterParams {
     uint32_t cull_mode;               // crh_cull of the colour cover
     uint32_t debug;                   // CRH_RASTER_DEBUG (tools only)
     uint32_t occlude;                 // every colour of the pass has 0 <= alpha <= 1 and |rgb| <= 1e30: a tile's list may be started late (k_raster_edges)
-    // ---- the edge pass (raster_edges.hip): the plain Stencil + Color pass binned in ONE traversal
+    // ---- the edge pass (bin_edges.hip, raster_edges.hip): the plain Stencil + Color pass binned in ONE traversal
     uint8_t* slots;                   // [slot_capacity][32 B] primitive heap: set-up triangles (4 slots), boundary edges and per-item cover slots (1 slot)
     uint32_t slot_capacity;
     const uint32_t* slot_begin;       // [n_items + 1] first slot of every item (a multiple of 4); slot numbers ascend in draw order and are the sort keys
@@ -148,7 +148,7 @@ struct RasterParams {
     const uint32_t* tile_order;       // [workgroups of the raster grid] the tile each workgroup of the edge pass' raster kernels draws (0xFFFFFFFF: none), or nullptr: the kernels' own XCD-aware order
     // k_bin_flat's batches by what they cost (round 4): a verified pass writes, per item, what the item takes of a batch's tables
     // (item_cost[2 i] = tile cells of its rectangle, [2 i + 1] = triangles | edges << 9 | 1 << 29 if its hull strip folds | 1 << 31 if it is not binned there at all); the
-    // host cuts the items into runs that fill ONE batch each (flat_batches, raster_edges.hip) and later passes start one workgroup per run.
+    // host cuts the items into runs that fill ONE batch each (flat_batches, bin_edges.hip) and later passes start one workgroup per run.
     uint32_t* item_cost;              // [2 n_items] or nullptr
     const uint32_t* bin_batches;      // [2 n_bin_batches] first item of every run and the one behind its last, the long runs first, or nullptr: equal numbers of items
     uint32_t n_bin_batches;           // (overflow[kExtraTurnsWord]: turns beyond the first that the runs' workgroups needed — stale costs)

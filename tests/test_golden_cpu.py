@@ -112,7 +112,7 @@ def test_header_is_plain_c():
 
 
 def test_binning_runs_partition_the_items_within_a_batch_and_start_with_the_long_ones(monkeypatch):
-    """Host logic of the binning kernel's batches by cost (csrc/raster_edges.hip flat_batches; no device involved): whatever the items cost,
+    """Host logic of the binning kernel's batches by cost (csrc/bin_edges.hip flat_batches; no device involved): whatever the items cost,
     the runs partition 0 .. n in order, every run fits ONE batch (items, triangles, edges, tile cells), an item wider than the pool is a run
     of its own, an item that is not binned there takes a place but nothing else, and the runs come longest predicted life first."""
     import ctypes as C

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host: compile one csrc/*.hip with -Rpass-analysis=kernel-resource-usage and print one line per kernel
-(VGPRs, AGPRs, SGPRs, scratch bytes per lane, occupancy, LDS). Usage: tools/resource_usage.py raster_edges.hip [extra hipcc flags...]"""
+(VGPRs, AGPRs, SGPRs, scratch bytes per lane, occupancy, LDS). Usage: tools/resource_usage.py raster_edges.hip [extra hipcc flags...]   (or bin_edges.hip, raster.hip, tessellate.hip)"""
 import os
 import re
 import subprocess
