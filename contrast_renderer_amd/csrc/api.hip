@@ -1238,8 +1238,9 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         g_error = "no raster pass draws this sample count";
         return CRH_ERR_UNSUPPORTED;
     }
-    // k_raster_rows keeps fill + 65536 * hull in one cell: exact below 2^15 entries per tile. Lists in place grow by half at most between two
-    // verified passes, so a frame that has ever shown a list of 16 384 entries keeps the per-sample kernel.
+    // k_raster_rows keeps fill + 65536 * hull in one cell: exact below 2^15 entries per tile (an entry moves either half by one at most). Lists in
+    // place grow to their place's capacity at most between two verified passes — c + c / 2 + 64 <= 24 638 for c < 16 384 (launch_tile_bases) —, so a
+    // frame that has ever shown a list of 16 384 entries keeps the per-sample kernel (tests/test_gpu_packed_cells.py).
     p.rows = (pass == 3 && f->longest_list < 16384u) ? 1u : 0u;
     p.fill_cells = f->longest_list < 16384u ? 1u : 0u; // (k_raster_fill keeps the same cell)
     if (edges != f->last_edges) f->pairs_known = false;

@@ -683,7 +683,9 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
 //     instructions per walked entry, half of the kernel's scalar work). A group's backdrop units are summed on the scalar unit (population
 //     counts of their masks) and applied with one add per sample row.
 //   * PACKED COUNTERS: a sample keeps  fill + 65536 * hull  in ONE register (k_raster_rows' cell; exact while a tile's list has fewer than
-//     16 384 entries — every entry moves a counter by two at most —, the host keeps frames with longer lists on k_raster_edges). A fill
+//     32 768 entries — every entry moves either counter by ONE at most: an edge's Y g(p) + A is -1, 0 or 1, a backdrop unit, a curve triangle's
+//     accept bit and each of a COVER's two folded units are one —; the host keeps frames that have shown a list of 16 384 entries on k_raster_edges,
+//     since a list in place may grow to c + c / 2 + 64 <= 24 638 entries unmeasured, tests/test_gpu_packed_cells.py). A fill
 //     edge or a curve triangle adds its accept bit with ONE add-with-carry (the compare's lane mask is the carry), four registers less per lane.
 //   * The sample rows an edge's y range or a triangle's box leaves out are folded into the compare as a sign bit (two cheap vector
 //     instructions per row) instead of lane masks built on the scalar unit (fifteen scalar instructions per entry: by the measured issue
@@ -1299,7 +1301,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
         if (r.direct && threadIdx.x == 0u) atomicMax(&r.overflow[3], n);
         n = 0;
     } else if (n > kLdsSortMax && r.direct && threadIdx.x == 0u) {
-        atomicMax(&r.overflow[3], n); // (the host takes frames with lists of 16 384 entries and more away from this kernel: its cells hold two 16-bit fields)
+        atomicMax(&r.overflow[3], n); // (the host takes frames that have shown a list of 16 384 entries away from this kernel: its cells hold two 16-bit fields, exact below 32 768 entries)
     }
     uint32_t my_key = 0xFFFFFFFFu;
     const bool sorted_in_place = n > kLdsSortMax;

@@ -168,7 +168,7 @@ struct RasterParams {
     uint32_t state_load;              // the planes hold what earlier passes left (0: first pass with state — the planes were initialised, nothing to read but the colours of a frame that was not cleared)
     uint32_t state_layers;            // alpha layers in state_alpha (Configuration::alpha_layer_count, <= 4)
     uint32_t winding_bits;            // Configuration::winding_counter_bits (the shift of the clip nesting counter inside the stencil byte)
-    uint32_t fill_cells;              // no tile list of this frame has shown 16 384 entries: k_raster_fill's packed counters (fill + 65536 * hull per sample) are exact; 0: k_raster_edges
+    uint32_t fill_cells;              // no tile list of this frame has shown 16 384 entries: k_raster_fill's packed counters (fill + 65536 * hull per sample) are exact (they are below 32 768 entries, and a list in place grows to 24 638 at most); 0: k_raster_edges
 };
 
 } // namespace crh
