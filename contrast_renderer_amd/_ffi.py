@@ -221,6 +221,10 @@ class PaintC(C.Structure):  # crh_paint
                 ("stops", GradientStopC * MAX_GRADIENT_STOPS)]
 
 
+class ImagePaintC(C.Structure):  # crh_image_paint
+    _fields_ = [("image", C.c_void_p), ("filter", C.c_uint32), ("spread_x", C.c_uint32), ("spread_y", C.c_uint32), ("m", C.c_float * 6)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -290,6 +294,12 @@ def load_library():
         "crh_scene_render_draws": (C.c_int, [V, V, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(DrawC), C.c_uint32]),
         "crh_paint_validate": (C.c_int, [C.POINTER(PaintC)]),
         "crh_scene_set_paints": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
+        "crh_image_create": (C.c_int, [V, C.c_uint32, C.c_uint32, V, C.POINTER(V)]),
+        "crh_image_create_from_frame": (C.c_int, [V, C.POINTER(V)]),
+        "crh_image_size": (C.c_int, [V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "crh_image_destroy": (None, [V]),
+        "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
+        "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),
         "crh_frame_download": (C.c_int, [V, V]),
         "crh_frame_download_f16": (C.c_int, [V, V]),

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -374,6 +375,20 @@ struct crh_frame {
 };
 
 constexpr int kTessBufs = 33; // buffers a tessellation run writes (crh_scene::tess_bufs)
+// The texels of a crh_image on the device, shared by the image and by every paint table that names it (crh_scene_set_paints_with_images):
+// freed with the last of them, so that no kernel of a pass reads an image its caller has destroyed.
+struct ImagePixels {
+    void* p = nullptr;
+    ~ImagePixels() {
+        if (p) (void)hipFree(p);
+    }
+};
+struct crh_image {
+    crh_renderer* renderer = nullptr;
+    uint32_t width = 0, height = 0;
+    std::shared_ptr<ImagePixels> pixels;
+};
+
 struct crh_scene {
     crh_renderer* renderer; // nullptr once the renderer has been destroyed (only crh_scene_destroy is valid then)
     int device = 0;
@@ -443,6 +458,11 @@ struct crh_scene {
     uint32_t first_painted = 0xFFFFFFFFu; // the lowest instance with a paint: the plain pass (instance i = Shape i) is a painted one when it is below n_shapes
     DevBuf paint_heads, paint_stops, paint_instance;
     DevBuf paint_items[kPipelineDepth];  // [n_items] PaintItem, written per pass (k_paint_items) beside the set-up triangles of prim_rec
+    // image paints (crh_scene_set_paints_with_images): association indices at n_paints and beyond name them; the table shares the pixels of its images
+    uint32_t n_image_paints = 0;
+    uint32_t first_image_painted = 0xFFFFFFFFu; // the lowest instance with an image paint
+    DevBuf image_paints;                        // [n_image_paints] ImagePaintRec
+    std::vector<std::shared_ptr<ImagePixels>> image_pixels;
     // frame pipelining: tessellation runs on its own stream; these events order it against the raster stream
     hipEvent_t tess_done = nullptr;     // recorded on the tessellation stream after the last tessellation kernel
     hipEvent_t vertices_free = nullptr; // recorded on the raster stream after k_prim_setup (last reader of the vertex streams and hulls)
@@ -503,6 +523,8 @@ struct crh_scene {
         for (DevBuf& b : prim_proj) b.release();
         for (DevBuf& b : paint_items) b.release();
         paint_heads.release(), paint_stops.release(), paint_instance.release();
+        image_paints.release();
+        image_pixels.clear();
         upload_t.release();
         upload_c.release();
         geometry_stage.release();
@@ -1208,14 +1230,18 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     // The general pass keeps the reference's triangle strips (raster.hip): clip nesting / alpha contexts, perspective, depth, and face
     // culling (a cull decision is per strip triangle). Everything else is the edge pass (bin_edges.hip, raster_edges.hip).
     // a pass that draws a painted instance with a Color cover (crh_scene_set_paints); a Scene without paints asks nothing
-    bool painted = false;
-    if (sc->n_paints != 0u) {
-        if (!recorded) painted = sc->first_painted < sc->d.n_shapes;
+    bool painted = false, imaged = false; // imaged: one of them is an image paint (k_raster_image)
+    if (sc->n_paints + sc->n_image_paints != 0u) {
+        if (!recorded) painted = sc->first_painted < sc->d.n_shapes, imaged = sc->first_image_painted < sc->d.n_shapes;
         else
             for (const DrawItem& it : f->items_host)
                 if ((it.ops >> 4) == (uint32_t)CRH_OP_COLOR + 1u && it.instance < sc->instance_paint.size() && sc->instance_paint[it.instance] >= 0) {
                     painted = true;
-                    break;
+                    if (sc->n_image_paints == 0u) break;
+                    if (sc->instance_paint[it.instance] >= (int32_t)sc->n_paints) {
+                        imaged = true;
+                        break;
+                    }
                 }
     }
     p.general = (projective || p.depth || r->config.cull_mode != CRH_CULL_NONE || (recorded && f->items_need_ops) || f->carry || !r->blend_over || painted) ? 1u : 0u;
@@ -1324,7 +1350,9 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
             launch_bin(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
             if (painted) { // behind k_prim_setup, in front of the event that says the instance data has been read
                 HIP_TRY(sc->paint_items[rec].ensure((size_t)p.n_items * sizeof(PaintItem) + 64));
-                launch_paint_items(p, PaintTable{sc->paint_items[rec].as<PaintItem>(), sc->paint_instance.as<int32_t>(), (uint32_t)sc->instance_paint.size()}, bin);
+                const PaintTable table = {sc->paint_items[rec].as<PaintItem>(), sc->paint_instance.as<int32_t>(), (uint32_t)sc->instance_paint.size()};
+                launch_paint_items(p, table, bin);
+                if (imaged) launch_paint_items_images(p, table, sc->n_paints, bin);
             }
             f->last_bin = kBinTriangles;
         }
@@ -1441,8 +1469,9 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     else
     {
         const PaintArgs paint_args = {sc->paint_items[rec].as<PaintItem>(), sc->paint_heads.as<PaintHead>(), sc->paint_stops.as<PaintStop>()};
+        const ImageArgs image_args = {sc->image_paints.as<ImagePaintRec>()};
         f->last_raster = launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke, (r->blend_over && !painted) ? nullptr : &r->blend_form,
-                                       painted ? &paint_args : nullptr);
+                                       painted ? &paint_args : nullptr, imaged ? &image_args : nullptr);
     }
     f->last_formulation = (uint32_t)pass | (measured ? 256u : 0u), f->last_general = p.general | (r->pipeline ? 0u : 256u);
     if (direct) f->last_bin |= 256u;
@@ -2463,15 +2492,51 @@ crh_status crh_paint_validate(const crh_paint* paint) {
     }
     return CRH_OK;
 }
+namespace {
+crh_status image_paint_error(const char* what) {
+    g_error = std::string("crh_image_paint: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+} // namespace
+crh_status crh_image_paint_validate(const crh_image_paint* paint) {
+    if (!paint) return image_paint_error("null paint");
+    for (float v : paint->m)
+        if (!std::isfinite(v)) return CRH_ERR_NON_FINITE;
+    if (!paint->image) return image_paint_error("null image");
+    if (paint->filter != CRH_FILTER_NEAREST && paint->filter != CRH_FILTER_LINEAR) return image_paint_error("unknown filter");
+    if (paint->spread_x > CRH_SPREAD_REFLECT || paint->spread_y > CRH_SPREAD_REFLECT) return image_paint_error("unknown spread");
+    return CRH_OK;
+}
 crh_status crh_scene_set_paints(crh_scene* sc, const crh_paint* paints, uint32_t n_paints, const int32_t* instance_paint, uint32_t n_instances) {
-    if (!sc || !sc->renderer || (n_paints && !paints) || (n_paints && n_instances && !instance_paint)) return paint_error("null argument");
+    return crh_scene_set_paints_with_images(sc, paints, n_paints, nullptr, 0u, instance_paint, n_instances);
+}
+crh_status crh_scene_set_paints_with_images(crh_scene* sc, const crh_paint* paints, uint32_t n_paints, const crh_image_paint* image_paints, uint32_t n_image_paints,
+                                            const int32_t* instance_paint, uint32_t n_instances) {
+    const uint32_t n_all = n_paints + n_image_paints;
+    if (!sc || !sc->renderer || (n_paints && !paints) || (n_image_paints && !image_paints) || (n_all && n_instances && !instance_paint) || n_all < n_paints) return paint_error("null argument");
     crh_renderer* r = sc->renderer;
+    std::vector<ImagePaintRec> image_recs;
+    std::vector<std::shared_ptr<ImagePixels>> image_pixels;
+    uint32_t first_image_painted = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < n_image_paints; ++k) {
+        const crh_status st = crh_image_paint_validate(&image_paints[k]);
+        if (st != CRH_OK) return st;
+        const crh_image_paint& q = image_paints[k];
+        if (q.image->renderer != r) return image_paint_error("an image of another renderer");
+        ImagePaintRec rec = {};
+        rec.texels = static_cast<const uint32_t*>(q.image->pixels->p);
+        rec.width = q.image->width, rec.height = q.image->height;
+        rec.filter = q.filter, rec.spread_x = q.spread_x, rec.spread_y = q.spread_y;
+        for (int i = 0; i < 6; ++i) rec.m[i] = q.m[i];
+        image_recs.push_back(rec);
+        image_pixels.push_back(q.image->pixels);
+    }
     // everything is checked and built on the host first: a failed call leaves the previous table in force
     std::vector<PaintHead> heads;
     std::vector<PaintStop> stops;
     std::vector<int32_t> assoc;
     uint32_t first_painted = 0xFFFFFFFFu;
-    if (n_paints) {
+    if (n_all) {
         for (uint32_t k = 0; k < n_paints; ++k) {
             const crh_status st = crh_paint_validate(&paints[k]);
             if (st != CRH_OK) return st;
@@ -2500,8 +2565,9 @@ crh_status crh_scene_set_paints(crh_scene* sc, const crh_paint* paints, uint32_t
         }
         assoc.assign(instance_paint, instance_paint + n_instances);
         for (uint32_t i = 0; i < n_instances; ++i) {
-            if (assoc[i] < -1 || assoc[i] >= (int32_t)n_paints) return paint_error("an instance_paint entry is neither -1 nor an index into paints");
+            if (assoc[i] < -1 || assoc[i] >= (int32_t)n_all) return paint_error("an instance_paint entry is neither -1 nor an index into paints");
             if (assoc[i] >= 0 && first_painted == 0xFFFFFFFFu) first_painted = i;
+            if (assoc[i] >= (int32_t)n_paints && first_image_painted == 0xFFFFFFFFu) first_image_painted = i;
         }
     }
     HIP_TRY(hipSetDevice(r->device));
@@ -2509,7 +2575,13 @@ crh_status crh_scene_set_paints(crh_scene* sc, const crh_paint* paints, uint32_t
     const crh_status settled = settle_frames_of(sc, false);
     if (settled != CRH_OK) return settled;
     HIP_TRY(r->sync());
-    if (n_paints) {
+    if (n_all) {
+        if (n_image_paints) { // (the kernel loads heads[0] at an image-painted cover too: a table of image paints alone still has one zeroed head)
+            heads.resize(std::max<size_t>(heads.size(), 1));
+            stops.resize(std::max<size_t>(stops.size(), 1));
+            HIP_TRY(sc->image_paints.ensure(image_recs.size() * sizeof(ImagePaintRec)));
+            HIP_TRY(hipMemcpy(sc->image_paints.p, image_recs.data(), image_recs.size() * sizeof(ImagePaintRec), hipMemcpyHostToDevice));
+        }
         HIP_TRY(sc->paint_heads.ensure(heads.size() * sizeof(PaintHead)));
         HIP_TRY(sc->paint_stops.ensure(stops.size() * sizeof(PaintStop)));
         HIP_TRY(sc->paint_instance.ensure(assoc.size() * 4 + 4));
@@ -2517,6 +2589,9 @@ crh_status crh_scene_set_paints(crh_scene* sc, const crh_paint* paints, uint32_t
         HIP_TRY(hipMemcpy(sc->paint_stops.p, stops.data(), stops.size() * sizeof(PaintStop), hipMemcpyHostToDevice));
         if (!assoc.empty()) HIP_TRY(hipMemcpy(sc->paint_instance.p, assoc.data(), assoc.size() * 4, hipMemcpyHostToDevice));
     }
+    sc->n_image_paints = n_image_paints;
+    sc->first_image_painted = first_image_painted;
+    sc->image_pixels = std::move(image_pixels); // the earlier table's images go with it (nothing in flight reads them: the renderer was waited for above)
     sc->n_paints = n_paints;
     sc->instance_paint = std::move(assoc);
     sc->first_painted = first_painted;
@@ -2689,6 +2764,62 @@ crh_status download_pixels(crh_frame* f, void* out, uint32_t format) {
 }
 } // namespace
 crh_status crh_frame_download(crh_frame* f, void* rgba8) { return download_pixels(f, rgba8, CRH_FORMAT_RGBA8); }
+namespace {
+constexpr uint32_t kMaxImageSize = 16384;
+crh_status new_image(crh_renderer* r, uint32_t width, uint32_t height, crh_image** out) {
+    auto pixels = std::make_shared<ImagePixels>();
+    HIP_TRY(hipMalloc(&pixels->p, (size_t)width * height * 4));
+    crh_image* image = new crh_image;
+    image->renderer = r, image->width = width, image->height = height, image->pixels = std::move(pixels);
+    *out = image;
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_image_create(crh_renderer* r, uint32_t width, uint32_t height, const void* rgba8, crh_image** out) {
+    if (!r || !rgba8 || !out || width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return CRH_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    const crh_status st = new_image(r, width, height, &image);
+    if (st != CRH_OK) return st;
+    if (!hip_ok(hipMemcpy(image->pixels->p, rgba8, (size_t)width * height * 4, hipMemcpyHostToDevice), "hipMemcpy(image)")) { // (returns with the bytes copied)
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+crh_status crh_image_create_from_frame(crh_frame* f, crh_image** out) {
+    if (!f || !f->renderer || !out) return CRH_ERR_INVALID_ARGUMENT;
+    if ((f->format != CRH_FORMAT_RGBA8 && f->format != CRH_FORMAT_RGBA8_ATTACHMENT) || f->slab_ty0 != 0u || f->slab_ty1 != 0xFFFFFFFFu) return CRH_ERR_UNSUPPORTED;
+    if (f->width > kMaxImageSize || f->height > kMaxImageSize) return CRH_ERR_UNSUPPORTED;
+    crh_renderer* r = f->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    const crh_status settled = settle_frame(f);
+    if (settled != CRH_OK) return settled;
+    crh_image* image = nullptr;
+    const crh_status st = new_image(r, f->width, f->height, &image);
+    if (st != CRH_OK) return st;
+    bool ok;
+    if (f->cleared) { // LoadOp::Clear without a pass since: transparent
+        ok = hip_ok(hipMemsetAsync(image->pixels->p, 0, f->image_bytes(), r->stream), "hipMemsetAsync(image)");
+    } else {
+        ok = hip_ok(order_after_external(f, r->stream), "order_after_external(image)") &&
+             hip_ok(hipMemcpyAsync(image->pixels->p, f->rgba8.p, f->image_bytes(), hipMemcpyDeviceToDevice, r->stream), "hipMemcpyAsync(image)");
+    }
+    ok = ok && hip_ok(r->sync(), "sync(image)"); // a snapshot: the next pass into the frame may start as soon as this returns
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+crh_status crh_image_size(const crh_image* image, uint32_t* width, uint32_t* height) {
+    if (!image || !width || !height) return CRH_ERR_INVALID_ARGUMENT;
+    *width = image->width, *height = image->height;
+    return CRH_OK;
+}
+void crh_image_destroy(crh_image* image) { delete image; } // (the pixels stay while a Scene's paint table names them)
 crh_status crh_frame_download_f16(crh_frame* f, void* rgba16f) { return download_pixels(f, rgba16f, CRH_FORMAT_RGBA16F); }
 extern "C" crh_status crh_debug_frame_counters(crh_frame* f, uint32_t out[8]) { // tools only (not in the public header)
     HIP_TRY(hipSetDevice(f->renderer->device));

@@ -559,19 +559,42 @@ constexpr int kMaxAlphaLayers = 4;
 //                walk reserves) are compiled out: fewer VGPRs, more waves per SIMD.
 //   BLEND == true (with OPS only): the colour cover blends with the renderer's Configuration::blending (`bf`) instead of premultiplied
 //                "over": the kernel k_raster_blend. Both kernels include the one body, csrc/raster_tile_body.inc.
+// the image block of the body (IMAGES: k_raster_image below, compiled out of the other kernels)
+CRH_D float image_coord(float u) { // NaN -> 0, then clamped to +-2^24: the floor that follows is an exact int
+    const float x = u == u ? u : 0.0f;
+    return fminf(fmaxf(x, -16777216.0f), 16777216.0f);
+}
+CRH_D int image_wrap(int i, int n, uint32_t spread) { // -> [0, n): n >= 1 (crh_image_create), |i| <= 2^24 + 1; spread is wave uniform
+    if (spread == CRH_SPREAD_REPEAT) {
+        const int k = i % n;
+        return k < 0 ? k + n : k;
+    }
+    if (spread == CRH_SPREAD_REFLECT) {
+        const int n2 = 2 * n;
+        int k = i % n2;
+        k = k < 0 ? k + n2 : k;
+        return k < n ? k : n2 - 1 - k;
+    }
+    return min(max(i, 0), n - 1);
+}
+CRH_D float texel_channel(uint32_t texel, int ch) { return (float)((texel >> (8 * ch)) & 255u) / 255.0f; }
+// how many of a turn's four samples fetch their texels together (msaa 8 holds eight samples' state per lane: DESIGN.md §7 "Image paints")
+#define CRH_IMAGE_FETCH_TOGETHER(S_) ((S_) == 8 ? 1 : 4)
 template <int S, int ROWS, bool OPS, bool STROKES, bool XFMT = false> // XFMT: the frame formats 3-8 (raster_common.hpp store_px)
 __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu((OPS || STROKES || S >= 4) ? 1 : CRH_TILE_WAVES))) void k_raster_tile(SceneDev s, RasterParams r) {
-    constexpr bool BLEND = false, PAINT = false;
+    constexpr bool BLEND = false, PAINT = false, IMAGES = false;
     const BlendForm bf = {}; // (not read: the blend block is compiled out)
     const PaintArgs pa = {}; // (nor this: the paint block is)
+    const ImageArgs ia = {};
 #include "raster_tile_body.inc"
 }
 // The general variant with the renderer's blend state in place of "over" (Configuration::blending; ROWS = tile_rows(S) as above)
 template <int S, bool STROKES, bool XFMT = false>
 __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_blend(SceneDev s, RasterParams r, BlendForm bf) {
     constexpr int ROWS = tile_rows(S);
-    constexpr bool OPS = true, BLEND = true, PAINT = false;
+    constexpr bool OPS = true, BLEND = true, PAINT = false, IMAGES = false;
     const PaintArgs pa = {};
+    const ImageArgs ia = {};
 #include "raster_tile_body.inc"
 }
 // k_raster_blend with gradient paints (crh_scene_set_paints): the colour cover of a painted item takes its source per sample from the paint
@@ -580,8 +603,32 @@ __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per
 template <int S, bool STROKES, bool XFMT = false>
 __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_paint(SceneDev s, RasterParams r, BlendForm bf, PaintArgs pa) {
     constexpr int ROWS = tile_rows(S);
-    constexpr bool OPS = true, BLEND = true, PAINT = true;
+    constexpr bool OPS = true, BLEND = true, PAINT = true, IMAGES = false;
+    const ImageArgs ia = {}; // (not read: the image block is compiled out)
 #include "raster_tile_body.inc"
+}
+// k_raster_paint with image paints (crh_scene_set_paints_with_images): the colour cover of an image-painted item takes its source per sample from
+// the texels of an RGBA8 image in HBM — CDNA has no sampler, so the wrap, the fetch (one texel for NEAREST, four for LINEAR) and the filter are
+// plain code in the body's image block (IMAGES, compiled out of the three kernels above). Gradient-painted and unpainted items are drawn as
+// k_raster_paint draws them. Only the pass that draws an image-painted instance through a Color cover runs this kernel.
+template <int S, bool STROKES, bool XFMT = false>
+__global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_image(SceneDev s, RasterParams r, BlendForm bf, PaintArgs pa, ImageArgs ia) {
+    constexpr int ROWS = tile_rows(S);
+    constexpr bool OPS = true, BLEND = true, PAINT = true, IMAGES = true;
+#include "raster_tile_body.inc"
+}
+// Behind k_paint_items in an image-painted pass, one thread per draw item: the record of an item whose instance names an image paint (an
+// association index at or beyond the gradients') gets paint = 0, pad = image paint + 1. The condition is k_paint_items' own, so only records
+// it wrote are touched.
+__global__ __launch_bounds__(64) void k_paint_items_images(RasterParams r, PaintTable t, uint32_t n_gradients) {
+    const uint32_t item = blockIdx.x * 64u + threadIdx.x;
+    if (item >= r.n_items) return;
+    const DrawItem it = item_of(r, item);
+    const int32_t paint = it.instance < t.n_instances ? t.instance_paint[it.instance] : -1;
+    if (paint < (int32_t)n_gradients || (it.ops >> 4) != (uint32_t)CRH_OP_COLOR + 1u) return;
+    if (r.shape_prim_begin[item + 1] > r.prim_capacity) return;
+    t.items[item].paint = 0u;
+    t.items[item].pad = (uint32_t)paint - n_gradients + 1u;
 }
 
 // One wavefront per draw item of a painted pass, behind k_prim_setup: an item whose instance has a paint and whose cover is Color gets its
@@ -737,11 +784,11 @@ void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hip
     if (after_fill) (void)hipEventRecord(after_fill, stream);
     if (mark) mark(ctx, "raster_tile_fill", 0);
 }
-// The raster kernel of msaa S: k_raster_paint for a pass that draws a painted instance, k_raster_blend for a blend state other than "over"
+// The raster kernel of msaa S: k_raster_image for a pass that draws an image-painted instance, k_raster_paint for a pass that draws a (gradient-)painted one, k_raster_blend for a blend state other than "over"
 // (r.general is set with both), else k_raster_tile, OPS for
 // clip nesting / alpha contexts / depth / projective instances
 template <int S>
-static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_t stream, dim3 grid, bool has_stroke, const BlendForm* blend, const PaintArgs* paint) {
+static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_t stream, dim3 grid, bool has_stroke, const BlendForm* blend, const PaintArgs* paint, const ImageArgs* images) {
     constexpr int ROWS = tile_rows(S);
     const dim3 block(64u * tile_waves(S));
     const uint32_t lds = tile_waves(S) * r.sort_capacity * 4u;
@@ -767,7 +814,16 @@ static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_
         else                                                                                                            \
             hipLaunchKernelGGL((k_raster_paint<S, STROKES_>), grid, block, lds, stream, s, r, *blend, *paint);         \
     } while (0)
-    if (blend && paint) {
+#define CRH_LAUNCH_IMAGE(STROKES_)                                                                                                 \
+    do {                                                                                                                         \
+        if (xfmt)                                                                                                                \
+            hipLaunchKernelGGL((k_raster_image<S, STROKES_, true>), grid, block, lds, stream, s, r, *blend, *paint, *images);   \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_raster_image<S, STROKES_>), grid, block, lds, stream, s, r, *blend, *paint, *images);         \
+    } while (0)
+    if (blend && paint && images) {
+        if (has_stroke) CRH_LAUNCH_IMAGE(true); else CRH_LAUNCH_IMAGE(false);
+    } else if (blend && paint) {
         if (has_stroke) CRH_LAUNCH_PAINT(true); else CRH_LAUNCH_PAINT(false);
     } else if (blend) {
         if (has_stroke) CRH_LAUNCH_BLEND(true); else CRH_LAUNCH_BLEND(false);
@@ -779,22 +835,26 @@ static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_
 #undef CRH_LAUNCH_TILE
 #undef CRH_LAUNCH_BLEND
 #undef CRH_LAUNCH_PAINT
+#undef CRH_LAUNCH_IMAGE
 }
 void launch_paint_items(const RasterParams& r, const PaintTable& t, hipStream_t stream) {
     if (r.n_items) hipLaunchKernelGGL(k_paint_items, dim3(r.n_items), dim3(64), 0, stream, r, t);
 }
+void launch_paint_items_images(const RasterParams& r, const PaintTable& t, uint32_t n_gradients, hipStream_t stream) {
+    if (r.n_items) hipLaunchKernelGGL(k_paint_items_images, dim3((r.n_items + 63u) / 64u), dim3(64), 0, stream, r, t, n_gradients);
+}
 // -> RasterVariant (0: nothing launched)
 uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx,
-                   uint64_t raster_bytes, bool has_stroke, const BlendForm* blend, const PaintArgs* paint) {
+                   uint64_t raster_bytes, bool has_stroke, const BlendForm* blend, const PaintArgs* paint, const ImageArgs* images) {
     // 8x8-tile blocks, an equal number per XCD (k_raster_tile's tile order)
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;
     const uint32_t blocks = ((r.tiles_x + kBlock - 1u) / kBlock) * ((r.tiles_y + kBlock - 1u) / kBlock);
     const dim3 grid((r.tile_order && r.order_places) ? r.order_places : ((blocks + 7u) / 8u) * kBlock * kBlock * 8u);
     switch (samples) {
-        case 1: launch_raster_s<1>(s, r, stream, grid, has_stroke, blend, paint); break;
-        case 2: launch_raster_s<2>(s, r, stream, grid, has_stroke, blend, paint); break;
-        case 4: launch_raster_s<4>(s, r, stream, grid, has_stroke, blend, paint); break;
-        case 8: launch_raster_s<8>(s, r, stream, grid, has_stroke, blend, paint); break;
+        case 1: launch_raster_s<1>(s, r, stream, grid, has_stroke, blend, paint, images); break;
+        case 2: launch_raster_s<2>(s, r, stream, grid, has_stroke, blend, paint, images); break;
+        case 4: launch_raster_s<4>(s, r, stream, grid, has_stroke, blend, paint, images); break;
+        case 8: launch_raster_s<8>(s, r, stream, grid, has_stroke, blend, paint, images); break;
         default: return 0u;
     }
     if (mark) mark(ctx, "raster_tiles", raster_bytes);

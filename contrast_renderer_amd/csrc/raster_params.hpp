@@ -91,6 +91,23 @@ struct PaintTable {
     const int32_t* instance_paint; // [n_instances] index into the paints, or -1: the solid colour
     uint32_t n_instances;
 };
+// Image paints of the colour cover (crh_scene_set_paints_with_images): a kernel argument of its own behind PaintArgs, read by k_raster_image only.
+//   ImagePaintRec  per image paint: the image's texels (premultiplied RGBA8, row-major, row 0 = top, one 32-bit word per texel), its size, the
+//                  filter, the spread of each axis and the path -> texel map m (u = m0 x + m1 y + m2, v = m3 x + m4 y + m5).
+// In the Scene's association an index below the number of gradients names a gradient, the others image paint (index - n_gradients).
+// k_paint_items writes that index to PaintItem::paint as it is and leaves PaintItem::pad 0; k_paint_items_images, behind it in an image-painted
+// pass, turns the record of an image-painted item into paint = 0, pad = image paint + 1 (pad == 0: the item's paint is a gradient).
+struct ImagePaintRec {
+    const uint32_t* texels;
+    uint32_t width, height;
+    uint32_t filter, spread_x, spread_y, pad0;
+    float m[6];
+    uint32_t pad1[2];
+};
+static_assert(sizeof(ImagePaintRec) == 64, "load_uniform takes 16-byte multiples");
+struct ImageArgs {
+    const ImagePaintRec* paints;
+};
 
 constexpr uint32_t kTessStatusWord = 126; // ... the status word of the optimistic tessellation a pass drew (api.hip: crh_scene::optimistic), copied in by the host side
 constexpr uint32_t kExtraTurnsWord = 76; // of RasterParams::overflow: behind the 8 flag words and the 64 cursors of the pair sub-streams

@@ -1,5 +1,6 @@
-// csrc/raster_tile_body.inc — the body of k_raster_tile<S, ROWS, OPS, STROKES>, k_raster_blend<S, STROKES> and k_raster_paint<S, STROKES>
-// (raster.hip), included into the three kernels with S, ROWS, OPS, STROKES, BLEND, the blend form `bf`, PAINT and the paint tables `pa` in scope. Included rather than shared as a __device__ function:
+// csrc/raster_tile_body.inc — the body of k_raster_tile<S, ROWS, OPS, STROKES>, k_raster_blend<S, STROKES>, k_raster_paint<S, STROKES> and
+// k_raster_image<S, STROKES> (raster.hip), included into the four kernels with S, ROWS, OPS, STROKES, BLEND, the blend form `bf`, PAINT, the paint
+// tables `pa`, IMAGES and the image paints `ia` in scope. Included rather than shared as a __device__ function:
 // the instruction stream of k_raster_tile stays what it was (an inlined body changed its register allocation and scheduling). The steps in
 // front of the walk that every tile kernel takes — the tile of the workgroup's place, the sort of a list in place — are the helpers of
 // raster_tile_list.hpp: tools/resource_usage.py shows the same registers, scratch, occupancy and LDS for every instantiation with them.
@@ -431,6 +432,60 @@
                     for (int c = 0; c < 4; ++c) any_blend |= (int)blend[(g + c) / S][(g + c) % S];
                     if (!__any(any_blend)) continue;
                     float t[4], pc[4][4] = {};
+                    if (IMAGES && pi.pad != 0u) { // wave uniform: an image paint (k_paint_items_images left image paint + 1 in pad)
+                        // (include/contrast_hip.h crh_scene_set_paints_with_images states the model.) The texels of a turn's samples — one each, or four for
+                        // LINEAR — are fetched together, every address from wrapped indices, and unpacked behind the last load: the loads of divergent
+                        // addresses are in flight at once instead of one round trip per sample.
+                        const ImagePaintRec im = load_uniform(&ia.paints[pi.pad - 1u]);
+                        const int iw = (int)im.width, ih = (int)im.height;
+                        const bool linear = im.filter == CRH_FILTER_LINEAR;
+                        constexpr int kTogether = CRH_IMAGE_FETCH_TOGETHER(S);
+#pragma unroll
+                        for (int c0 = 0; c0 < 4; c0 += kTogether) {
+                            uint32_t tex[kTogether][4];
+                            float frac[kTogether][2];
+#pragma unroll
+                            for (int c = c0; c < c0 + kTogether; ++c) {
+                                const int b = (g + c) / S, k = (g + c) % S;
+                                const float fx = tx0 + sx[k], fy = ty0 + (sy0[k] + (float)(4 * b)); // the sample's place on the frame (exact)
+                                float X = fmaf(fy, pi.h[1], fmaf(fx, pi.h[0], pi.h[2])), Y = fmaf(fy, pi.h[4], fmaf(fx, pi.h[3], pi.h[5]));
+                                if (!pi.affine) { // wave uniform
+                                    const float W = fmaf(fy, pi.h[7], fmaf(fx, pi.h[6], pi.h[8]));
+                                    X = X / W;
+                                    Y = Y / W;
+                                }
+                                const float u = image_coord(fmaf(Y, im.m[1], fmaf(X, im.m[0], im.m[2]))), v = image_coord(fmaf(Y, im.m[4], fmaf(X, im.m[3], im.m[5])));
+                                if (linear) {
+                                    const float au = u - 0.5f, av = v - 0.5f;
+                                    const float fu = floorf(au), fv = floorf(av);
+                                    frac[c - c0][0] = au - fu, frac[c - c0][1] = av - fv;
+                                    const int i0 = image_wrap((int)fu, iw, im.spread_x), i1 = image_wrap((int)fu + 1, iw, im.spread_x);
+                                    const int j0 = image_wrap((int)fv, ih, im.spread_y), j1 = image_wrap((int)fv + 1, ih, im.spread_y);
+                                    tex[c - c0][0] = im.texels[(uint32_t)j0 * im.width + (uint32_t)i0];
+                                    tex[c - c0][1] = im.texels[(uint32_t)j0 * im.width + (uint32_t)i1];
+                                    tex[c - c0][2] = im.texels[(uint32_t)j1 * im.width + (uint32_t)i0];
+                                    tex[c - c0][3] = im.texels[(uint32_t)j1 * im.width + (uint32_t)i1];
+                                } else {
+                                    const int i0 = image_wrap((int)floorf(u), iw, im.spread_x), j0 = image_wrap((int)floorf(v), ih, im.spread_y);
+                                    tex[c - c0][0] = im.texels[(uint32_t)j0 * im.width + (uint32_t)i0];
+                                }
+                            }
+#pragma unroll
+                            for (int c = c0; c < c0 + kTogether; ++c) {
+#pragma unroll
+                                for (int ch = 0; ch < 4; ++ch) {
+                                    const float t00 = texel_channel(tex[c - c0][0], ch);
+                                    if (linear) {
+                                        const float t01 = texel_channel(tex[c - c0][1], ch), t10 = texel_channel(tex[c - c0][2], ch), t11 = texel_channel(tex[c - c0][3], ch);
+                                        const float top = t00 + frac[c - c0][0] * (t01 - t00), bottom = t10 + frac[c - c0][0] * (t11 - t10);
+                                        pc[c][ch] = top + frac[c - c0][1] * (bottom - top);
+                                    } else {
+                                        pc[c][ch] = t00;
+                                    }
+                                }
+                            }
+                        }
+                    } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int b = (g + c) / S, k = (g + c) % S;
@@ -463,13 +518,19 @@
                             for (int ch = 0; ch < 4; ++ch) pc[c][ch] = here ? fmaf(f, st.dc[ch], st.c[ch]) : pc[c][ch];
                         }
                     }
+                    } // a gradient
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int b = (g + c) / S, k = (g + c) % S;
                         float src[4], us[4], ud[4];
                         const float sa = pc[c][3] * pi.tint[3];
+                        if (IMAGES && pi.pad != 0u) { // texels are premultiplied: the tint is premultiplied first, (rgb * a, a) as k_prim_setup does
+#pragma unroll
+                            for (int ch = 0; ch < 3; ++ch) src[ch] = clamp_unit(pc[c][ch] * (pi.tint[ch] * pi.tint[3]));
+                        } else {
 #pragma unroll
                         for (int ch = 0; ch < 3; ++ch) src[ch] = clamp_unit((pc[c][ch] * pi.tint[ch]) * sa); // (rgb * a, a) as k_prim_setup premultiplies the solid colour
+                        }
                         src[3] = clamp_unit(sa);
 #pragma unroll
                         for (int ch = 0; ch < 4; ++ch) {

@@ -365,6 +365,103 @@ class Frame:
             self.handle = None
 
 
+class Filter(IntEnum):  # CRH_FILTER_*
+    Nearest = 0
+    Linear = 1
+
+
+class Image:
+    """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
+    [height, width, 4] uint8 array, copied before the constructor returns. One level, no mipmaps: an image drawn much smaller than its texels aliases."""
+
+    def __init__(self, renderer: Renderer, pixels):
+        pixels = np.asarray(pixels)
+        if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"an image takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+        data = np.ascontiguousarray(pixels)
+        self.renderer, self.lib = renderer, renderer.lib
+        handle = C.c_void_p()
+        check(self.lib.crh_image_create(renderer.handle, data.shape[1], data.shape[0], data.ctypes.data, C.byref(handle)))
+        self.handle = handle
+        self.width, self.height = int(data.shape[1]), int(data.shape[0])
+
+    @staticmethod
+    def from_frame(frame: Frame):
+        """crh_image_create_from_frame: a snapshot of what the frame shows (an RGBA8 or RGBA8-attachment frame, not restricted by
+        set_tile_rows), copied on the device; later passes into the frame do not change it."""
+        image = Image.__new__(Image)
+        image.renderer, image.lib = frame.renderer, frame.lib
+        handle = C.c_void_p()
+        check(image.lib.crh_image_create_from_frame(frame.handle, C.byref(handle)))
+        image.handle = handle
+        w, h = C.c_uint32(), C.c_uint32()
+        check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
+        image.width, image.height = int(w.value), int(h.value)
+        return image
+
+    def destroy(self):
+        """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""
+        if getattr(self, "handle", None):
+            self.lib.crh_image_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.destroy()
+
+
+@dataclass(frozen=True)
+class ImagePaint:
+    """crh_image_paint: the texels of an Image as the source of a Color cover, times the instance colour (include/contrast_hip.h
+    crh_scene_set_paints_with_images states the model). `matrix` = (m0 .. m5) maps path coordinates to texels: u = m0 x + m1 y + m2,
+    v = m3 x + m4 y + m5; texel (i, j) covers [i, i + 1) x [j, j + 1), row 0 is the image's top."""
+    image: Image
+    matrix: Tuple[float, float, float, float, float, float]
+    filter: int = Filter.Linear
+    spread_x: int = Spread.Pad
+    spread_y: int = Spread.Pad
+
+    def __post_init__(self):
+        object.__setattr__(self, "matrix", tuple(float(v) for v in self.matrix))
+        if len(self.matrix) != 6:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, "an image paint's matrix has six entries")
+
+    @staticmethod
+    def fit(image, lower, upper, filter=Filter.Linear, spread_x=Spread.Pad, spread_y=Spread.Pad):
+        """The path rectangle [lower, upper] onto the whole image, upright under a transform that does not mirror: path y points up on the
+        frame, so y = upper[1] is the image's row 0."""
+        sx, sy = image.width / (float(upper[0]) - float(lower[0])), image.height / (float(upper[1]) - float(lower[1]))
+        return ImagePaint(image, (sx, 0.0, -sx * float(lower[0]), 0.0, -sy, sy * float(upper[1])), filter, spread_x, spread_y)
+
+    def to_c(self):
+        c = _ffi.ImagePaintC()
+        c.image = self.image.handle
+        c.filter, c.spread_x, c.spread_y = int(self.filter), int(self.spread_x), int(self.spread_y)
+        for i in range(6):
+            c.m[i] = self.matrix[i]
+        return c
+
+    def validate(self):
+        """crh_image_paint_validate (host only): raises ContrastError for what Scene.set_paints would refuse."""
+        check(_ffi.load_library().crh_image_paint_validate(C.byref(self.to_c())))
+
+
+def split_paints(paints, instance_paint):
+    """A list of Paint and ImagePaint mixed -> (gradients, image paints, association): the C ABI numbers the gradients first and the image
+    paints behind them, so the indices of the mixed list are remapped."""
+    gradients = [p for p in paints if not isinstance(p, ImagePaint)]
+    images = [p for p in paints if isinstance(p, ImagePaint)]
+    place, g, m = [], 0, 0
+    for p in paints:
+        if isinstance(p, ImagePaint):
+            place.append(len(gradients) + m)
+            m += 1
+        else:
+            place.append(g)
+            g += 1
+    which = [int(k) for k in np.asarray(instance_paint, dtype=np.int64).ravel()]
+    return gradients, images, [place[k] if 0 <= k < len(place) else k for k in which]
+
+
 COMM_ID_BYTES = 128
 
 
@@ -511,13 +608,22 @@ class Scene:
         check(self.lib.crh_scene_set_instances(self.handle, t.ctypes.data_as(fp), c.ctypes.data_as(fp)))
 
     def set_paints(self, paints, instance_paint):
-        """crh_scene_set_paints: `paints` = [Paint], `instance_paint[i]` = the index of instance i's paint or -1 for its solid colour (instances
+        """crh_scene_set_paints: `paints` = [Paint or ImagePaint, mixed], `instance_paint[i]` = the index of instance i's paint or -1 for its solid colour (instances
         beyond the list are solid). Stays with the Scene until the next call; an empty `paints` clears it. The call waits for the renderer's
-        work in flight (the kernels of a pass read the table): set it when it changes, not per frame."""
+        work in flight (the kernels of a pass read the table): set it when it changes, not per frame. A list with an ImagePaint goes through
+        crh_scene_set_paints_with_images (gradients first, the indices remapped); the table keeps the pixels of its images."""
         self._install_paints(paints, instance_paint)
         self._pass_paints = None  # the caller's own table: passes without paints leave it alone
 
     def _install_paints(self, paints, instance_paint):
+        if any(isinstance(p, ImagePaint) for p in paints):
+            gradients, images, remapped = split_paints(paints, instance_paint)
+            table = (_ffi.PaintC * max(1, len(gradients)))(*[p.to_c() for p in gradients])
+            image_table = (_ffi.ImagePaintC * len(images))(*[p.to_c() for p in images])
+            which = np.ascontiguousarray(remapped, dtype=np.int32).ravel()
+            check(self.lib.crh_scene_set_paints_with_images(self.handle, table if gradients else None, len(gradients), image_table, len(images),
+                                                            which.ctypes.data_as(C.POINTER(C.c_int32)) if len(which) else None, len(which)))
+            return
         table = (_ffi.PaintC * max(1, len(paints)))(*[p.to_c() for p in paints])
         which = np.ascontiguousarray(instance_paint, dtype=np.int32).ravel()
         check(self.lib.crh_scene_set_paints(self.handle, table if len(paints) else None, len(paints), which.ctypes.data_as(C.POINTER(C.c_int32)) if len(which) else None, len(which)))
@@ -613,7 +719,7 @@ class RenderPass:
 
     def push_instance(self, transform, color, paint=None):
         """Instance data of the pass (the instance buffers bound at slots 0 / 2, renderer.rs:462-466): returns the instance index.
-        `paint`: a Paint that takes the place of `color` as the source of the instance's Color covers (times `color`)."""
+        `paint`: a Paint or an ImagePaint that takes the place of `color` as the source of the instance's Color covers (times `color`)."""
         self.transforms.append(np.asarray(transform, dtype=np.float32).reshape(16))
         self.colors.append(np.asarray(color, dtype=np.float32).reshape(4))
         if paint is None:

@@ -407,6 +407,52 @@ typedef struct crh_paint {
 crh_status crh_paint_validate(const crh_paint* paint); /* host only: needs no renderer and no device */
 crh_status crh_scene_set_paints(crh_scene* scene, const crh_paint* paints, uint32_t n_paints, const int32_t* instance_paint, uint32_t n_instances);
 
+/* Image paints: the source of a Color cover, per sample, from the texels of an image — a bitmap inside a path, a pattern, a glyph atlas, an
+ * earlier frame drawn again as a layer (what a user of the reference does with a cover pipeline that samples a texture). An image paint is a
+ * type of its own beside crh_paint; one association names both. The model, which the tests check against float64:
+ *   image        width x height texels of premultiplied RGBA8 unorm, row 0 = top: the bytes crh_frame_download hands out. T[j][i] is texel
+ *                (column i, row j), its four codes / 255 — on the device the f32 value (float)k / 255.0f. Texel (i, j) covers [i, i+1) x [j, j+1).
+ *   coordinates  p is the sample's position in the Shape's path coordinates, exactly as for gradients (crh_scene_set_paints above);
+ *                u = m0 p.x + m1 p.y + m2, v = m3 p.x + m4 p.y + m5 (f32: fma(p.y, m1, fma(p.x, m0, m2))), then NaN -> 0 and clamped to +-2^24.
+ *   NEAREST      value = T[wrap(floor(v), height, spread_y)][wrap(floor(u), width, spread_x)]
+ *   LINEAR       a = u - 0.5, i = floor(a), fx = a - i; b = v - 0.5, j = floor(b), fy = b - j;
+ *                top = T[j'][i'] + fx (T[j'][i+1'] - T[j'][i']), bottom the same with (j+1)', value = top + fy (bottom - top) per premultiplied
+ *                channel, where ' wraps each of the four indices separately: equal texels give their value back exactly.
+ *   wrap(i, n)   PAD: clamp(i, 0, n - 1); REPEAT: i - n floor(i / n); REFLECT: k = i - 2n floor(i / 2n), k < n ? k : 2n - 1 - k.
+ *                spread_x is applied with the width, spread_y with the height.
+ *   source       (value.rgb * (tint.rgb * tint.a), value.a * tint.a) with tint = the instance colour, premultiplied first as the solid colour
+ *                is; then clamped and blended exactly as a gradient's source: the renderer's blend state, the frame format's rounding of
+ *                writes, the write mask, always the Rgba8Unorm-attachment model.
+ *   reads        every texel address is formed from wrapped indices only: no value of (u, v) reads outside the image.
+ *   no mipmaps   one level, two filters: an image drawn much smaller than its texels (minified) aliases. Scale the image first.
+ * crh_image_create copies width * height * 4 host bytes to the device before it returns; 1 <= width, height <= 16384, else
+ * CRH_ERR_INVALID_ARGUMENT. crh_image_create_from_frame settles the frame and copies its resolved bytes on the device: a snapshot — later
+ * passes into the frame do not change the image. It takes CRH_FORMAT_RGBA8 and CRH_FORMAT_RGBA8_ATTACHMENT frames that are not restricted by
+ * crh_frame_set_tile_rows, anything else is CRH_ERR_UNSUPPORTED. An image belongs to its renderer.
+ * crh_scene_set_paints_with_images is crh_scene_set_paints with image paints behind the gradients: instance_paint[i] in [0, n_paints) names
+ * gradient i, in [n_paints, n_paints + n_image_paints) image paint (i - n_paints), -1 the solid colour — one association, so no instance
+ * carries both. crh_scene_set_paints(s, p, n, a, m) is this call with no image paints; both tables empty clears. Errors as there, with a
+ * crh_last_error text, and a failed call leaves the previous table in force: a null image, an unknown filter or spread CRH_ERR_INVALID_ARGUMENT,
+ * a non-finite m CRH_ERR_NON_FINITE, an image of another renderer CRH_ERR_INVALID_ARGUMENT. The table keeps the pixels of its images alive (a
+ * shared reference) until it is replaced or the Scene is destroyed: crh_image_destroy while a table names the image is legal. The call settles
+ * and waits as crh_scene_set_paints does. A pass that draws an image-painted instance through a Color cover runs k_raster_image, the general
+ * triangle kernel with the image block; every other pass — a gradient-only table's included — launches what it launched before. */
+typedef struct crh_image crh_image;
+enum { CRH_FILTER_NEAREST = 0, CRH_FILTER_LINEAR = 1 };
+crh_status crh_image_create(crh_renderer* renderer, uint32_t width, uint32_t height, const void* rgba8, crh_image** out);
+crh_status crh_image_create_from_frame(crh_frame* frame, crh_image** out);
+crh_status crh_image_size(const crh_image* image, uint32_t* width, uint32_t* height);
+void crh_image_destroy(crh_image* image);
+typedef struct crh_image_paint {
+    const crh_image* image;
+    uint32_t filter;             /* CRH_FILTER_* */
+    uint32_t spread_x, spread_y; /* crh_spread, per axis */
+    float m[6];                  /* path -> texel: u = m0 x + m1 y + m2, v = m3 x + m4 y + m5 */
+} crh_image_paint;
+crh_status crh_image_paint_validate(const crh_image_paint* paint); /* host only: needs no renderer and no device */
+crh_status crh_scene_set_paints_with_images(crh_scene* scene, const crh_paint* paints, uint32_t n_paints, const crh_image_paint* image_paints,
+                                            uint32_t n_image_paints, const int32_t* instance_paint, uint32_t n_instances);
+
 /* LoadOp::Load of caller content: `rgba8` = width*height*4 bytes of premultiplied RGBA8, row 0 = top, replace the frame's pixels; every
  * sample of a pixel starts from its value. The stencil attachment, the saved alpha layers and the pass state are reset as by
  * crh_frame_clear, the depth attachment is left alone. The frame is NOT cleared afterwards: the next pass loads these pixels. Ordered

@@ -592,6 +592,55 @@ class Paint {
     crh_paint c_;
 };
 
+// Image paints: the texels of an Image as the source of a Color cover (include/contrast_hip.h crh_scene_set_paints_with_images states the model)
+enum class Filter : uint32_t { Nearest = CRH_FILTER_NEAREST, Linear = CRH_FILTER_LINEAR };
+// crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level, no mipmaps.
+// Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
+class Image {
+  public:
+    Image(const Renderer& renderer, uint32_t width, uint32_t height, const uint8_t* rgba8) : width_(width), height_(height) { check(crh_image_create(renderer.raw(), width, height, rgba8, &handle_)); }
+    // a snapshot of what the frame shows (an RGBA8 or RGBA8-attachment frame), copied on the device
+    static Image from_frame(Frame& frame) {
+        Image image;
+        check(crh_image_create_from_frame(frame.raw(), &image.handle_));
+        check(crh_image_size(image.handle_, &image.width_, &image.height_));
+        return image;
+    }
+    ~Image() {
+        if (handle_) crh_image_destroy(handle_);
+    }
+    Image(Image&& other) noexcept : handle_(other.handle_), width_(other.width_), height_(other.height_) { other.handle_ = nullptr; }
+    Image(const Image&) = delete;
+    Image& operator=(const Image&) = delete;
+    uint32_t width() const { return width_; }
+    uint32_t height() const { return height_; }
+    const crh_image* raw() const { return handle_; }
+
+  private:
+    Image() = default;
+    crh_image* handle_ = nullptr;
+    uint32_t width_ = 0, height_ = 0;
+};
+class ImagePaint {
+  public:
+    // matrix: path -> texel, u = m0 x + m1 y + m2, v = m3 x + m4 y + m5
+    ImagePaint(const Image& image, const std::array<float, 6>& matrix, Filter filter = Filter::Linear, Spread spread_x = Spread::Pad, Spread spread_y = Spread::Pad) {
+        c_ = crh_image_paint{};
+        c_.image = image.raw(), c_.filter = (uint32_t)filter, c_.spread_x = (uint32_t)spread_x, c_.spread_y = (uint32_t)spread_y;
+        for (size_t i = 0; i < 6; ++i) c_.m[i] = matrix[i];
+    }
+    // the path rectangle [lower, upper] onto the whole image; path y points up on the frame, so y = upper[1] is the image's row 0
+    static ImagePaint fit(const Image& image, const std::array<float, 2>& lower, const std::array<float, 2>& upper, Filter filter = Filter::Linear) {
+        const float sx = (float)image.width() / (upper[0] - lower[0]), sy = (float)image.height() / (upper[1] - lower[1]);
+        return ImagePaint(image, {sx, 0.0f, -sx * lower[0], 0.0f, -sy, sy * upper[1]}, filter);
+    }
+    void validate() const { check(crh_image_paint_validate(&c_)); } // host only: throws what Scene::set_paints would
+    const crh_image_paint& to_c() const { return c_; }
+
+  private:
+    crh_image_paint c_;
+};
+
 // A batch of Shapes built together (one launch tessellates all of them). Shape below is the n == 1 case with the reference's signature.
 class Scene {
   public:
@@ -601,7 +650,7 @@ class Scene {
         check(crh_scene_upload(renderer.raw(), &view, existing ? existing->raw() : nullptr, &handle_));
         if (existing) {
             existing->release();
-            pass_table_ = std::move(existing->pass_table_), pass_assoc_ = std::move(existing->pass_assoc_), holds_pass_table_ = existing->holds_pass_table_; // (the C scene keeps its table)
+            pass_table_ = std::move(existing->pass_table_), pass_images_ = std::move(existing->pass_images_), pass_assoc_ = std::move(existing->pass_assoc_), holds_pass_table_ = existing->holds_pass_table_; // (the C scene keeps its table)
         }
         crh_status st = crh_scene_tessellate(handle_);
         if (st == CRH_OK) st = crh_scene_status(handle_); // surfaces the reference's panics at the call site, like the reference
@@ -615,7 +664,7 @@ class Scene {
         if (handle_) crh_scene_destroy(handle_);
     }
     Scene(Scene&& other) noexcept
-        : handle_(other.release()), n_shapes_(other.n_shapes_), pass_table_(std::move(other.pass_table_)), pass_assoc_(std::move(other.pass_assoc_)), holds_pass_table_(other.holds_pass_table_) {}
+        : handle_(other.release()), n_shapes_(other.n_shapes_), pass_table_(std::move(other.pass_table_)), pass_images_(std::move(other.pass_images_)), pass_assoc_(std::move(other.pass_assoc_)), holds_pass_table_(other.holds_pass_table_) {}
     Scene(const Scene&) = delete;
     Scene& operator=(const Scene&) = delete;
     uint32_t n_shapes() const { return n_shapes_; }
@@ -641,23 +690,30 @@ class Scene {
     // crh_scene_set_paints: instance_paint[i] = the index into `paints` of instance i's paint, or -1 for its solid colour; stays until the next call,
     // no paints clears it. The call waits for the renderer's work in flight: set the table when it changes, not per frame.
     void set_paints(const std::vector<Paint>& paints, const std::vector<int32_t>& instance_paint) const {
-        install_paints(paints, instance_paint);
+        install_paints(paints, {}, instance_paint);
         holds_pass_table_ = false; // the caller's own table: passes without paints leave it alone
+    }
+    // crh_scene_set_paints_with_images: instance_paint[i] below paints.size() names a gradient, from there on image paint i - paints.size()
+    void set_paints(const std::vector<Paint>& paints, const std::vector<ImagePaint>& image_paints, const std::vector<int32_t>& instance_paint) const {
+        install_paints(paints, image_paints, instance_paint);
+        holds_pass_table_ = false;
     }
     // What RenderPass::submit asks for in front of its draws: the pass's table (none: the pass has no paints). A table an earlier pass put here
     // belongs to that pass's instance numbering, so it is replaced or removed; the call is skipped when the Scene already holds this very table.
-    void paints_of_pass(const std::vector<Paint>& paints, const std::vector<int32_t>& instance_paint) const {
-        if (paints.empty()) {
-            if (holds_pass_table_) install_paints({}, {});
+    void paints_of_pass(const std::vector<Paint>& paints, const std::vector<int32_t>& instance_paint, const std::vector<ImagePaint>& image_paints = {}) const {
+        if (paints.empty() && image_paints.empty()) {
+            if (holds_pass_table_) install_paints({}, {}, {});
             holds_pass_table_ = false;
             return;
         }
-        bool same = holds_pass_table_ && pass_table_.size() == paints.size() && pass_assoc_ == instance_paint;
+        bool same = holds_pass_table_ && pass_table_.size() == paints.size() && pass_images_.size() == image_paints.size() && pass_assoc_ == instance_paint;
         for (size_t i = 0; same && i < paints.size(); ++i) same = std::memcmp(&pass_table_[i], &paints[i].to_c(), sizeof(crh_paint)) == 0;
+        for (size_t i = 0; same && i < image_paints.size(); ++i) same = same_image_paint(pass_images_[i], image_paints[i].to_c());
         if (same) return;
-        install_paints(paints, instance_paint);
-        pass_table_.clear();
+        install_paints(paints, image_paints, instance_paint);
+        pass_table_.clear(), pass_images_.clear();
         for (const Paint& p : paints) pass_table_.push_back(p.to_c());
+        for (const ImagePaint& p : image_paints) pass_images_.push_back(p.to_c());
         pass_assoc_ = instance_paint;
         holds_pass_table_ = true;
     }
@@ -669,15 +725,25 @@ class Scene {
     }
 
   private:
-    void install_paints(const std::vector<Paint>& paints, const std::vector<int32_t>& instance_paint) const {
+    void install_paints(const std::vector<Paint>& paints, const std::vector<ImagePaint>& image_paints, const std::vector<int32_t>& instance_paint) const {
         std::vector<crh_paint> table;
         for (const Paint& p : paints) table.push_back(p.to_c());
-        check(crh_scene_set_paints(handle_, table.data(), (uint32_t)table.size(), instance_paint.data(), (uint32_t)instance_paint.size()));
+        if (image_paints.empty()) { // a list without an image paint goes the way it always went
+            check(crh_scene_set_paints(handle_, table.data(), (uint32_t)table.size(), instance_paint.data(), (uint32_t)instance_paint.size()));
+            return;
+        }
+        std::vector<crh_image_paint> images;
+        for (const ImagePaint& p : image_paints) images.push_back(p.to_c());
+        check(crh_scene_set_paints_with_images(handle_, table.data(), (uint32_t)table.size(), images.data(), (uint32_t)images.size(), instance_paint.data(), (uint32_t)instance_paint.size()));
+    }
+    static bool same_image_paint(const crh_image_paint& a, const crh_image_paint& b) { // (field by field: the struct has padding)
+        return a.image == b.image && a.filter == b.filter && a.spread_x == b.spread_x && a.spread_y == b.spread_y && std::memcmp(a.m, b.m, sizeof(a.m)) == 0;
     }
     crh_scene* handle_ = nullptr;
     uint32_t n_shapes_ = 0;
     // the paint table a RenderPass installed (none: the Scene holds the caller's own table, or nothing)
     mutable std::vector<crh_paint> pass_table_;
+    mutable std::vector<crh_image_paint> pass_images_;
     mutable std::vector<int32_t> pass_assoc_;
     mutable bool holds_pass_table_ = false;
 };
@@ -698,6 +764,13 @@ class RenderPass {
         const uint32_t index = push_instance(transform, color);
         instance_paint_.back() = (int32_t)paints_.size();
         paints_.push_back(paint);
+        return index;
+    }
+    // ... with an image paint: the pass numbers its gradients first and its image paints behind them when it submits
+    uint32_t push_instance(const float (&transform)[16], const float (&color)[4], const ImagePaint& paint) {
+        const uint32_t index = push_instance(transform, color);
+        instance_paint_.back() = -2 - (int32_t)image_paints_.size(); // (-2 - k: image paint k, resolved in submit)
+        image_paints_.push_back(paint);
         return index;
     }
     // Renderer::set_clip_depth (renderer.rs:932-938)
@@ -729,7 +802,10 @@ class RenderPass {
         for (size_t begin = 0; begin < draws_.size();) {
             size_t end = begin;
             while (end < draws_.size() && scenes_[end] == scenes_[begin]) ++end;
-            scenes_[begin]->paints_of_pass(paints_, instance_paint_); // (a pass without paints removes what an earlier pass installed)
+            std::vector<int32_t> association = instance_paint_;
+            for (int32_t& k : association)
+                if (k <= -2) k = (int32_t)paints_.size() + (-2 - k);
+            scenes_[begin]->paints_of_pass(paints_, association, image_paints_); // (a pass without paints removes what an earlier pass installed)
             check(crh_scene_render_draws(scenes_[begin]->raw(), frame_.raw(), transforms_.data(), colors_.data(), (uint32_t)(colors_.size() / 4), draws_.data() + begin, (uint32_t)(end - begin)));
             begin = end;
         }
@@ -742,6 +818,7 @@ class RenderPass {
     Frame& frame_;
     std::vector<float> transforms_, colors_;
     std::vector<Paint> paints_;
+    std::vector<ImagePaint> image_paints_;
     std::vector<int32_t> instance_paint_; // per instance: index into paints_, or -1
     std::vector<crh_draw> draws_;
     std::vector<const Scene*> scenes_; // the object every draw belongs to

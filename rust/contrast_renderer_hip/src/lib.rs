@@ -728,6 +728,73 @@ impl Scene {
         status(unsafe { ffi::crh_scene_set_paints(self.raw, table.as_ptr(), table.len() as u32, instance_paint.as_ptr(), instance_paint.len() as u32) })
     }
 }
+/// How an image paint reads between texel centres (`CRH_FILTER_*`)
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum Filter {
+    Nearest = 0,
+    Linear = 1,
+}
+/// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level, no
+/// mipmaps. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels.
+pub struct Image {
+    raw: *mut ffi::crh_image,
+    width: u32,
+    height: u32,
+}
+impl Image {
+    /// `rgba8`: width * height * 4 bytes, copied before the call returns
+    pub fn new(renderer: &Renderer, width: u32, height: u32, rgba8: &[u8]) -> Result<Image, Error> {
+        assert_eq!(rgba8.len(), width as usize * height as usize * 4);
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_create(renderer.raw, width, height, rgba8.as_ptr() as *const _, &mut raw) })?;
+        Ok(Image { raw, width, height })
+    }
+    /// A snapshot of what the frame shows (an RGBA8 or RGBA8-attachment frame), copied on the device
+    pub fn from_frame(frame: &Frame) -> Result<Image, Error> {
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_create_from_frame(frame.raw, &mut raw) })?;
+        let (mut width, mut height) = (0u32, 0u32);
+        status(unsafe { ffi::crh_image_size(raw, &mut width, &mut height) })?;
+        Ok(Image { raw, width, height })
+    }
+    pub fn size(&self) -> (u32, u32) {
+        (self.width, self.height)
+    }
+}
+impl Drop for Image {
+    fn drop(&mut self) {
+        unsafe { ffi::crh_image_destroy(self.raw) }
+    }
+}
+/// The texels of an `Image` as the source of a Color cover, times the instance colour (include/contrast_hip.h,
+/// `crh_scene_set_paints_with_images`, states the model). `matrix` maps path coordinates to texels: u = m0 x + m1 y + m2, v = m3 x + m4 y + m5.
+#[derive(Clone, Copy)]
+pub struct ImagePaint(pub ffi::crh_image_paint);
+impl ImagePaint {
+    pub fn new(image: &Image, matrix: [f32; 6], filter: Filter, spread_x: Spread, spread_y: Spread) -> Self {
+        ImagePaint(ffi::crh_image_paint { image: image.raw, filter: filter as u32, spread_x: spread_x as u32, spread_y: spread_y as u32, m: matrix })
+    }
+    /// The path rectangle [lower, upper] onto the whole image; path y points up on the frame, so y = upper[1] is the image's row 0
+    pub fn fit(image: &Image, lower: [f32; 2], upper: [f32; 2], filter: Filter) -> Self {
+        let (sx, sy) = (image.width as f32 / (upper[0] - lower[0]), image.height as f32 / (upper[1] - lower[1]));
+        Self::new(image, [sx, 0.0, -sx * lower[0], 0.0, -sy, sy * upper[1]], filter, Spread::Pad, Spread::Pad)
+    }
+    /// Host only: what `Scene::set_paints_with_images` would refuse
+    pub fn validate(&self) -> Result<(), Error> {
+        status(unsafe { ffi::crh_image_paint_validate(&self.0) })
+    }
+}
+impl Scene {
+    /// `instance_paint[i]` below `paints.len()` names a gradient, from there on image paint `i - paints.len()`, -1 the solid colour. Stays
+    /// with the Scene until the next call (of this or of `set_paints`); the table keeps the pixels of its images.
+    pub fn set_paints_with_images(&self, paints: &[Paint], image_paints: &[ImagePaint], instance_paint: &[i32]) -> Result<(), Error> {
+        let table: Vec<ffi::crh_paint> = paints.iter().map(|p| p.0).collect();
+        let images: Vec<ffi::crh_image_paint> = image_paints.iter().map(|p| p.0).collect();
+        status(unsafe {
+            ffi::crh_scene_set_paints_with_images(self.raw, table.as_ptr(), table.len() as u32, images.as_ptr(), images.len() as u32, instance_paint.as_ptr(), instance_paint.len() as u32)
+        })
+    }
+}
 impl Drop for Scene {
     fn drop(&mut self) {
         unsafe { ffi::crh_scene_destroy(self.raw) }
