@@ -377,10 +377,15 @@ struct crh_frame {
 constexpr int kTessBufs = 33; // buffers a tessellation run writes (crh_scene::tess_bufs)
 // The texels of a crh_image on the device, shared by the image and by every paint table that names it (crh_scene_set_paints_with_images):
 // freed with the last of them, so that no kernel of a pass reads an image its caller has destroyed.
+// Its mipmaps (crh_image_generate_mipmaps) are one more allocation of the same object — the level table at its head, the levels >= 1 behind it —
+// so a table keeps them alive exactly as it keeps level 0.
 struct ImagePixels {
     void* p = nullptr;
+    void* chain = nullptr;          // [kImageLevelTableWords | level 1 | level 2 | ...] 32-bit words, or nullptr: one level
+    std::vector<ImageLevel> levels; // the table as the host wrote it (empty: one level)
     ~ImagePixels() {
         if (p) (void)hipFree(p);
+        if (chain) (void)hipFree(chain);
     }
 };
 struct crh_image {
@@ -461,6 +466,8 @@ struct crh_scene {
     // image paints (crh_scene_set_paints_with_images): association indices at n_paints and beyond name them; the table shares the pixels of its images
     uint32_t n_image_paints = 0;
     uint32_t first_image_painted = 0xFFFFFFFFu; // the lowest instance with an image paint
+    uint32_t first_mip_painted = 0xFFFFFFFFu;   // ... with an image paint that reads a mip chain (CRH_FILTER_MIPMAP on an image with levels)
+    std::vector<uint32_t> mip_paints;           // the association indices of those paints
     DevBuf image_paints;                        // [n_image_paints] ImagePaintRec
     std::vector<std::shared_ptr<ImagePixels>> image_pixels;
     // frame pipelining: tessellation runs on its own stream; these events order it against the raster stream
@@ -1230,9 +1237,9 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     // The general pass keeps the reference's triangle strips (raster.hip): clip nesting / alpha contexts, perspective, depth, and face
     // culling (a cull decision is per strip triangle). Everything else is the edge pass (bin_edges.hip, raster_edges.hip).
     // a pass that draws a painted instance with a Color cover (crh_scene_set_paints); a Scene without paints asks nothing
-    bool painted = false, imaged = false; // imaged: one of them is an image paint (k_raster_image)
+    bool painted = false, imaged = false, mipped = false; // imaged: one of them is an image paint (k_raster_image); mipped: one that reads a mip chain (k_raster_mip)
     if (sc->n_paints + sc->n_image_paints != 0u) {
-        if (!recorded) painted = sc->first_painted < sc->d.n_shapes, imaged = sc->first_image_painted < sc->d.n_shapes;
+        if (!recorded) painted = sc->first_painted < sc->d.n_shapes, imaged = sc->first_image_painted < sc->d.n_shapes, mipped = sc->first_mip_painted < sc->d.n_shapes;
         else
             for (const DrawItem& it : f->items_host)
                 if ((it.ops >> 4) == (uint32_t)CRH_OP_COLOR + 1u && it.instance < sc->instance_paint.size() && sc->instance_paint[it.instance] >= 0) {
@@ -1240,7 +1247,11 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
                     if (sc->n_image_paints == 0u) break;
                     if (sc->instance_paint[it.instance] >= (int32_t)sc->n_paints) {
                         imaged = true;
-                        break;
+                        if (sc->mip_paints.empty()) break;
+                        if (std::find(sc->mip_paints.begin(), sc->mip_paints.end(), (uint32_t)sc->instance_paint[it.instance]) != sc->mip_paints.end()) {
+                            mipped = true;
+                            break;
+                        }
                     }
                 }
     }
@@ -1471,7 +1482,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         const PaintArgs paint_args = {sc->paint_items[rec].as<PaintItem>(), sc->paint_heads.as<PaintHead>(), sc->paint_stops.as<PaintStop>()};
         const ImageArgs image_args = {sc->image_paints.as<ImagePaintRec>()};
         f->last_raster = launch_raster(sc->d, p, r->config.msaa_sample_count, r->stream, r->mark_fn(), r, raster_bytes, sc->has_stroke, (r->blend_over && !painted) ? nullptr : &r->blend_form,
-                                       painted ? &paint_args : nullptr, imaged ? &image_args : nullptr);
+                                       painted ? &paint_args : nullptr, imaged ? &image_args : nullptr, mipped);
     }
     f->last_formulation = (uint32_t)pass | (measured ? 256u : 0u), f->last_general = p.general | (r->pipeline ? 0u : 256u);
     if (direct) f->last_bin |= 256u;
@@ -2503,7 +2514,7 @@ crh_status crh_image_paint_validate(const crh_image_paint* paint) {
     for (float v : paint->m)
         if (!std::isfinite(v)) return CRH_ERR_NON_FINITE;
     if (!paint->image) return image_paint_error("null image");
-    if (paint->filter != CRH_FILTER_NEAREST && paint->filter != CRH_FILTER_LINEAR) return image_paint_error("unknown filter");
+    if ((paint->filter & ~(uint32_t)CRH_FILTER_MIPMAP) > CRH_FILTER_LINEAR) return image_paint_error("unknown filter");
     if (paint->spread_x > CRH_SPREAD_REFLECT || paint->spread_y > CRH_SPREAD_REFLECT) return image_paint_error("unknown spread");
     return CRH_OK;
 }
@@ -2517,7 +2528,8 @@ crh_status crh_scene_set_paints_with_images(crh_scene* sc, const crh_paint* pain
     crh_renderer* r = sc->renderer;
     std::vector<ImagePaintRec> image_recs;
     std::vector<std::shared_ptr<ImagePixels>> image_pixels;
-    uint32_t first_image_painted = 0xFFFFFFFFu;
+    std::vector<uint32_t> mip_paints; // association indices of the image paints that read a mip chain
+    uint32_t first_image_painted = 0xFFFFFFFFu, first_mip_painted = 0xFFFFFFFFu;
     for (uint32_t k = 0; k < n_image_paints; ++k) {
         const crh_status st = crh_image_paint_validate(&image_paints[k]);
         if (st != CRH_OK) return st;
@@ -2527,6 +2539,12 @@ crh_status crh_scene_set_paints_with_images(crh_scene* sc, const crh_paint* pain
         rec.texels = static_cast<const uint32_t*>(q.image->pixels->p);
         rec.width = q.image->width, rec.height = q.image->height;
         rec.filter = q.filter, rec.spread_x = q.spread_x, rec.spread_y = q.spread_y;
+        // the levels the image has now: a table set before crh_image_generate_mipmaps keeps its one level. CRH_FILTER_MIPMAP on one level is the
+        // base filter (f = 0 everywhere), so the flag stays on the record — and asks for k_raster_mip — only where there is a chain to read.
+        rec.levels = q.image->pixels->chain ? (uint32_t)q.image->pixels->levels.size() : 1u;
+        rec.chain = static_cast<const ImageLevel*>(q.image->pixels->chain);
+        if (rec.levels <= 1u) rec.filter &= ~(uint32_t)CRH_FILTER_MIPMAP;
+        if ((rec.filter & CRH_FILTER_MIPMAP) != 0u) mip_paints.push_back(n_paints + k);
         for (int i = 0; i < 6; ++i) rec.m[i] = q.m[i];
         image_recs.push_back(rec);
         image_pixels.push_back(q.image->pixels);
@@ -2568,6 +2586,7 @@ crh_status crh_scene_set_paints_with_images(crh_scene* sc, const crh_paint* pain
             if (assoc[i] < -1 || assoc[i] >= (int32_t)n_all) return paint_error("an instance_paint entry is neither -1 nor an index into paints");
             if (assoc[i] >= 0 && first_painted == 0xFFFFFFFFu) first_painted = i;
             if (assoc[i] >= (int32_t)n_paints && first_image_painted == 0xFFFFFFFFu) first_image_painted = i;
+            if (first_mip_painted == 0xFFFFFFFFu && std::find(mip_paints.begin(), mip_paints.end(), (uint32_t)assoc[i]) != mip_paints.end()) first_mip_painted = i;
         }
     }
     HIP_TRY(hipSetDevice(r->device));
@@ -2591,6 +2610,8 @@ crh_status crh_scene_set_paints_with_images(crh_scene* sc, const crh_paint* pain
     }
     sc->n_image_paints = n_image_paints;
     sc->first_image_painted = first_image_painted;
+    sc->first_mip_painted = first_mip_painted;
+    sc->mip_paints = std::move(mip_paints);
     sc->image_pixels = std::move(image_pixels); // the earlier table's images go with it (nothing in flight reads them: the renderer was waited for above)
     sc->n_paints = n_paints;
     sc->instance_paint = std::move(assoc);
@@ -2819,7 +2840,61 @@ crh_status crh_image_size(const crh_image* image, uint32_t* width, uint32_t* hei
     *width = image->width, *height = image->height;
     return CRH_OK;
 }
-void crh_image_destroy(crh_image* image) { delete image; } // (the pixels stay while a Scene's paint table names them)
+crh_status crh_image_generate_mipmaps(crh_image* image) {
+    if (!image || !image->renderer) return CRH_ERR_INVALID_ARGUMENT;
+    ImagePixels& px = *image->pixels;
+    if (px.chain) return CRH_OK; // (the levels are what they were: level 0 never changes)
+    crh_renderer* r = image->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    std::vector<ImageLevel> levels;
+    uint32_t w = image->width, h = image->height, words = kImageLevelTableWords;
+    for (;;) {
+        ImageLevel l = {};
+        l.offset = levels.empty() ? 0u : words, l.width = w, l.height = h;
+        l.sx = (float)w / (float)image->width, l.sy = (float)h / (float)image->height;
+        if (!levels.empty()) words += w * h; // (< 2^27 + 2^25 ...: the levels >= 1 of a 16384^2 image are a third of its 2^28 texels)
+        levels.push_back(l);
+        if (w == 1u && h == 1u) break;
+        w = std::max(1u, w >> 1), h = std::max(1u, h >> 1);
+    }
+    void* chain = nullptr;
+    HIP_TRY(hipMalloc(&chain, (size_t)words * 4));
+    bool ok = hip_ok(hipMemsetAsync(chain, 0, (size_t)kImageLevelTableWords * 4, r->stream), "hipMemsetAsync(levels)") &&
+              hip_ok(hipMemcpyAsync(chain, levels.data(), levels.size() * sizeof(ImageLevel), hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(levels)");
+    for (size_t l = 1; ok && l < levels.size(); ++l) {
+        const uint32_t* src = l == 1 ? static_cast<const uint32_t*>(px.p) : static_cast<const uint32_t*>(chain) + levels[l - 1].offset;
+        launch_image_downsample(src, levels[l - 1].width, levels[l - 1].height, static_cast<uint32_t*>(chain) + levels[l].offset, levels[l].width, levels[l].height, r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_downsample");
+    }
+    ok = hip_ok(r->sync(), "sync(mipmaps)") && ok; // (also behind a failed launch: `levels` is read by the copy above until the stream has drained)
+    if (!ok) {
+        (void)hipFree(chain);
+        return CRH_ERR_HIP;
+    }
+    px.chain = chain, px.levels = std::move(levels);
+    return CRH_OK;
+}
+crh_status crh_image_level_count(const crh_image* image, uint32_t* count) {
+    if (!image || !count) return CRH_ERR_INVALID_ARGUMENT;
+    *count = image->pixels->chain ? (uint32_t)image->pixels->levels.size() : 1u;
+    return CRH_OK;
+}
+crh_status crh_image_download_level(const crh_image* image, uint32_t level, void* rgba8, uint32_t* width, uint32_t* height) {
+    if (!image || !image->renderer) return CRH_ERR_INVALID_ARGUMENT;
+    const ImagePixels& px = *image->pixels;
+    if (level >= (px.chain ? (uint32_t)px.levels.size() : 1u)) return CRH_ERR_INVALID_ARGUMENT;
+    const uint32_t w = level ? px.levels[level].width : image->width, h = level ? px.levels[level].height : image->height;
+    if (width) *width = w;
+    if (height) *height = h;
+    if (!rgba8) return CRH_OK; // the size alone
+    crh_renderer* r = image->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    const void* src = level ? static_cast<const void*>(static_cast<const uint32_t*>(px.chain) + px.levels[level].offset) : px.p;
+    HIP_TRY(hipMemcpyAsync(rgba8, src, (size_t)w * h * 4, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r->sync());
+    return CRH_OK;
+}
+void crh_image_destroy(crh_image* image) { delete image; } // (the pixels and their mipmaps stay while a Scene's paint table names them)
 crh_status crh_frame_download_f16(crh_frame* f, void* rgba16f) { return download_pixels(f, rgba16f, CRH_FORMAT_RGBA16F); }
 extern "C" crh_status crh_debug_frame_counters(crh_frame* f, uint32_t out[8]) { // tools only (not in the public header)
     HIP_TRY(hipSetDevice(f->renderer->device));

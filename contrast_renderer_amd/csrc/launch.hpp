@@ -25,9 +25,10 @@ void launch_item_ranges(const SceneDev& s, const RasterParams& r, uint32_t* item
 void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup);
 void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_fill);
 uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, uint64_t raster_bytes, bool has_stroke,
-                       const BlendForm* blend, const PaintArgs* paint = nullptr, const ImageArgs* images = nullptr); // -> RasterVariant; blend: nullptr = premultiplied "over", otherwise k_raster_blend; paint (with blend): k_raster_paint; images (with paint): k_raster_image
+                       const BlendForm* blend, const PaintArgs* paint = nullptr, const ImageArgs* images = nullptr, bool mips = false); // -> RasterVariant; blend: nullptr = premultiplied "over", otherwise k_raster_blend; paint (with blend): k_raster_paint; images (with paint): k_raster_image; mips (with images): k_raster_mip
 void launch_paint_items(const RasterParams& r, const PaintTable& t, hipStream_t stream); // behind launch_bin: the PaintItem records and the tags of a painted pass
 void launch_paint_items_images(const RasterParams& r, const PaintTable& t, uint32_t n_gradients, hipStream_t stream); // behind launch_paint_items in an image-painted pass: which records name an image paint
+void launch_image_downsample(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint32_t* dst, uint32_t dst_w, uint32_t dst_h, hipStream_t stream); // one level of a mip chain from the level above
 void launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t* block_sum, uint32_t n, hipStream_t stream); // exclusive scan; out[n] = the total
 void launch_scan_u32_pair(const uint32_t* in0, uint32_t* out0, uint32_t* block_sum0, const uint32_t* in1, uint32_t* out1, uint32_t* block_sum1, uint32_t n, hipStream_t stream);
 void launch_scan_tiles(const RasterParams& r, hipStream_t stream); // exclusive scan of tile_count -> tile_offset, pair total, longest list

@@ -21,6 +21,8 @@
 //
 // Roofline note: algorithmic traffic = emitted vertices read once + W*H*4 bytes written once; the raster kernel is VALU-issue bound
 // (edge functions per sample), the others latency bound; there is no GEMM shape for MFMA anywhere.
+#include <type_traits>
+
 #include "launch.hpp"
 #include "raster_tile_list.hpp"
 
@@ -580,9 +582,141 @@ CRH_D int image_wrap(int i, int n, uint32_t spread) { // -> [0, n): n >= 1 (crh_
 CRH_D float texel_channel(uint32_t texel, int ch) { return (float)((texel >> (8 * ch)) & 255u) / 255.0f; }
 // how many of a turn's four samples fetch their texels together (msaa 8 holds eight samples' state per lane: DESIGN.md §7 "Image paints")
 #define CRH_IMAGE_FETCH_TOGETHER(S_) ((S_) == 8 ? 1 : 4)
+// ---- the mipmap block of the body (MIPS: k_raster_mip below, compiled out of the other kernels; include/contrast_hip.h crh_image_generate_mipmaps states the model)
+// how many of a sample's two levels are fetched in one go: both where the registers allow it, one after the other where eight samples' state is held
+#define CRH_MIP_LEVELS_TOGETHER(S_) ((S_) == 8 ? 1 : 2)
+// lod = clamp(log2(rho), 0, L - 1) from rho^2 (half the logarithm: no square root); NaN and rho == 0 give 0
+CRH_D float mip_lod(float rho2, uint32_t levels) { return fminf(fmaxf(0.5f * __log2f(rho2), 0.0f), (float)(levels - 1u)); }
+// rho^2 = the longer column of J = d(u, v) / d(frame position), squared: jx = (dX/dsx, dY/dsx), jy = (dX/dsy, dY/dsy) of the path position,
+// taken through the path -> texel map m. A NaN column wins (lod 0).
+CRH_D float mip_rho2(const float (&m)[6], float dXx, float dYx, float dXy, float dYy) {
+    const float ux = m[0] * dXx + m[1] * dYx, vx = m[3] * dXx + m[4] * dYx;
+    const float uy = m[0] * dXy + m[1] * dYy, vy = m[3] * dXy + m[4] * dYy;
+    const float cx = ux * ux + vx * vx, cy = uy * uy + vy * vy;
+    return (cx > cy || cx != cx) ? cx : cy;
+}
+// The texels a sample reads at one level — one for NEAREST, four for LINEAR — every address from indices wrapped with the level's own size,
+// and the fractions of the LINEAR filter: the image block's rule at texel coordinates (u, v) of that level. Loads only; image_filter unpacks.
+CRH_D void image_fetch(const uint32_t* texels, uint32_t width, uint32_t height, float u, float v, bool linear, uint32_t spread_x, uint32_t spread_y, uint32_t (&tex)[4], float (&frac)[2]) {
+    const int iw = (int)width, ih = (int)height;
+    if (linear) {
+        const float au = u - 0.5f, av = v - 0.5f;
+        const float fu = floorf(au), fv = floorf(av);
+        frac[0] = au - fu, frac[1] = av - fv;
+        const int i0 = image_wrap((int)fu, iw, spread_x), i1 = image_wrap((int)fu + 1, iw, spread_x);
+        const int j0 = image_wrap((int)fv, ih, spread_y), j1 = image_wrap((int)fv + 1, ih, spread_y);
+        tex[0] = texels[(uint32_t)j0 * width + (uint32_t)i0];
+        tex[1] = texels[(uint32_t)j0 * width + (uint32_t)i1];
+        tex[2] = texels[(uint32_t)j1 * width + (uint32_t)i0];
+        tex[3] = texels[(uint32_t)j1 * width + (uint32_t)i1];
+    } else {
+        const int i0 = image_wrap((int)floorf(u), iw, spread_x), j0 = image_wrap((int)floorf(v), ih, spread_y);
+        tex[0] = texels[(uint32_t)j0 * width + (uint32_t)i0];
+    }
+}
+CRH_D float image_filter(const uint32_t (&tex)[4], const float (&frac)[2], bool linear, int ch) {
+    const float t00 = texel_channel(tex[0], ch);
+    if (!linear) return t00;
+    const float t01 = texel_channel(tex[1], ch), t10 = texel_channel(tex[2], ch), t11 = texel_channel(tex[3], ch);
+    const float top = t00 + frac[0] * (t01 - t00), bottom = t10 + frac[0] * (t11 - t10);
+    return top + frac[1] * (bottom - top);
+}
+// What an affine item's mipmapped cover needs, wave uniform (one Jacobian for every sample): the two level records and the fraction between them
+struct MipUniform {
+    ImageLevel level[2];
+    float f;
+};
+CRH_D MipUniform mip_uniform(const PaintItem& pi, const ImagePaintRec& im) {
+    MipUniform out;
+    const float lod = mip_lod(mip_rho2(im.m, pi.h[0], pi.h[3], pi.h[1], pi.h[4]), im.levels);
+    const uint32_t l0 = __builtin_amdgcn_readfirstlane((uint32_t)lod), l1 = min(l0 + 1u, im.levels - 1u);
+    out.f = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(lod - (float)l0)));
+    out.level[0] = load_uniform(&im.chain[l0]);
+    out.level[1] = load_uniform(&im.chain[l1]);
+    return out;
+}
+// N samples of a mipmapped image paint at the frame positions (fx, fy) -> the premultiplied value s(l0) + f (s(l1) - s(l0)) of each.
+// UNIFORM (an affine item): the levels and f of `uni`, and no fetch at the second level when f == 0 — a magnified placement costs what its base
+// filter costs. Otherwise (a projective item) lod per sample from the sample's own (X, Y, W), and the level records by per-lane loads from the
+// table. All loads of a step — N samples x CRH_MIP_LEVELS_TOGETHER levels — are issued before the first unpack.
+template <int N, int TOGETHER, bool UNIFORM>
+CRH_D void mip_samples(const PaintItem& pi, const ImagePaintRec& im, const MipUniform& uni, const float (&fx)[N], const float (&fy)[N], float (&out)[N][4]) {
+    const bool linear = (im.filter & 1u) == CRH_FILTER_LINEAR;
+    const uint32_t* chain = reinterpret_cast<const uint32_t*>(im.chain);
+    float u[N], v[N], f[N];
+    uint32_t level[N][2];
+    int second = 0;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        float X = fmaf(fy[c], pi.h[1], fmaf(fx[c], pi.h[0], pi.h[2])), Y = fmaf(fy[c], pi.h[4], fmaf(fx[c], pi.h[3], pi.h[5]));
+        if (UNIFORM) {
+            f[c] = uni.f;
+            level[c][0] = level[c][1] = 0u; // (not read)
+        } else {
+            const float W = fmaf(fy[c], pi.h[7], fmaf(fx[c], pi.h[6], pi.h[8]));
+            X = X / W;
+            Y = Y / W;
+            // d(X, Y) / d(sx, sy) = (h0 - X h6, h3 - Y h6; h1 - X h7, h4 - Y h7) / W: the division once, on rho^2
+            const float rho2 = mip_rho2(im.m, pi.h[0] - X * pi.h[6], pi.h[3] - Y * pi.h[6], pi.h[1] - X * pi.h[7], pi.h[4] - Y * pi.h[7]) / (W * W);
+            const float lod = mip_lod(rho2, im.levels);
+            level[c][0] = (uint32_t)lod;
+            level[c][1] = min(level[c][0] + 1u, im.levels - 1u);
+            f[c] = lod - (float)level[c][0];
+        }
+        second |= (int)(f[c] != 0.0f);
+        u[c] = image_coord(fmaf(Y, im.m[1], fmaf(X, im.m[0], im.m[2])));
+        v[c] = image_coord(fmaf(Y, im.m[4], fmaf(X, im.m[3], im.m[5])));
+    }
+    const bool both = UNIFORM ? uni.f != 0.0f : __any(second) != 0; // wave uniform
+    auto step = [&](auto first) __attribute__((always_inline)) { // the levels [p0, p0 + TOGETHER) of every sample; p0 a compile-time constant, so that no array is indexed at run time
+        constexpr int p0 = decltype(first)::value;
+        uint32_t tex[N][TOGETHER][4];
+        float frac[N][TOGETHER][2];
+        ImageLevel lr[UNIFORM ? 1 : N][TOGETHER]; // a projective item: the records of this step's levels, all loaded before the first texel address
+        if (!UNIFORM) {
+#pragma unroll
+            for (int c = 0; c < N; ++c)
+#pragma unroll
+                for (int p = p0; p < p0 + TOGETHER; ++p) {
+                    if (p == 1 && !both) continue;
+                    const ImageLevel* at = &im.chain[level[c][p]]; // level < im.levels <= kMaxImageLevels: inside the table
+                    lr[c][p - p0].offset = at->offset, lr[c][p - p0].width = at->width, lr[c][p - p0].height = at->height;
+                    lr[c][p - p0].sx = at->sx, lr[c][p - p0].sy = at->sy;
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+#pragma unroll
+            for (int p = p0; p < p0 + TOGETHER; ++p) {
+                if (p == 1 && !both) continue;
+                if (UNIFORM) {
+                    const ImageLevel& l = uni.level[p];
+                    const uint32_t* texels = l.offset == 0u ? im.texels : chain + l.offset; // wave uniform: level 0 is the image's own allocation
+                    image_fetch(texels, l.width, l.height, u[c] * l.sx, v[c] * l.sy, linear, im.spread_x, im.spread_y, tex[c][p - p0], frac[c][p - p0]);
+                } else {
+                    const ImageLevel& l = lr[c][p - p0];
+                    const uint32_t* texels = level[c][p] == 0u ? im.texels : chain + l.offset;
+                    image_fetch(texels, l.width, l.height, u[c] * l.sx, v[c] * l.sy, linear, im.spread_x, im.spread_y, tex[c][p - p0], frac[c][p - p0]);
+                }
+            }
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+#pragma unroll
+            for (int p = p0; p < p0 + TOGETHER; ++p) {
+                if (p == 1 && !both) continue;
+#pragma unroll
+                for (int ch = 0; ch < 4; ++ch) {
+                    const float value = image_filter(tex[c][p - p0], frac[c][p - p0], linear, ch);
+                    out[c][ch] = p == 0 ? value : out[c][ch] + f[c] * (value - out[c][ch]);
+                }
+            }
+    };
+    step(std::integral_constant<int, 0>());
+    if (TOGETHER == 1 && both) step(std::integral_constant<int, 1>());
+}
 template <int S, int ROWS, bool OPS, bool STROKES, bool XFMT = false> // XFMT: the frame formats 3-8 (raster_common.hpp store_px)
 __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu((OPS || STROKES || S >= 4) ? 1 : CRH_TILE_WAVES))) void k_raster_tile(SceneDev s, RasterParams r) {
-    constexpr bool BLEND = false, PAINT = false, IMAGES = false;
+    constexpr bool BLEND = false, PAINT = false, IMAGES = false, MIPS = false;
     const BlendForm bf = {}; // (not read: the blend block is compiled out)
     const PaintArgs pa = {}; // (nor this: the paint block is)
     const ImageArgs ia = {};
@@ -592,7 +726,7 @@ __global__ __launch_bounds__(64 * (4 / ROWS)) __attribute__((amdgpu_waves_per_eu
 template <int S, bool STROKES, bool XFMT = false>
 __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_blend(SceneDev s, RasterParams r, BlendForm bf) {
     constexpr int ROWS = tile_rows(S);
-    constexpr bool OPS = true, BLEND = true, PAINT = false, IMAGES = false;
+    constexpr bool OPS = true, BLEND = true, PAINT = false, IMAGES = false, MIPS = false;
     const PaintArgs pa = {};
     const ImageArgs ia = {};
 #include "raster_tile_body.inc"
@@ -603,7 +737,7 @@ __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per
 template <int S, bool STROKES, bool XFMT = false>
 __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_paint(SceneDev s, RasterParams r, BlendForm bf, PaintArgs pa) {
     constexpr int ROWS = tile_rows(S);
-    constexpr bool OPS = true, BLEND = true, PAINT = true, IMAGES = false;
+    constexpr bool OPS = true, BLEND = true, PAINT = true, IMAGES = false, MIPS = false;
     const ImageArgs ia = {}; // (not read: the image block is compiled out)
 #include "raster_tile_body.inc"
 }
@@ -614,8 +748,34 @@ __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per
 template <int S, bool STROKES, bool XFMT = false>
 __global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_image(SceneDev s, RasterParams r, BlendForm bf, PaintArgs pa, ImageArgs ia) {
     constexpr int ROWS = tile_rows(S);
-    constexpr bool OPS = true, BLEND = true, PAINT = true, IMAGES = true;
+    constexpr bool OPS = true, BLEND = true, PAINT = true, IMAGES = true, MIPS = false;
 #include "raster_tile_body.inc"
+}
+// k_raster_image with mipmaps (CRH_FILTER_MIPMAP on an image with a level chain, crh_image_generate_mipmaps): an image paint that carries the flag takes
+// its source from two levels of the chain, chosen per item (affine) or per sample (projective) by the size of a pixel in texels — the body's mipmap
+// block (MIPS, compiled out of the four kernels above). Every other item, an unflagged image paint's included, is drawn as k_raster_image draws it.
+// Only the pass that draws a flagged image paint through a Color cover runs this kernel.
+template <int S, bool STROKES, bool XFMT = false>
+__global__ __launch_bounds__(64 * tile_waves(S)) __attribute__((amdgpu_waves_per_eu(1))) void k_raster_mip(SceneDev s, RasterParams r, BlendForm bf, PaintArgs pa, ImageArgs ia) {
+    constexpr int ROWS = tile_rows(S);
+    constexpr bool OPS = true, BLEND = true, PAINT = true, IMAGES = true, MIPS = true;
+#include "raster_tile_body.inc"
+}
+// crh_image_generate_mipmaps, one launch per level, one thread per texel of the level written: the rounded mean of the 2 x 2 block of the level
+// above per channel, (a + b + c + d + 2) >> 2 on the codes, the block's columns and rows clamped to that level (a level one texel wide or high).
+__global__ __launch_bounds__(256) void k_image_downsample(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint32_t* dst, uint32_t dst_w, uint32_t dst_h) {
+    const uint32_t at = blockIdx.x * 256u + threadIdx.x; // < 2^26: a level >= 1 has at most 8192^2 texels
+    if (at >= dst_w * dst_h) return;
+    const uint32_t j = at / dst_w, i = at - j * dst_w;
+    const uint32_t i0 = min(2u * i, src_w - 1u), i1 = min(2u * i + 1u, src_w - 1u), j0 = min(2u * j, src_h - 1u), j1 = min(2u * j + 1u, src_h - 1u);
+    const uint32_t a = src[j0 * src_w + i0], b = src[j0 * src_w + i1], c = src[j1 * src_w + i0], d = src[j1 * src_w + i1];
+    uint32_t out = 0u;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+        const int sh = 8 * ch;
+        out |= ((((a >> sh) & 255u) + ((b >> sh) & 255u) + ((c >> sh) & 255u) + ((d >> sh) & 255u) + 2u) >> 2) << sh;
+    }
+    dst[at] = out;
 }
 // Behind k_paint_items in an image-painted pass, one thread per draw item: the record of an item whose instance names an image paint (an
 // association index at or beyond the gradients') gets paint = 0, pad = image paint + 1. The condition is k_paint_items' own, so only records
@@ -784,11 +944,11 @@ void launch_fill(const SceneDev& s, const RasterParams& r, uint32_t samples, hip
     if (after_fill) (void)hipEventRecord(after_fill, stream);
     if (mark) mark(ctx, "raster_tile_fill", 0);
 }
-// The raster kernel of msaa S: k_raster_image for a pass that draws an image-painted instance, k_raster_paint for a pass that draws a (gradient-)painted one, k_raster_blend for a blend state other than "over"
+// The raster kernel of msaa S: k_raster_mip for a pass that draws an image paint with CRH_FILTER_MIPMAP, k_raster_image for a pass that draws an image-painted instance, k_raster_paint for a pass that draws a (gradient-)painted one, k_raster_blend for a blend state other than "over"
 // (r.general is set with both), else k_raster_tile, OPS for
 // clip nesting / alpha contexts / depth / projective instances
 template <int S>
-static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_t stream, dim3 grid, bool has_stroke, const BlendForm* blend, const PaintArgs* paint, const ImageArgs* images) {
+static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_t stream, dim3 grid, bool has_stroke, const BlendForm* blend, const PaintArgs* paint, const ImageArgs* images, bool mips) {
     constexpr int ROWS = tile_rows(S);
     const dim3 block(64u * tile_waves(S));
     const uint32_t lds = tile_waves(S) * r.sort_capacity * 4u;
@@ -821,7 +981,16 @@ static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_
         else                                                                                                                     \
             hipLaunchKernelGGL((k_raster_image<S, STROKES_>), grid, block, lds, stream, s, r, *blend, *paint, *images);         \
     } while (0)
-    if (blend && paint && images) {
+#define CRH_LAUNCH_MIP(STROKES_)                                                                                                   \
+    do {                                                                                                                         \
+        if (xfmt)                                                                                                                \
+            hipLaunchKernelGGL((k_raster_mip<S, STROKES_, true>), grid, block, lds, stream, s, r, *blend, *paint, *images);     \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_raster_mip<S, STROKES_>), grid, block, lds, stream, s, r, *blend, *paint, *images);           \
+    } while (0)
+    if (blend && paint && images && mips) {
+        if (has_stroke) CRH_LAUNCH_MIP(true); else CRH_LAUNCH_MIP(false);
+    } else if (blend && paint && images) {
         if (has_stroke) CRH_LAUNCH_IMAGE(true); else CRH_LAUNCH_IMAGE(false);
     } else if (blend && paint) {
         if (has_stroke) CRH_LAUNCH_PAINT(true); else CRH_LAUNCH_PAINT(false);
@@ -836,6 +1005,7 @@ static void launch_raster_s(const SceneDev& s, const RasterParams& r, hipStream_
 #undef CRH_LAUNCH_BLEND
 #undef CRH_LAUNCH_PAINT
 #undef CRH_LAUNCH_IMAGE
+#undef CRH_LAUNCH_MIP
 }
 void launch_paint_items(const RasterParams& r, const PaintTable& t, hipStream_t stream) {
     if (r.n_items) hipLaunchKernelGGL(k_paint_items, dim3(r.n_items), dim3(64), 0, stream, r, t);
@@ -843,18 +1013,22 @@ void launch_paint_items(const RasterParams& r, const PaintTable& t, hipStream_t 
 void launch_paint_items_images(const RasterParams& r, const PaintTable& t, uint32_t n_gradients, hipStream_t stream) {
     if (r.n_items) hipLaunchKernelGGL(k_paint_items_images, dim3((r.n_items + 63u) / 64u), dim3(64), 0, stream, r, t, n_gradients);
 }
+// One level of an image's chain from the level above it (crh_image_generate_mipmaps)
+void launch_image_downsample(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint32_t* dst, uint32_t dst_w, uint32_t dst_h, hipStream_t stream) {
+    hipLaunchKernelGGL(k_image_downsample, dim3((dst_w * dst_h + 255u) / 256u), dim3(256), 0, stream, src, src_w, src_h, dst, dst_w, dst_h);
+}
 // -> RasterVariant (0: nothing launched)
 uint32_t launch_raster(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx,
-                   uint64_t raster_bytes, bool has_stroke, const BlendForm* blend, const PaintArgs* paint, const ImageArgs* images) {
+                   uint64_t raster_bytes, bool has_stroke, const BlendForm* blend, const PaintArgs* paint, const ImageArgs* images, bool mips) {
     // 8x8-tile blocks, an equal number per XCD (k_raster_tile's tile order)
     constexpr uint32_t kBlock = 1u << CRH_XCD_BLOCK_LOG2;
     const uint32_t blocks = ((r.tiles_x + kBlock - 1u) / kBlock) * ((r.tiles_y + kBlock - 1u) / kBlock);
     const dim3 grid((r.tile_order && r.order_places) ? r.order_places : ((blocks + 7u) / 8u) * kBlock * kBlock * 8u);
     switch (samples) {
-        case 1: launch_raster_s<1>(s, r, stream, grid, has_stroke, blend, paint, images); break;
-        case 2: launch_raster_s<2>(s, r, stream, grid, has_stroke, blend, paint, images); break;
-        case 4: launch_raster_s<4>(s, r, stream, grid, has_stroke, blend, paint, images); break;
-        case 8: launch_raster_s<8>(s, r, stream, grid, has_stroke, blend, paint, images); break;
+        case 1: launch_raster_s<1>(s, r, stream, grid, has_stroke, blend, paint, images, mips); break;
+        case 2: launch_raster_s<2>(s, r, stream, grid, has_stroke, blend, paint, images, mips); break;
+        case 4: launch_raster_s<4>(s, r, stream, grid, has_stroke, blend, paint, images, mips); break;
+        case 8: launch_raster_s<8>(s, r, stream, grid, has_stroke, blend, paint, images, mips); break;
         default: return 0u;
     }
     if (mark) mark(ctx, "raster_tiles", raster_bytes);

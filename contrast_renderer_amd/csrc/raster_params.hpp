@@ -1,6 +1,7 @@
 // csrc/raster_params.hpp — launch parameters of the tile rasterizer, shared by raster.hip and api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #ifndef CRH_XCD_BLOCK_LOG2
@@ -97,14 +98,26 @@ struct PaintTable {
 // In the Scene's association an index below the number of gradients names a gradient, the others image paint (index - n_gradients).
 // k_paint_items writes that index to PaintItem::paint as it is and leaves PaintItem::pad 0; k_paint_items_images, behind it in an image-painted
 // pass, turns the record of an image-painted item into paint = 0, pad = image paint + 1 (pad == 0: the item's paint is a gradient).
+// Mipmaps (crh_image_generate_mipmaps; read by k_raster_mip only): `levels` is the number of levels the image had when the table was built (1: none
+// but the image itself) and `chain` the allocation that holds the levels >= 1, with the level table at its head:
+//   ImageLevel  per level l: the offset of its texels from `chain` in 32-bit words (level 0: not read, its texels are `texels`), its size
+//               (max(1, w >> l), max(1, h >> l)) and sx = (float)w_l / (float)w_0, sy likewise: the scale of texel coordinates from level 0 to l.
+struct ImageLevel {
+    uint32_t offset, width, height;
+    float sx, sy;
+    uint32_t pad[3];
+};
+constexpr uint32_t kMaxImageLevels = 15;                                              // an image is at most 16384 texels wide or high
+constexpr uint32_t kImageLevelTableWords = 128;                                       // the table's place at the head of the chain (15 records of 8 words, rounded up)
+static_assert(sizeof(ImageLevel) == 32 && kMaxImageLevels * sizeof(ImageLevel) <= kImageLevelTableWords * 4, "load_uniform takes 16-byte multiples");
 struct ImagePaintRec {
     const uint32_t* texels;
     uint32_t width, height;
-    uint32_t filter, spread_x, spread_y, pad0;
+    uint32_t filter, spread_x, spread_y, levels;
     float m[6];
-    uint32_t pad1[2];
+    const ImageLevel* chain;
 };
-static_assert(sizeof(ImagePaintRec) == 64, "load_uniform takes 16-byte multiples");
+static_assert(sizeof(ImagePaintRec) == 64 && offsetof(ImagePaintRec, chain) == 56, "load_uniform takes 16-byte multiples");
 struct ImageArgs {
     const ImagePaintRec* paints;
 };

@@ -437,6 +437,28 @@
                         // LINEAR — are fetched together, every address from wrapped indices, and unpacked behind the last load: the loads of divergent
                         // addresses are in flight at once instead of one round trip per sample.
                         const ImagePaintRec im = load_uniform(&ia.paints[pi.pad - 1u]);
+                        if (MIPS && (im.filter & CRH_FILTER_MIPMAP) != 0u && im.levels > 1u) { // wave uniform; the host leaves the flag only on a paint whose image has a chain
+                            // (include/contrast_hip.h crh_image_generate_mipmaps states the model; raster.hip mip_samples is the block.) lod once per painted
+                            // cover for an affine item — this turn is the only one below msaa 8 — and per sample for a projective one.
+                            MipUniform uni = {};
+                            if (pi.affine) uni = mip_uniform(pi, im);
+                            constexpr int kTogether = CRH_IMAGE_FETCH_TOGETHER(S), kLevels = CRH_MIP_LEVELS_TOGETHER(S);
+#pragma unroll
+                            for (int c0 = 0; c0 < 4; c0 += kTogether) {
+                                float fx[kTogether], fy[kTogether], value[kTogether][4];
+#pragma unroll
+                                for (int c = c0; c < c0 + kTogether; ++c) {
+                                    const int b = (g + c) / S, k = (g + c) % S;
+                                    fx[c - c0] = tx0 + sx[k], fy[c - c0] = ty0 + (sy0[k] + (float)(4 * b)); // the sample's place on the frame (exact)
+                                }
+                                if (pi.affine) mip_samples<kTogether, kLevels, true>(pi, im, uni, fx, fy, value);
+                                else mip_samples<kTogether, kLevels, false>(pi, im, uni, fx, fy, value);
+#pragma unroll
+                                for (int c = c0; c < c0 + kTogether; ++c)
+#pragma unroll
+                                    for (int ch = 0; ch < 4; ++ch) pc[c][ch] = value[c - c0][ch];
+                            }
+                        } else {
                         const int iw = (int)im.width, ih = (int)im.height;
                         const bool linear = im.filter == CRH_FILTER_LINEAR;
                         constexpr int kTogether = CRH_IMAGE_FETCH_TOGETHER(S);
@@ -485,6 +507,7 @@
                                 }
                             }
                         }
+                        } // one level
                     } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {

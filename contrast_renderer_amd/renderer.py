@@ -365,14 +365,17 @@ class Frame:
             self.handle = None
 
 
-class Filter(IntEnum):  # CRH_FILTER_*
+class Filter(IntEnum):  # CRH_FILTER_*: the two base filters, and each with CRH_FILTER_MIPMAP (0x100) OR-ed on
     Nearest = 0
     Linear = 1
+    NearestMipmap = 0x100
+    LinearMipmap = 0x101
 
 
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
-    [height, width, 4] uint8 array, copied before the constructor returns. One level, no mipmaps: an image drawn much smaller than its texels aliases."""
+    [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
+    its texels aliases unless it has mipmaps and its paint's filter is Filter.NearestMipmap or Filter.LinearMipmap."""
 
     def __init__(self, renderer: Renderer, pixels):
         pixels = np.asarray(pixels)
@@ -398,6 +401,26 @@ class Image:
         check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
         image.width, image.height = int(w.value), int(h.value)
         return image
+
+    def generate_mipmaps(self):
+        """crh_image_generate_mipmaps: the levels below the image, each the rounded 2 x 2 mean of the one above, built on the device; complete
+        when this returns. A second call changes nothing. A paint table set before the call keeps drawing the one level."""
+        check(self.lib.crh_image_generate_mipmaps(self.handle))
+
+    @property
+    def levels(self):
+        """crh_image_level_count: 1 until generate_mipmaps(), then floor(log2(max(width, height))) + 1."""
+        n = C.c_uint32()
+        check(self.lib.crh_image_level_count(self.handle, C.byref(n)))
+        return int(n.value)
+
+    def download_level(self, level):
+        """crh_image_download_level -> the [height, width, 4] uint8 texels of level `level` (0 = the image itself)."""
+        w, h = C.c_uint32(), C.c_uint32()
+        check(self.lib.crh_image_download_level(self.handle, int(level), None, C.byref(w), C.byref(h)))
+        out = np.empty((int(h.value), int(w.value), 4), dtype=np.uint8)
+        check(self.lib.crh_image_download_level(self.handle, int(level), out.ctypes.data, C.byref(w), C.byref(h)))
+        return out
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

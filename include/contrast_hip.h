@@ -424,7 +424,8 @@ crh_status crh_scene_set_paints(crh_scene* scene, const crh_paint* paints, uint3
  *                is; then clamped and blended exactly as a gradient's source: the renderer's blend state, the frame format's rounding of
  *                writes, the write mask, always the Rgba8Unorm-attachment model.
  *   reads        every texel address is formed from wrapped indices only: no value of (u, v) reads outside the image.
- *   no mipmaps   one level, two filters: an image drawn much smaller than its texels (minified) aliases. Scale the image first.
+ *   minified     one level and these two filters alias when the image is drawn much smaller than its texels: generate mipmaps and OR
+ *                CRH_FILTER_MIPMAP onto the filter (crh_image_generate_mipmaps below).
  * crh_image_create copies width * height * 4 host bytes to the device before it returns; 1 <= width, height <= 16384, else
  * CRH_ERR_INVALID_ARGUMENT. crh_image_create_from_frame settles the frame and copies its resolved bytes on the device: a snapshot — later
  * passes into the frame do not change the image. It takes CRH_FORMAT_RGBA8 and CRH_FORMAT_RGBA8_ATTACHMENT frames that are not restricted by
@@ -438,14 +439,48 @@ crh_status crh_scene_set_paints(crh_scene* scene, const crh_paint* paints, uint3
  * and waits as crh_scene_set_paints does. A pass that draws an image-painted instance through a Color cover runs k_raster_image, the general
  * triangle kernel with the image block; every other pass — a gradient-only table's included — launches what it launched before. */
 typedef struct crh_image crh_image;
-enum { CRH_FILTER_NEAREST = 0, CRH_FILTER_LINEAR = 1 };
+enum { CRH_FILTER_NEAREST = 0, CRH_FILTER_LINEAR = 1, CRH_FILTER_MIPMAP = 0x100 /* OR-ed onto one of the two: the valid words are 0, 1, 0x100, 0x101 */ };
 crh_status crh_image_create(crh_renderer* renderer, uint32_t width, uint32_t height, const void* rgba8, crh_image** out);
 crh_status crh_image_create_from_frame(crh_frame* frame, crh_image** out);
 crh_status crh_image_size(const crh_image* image, uint32_t* width, uint32_t* height);
 void crh_image_destroy(crh_image* image);
+/* Mipmaps: a chain of levels below the image, and a filter flag that blends two of them by the size of a pixel in texels (trilinear minification
+ * with LINEAR), so that a minified image paint — an atlas under a zoomed-out transform, a layer under a tilted camera — no longer aliases.
+ * crh_image_generate_mipmaps builds levels 1 .. L-1 on the device from level 0 (the image), L = floor(log2(max(width, height))) + 1, on the
+ * renderer's stream, and returns when they are complete:
+ *   level l+1    size (max(1, w_l >> 1), max(1, h_l >> 1)); channel c of its texel (i, j) = (a + b + c + d + 2) >> 2 over the codes of level l at
+ *                columns {min(2i, w_l-1), min(2i+1, w_l-1)} x rows {min(2j, h_l-1), min(2j+1, h_l-1)}: integer, bit-exact. Texels are
+ *                premultiplied, so the plain mean is the right one and rgb <= a survives it.
+ * The levels belong to the image's pixels: a paint table keeps them alive as it keeps level 0, for images of crh_image_create and of
+ * crh_image_create_from_frame alike. A second call changes nothing and returns CRH_OK. A paint table holds the levels its images had when it
+ * was set: a table set before the call keeps drawing the one level. crh_image_level_count is 1 until then. crh_image_download_level copies
+ * level `level` (0 = the image) to `rgba8`, width * height * 4 bytes of that level, and reports its size; rgba8 == NULL only reports the size
+ * (width and height may be NULL); level >= the count is CRH_ERR_INVALID_ARGUMENT.
+ * CRH_FILTER_MIPMAP on crh_image_paint::filter, evaluated in f32 on the device and checked against float64 by the tests:
+ *   J            the derivative of (u, v) by the sample's position (sx, sy) on the frame, in texels per pixel. With (X, Y, W) = the rows of the
+ *                inverse path -> pixel homography h applied to (sx, sy, 1) and p = (X, Y) / W: dp.x/dsx = (h0 - p.x h6) / W, dp.x/dsy =
+ *                (h1 - p.x h7) / W, p.y the same with h3, h4 — for an affine instance the constants h0, h1, h3, h4, one J per item — and
+ *                du/ds = m0 dp.x/ds + m1 dp.y/ds, dv/ds = m3 dp.x/ds + m4 dp.y/ds.
+ *   lod          rho = max(|(du/dsx, dv/dsx)|, |(du/dsy, dv/dsy)|); lod = clamp(log2(rho), 0, L - 1), with NaN -> 0 and rho = 0 -> 0 (on the
+ *                device half the hardware log2 of rho^2); l0 = floor(lod), f = lod - l0, l1 = min(l0 + 1, L - 1).
+ *   sampling     at level l the coordinates are u_l = u * sx_l, v_l = v * sy_l with sx_l = (float)w_l / (float)w_0 (one f32 division on the host),
+ *                so that REPEAT and REFLECT periods agree across levels of sizes that are no powers of two; then the base filter's rule
+ *                above (NEAREST or LINEAR, each index wrapped per axis with level l's size), giving s(l).
+ *   value        s(l0) + f (s(l1) - s(l0)) per premultiplied channel; then `source` above: tint, clamp, blend, format.
+ * Hence: an image of one level, and any magnified placement (rho <= 1), give the base filter's bytes exactly (f = 0; the second level is not
+ * even fetched for an affine instance); equal levels give their value back exactly; every address is formed from wrapped indices of its own
+ * level, so no (u, v) reads outside a level. A pass that draws, through a Color cover, an instance whose image paint carries the flag and
+ * whose image had levels when the table was set runs k_raster_mip; every other pass launches what it launched before.
+ * Limits: a level of odd width or height drops its last column or row in the step below it (the 2 x 2 blocks cover 2 (w >> 1) columns), so
+ * content there fades from the lower levels and sizes that are no powers of two shift by up to a texel per level; the footprint is isotropic
+ * (the longer axis of J picks the level: a strongly anisotropic placement blurs along its short axis); levels are not gamma corrected (the
+ * codes are averaged as they are, linear light as the frame's bytes are). */
+crh_status crh_image_generate_mipmaps(crh_image* image);
+crh_status crh_image_level_count(const crh_image* image, uint32_t* count);
+crh_status crh_image_download_level(const crh_image* image, uint32_t level, void* rgba8, uint32_t* width, uint32_t* height);
 typedef struct crh_image_paint {
     const crh_image* image;
-    uint32_t filter;             /* CRH_FILTER_* */
+    uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */
     uint32_t spread_x, spread_y; /* crh_spread, per axis */
     float m[6];                  /* path -> texel: u = m0 x + m1 y + m2, v = m3 x + m4 y + m5 */
 } crh_image_paint;

@@ -593,8 +593,9 @@ class Paint {
 };
 
 // Image paints: the texels of an Image as the source of a Color cover (include/contrast_hip.h crh_scene_set_paints_with_images states the model)
-enum class Filter : uint32_t { Nearest = CRH_FILTER_NEAREST, Linear = CRH_FILTER_LINEAR };
-// crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level, no mipmaps.
+enum class Filter : uint32_t { Nearest = CRH_FILTER_NEAREST, Linear = CRH_FILTER_LINEAR, NearestMipmap = CRH_FILTER_NEAREST | CRH_FILTER_MIPMAP, LinearMipmap = CRH_FILTER_LINEAR | CRH_FILTER_MIPMAP };
+// crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
+// generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
 class Image {
   public:
@@ -615,6 +616,23 @@ class Image {
     uint32_t width() const { return width_; }
     uint32_t height() const { return height_; }
     const crh_image* raw() const { return handle_; }
+    // the levels below the image, built on the device; a second call changes nothing, and a table set before the call keeps its one level
+    void generate_mipmaps() { check(crh_image_generate_mipmaps(handle_)); }
+    uint32_t levels() const {
+        uint32_t n = 0;
+        check(crh_image_level_count(handle_, &n));
+        return n;
+    }
+    // -> the texels of level `level` (0 = the image), width * height * 4 bytes of that level's size
+    std::vector<uint8_t> download_level(uint32_t level, uint32_t* width = nullptr, uint32_t* height = nullptr) const {
+        uint32_t w = 0, h = 0;
+        check(crh_image_download_level(handle_, level, nullptr, &w, &h));
+        std::vector<uint8_t> out((size_t)w * h * 4);
+        check(crh_image_download_level(handle_, level, out.data(), &w, &h));
+        if (width) *width = w;
+        if (height) *height = h;
+        return out;
+    }
 
   private:
     Image() = default;

@@ -733,9 +733,13 @@ impl Scene {
 pub enum Filter {
     Nearest = 0,
     Linear = 1,
+    /// `CRH_FILTER_NEAREST | CRH_FILTER_MIPMAP`: the nearest texel of two levels, blended by the level of detail
+    NearestMipmap = 0x100,
+    /// `CRH_FILTER_LINEAR | CRH_FILTER_MIPMAP`: trilinear
+    LinearMipmap = 0x101,
 }
-/// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level, no
-/// mipmaps. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels.
+/// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
+/// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
     raw: *mut ffi::crh_image,
     width: u32,
@@ -759,6 +763,25 @@ impl Image {
     }
     pub fn size(&self) -> (u32, u32) {
         (self.width, self.height)
+    }
+    /// `crh_image_generate_mipmaps`: the levels below the image, built on the device. A second call changes nothing; a paint table set before
+    /// the call keeps drawing the one level.
+    pub fn generate_mipmaps(&mut self) -> Result<(), Error> {
+        status(unsafe { ffi::crh_image_generate_mipmaps(self.raw) })
+    }
+    /// 1 until `generate_mipmaps`, then floor(log2(max(width, height))) + 1
+    pub fn levels(&self) -> Result<u32, Error> {
+        let mut n = 0u32;
+        status(unsafe { ffi::crh_image_level_count(self.raw, &mut n) })?;
+        Ok(n)
+    }
+    /// -> (width, height, texels) of level `level` (0 = the image itself)
+    pub fn download_level(&self, level: u32) -> Result<(u32, u32, Vec<u8>), Error> {
+        let (mut width, mut height) = (0u32, 0u32);
+        status(unsafe { ffi::crh_image_download_level(self.raw, level, ptr::null_mut(), &mut width, &mut height) })?;
+        let mut out = vec![0u8; width as usize * height as usize * 4];
+        status(unsafe { ffi::crh_image_download_level(self.raw, level, out.as_mut_ptr() as *mut _, &mut width, &mut height) })?;
+        Ok((width, height, out))
     }
 }
 impl Drop for Image {
