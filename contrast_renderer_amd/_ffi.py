@@ -301,6 +301,8 @@ def load_library():
         "crh_image_generate_mipmaps": (C.c_int, [V]),
         "crh_image_level_count": (C.c_int, [V, C.POINTER(C.c_uint32)]),
         "crh_image_download_level": (C.c_int, [V, C.c_uint32, V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "crh_blur_taps": (C.c_int, [C.c_float, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+        "crh_image_blur": (C.c_int, [V, C.c_float, C.c_float, C.c_uint32, C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

@@ -2894,6 +2894,106 @@ crh_status crh_image_download_level(const crh_image* image, uint32_t level, void
     HIP_TRY(r->sync());
     return CRH_OK;
 }
+namespace {
+static_assert(CRH_MAX_BLUR_RADIUS == kBlurMaxRadius, "k_image_blur_h's apron is the largest radius");
+crh_status blur_error(const char* what) {
+    g_error = std::string("crh_blur_taps: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+// The tap rule of include/contrast_hip.h (crh_image_blur), in double: q[0 .. R] of one axis, summing to exactly 65536 over the 2 R + 1 positions.
+crh_status blur_taps(float sigma, std::vector<uint32_t>& q) {
+    if (!std::isfinite(sigma)) return CRH_ERR_NON_FINITE;
+    if (sigma < 0.0f) return blur_error("sigma is negative");
+    if (sigma > CRH_MAX_BLUR_SIGMA) return blur_error("sigma exceeds CRH_MAX_BLUR_SIGMA");
+    const double s = (double)sigma;
+    const uint32_t R = (uint32_t)std::ceil(3.0 * s);
+    q.assign(R + 1u, 0u);
+    if (R == 0u) {
+        q[0] = 65536u;
+        return CRH_OK;
+    }
+    std::vector<double> w(R + 1u);
+    for (uint32_t k = 0; k <= R; ++k) w[k] = std::exp(-(double)(k * k) / (2.0 * s * s));
+    double S = w[0];
+    for (uint32_t k = 1; k <= R; ++k) S += 2.0 * w[k];
+    int64_t total = 0;
+    for (uint32_t k = 0; k <= R; ++k) {
+        q[k] = (uint32_t)std::floor(w[k] / S * 65536.0 + 0.5);
+        total += k == 0u ? (int64_t)q[k] : 2 * (int64_t)q[k];
+    }
+    // the rounding's deficit d goes to the taps next to the centre in pairs, its odd unit to the centre (|d| / 2 <= R: |d| <= 27 over (0, 64])
+    const int64_t d = 65536 - total, g = d < 0 ? -1 : 1, m = std::min<int64_t>((d < 0 ? -d : d) / 2, (int64_t)R);
+    for (int64_t k = 1; k <= m; ++k) q[k] = (uint32_t)((int64_t)q[k] + g);
+    q[0] = (uint32_t)((int64_t)q[0] + d - 2 * g * m);
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_blur_taps(float sigma, uint32_t* taps, uint32_t capacity, uint32_t* radius) {
+    std::vector<uint32_t> q;
+    const crh_status st = blur_taps(sigma, q);
+    if (st != CRH_OK) return st;
+    if (taps) {
+        if (capacity < (uint32_t)q.size()) return blur_error("capacity is below radius + 1");
+        std::copy(q.begin(), q.end(), taps);
+    }
+    if (radius) *radius = (uint32_t)q.size() - 1u;
+    return CRH_OK;
+}
+crh_status crh_image_blur(const crh_image* src, float sigma_x, float sigma_y, uint32_t edge, crh_image** out) {
+    if (!src || !src->renderer || !out || edge > CRH_BLUR_EDGE_REFLECT) return CRH_ERR_INVALID_ARGUMENT;
+    std::vector<uint32_t> qx, qy;
+    crh_status st = blur_taps(sigma_x, qx);
+    if (st == CRH_OK) st = blur_taps(sigma_y, qy);
+    if (st != CRH_OK) return st;
+    const uint32_t rx = (uint32_t)qx.size() - 1u, ry = (uint32_t)qy.size() - 1u;
+    const bool grows = edge == CRH_BLUR_EDGE_TRANSPARENT;
+    const uint32_t out_w = src->width + (grows ? 2u * rx : 0u), out_h = src->height + (grows ? 2u * ry : 0u);
+    if (out_w > kMaxImageSize || out_h > kMaxImageSize) {
+        g_error = "crh_image_blur: a side of the grown result exceeds 16384";
+        return CRH_ERR_UNSUPPORTED;
+    }
+    // The kernels take 16-bit taps two to a word (v_dot2_u32_u16). Only q[0] = 65536 does not fit, and then every other tap is 0: that axis is the
+    // identity, which the kernels do with radius 0 (the result still grows by the axis's radius under TRANSPARENT).
+    const uint32_t kx = qx[0] == 65536u ? 0u : rx, ky = qy[0] == 65536u ? 0u : ry;
+    // one upload, at the head of the intermediate's allocation: [q_x[0] | q_x[2 p + 1] | q_x[2 p + 2] << 16 ...] for k_image_blur_h, then, unless
+    // the vertical axis is the identity, F[n] | F[n - 1] << 16 over F = q_y[|d|], d = -ky .. ky, between kBlurTapPad zeros on either side
+    std::vector<uint32_t> words(1u + (kx + 1u) / 2u, 0u);
+    words[0] = qx[0];
+    for (uint32_t k = 1; k <= kx; ++k) words[(k + 1u) / 2u] |= qx[k] << (k % 2u ? 0 : 16);
+    const size_t vertical = words.size();
+    if (qy[0] != 65536u) {
+        std::vector<uint32_t> F(2u * ky + 1u + 2u * kBlurTapPad, 0u);
+        for (uint32_t k = 0; k <= ky; ++k) F[kBlurTapPad + ky - k] = F[kBlurTapPad + ky + k] = qy[k];
+        for (size_t n = 0; n < F.size(); ++n) words.push_back(F[n] | (n ? F[n - 1] << 16 : 0u));
+    }
+    const size_t taps_bytes = (words.size() * 4 + 255) / 256 * 256; // (the intermediate behind them stays 256-byte aligned)
+    crh_renderer* r = src->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    st = new_image(r, out_w, out_h, &image);
+    if (st != CRH_OK) return st;
+    void* scratch = nullptr; // [the taps | the intermediate: four 16-bit values per texel, the source's rows at the result's width]
+    bool ok = hip_ok(hipMalloc(&scratch, taps_bytes + (size_t)out_w * src->height * 8), "hipMalloc(blur intermediate)") &&
+              hip_ok(hipMemcpyAsync(scratch, words.data(), words.size() * 4, hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(blur taps)");
+    const uint32_t* taps_dev = static_cast<const uint32_t*>(scratch);
+    void* tmp = static_cast<char*>(scratch) + taps_bytes;
+    if (ok) {
+        launch_image_blur_h(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, tmp, out_w, taps_dev, kx, grows ? rx : 0u, edge, r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_blur_h");
+    }
+    if (ok) {
+        launch_image_blur_v(tmp, src->height, static_cast<uint32_t*>(image->pixels->p), out_w, out_h, qy[0] != 65536u ? taps_dev + vertical : nullptr, ky, grows ? ry : 0u, edge, r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_blur_v");
+    }
+    ok = hip_ok(r->sync(), "sync(blur)") && ok; // (also behind a failure: `words` is read by the copy until the stream has drained)
+    if (scratch) (void)hipFree(scratch);
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
 void crh_image_destroy(crh_image* image) { delete image; } // (the pixels and their mipmaps stay while a Scene's paint table names them)
 crh_status crh_frame_download_f16(crh_frame* f, void* rgba16f) { return download_pixels(f, rgba16f, CRH_FORMAT_RGBA16F); }
 extern "C" crh_status crh_debug_frame_counters(crh_frame* f, uint32_t out[8]) { // tools only (not in the public header)

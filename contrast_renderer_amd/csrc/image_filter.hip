@@ -1,0 +1,166 @@
+// csrc/image_filter.hip — crh_image_blur: a separable Gaussian blur of a premultiplied RGBA8 image as two kernels, integer and bit-exact
+// (include/contrast_hip.h states the model). k_image_blur_h filters rows of the source into an intermediate of four 16-bit values per
+// texel; k_image_blur_v filters the columns of that into packed RGBA8. Nothing here touches a raster kernel: the wrap helper is this file's own.
+#include <hip/hip_runtime.h>
+
+#include "launch.hpp"
+
+namespace crh {
+namespace {
+
+constexpr int kBlurSegment = 256; // horizontal: output texels of one row per workgroup, one per lane
+constexpr int kBlurApron = 192;   // CRH_MAX_BLUR_RADIUS: texels staged beyond the segment on either side
+constexpr int kBlurColumns = 64;  // vertical: columns per workgroup, one per lane of a wave
+constexpr int kBlurWaves = 4;     // vertical: waves per workgroup
+constexpr int kBlurRows = 8;      // vertical: output rows per lane
+constexpr int kBlurBlockRows = kBlurWaves * kBlurRows; // vertical: output rows per workgroup
+constexpr int kBlurChunk = 32;    // vertical: intermediate rows staged in LDS at a time
+static_assert(kBlurRows == (int)kBlurTapPad, "a row pair may start one row early: the vertical table holds kBlurTapPad = rows per lane zeros on either side");
+static_assert(kBlurApron == (int)kBlurMaxRadius, "the apron holds the largest radius");
+
+// The image-paint block's wrap(i, n) for edges 1..3 (PAD, REPEAT, REFLECT), any int32 i, 1 <= n <= 16384: -> [0, n).
+// |i| may be many times n (a radius of 192 on a one-texel axis), so REPEAT and REFLECT reduce with a remainder, not a single fold.
+__device__ __forceinline__ int blur_wrap(int i, int n, uint32_t edge) {
+    if ((uint32_t)i < (uint32_t)n) return i; // (inside: every edge agrees)
+    if (edge == 1u) return i < 0 ? 0 : n - 1;
+    const int p = edge == 2u ? n : 2 * n;
+    int k = i % p;
+    if (k < 0) k += p;
+    return k < n ? k : p - 1 - k;
+}
+
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+// (lo.u16[0], hi.u16[0]) and (lo.u16[1], hi.u16[1]) of two words: one v_perm_b32 each
+__device__ __forceinline__ uint32_t low_halves(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x05040100u); }
+__device__ __forceinline__ uint32_t high_halves(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
+// acc + v.u16[0] * q.u16[0] + v.u16[1] * q.u16[1] in 32 bits (v_dot2_u32_u16): two taps of one channel per instruction
+__device__ __forceinline__ uint32_t dot2(uint32_t v, uint32_t q, uint32_t acc) { return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, v), __builtin_bit_cast(u16x2, q), acc, false); }
+
+} // namespace
+
+// Horizontal pass. Grid (ceil(out_w / 256), src_h), 256 lanes: the workgroup stages the texels its segment of one row reads — the segment and
+// an apron of radius + 1 on either side, wrapped or zero by the edge — in LDS, each texel unpacked to two words of two 16-bit fields
+// (r | b << 16, g | a << 16); then every lane forms its own output from LDS. Lane l reads the 8 bytes at l + const: consecutive lanes,
+// consecutive banks. The taps are read with a wave-uniform index, so they come through the scalar cache into SGPRs: taps[0] = q[0] as a
+// 32-bit word (65536 when the axis is the identity), taps[1 + p] = q[2 p + 1] | q[2 p + 2] << 16, a pair of 16-bit taps (q[radius + 1] = 0
+// pads an odd radius: hence the apron's extra texel). The sum runs over tap PAIRS, q[k] (c(i - k) + c(i + k)): the two texels are added in
+// their 16-bit fields (<= 510), the sums of taps k and k + 1 are regrouped by channel (v_perm_b32) and each channel takes both taps in one
+// v_dot2_u32_u16: 12 vector instructions and four 8-byte LDS reads for 16 multiply-adds.
+//   t = (sum_k q[|k|] c(i + k) + 128) >> 8 per channel, <= 65280; four of them are one 8-byte store.
+// `origin`: the source column under output column 0 is -origin (the axis's radius for TRANSPARENT, else 0). `radius` is 0 when q[0] = 65536.
+__global__ __launch_bounds__(kBlurSegment) void k_image_blur_h(const uint32_t* __restrict__ src, uint32_t src_w, uint2* __restrict__ tmp, uint32_t out_w, const uint32_t* __restrict__ taps,
+                                                                uint32_t radius, uint32_t origin, uint32_t edge) {
+    __shared__ uint2 row[kBlurSegment + 2 * (kBlurApron + 1)];
+    const uint32_t j = blockIdx.y, o0 = blockIdx.x * (uint32_t)kBlurSegment, lane = threadIdx.x;
+    const uint32_t* line = src + (size_t)j * src_w;
+    const uint32_t apron = radius + 1u; // (radius <= kBlurApron: the host refuses more)
+    const int first = (int)o0 - (int)origin - (int)apron; // the source column of row[0]
+    for (uint32_t at = lane; at < (uint32_t)kBlurSegment + 2u * apron; at += (uint32_t)kBlurSegment) {
+        const int i = first + (int)at;
+        uint32_t texel = 0u;
+        if (edge != 0u) texel = line[blur_wrap(i, (int)src_w, edge)];
+        else if ((uint32_t)i < src_w) texel = line[i];
+        row[at] = make_uint2(texel & 0x00FF00FFu, (texel >> 8) & 0x00FF00FFu);
+    }
+    __syncthreads();
+    const uint32_t o = o0 + lane;
+    if (o >= out_w) return;
+    const uint32_t centre = lane + apron;
+    const uint2 c = row[centre];
+    const uint32_t q0 = taps[0];
+    uint32_t r = __umul24(q0, c.x & 0xFFFFu), b = __umul24(q0, c.x >> 16), g = __umul24(q0, c.y & 0xFFFFu), a = __umul24(q0, c.y >> 16);
+    for (uint32_t k = 1; k <= radius; k += 2) {
+        const uint32_t q = taps[(k + 1u) >> 1];
+        const uint2 l0 = row[centre - k], h0 = row[centre + k], l1 = row[centre - k - 1u], h1 = row[centre + k + 1u];
+        const uint32_t rb0 = l0.x + h0.x, ga0 = l0.y + h0.y, rb1 = l1.x + h1.x, ga1 = l1.y + h1.y; // sums <= 510 in 16-bit fields
+        r = dot2(low_halves(rb0, rb1), q, r), b = dot2(high_halves(rb0, rb1), q, b);
+        g = dot2(low_halves(ga0, ga1), q, g), a = dot2(high_halves(ga0, ga1), q, a);
+    }
+    r = (r + 128u) >> 8, g = (g + 128u) >> 8, b = (b + 128u) >> 8, a = (a + 128u) >> 8;
+    tmp[(size_t)j * out_w + o] = make_uint2(r | (g << 16), b | (a << 16));
+}
+
+// Vertical pass. Grid (ceil(out_w / 64), ceil(out_h / 32)), 4 waves: lanes run along x, so every global and LDS access of a wave is 64
+// consecutive 4- or 8-byte words. The workgroup covers 32 output rows of 64 columns; wave w owns rows 8 w .. 8 w + 7 of them, eight rows per
+// lane in 32 accumulators. The 32 + 2 radius intermediate rows the block reads are staged once, 32 rows (16 KiB) at a time. The staged rows
+// are taken in PAIRS (i, i + 1): a lane reads its 8 bytes of each once, regroups the two rows by channel (four v_perm_b32) and adds the pair
+// to each of its eight rows with one v_dot2_u32_u16 per channel — 36 vector instructions for 64 multiply-adds. `pairs` is the table
+// F[n] | F[n - 1] << 16 of 16-bit taps, F = the symmetric q[|d|], d = -radius .. radius, between 8 zeros on either side: row i meets output
+// row m with F[8 + 2 radius - (i - lo) + m] and row i + 1 with the word before, so the eight tap pairs of a row pair are eight consecutive
+// words at a wave-uniform index — one scalar load, no branch — and a row outside an output's window meets a zero.
+//   out = (sum_k q[|k|] t(i, j + k) + 2^23) >> 24 per channel; the sum is < 2^32 (65280 * 65536).
+// `origin`: the intermediate row under output row 0 is -origin (the axis's radius for TRANSPARENT, else 0); tmp has tmp_h rows of out_w
+// texels. radius = 0 with pairs = nullptr stands for q[0] = 65536 (the identity on this axis, which no 16-bit tap holds): out = (t + 128) >> 8.
+__global__ __launch_bounds__(kBlurColumns * kBlurWaves) void k_image_blur_v(const uint2* __restrict__ tmp, uint32_t tmp_h, uint32_t* __restrict__ out, uint32_t out_w, uint32_t out_h,
+                                                                            const uint32_t* __restrict__ pairs, uint32_t radius, uint32_t origin, uint32_t edge) {
+    __shared__ uint2 rows[kBlurChunk][kBlurColumns];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t x = blockIdx.x * (uint32_t)kBlurColumns + lane;
+    const int block_j0 = (int)(blockIdx.y * (uint32_t)kBlurBlockRows);
+    const int j0 = block_j0 + (int)(wave * (uint32_t)kBlurRows); // this wave's first output row
+    if (pairs == nullptr) { // the identity: a texel of the intermediate, rounded
+        if (x >= out_w) return;
+        for (int m = 0; m < kBlurRows && j0 + m < (int)out_h; ++m) {
+            const int i = j0 + m - (int)origin;
+            uint2 t = make_uint2(0u, 0u);
+            if (edge != 0u) t = tmp[(size_t)blur_wrap(i, (int)tmp_h, edge) * out_w + x];
+            else if ((uint32_t)i < tmp_h) t = tmp[(size_t)i * out_w + x];
+            out[(size_t)(j0 + m) * out_w + x] = (((t.x & 0xFFFFu) + 128u) >> 8) | ((((t.x >> 16) + 128u) >> 8) << 8) | ((((t.y & 0xFFFFu) + 128u) >> 8) << 16) | ((((t.y >> 16) + 128u) >> 8) << 24);
+        }
+        return;
+    }
+    const int R = (int)radius;
+    // intermediate rows, as source rows (output row j is centred on j - origin): the block reads [block_lo, block_hi], this wave [lo, hi]
+    const int last_row = min(block_j0 + kBlurBlockRows, (int)out_h) - 1;
+    const int block_lo = block_j0 - (int)origin - R, block_hi = last_row - (int)origin + R;
+    const int lo = j0 - (int)origin - R, hi = j0 + kBlurRows - 1 - (int)origin + R;
+    uint32_t acc[kBlurRows][4];
+#pragma unroll
+    for (int m = 0; m < kBlurRows; ++m) acc[m][0] = acc[m][1] = acc[m][2] = acc[m][3] = 0u;
+    for (int chunk = block_lo; chunk <= block_hi; chunk += kBlurChunk) {
+        __syncthreads(); // (the rows of the chunk before have been read)
+        for (int s = (int)wave; s < kBlurChunk; s += kBlurWaves) { // every row of the chunk is written: zeros beyond block_hi
+            const int i = chunk + s;
+            uint2 t = make_uint2(0u, 0u);
+            if (x < out_w && i <= block_hi) {
+                if (edge != 0u) t = tmp[(size_t)blur_wrap(i, (int)tmp_h, edge) * out_w + x];
+                else if ((uint32_t)i < tmp_h) t = tmp[(size_t)i * out_w + x];
+            }
+            rows[s][lane] = t;
+        }
+        __syncthreads();
+        // this wave's rows of the chunk, [from, to], in pairs that start on an even row of the chunk (16 pairs: none leaves it). The pair's
+        // first row may be lo - 1 and its second hi + 1: both meet zeros of the table (F's indices run from 0 to 2 R + 16).
+        const int from = max(chunk, lo), to = min(min(chunk + kBlurChunk - 1, block_hi), hi); // wave-uniform
+        for (int i = chunk + ((from - chunk) & ~1); i <= to; i += 2) {
+            const uint2 t0 = rows[i - chunk][lane], t1 = rows[i + 1 - chunk][lane];
+            const uint32_t rr = low_halves(t0.x, t1.x), gg = high_halves(t0.x, t1.x), bb = low_halves(t0.y, t1.y), aa = high_halves(t0.y, t1.y);
+            const uint32_t* q = pairs + (uint32_t)((int)kBlurTapPad + 2 * R - (i - lo)); // ascending in m
+#pragma unroll
+            for (int m = 0; m < kBlurRows; ++m) {
+                const uint32_t qm = q[m];
+                acc[m][0] = dot2(rr, qm, acc[m][0]), acc[m][1] = dot2(gg, qm, acc[m][1]), acc[m][2] = dot2(bb, qm, acc[m][2]), acc[m][3] = dot2(aa, qm, acc[m][3]);
+            }
+        }
+    }
+    if (x >= out_w) return;
+#pragma unroll
+    for (int m = 0; m < kBlurRows; ++m) {
+        const int j = j0 + m;
+        if (j >= (int)out_h) break;
+        const uint32_t half = 1u << 23;
+        out[(size_t)j * out_w + x] = ((acc[m][0] + half) >> 24) | (((acc[m][1] + half) >> 24) << 8) | (((acc[m][2] + half) >> 24) << 16) | (((acc[m][3] + half) >> 24) << 24);
+    }
+}
+
+void launch_image_blur_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, void* tmp, uint32_t out_w, const uint32_t* taps, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream) {
+    const dim3 grid((out_w + (uint32_t)kBlurSegment - 1u) / (uint32_t)kBlurSegment, src_h); // from the output: src_h <= 16384 rows of the intermediate
+    hipLaunchKernelGGL(k_image_blur_h, grid, dim3(kBlurSegment), 0, stream, src, src_w, static_cast<uint2*>(tmp), out_w, taps, radius, origin, edge);
+}
+
+void launch_image_blur_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* pairs, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream) {
+    const dim3 grid((out_w + (uint32_t)kBlurColumns - 1u) / (uint32_t)kBlurColumns, (out_h + (uint32_t)kBlurBlockRows - 1u) / (uint32_t)kBlurBlockRows);
+    hipLaunchKernelGGL(k_image_blur_v, grid, dim3(kBlurColumns * kBlurWaves), 0, stream, static_cast<const uint2*>(tmp), tmp_h, out, out_w, out_h, pairs, radius, origin, edge);
+}
+
+} // namespace crh

@@ -1,4 +1,4 @@
-// csrc/launch.hpp — the interface between the translation units: what api.hip calls in tessellate.hip, raster.hip, bin_edges.hip and raster_edges.hip, and
+// csrc/launch.hpp — the interface between the translation units: what api.hip calls in tessellate.hip, raster.hip, image_filter.hip, bin_edges.hip and raster_edges.hip, and
 // what those call in each other. Included by the callers AND by every file that defines one of these, so that the compiler checks each
 // definition against its declaration.
 #pragma once
@@ -35,6 +35,13 @@ void launch_scan_tiles(const RasterParams& r, hipStream_t stream); // exclusive 
 void launch_state_colors_from_image(const RasterParams& r, uint32_t samples, hipStream_t stream);
 void launch_selftest_srgb(const float* x, uint8_t* codes, uint64_t n, float* decoded, hipStream_t stream);
 void launch_composite(const uint8_t* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, uint8_t* dst, hipStream_t stream);
+
+// image_filter.hip: crh_image_blur's two passes (the kernels' comments state the two tap tables). `tmp` = four 16-bit values per texel, src_h rows
+// of out_w; origin = the axis's radius for CRH_BLUR_EDGE_TRANSPARENT (the result grows), else 0; radius = 0 for an axis whose q[0] is 65536.
+constexpr uint32_t kBlurMaxRadius = 192; // CRH_MAX_BLUR_RADIUS
+constexpr uint32_t kBlurTapPad = 8;      // zero taps on either side of k_image_blur_v's table: the output rows a lane accumulates
+void launch_image_blur_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, void* tmp, uint32_t out_w, const uint32_t* taps, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream);
+void launch_image_blur_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* pairs, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream); // pairs == nullptr: the identity
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);

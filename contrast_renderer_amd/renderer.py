@@ -372,10 +372,34 @@ class Filter(IntEnum):  # CRH_FILTER_*: the two base filters, and each with CRH_
     LinearMipmap = 0x101
 
 
+class BlurEdge(IntEnum):  # crh_blur_edge: what a blur reads outside the image
+    Transparent = 0  # (0, 0, 0, 0); the result grows by the radius on every side
+    Pad = 1
+    Repeat = 2
+    Reflect = 3
+
+
+MAX_BLUR_SIGMA = 64.0   # CRH_MAX_BLUR_SIGMA
+MAX_BLUR_RADIUS = 192   # CRH_MAX_BLUR_RADIUS
+
+
+def blur_taps(sigma):
+    """crh_blur_taps (host only) -> (taps, radius): the integer taps q[0 .. radius] of one axis of Image.blur as a uint32 array, radius =
+    ceil(3 sigma); symmetric about q[0], summing to exactly 65536 over the 2 radius + 1 positions (include/contrast_hip.h crh_image_blur)."""
+    lib = _ffi.load_library()
+    taps = np.zeros(MAX_BLUR_RADIUS + 1, dtype=np.uint32)
+    radius = C.c_uint32()
+    check(lib.crh_blur_taps(float(sigma), taps.ctypes.data_as(C.POINTER(C.c_uint32)), len(taps), C.byref(radius)))
+    return taps[:int(radius.value) + 1].copy(), int(radius.value)
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
-    its texels aliases unless it has mipmaps and its paint's filter is Filter.NearestMipmap or Filter.LinearMipmap."""
+    its texels aliases unless it has mipmaps and its paint's filter is Filter.NearestMipmap or Filter.LinearMipmap. `origin` = the texel of this
+    image that lies over texel (0, 0) of the image it was blurred from: (0, 0) unless blur() grew it."""
+
+    origin = (0, 0)
 
     def __init__(self, renderer: Renderer, pixels):
         pixels = np.asarray(pixels)
@@ -421,6 +445,25 @@ class Image:
         out = np.empty((int(h.value), int(w.value), 4), dtype=np.uint8)
         check(self.lib.crh_image_download_level(self.handle, int(level), out.ctypes.data, C.byref(w), C.byref(h)))
         return out
+
+    def blur(self, sigma_x, sigma_y=None, edge=BlurEdge.Transparent):
+        """crh_image_blur -> a new Image of one level: the separable Gaussian of this image's level 0, integer and bit-exact, built on the
+        device and complete when this returns (a synchronous call: one wait per blur). sigma_y=None means sigma_x; both in [0,
+        MAX_BLUR_SIGMA]. BlurEdge.Transparent grows the result by the radius ceil(3 sigma) on every side, and the result's `origin` is
+        (Rx, Ry); the other edges keep the size. This image is not modified."""
+        sigma_x = float(sigma_x)
+        sigma_y = sigma_x if sigma_y is None else float(sigma_y)
+        image = Image.__new__(Image)
+        image.renderer, image.lib = self.renderer, self.lib
+        handle = C.c_void_p()
+        check(self.lib.crh_image_blur(self.handle, sigma_x, sigma_y, int(edge), C.byref(handle)))
+        image.handle = handle
+        w, h = C.c_uint32(), C.c_uint32()
+        check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
+        image.width, image.height = int(w.value), int(h.value)
+        if int(edge) == BlurEdge.Transparent:
+            image.origin = ((image.width - self.width) // 2, (image.height - self.height) // 2)
+        return image
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

@@ -478,6 +478,45 @@ void crh_image_destroy(crh_image* image);
 crh_status crh_image_generate_mipmaps(crh_image* image);
 crh_status crh_image_level_count(const crh_image* image, uint32_t* count);
 crh_status crh_image_download_level(const crh_image* image, uint32_t level, void* rgba8, uint32_t* width, uint32_t* height);
+/* Blur: a separable Gaussian of an image on the device — the soft layer behind a drop shadow, a glow, a soft mask, a blurred backdrop. A
+ * blurred snapshot of a frame (crh_image_create_from_frame) drawn as an image paint with the tint (0, 0, 0, a) is a drop shadow: the tint rule
+ * of `source` above needs nothing more. The model is integer and bit-exact; the tests check every byte against it.
+ *   taps         one axis, from the f32 sigma widened to double s: R = (uint32_t)ceil(3.0 * s); w[k] = exp(-(k*k) / (2 s s)), k = 0 .. R;
+ *                S = w[0] + 2 w[1] + ... + 2 w[R], summed in that order; q[k] = floor(w[k] / S * 65536 + 0.5); then the rounding's deficit
+ *                d = 65536 - (q[0] + 2 sum_{k>=1} q[k]), g = sign(d), m = |d| / 2 (integer division): q[1 .. m] += g, q[0] += d - 2 g m.
+ *                Symmetric, non-negative, exactly 65536 over the 2 R + 1 positions; every tap within 1.5 of w[k] / S * 65536 (|d| <= 27 over
+ *                (0, 64]). s == 0: R = 0 and the single tap 65536, the identity on that axis.
+ *   edge         PAD, REPEAT, REFLECT keep the size (w, h): a tap at source index i reads wrap(i, n) by exactly the rules of the image-paint
+ *                block above, |i| any multiple of n beyond it (R = 192 on a 1-texel axis). TRANSPARENT takes texels outside the source as
+ *                (0, 0, 0, 0) and grows the result to (w + 2 Rx, h + 2 Ry): its texel (i, j) is centred on source texel (i - Rx, j - Ry), so
+ *                nothing of a shadow is cut off. A grown side above 16384 is CRH_ERR_UNSUPPORTED.
+ *   horizontal   per channel on the 8-bit codes c: t(i, j) = (sum_k qx[|k|] c(i + k, j) + 128) >> 8, k = -Rx .. Rx: a 16-bit value <= 65280
+ *                (the sum is <= 255 * 65536 < 2^24).
+ *   vertical     out(i, j) = (sum_k qy[|k|] t(i, j + k) + 2^23) >> 24, k = -Ry .. Ry (the sum is <= 65280 * 65536 < 2^32: unsigned 32 bits).
+ * Texels are premultiplied, so the plain weighted mean is the right one. Hence: a constant image comes back exactly under the three same-size
+ * edges, and on a texel whose window lies wholly inside the source under TRANSPARENT; rgb <= a survives (both roundings are monotone); sigma 0
+ * on both axes is a copy. The codes are averaged as they are, with no gamma handling, as the mip levels are.
+ * crh_blur_taps is host only (no renderer, no device): it writes q[0 .. R] to `taps` and R to *radius; taps == NULL only reports the radius;
+ * capacity < R + 1 with taps is CRH_ERR_INVALID_ARGUMENT; a non-finite sigma CRH_ERR_NON_FINITE; sigma < 0 or > CRH_MAX_BLUR_SIGMA
+ * CRH_ERR_INVALID_ARGUMENT with a crh_last_error text. crh_image_blur validates both sigmas through it before it touches the device.
+ * crh_image_blur gives a fresh image of the source's renderer with one level (crh_image_generate_mipmaps works on it). The source is not
+ * modified and only its level 0 is read. The call runs k_image_blur_h and k_image_blur_v on the renderer's stream and returns when the result
+ * is complete, as crh_image_generate_mipmaps does; the intermediate (8 bytes per texel of the result's width and the source's height) is freed
+ * before it returns. A null argument or an edge above 3 is CRH_ERR_INVALID_ARGUMENT; a failed allocation or launch frees everything and returns
+ * CRH_ERR_HIP; a refused call leaves *out untouched.
+ * Limits: the call is synchronous — a caller that blurs every frame waits once per blur; no in-place variant; radii end at
+ * CRH_MAX_BLUR_RADIUS; a true Gaussian, no box or recursive approximation, so the cost grows with sigma; a frame is blurred through a
+ * snapshot only; no per-pass backdrop filter. */
+#define CRH_MAX_BLUR_SIGMA 64.0f
+#define CRH_MAX_BLUR_RADIUS 192u
+typedef enum crh_blur_edge {
+    CRH_BLUR_EDGE_TRANSPARENT = 0,
+    CRH_BLUR_EDGE_PAD = 1,
+    CRH_BLUR_EDGE_REPEAT = 2,
+    CRH_BLUR_EDGE_REFLECT = 3
+} crh_blur_edge;
+crh_status crh_blur_taps(float sigma, uint32_t* taps, uint32_t capacity, uint32_t* radius); /* host only: no renderer, no device */
+crh_status crh_image_blur(const crh_image* src, float sigma_x, float sigma_y, uint32_t edge, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

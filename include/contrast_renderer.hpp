@@ -594,6 +594,17 @@ class Paint {
 
 // Image paints: the texels of an Image as the source of a Color cover (include/contrast_hip.h crh_scene_set_paints_with_images states the model)
 enum class Filter : uint32_t { Nearest = CRH_FILTER_NEAREST, Linear = CRH_FILTER_LINEAR, NearestMipmap = CRH_FILTER_NEAREST | CRH_FILTER_MIPMAP, LinearMipmap = CRH_FILTER_LINEAR | CRH_FILTER_MIPMAP };
+// what Image::blur reads outside the image (crh_blur_edge); Transparent grows the result by the radius on every side
+enum class BlurEdge : uint32_t { Transparent = CRH_BLUR_EDGE_TRANSPARENT, Pad = CRH_BLUR_EDGE_PAD, Repeat = CRH_BLUR_EDGE_REPEAT, Reflect = CRH_BLUR_EDGE_REFLECT };
+// crh_blur_taps (host only) -> the integer taps q[0 .. radius] of one axis of Image::blur, radius = ceil(3 sigma) = size() - 1; they sum to
+// exactly 65536 over the 2 radius + 1 positions (include/contrast_hip.h crh_image_blur states the rule)
+inline std::vector<uint32_t> blur_taps(float sigma) {
+    uint32_t radius = 0;
+    check(crh_blur_taps(sigma, nullptr, 0, &radius));
+    std::vector<uint32_t> taps(radius + 1u);
+    check(crh_blur_taps(sigma, taps.data(), (uint32_t)taps.size(), &radius));
+    return taps;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -610,7 +621,7 @@ class Image {
     ~Image() {
         if (handle_) crh_image_destroy(handle_);
     }
-    Image(Image&& other) noexcept : handle_(other.handle_), width_(other.width_), height_(other.height_) { other.handle_ = nullptr; }
+    Image(Image&& other) noexcept : handle_(other.handle_), width_(other.width_), height_(other.height_), origin_(other.origin_) { other.handle_ = nullptr; }
     Image(const Image&) = delete;
     Image& operator=(const Image&) = delete;
     uint32_t width() const { return width_; }
@@ -633,11 +644,24 @@ class Image {
         if (height) *height = h;
         return out;
     }
+    // crh_image_blur -> a new Image of one level: the separable Gaussian of this image's level 0, integer and bit-exact, complete on return (a
+    // synchronous call: one wait per blur). sigma_y < 0 means sigma_x. BlurEdge::Transparent grows the result by ceil(3 sigma) on every side
+    // and its origin() is (Rx, Ry); the other edges keep the size. This image is not modified.
+    Image blur(float sigma_x, float sigma_y = -1.0f, BlurEdge edge = BlurEdge::Transparent) const {
+        Image image;
+        check(crh_image_blur(handle_, sigma_x, sigma_y < 0.0f ? sigma_x : sigma_y, (uint32_t)edge, &image.handle_));
+        check(crh_image_size(image.handle_, &image.width_, &image.height_));
+        if (edge == BlurEdge::Transparent) image.origin_ = {(image.width_ - width_) / 2u, (image.height_ - height_) / 2u};
+        return image;
+    }
+    // the texel of this image over texel (0, 0) of the image it was blurred from: (0, 0) unless blur() grew it
+    std::array<uint32_t, 2> origin() const { return origin_; }
 
   private:
     Image() = default;
     crh_image* handle_ = nullptr;
     uint32_t width_ = 0, height_ = 0;
+    std::array<uint32_t, 2> origin_ = {0u, 0u};
 };
 class ImagePaint {
   public:

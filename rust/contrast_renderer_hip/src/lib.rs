@@ -738,12 +738,31 @@ pub enum Filter {
     /// `CRH_FILTER_LINEAR | CRH_FILTER_MIPMAP`: trilinear
     LinearMipmap = 0x101,
 }
+/// What `Image::blur` reads outside the image (`crh_blur_edge`)
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum BlurEdge {
+    /// (0, 0, 0, 0); the result grows by the radius on every side
+    Transparent = 0,
+    Pad = 1,
+    Repeat = 2,
+    Reflect = 3,
+}
+/// `crh_blur_taps` (host only) -> the integer taps q[0 ..= radius] of one axis of `Image::blur`, radius = ceil(3 sigma) = len() - 1; they sum
+/// to exactly 65536 over the 2 radius + 1 positions (include/contrast_hip.h, `crh_image_blur`, states the rule).
+pub fn blur_taps(sigma: f32) -> Result<Vec<u32>, Error> {
+    let mut radius = 0u32;
+    status(unsafe { ffi::crh_blur_taps(sigma, ptr::null_mut(), 0, &mut radius) })?;
+    let mut taps = vec![0u32; radius as usize + 1];
+    status(unsafe { ffi::crh_blur_taps(sigma, taps.as_mut_ptr(), taps.len() as u32, &mut radius) })?;
+    Ok(taps)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
     raw: *mut ffi::crh_image,
     width: u32,
     height: u32,
+    origin: (u32, u32),
 }
 impl Image {
     /// `rgba8`: width * height * 4 bytes, copied before the call returns
@@ -751,7 +770,7 @@ impl Image {
         assert_eq!(rgba8.len(), width as usize * height as usize * 4);
         let mut raw = ptr::null_mut();
         status(unsafe { ffi::crh_image_create(renderer.raw, width, height, rgba8.as_ptr() as *const _, &mut raw) })?;
-        Ok(Image { raw, width, height })
+        Ok(Image { raw, width, height, origin: (0, 0) })
     }
     /// A snapshot of what the frame shows (an RGBA8 or RGBA8-attachment frame), copied on the device
     pub fn from_frame(frame: &Frame) -> Result<Image, Error> {
@@ -759,7 +778,7 @@ impl Image {
         status(unsafe { ffi::crh_image_create_from_frame(frame.raw, &mut raw) })?;
         let (mut width, mut height) = (0u32, 0u32);
         status(unsafe { ffi::crh_image_size(raw, &mut width, &mut height) })?;
-        Ok(Image { raw, width, height })
+        Ok(Image { raw, width, height, origin: (0, 0) })
     }
     pub fn size(&self) -> (u32, u32) {
         (self.width, self.height)
@@ -782,6 +801,21 @@ impl Image {
         let mut out = vec![0u8; width as usize * height as usize * 4];
         status(unsafe { ffi::crh_image_download_level(self.raw, level, out.as_mut_ptr() as *mut _, &mut width, &mut height) })?;
         Ok((width, height, out))
+    }
+    /// `crh_image_blur` -> a new `Image` of one level: the separable Gaussian of this image's level 0, integer and bit-exact, complete on
+    /// return (a synchronous call: one wait per blur). Sigmas in [0, `CRH_MAX_BLUR_SIGMA`]. `BlurEdge::Transparent` grows the result by
+    /// ceil(3 sigma) on every side and its `origin()` is (Rx, Ry); the other edges keep the size. This image is not modified.
+    pub fn blur(&self, sigma_x: f32, sigma_y: f32, edge: BlurEdge) -> Result<Image, Error> {
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_blur(self.raw, sigma_x, sigma_y, edge as u32, &mut raw) })?;
+        let (mut width, mut height) = (0u32, 0u32);
+        status(unsafe { ffi::crh_image_size(raw, &mut width, &mut height) })?;
+        let origin = if edge == BlurEdge::Transparent { ((width - self.width) / 2, (height - self.height) / 2) } else { (0, 0) };
+        Ok(Image { raw, width, height, origin })
+    }
+    /// The texel of this image over texel (0, 0) of the image it was blurred from: (0, 0) unless `blur` grew it
+    pub fn origin(&self) -> (u32, u32) {
+        self.origin
     }
 }
 impl Drop for Image {
