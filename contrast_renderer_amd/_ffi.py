@@ -225,6 +225,10 @@ class ImagePaintC(C.Structure):  # crh_image_paint
     _fields_ = [("image", C.c_void_p), ("filter", C.c_uint32), ("spread_x", C.c_uint32), ("spread_y", C.c_uint32), ("m", C.c_float * 6)]
 
 
+class CompositeC(C.Structure):  # crh_composite
+    _fields_ = [("op", C.c_uint32), ("mode", C.c_uint32), ("opacity", C.c_float), ("x", C.c_int32), ("y", C.c_int32)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -303,9 +307,13 @@ def load_library():
         "crh_image_download_level": (C.c_int, [V, C.c_uint32, V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "crh_blur_taps": (C.c_int, [C.c_float, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
         "crh_image_blur": (C.c_int, [V, C.c_float, C.c_float, C.c_uint32, C.POINTER(V)]),
+        "crh_composite_validate": (C.c_int, [C.POINTER(CompositeC)]),
+        "crh_composite_texels": (C.c_int, [C.POINTER(CompositeC), V, V, C.c_uint64, V]),
+        "crh_image_composite": (C.c_int, [V, V, C.POINTER(CompositeC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),
+        "crh_frame_load_image": (C.c_int, [V, V]),
         "crh_frame_download": (C.c_int, [V, V]),
         "crh_frame_download_f16": (C.c_int, [V, V]),
         "crh_frame_device_pointer": (C.c_int, [V, C.POINTER(V)]),

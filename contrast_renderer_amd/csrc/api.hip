@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "composite.hpp"
 #include "launch.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
@@ -2379,20 +2380,39 @@ crh_status crh_frame_keep_pass_state(crh_frame* f) {
     f->carry = true; // (the planes are allocated and initialised — from the image, if the frame shows one — in front of the next pass: render_impl)
     return CRH_OK;
 }
-crh_status crh_frame_upload(crh_frame* f, const void* rgba8) {
-    if (!f || !f->renderer || !rgba8 || f->format == CRH_FORMAT_RGBA16F || f->slab_ty0 != 0u || f->slab_ty1 != 0xFFFFFFFFu) return CRH_ERR_INVALID_ARGUMENT;
+namespace {
+// LoadOp::Load of width * height * 4 bytes from the host or the device (crh_frame_upload, crh_frame_load_image); the caller has checked its arguments
+crh_status load_pixels(crh_frame* f, const void* rgba8, hipMemcpyKind kind) {
     crh_renderer* r = f->renderer;
     HIP_TRY(hipSetDevice(r->device));
     const crh_status st = settle_frame(f); // (a pass drawn again after the fact would draw over the new pixels)
     if (st != CRH_OK) return st;
     HIP_TRY(order_after_external(f, r->stream)); // behind the exchange's last read and write of the pixels
     // on the raster stream: behind the last pass into the frame, in front of the next one
-    HIP_TRY(hipMemcpyAsync(f->rgba8.p, rgba8, f->image_bytes(), hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipMemcpyAsync(f->rgba8.p, rgba8, f->image_bytes(), kind, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream)); // (the caller's bytes are copied when the call returns)
     f->cleared = false; // LoadOp::Load: the next pass reads these pixels
     f->carry = f->carry_valid = f->carry_recolor = false; // the stencil attachment and the alpha layers start from zero, as after crh_frame_clear
     f->counts_describe_pixels = false, f->check_pending = false, f->last_scene = nullptr;
     return CRH_OK;
+}
+bool loadable(const crh_frame* f) { return f && f->renderer && f->format != CRH_FORMAT_RGBA16F && f->slab_ty0 == 0u && f->slab_ty1 == 0xFFFFFFFFu; }
+} // namespace
+crh_status crh_frame_upload(crh_frame* f, const void* rgba8) {
+    if (!loadable(f) || !rgba8) return CRH_ERR_INVALID_ARGUMENT;
+    return load_pixels(f, rgba8, hipMemcpyHostToDevice);
+}
+crh_status crh_frame_load_image(crh_frame* f, const crh_image* image) {
+    if (!loadable(f) || !image) return CRH_ERR_INVALID_ARGUMENT;
+    if (image->renderer != f->renderer) {
+        g_error = "crh_frame_load_image: the image belongs to another renderer";
+        return CRH_ERR_INVALID_ARGUMENT;
+    }
+    if (image->width != f->width || image->height != f->height) {
+        g_error = "crh_frame_load_image: the image's size is not the frame's";
+        return CRH_ERR_INVALID_ARGUMENT;
+    }
+    return load_pixels(f, image->pixels->p, hipMemcpyDeviceToDevice);
 }
 crh_status crh_frame_clear_depth(crh_frame* f, float value) {
     if (!f || !f->depth.p || !std::isfinite(value)) return CRH_ERR_INVALID_ARGUMENT;
@@ -2987,6 +3007,64 @@ crh_status crh_image_blur(const crh_image* src, float sigma_x, float sigma_y, ui
     }
     ok = hip_ok(r->sync(), "sync(blur)") && ok; // (also behind a failure: `words` is read by the copy until the stream has drained)
     if (scratch) (void)hipFree(scratch);
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+namespace {
+static_assert(CRH_COMPOSITE_PLUS + 1 == kCompositeOps && CRH_BLEND_EXCLUSION + 1 == kBlendModes, "composite.hpp's table and modes are the header's");
+static_assert(CRH_BLEND_NORMAL == kBlendNormal && CRH_BLEND_MULTIPLY == kBlendMultiply && CRH_BLEND_SCREEN == kBlendScreen && CRH_BLEND_OVERLAY == kBlendOverlay && CRH_BLEND_DARKEN == kBlendDarken &&
+                  CRH_BLEND_LIGHTEN == kBlendLighten && CRH_BLEND_HARD_LIGHT == kBlendHardLight && CRH_BLEND_DIFFERENCE == kBlendDifference && CRH_BLEND_EXCLUSION == kBlendExclusion,
+              "composite.hpp's modes are the header's");
+crh_status composite_error(const char* what) {
+    g_error = std::string("crh_composite_validate: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+uint32_t opacity_code(float opacity) { return (uint32_t)std::floor((double)opacity * 255.0 + 0.5); }
+} // namespace
+crh_status crh_composite_validate(const crh_composite* how) {
+    if (!how) return CRH_ERR_INVALID_ARGUMENT;
+    if (how->op > CRH_COMPOSITE_PLUS) return composite_error("op is above CRH_COMPOSITE_PLUS");
+    if (how->mode > CRH_BLEND_EXCLUSION) return composite_error("mode is above CRH_BLEND_EXCLUSION");
+    if (!std::isfinite(how->opacity)) return CRH_ERR_NON_FINITE;
+    if (how->opacity < 0.0f || how->opacity > 1.0f) return composite_error("opacity is outside [0, 1]");
+    return CRH_OK;
+}
+crh_status crh_composite_texels(const crh_composite* how, const void* source_rgba8, const void* backdrop_rgba8, uint64_t n, void* out_rgba8) {
+    const crh_status st = crh_composite_validate(how);
+    if (st != CRH_OK) return st;
+    if (n == 0u) return CRH_OK;
+    if (!source_rgba8 || !backdrop_rgba8 || !out_rgba8) return CRH_ERR_INVALID_ARGUMENT;
+    const uint8_t* source = static_cast<const uint8_t*>(source_rgba8);
+    const uint8_t* backdrop = static_cast<const uint8_t*>(backdrop_rgba8);
+    uint8_t* out = static_cast<uint8_t*>(out_rgba8);
+    const uint32_t o = opacity_code(how->opacity);
+    const CompositeFactors f = composite_factors(how->op);
+#define CRH_COMPOSITE_RUN(M) composite_run<M>(source, backdrop, n, o, f, out)
+    CRH_COMPOSITE_MODES(how->mode, CRH_COMPOSITE_RUN)
+#undef CRH_COMPOSITE_RUN
+    return CRH_OK;
+}
+crh_status crh_image_composite(const crh_image* backdrop, const crh_image* source, const crh_composite* how, crh_image** out) {
+    if (!backdrop || !backdrop->renderer || !source || !how || !out) return CRH_ERR_INVALID_ARGUMENT;
+    crh_status st = crh_composite_validate(how);
+    if (st != CRH_OK) return st;
+    if (source->renderer != backdrop->renderer) {
+        g_error = "crh_image_composite: the images belong to different renderers";
+        return CRH_ERR_INVALID_ARGUMENT;
+    }
+    crh_renderer* r = backdrop->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    st = new_image(r, backdrop->width, backdrop->height, &image);
+    if (st != CRH_OK) return st;
+    launch_image_composite(static_cast<const uint32_t*>(backdrop->pixels->p), backdrop->width, backdrop->height, static_cast<const uint32_t*>(source->pixels->p), source->width, source->height,
+                           how->x, how->y, opacity_code(how->opacity), how->mode, how->op, static_cast<uint32_t*>(image->pixels->p), r->stream);
+    bool ok = hip_ok(hipGetLastError(), "k_image_composite");
+    ok = hip_ok(r->sync(), "sync(composite)") && ok;
     if (!ok) {
         delete image;
         return CRH_ERR_HIP;

@@ -1,8 +1,12 @@
 // csrc/image_filter.hip — crh_image_blur: a separable Gaussian blur of a premultiplied RGBA8 image as two kernels, integer and bit-exact
 // (include/contrast_hip.h states the model). k_image_blur_h filters rows of the source into an intermediate of four 16-bit values per
 // texel; k_image_blur_v filters the columns of that into packed RGBA8. Nothing here touches a raster kernel: the wrap helper is this file's own.
+// crh_image_composite: k_image_composite combines two images texel by texel with the rule of composite.hpp.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
+#include "composite.hpp"
 #include "launch.hpp"
 
 namespace crh {
@@ -161,6 +165,65 @@ void launch_image_blur_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, vo
 void launch_image_blur_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* pairs, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream) {
     const dim3 grid((out_w + (uint32_t)kBlurColumns - 1u) / (uint32_t)kBlurColumns, (out_h + (uint32_t)kBlurBlockRows - 1u) / (uint32_t)kBlurBlockRows);
     hipLaunchKernelGGL(k_image_blur_v, grid, dim3(kBlurColumns * kBlurWaves), 0, stream, static_cast<const uint2*>(tmp), tmp_h, out, out_w, out_h, pairs, radius, origin, edge);
+}
+
+namespace {
+constexpr int kCompositeLanes = 256;        // lanes per workgroup: one group of V texels of a row each
+constexpr uint32_t kCompositeBlocks = 8192; // the grid's cap: four rounds of 256 CUs x 8 workgroups (measured against 2048 and none: DESIGN.md); the rows beyond it are strided over
+template <int V> struct TexelGroup { typedef uint32_t type __attribute__((ext_vector_type(V))); }; // V texels: one access of 4 V bytes
+} // namespace
+
+// crh_image_composite. Streaming: 4 + 4 bytes read and 4 written per texel. A workgroup owns the row segment blockIdx.x of 256 V texels and
+// strides over the rows blockIdx.y, blockIdx.y + gridDim.y, ...; a lane owns V consecutive texels of it, V = 4, 2 or 1: the most for which
+// every row of the backdrop (and so of the result) starts on a multiple of 4 V bytes, w % V == 0, so that the group is one aligned load
+// and one aligned store and lies wholly inside the row or wholly outside it. The source is shifted by (x, y) against the result: its group
+// is one load of 4 V bytes only where `source_wide` says that its rows and the shift keep it aligned (source_w % V == 0 and x % V == 0:
+// then a group is wholly inside the source or wholly outside, too); otherwise V loads of 4 bytes. Every source address is formed behind
+// the range check, in unsigned arithmetic: i - x and j - y wrap modulo 2^32 for any int32 shift, and the true difference lies in
+// (-2^31 - 1, 2^31 + 16384), so the wrapped value is below the source's size (<= 16384) exactly when the true one is in range.
+// The operator is four wave-uniform integers (composite.hpp CompositeFactors), the mode one branch outside the texel and channel loops.
+template <int V>
+__global__ __launch_bounds__(kCompositeLanes) void k_image_composite(const uint32_t* __restrict__ backdrop, uint32_t w, uint32_t h, const uint32_t* __restrict__ source, uint32_t source_w,
+                                                                      uint32_t source_h, uint32_t x, uint32_t y, uint32_t source_wide, uint32_t o, uint32_t mode, CompositeFactors f,
+                                                                      uint32_t* __restrict__ out) {
+    typedef typename TexelGroup<V>::type Group;
+    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
+    if (i >= w) return; // (w % V == 0 and i % V == 0: the whole group is outside)
+    const uint32_t si = i - x;
+    for (uint32_t j = blockIdx.y; j < h; j += gridDim.y) {
+        const size_t at = (size_t)j * w + i;
+        const uint32_t sj = j - y;
+        const Group b = *reinterpret_cast<const Group*>(backdrop + at);
+        Group s = 0u, r;
+        if (sj < source_h) {
+            const uint32_t* line = source + (size_t)sj * source_w;
+            if (source_wide) {
+                if (si < source_w) s = *reinterpret_cast<const Group*>(line + si);
+            } else {
+#pragma unroll
+                for (int t = 0; t < V; ++t)
+                    if (si + (uint32_t)t < source_w) s[t] = line[si + (uint32_t)t];
+            }
+        }
+#define CRH_COMPOSITE_GROUP(M) \
+    _Pragma("unroll") for (int t = 0; t < V; ++t) r[t] = composite_texel<M>(s[t], b[t], o, f)
+        CRH_COMPOSITE_MODES(mode, CRH_COMPOSITE_GROUP)
+#undef CRH_COMPOSITE_GROUP
+        *reinterpret_cast<Group*>(out + at) = r;
+    }
+}
+
+void launch_image_composite(const uint32_t* backdrop, uint32_t w, uint32_t h, const uint32_t* source, uint32_t source_w, uint32_t source_h, int32_t x, int32_t y, uint32_t o, uint32_t mode,
+                            uint32_t op, uint32_t* out, hipStream_t stream) {
+    const uint32_t v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
+    // (uint32_t)x % v is x mod v for a negative x as well: v divides 2^32
+    const uint32_t wide = v > 1u && source_w % v == 0u && (uint32_t)x % v == 0u ? 1u : 0u;
+    const uint32_t segments = (w + (uint32_t)kCompositeLanes * v - 1u) / ((uint32_t)kCompositeLanes * v); // <= 64
+    const dim3 grid(segments, std::min(h, std::max(1u, kCompositeBlocks / segments)));
+    const CompositeFactors f = composite_factors(op);
+    if (v == 4u) hipLaunchKernelGGL(k_image_composite<4>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, o, mode, f, out);
+    else if (v == 2u) hipLaunchKernelGGL(k_image_composite<2>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, o, mode, f, out);
+    else hipLaunchKernelGGL(k_image_composite<1>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, 0u, o, mode, f, out);
 }
 
 } // namespace crh

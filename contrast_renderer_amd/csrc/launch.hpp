@@ -42,6 +42,10 @@ constexpr uint32_t kBlurMaxRadius = 192; // CRH_MAX_BLUR_RADIUS
 constexpr uint32_t kBlurTapPad = 8;      // zero taps on either side of k_image_blur_v's table: the output rows a lane accumulates
 void launch_image_blur_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, void* tmp, uint32_t out_w, const uint32_t* taps, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream);
 void launch_image_blur_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* pairs, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream); // pairs == nullptr: the identity
+// image_filter.hip: crh_image_composite's kernel. The result (w x h, as the backdrop) pairs its texel (i, j) with source texel (i - x, j - y), (0, 0, 0, 0)
+// outside the source; o = the opacity's code, mode < 9, op < 13 (composite.hpp holds the rule and the operator's table). x, y: any int32.
+void launch_image_composite(const uint32_t* backdrop, uint32_t w, uint32_t h, const uint32_t* source, uint32_t source_w, uint32_t source_h, int32_t x, int32_t y, uint32_t o, uint32_t mode,
+                            uint32_t op, uint32_t* out, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);

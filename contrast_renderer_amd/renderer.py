@@ -344,6 +344,12 @@ class Frame:
         data = np.ascontiguousarray(image)
         check(self.lib.crh_frame_upload(self.handle, data.ctypes.data))
 
+    def load_image(self, image):
+        """crh_frame_load_image: upload() with the bytes taken from level 0 of an Image on the device — how a composed layer comes back into
+        a frame without a round trip through the host. The same reset and the same frames refused as upload(); an image of another size or
+        of another renderer is refused (InvalidArgument). Complete when this returns: the image may be destroyed afterwards."""
+        check(self.lib.crh_frame_load_image(self.handle, image.handle))
+
     def download(self):
         """-> [height, width, 4] uint8 in the frame's storage order (R G B A, or B G R A for a BGRA format) or float16 (an RGBA16F frame)."""
         if self.format == FORMAT_RGBA16F:
@@ -391,6 +397,47 @@ def blur_taps(sigma):
     radius = C.c_uint32()
     check(lib.crh_blur_taps(float(sigma), taps.ctypes.data_as(C.POINTER(C.c_uint32)), len(taps), C.byref(radius)))
     return taps[:int(radius.value) + 1].copy(), int(radius.value)
+
+
+class CompositeOp(IntEnum):  # crh_composite_op: Porter-Duff, (fa, fb) in include/contrast_hip.h
+    Clear = 0
+    Copy = 1
+    Dst = 2
+    SrcOver = 3
+    DstOver = 4
+    SrcIn = 5
+    DstIn = 6
+    SrcOut = 7
+    DstOut = 8
+    SrcAtop = 9
+    DstAtop = 10
+    Xor = 11
+    Plus = 12
+
+
+class BlendMode(IntEnum):  # crh_blend_mode: the W3C compositing-1 separable modes with a polynomial premultiplied form
+    Normal = 0
+    Multiply = 1
+    Screen = 2
+    Overlay = 3
+    Darken = 4
+    Lighten = 5
+    HardLight = 6
+    Difference = 7
+    Exclusion = 8
+
+
+def composite_texels(source, backdrop, op=CompositeOp.SrcOver, mode=BlendMode.Normal, opacity=1.0):
+    """crh_composite_texels (host only): the compositing rule of Image.composite on n texel pairs, two (n, 4) uint8 arrays of premultiplied
+    RGBA8 -> an (n, 4) uint8 array (include/contrast_hip.h crh_image_composite states the rule)."""
+    source, backdrop = np.ascontiguousarray(source), np.ascontiguousarray(backdrop)
+    for texels in (source, backdrop):
+        if texels.dtype != np.uint8 or texels.ndim != 2 or texels.shape[1] != 4 or texels.shape != source.shape:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"composite_texels takes two (n, 4) uint8 arrays of one length, not {source.shape} {source.dtype} and {backdrop.shape} {backdrop.dtype}")
+    how = _ffi.CompositeC(int(op), int(mode), float(opacity), 0, 0)
+    out = np.empty_like(source)
+    check(_ffi.load_library().crh_composite_texels(C.byref(how), source.ctypes.data, backdrop.ctypes.data, source.shape[0], out.ctypes.data))
+    return out
 
 
 class Image:
@@ -463,6 +510,22 @@ class Image:
         image.width, image.height = int(w.value), int(h.value)
         if int(edge) == BlurEdge.Transparent:
             image.origin = ((image.width - self.width) // 2, (image.height - self.height) // 2)
+        return image
+
+    def composite(self, source, op=CompositeOp.SrcOver, mode=BlendMode.Normal, opacity=1.0, offset=(0, 0)):
+        """crh_image_composite, called on the backdrop -> a new Image of one level and of this image's size, origin (0, 0): `source` combined
+        with this image texel by texel by a Porter-Duff operator, a blend mode and a group opacity in [0, 1], integer and bit-exact, built on
+        the device and complete when this returns. Source texel (0, 0) lies over this image's texel `offset`, any integers; outside the
+        source the source is transparent. To place a BlurEdge.Transparent result, which grew by its `origin`, so that the image it was
+        blurred from would lie at (dx, dy): offset = (dx - source.origin[0], dy - source.origin[1]). Neither image is modified; `source` may
+        be this image."""
+        how = _ffi.CompositeC(int(op), int(mode), float(opacity), int(offset[0]), int(offset[1]))
+        image = Image.__new__(Image)
+        image.renderer, image.lib = self.renderer, self.lib
+        handle = C.c_void_p()
+        check(self.lib.crh_image_composite(self.handle, source.handle, C.byref(how), C.byref(handle)))
+        image.handle = handle
+        image.width, image.height = self.width, self.height
         return image
 
     def destroy(self):

@@ -517,6 +517,77 @@ typedef enum crh_blur_edge {
 } crh_blur_edge;
 crh_status crh_blur_taps(float sigma, uint32_t* taps, uint32_t capacity, uint32_t* radius); /* host only: no renderer, no device */
 crh_status crh_image_blur(const crh_image* src, float sigma_x, float sigma_y, uint32_t edge, crh_image** out);
+/* Compositing: two images into a third, texel by texel on the device — what makes snapshots, mipmaps and blurs LAYERS: a mask applied to a
+ * layer (DST_IN, SRC_IN), a blend mode, a group opacity, a shadow placed under its layer (DST_OVER at an offset, with the grown origin of
+ * a blurred image). The model is integer and bit-exact; the tests check every byte against it. All values are 8-bit codes, all arithmetic
+ * is unsigned 32-bit.
+ *   size         the result has the backdrop's size. Its texel (i, j) pairs backdrop texel (i, j) with source texel (i - x, j - y); outside
+ *                the source that texel is (0, 0, 0, 0). Nothing else is special there: SRC_IN, DST_IN, COPY and CLEAR clear outside the
+ *                source, exactly as the formula says.
+ *   load         each colour code of both texels is clamped to its alpha, c = min(c, a): every term below stays non-negative, and bytes
+ *                that are not premultiplied have a defined result.
+ *   opacity      the code o = floor((double)opacity * 255 + 0.5); every source code, alpha included, becomes s = (s o + 127) / 255 (integer
+ *                division). o = 255 is the identity; the mapping is monotone, so c <= a survives.
+ *   blend term   per colour channel, in units of 1 / 255^2, from the source's colour and alpha sc, sa and the backdrop's bc, ba:
+ *                NORMAL T = sc ba; MULTIPLY T = sc bc; SCREEN T = sc ba + bc sa - sc bc; DARKEN T = min(sc ba, bc sa);
+ *                LIGHTEN T = max(sc ba, bc sa); DIFFERENCE T = |sc ba - bc sa|; EXCLUSION T = sc ba + bc sa - 2 sc bc;
+ *                HARD_LIGHT T = 2 sc <= sa ? 2 sc bc : sa ba - 2 (ba - bc) (sa - sc); OVERLAY the same two branches, chosen by 2 bc <= ba.
+ *                0 <= T <= sa ba in every mode. Then X = sc (255 - ba) + T (for NORMAL: 255 sc).
+ *   operator     fa = A0 + A1 ba and fb = B0 + B1 sa, each one of 0, 255, the other texel's alpha or its complement. (fa, fb) =
+ *                CLEAR (0, 0); COPY (255, 0); DST (0, 255); SRC_OVER (255, 255 - sa); DST_OVER (255 - ba, 255); SRC_IN (ba, 0);
+ *                DST_IN (0, sa); SRC_OUT (255 - ba, 0); DST_OUT (0, 255 - sa); SRC_ATOP (ba, 255 - sa); DST_ATOP (255 - ba, sa);
+ *                XOR (255 - ba, 255 - sa); PLUS (255, 255).
+ *   output       co = min(255, (fa X + 255 fb bc + 32512) / 65025), ao = min(255, (fa sa + fb ba + 127) / 255): ONE rounding of the exact
+ *                rational value, half up (65025 and 255 are odd: no ties). The mode does not enter ao. The largest numerator is
+ *                33 162 750: 32 bits hold it.
+ * Hence: co <= ao; NORMAL + SRC_OVER at o = 255 is sc + round(bc (255 - sa) / 255); DST is a copy of the backdrop and COPY the placed
+ * source; a transparent source leaves the backdrop unchanged under SRC_OVER, DST_OVER, DST_OUT, SRC_ATOP, XOR and PLUS; every result is
+ * within 0.5 code of the W3C compositing-1 real-valued formula evaluated on the codes after the load and opacity stages.
+ * crh_composite_validate and crh_composite_texels are host only (no renderer, no device). validate: a null `how` is
+ * CRH_ERR_INVALID_ARGUMENT; an op above 12, a mode above 8 or an opacity outside [0, 1] CRH_ERR_INVALID_ARGUMENT with a crh_last_error
+ * text; a non-finite opacity CRH_ERR_NON_FINITE. texels: the rule on n pairs of texels (x and y are ignored), 4 n bytes each in the order
+ * r g b a at any alignment; out may be either input.
+ * crh_image_composite validates before it touches the device: a null argument or images of different renderers are
+ * CRH_ERR_INVALID_ARGUMENT, and a refused call leaves *out untouched. backdrop == source is legal. The result is a fresh image of one level
+ * (crh_image_generate_mipmaps works on it), complete when the call returns, as crh_image_blur's; only the inputs' level 0 is read and
+ * they are not modified. A failed allocation or launch frees everything and returns CRH_ERR_HIP.
+ * Limits: the call is synchronous; images are immutable, so there is no in-place variant; offsets are integers; no color-dodge,
+ * color-burn or soft-light (they divide or take a root and need an exactness argument of their own) and no non-separable modes; the codes
+ * are combined as they are, with no gamma handling; this is not a per-draw blend mode of the raster path. */
+typedef enum crh_composite_op { /* Porter-Duff */
+    CRH_COMPOSITE_CLEAR = 0,
+    CRH_COMPOSITE_COPY = 1,
+    CRH_COMPOSITE_DST = 2,
+    CRH_COMPOSITE_SRC_OVER = 3,
+    CRH_COMPOSITE_DST_OVER = 4,
+    CRH_COMPOSITE_SRC_IN = 5,
+    CRH_COMPOSITE_DST_IN = 6,
+    CRH_COMPOSITE_SRC_OUT = 7,
+    CRH_COMPOSITE_DST_OUT = 8,
+    CRH_COMPOSITE_SRC_ATOP = 9,
+    CRH_COMPOSITE_DST_ATOP = 10,
+    CRH_COMPOSITE_XOR = 11,
+    CRH_COMPOSITE_PLUS = 12
+} crh_composite_op;
+typedef enum crh_blend_mode { /* W3C compositing-1 separable modes with a polynomial premultiplied form */
+    CRH_BLEND_NORMAL = 0,
+    CRH_BLEND_MULTIPLY = 1,
+    CRH_BLEND_SCREEN = 2,
+    CRH_BLEND_OVERLAY = 3,
+    CRH_BLEND_DARKEN = 4,
+    CRH_BLEND_LIGHTEN = 5,
+    CRH_BLEND_HARD_LIGHT = 6,
+    CRH_BLEND_DIFFERENCE = 7,
+    CRH_BLEND_EXCLUSION = 8
+} crh_blend_mode;
+typedef struct crh_composite {
+    uint32_t op, mode;
+    float opacity; /* [0, 1]; the code o = floor((double)opacity * 255 + 0.5) */
+    int32_t x, y;  /* source texel (0, 0) lies over backdrop texel (x, y); any int32 */
+} crh_composite;
+crh_status crh_composite_validate(const crh_composite* how); /* host only */
+crh_status crh_composite_texels(const crh_composite* how, const void* source_rgba8, const void* backdrop_rgba8, uint64_t n, void* out_rgba8); /* host only */
+crh_status crh_image_composite(const crh_image* backdrop, const crh_image* source, const crh_composite* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */
@@ -533,6 +604,11 @@ crh_status crh_scene_set_paints_with_images(crh_scene* scene, const crh_paint* p
  * behind the last pass into the frame; the host bytes are copied before the call returns. CRH_ERR_INVALID_ARGUMENT for a
  * CRH_FORMAT_RGBA16F frame and for a frame restricted by crh_frame_set_tile_rows. */
 crh_status crh_frame_upload(crh_frame* frame, const void* rgba8);
+/* LoadOp::Load of an image: crh_frame_upload with the bytes taken from level 0 of `image` on the device — how a composed layer comes back
+ * into a frame without a round trip through the host. The same ordering, the same reset of stencil, alpha layers and pass state, the same
+ * frames refused; the call returns when the copy is done, so the image may be destroyed afterwards. An image of another size or of another
+ * renderer is CRH_ERR_INVALID_ARGUMENT. */
+crh_status crh_frame_load_image(crh_frame* frame, const crh_image* image);
 /* MSAA resolve (box average, examples/showcase/main.rs:215) + copy to host, `rgba8` = width*height*4 bytes, row 0 = top. */
 crh_status crh_frame_download(crh_frame* frame, void* rgba8);
 /* The same for a CRH_FORMAT_RGBA16F frame: width*height*8 bytes (four IEEE binary16 per pixel). Each entry point refuses the other format. */

@@ -538,6 +538,9 @@ class Frame {
         if (rgba8.size() != (size_t)width_ * height_ * 4) throw Error(CRH_ERR_INVALID_ARGUMENT);
         check(crh_frame_upload(handle_, rgba8.data()));
     }
+    // crh_frame_load_image: upload() with the bytes taken from level 0 of an Image on the device (the same size, the same renderer); complete on
+    // return, so the image may be destroyed afterwards
+    inline void load_image(const class Image& image);
     std::vector<uint8_t> download() {                 // MSAA resolve + read back: premultiplied 8-bit pixels in the frame's storage order, row 0 = top
         std::vector<uint8_t> out((size_t)width_ * height_ * 4);
         check(crh_frame_download(handle_, out.data()));
@@ -605,6 +608,25 @@ inline std::vector<uint32_t> blur_taps(float sigma) {
     check(crh_blur_taps(sigma, taps.data(), (uint32_t)taps.size(), &radius));
     return taps;
 }
+// Compositing (include/contrast_hip.h crh_image_composite states the rule): the Porter-Duff operator, the blend mode, and the rule on texel pairs
+enum class CompositeOp : uint32_t {
+    Clear = CRH_COMPOSITE_CLEAR, Copy = CRH_COMPOSITE_COPY, Dst = CRH_COMPOSITE_DST, SrcOver = CRH_COMPOSITE_SRC_OVER, DstOver = CRH_COMPOSITE_DST_OVER, SrcIn = CRH_COMPOSITE_SRC_IN,
+    DstIn = CRH_COMPOSITE_DST_IN, SrcOut = CRH_COMPOSITE_SRC_OUT, DstOut = CRH_COMPOSITE_DST_OUT, SrcAtop = CRH_COMPOSITE_SRC_ATOP, DstAtop = CRH_COMPOSITE_DST_ATOP, Xor = CRH_COMPOSITE_XOR,
+    Plus = CRH_COMPOSITE_PLUS
+};
+enum class BlendMode : uint32_t {
+    Normal = CRH_BLEND_NORMAL, Multiply = CRH_BLEND_MULTIPLY, Screen = CRH_BLEND_SCREEN, Overlay = CRH_BLEND_OVERLAY, Darken = CRH_BLEND_DARKEN, Lighten = CRH_BLEND_LIGHTEN,
+    HardLight = CRH_BLEND_HARD_LIGHT, Difference = CRH_BLEND_DIFFERENCE, Exclusion = CRH_BLEND_EXCLUSION
+};
+// crh_composite_texels (host only): the rule on source.size() / 4 texel pairs of premultiplied RGBA8 -> as many bytes
+inline std::vector<uint8_t> composite_texels(const std::vector<uint8_t>& source, const std::vector<uint8_t>& backdrop, CompositeOp op = CompositeOp::SrcOver, BlendMode mode = BlendMode::Normal,
+                                             float opacity = 1.0f) {
+    if (source.size() != backdrop.size() || source.size() % 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const crh_composite how = {(uint32_t)op, (uint32_t)mode, opacity, 0, 0};
+    std::vector<uint8_t> out(source.size());
+    check(crh_composite_texels(&how, source.data(), backdrop.data(), source.size() / 4u, out.data()));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -656,6 +678,18 @@ class Image {
     }
     // the texel of this image over texel (0, 0) of the image it was blurred from: (0, 0) unless blur() grew it
     std::array<uint32_t, 2> origin() const { return origin_; }
+    // crh_image_composite, called on the backdrop -> a new Image of one level, of this image's size, origin (0, 0): `source` combined with this
+    // image texel by texel by a Porter-Duff operator, a blend mode and a group opacity in [0, 1]; integer and bit-exact, complete on return.
+    // Source texel (0, 0) lies over this image's texel `offset` (any integers; the source is transparent outside itself). To place a
+    // BlurEdge::Transparent result so that the image it was blurred from would lie at (dx, dy): offset = {dx - origin()[0], dy - origin()[1]}
+    // of the source. Neither image is modified; `source` may be this image.
+    Image composite(const Image& source, CompositeOp op = CompositeOp::SrcOver, BlendMode mode = BlendMode::Normal, float opacity = 1.0f, std::array<int32_t, 2> offset = {0, 0}) const {
+        const crh_composite how = {(uint32_t)op, (uint32_t)mode, opacity, offset[0], offset[1]};
+        Image image;
+        check(crh_image_composite(handle_, source.handle_, &how, &image.handle_));
+        image.width_ = width_, image.height_ = height_;
+        return image;
+    }
 
   private:
     Image() = default;
@@ -663,6 +697,7 @@ class Image {
     uint32_t width_ = 0, height_ = 0;
     std::array<uint32_t, 2> origin_ = {0u, 0u};
 };
+inline void Frame::load_image(const Image& image) { check(crh_frame_load_image(handle_, image.raw())); }
 class ImagePaint {
   public:
     // matrix: path -> texel, u = m0 x + m1 y + m2, v = m3 x + m4 y + m5

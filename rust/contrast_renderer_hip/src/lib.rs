@@ -560,6 +560,11 @@ impl Frame {
         assert_eq!(rgba8.len(), (self.width * self.height * 4) as usize);
         status(unsafe { ffi::crh_frame_upload(self.raw, rgba8.as_ptr() as *const _) }).unwrap()
     }
+    /// `crh_frame_load_image`: `upload` with the bytes taken from level 0 of an `Image` on the device (the same size, the same renderer);
+    /// complete on return, so the image may be dropped afterwards.
+    pub fn load_image(&mut self, image: &Image) -> Result<(), Error> {
+        status(unsafe { ffi::crh_frame_load_image(self.raw, image.raw) })
+    }
     /// Premultiplied 8-bit pixels in the frame's storage order, row 0 = top
     pub fn download(&mut self) -> Vec<u8> {
         let mut pixels = vec![0u8; (self.width * self.height * 4) as usize];
@@ -756,6 +761,45 @@ pub fn blur_taps(sigma: f32) -> Result<Vec<u32>, Error> {
     status(unsafe { ffi::crh_blur_taps(sigma, taps.as_mut_ptr(), taps.len() as u32, &mut radius) })?;
     Ok(taps)
 }
+/// The Porter-Duff operator of `Image::composite` (`crh_composite_op`)
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum CompositeOp {
+    Clear = 0,
+    Copy = 1,
+    Dst = 2,
+    SrcOver = 3,
+    DstOver = 4,
+    SrcIn = 5,
+    DstIn = 6,
+    SrcOut = 7,
+    DstOut = 8,
+    SrcAtop = 9,
+    DstAtop = 10,
+    Xor = 11,
+    Plus = 12,
+}
+/// The blend mode of `Image::composite` (`crh_blend_mode`): the W3C compositing-1 separable modes with a polynomial premultiplied form
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum BlendMode {
+    Normal = 0,
+    Multiply = 1,
+    Screen = 2,
+    Overlay = 3,
+    Darken = 4,
+    Lighten = 5,
+    HardLight = 6,
+    Difference = 7,
+    Exclusion = 8,
+}
+/// `crh_composite_texels` (host only): the compositing rule on `source.len() / 4` texel pairs of premultiplied RGBA8
+/// (include/contrast_hip.h, `crh_image_composite`, states the rule).
+pub fn composite_texels(source: &[u8], backdrop: &[u8], op: CompositeOp, mode: BlendMode, opacity: f32) -> Result<Vec<u8>, Error> {
+    assert!(source.len() == backdrop.len() && source.len() % 4 == 0);
+    let how = ffi::crh_composite { op: op as u32, mode: mode as u32, opacity, x: 0, y: 0 };
+    let mut out = vec![0u8; source.len()];
+    status(unsafe { ffi::crh_composite_texels(&how, source.as_ptr() as *const _, backdrop.as_ptr() as *const _, (source.len() / 4) as u64, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -816,6 +860,17 @@ impl Image {
     /// The texel of this image over texel (0, 0) of the image it was blurred from: (0, 0) unless `blur` grew it
     pub fn origin(&self) -> (u32, u32) {
         self.origin
+    }
+    /// `crh_image_composite`, called on the backdrop -> a new `Image` of one level, of this image's size, origin (0, 0): `source` combined
+    /// with this image texel by texel by a Porter-Duff operator, a blend mode and a group opacity in [0, 1]; integer and bit-exact, complete
+    /// on return. Source texel (0, 0) lies over this image's texel `offset` (any integers; the source is transparent outside itself). To
+    /// place a `BlurEdge::Transparent` result so that the image it was blurred from would lie at (dx, dy): offset = (dx - origin().0,
+    /// dy - origin().1) of the source. Neither image is modified; `source` may be this image.
+    pub fn composite(&self, source: &Image, op: CompositeOp, mode: BlendMode, opacity: f32, offset: (i32, i32)) -> Result<Image, Error> {
+        let how = ffi::crh_composite { op: op as u32, mode: mode as u32, opacity, x: offset.0, y: offset.1 };
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_composite(self.raw, source.raw, &how, &mut raw) })?;
+        Ok(Image { raw, width: self.width, height: self.height, origin: (0, 0) })
     }
 }
 impl Drop for Image {
