@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "color_filter.hpp"
 #include "composite.hpp"
 #include "launch.hpp"
 #include "raster_params.hpp"
@@ -3065,6 +3066,59 @@ crh_status crh_image_composite(const crh_image* backdrop, const crh_image* sourc
                            how->x, how->y, opacity_code(how->opacity), how->mode, how->op, static_cast<uint32_t*>(image->pixels->p), r->stream);
     bool ok = hip_ok(hipGetLastError(), "k_image_composite");
     ok = hip_ok(r->sync(), "sync(composite)") && ok;
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+namespace {
+static_assert(CRH_COLOR_MATRIX_MAX == kColorMatrixMax, "color_filter.hpp's bound is the header's");
+// validates and quantises: the one way from the caller's floats to the coefficients, for the host rule and the kernel alike
+crh_status color_filter_coefficients(const float* matrix, ColorFilterCoefficients* f) {
+    switch (color_filter_quantize(matrix, f)) {
+    case kColorFilterNonFinite: return CRH_ERR_NON_FINITE;
+    case kColorFilterTooLarge: g_error = "crh_color_filter_validate: a coefficient is outside [-CRH_COLOR_MATRIX_MAX, CRH_COLOR_MATRIX_MAX]"; return CRH_ERR_INVALID_ARGUMENT;
+    default: return CRH_OK;
+    }
+}
+} // namespace
+crh_status crh_color_filter_validate(const float* matrix, const uint8_t* tables) {
+    (void)tables; // (every byte is a legal entry)
+    ColorFilterCoefficients f;
+    return color_filter_coefficients(matrix, &f);
+}
+crh_status crh_color_filter_texels(const float* matrix, const uint8_t* tables, const void* rgba8, uint64_t n, void* out) {
+    ColorFilterCoefficients f;
+    const crh_status st = color_filter_coefficients(matrix, &f);
+    if (st != CRH_OK) return st;
+    if (n == 0u) return CRH_OK;
+    if (!rgba8 || !out) return CRH_ERR_INVALID_ARGUMENT;
+    if (tables) color_filter_run<true>(static_cast<const uint8_t*>(rgba8), n, f, tables, static_cast<uint8_t*>(out));
+    else color_filter_run<false>(static_cast<const uint8_t*>(rgba8), n, f, nullptr, static_cast<uint8_t*>(out));
+    return CRH_OK;
+}
+crh_status crh_image_color_filter(const crh_image* src, const float* matrix, const uint8_t* tables, crh_image** out) {
+    if (!src || !src->renderer || !out) return CRH_ERR_INVALID_ARGUMENT;
+    ColorFilterCoefficients f;
+    crh_status st = color_filter_coefficients(matrix, &f);
+    if (st != CRH_OK) return st;
+    crh_renderer* r = src->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    st = new_image(r, src->width, src->height, &image);
+    if (st != CRH_OK) return st;
+    void* tables_dev = nullptr; // the caller's 1024 bytes, as they are
+    bool ok = true;
+    if (tables)
+        ok = hip_ok(hipMalloc(&tables_dev, 1024), "hipMalloc(colour tables)") && hip_ok(hipMemcpyAsync(tables_dev, tables, 1024, hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(colour tables)");
+    if (ok) {
+        launch_image_color_filter(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, f, static_cast<const uint32_t*>(tables_dev), static_cast<uint32_t*>(image->pixels->p), r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_color_filter");
+    }
+    ok = hip_ok(r->sync(), "sync(colour filter)") && ok; // (also behind a failure: `tables` is read by the copy until the stream has drained)
+    if (tables_dev) (void)hipFree(tables_dev);
     if (!ok) {
         delete image;
         return CRH_ERR_HIP;

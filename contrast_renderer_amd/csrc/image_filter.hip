@@ -2,10 +2,12 @@
 // (include/contrast_hip.h states the model). k_image_blur_h filters rows of the source into an intermediate of four 16-bit values per
 // texel; k_image_blur_v filters the columns of that into packed RGBA8. Nothing here touches a raster kernel: the wrap helper is this file's own.
 // crh_image_composite: k_image_composite combines two images texel by texel with the rule of composite.hpp.
+// crh_image_color_filter: k_image_color_filter maps every texel of an image with the rule of color_filter.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "color_filter.hpp"
 #include "composite.hpp"
 #include "launch.hpp"
 
@@ -224,6 +226,56 @@ void launch_image_composite(const uint32_t* backdrop, uint32_t w, uint32_t h, co
     if (v == 4u) hipLaunchKernelGGL(k_image_composite<4>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, o, mode, f, out);
     else if (v == 2u) hipLaunchKernelGGL(k_image_composite<2>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, o, mode, f, out);
     else hipLaunchKernelGGL(k_image_composite<1>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, 0u, o, mode, f, out);
+}
+
+namespace {
+__device__ const UnpremultiplyTable k_unpremultiply{}; // color_filter.hpp's reciprocals, staged in LDS by every workgroup of the kernel below
+} // namespace
+
+// crh_image_color_filter. Streaming: 4 bytes read and 4 written per texel, k_image_composite's geometry with one input: a workgroup owns the
+// row segment blockIdx.x of 256 V texels and strides over the rows blockIdx.y, blockIdx.y + gridDim.y, ...; a lane owns V consecutive texels,
+// V = 4, 2 or 1 with w % V == 0, so that its group is one aligned load and one aligned store and lies wholly inside the row or wholly outside
+// it: every address is (row j < h) * w + (column i < w). The 16 coefficients and 4 biases are kernel arguments, wave-uniform (SGPRs); the
+// matrix stage is 16 signed 24-bit multiply-adds per texel. The unpremultiply's 256 reciprocals and, with TABLES, the four 256-byte tables
+// (as they are in memory: four byte planes, entry v of channel i at byte 256 i + v) are staged in LDS once per workgroup, one word per lane
+// each, and read per texel with data-dependent indices: one 4-byte read for the alpha's reciprocal, four 1-byte reads for the tables.
+// TABLES = false stages and reads no table and declares no LDS for one.
+template <int V, bool TABLES>
+__global__ __launch_bounds__(kCompositeLanes) void k_image_color_filter(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, ColorFilterCoefficients f,
+                                                                         const uint32_t* __restrict__ tables, uint32_t* __restrict__ out) {
+    typedef typename TexelGroup<V>::type Group;
+    __shared__ uint32_t recip[256];
+    __shared__ uint32_t lut[TABLES ? 256 : 1];
+    recip[threadIdx.x] = k_unpremultiply.r[threadIdx.x];
+    if (TABLES) lut[threadIdx.x] = tables[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
+    if (i >= w) return; // (w % V == 0 and i % V == 0: the whole group is outside)
+    for (uint32_t j = blockIdx.y; j < h; j += gridDim.y) {
+        const size_t at = (size_t)j * w + i;
+        const Group s = *reinterpret_cast<const Group*>(src + at);
+        Group r;
+#pragma unroll
+        for (int t = 0; t < V; ++t) r[t] = color_filter_texel<TABLES>(s[t], f, recip, reinterpret_cast<const uint8_t*>(lut));
+        *reinterpret_cast<Group*>(out + at) = r;
+    }
+}
+
+void launch_image_color_filter(const uint32_t* src, uint32_t w, uint32_t h, const ColorFilterCoefficients& f, const uint32_t* tables, uint32_t* out, hipStream_t stream) {
+    const uint32_t v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
+    const uint32_t segments = (w + (uint32_t)kCompositeLanes * v - 1u) / ((uint32_t)kCompositeLanes * v); // <= 64
+    const dim3 grid(segments, std::min(h, std::max(1u, kCompositeBlocks / segments)));
+#define CRH_COLOR_FILTER_LAUNCH(V, TABLES) hipLaunchKernelGGL((k_image_color_filter<V, TABLES>), grid, dim3(kCompositeLanes), 0, stream, src, w, h, f, tables, out)
+    if (tables) {
+        if (v == 4u) CRH_COLOR_FILTER_LAUNCH(4, true);
+        else if (v == 2u) CRH_COLOR_FILTER_LAUNCH(2, true);
+        else CRH_COLOR_FILTER_LAUNCH(1, true);
+    } else {
+        if (v == 4u) CRH_COLOR_FILTER_LAUNCH(4, false);
+        else if (v == 2u) CRH_COLOR_FILTER_LAUNCH(2, false);
+        else CRH_COLOR_FILTER_LAUNCH(1, false);
+    }
+#undef CRH_COLOR_FILTER_LAUNCH
 }
 
 } // namespace crh

@@ -46,6 +46,10 @@ void launch_image_blur_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_
 // outside the source; o = the opacity's code, mode < 9, op < 13 (composite.hpp holds the rule and the operator's table). x, y: any int32.
 void launch_image_composite(const uint32_t* backdrop, uint32_t w, uint32_t h, const uint32_t* source, uint32_t source_w, uint32_t source_h, int32_t x, int32_t y, uint32_t o, uint32_t mode,
                             uint32_t op, uint32_t* out, hipStream_t stream);
+// image_filter.hip: crh_image_color_filter's kernel. src and out: w x h texels; f from color_filter_quantize; tables: the 1024 table bytes on the
+// device (256 words), or nullptr for none (color_filter.hpp holds the rule).
+struct ColorFilterCoefficients;
+void launch_image_color_filter(const uint32_t* src, uint32_t w, uint32_t h, const ColorFilterCoefficients& f, const uint32_t* tables, uint32_t* out, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);

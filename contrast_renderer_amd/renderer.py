@@ -5,6 +5,7 @@ All arithmetic runs in libcontrast_hip.so on the GPU; this module only marshals 
 """
 import ctypes as C
 import dataclasses
+import math
 from dataclasses import dataclass
 from enum import IntEnum, IntFlag
 from typing import ClassVar, Optional, Tuple
@@ -440,6 +441,82 @@ def composite_texels(source, backdrop, op=CompositeOp.SrcOver, mode=BlendMode.No
     return out
 
 
+COLOR_MATRIX_MAX = 16.0  # CRH_COLOR_MATRIX_MAX
+
+
+class ColorMatrix:
+    """The 4 x 5 matrices of Image.color_filter as lists of 20 floats, row-major: rows r', g', b', a', columns r, g, b, a, 1 on unpremultiplied
+    colours in [0, 1]. The coefficients are those of SVG filter effects (feColorMatrix), computed in float64 and rounded to f32 once."""
+
+    @staticmethod
+    def _rows(rows):
+        return [float(np.float32(v)) for row in rows for v in row]
+
+    @staticmethod
+    def identity():
+        return ColorMatrix._rows([[1, 0, 0, 0, 0], [0, 1, 0, 0, 0], [0, 0, 1, 0, 0], [0, 0, 0, 1, 0]])
+
+    @staticmethod
+    def saturate(s):
+        """feColorMatrix type="saturate": s = 0 is grayscale, 1 the identity, above 1 oversaturates"""
+        s = float(s)
+        return ColorMatrix._rows([[0.213 + 0.787 * s, 0.715 - 0.715 * s, 0.072 - 0.072 * s, 0, 0],
+                                  [0.213 - 0.213 * s, 0.715 + 0.285 * s, 0.072 - 0.072 * s, 0, 0],
+                                  [0.213 - 0.213 * s, 0.715 - 0.715 * s, 0.072 + 0.928 * s, 0, 0],
+                                  [0, 0, 0, 1, 0]])
+
+    @staticmethod
+    def hue_rotate(degrees):
+        """feColorMatrix type="hueRotate": the hue turned by `degrees`"""
+        angle = math.radians(float(degrees))
+        c, s = math.cos(angle), math.sin(angle)
+        return ColorMatrix._rows([[0.213 + c * 0.787 - s * 0.213, 0.715 - c * 0.715 - s * 0.715, 0.072 - c * 0.072 + s * 0.928, 0, 0],
+                                  [0.213 - c * 0.213 + s * 0.143, 0.715 + c * 0.285 + s * 0.140, 0.072 - c * 0.072 - s * 0.283, 0, 0],
+                                  [0.213 - c * 0.213 - s * 0.787, 0.715 - c * 0.715 + s * 0.715, 0.072 + c * 0.928 + s * 0.072, 0, 0],
+                                  [0, 0, 0, 1, 0]])
+
+    @staticmethod
+    def luminance_to_alpha():
+        """feColorMatrix type="luminanceToAlpha": the colour becomes (0, 0, 0), the alpha the luminance — SVG's default mask type"""
+        return ColorMatrix._rows([[0, 0, 0, 0, 0], [0, 0, 0, 0, 0], [0, 0, 0, 0, 0], [0.2125, 0.7154, 0.0721, 0, 0]])
+
+    @staticmethod
+    def flood(r, g, b, a):
+        """Every texel takes the straight colour (r, g, b) and a times its alpha: the colour of a drop shadow"""
+        return ColorMatrix._rows([[0, 0, 0, 0, r], [0, 0, 0, 0, g], [0, 0, 0, 0, b], [0, 0, 0, a, 0]])
+
+    @staticmethod
+    def opacity(a):
+        return ColorMatrix._rows([[1, 0, 0, 0, 0], [0, 1, 0, 0, 0], [0, 0, 1, 0, 0], [0, 0, 0, a, 0]])
+
+
+def _color_filter_arguments(matrix, tables):
+    """-> (a c_float * 20 or None, a contiguous uint8 array of 1024 or None)"""
+    m = t = None
+    if matrix is not None:
+        values = [float(v) for v in np.asarray(matrix, dtype=np.float64).ravel()]
+        if len(values) != 20:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"a colour matrix has 20 coefficients, not {len(values)}")
+        m = (C.c_float * 20)(*values)
+    if tables is not None:
+        t = np.ascontiguousarray(tables)
+        if t.dtype != np.uint8 or t.size != 1024:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"colour tables are 1024 uint8 values (r, g, b, a: 256 each), not {t.shape} {t.dtype}")
+    return m, t
+
+
+def color_filter_texels(texels, matrix=None, tables=None):
+    """crh_color_filter_texels (host only): the colour-filter rule of Image.color_filter on an (n, 4) uint8 array of premultiplied RGBA8 ->
+    an (n, 4) uint8 array (include/contrast_hip.h crh_image_color_filter states the rule)."""
+    texels = np.ascontiguousarray(texels)
+    if texels.dtype != np.uint8 or texels.ndim != 2 or texels.shape[1] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"color_filter_texels takes an (n, 4) uint8 array, not {texels.shape} {texels.dtype}")
+    m, t = _color_filter_arguments(matrix, tables)
+    out = np.empty_like(texels)
+    check(_ffi.load_library().crh_color_filter_texels(m, None if t is None else t.ctypes.data_as(C.POINTER(C.c_uint8)), texels.ctypes.data, texels.shape[0], out.ctypes.data))
+    return out
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -526,6 +603,21 @@ class Image:
         check(self.lib.crh_image_composite(self.handle, source.handle, C.byref(how), C.byref(handle)))
         image.handle = handle
         image.width, image.height = self.width, self.height
+        return image
+
+    def color_filter(self, matrix=None, tables=None):
+        """crh_image_color_filter -> a new Image of one level, of this image's size and origin: every texel unpremultiplied, through the
+        4 x 5 `matrix` (20 floats, row-major, |m| <= COLOR_MATRIX_MAX; ColorMatrix builds the usual ones; None = the identity), then through
+        `tables` (1024 uint8: r, g, b, a, 256 entries each; None = the identity), and premultiplied again — integer and bit-exact, built on
+        the device and complete when this returns. A blurred snapshot through ColorMatrix.flood(r, g, b, a) is a drop shadow in that colour.
+        This image is not modified."""
+        m, t = _color_filter_arguments(matrix, tables)
+        image = Image.__new__(Image)
+        image.renderer, image.lib = self.renderer, self.lib
+        handle = C.c_void_p()
+        check(self.lib.crh_image_color_filter(self.handle, m, None if t is None else t.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(handle)))
+        image.handle = handle
+        image.width, image.height, image.origin = self.width, self.height, self.origin
         return image
 
     def destroy(self):

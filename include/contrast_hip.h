@@ -480,7 +480,8 @@ crh_status crh_image_level_count(const crh_image* image, uint32_t* count);
 crh_status crh_image_download_level(const crh_image* image, uint32_t level, void* rgba8, uint32_t* width, uint32_t* height);
 /* Blur: a separable Gaussian of an image on the device — the soft layer behind a drop shadow, a glow, a soft mask, a blurred backdrop. A
  * blurred snapshot of a frame (crh_image_create_from_frame) drawn as an image paint with the tint (0, 0, 0, a) is a drop shadow: the tint rule
- * of `source` above needs nothing more. The model is integer and bit-exact; the tests check every byte against it.
+ * of `source` above needs nothing more (as an image, in any colour: crh_image_color_filter with a flood matrix). The model is integer and
+ * bit-exact; the tests check every byte against it.
  *   taps         one axis, from the f32 sigma widened to double s: R = (uint32_t)ceil(3.0 * s); w[k] = exp(-(k*k) / (2 s s)), k = 0 .. R;
  *                S = w[0] + 2 w[1] + ... + 2 w[R], summed in that order; q[k] = floor(w[k] / S * 65536 + 0.5); then the rounding's deficit
  *                d = 65536 - (q[0] + 2 sum_{k>=1} q[k]), g = sign(d), m = |d| / 2 (integer division): q[1 .. m] += g, q[0] += d - 2 g m.
@@ -519,7 +520,7 @@ crh_status crh_blur_taps(float sigma, uint32_t* taps, uint32_t capacity, uint32_
 crh_status crh_image_blur(const crh_image* src, float sigma_x, float sigma_y, uint32_t edge, crh_image** out);
 /* Compositing: two images into a third, texel by texel on the device — what makes snapshots, mipmaps and blurs LAYERS: a mask applied to a
  * layer (DST_IN, SRC_IN), a blend mode, a group opacity, a shadow placed under its layer (DST_OVER at an offset, with the grown origin of
- * a blurred image). The model is integer and bit-exact; the tests check every byte against it. All values are 8-bit codes, all arithmetic
+ * a blurred image; its colour from crh_image_color_filter). The model is integer and bit-exact; the tests check every byte against it. All values are 8-bit codes, all arithmetic
  * is unsigned 32-bit.
  *   size         the result has the backdrop's size. Its texel (i, j) pairs backdrop texel (i, j) with source texel (i - x, j - y); outside
  *                the source that texel is (0, 0, 0, 0). Nothing else is special there: SRC_IN, DST_IN, COPY and CLEAR clear outside the
@@ -588,6 +589,45 @@ typedef struct crh_composite {
 crh_status crh_composite_validate(const crh_composite* how); /* host only */
 crh_status crh_composite_texels(const crh_composite* how, const void* source_rgba8, const void* backdrop_rgba8, uint64_t n, void* out_rgba8); /* host only */
 crh_status crh_image_composite(const crh_image* backdrop, const crh_image* source, const crh_composite* how, crh_image** out);
+/* Colour filters: every texel of an image through a 4 x 5 matrix on its unpremultiplied colour (SVG feColorMatrix) and then through a
+ * 256-entry table per channel (feComponentTransfer), on the device — the colour of a drop shadow (a flood matrix on the blurred layer),
+ * a luminance mask turned into alpha for DST_IN, grayscale, saturate, hue rotation, invert, brightness and contrast, a threshold, a
+ * per-layer opacity curve, and the gamma tables that linearise before a blur and re-encode after it. The model is integer and bit-exact;
+ * the tests check every byte against it. All values are 8-bit codes, all arithmetic is signed 32-bit.
+ *   matrix       20 floats, row-major 4 x 5: rows r', g', b', a', columns r, g, b, a, 1. NULL is the identity.
+ *   tables       1024 bytes, r[256] g[256] b[256] a[256]. NULL is the identity. Both NULL is a legal copy (of the loaded texels).
+ *   load         each colour code is clamped to its alpha, c = min(c, a), as compositing does.
+ *   unpremultiply  u_c = (255 c + a / 2) / a (integer division) for a > 0 and 0 for a = 0; u_a = a. Straight 8-bit codes: u_c <= 255
+ *                because c <= a.
+ *   coefficients k[i][j] = (int32) floor((double) m[i][j] * 65536 + 0.5). Every m is finite (else CRH_ERR_NON_FINITE) and
+ *                |m| <= CRH_COLOR_MATRIX_MAX (else CRH_ERR_INVALID_ARGUMENT with a crh_last_error text), so |k| <= 2^20: a signed 24-bit
+ *                operand.
+ *   matrix stage n_i = k[i][0] u_r + k[i][1] u_g + k[i][2] u_b + k[i][3] u_a + 255 k[i][4] + 32768;
+ *                |n_i| <= 5 * 255 * 2^20 + 32768 = 1 336 967 168 < 2^31. v_i = clamp(floor(n_i / 65536), 0, 255), the floor an arithmetic
+ *                shift. The identity's k is exactly 65536 on the diagonal: v = u.
+ *   table stage  v_i = tables[256 i + v_i] when tables are given.
+ *   premultiply  a' = v_a, c' = (v_c v_a + 127) / 255 (integer division). Hence c' <= a'.
+ * Hence: the identity (NULL / NULL, the identity matrix, identity tables) returns every premultiplied texel exactly (|u a / 255 - c| <=
+ * a / 510 < 1/2 for a < 255; all 32 896 pairs c <= a are tested); a texel with a = 0 goes in as (0, 0, 0, 0) whatever its colour bytes
+ * are; the flood matrix — zero colour columns, the bias (r, g, b), m[3][3] = alpha — gives round(colour * round(alpha a)), a shadow's
+ * colour; luminanceToAlpha gives an alpha from the straight colour times alpha; without tables every result lies within
+ * e_c + e_a + e_c e_a / 255 + 1/2 codes (colour) and e_a (alpha) of the real-valued formula on the loaded codes, where
+ * e_i = (1 + sum_{j<3} |m_ij|) / 2 + 5 * 255 * 2^-17.
+ * crh_color_filter_validate and crh_color_filter_texels are host only (no renderer, no device). texels: the rule on n texels, 4 n bytes in
+ * the order r g b a at any alignment; out may be rgba8; n == 0 is legal, otherwise a null rgba8 or out is CRH_ERR_INVALID_ARGUMENT; a
+ * refused call writes nothing.
+ * crh_image_color_filter validates before it touches the device: a null src or out is CRH_ERR_INVALID_ARGUMENT, and a refused call leaves
+ * *out untouched. The result is a fresh image of the source's renderer and size with one level (crh_image_generate_mipmaps, blur,
+ * composite, image paints and crh_frame_load_image work on it), complete when the call returns: k_image_color_filter runs on the
+ * renderer's stream. Only level 0 of the source is read and the source is not modified. A failed allocation or launch frees everything
+ * and returns CRH_ERR_HIP.
+ * Limits: the call is synchronous, like blur and composite — one wait per filter; images are immutable, so there is no in-place variant;
+ * the straight intermediates are 8-bit codes, so two filters in a row round twice (fold matrices on the host instead); tables are
+ * applied after the matrix only; this is not a per-draw filter of the raster path. */
+#define CRH_COLOR_MATRIX_MAX 16.0f
+crh_status crh_color_filter_validate(const float* matrix, const uint8_t* tables); /* host only */
+crh_status crh_color_filter_texels(const float* matrix, const uint8_t* tables, const void* rgba8, uint64_t n, void* out); /* host only */
+crh_status crh_image_color_filter(const crh_image* src, const float* matrix, const uint8_t* tables, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

@@ -627,6 +627,51 @@ inline std::vector<uint8_t> composite_texels(const std::vector<uint8_t>& source,
     check(crh_composite_texels(&how, source.data(), backdrop.data(), source.size() / 4u, out.data()));
     return out;
 }
+// Colour filters (include/contrast_hip.h crh_image_color_filter states the rule): a 4 x 5 matrix on unpremultiplied colours, rows r', g', b', a',
+// columns r, g, b, a, 1, and one 256-entry table per channel. The constructors use the SVG filter-effects coefficients, computed in double and
+// rounded to float once.
+using ColorMatrixValues = std::array<float, 20>;
+using ColorTables = std::array<uint8_t, 1024>; // r[256] g[256] b[256] a[256]
+struct ColorMatrix {
+    static ColorMatrixValues from_rows(const double (&m)[20]) {
+        ColorMatrixValues out;
+        for (size_t n = 0; n < 20; ++n) out[n] = (float)m[n];
+        return out;
+    }
+    static ColorMatrixValues identity() { return opacity(1.0); }
+    static ColorMatrixValues saturate(double s) {
+        const double m[20] = {0.213 + 0.787 * s, 0.715 - 0.715 * s, 0.072 - 0.072 * s, 0, 0, 0.213 - 0.213 * s, 0.715 + 0.285 * s, 0.072 - 0.072 * s, 0, 0,
+                              0.213 - 0.213 * s, 0.715 - 0.715 * s, 0.072 + 0.928 * s, 0, 0, 0, 0, 0, 1, 0};
+        return from_rows(m);
+    }
+    static ColorMatrixValues hue_rotate(double degrees) {
+        const double angle = degrees * 3.14159265358979323846 / 180.0, c = std::cos(angle), s = std::sin(angle);
+        const double m[20] = {0.213 + c * 0.787 - s * 0.213, 0.715 - c * 0.715 - s * 0.715, 0.072 - c * 0.072 + s * 0.928, 0, 0,
+                              0.213 - c * 0.213 + s * 0.143, 0.715 + c * 0.285 + s * 0.140, 0.072 - c * 0.072 - s * 0.283, 0, 0,
+                              0.213 - c * 0.213 - s * 0.787, 0.715 - c * 0.715 + s * 0.715, 0.072 + c * 0.928 + s * 0.072, 0, 0, 0, 0, 0, 1, 0};
+        return from_rows(m);
+    }
+    static ColorMatrixValues luminance_to_alpha() {
+        const double m[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.2125, 0.7154, 0.0721, 0, 0};
+        return from_rows(m);
+    }
+    // every texel takes the straight colour (r, g, b) and a times its alpha: the colour of a drop shadow
+    static ColorMatrixValues flood(double r, double g, double b, double a) {
+        const double m[20] = {0, 0, 0, 0, r, 0, 0, 0, 0, g, 0, 0, 0, 0, b, 0, 0, 0, a, 0};
+        return from_rows(m);
+    }
+    static ColorMatrixValues opacity(double a) {
+        const double m[20] = {1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, a, 0};
+        return from_rows(m);
+    }
+};
+// crh_color_filter_texels (host only): the rule on texels.size() / 4 texels of premultiplied RGBA8 -> as many bytes; a null matrix or tables is the identity
+inline std::vector<uint8_t> color_filter_texels(const std::vector<uint8_t>& texels, const ColorMatrixValues* matrix = nullptr, const ColorTables* tables = nullptr) {
+    if (texels.size() % 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    std::vector<uint8_t> out(texels.size());
+    check(crh_color_filter_texels(matrix ? matrix->data() : nullptr, tables ? tables->data() : nullptr, texels.data(), texels.size() / 4u, out.data()));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -688,6 +733,15 @@ class Image {
         Image image;
         check(crh_image_composite(handle_, source.handle_, &how, &image.handle_));
         image.width_ = width_, image.height_ = height_;
+        return image;
+    }
+    // crh_image_color_filter -> a new Image of one level, of this image's size and origin: every texel unpremultiplied, through the matrix, then
+    // through the tables, and premultiplied again; integer and bit-exact, complete on return. A null matrix or tables is the identity. A blurred
+    // snapshot through ColorMatrix::flood(r, g, b, a) is a drop shadow in that colour. This image is not modified.
+    Image color_filter(const ColorMatrixValues* matrix = nullptr, const ColorTables* tables = nullptr) const {
+        Image image;
+        check(crh_image_color_filter(handle_, matrix ? matrix->data() : nullptr, tables ? tables->data() : nullptr, &image.handle_));
+        image.width_ = width_, image.height_ = height_, image.origin_ = origin_;
         return image;
     }
 

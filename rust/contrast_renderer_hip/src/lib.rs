@@ -800,6 +800,57 @@ pub fn composite_texels(source: &[u8], backdrop: &[u8], op: CompositeOp, mode: B
     status(unsafe { ffi::crh_composite_texels(&how, source.as_ptr() as *const _, backdrop.as_ptr() as *const _, (source.len() / 4) as u64, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// The 4 x 5 matrices of `Image::color_filter`: rows r', g', b', a', columns r, g, b, a, 1 on unpremultiplied colours in [0, 1]. The
+/// coefficients are those of SVG filter effects (feColorMatrix), computed in f64 and rounded to f32 once.
+pub struct ColorMatrix;
+impl ColorMatrix {
+    fn rows(m: [f64; 20]) -> [f32; 20] {
+        let mut out = [0f32; 20];
+        for (o, v) in out.iter_mut().zip(m.iter()) {
+            *o = *v as f32;
+        }
+        out
+    }
+    pub fn identity() -> [f32; 20] {
+        Self::opacity(1.0)
+    }
+    pub fn saturate(s: f64) -> [f32; 20] {
+        Self::rows([
+            0.213 + 0.787 * s, 0.715 - 0.715 * s, 0.072 - 0.072 * s, 0.0, 0.0, //
+            0.213 - 0.213 * s, 0.715 + 0.285 * s, 0.072 - 0.072 * s, 0.0, 0.0, //
+            0.213 - 0.213 * s, 0.715 - 0.715 * s, 0.072 + 0.928 * s, 0.0, 0.0, //
+            0.0, 0.0, 0.0, 1.0, 0.0,
+        ])
+    }
+    pub fn hue_rotate(degrees: f64) -> [f32; 20] {
+        let (s, c) = degrees.to_radians().sin_cos();
+        Self::rows([
+            0.213 + c * 0.787 - s * 0.213, 0.715 - c * 0.715 - s * 0.715, 0.072 - c * 0.072 + s * 0.928, 0.0, 0.0, //
+            0.213 - c * 0.213 + s * 0.143, 0.715 + c * 0.285 + s * 0.140, 0.072 - c * 0.072 - s * 0.283, 0.0, 0.0, //
+            0.213 - c * 0.213 - s * 0.787, 0.715 - c * 0.715 + s * 0.715, 0.072 + c * 0.928 + s * 0.072, 0.0, 0.0, //
+            0.0, 0.0, 0.0, 1.0, 0.0,
+        ])
+    }
+    pub fn luminance_to_alpha() -> [f32; 20] {
+        Self::rows([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.2125, 0.7154, 0.0721, 0.0, 0.0])
+    }
+    /// Every texel takes the straight colour (r, g, b) and a times its alpha: the colour of a drop shadow
+    pub fn flood(r: f64, g: f64, b: f64, a: f64) -> [f32; 20] {
+        Self::rows([0.0, 0.0, 0.0, 0.0, r, 0.0, 0.0, 0.0, 0.0, g, 0.0, 0.0, 0.0, 0.0, b, 0.0, 0.0, 0.0, a, 0.0])
+    }
+    pub fn opacity(a: f64) -> [f32; 20] {
+        Self::rows([1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, a, 0.0])
+    }
+}
+/// `crh_color_filter_texels` (host only): the colour-filter rule on `texels.len() / 4` texels of premultiplied RGBA8; `None` is the identity
+/// (include/contrast_hip.h, `crh_image_color_filter`, states the rule).
+pub fn color_filter_texels(texels: &[u8], matrix: Option<&[f32; 20]>, tables: Option<&[u8; 1024]>) -> Result<Vec<u8>, Error> {
+    assert!(texels.len() % 4 == 0);
+    let mut out = vec![0u8; texels.len()];
+    let (m, t) = (matrix.map_or(ptr::null(), |m| m.as_ptr()), tables.map_or(ptr::null(), |t| t.as_ptr()));
+    status(unsafe { ffi::crh_color_filter_texels(m, t, texels.as_ptr() as *const _, (texels.len() / 4) as u64, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -871,6 +922,15 @@ impl Image {
         let mut raw = ptr::null_mut();
         status(unsafe { ffi::crh_image_composite(self.raw, source.raw, &how, &mut raw) })?;
         Ok(Image { raw, width: self.width, height: self.height, origin: (0, 0) })
+    }
+    /// `crh_image_color_filter` -> a new `Image` of one level, of this image's size and origin: every texel unpremultiplied, through the 4 x 5
+    /// matrix, then through the four 256-entry tables, and premultiplied again; integer and bit-exact, complete on return. `None` is the
+    /// identity. A blurred snapshot through `ColorMatrix::flood(r, g, b, a)` is a drop shadow in that colour. This image is not modified.
+    pub fn color_filter(&self, matrix: Option<&[f32; 20]>, tables: Option<&[u8; 1024]>) -> Result<Image, Error> {
+        let mut raw = ptr::null_mut();
+        let (m, t) = (matrix.map_or(ptr::null(), |m| m.as_ptr()), tables.map_or(ptr::null(), |t| t.as_ptr()));
+        status(unsafe { ffi::crh_image_color_filter(self.raw, m, t, &mut raw) })?;
+        Ok(Image { raw, width: self.width, height: self.height, origin: self.origin })
     }
 }
 impl Drop for Image {
