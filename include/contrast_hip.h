@@ -246,7 +246,9 @@ crh_status crh_convert_dynamic_stroke_options(const crh_dynamic_stroke_options* 
  * points) also keep the capacities of its vertex streams: the next crh_scene_tessellate does not wait for
  * the totals of the new paths; a tessellation that does not fit after all is noticed when a frame drawn from
  * it is settled (crh_frame_synchronize, crh_frame_download, ...) or by crh_scene_status, sized and repeated,
- * the frame drawn again. The host arrays of `batch` are copied before the call returns. */
+ * the frame drawn again. The host arrays of `batch` are copied before the call returns. `existing` keeps its paint table and
+ * association (crh_scene_set_paints, crh_scene_set_paints_with_images) whatever the new Shape count: instance i of the new Shapes has the
+ * paint instance_paint[i] where the association reaches and its solid colour beyond it; its instances are to be set again. */
 crh_status crh_scene_upload(crh_renderer* renderer, const crh_path_batch* batch, crh_scene* existing, crh_scene** out);
 /* The arithmetic of from_paths for every shape of the scene, on the GPU:
  * StrokeBuilder::add_path (stroke.rs:205-465), FillBuilder::add_path (fill.rs:263-367),

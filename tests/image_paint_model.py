@@ -273,3 +273,86 @@ def stroke_case(filter, size=SIZE):
     err = uv_error(size + 80.0, texel_px(spec, t, size), float(max(np.abs(u).max(), np.abs(v).max())))
     src, seam = image_source(spec, np.float32([1.0, 1.0, 1.0, 1.0]), p, err)
     return t, spec, src, seam, extra_of(spec, err)
+
+
+# ---------------------------------------------------------------- the coordinate rule at its ends: exact expectations from the header's text alone
+
+EXTREME_SIZE = 64  # the frame: a power of two, so the blit's inverse homography is exact and (X, Y) = the pixel centres k + 0.5
+EXTREME_IMAGE = (8, 5)  # width, height: 2^23 and 2^24 leave other remainders modulo 5 and 10 than modulo 8 and 16
+EXTREME_SPREADS = [(Spread.Pad, Spread.Pad), (Spread.Repeat, Spread.Repeat), (Spread.Reflect, Spread.Reflect), (Spread.Repeat, Spread.Reflect)]
+LIMIT = 2.0 ** 24
+NEUTRAL = 2.0 ** 22
+
+
+def extreme_rows():
+    """(name, own, other, offset): one row of the matrix, coordinate = own * (the row's own axis) + other * (the other axis) + offset. The
+    coefficient of the own axis is chosen so that every sum is exact or far from a rounding boundary of f32:
+      2^23 - 32 with own = -1: 2^23 - 32 - (k + 0.5) lies below 2^23, where the f32 step is 0.5: exact, and below the clamp;
+      2^24 with own = 0: exactly at the clamp; 2^24 + 64 with own = 1: 2^24 + 64 + k + 0.5 rounds to an even integer (the step is 2, a tie
+      would be an odd integer) and is clamped; the negatives mirrored; +-3e38 with own = 0 (3e38 + 0.5 is not exact in float64);
+      own = 3e38: the product overflows to +inf (1.5e38 in the first column) and is clamped;
+      own = 3e38, other = -3e38, offset 1e38: +-inf or +-1e38 and beyond. The product of an fma is not rounded, so inf - inf does not occur for
+      a finite matrix and finite (X, Y): NaN reaches the rule through the division of a projective instance only."""
+    a, b, c, big = 2.0 ** 23 - 32.0, 2.0 ** 24 - 8.5 + 8.5, 2.0 ** 24 + 64.0, 3e38
+    return [("2^23-32", -1.0, 0.0, a), ("-(2^23-32)", 1.0, 0.0, -a), ("2^24", 0.0, 0.0, b), ("-2^24", 0.0, 0.0, -b), ("2^24+64", 1.0, 0.0, c),
+            ("-(2^24+64)", -1.0, 0.0, -c), ("3e38", 0.0, 0.0, big), ("-3e38", 0.0, 0.0, -big), ("overflow", big, 0.0, 0.0), ("inf-and-back", big, -big, 1e38)]
+
+
+def extreme_matrices():
+    """(name, (m0 .. m5)): every row of extreme_rows on u, the same on v, and one matrix with another extreme per axis. The other axis of the
+    first two is the pixel centre + 2^22: exact where the f32 step is 0.5, so that an f32 error of (X, Y) is rounded away there too — at the
+    identity a LINEAR sample sits on the texel centre, where such an error moves floor(v - 0.5) to the texel before with a fraction next to 1."""
+    out = [(f"u:{n}", (own, other, c, 0.0, 1.0, NEUTRAL)) for n, own, other, c in extreme_rows()]
+    out += [(f"v:{n}", (1.0, 0.0, NEUTRAL, other, own, c)) for n, own, other, c in extreme_rows()]
+    rows = {n: (own, other, c) for n, own, other, c in extreme_rows()}
+    (uo, ux, uc), (vo, vx, vc) = rows["2^23-32"], rows["-(2^24+64)"]
+    return out + [("u:2^23-32,v:-(2^24+64)", (uo, ux, uc, vx, vo, vc))]
+
+
+def fma32(a, b, c, exact=True):
+    """fma(a, b, c) of f32 values held in float64 arrays: the product of two f32 values is exact in float64; the sum is asserted to be (two-sum:
+    the error term is zero) unless `exact` is False; one rounding to f32, overflow to inf."""
+    a, b, c = (np.asarray(x, dtype=np.float64) for x in (a, b, c))
+    assert (np.float64(np.float32(a)) == a).all() and (np.float64(np.float32(b)) == b).all()
+    with np.errstate(over="ignore", invalid="ignore"):
+        p = a * b
+        s = p + c
+        if exact:
+            finite = np.isfinite(s) & np.isfinite(c)
+            t = s - p
+            err = np.where(finite, (p - (s - t)) + (c - t), 0.0)
+            assert (err == 0.0).all(), "a product-sum that float64 does not hold exactly"
+        return np.float64(np.float32(s))
+
+
+def extreme_uv(matrix, X, Y, exact=True):
+    """The header's coordinates: u = fma(Y, m1, fma(X, m0, m2)), v = fma(Y, m4, fma(X, m3, m5)) in f32, NaN -> 0, clamped to +-2^24."""
+    m = np.float64(np.float32(matrix))
+    u, v = fma32(Y, m[1], fma32(X, m[0], m[2], exact), exact), fma32(Y, m[4], fma32(X, m[3], m[5], exact), exact)
+    return tuple(np.clip(np.where(np.isnan(c), 0.0, c), -LIMIT, LIMIT) for c in (u, v))
+
+
+def extreme_taps(matrix, filter, spread_x, spread_y, size=EXTREME_SIZE, image=EXTREME_IMAGE, scale=(1.0, 1.0), exact=True):
+    """-> (i0, i1, j0, j1, fx, fy), each [size, size]: the wrapped indices and the fractions of the filter at every pixel centre scaled by
+    `scale` (the perturbation of the stability check). NEAREST: i1 = i0, j1 = j0 and the fractions are 0."""
+    w, h = image
+    Y, X = np.meshgrid((np.arange(size) + 0.5) * scale[1], (np.arange(size) + 0.5) * scale[0], indexing="ij")
+    if scale != (1.0, 1.0):
+        X, Y = np.float64(np.float32(X)), np.float64(np.float32(Y))
+    u, v = extreme_uv(matrix, X, Y, exact)
+    if int(filter) & 1 == int(Filter.Nearest):
+        i, j = wrap(np.floor(u).astype(np.int64), w, spread_x), wrap(np.floor(v).astype(np.int64), h, spread_y)
+        return i, i, j, j, np.zeros_like(u), np.zeros_like(v)
+    a, b = np.float64(np.float32(u - 0.5)), np.float64(np.float32(v - 0.5))
+    i, j = np.floor(a).astype(np.int64), np.floor(b).astype(np.int64)
+    return wrap(i, w, spread_x), wrap(i + 1, w, spread_x), wrap(j, h, spread_y), wrap(j + 1, h, spread_y), a - i, b - j
+
+
+def extreme_expectation(pixels, matrix, filter, spread_x, spread_y, size=EXTREME_SIZE):
+    """The bytes of the blit under a white tint into a cleared frame. Every case sits on a texel centre (the fractions are 0, asserted), so the
+    value is one texel's codes, which decode to k / 255 and encode to k again."""
+    h, w = pixels.shape[:2]
+    i0, _, j0, _, fx, fy = extreme_taps(matrix, filter, spread_x, spread_y, size, (w, h))
+    assert not fx.any() and not fy.any()
+    assert i0.min() >= 0 and i0.max() < w and j0.min() >= 0 and j0.max() < h
+    return pixels[j0, i0]

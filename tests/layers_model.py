@@ -1,0 +1,403 @@
+"""The generator and the host model of the stateful image and layer fuzz (tests/test_gpu_layers_fuzz.py): random sequences over one Renderer,
+two frames (RGBA8 and RGBA8_ATTACHMENT), a pool of images, a solid Scene and a blit Scene per frame — images created, snapshot from frames,
+blurred, composited, colour filtered, mipmapped, loaded back into frames, drawn as image paints through tables that outlive their images,
+between clears, uploads, plain passes and re-uploads of the solid Scene. Every image operation has an integer model (blur_model,
+composite_model, color_filter_model, mip_model) and every pass an exact expectation (the oracle for the solid Scene, the image's own bytes for
+an identity blit), so every check is of bytes. No GPU and no library call in here: the oracle alone."""
+import numpy as np
+
+from contrast_renderer_amd import scenes
+
+import blur_model as BM
+import color_filter_model as FM
+import composite_model as CM
+import mip_model as MM
+
+FORMATS = (0, 2)  # FORMAT_RGBA8, FORMAT_RGBA8_ATTACHMENT: frame 0 and frame 1
+MAX_POOL = 8
+MAX_SIDE = 300  # a TRANSPARENT blur is given another edge when it would grow an image beyond this (the sigma-64 blur apart)
+SIGMAS = (0.0, 0.01, 0.3, 1.0, 2.5, 6.0)
+NEAREST, LINEAR, MIPMAP = 0, 1, 0x100
+STENCIL, COLOR = 0, 3  # RenderOperation.Stencil, RenderOperation.Color
+KINDS = ("create", "snapshot", "blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image", "clear", "solid", "upload", "load_image",
+         "download", "set_table", "replace_table", "clear_table", "blit", "blit_mip", "white_paint", "reupload")
+WEIGHTS = (0.06, 0.07, 0.11, 0.09, 0.08, 0.04, 0.08, 0.04, 0.01, 0.09, 0.06, 0.05, 0.06, 0.03, 0.05, 0.04, 0.06, 0.03, 0.03, 0.03)
+
+
+def master_case(seed):
+    """The master batch of a seed: scene_mixed, the first of its random seeds the oracle can tessellate (as the lifecycle fuzz picks its own)."""
+    from oracle.binding import Oracle
+    rng = np.random.RandomState(9300 + seed)
+    n = int(rng.randint(10, 20))
+    while True:
+        sc = scenes.scene_mixed(n, (160, 160), seed=int(rng.randint(0, 100000)))
+        if Oracle(sc["batch"]).status() == 0:
+            return sc
+
+
+def threshold_tables():
+    """The identity on the colours, alpha to 0 below 128 and to 255 from there: what makes an image one that a blit may draw over content."""
+    t = FM.identity_tables().reshape(4, 256).copy()
+    t[3] = np.where(np.arange(256) < 128, 0, 255)
+    return t.reshape(-1)
+
+
+def premultiplied(pixels):
+    return bool((pixels[..., :3] <= pixels[..., 3:4]).all())
+
+
+def binary_alpha(pixels):
+    return bool(((pixels[..., 3] == 0) | (pixels[..., 3] == 255)).all())
+
+
+def blit_bytes(pixels, old):
+    """The model's blit rule: the identity placement samples texel (column, row) at pixel (column, row) — a NEAREST floor of k + 0.5, a LINEAR
+    fraction of 0 — under a white tint: the image's bytes into a cleared frame (old is None); over content, an image of alpha 0 or 255 only:
+    its bytes where alpha = 255, the old bytes where alpha = 0. Code k decodes to k / 255 and encodes to k again in both frame formats."""
+    if old is None:
+        return pixels.copy()
+    assert binary_alpha(pixels) and premultiplied(pixels)
+    return np.where(pixels[..., 3:4] == 255, pixels, old)
+
+
+def step_blur(pixels, sigma_x, sigma_y, edge):
+    return BM.blur_sigma(pixels, sigma_x, sigma_y, edge)
+
+
+def step_composite(backdrop, source, op, mode, opacity, offset):
+    return CM.composite(backdrop, source, op, mode, CM.opacity_code(opacity), offset[0], offset[1])
+
+
+def step_color_filter(pixels, matrix, tables):
+    return FM.texels(pixels, matrix, tables)
+
+
+class Model:
+    """What every frame and every pool image must hold. apply(op) -> the arrays the device's answers to the op are compared with (empty for
+    an op that checks nothing)."""
+
+    def __init__(self, setup, batch=None, oracle=None):
+        from oracle.binding import Oracle
+        self.s = setup
+        self.batch = master_case(setup["seed"])["batch"] if batch is None else batch
+        self.oracle = Oracle(self.batch) if oracle is None else oracle
+        w, h = setup["width"], setup["height"]
+        self.frame = [dict(image=np.zeros((h, w, 4), np.uint8), cleared=True, last="clear") for _ in FORMATS]
+        self.pool = []  # dict(pixels, mip, depth): depth = the device operations behind the image
+        self.table = [None, None]  # of the blit Scene of each frame: dict(pixels, filter, destroyed, index)
+        self.slice = tuple(setup["slice"])
+        self.instances = None
+
+    # ---- passes
+    def solid_pass(self, j, instances):
+        from oracle.binding import render_pass
+        if instances is not None:
+            self.instances = instances
+        a, b = self.slice
+        t, c = self.instances
+        assert len(t) == b - a
+        draws = [d for i in range(b - a) for d in ((a + i, i, STENCIL, 0, 0), (a + i, i, COLOR, 0, 0))]
+        f = self.frame[j]
+        image, _ = render_pass(self.oracle, self.s["width"], self.s["height"], self.s["msaa"], 4, 4, 0, t, c, draws,
+                               load=None if f["cleared"] else f["image"], attachment8=FORMATS[j] == 2)
+        f.update(image=image, cleared=False, last="solid")
+
+    def blit(self, j):
+        f, table = self.frame[j], self.table[j]
+        f.update(image=blit_bytes(table["pixels"], None if f["cleared"] else f["image"]), last="painted-cleared" if f["cleared"] else "painted", cleared=False)
+
+    def apply(self, op):
+        kind = op["kind"]
+        if kind == "create":
+            self.pool.append(dict(pixels=op["pixels"], mip=False, depth=0))
+        elif kind == "snapshot":
+            self.pool.append(dict(pixels=self.frame[op["frame"]]["image"].copy(), mip=False, depth=1))
+        elif kind == "blur":
+            src = self.pool[op["image"]]
+            self.pool.append(dict(pixels=step_blur(src["pixels"], op["sigma"][0], op["sigma"][1], op["edge"]), mip=False, depth=src["depth"] + 1))
+        elif kind == "composite":
+            back, src = self.pool[op["image"]], self.pool[op["source"]]
+            self.pool.append(dict(pixels=step_composite(back["pixels"], src["pixels"], op["op"], op["mode"], op["opacity"], op["offset"]), mip=False,
+                                  depth=max(back["depth"], src["depth"]) + 1))
+        elif kind == "color_filter":
+            src = self.pool[op["image"]]
+            self.pool.append(dict(pixels=step_color_filter(src["pixels"], op["matrix"], op["tables"]), mip=False, depth=src["depth"] + 1))
+        elif kind == "mipmaps":
+            self.pool[op["image"]]["mip"] = True
+        elif kind == "check_image":
+            e = self.pool[op["image"]]
+            return MM.chain(e["pixels"]) if e["mip"] else [e["pixels"]]
+        elif kind == "destroy_image":
+            self.pool.pop(op["image"])
+            for table in self.table:
+                if table is not None:
+                    if table["index"] == op["image"]:
+                        table["index"], table["destroyed"] = None, True
+                    elif table["index"] is not None and table["index"] > op["image"]:
+                        table["index"] -= 1
+        elif kind == "clear":
+            f = self.frame[op["frame"]]
+            f.update(image=np.zeros_like(f["image"]), cleared=True, last="clear")
+        elif kind == "solid":
+            self.solid_pass(op["frame"], op.get("instances"))
+        elif kind == "upload":
+            self.frame[op["frame"]].update(image=op["pixels"], cleared=False, last="upload")
+        elif kind == "load_image":
+            self.frame[op["frame"]].update(image=self.pool[op["image"]]["pixels"].copy(), cleared=False, last="load")
+        elif kind == "download":
+            return [self.frame[op["frame"]]["image"]]
+        elif kind in ("set_table", "replace_table"):
+            self.table[op["frame"]] = dict(pixels=self.pool[op["image"]]["pixels"], filter=op["filter"], destroyed=False, index=op["image"])
+        elif kind == "clear_table":
+            self.table[op["frame"]] = None
+        elif kind == "blit":
+            self.blit(op["frame"])
+        elif kind == "blit_mip":
+            assert self.pool[op["image"]]["mip"]
+            self.table[op["frame"]] = dict(pixels=self.pool[op["image"]]["pixels"], filter=op["filter"], destroyed=False, index=op["image"])
+            self.blit(op["frame"])
+        elif kind == "white_paint":  # a white image paint is the solid colour, byte for byte; the table is cleared behind the pass
+            f = self.frame[op["frame"]]
+            last = "painted-cleared" if f["cleared"] else "painted"
+            self.solid_pass(op["frame"], op.get("instances"))
+            f["last"] = last
+        elif kind == "reupload":
+            # crh_scene_upload keeps the table and the association of an existing Scene: instance i of the new Shapes has the paint
+            # association[i] where the association reaches, none beyond it. The paint is white, so the bytes are the solid pass's; whether the
+            # pass is a painted one (the general kernel) follows from the association and the new Shape count: expected_general().
+            f = self.frame[op["frame"]]
+            general = self.expected_general(op)
+            last = ("painted-cleared" if f["cleared"] else "painted") if general else "solid"
+            self.slice = tuple(op["slice"])
+            self.solid_pass(op["frame"], op["instances"])
+            f["last"] = last
+        else:
+            raise AssertionError(kind)
+        return []
+
+    @staticmethod
+    def expected_general(op):
+        """A re-upload's pass is a painted one when an instance below the new Shape count has a paint: the association is
+        [-1] * first + [0] * (length - first)."""
+        n = op["slice"][1] - op["slice"][0]
+        return int(op["assoc_first"] < min(op["assoc_length"], n))
+
+
+def random_texels(rng, how, w, h):
+    if how == "premultiplied":
+        return BM.random_premultiplied(rng, w, h)
+    if how == "straight":  # colours above their alpha: loaded with a clamp by compositing and the colour filter, summed as they are by the blur
+        t = rng.randint(0, 256, (h, w, 4)).astype(np.uint8)
+        t[..., 3] = rng.randint(0, 200, (h, w))
+        t[..., 0] = np.maximum(t[..., 0], np.minimum(255, t[..., 3].astype(int) + 1)).astype(np.uint8)
+        return t
+    if how == "white":
+        return np.full((h, w, 4), 255, dtype=np.uint8)
+    if how == "checker":
+        j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+        return np.repeat(np.where((i + j) % 2 == 0, 255, 0).astype(np.uint8)[:, :, None], 4, axis=2)
+    assert how == "alpha0"
+    t = rng.randint(0, 256, (h, w, 4)).astype(np.uint8)
+    t[..., 3] = 0
+    return t
+
+
+TEXELS = ("premultiplied", "straight", "white", "checker", "alpha0")
+
+
+def generate(seed):
+    """-> (setup, ops): the fixtures of a seed and its op list, which holds every random value the replay needs (texels, matrices, instances).
+    The generator runs the model as it goes: what an op may do depends on what the images and frames hold."""
+    rng = np.random.RandomState(7300 + seed)
+    width, height = int(rng.randint(50, 251)), int(rng.randint(40, 161))
+    width -= 1 if width % 16 == 0 else 0
+    height -= 1 if height % 16 == 0 else 0
+    sc = master_case(seed)
+    n_master = sc["batch"].n_shapes
+
+    def new_slice():
+        a = int(rng.randint(0, n_master - 2))
+        return a, int(rng.randint(a + 2, min(n_master, a + 12) + 1))
+
+    def place(n):
+        t = scenes.place(width, height, rng.uniform(0, width, n), rng.uniform(0, height, n), rng.uniform(0.2, 0.7, n) * min(width, height))
+        c = np.concatenate([rng.uniform(0, 1, (n, 3)), rng.uniform(0.2, 1, (n, 1))], axis=1).astype(np.float32)
+        c[::3, 3] = 1.0
+        return t.astype(np.float32), c
+
+    setup = dict(seed=seed, width=width, height=height, msaa=int(rng.choice([1, 4])), slice=new_slice())
+    model = Model(setup, sc["batch"])
+    ops = []
+    big_blur_left = 1
+
+    def emit(op):
+        model.apply(op)
+        ops.append(op)
+
+    def pick(indices):
+        return indices[int(rng.randint(0, len(indices)))]
+
+    def frame_sized(extra=lambda e: True):
+        return [i for i, e in enumerate(model.pool) if e["pixels"].shape[:2] == (height, width) and extra(e)]
+
+    def blittable(j):
+        """the pool images a blit into frame j may draw now"""
+        over = not model.frame[j]["cleared"]
+        return frame_sized(lambda e: premultiplied(e["pixels"]) and (not over or binary_alpha(e["pixels"])))
+
+    def room():
+        while len(model.pool) >= MAX_POOL:
+            emit(dict(kind="destroy_image", image=int(rng.randint(0, len(model.pool)))))
+
+    def white_image():
+        return dict(size=(int(rng.randint(1, 10)), int(rng.randint(1, 10))), mip=bool(rng.randint(0, 2)),
+                    matrix=[float(np.float32(v)) for v in rng.uniform(-4, 4, 6) * 10.0 ** rng.randint(-2, 7, 6)],
+                    filter=int(rng.choice([NEAREST, LINEAR, NEAREST | MIPMAP, LINEAR | MIPMAP])), spreads=[int(v) for v in rng.randint(0, 3, 2)])
+
+    def instances_for(op):
+        if model.instances is None or len(model.instances[0]) != model.slice[1] - model.slice[0] or rng.uniform() < 0.4:
+            op["instances"] = place(model.slice[1] - model.slice[0])
+        return op
+
+    def a_filter():
+        return int(rng.choice([NEAREST, LINEAR])) if setup["msaa"] == 1 else NEAREST  # (a LINEAR sample off the pixel centre mixes texels)
+
+    n_steps = int(rng.randint(40, 61))
+    emit(dict(kind="upload", frame=0, pixels=BM.random_premultiplied(rng, width, height)))  # (the frames show something from the start)
+    emit(instances_for(dict(kind="solid", frame=1)))
+    while len(ops) < n_steps:
+        kind = KINDS[int(rng.choice(len(KINDS), p=np.float64(WEIGHTS) / np.sum(WEIGHTS)))]
+        j = int(rng.randint(0, 2))
+        pool = model.pool
+        if kind == "create" or (not pool and kind in ("blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image")):
+            room()
+            w, h = (width, height) if rng.uniform() < 0.5 else (int(rng.randint(1, 41)), int(rng.randint(1, 31)))
+            how = TEXELS[int(rng.randint(0, len(TEXELS)))]
+            emit(dict(kind="create", how=how, pixels=random_texels(rng, how, w, h)))
+        elif kind == "snapshot":
+            room()
+            if model.frame[j]["cleared"] and rng.uniform() < 0.8:
+                j = 1 - j  # (mostly of a frame that shows something)
+            emit(dict(kind="snapshot", frame=j, after=model.frame[j]["last"]))
+        elif kind == "blur":
+            room()
+            wide = [k for k, e in enumerate(pool) if e["pixels"].shape[1] > 256]  # (k_image_blur_h's row segment is 256 texels)
+            i = pick(wide) if wide and rng.uniform() < 0.8 else int(rng.randint(0, len(pool)))
+            h, w = pool[i]["pixels"].shape[:2]
+            sigma = [float(rng.choice(SIGMAS)), float(rng.choice(SIGMAS))]
+            edge = int(rng.randint(0, 4))
+            big = bool(big_blur_left and max(w, h) <= 260 and rng.uniform() < 0.4)
+            if big:  # once per seed: the largest radius, 192, on one axis
+                sigma[int(rng.uniform() < 0.4)] = 64.0
+                edge = BM.TRANSPARENT if rng.uniform() < 0.6 else edge
+                big_blur_left -= 1
+            elif edge == BM.TRANSPARENT and (w + 2 * BM.radius_of(sigma[0]) > MAX_SIDE or h + 2 * BM.radius_of(sigma[1]) > MAX_SIDE):
+                edge = int(rng.randint(1, 4))
+            if edge == BM.TRANSPARENT and max(w + 2 * BM.radius_of(sigma[0]), h + 2 * BM.radius_of(sigma[1])) > 16384:
+                continue  # (the library refuses it)
+            emit(dict(kind="blur", image=i, sigma=sigma, edge=edge, width=w))
+            if big and pool[-1]["pixels"].shape[1] > 256 and rng.uniform() < 0.7:  # the grown row, wider than k_image_blur_h's segment, blurred along itself
+                room()
+                emit(dict(kind="blur", image=len(pool) - 1, sigma=[float(rng.choice(SIGMAS[2:])), float(rng.choice(SIGMAS))], edge=int(rng.randint(1, 4)), width=pool[-1]["pixels"].shape[1]))
+        elif kind == "composite":
+            room()
+            sized = frame_sized()
+            i = pick(sized) if sized and rng.uniform() < 0.4 else int(rng.randint(0, len(pool)))
+            s = i if rng.uniform() < 0.15 else int(rng.randint(0, len(pool)))
+            w = pool[i]["pixels"].shape[1]
+            emit(dict(kind="composite", image=i, source=s, op=int(rng.randint(0, 13)), mode=int(rng.randint(0, 9)),
+                      opacity=float(rng.choice([0.0, 1.0, rng.uniform(), rng.uniform()], p=[0.15, 0.35, 0.25, 0.25])), offset=[int(v) for v in (rng.randint(-w - 3, w + 4, 2) if rng.uniform() < 0.3 else rng.randint(-(w // 4) - 1, w // 4 + 2, 2))], width=w))
+        elif kind == "color_filter":
+            room()
+            sized = frame_sized(lambda e: premultiplied(e["pixels"]))
+            how = rng.uniform()
+            if how < 0.3 and sized:  # the threshold on alpha: an image a blit may draw over content
+                i, matrix, tables = pick(sized), None, threshold_tables()
+            else:
+                i = int(rng.randint(0, len(pool)))
+                listed = FM.matrices()
+                matrix = listed[int(rng.randint(0, len(listed)))][1] if how < 0.7 else [float(np.float32(v)) for v in rng.uniform(-FM.MATRIX_MAX, FM.MATRIX_MAX, 20) * rng.choice([1.0, 0.1], 20)]
+                tables = rng.randint(0, 256, 1024).astype(np.uint8) if rng.uniform() < 0.4 else None
+            emit(dict(kind="color_filter", image=i, matrix=matrix, tables=tables, width=pool[i]["pixels"].shape[1]))
+        elif kind == "mipmaps":
+            emit(dict(kind="mipmaps", image=int(rng.randint(0, len(pool)))))
+        elif kind == "check_image":
+            deep = [i for i, e in enumerate(pool) if e["depth"] >= 3]
+            i = pick(deep) if deep and rng.uniform() < 0.6 else int(rng.randint(0, len(pool)))
+            emit(dict(kind="check_image", image=i, depth=pool[i]["depth"]))
+        elif kind == "destroy_image":
+            named = [t["index"] for t in model.table if t is not None and t["index"] is not None]
+            i = pick(named) if named and rng.uniform() < 0.6 else int(rng.randint(0, len(pool)))
+            emit(dict(kind="destroy_image", image=i))
+        elif kind == "clear":
+            emit(dict(kind="clear", frame=j))
+        elif kind == "solid":
+            emit(instances_for(dict(kind="solid", frame=j)))
+        elif kind == "upload":
+            emit(dict(kind="upload", frame=j, pixels=BM.random_premultiplied(rng, width, height)))
+        elif kind == "load_image":
+            sized = frame_sized(lambda e: premultiplied(e["pixels"]))
+            if not sized:
+                continue
+            emit(dict(kind="load_image", frame=j, image=pick(sized)))
+        elif kind == "download":
+            if model.frame[j]["cleared"] and rng.uniform() < 0.7:
+                j = 1 - j
+            emit(dict(kind="download", frame=j))
+        elif kind in ("set_table", "replace_table"):
+            sized = frame_sized(lambda e: premultiplied(e["pixels"]))
+            if not sized or (model.table[j] is None) != (kind == "set_table"):
+                continue
+            binary = [i for i in sized if binary_alpha(pool[i]["pixels"])]
+            emit(dict(kind=kind, frame=j, image=pick(binary) if binary and rng.uniform() < 0.5 else pick(sized), filter=a_filter()))
+        elif kind == "clear_table":
+            if model.table[j] is not None:
+                emit(dict(kind="clear_table", frame=j))
+        elif kind == "blit":
+            if model.table[j] is None:
+                sized = frame_sized(lambda e: premultiplied(e["pixels"]))
+                if not sized:
+                    continue
+                emit(dict(kind="set_table", frame=j, image=pick(sized), filter=a_filter()))
+            table = model.table[j]
+            if table["index"] is not None and rng.uniform() < 0.3:
+                emit(dict(kind="destroy_image", image=table["index"]))  # the table keeps the pixels
+            if not model.frame[j]["cleared"] and not (binary_alpha(table["pixels"]) and rng.uniform() < 0.8):
+                emit(dict(kind="clear", frame=j))
+            emit(dict(kind="blit", frame=j, destroyed=table["destroyed"], over=not model.frame[j]["cleared"]))
+        elif kind == "blit_mip":
+            if not model.frame[j]["cleared"] and rng.uniform() < 0.5:
+                emit(dict(kind="clear", frame=j))
+            usable = blittable(j)
+            if not usable:
+                continue
+            i = pick(usable)
+            if not pool[i]["mip"]:
+                emit(dict(kind="mipmaps", image=i))
+            emit(dict(kind="blit_mip", frame=j, image=i, filter=a_filter() | MIPMAP))
+        elif kind == "white_paint":
+            if rng.uniform() < 0.4 and not model.frame[j]["cleared"]:
+                emit(dict(kind="clear", frame=j))
+            emit(instances_for(dict(kind="white_paint", frame=j, white=white_image())))
+            emit(instances_for(dict(kind="solid", frame=int(rng.randint(0, 2)), after_white=True)))
+        else:
+            assert kind == "reupload"
+            a, b = model.slice if rng.uniform() < 0.4 else new_slice()
+            length = int(rng.randint(1, b - a + 5))
+            emit(dict(kind="reupload", frame=j, slice=(a, b), assoc_length=length, assoc_first=int(rng.randint(0, length + 1)), white=white_image(), instances=place(b - a)))
+    for j in range(2):
+        emit(dict(kind="download", frame=j))
+    for i in range(len(model.pool)):
+        emit(dict(kind="check_image", image=i, depth=model.pool[i]["depth"]))
+    return setup, ops
+
+
+def replay_model(setup, ops):
+    """-> [(op index, [expected arrays])] of every op that checks something."""
+    model = Model(setup)
+    out = []
+    for k, op in enumerate(ops):
+        expect = model.apply(op)
+        if expect:
+            out.append((k, expect))
+    return out

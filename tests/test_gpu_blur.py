@@ -72,6 +72,35 @@ def test_the_blur_equals_the_integer_model(size, edge, sigmas, renderer, no_pins
     assert np.array_equal(source.download_level(0), pixels)
 
 
+def saturated_pixels(kind, w, h):
+    """All 255, or a checker of period 1 of (0, 0, 0, 0) and (255, 255, 255, 255): the inputs that take the 32-bit sums of both kernels to their
+    bounds (k_image_blur_h: 65536 * 255; k_image_blur_v: 65536 * 65280) and, for the checker, make every lane alternate between 0 and the bound."""
+    if (kind, w, h) not in _pixels:
+        j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+        on = np.ones((h, w), dtype=bool) if kind == "white" else (i + j) % 2 == 0
+        _pixels[(kind, w, h)] = np.repeat(np.where(on, 255, 0).astype(np.uint8)[:, :, None], 4, axis=2)
+        _pixels[(kind, w, h)].setflags(write=False)
+    return _pixels[(kind, w, h)]
+
+
+@pytest.mark.parametrize("sigmas", [(64.0, 64.0), (64.0, 0.0), (0.0, 64.0)], ids=["64-64", "64-0", "0-64"])
+@pytest.mark.parametrize("edge", EDGES, ids=[e.name for e in EDGES])
+@pytest.mark.parametrize("size", [(70, 300), (300, 70)], ids=["70x300", "300x70"])
+@pytest.mark.parametrize("kind", ["white", "checker"])
+def test_a_saturated_image_at_the_largest_radius(kind, size, edge, sigmas, renderer, no_pins):
+    """The taps of an axis sum to exactly 65536, so an all-255 image stays all 255 under every edge that reads texels of the image only; under
+    TRANSPARENT, and for the checker under every edge, the integer model says what the partial sums round to."""
+    pixels = saturated_pixels(kind, *size)
+    expect, (rx, ry) = expect_of(pixels, *sigmas, edge)
+    grown = edge == BlurEdge.Transparent
+    assert (rx, ry) == tuple(192 if s else 0 for s in sigmas)
+    if kind == "white" and not grown:
+        assert (expect == 255).all()
+    else:
+        assert ((expect > 0) & (expect < 255)).mean() > 0.2  # (partial sums: the rounding decides)
+    check(Image(renderer, pixels).blur(*sigmas, edge), expect, (rx, ry) if grown else (0, 0), (kind, size, edge.name, sigmas))
+
+
 @pytest.mark.parametrize("edge", [BlurEdge.Reflect, BlurEdge.Pad], ids=["Reflect", "Pad"])
 def test_the_widest_index_range(edge, renderer, no_pins):
     pixels = pixels_of(16384, 1)

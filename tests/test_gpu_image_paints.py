@@ -359,3 +359,66 @@ def test_two_slabs_of_tile_rows_equal_the_whole_image_painted_frame(no_pins):
     whole, upper, lower = rows(0, SIZE), rows(0, 64), rows(64, SIZE)
     assert (whole[..., 3] > 0).mean() > 0.3
     assert np.array_equal(upper[:64], whole[:64]) and np.array_equal(lower[64:], whole[64:]) and not upper[64:].any() and not lower[:64].any()
+
+
+# ---------------------------------------------------------------- 11. the coordinate rule at its ends: NaN -> 0, the clamp to +-2^24, the wrap of what is left
+
+def blit_rectangle(r, size):
+    """The Scene and the transform of _blit without a table: path coordinates = pixel coordinates, the rectangle covers the frame."""
+    scene = R.Scene(r, batch_from_shapes([([], [Path.from_rect((size / 2.0, size / 2.0), (size / 2.0, size / 2.0))])]))
+    t = np.zeros(16, dtype=np.float32)
+    t[0], t[5], t[10], t[15], t[12], t[13] = 2.0 / size, -2.0 / size, 1.0, 1.0, -1.0, 1.0
+    return scene, t.reshape(1, 16), np.float32([[1.0, 1.0, 1.0, 1.0]])
+
+
+def differing(got, expect):
+    bad = (got != expect).any(axis=2)
+    return f"{int(bad.sum())} of {bad.size} pixels differ, first at (row, column) {tuple(np.argwhere(bad)[0])}" if bad.any() else None
+
+
+@pytest.mark.parametrize("spreads", IM.EXTREME_SPREADS, ids=[f"{a.name}-{b.name}" for a, b in IM.EXTREME_SPREADS])
+@pytest.mark.parametrize("filter", FILTERS, ids=["nearest", "linear"])
+def test_coordinates_at_and_beyond_the_clamp_read_the_texel_the_rule_names(filter, spreads, no_pins):
+    """image_paint_model.extreme_matrices: offsets next to 2^23, at 2^24 and beyond it, 3e38, products that overflow to inf, on either axis
+    and on both. The expectation is the header's rule evaluated exactly (tests/test_image_paints_cpu.py holds it stable against an f32 error
+    of the position), so the comparison is of bytes. Every index is formed by image_wrap from an int of magnitude <= 2^24 + 1."""
+    size = IM.EXTREME_SIZE
+    r = R.Renderer(R.Configuration(), device=0)
+    pixels = IM.random_image(np.random.RandomState(5), *IM.EXTREME_IMAGE)
+    image = Image(r, pixels)
+    scene, t, white = blit_rectangle(r, size)
+    frame = R.Frame(r, size, size)
+    for name, matrix in IM.extreme_matrices():
+        scene.set_paints([ImagePaint(image, matrix, filter, *spreads)], [0])
+        frame.clear()
+        scene.render(frame, t, white)
+        what = differing(frame.download(), IM.extreme_expectation(pixels, matrix, filter, *spreads))
+        assert what is None, f"{name} {matrix}: {what}"
+        assert last_pass(frame)["raster"] == "ops"
+
+
+@pytest.mark.parametrize("filter", [Filter.Nearest, Filter.LinearMipmap], ids=["nearest", "linear-mipmap"])
+def test_a_white_image_under_a_camera_through_the_near_plane_equals_the_solid_blob(filter, no_pins):
+    """The projective coordinates divide by a W that goes through 0 across the frame: whatever (u, v) comes of it — inf, NaN — is a texel of
+    the all-255 image, so the cover is the solid colour's, byte for byte the oracle's."""
+    from oracle.binding import Oracle, render_pass
+    from test_perspective_ground_truth import CASES, blob, camera
+    size = 96
+    m = np.float32(camera(**CASES["through_the_near_plane"])).reshape(1, 16)
+    colour = np.float32([[1.0, 0.9, 0.8, 0.9]])
+    batch = batch_from_shapes([([], [blob()])])
+    r = R.Renderer(R.Configuration(), device=0)
+    white = Image(r, np.full((5, 8, 4), 255, dtype=np.uint8))
+    white.generate_mipmaps()
+    scene = R.Scene(r, batch)
+    scene.set_paints([ImagePaint(white, (3.0, 1.0, 4.0, -1.0, 3.0, 4.0), filter, Spread.Repeat, Spread.Reflect)], [0])
+    frame = R.Frame(r, size, size)
+    frame.clear()
+    scene.render(frame, m, colour)
+    tap = last_pass(frame)
+    assert tap["general"] == 1 and tap["raster"] == "ops", tap
+    draws = [(0, 0, op, 0, 0) for op in (R.RenderOperation.Stencil, R.RenderOperation.Color)]
+    expect, _ = render_pass(Oracle(batch), size, size, 1, 4, 4, 0, m, colour, draws)
+    assert 400 < (expect[..., 3] > 0).sum() < size * size - 400
+    what = differing(frame.download(), expect)
+    assert what is None, what

@@ -359,3 +359,58 @@ def test_only_a_pass_that_draws_a_flagged_image_paint_changes_what_is_launched(n
     scene.set_paints([], [])
     image, tap = plain()
     assert tap == tap_solid and np.array_equal(image, solid)
+
+
+# ---------------------------------------------------------------- 10. lod at its ends: rho huge or +inf, rho = 0
+
+@pytest.mark.parametrize("spreads", IM.EXTREME_SPREADS, ids=[f"{a.name}-{b.name}" for a, b in IM.EXTREME_SPREADS])
+@pytest.mark.parametrize("filter", MIP_FILTERS, ids=["nearest", "linear"])
+def test_lod_at_its_ends_reads_the_last_level_or_the_base_filter(filter, spreads, no_pins):
+    """m0 = m4 = 1e30 or 3e38: rho^2 overflows to +inf in f32, lod = L - 1 and f = 0, every pixel holds the bytes of the 1 x 1 level whatever
+    the clamped (u, v) wrap to. m0 = m1 = m3 = m4 = 0: rho = 0, lod = 0, every pixel is texel (wrap(floor(m2)), wrap(floor(m5))) of level 0.
+    The extreme matrices of the plain filters have rho = 1 or beyond on an axis that is constant: those with lod = 0 must give the plain
+    filter's bytes. A Jacobian column that is NaN: the placement turned by 45 degrees with dX/dsx = dY/dsx = 2, so that m0 = 3e38, m1 = -3e38
+    give du/dsx = inf - inf (the library is built without contraction: both products are rounded) while du/dsy = -inf; the NaN column wins,
+    lod = 0. There X >= 272 on the whole frame, u = fma(Y, m1, +inf) = +inf is clamped to 2^24, v = 1.5: one texel of level 0."""
+    from test_gpu_image_paints import blit_rectangle, differing
+    size = IM.EXTREME_SIZE
+    r = R.Renderer(R.Configuration(), device=0)
+    pixels = IM.random_image(np.random.RandomState(5), *IM.EXTREME_IMAGE)
+    chain = MM.chain(pixels)
+    assert len(chain) == 4 and chain[-1].shape == (1, 1, 4)
+    image = Image(r, pixels)
+    image.generate_mipmaps()
+    scene, t, white = blit_rectangle(r, size)
+    frame = R.Frame(r, size, size)
+
+    def drawn(matrix):
+        scene.set_paints([ImagePaint(image, matrix, filter, *spreads)], [0])
+        frame.clear()
+        scene.render(frame, t, white)
+        assert last_pass(frame)["raster"] == "ops"
+        return frame.download()
+    for big in (1e30, 3e38):
+        what = differing(drawn((big, 0.0, 0.0, 0.0, big, 0.0)), np.broadcast_to(chain[-1], (size, size, 4)))
+        assert what is None, f"m0 = m4 = {big}: {what}"
+    for m2, m5 in ((3.5, 1.5), (-1027.5, 16777216.0), (3e38, -3e38)):
+        matrix = (0.0, 0.0, m2, 0.0, 0.0, m5)
+        expect = IM.extreme_expectation(pixels, matrix, Filter(int(filter) & 1), *spreads)
+        assert len(np.unique(expect.reshape(-1, 4), axis=0)) == 1
+        what = differing(drawn(matrix), expect)
+        assert what is None, f"rho = 0 at {m2}, {m5}: {what}"
+    for name, matrix in IM.extreme_matrices():  # lod = 0 where both columns of J have a norm of at most 1: the plain filter's bytes
+        columns = (np.hypot(matrix[0], matrix[3]), np.hypot(matrix[1], matrix[4]))
+        if max(columns) <= 1.0:
+            what = differing(drawn(matrix), IM.extreme_expectation(pixels, matrix, Filter(int(filter) & 1), *spreads))
+            assert what is None, f"{name}: {what}"
+    turned = R.Scene(r, batch_from_shapes([([], [Path.from_rect((400.0, 128.0), (200.0, 200.0))])]))
+    k, ox, oy = 0.25, -100.0, 100.0  # pixel = (k (X + Y) + ox, k (Y - X) + oy): X = 2 (sx - sy + 200), Y = 2 (sx + sy), exact
+    t2 = np.zeros(16, dtype=np.float32)
+    t2[0], t2[4], t2[12], t2[1], t2[5], t2[13], t2[10], t2[15] = 2 * k / size, 2 * k / size, 2 * ox / size - 1.0, 2 * k / size, -2 * k / size, 1.0 - 2 * oy / size, 1.0, 1.0
+    turned.set_paints([ImagePaint(image, (3e38, -3e38, 0.0, 0.0, 0.0, 1.5), filter, *spreads)], [0])
+    frame.clear()
+    turned.render(frame, t2.reshape(1, 16), white)
+    texel = pixels[int(IM.wrap(np.int64(1), 5, spreads[1])), int(IM.wrap(np.int64(2 ** 24), 8, spreads[0]))]
+    assert not np.array_equal(texel, chain[-1][0, 0])
+    what = differing(frame.download(), np.broadcast_to(texel, (size, size, 4)))
+    assert what is None, f"a NaN column of J: {what}"

@@ -203,3 +203,41 @@ def test_the_model_alone_passes_its_caps_on_the_cases_with_their_own_expectation
     for f in (Filter.Nearest, Filter.Linear):
         _, _, src, seam, extra = IM.stroke_case(f)
         assert seam.mean() <= 0.02 and extra < 0.25 / 255.0 and (src >= 0).all() and (src <= 1).all()
+
+
+# ---------------------------------------------------------------- the coordinate rule at its ends (tests/test_gpu_image_paints.py, test_gpu_mipmaps.py)
+
+def test_the_extreme_matrices_have_exact_and_stable_expectations():
+    """What the GPU tests compare byte for byte must not hang on a rounding: every product-sum of the expectation is exact in float64 (fma32
+    asserts it) and rounded to f32 once; every index and fraction stays what it is when X and Y move by a relative 2^-20 in any of the four
+    directions; every fraction is 0, so a LINEAR value is one texel's codes; and the cases reach what they are named after."""
+    import image_paint_model as IM
+    names = [n for n, _ in IM.extreme_matrices()]
+    assert len(names) == len(set(names)) == 21
+    e = 2.0 ** -20
+    size = IM.EXTREME_SIZE
+    Y, X = np.meshgrid(np.arange(size) + 0.5, np.arange(size) + 0.5, indexing="ij")
+    reached = {}
+    for name, matrix in IM.extreme_matrices():
+        u, v = IM.extreme_uv(matrix, X, Y)
+        raw_u = IM.fma32(Y, np.float32(matrix[1]), IM.fma32(X, np.float32(matrix[0]), np.float32(matrix[2])))
+        reached[name] = (float(np.abs(u).max()), float(np.abs(v).max()), bool(np.isinf(raw_u).any()))
+        for filter in (Filter.Nearest, Filter.Linear):
+            for spreads in IM.EXTREME_SPREADS:
+                taps = IM.extreme_taps(matrix, filter, *spreads)
+                assert not taps[4].any() and not taps[5].any(), (name, filter)
+                for sx in (1.0 - e, 1.0 + e):
+                    for sy in (1.0 - e, 1.0 + e):
+                        moved = IM.extreme_taps(matrix, filter, *spreads, scale=(sx, sy), exact=False)
+                        assert all(np.array_equal(a, b) for a, b in zip(taps, moved)), (name, filter, spreads, sx, sy)
+    assert reached["u:2^23-32"][0] < 2.0 ** 23 and reached["u:2^23-32"][0] > 2.0 ** 23 - 33
+    for name in ("2^24", "-2^24", "2^24+64", "-(2^24+64)", "3e38", "-3e38", "overflow", "inf-and-back"):
+        assert reached["u:" + name][0] == 2.0 ** 24 and reached["v:" + name][1] == 2.0 ** 24, name
+    assert reached["u:overflow"][2] and reached["u:inf-and-back"][2] and not reached["u:2^24+64"][2]
+    # 2^23 and 2^24 differ modulo the height and twice the height: a clamp at another power of two shows
+    assert (2 ** 23) % 5 != (2 ** 24) % 5 and (2 ** 23) % 10 != (2 ** 24) % 10
+    # ... and the expectation shows more than one texel per case: the wrap is exercised, not a constant
+    pixels = IM.random_image(np.random.RandomState(5), *IM.EXTREME_IMAGE)
+    for name, matrix in IM.extreme_matrices():
+        expect = IM.extreme_expectation(pixels, matrix, Filter.Linear, Spread.Repeat, Spread.Reflect)
+        assert len(np.unique(expect.reshape(-1, 4), axis=0)) >= 5, name
