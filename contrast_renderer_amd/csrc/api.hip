@@ -3225,6 +3225,23 @@ crh_status crh_internal_frame_touched(crh_frame* f, void* stream, int written) {
     }
     return CRH_OK;
 }
+// The exchange is about to read (will_write = 0) or write (1) the frame's pixels with work enqueued on `stream`: ordered ON THE DEVICE behind
+// what another exchange stream — another rank of a loopback group, another communicator — last wrote there, and a write behind its last
+// read as well. No host wait. (crh_internal_frame_info orders behind these events only for a cleared frame, and on the renderer's stream.)
+// The limit: a frame has ONE read event, recorded again by every reader, so a write is ordered behind the LAST stream that read the frame.
+// Earlier readers are covered where something else orders them: the packing of an exchange is complete on the host when the exchange returns
+// (phase_plan waits behind it), and the streams of one loopback group wait for each other at the end of an exchange. The slab copies of
+// crh_frame_gather_slabs are not waited for: a layer gathered by one communicator, then read by a second one, then written by the second
+// one's rank 0 is ordered behind the second reader only.
+crh_status crh_internal_frame_order(crh_frame* f, void* stream, int will_write) {
+    if (!f) return CRH_ERR_INVALID_ARGUMENT;
+    if (will_write) {
+        HIP_TRY(order_after_external(f, static_cast<hipStream_t>(stream)));
+    } else if (f->ext_write_set) {
+        HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(stream), f->ext_write, 0));
+    }
+    return CRH_OK;
+}
 // The entries per tile of the frame's last pass, on the device, when a tile without entries is a transparent tile (NULL otherwise: the
 // exchange then looks at the pixels). Valid after crh_internal_frame_info (which settles the pass).
 crh_status crh_internal_frame_tile_counts(crh_frame* f, const uint32_t** counts, uint32_t* n_tiles, uint32_t* first_tile, uint32_t* end_tile) {

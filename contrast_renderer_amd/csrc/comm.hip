@@ -39,6 +39,7 @@ void set_last_error(const std::string& text);
 extern "C" crh_status crh_internal_frame_geometry(crh_frame* f, uint32_t* width, uint32_t* height, uint32_t* format, int* device);
 extern "C" crh_status crh_internal_frame_info(crh_frame* f, void** rgba8, uint32_t* width, uint32_t* height, int* device);
 extern "C" crh_status crh_internal_frame_touched(crh_frame* f, void* stream, int written);
+extern "C" crh_status crh_internal_frame_order(crh_frame* f, void* stream, int will_write);
 extern "C" crh_status crh_internal_frame_slab(crh_frame* f, uint32_t* row_begin, uint32_t* row_end);
 extern "C" crh_status crh_internal_frame_tile_counts(crh_frame* f, const uint32_t** counts, uint32_t* n_tiles, uint32_t* first_tile, uint32_t* end_tile);
 extern "C" int crh_internal_renderer_device(crh_renderer* r);
@@ -508,6 +509,8 @@ crh_status phase_pack(crh_comm* c, crh_frame* layer, crh_frame* result) {
         set_last_error("crh_frame_exchange: rank " + std::to_string(c->rank) + " exchanges a BGRA or sRGB frame");
     }
     HIP_TRY(hipSetDevice(c->device));
+    // another communicator's stream may have written these pixels — rank 0's unpack of the exchange before, a second group —: behind it, on the device
+    if ((st = crh_internal_frame_order(layer, c->stream, 0)) != CRH_OK) return st;
     begin_phase(c, kPack);
     uint32_t* header = c->host_header.as<uint32_t>(); // (the previous exchange's copy of it was waited for with its bitmaps)
     header[0] = kMagic, header[1] = w, header[2] = h | (format << 24), header[3] = (uint32_t)layer_status;
@@ -629,6 +632,7 @@ crh_status phase_unpack(crh_comm* c, crh_frame* result) {
     void* pixels = nullptr;
     if ((st = crh_internal_frame_info(result, &pixels, &w, &h, &device)) != CRH_OK) return st; // what the frame showed so far is settled (and discarded)
     HIP_TRY(hipSetDevice(c->device));
+    if ((st = crh_internal_frame_order(result, c->stream, 1)) != CRH_OK) return st; // behind the last read and the last write another stream made of this frame (the limit: crh_internal_frame_order)
     begin_phase(c, kUnpack);
     hipLaunchKernelGGL(k_unpack_tiles, dim3((c->n_tiles + 3u) / 4u), dim3(256), 0, c->stream, static_cast<uint32_t*>(pixels), w, h, c->tiles_x, c->n_tiles,
                        c->or_bitmap.as<uint32_t>(), c->or_prefix.as<uint32_t>(), c->gathered.as<uint32_t>());
@@ -918,6 +922,8 @@ crh_status crh_frame_gather_slabs(crh_comm* c, crh_frame* layer, crh_frame* resu
     void *pixels = nullptr, *out = nullptr;
     if (mine == CRH_OK) mine = crh_internal_frame_info(layer, &pixels, &w, &h, &device); // settles the layer: its pixels are final
     if (mine == CRH_OK && result) mine = crh_internal_frame_info(result, &out, &rw, &rh, &device);
+    if (mine == CRH_OK) mine = crh_internal_frame_order(layer, c->stream, 0); // the transfers below run behind what another communicator's stream wrote into the layer,
+    if (mine == CRH_OK && result) mine = crh_internal_frame_order(result, c->stream, 1); // ... and read from or wrote into the result frame
     if (mine == CRH_OK) { // the layer draws exactly this rank's slab of rows (crh_frame_set_tile_rows(crh_comm_slab_rows(...))): anything else would gather transparent or partial rows
         uint32_t row0 = 0, row1 = 0, slab0 = 0, slab1 = 0;
         mine = crh_internal_frame_slab(layer, &slab0, &slab1);
@@ -1012,6 +1018,8 @@ crh_status crh_comm_local_gather_slabs(crh_comm* rank0, crh_frame* const* layers
     for (uint32_t k = 0; k < world; ++k) { // every rank "sends" on its own stream; rank 0's stream is where the result is complete
         crh_comm* c = g[k];
         c->timed = false;
+        // this rank's copy runs behind what another communicator's stream wrote into its layer, and read from or wrote into the result frame
+        if ((st = crh_internal_frame_order(layers[k], c->stream, 0)) != CRH_OK || (st = crh_internal_frame_order(result, c->stream, 1)) != CRH_OK) return st;
         mark_all_phases(c);
         begin_phase(c, kGather);
         size_t off = 0, bytes = 0;

@@ -773,7 +773,9 @@ crh_status crh_comm_unique_id(void* id128);
 crh_status crh_comm_create(crh_renderer* renderer, uint32_t rank, uint32_t world, const void* id128, crh_comm** out);
 void crh_comm_destroy(crh_comm* comm);
 /* collective: `layer` = this rank's frame; `result` = the frame that receives the image on rank 0, NULL on every other rank.
- * Waits for the last pass into `layer` only; runs on a stream of its own, so the renderer may already be drawing the next step. */
+ * Waits for the last pass into `layer` only; runs on a stream of its own, so the renderer may already be drawing the next step.
+ * `result` may be one of the layers (here and in crh_comm_local_exchange, at any rank): the image is the composite of the layers as they
+ * were when the call was made, and the frame shows it afterwards. */
 crh_status crh_frame_exchange(crh_comm* comm, crh_frame* layer, crh_frame* result);
 /* The other split of SURVEY.md §8(e) — shard by TILE instead of by path index (no such component upstream either; it mirrors what a wgpu
  * scissor rectangle on renderer.rs:267-355's passes would do): the passes into `frame` draw the tile rows that cover the pixel rows
