@@ -313,6 +313,9 @@ def load_library():
         "crh_color_filter_validate": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_uint8)]),
         "crh_color_filter_texels": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_uint8), V, C.c_uint64, V]),
         "crh_image_color_filter": (C.c_int, [V, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(V)]),
+        "crh_morphology_size": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "crh_morphology_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, V]),
+        "crh_image_morphology": (C.c_int, [V, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

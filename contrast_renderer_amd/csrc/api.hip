@@ -17,6 +17,7 @@
 #include "color_filter.hpp"
 #include "composite.hpp"
 #include "launch.hpp"
+#include "morphology.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
 
@@ -3119,6 +3120,93 @@ crh_status crh_image_color_filter(const crh_image* src, const float* matrix, con
     }
     ok = hip_ok(r->sync(), "sync(colour filter)") && ok; // (also behind a failure: `tables` is read by the copy until the stream has drained)
     if (tables_dev) (void)hipFree(tables_dev);
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+namespace {
+static_assert(CRH_MAX_MORPHOLOGY_RADIUS == kMorphologyMaxRadius && CRH_MORPHOLOGY_ERODE == kMorphologyErode && CRH_MORPHOLOGY_DILATE == kMorphologyDilate &&
+                  CRH_BLUR_EDGE_TRANSPARENT == kMorphologyTransparent,
+              "morphology.hpp's limit, operators and edge are the header's");
+crh_status morphology_error(const char* what) {
+    g_error = std::string("crh_morphology_size: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+// validates, and gives the size of the result: the one check of crh_morphology_size, crh_morphology_texels and crh_image_morphology
+crh_status morphology_size(uint32_t width, uint32_t height, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, uint32_t* out_width, uint32_t* out_height) {
+    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return morphology_error("width and height lie in [1, 16384]");
+    if (op > CRH_MORPHOLOGY_DILATE) return morphology_error("op is above CRH_MORPHOLOGY_DILATE");
+    if (edge > CRH_BLUR_EDGE_REFLECT) return morphology_error("edge is above CRH_BLUR_EDGE_REFLECT");
+    if (radius_x > CRH_MAX_MORPHOLOGY_RADIUS || radius_y > CRH_MAX_MORPHOLOGY_RADIUS) return morphology_error("a radius exceeds CRH_MAX_MORPHOLOGY_RADIUS");
+    const bool grows = morphology_grows(op, edge);
+    const uint32_t w = width + (grows ? 2u * radius_x : 0u), h = height + (grows ? 2u * radius_y : 0u);
+    if (w > kMaxImageSize || h > kMaxImageSize) {
+        g_error = "crh_morphology_size: a side of the grown result exceeds 16384";
+        return CRH_ERR_UNSUPPORTED;
+    }
+    *out_width = w, *out_height = h;
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_morphology_size(uint32_t width, uint32_t height, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, uint32_t* out_width, uint32_t* out_height) {
+    if (!out_width || !out_height) return morphology_error("a null argument");
+    uint32_t w = 0u, h = 0u;
+    const crh_status st = morphology_size(width, height, op, radius_x, radius_y, edge, &w, &h);
+    if (st != CRH_OK) return st;
+    *out_width = w, *out_height = h;
+    return CRH_OK;
+}
+crh_status crh_morphology_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, void* out_rgba8) {
+    if (!rgba8 || !out_rgba8) return morphology_error("a null argument");
+    if (rgba8 == out_rgba8) return morphology_error("out_rgba8 is rgba8");
+    uint32_t w = 0u, h = 0u;
+    const crh_status st = morphology_size(width, height, op, radius_x, radius_y, edge, &w, &h);
+    if (st != CRH_OK) return st;
+    if (op == CRH_MORPHOLOGY_DILATE) morphology_run<true>(static_cast<const uint8_t*>(rgba8), width, height, radius_x, radius_y, edge, static_cast<uint8_t*>(out_rgba8));
+    else morphology_run<false>(static_cast<const uint8_t*>(rgba8), width, height, radius_x, radius_y, edge, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_morphology(const crh_image* src, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, crh_image** out) {
+    if (!src || !src->renderer || !out) return morphology_error("a null argument");
+    uint32_t out_w = 0u, out_h = 0u;
+    crh_status st = morphology_size(src->width, src->height, op, radius_x, radius_y, edge, &out_w, &out_h);
+    if (st != CRH_OK) return st;
+    const bool grows = morphology_grows(op, edge);
+    crh_renderer* r = src->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    st = new_image(r, out_w, out_h, &image);
+    if (st != CRH_OK) return st;
+    const uint32_t* from = static_cast<const uint32_t*>(src->pixels->p);
+    uint32_t* to = static_cast<uint32_t*>(image->pixels->p);
+    // A zero radius skips its pass (and does not grow its axis): no pass is a copy, one pass goes from the source to the result, and only two
+    // passes need the intermediate — packed RGBA8, the result's width and the source's height.
+    void* tmp = nullptr;
+    bool ok = true;
+    if (radius_x == 0u && radius_y == 0u) {
+        ok = hip_ok(hipMemcpyAsync(to, from, (size_t)out_w * out_h * 4, hipMemcpyDeviceToDevice, r->stream), "hipMemcpyAsync(morphology copy)");
+    } else if (radius_y == 0u) {
+        launch_image_morph_h(from, src->width, src->height, to, out_w, op, radius_x, grows ? radius_x : 0u, edge, r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_morph_h");
+    } else if (radius_x == 0u) {
+        launch_image_morph_v(from, src->height, to, out_w, out_h, op, radius_y, grows ? radius_y : 0u, edge, r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_morph_v");
+    } else {
+        ok = hip_ok(hipMalloc(&tmp, (size_t)out_w * src->height * 4), "hipMalloc(morphology intermediate)");
+        if (ok) {
+            launch_image_morph_h(from, src->width, src->height, static_cast<uint32_t*>(tmp), out_w, op, radius_x, grows ? radius_x : 0u, edge, r->stream);
+            ok = hip_ok(hipGetLastError(), "k_image_morph_h");
+        }
+        if (ok) {
+            launch_image_morph_v(static_cast<const uint32_t*>(tmp), src->height, to, out_w, out_h, op, radius_y, grows ? radius_y : 0u, edge, r->stream);
+            ok = hip_ok(hipGetLastError(), "k_image_morph_v");
+        }
+    }
+    ok = hip_ok(r->sync(), "sync(morphology)") && ok; // (also behind a failure: the intermediate is read until the stream has drained)
+    if (tmp) (void)hipFree(tmp);
     if (!ok) {
         delete image;
         return CRH_ERR_HIP;

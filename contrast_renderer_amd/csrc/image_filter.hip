@@ -3,6 +3,8 @@
 // texel; k_image_blur_v filters the columns of that into packed RGBA8. Nothing here touches a raster kernel: the wrap helper is this file's own.
 // crh_image_composite: k_image_composite combines two images texel by texel with the rule of composite.hpp.
 // crh_image_color_filter: k_image_color_filter maps every texel of an image with the rule of color_filter.hpp.
+// crh_image_morphology: k_image_morph_h and k_image_morph_v take the per-channel min or max over a rectangle with the rule of morphology.hpp,
+// at a cost per texel that does not grow linearly with the radius.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,6 +12,7 @@
 #include "color_filter.hpp"
 #include "composite.hpp"
 #include "launch.hpp"
+#include "morphology.hpp"
 
 namespace crh {
 namespace {
@@ -276,6 +279,141 @@ void launch_image_color_filter(const uint32_t* src, uint32_t w, uint32_t h, cons
         else CRH_COLOR_FILTER_LAUNCH(1, false);
     }
 #undef CRH_COLOR_FILTER_LAUNCH
+}
+
+namespace {
+constexpr int kMorphSegment = 256; // horizontal: output texels of one row per workgroup, one per lane (k_image_blur_h's segment)
+constexpr int kMorphApron = 192;   // CRH_MAX_MORPHOLOGY_RADIUS: texels staged beyond the segment on either side
+constexpr int kMorphStaged = kMorphSegment + 2 * kMorphApron;                         // 640: the most texels a workgroup stages
+constexpr int kMorphOwned = (kMorphStaged + kMorphSegment - 1) / kMorphSegment;        // 3: staged texels per lane
+constexpr int kMorphColumns = 64;  // vertical: columns per workgroup, one per lane of its single wave
+static_assert(kMorphApron == (int)kMorphologyMaxRadius, "the apron holds the largest radius");
+} // namespace
+
+// Horizontal pass, by doubling in LDS. Grid (ceil(out_w / 256), src_h), 256 lanes: the workgroup stages the L = 256 + 2 radius texels its
+// segment of one row reads, wrapped or zero by the edge, each split into two words of two 16-bit fields (morphology.hpp). Lane l owns the
+// staged texels l, l + 256 and l + 512 and keeps them in registers. Step k turns m_k[i], the extreme of the 2^k texels from i on, into
+// m_{k+1}[i] = op(m_k[i], m_k[i + 2^k]): per owned texel one 8-byte LDS read at lane + const (consecutive lanes, consecutive banks), two
+// v_pk_min_u16 / v_pk_max_u16 and one 8-byte write into the other of two buffers, so a step needs one barrier. After p = floor(log2(2 radius + 1))
+// steps (at most 8) the window of output o0 + l, the staged texels l .. l + 2 radius, is two overlapping spans of 2^p:
+//   out = op(m_p[l], m_p[l + 2 radius + 1 - 2^p]).
+// An m_k[i] whose span would pass the staged texels (i + 2^k > L) keeps its value of the step before; no span that an output reads contains
+// one, because l + 2 radius + 1 <= L. Every LDS index is checked against L, every source address is formed from a wrapped or range-checked
+// column. `origin`: the source column under output column 0 is -origin (the radius for a growing result, else 0). radius >= 1.
+template <bool DILATE>
+__global__ __launch_bounds__(kMorphSegment) void k_image_morph_h(const uint32_t* __restrict__ src, uint32_t src_w, uint32_t* __restrict__ out, uint32_t out_w, uint32_t radius, uint32_t origin,
+                                                                  uint32_t edge) {
+    __shared__ uint2 spans[2][kMorphStaged];
+    const uint32_t j = blockIdx.y, o0 = blockIdx.x * (uint32_t)kMorphSegment, lane = threadIdx.x;
+    const uint32_t* line = src + (size_t)j * src_w;
+    const uint32_t window = 2u * radius + 1u, staged = (uint32_t)kMorphSegment + 2u * radius; // (radius <= kMorphApron: the host refuses more)
+    const int first = (int)o0 - (int)origin - (int)radius; // the source column of staged texel 0
+    MorphologyTexel own[kMorphOwned];
+#pragma unroll
+    for (int t = 0; t < kMorphOwned; ++t) {
+        const uint32_t at = lane + (uint32_t)(t * kMorphSegment);
+        const int i = first + (int)at;
+        uint32_t texel = 0u;
+        if (at < staged) {
+            if (edge != 0u) texel = line[morphology_wrap(i, (int)src_w, edge)];
+            else if ((uint32_t)i < src_w) texel = line[i];
+        }
+        own[t] = morphology_split(texel);
+        if (at < staged) spans[0][at] = make_uint2(own[t].rb, own[t].ga);
+    }
+    __syncthreads();
+    uint32_t span = 1u, from = 0u;
+    for (; 2u * span <= window; span *= 2u, from ^= 1u) { // (wave- and workgroup-uniform: every lane meets every barrier)
+#pragma unroll
+        for (int t = 0; t < kMorphOwned; ++t) {
+            const uint32_t at = lane + (uint32_t)(t * kMorphSegment);
+            if (at + span < staged) {
+                const uint2 next = spans[from][at + span];
+                own[t] = morphology_extreme<DILATE>(own[t], MorphologyTexel{next.x, next.y});
+            }
+            if (at < staged) spans[from ^ 1u][at] = make_uint2(own[t].rb, own[t].ga);
+        }
+        __syncthreads();
+    }
+    const uint32_t o = o0 + lane;
+    if (o >= out_w) return;
+    const uint2 last = spans[from][lane + window - span]; // lane + window - span + span <= 255 + window = staged
+    out[(size_t)j * out_w + o] = morphology_merge(morphology_extreme<DILATE>(own[0], MorphologyTexel{last.x, last.y}));
+}
+
+// Vertical pass, van Herk / Gil-Werman. Grid (ceil(out_w / 64), ceil(out_h / (2 radius + 1))), one wave: lanes run along x, so every global
+// and LDS access of the wave is 64 consecutive words. The workgroup owns the W = 2 radius + 1 output rows j0 .. j0 + W - 1 of 64 columns; its
+// pivot is the input row c under output row j0 + radius. A lane first walks its column UP from c, keeping the running extreme
+// S[k] = op(in[c - k] .. in[c]) and storing each, packed, in LDS (row k, its own word: no lane reads another's, so no barrier); then DOWN
+// from c with the running extreme P = op(in[c] .. in[c + m]): output row j0 + m has the window [c - (2 radius - m), c + m], so
+//   out(j0 + m) = op(S[2 radius - m], P).
+// 4 radius + 1 rows read and 3 (2 radius) + 1 texel comparisons for 2 radius + 1 outputs: two loads, three comparisons (six
+// v_pk_min_u16 / v_pk_max_u16), one LDS write and one LDS read per texel at every radius. ROWS = the rows of S the LDS holds, >= W (the launcher picks
+// the smallest of three instantiations, so a small radius does not pay the LDS of the largest). `in` has in_h rows of out_w texels;
+// `origin`: the input row under output row 0 is -origin. The row index is wave-uniform: the wrap is scalar arithmetic, and its one remainder is
+// taken at the pivot (morphology.hpp's phase). radius >= 1.
+template <bool DILATE, int ROWS>
+__global__ __launch_bounds__(kMorphColumns) void k_image_morph_v(const uint32_t* __restrict__ in, uint32_t in_h, uint32_t* __restrict__ out, uint32_t out_w, uint32_t out_h, uint32_t radius,
+                                                                  uint32_t origin, uint32_t edge) {
+    __shared__ uint32_t suffix[ROWS][kMorphColumns];
+    // rows loaded ahead of their use: the more LDS an instantiation takes, the fewer waves share a CU and the more each must keep in flight itself
+    constexpr int kAhead = ROWS <= 33 ? 8 : ROWS <= 129 ? 16 : 32;
+    const uint32_t lane = threadIdx.x, x = blockIdx.x * (uint32_t)kMorphColumns + lane;
+    const uint32_t reach = min(2u * radius, (uint32_t)(ROWS - 1)); // = 2 radius (the launcher's choice of ROWS); the bound keeps every LDS index below ROWS
+    const uint32_t j0 = blockIdx.y * (reach + 1u);
+    const int c = (int)j0 - (int)origin + (int)radius;
+    if (x >= out_w) return; // (no barrier below: a lane shares nothing with its neighbours)
+    const uint32_t* column = in + x;
+    const int n = (int)in_h, period = morphology_period(n, edge);
+    // Row i of the lane's column, (0, 0, 0, 0) outside the image under TRANSPARENT: the address comes from the wrapped (or, for TRANSPARENT,
+    // clamped) row in every case and the load is unconditional, so the loads of an unrolled stretch are in flight together.
+    auto texel_of = [&](int i, int phase) {
+        const uint32_t texel = column[(size_t)morphology_wrap_at(i, phase, n, edge) * out_w];
+        return morphology_split(edge == 0u && (uint32_t)i >= in_h ? 0u : texel);
+    };
+    const int phase_c = morphology_phase(c, n, edge); // the walk's one division; from here the phase moves by one with the row
+    const MorphologyTexel centre = texel_of(c, phase_c);
+    MorphologyTexel s = centre;
+    suffix[0][lane] = morphology_merge(s);
+    int phase = phase_c;
+#pragma unroll kAhead
+    for (uint32_t k = 1u; k <= reach; ++k) {
+        phase = morphology_phase_before(phase, period);
+        s = morphology_extreme<DILATE>(s, texel_of(c - (int)k, phase));
+        suffix[k][lane] = morphology_merge(s);
+    }
+    MorphologyTexel p = centre;
+    const uint32_t rows = min(reach + 1u, out_h - j0); // (j0 < out_h by the grid)
+    out[(size_t)j0 * out_w + x] = morphology_merge(morphology_extreme<DILATE>(p, morphology_split(suffix[reach][lane])));
+    phase = phase_c;
+#pragma unroll kAhead
+    for (uint32_t m = 1u; m < rows; ++m) {
+        phase = morphology_phase_next(phase, period);
+        p = morphology_extreme<DILATE>(p, texel_of(c + (int)m, phase));
+        out[(size_t)(j0 + m) * out_w + x] = morphology_merge(morphology_extreme<DILATE>(p, morphology_split(suffix[reach - m][lane])));
+    }
+}
+
+void launch_image_morph_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint32_t* out, uint32_t out_w, uint32_t op, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream) {
+    const dim3 grid((out_w + (uint32_t)kMorphSegment - 1u) / (uint32_t)kMorphSegment, src_h); // src_h <= 16384 rows: below the grid's limit of 65535
+    if (op == kMorphologyDilate) hipLaunchKernelGGL(k_image_morph_h<true>, grid, dim3(kMorphSegment), 0, stream, src, src_w, out, out_w, radius, origin, edge);
+    else hipLaunchKernelGGL(k_image_morph_h<false>, grid, dim3(kMorphSegment), 0, stream, src, src_w, out, out_w, radius, origin, edge);
+}
+
+void launch_image_morph_v(const uint32_t* in, uint32_t in_h, uint32_t* out, uint32_t out_w, uint32_t out_h, uint32_t op, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream) {
+    const uint32_t window = 2u * radius + 1u;
+    const dim3 grid((out_w + (uint32_t)kMorphColumns - 1u) / (uint32_t)kMorphColumns, (out_h + window - 1u) / window); // <= 16384 / 3 + 1 row blocks
+#define CRH_MORPH_V_LAUNCH(DILATE, ROWS) hipLaunchKernelGGL((k_image_morph_v<DILATE, ROWS>), grid, dim3(kMorphColumns), 0, stream, in, in_h, out, out_w, out_h, radius, origin, edge)
+    if (op == kMorphologyDilate) {
+        if (window <= 33u) CRH_MORPH_V_LAUNCH(true, 33);
+        else if (window <= 129u) CRH_MORPH_V_LAUNCH(true, 129);
+        else CRH_MORPH_V_LAUNCH(true, 2 * kMorphApron + 1);
+    } else {
+        if (window <= 33u) CRH_MORPH_V_LAUNCH(false, 33);
+        else if (window <= 129u) CRH_MORPH_V_LAUNCH(false, 129);
+        else CRH_MORPH_V_LAUNCH(false, 2 * kMorphApron + 1);
+    }
+#undef CRH_MORPH_V_LAUNCH
 }
 
 } // namespace crh

@@ -50,6 +50,10 @@ void launch_image_composite(const uint32_t* backdrop, uint32_t w, uint32_t h, co
 // device (256 words), or nullptr for none (color_filter.hpp holds the rule).
 struct ColorFilterCoefficients;
 void launch_image_color_filter(const uint32_t* src, uint32_t w, uint32_t h, const ColorFilterCoefficients& f, const uint32_t* tables, uint32_t* out, hipStream_t stream);
+// image_filter.hip: crh_image_morphology's two passes (morphology.hpp holds the rule; op < 2, 1 <= radius <= 192, edge < 4). h: src_h rows of src_w
+// texels -> src_h rows of out_w; v: in_h rows of out_w texels -> out_h rows of out_w. origin = the axis's radius where the result grows, else 0.
+void launch_image_morph_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint32_t* out, uint32_t out_w, uint32_t op, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream);
+void launch_image_morph_v(const uint32_t* in, uint32_t in_h, uint32_t* out, uint32_t out_w, uint32_t out_h, uint32_t op, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);

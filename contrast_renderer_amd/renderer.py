@@ -517,11 +517,41 @@ def color_filter_texels(texels, matrix=None, tables=None):
     return out
 
 
+class MorphologyOp(IntEnum):  # crh_morphology_op: the per-channel min or max over the window
+    Erode = 0
+    Dilate = 1
+
+
+MAX_MORPHOLOGY_RADIUS = 192  # CRH_MAX_MORPHOLOGY_RADIUS
+
+
+def morphology_size(width, height, op, radius_x, radius_y=None, edge=BlurEdge.Transparent):
+    """crh_morphology_size (host only) -> (width, height) of the result of Image.morphology on a width x height image: grown by the radius on
+    every side for MorphologyOp.Dilate under BlurEdge.Transparent, else the same. Raises ContrastError for what Image.morphology refuses."""
+    radius_y = radius_x if radius_y is None else radius_y
+    w, h = C.c_uint32(), C.c_uint32()
+    check(_ffi.load_library().crh_morphology_size(int(width), int(height), int(op), int(radius_x), int(radius_y), int(edge), C.byref(w), C.byref(h)))
+    return int(w.value), int(h.value)
+
+
+def morphology_texels(pixels, op, radius_x, radius_y=None, edge=BlurEdge.Transparent):
+    """crh_morphology_texels (host only): the rule of Image.morphology on a (height, width, 4) uint8 array -> the (height', width', 4) uint8
+    result (include/contrast_hip.h crh_image_morphology states the rule). radius_y=None means radius_x."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"morphology_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    radius_y = radius_x if radius_y is None else radius_y
+    w, h = morphology_size(pixels.shape[1], pixels.shape[0], op, radius_x, radius_y, edge)
+    out = np.empty((h, w, 4), dtype=np.uint8)
+    check(_ffi.load_library().crh_morphology_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, int(op), int(radius_x), int(radius_y), int(edge), out.ctypes.data))
+    return out
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
     its texels aliases unless it has mipmaps and its paint's filter is Filter.NearestMipmap or Filter.LinearMipmap. `origin` = the texel of this
-    image that lies over texel (0, 0) of the image it was blurred from: (0, 0) unless blur() grew it."""
+    image that lies over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless blur() or morphology() grew it."""
 
     origin = (0, 0)
 
@@ -619,6 +649,34 @@ class Image:
         image.handle = handle
         image.width, image.height, image.origin = self.width, self.height, self.origin
         return image
+
+    def morphology(self, op, radius_x, radius_y=None, edge=BlurEdge.Transparent):
+        """crh_image_morphology -> a new Image of one level: per channel the min (MorphologyOp.Erode) or max (MorphologyOp.Dilate) of this
+        image's level 0 over the rectangle |dx| <= radius_x, |dy| <= radius_y, exact, built on the device and complete when this returns (a
+        synchronous call). radius_y=None means radius_x; both integers in [0, MAX_MORPHOLOGY_RADIUS]. Dilate under BlurEdge.Transparent grows
+        the result by the radius on every side, and the result's `origin` is (radius_x, radius_y), by blur()'s convention; everything else
+        keeps the size and origin (0, 0). This image is not modified."""
+        radius_x = int(radius_x)
+        radius_y = radius_x if radius_y is None else int(radius_y)
+        image = Image.__new__(Image)
+        image.renderer, image.lib = self.renderer, self.lib
+        handle = C.c_void_p()
+        check(self.lib.crh_image_morphology(self.handle, int(op), radius_x, radius_y, int(edge), C.byref(handle)))
+        image.handle = handle
+        w, h = C.c_uint32(), C.c_uint32()
+        check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
+        image.width, image.height = int(w.value), int(h.value)
+        if int(op) == MorphologyOp.Dilate and int(edge) == BlurEdge.Transparent:
+            image.origin = (radius_x, radius_y)
+        return image
+
+    def dilate(self, radius_x, radius_y=None, edge=BlurEdge.Transparent):
+        """morphology(MorphologyOp.Dilate, ...): an outline's or a spread's growth."""
+        return self.morphology(MorphologyOp.Dilate, radius_x, radius_y, edge)
+
+    def erode(self, radius_x, radius_y=None, edge=BlurEdge.Transparent):
+        """morphology(MorphologyOp.Erode, ...): a choke, a negative spread."""
+        return self.morphology(MorphologyOp.Erode, radius_x, radius_y, edge)
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

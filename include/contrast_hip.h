@@ -630,6 +630,48 @@ crh_status crh_image_composite(const crh_image* backdrop, const crh_image* sourc
 crh_status crh_color_filter_validate(const float* matrix, const uint8_t* tables); /* host only */
 crh_status crh_color_filter_texels(const float* matrix, const uint8_t* tables, const void* rgba8, uint64_t n, void* out); /* host only */
 crh_status crh_image_color_filter(const crh_image* src, const float* matrix, const uint8_t* tables, crh_image** out);
+/* Morphology: the per-channel min (ERODE) or max (DILATE) of an image over a rectangle, on the device (SVG feMorphology) — an outline round
+ * text or artwork (a snapshot dilated by n, flooded with a colour by crh_image_color_filter, DST_OVER under the layer at the grown origin),
+ * the spread of a shadow or glow (dilate before the blur; erode for a negative spread or an inner shadow), a mask choked or grown before
+ * DST_IN, and open / close (one after the other) to remove specks from a rendered mask. The model is exact by nature, because min and max
+ * do not round; the tests check every byte against it.
+ *   window       out(i, j), per channel c of r, g, b, a independently, is the min (ERODE) or max (DILATE) of c(i + dx, j + dy) over
+ *                |dx| <= radius_x, |dy| <= radius_y. The values are the 8-bit codes as they are: no load clamp and no rounding anywhere.
+ *   edge         a crh_blur_edge. PAD, REPEAT and REFLECT keep the size (w, h): an index outside the axis reads wrap(i, n) by exactly the
+ *                rules of the image-paint block above, any number of periods out (a radius of 192 on a 1-texel axis). TRANSPARENT reads
+ *                (0, 0, 0, 0) outside the source.
+ *   grown result under TRANSPARENT, DILATE grows the result to (w + 2 radius_x, h + 2 radius_y): its texel (i, j) is centred on source texel
+ *                (i - radius_x, j - radius_y), as crh_image_blur grows, so nothing of an outline is cut off. ERODE keeps (w, h): growing
+ *                would add zeros only. A grown side above 16384 is CRH_ERR_UNSUPPORTED.
+ * Hence: radius (0, 0) is a byte-for-byte copy; rgb <= a survives both operators (min and max are monotone in every channel); under the
+ * three same-size edges dilate >= source >= erode texel by texel (the window holds its centre), and erode(x) == 255 - dilate(255 - x);
+ * a window that covers a whole axis gives that row's or column's extreme; two dilations (or two erosions) by r1 and then r2 under one edge
+ * equal one by r1 + r2 (for TRANSPARENT dilate the origins add); and the window is a rectangle, so rows-then-columns, columns-then-rows
+ * and a 2-D pass give the same bytes: the model does not bind the kernels' order.
+ * crh_morphology_size and crh_morphology_texels are host only (no renderer, no device) and take 1 <= width, height <= 16384. size:
+ * validates and reports the size of the result. texels: the rule on a whole image in host memory, width * height * 4 bytes in the order
+ * r g b a at any alignment, row 0 first, into out_rgba8, which holds the result's size; out_rgba8 == rgba8 is refused.
+ * Every error is found before the device is touched, and a refused call leaves *out (or the out buffers) untouched and writes nothing: a
+ * null argument, op > 1, edge > 3, a radius above CRH_MAX_MORPHOLOGY_RADIUS or a size outside [1, 16384] is CRH_ERR_INVALID_ARGUMENT with a
+ * crh_last_error text.
+ * crh_image_morphology gives a fresh image of the source's renderer with one level (crh_image_generate_mipmaps, blur, composite, colour
+ * filter, image paints and crh_frame_load_image work on it), complete when the call returns: k_image_morph_h (source -> intermediate) and
+ * k_image_morph_v (intermediate -> result) run on the renderer's stream, at a cost per texel that does not grow linearly with the radius. Only level 0
+ * of the source is read and the source is not modified. The intermediate (packed RGBA8, the result's width and the source's height) is
+ * freed before the call returns; a zero radius on an axis skips that axis's pass. A failed allocation or launch frees everything and
+ * returns CRH_ERR_HIP.
+ * Limits: the call is synchronous, like its siblings — one wait per call; the structuring element is a rectangle: no disc; the radii are
+ * integers; the operator acts per channel on premultiplied codes, as SVG does; images are immutable, so there is no in-place variant. */
+#define CRH_MAX_MORPHOLOGY_RADIUS 192u
+typedef enum crh_morphology_op {
+    CRH_MORPHOLOGY_ERODE = 0,
+    CRH_MORPHOLOGY_DILATE = 1
+} crh_morphology_op;
+crh_status crh_morphology_size(uint32_t width, uint32_t height, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, uint32_t* out_width,
+                               uint32_t* out_height); /* host only: validates, and reports the size of the result */
+crh_status crh_morphology_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge,
+                                 void* out_rgba8); /* host only: the rule on a whole image in host memory */
+crh_status crh_image_morphology(const crh_image* src, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

@@ -672,6 +672,23 @@ inline std::vector<uint8_t> color_filter_texels(const std::vector<uint8_t>& texe
     check(crh_color_filter_texels(matrix ? matrix->data() : nullptr, tables ? tables->data() : nullptr, texels.data(), texels.size() / 4u, out.data()));
     return out;
 }
+// Morphology (include/contrast_hip.h crh_image_morphology states the rule): per channel the min (Erode) or max (Dilate) over a rectangle
+enum class MorphologyOp : uint32_t { Erode = CRH_MORPHOLOGY_ERODE, Dilate = CRH_MORPHOLOGY_DILATE };
+// crh_morphology_size (host only) -> the size of Image::morphology's result on a width x height image; throws what it would refuse
+inline std::array<uint32_t, 2> morphology_size(uint32_t width, uint32_t height, MorphologyOp op, uint32_t radius_x, uint32_t radius_y, BlurEdge edge = BlurEdge::Transparent) {
+    std::array<uint32_t, 2> out = {0u, 0u};
+    check(crh_morphology_size(width, height, (uint32_t)op, radius_x, radius_y, (uint32_t)edge, &out[0], &out[1]));
+    return out;
+}
+// crh_morphology_texels (host only): the rule on a width x height image of RGBA8 in host memory -> the bytes of the result, of morphology_size's size
+inline std::vector<uint8_t> morphology_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, MorphologyOp op, uint32_t radius_x, uint32_t radius_y,
+                                              BlurEdge edge = BlurEdge::Transparent) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const std::array<uint32_t, 2> size = morphology_size(width, height, op, radius_x, radius_y, edge);
+    std::vector<uint8_t> out((size_t)size[0] * size[1] * 4u);
+    check(crh_morphology_texels(width, height, texels.data(), (uint32_t)op, radius_x, radius_y, (uint32_t)edge, out.data()));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -721,7 +738,7 @@ class Image {
         if (edge == BlurEdge::Transparent) image.origin_ = {(image.width_ - width_) / 2u, (image.height_ - height_) / 2u};
         return image;
     }
-    // the texel of this image over texel (0, 0) of the image it was blurred from: (0, 0) unless blur() grew it
+    // the texel of this image over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless blur() or morphology() grew it
     std::array<uint32_t, 2> origin() const { return origin_; }
     // crh_image_composite, called on the backdrop -> a new Image of one level, of this image's size, origin (0, 0): `source` combined with this
     // image texel by texel by a Porter-Duff operator, a blend mode and a group opacity in [0, 1]; integer and bit-exact, complete on return.
@@ -744,6 +761,21 @@ class Image {
         image.width_ = width_, image.height_ = height_, image.origin_ = origin_;
         return image;
     }
+    // crh_image_morphology -> a new Image of one level: per channel the min (Erode) or max (Dilate) of this image's level 0 over the rectangle
+    // |dx| <= radius_x, |dy| <= radius_y; exact, complete on return (a synchronous call). Dilate under BlurEdge::Transparent grows the result by
+    // the radius on every side and its origin() is (radius_x, radius_y), as blur() grows; everything else keeps the size and origin (0, 0).
+    // Radii end at CRH_MAX_MORPHOLOGY_RADIUS. This image is not modified.
+    Image morphology(MorphologyOp op, uint32_t radius_x, uint32_t radius_y, BlurEdge edge = BlurEdge::Transparent) const {
+        Image image;
+        check(crh_image_morphology(handle_, (uint32_t)op, radius_x, radius_y, (uint32_t)edge, &image.handle_));
+        check(crh_image_size(image.handle_, &image.width_, &image.height_));
+        if (op == MorphologyOp::Dilate && edge == BlurEdge::Transparent) image.origin_ = {radius_x, radius_y};
+        return image;
+    }
+    Image dilate(uint32_t radius_x, uint32_t radius_y, BlurEdge edge = BlurEdge::Transparent) const { return morphology(MorphologyOp::Dilate, radius_x, radius_y, edge); }
+    Image dilate(uint32_t radius) const { return morphology(MorphologyOp::Dilate, radius, radius); }
+    Image erode(uint32_t radius_x, uint32_t radius_y, BlurEdge edge = BlurEdge::Transparent) const { return morphology(MorphologyOp::Erode, radius_x, radius_y, edge); }
+    Image erode(uint32_t radius) const { return morphology(MorphologyOp::Erode, radius, radius); }
 
   private:
     Image() = default;

@@ -851,6 +851,27 @@ pub fn color_filter_texels(texels: &[u8], matrix: Option<&[f32; 20]>, tables: Op
     status(unsafe { ffi::crh_color_filter_texels(m, t, texels.as_ptr() as *const _, (texels.len() / 4) as u64, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// The operator of `Image::morphology` (`crh_morphology_op`): per channel the min or the max over the window
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum MorphologyOp {
+    Erode = 0,
+    Dilate = 1,
+}
+/// `crh_morphology_size` (host only) -> (width, height) of the result of `Image::morphology` on a width x height image
+pub fn morphology_size(width: u32, height: u32, op: MorphologyOp, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<(u32, u32), Error> {
+    let (mut w, mut h) = (0u32, 0u32);
+    status(unsafe { ffi::crh_morphology_size(width, height, op as u32, radius_x, radius_y, edge as u32, &mut w, &mut h) })?;
+    Ok((w, h))
+}
+/// `crh_morphology_texels` (host only): the rule on a width x height image of RGBA8 in host memory -> (width, height, texels) of the result
+/// (include/contrast_hip.h, `crh_image_morphology`, states the rule).
+pub fn morphology_texels(width: u32, height: u32, texels: &[u8], op: MorphologyOp, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<(u32, u32, Vec<u8>), Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    let (w, h) = morphology_size(width, height, op, radius_x, radius_y, edge)?;
+    let mut out = vec![0u8; w as usize * h as usize * 4];
+    status(unsafe { ffi::crh_morphology_texels(width, height, texels.as_ptr() as *const _, op as u32, radius_x, radius_y, edge as u32, out.as_mut_ptr() as *mut _) })?;
+    Ok((w, h, out))
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -908,7 +929,7 @@ impl Image {
         let origin = if edge == BlurEdge::Transparent { ((width - self.width) / 2, (height - self.height) / 2) } else { (0, 0) };
         Ok(Image { raw, width, height, origin })
     }
-    /// The texel of this image over texel (0, 0) of the image it was blurred from: (0, 0) unless `blur` grew it
+    /// The texel of this image over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless `blur` or `morphology` grew it
     pub fn origin(&self) -> (u32, u32) {
         self.origin
     }
@@ -931,6 +952,24 @@ impl Image {
         let (m, t) = (matrix.map_or(ptr::null(), |m| m.as_ptr()), tables.map_or(ptr::null(), |t| t.as_ptr()));
         status(unsafe { ffi::crh_image_color_filter(self.raw, m, t, &mut raw) })?;
         Ok(Image { raw, width: self.width, height: self.height, origin: self.origin })
+    }
+    /// `crh_image_morphology` -> a new `Image` of one level: per channel the min (`Erode`) or max (`Dilate`) of this image's level 0 over the
+    /// rectangle |dx| <= radius_x, |dy| <= radius_y; exact, complete on return (a synchronous call). Radii in [0, `CRH_MAX_MORPHOLOGY_RADIUS`].
+    /// `Dilate` under `BlurEdge::Transparent` grows the result by the radius on every side and its `origin()` is (radius_x, radius_y), as
+    /// `blur` grows; everything else keeps the size and origin (0, 0). This image is not modified.
+    pub fn morphology(&self, op: MorphologyOp, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<Image, Error> {
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_morphology(self.raw, op as u32, radius_x, radius_y, edge as u32, &mut raw) })?;
+        let (mut width, mut height) = (0u32, 0u32);
+        status(unsafe { ffi::crh_image_size(raw, &mut width, &mut height) })?;
+        let origin = if op == MorphologyOp::Dilate && edge == BlurEdge::Transparent { (radius_x, radius_y) } else { (0, 0) };
+        Ok(Image { raw, width, height, origin })
+    }
+    pub fn dilate(&self, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<Image, Error> {
+        self.morphology(MorphologyOp::Dilate, radius_x, radius_y, edge)
+    }
+    pub fn erode(&self, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<Image, Error> {
+        self.morphology(MorphologyOp::Erode, radius_x, radius_y, edge)
     }
 }
 impl Drop for Image {
