@@ -2493,6 +2493,8 @@ crh_status crh_scene_set_instances(crh_scene* sc, const float* transforms, const
     return CRH_OK;
 }
 namespace {
+constexpr float kTurnF32 = 6.28318530717958647692f;  // the f32 nearest to 2 pi: the largest sweep of a conic paint
+constexpr double kTurn = 6.28318530717958647692;
 crh_status paint_error(const char* what) {
     g_error = std::string("crh_paint: ") + what;
     return CRH_ERR_INVALID_ARGUMENT;
@@ -2509,7 +2511,7 @@ crh_status crh_paint_validate(const crh_paint* paint) {
         for (float v : paint->stops[i].color)
             if (!std::isfinite(v)) return CRH_ERR_NON_FINITE;
     }
-    if (paint->kind != CRH_PAINT_LINEAR && paint->kind != CRH_PAINT_RADIAL) return paint_error("unknown kind");
+    if (paint->kind != CRH_PAINT_LINEAR && paint->kind != CRH_PAINT_RADIAL && paint->kind != CRH_PAINT_CONIC) return paint_error("unknown kind");
     if (paint->spread > CRH_SPREAD_REFLECT) return paint_error("unknown spread");
     for (uint32_t i = 0; i < paint->n_stops; ++i) {
         const float o = paint->stops[i].offset;
@@ -2520,6 +2522,11 @@ crh_status crh_paint_validate(const crh_paint* paint) {
         const float dx = paint->p1[0] - paint->p0[0], dy = paint->p1[1] - paint->p0[1];
         const float dd = dx * dx + dy * dy;
         if (!(dd > 0.0f) || !std::isfinite(dd)) return paint_error("a linear paint needs p0 != p1");
+    } else if (paint->kind == CRH_PAINT_CONIC) {
+        const double sweep = (double)paint->p1[1] - (double)paint->p1[0];
+        if (sweep == 0.0) return paint_error("a conic paint needs a start angle != its end angle");
+        if (std::fabs(sweep) > (double)kTurnF32) return paint_error("a conic paint sweeps at most one turn (the f32 nearest to 2 pi)");
+        if (!std::isfinite((float)(kTurn / std::fabs(sweep)))) return paint_error("a conic paint's sweep is too small: 2 pi / |sweep| overflows f32");
     } else if (!(paint->p1[0] > 0.0f)) {
         return paint_error("a radial paint needs a radius > 0");
     }
@@ -2587,6 +2594,9 @@ crh_status crh_scene_set_paints_with_images(crh_scene* sc, const crh_paint* pain
             if (q.kind == CRH_PAINT_LINEAR) {
                 h.d[0] = q.p1[0] - q.p0[0], h.d[1] = q.p1[1] - q.p0[1];
                 h.dd = h.d[0] * h.d[0] + h.d[1] * h.d[1];
+            } else if (q.kind == CRH_PAINT_CONIC) { // s, k and the direction, each from the f32 fields in binary64, rounded once (include/contrast_hip.h)
+                const double start = (double)q.p1[0] / kTurn, sweep = (double)q.p1[1] - (double)q.p1[0];
+                h.d[0] = (float)(start - std::floor(start)), h.d[1] = (float)(kTurn / std::fabs(sweep)), h.dd = sweep > 0.0 ? 1.0f : -1.0f;
             } else {
                 h.d[0] = q.p1[0], h.d[1] = 0.0f, h.dd = 1.0f;
             }

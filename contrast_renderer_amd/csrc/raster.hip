@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "launch.hpp"
+#include "paint_angle.hpp"
 #include "raster_tile_list.hpp"
 
 namespace crh {

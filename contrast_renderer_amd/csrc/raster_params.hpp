@@ -59,7 +59,8 @@ struct BlendForm {
 //   PaintItem  per draw item of a painted pass (k_paint_items writes it, in front of the raster kernel): the inverse of the item's
 //              path -> pixel homography (rows X, Y, W; inverted in float64, stored as f32; an affine instance has the row W = (0, 0, 1) exactly),
 //              the instance colour (straight alpha) and the paint's index. The item's cover primitives carry item + 1 in frag.flat_u.
-//   PaintHead  per paint: kind, spread, p0, and d = p1 - p0 with dd = dot(d, d) (linear) or d[0] = the radius (radial)
+//   PaintHead  per paint: kind, spread, p0, and d = p1 - p0 with dd = dot(d, d) (linear), d[0] = the radius (radial), or d = (s, k) with
+//              dd = +1 (sweep > 0) or -1 (sweep < 0) the direction (conic: include/contrast_hip.h names s and k)
 //   PaintStop  per stop i: the offset o_i, 1 / (o_{i+1} - o_i) (0 for a hard edge and behind the last stop), the colour c_i and c_{i+1} - c_i
 //              (0 behind the last stop), so that colour(t) = c_i + max((t - o_i) * inv, 0) * dc for the last i with t >= o_i (i = 0 if there is none)
 struct PaintItem {

@@ -509,6 +509,33 @@
                         }
                         } // one level
                     } else {
+                    // The kind is chosen once per turn of four samples, not per sample: the loop of the linear and radial kinds is the one the kernel had
+                    // before the conic kind, so their code does not pay for it (chosen inside the loop, it became a chain of scalar branches per sample).
+                    if (ph.kind == CRH_PAINT_CONIC) { // wave uniform. d = (s, k), dd = +-1 the direction (raster_params.hpp PaintHead)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int b = (g + c) / S, k = (g + c) % S;
+                        const float fx = tx0 + sx[k], fy = ty0 + (sy0[k] + (float)(4 * b)); // the sample's place on the frame (exact)
+                        float X = fmaf(fy, pi.h[1], fmaf(fx, pi.h[0], pi.h[2])), Y = fmaf(fy, pi.h[4], fmaf(fx, pi.h[3], pi.h[5]));
+                        if (!pi.affine) { // wave uniform
+                            const float W = fmaf(fy, pi.h[7], fmaf(fx, pi.h[6], pi.h[8]));
+                            X = X / W;
+                            Y = Y / W;
+                        }
+                        const float ux = X - ph.p0[0], uy = Y - ph.p0[1];
+                        const float bt = (paint_turns(uy, ux) - ph.d[0]) * ph.dd;
+                        float v = (bt < 0.0f ? bt + 1.0f : bt) * ph.d[1];
+                        if (ph.spread == CRH_SPREAD_REPEAT) {
+                            v = v - floorf(v);
+                        } else if (ph.spread == CRH_SPREAD_REFLECT) {
+                            const float u = v - 2.0f * floorf(v * 0.5f);
+                            v = u <= 1.0f ? u : 2.0f - u;
+                        } else {
+                            v = clamp_unit(v);
+                        }
+                        t[c] = v;
+                    }
+                    } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int b = (g + c) / S, k = (g + c) % S;
@@ -530,6 +557,7 @@
                             v = clamp_unit(v);
                         }
                         t[c] = v;
+                    }
                     }
                     for (uint32_t i = 0; i < ph.n_stops; ++i) { // wave uniform: the stop's record in scalar registers, a select per sample
                         const PaintStop st = load_uniform(&pa.stops[ph.first_stop + i]);

@@ -14,6 +14,7 @@
 //                 element's counts kept from the first tessellation of the paths — see "k_tess_runs" below.
 #include "fill.hpp"
 #include "launch.hpp"
+#include "paint_angle.hpp"
 #include "scene.hpp"
 #include "stroke.hpp"
 
@@ -926,6 +927,7 @@ __global__ void k_fmath(int fn, const float* a, const float* b, float* out, uint
         case 7: out[i] = a[i] / b[i]; break;
         case 8: out[i] = 1.0f / sqrtf(a[i] * a[i] + b[i] * b[i]); break;
         case 9: out[i] = a[i] * b[i] - 4.0f * a[i] * b[i] * b[i]; break;
+        case 10: out[i] = paint_turns(a[i], b[i]); break;
         default: out[i] = crh_wgsl_mod(a[i], b[i]); break;
     }
 }

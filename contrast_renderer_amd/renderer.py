@@ -155,6 +155,7 @@ class Spread(IntEnum):  # crh_spread: what a gradient does outside [0, 1]
 class PaintKind(IntEnum):  # crh_paint_kind
     Linear = 1
     Radial = 2
+    Conic = 4  # (3 is not a kind: crh_paint_validate refuses it)
 
 
 @dataclass(frozen=True)
@@ -165,7 +166,7 @@ class GradientStop:  # crh_gradient_stop: offset in [0, 1], straight RGBA
 
 @dataclass(frozen=True)
 class Paint:
-    """crh_paint: a linear or radial gradient in the Shape's path coordinates, the source of a Color cover in place of the instance's one
+    """crh_paint: a linear, radial or conic gradient in the Shape's path coordinates, the source of a Color cover in place of the instance's one
     colour (include/contrast_hip.h crh_scene_set_paints states the model). Stops: GradientStop or (offset, (r, g, b, a)) pairs, at most 8."""
     kind: int
     spread: int
@@ -186,6 +187,12 @@ class Paint:
     def radial(center, radius, stops, spread=Spread.Pad):
         """t = distance from `center` / radius."""
         return Paint(PaintKind.Radial, spread, (float(center[0]), float(center[1])), (float(radius), 0.0), Paint._stops(stops))
+
+    @staticmethod
+    def conic(center, start, end, stops, spread=Spread.Pad):
+        """t = 0 on the ray from `center` at the angle `start`, t = 1 at `end`: radians, from +x towards +y in the Shape's path coordinates,
+        0 < |end - start| <= 2 pi; end < start reads the stops clockwise."""
+        return Paint(PaintKind.Conic, spread, (float(center[0]), float(center[1])), (float(start), float(end)), Paint._stops(stops))
 
     def to_c(self):
         if not 0 < len(self.stops) <= _ffi.MAX_GRADIENT_STOPS:

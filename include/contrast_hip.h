@@ -375,6 +375,13 @@ crh_status crh_scene_render_draws(crh_scene* scene, crh_frame* frame, const floa
  *                3x3 homography made of columns 0, 1, 3 and rows x, y, w of the transform and the clip -> pixel map).
  *   linear       t = dot(p - p0, p1 - p0) / dot(p1 - p0, p1 - p0)
  *   radial       t = |p - p0| / radius         (p0 the centre, radius = p1[0] > 0, p1[1] = 0)
+ *   conic        p0 the centre, p1[0] the start angle and p1[1] the end angle, both in radians. With a = turns(p.y - p0.y, p.x - p0.x) in
+ *                [0, 1), the angle of p - p0 in the Shape's path coordinates from +x towards +y in turns (turns(0, 0) = 0; the four axes give
+ *                exactly 0, 0.25, 0.5 and 0.75), and the table's sweep = p1[1] - p1[0], s = (p1[0] / 2 pi) - floor(p1[0] / 2 pi), k = 2 pi / |sweep|:
+ *                b = a - s for sweep > 0, b = s - a for sweep < 0 (the same stops read clockwise); if b < 0 then b = b + 1; t = b k.
+ *                (In f32 the sum may round to exactly 1 on the start ray: inside the stated error, and on the seam.) With |sweep| < 2 pi, t runs
+ *                past 1: PAD holds the last stop over the rest of the turn, REPEAT and REFLECT tile the wedge round the circle. The device
+ *                evaluates a in f32 (csrc/paint_angle.hpp paint_turns, which states its error against the exact angle as kPaintTurnsError).
  *   spread       PAD: t = clamp(t, 0, 1); REPEAT: t = t - floor(t); REFLECT: u = t - 2 floor(t / 2), t = u <= 1 ? u : 2 - u
  *   stops        offsets non-decreasing in [0, 1]. In front of the first stop its colour, behind the last stop its colour; between stops i and
  *                i + 1 with o_i < o_i+1: c_i + f (c_i+1 - c_i), f = (t - o_i) / (o_i+1 - o_i), per straight-alpha channel — equal stop colours
@@ -389,12 +396,15 @@ crh_status crh_scene_render_draws(crh_scene* scene, crh_frame* frame, const floa
  * painted instance runs the general triangle kernel (as a blend state other than "over" does); every other pass is launched as before.
  * Errors: a non-finite field CRH_ERR_NON_FINITE; an unknown kind or spread, n_stops 0 or > CRH_MAX_GRADIENT_STOPS, decreasing offsets or one outside
  * [0, 1], a linear paint with p0 == p1 (precisely: whose dot(p1 - p0, p1 - p0), evaluated in f32, is not a positive finite number — it may
- * underflow or overflow for p0 != p1), a radial one with radius <= 0, an instance_paint entry >= n_paints or < -1: CRH_ERR_INVALID_ARGUMENT with a
+ * underflow or overflow for p0 != p1), a radial one with radius <= 0, a conic one with sweep == 0 or
+ * |sweep| greater than the f32 nearest to 2 pi (or so small that k overflows f32), an instance_paint entry >= n_paints or < -1: CRH_ERR_INVALID_ARGUMENT with a
  * crh_last_error text. A failed call leaves the Scene's previous table in place.
- * The table's p1 - p0 and dot(p1 - p0, p1 - p0) are evaluated once, in f32, when the call builds the table. The call settles the frames drawn
+ * The table's p1 - p0 and dot(p1 - p0, p1 - p0) are evaluated once, in f32, when the call builds the table; a conic paint's sweep, s and k each
+ * once in binary64 from the f32 fields, rounded once to f32. The call settles the frames drawn
  * from the Scene and waits for the renderer's work in flight (kernels read the table): set a table when it changes, not once per frame. */
 #define CRH_MAX_GRADIENT_STOPS 8
-typedef enum crh_paint_kind { CRH_PAINT_LINEAR = 1, CRH_PAINT_RADIAL = 2 } crh_paint_kind;
+/* (3 is not a kind and stays refused: an image paint is a type of its own, crh_image_paint below, not a crh_paint of a third kind) */
+typedef enum crh_paint_kind { CRH_PAINT_LINEAR = 1, CRH_PAINT_RADIAL = 2, CRH_PAINT_CONIC = 4 } crh_paint_kind;
 typedef enum crh_spread { CRH_SPREAD_PAD = 0, CRH_SPREAD_REPEAT = 1, CRH_SPREAD_REFLECT = 2 } crh_spread;
 typedef struct crh_gradient_stop {
     float offset;
@@ -402,7 +412,7 @@ typedef struct crh_gradient_stop {
 } crh_gradient_stop;
 typedef struct crh_paint {
     uint32_t kind, spread; /* crh_paint_kind, crh_spread */
-    float p0[2], p1[2];    /* linear: t = 0 at p0, t = 1 at p1; radial: centre p0, radius p1[0] (> 0), p1[1] = 0 */
+    float p0[2], p1[2];    /* linear: t = 0 at p0, t = 1 at p1; radial: centre p0, radius p1[0] (> 0), p1[1] = 0; conic: centre p0, start angle p1[0], end angle p1[1] */
     uint32_t n_stops;      /* 1..CRH_MAX_GRADIENT_STOPS */
     crh_gradient_stop stops[CRH_MAX_GRADIENT_STOPS];
 } crh_paint;
@@ -721,8 +731,8 @@ typedef struct crh_kernel_time {
     uint64_t algorithmic_bytes;
 } crh_kernel_time;
 crh_status crh_renderer_kernel_times(crh_renderer* renderer, crh_kernel_time* out, uint32_t capacity, uint32_t* count);
-/* Self-test tap: evaluates include/crh_fmath.h ON THE GPU (fn 0 atan2(a,b), 1 acos(a), 2 sin(a), 3 cos(a), 4 pow(a,b), 5 wgsl_mod(a,b))
- * so that tests can check device results bit for bit against the host evaluation of the same header. Host pointers. */
+/* Self-test tap: evaluates include/crh_fmath.h ON THE GPU (fn 0 atan2(a,b), 1 acos(a), 2 sin(a), 3 cos(a), 4 pow(a,b), 5 wgsl_mod(a,b)),
+ * and fn 10 csrc/paint_angle.hpp paint_turns(a,b), so that tests can check device results bit for bit against the host evaluation of the same header. Host pointers. */
 crh_status crh_selftest_fmath(crh_renderer* renderer, int fn, const float* a, const float* b, float* out, uint64_t n);
 /* Self-test tap of the sRGB codec of the *_SRGB formats, run ON THE GPU by the functions the raster kernels use: codes[i] = encode(x[i]) for
  * i < n, decoded[c] = decode(c) for the 256 codes (both as defined at CRH_FORMAT_RGBA8_SRGB above). Host pointers. */

@@ -578,6 +578,10 @@ class Paint {
     static Paint radial(const std::array<float, 2>& center, float radius, const std::vector<GradientStop>& stops, Spread spread = Spread::Pad) {
         return Paint(CRH_PAINT_RADIAL, spread, center, {radius, 0.0f}, stops);
     }
+    // t = 0 on the ray from `center` at the angle `start`, t = 1 at `end`: radians, from +x towards +y, 0 < |end - start| <= 2 pi; end < start reads the stops clockwise
+    static Paint conic(const std::array<float, 2>& center, float start, float end, const std::vector<GradientStop>& stops, Spread spread = Spread::Pad) {
+        return Paint(CRH_PAINT_CONIC, spread, center, {start, end}, stops);
+    }
     void validate() const { check(crh_paint_validate(&c_)); } // host only: throws what Scene::set_paints would
     const crh_paint& to_c() const { return c_; }
 

@@ -699,7 +699,7 @@ pub enum Spread {
     Repeat = 1,
     Reflect = 2,
 }
-/// A linear or radial gradient in the Shape's path coordinates: the source of a Color cover in place of the instance's one colour
+/// A linear, radial or conic gradient in the Shape's path coordinates: the source of a Color cover in place of the instance's one colour
 /// (include/contrast_hip.h, `crh_scene_set_paints`, states the model). Stops are (offset, straight RGBA), at most 8.
 #[derive(Clone, Copy)]
 pub struct Paint(pub ffi::crh_paint);
@@ -719,6 +719,11 @@ impl Paint {
     /// t = distance from `center` / `radius`
     pub fn radial(center: [f32; 2], radius: f32, stops: &[(f32, [f32; 4])], spread: Spread) -> Self {
         Self::with(2, spread, center, [radius, 0.0], stops)
+    }
+    /// t = 0 on the ray from `center` at the angle `start`, t = 1 at `end`: radians, from +x towards +y, 0 < |end - start| <= 2 pi;
+    /// `end < start` reads the stops clockwise
+    pub fn conic(center: [f32; 2], start: f32, end: f32, stops: &[(f32, [f32; 4])], spread: Spread) -> Self {
+        Self::with(ffi::CRH_PAINT_CONIC, spread, center, [start, end], stops)
     }
     /// Host only: what `Scene::set_paints` would refuse
     pub fn validate(&self) -> Result<(), Error> {
