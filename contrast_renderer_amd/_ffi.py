@@ -229,6 +229,11 @@ class CompositeC(C.Structure):  # crh_composite
     _fields_ = [("op", C.c_uint32), ("mode", C.c_uint32), ("opacity", C.c_float), ("x", C.c_int32), ("y", C.c_int32)]
 
 
+class ConvolveC(C.Structure):  # crh_convolve
+    _fields_ = [("order_x", C.c_uint32), ("order_y", C.c_uint32), ("target_x", C.c_uint32), ("target_y", C.c_uint32), ("kernel", C.POINTER(C.c_float)),
+                ("divisor", C.c_float), ("bias", C.c_float), ("edge", C.c_uint32), ("preserve_alpha", C.c_uint32)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -316,6 +321,10 @@ def load_library():
         "crh_morphology_size": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "crh_morphology_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, V]),
         "crh_image_morphology": (C.c_int, [V, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(V)]),
+        "crh_convolve_validate": (C.c_int, [C.POINTER(ConvolveC)]),
+        "crh_convolve_coefficients": (C.c_int, [C.POINTER(ConvolveC), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32)]),
+        "crh_convolve_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.POINTER(ConvolveC), V]),
+        "crh_image_convolve": (C.c_int, [V, C.POINTER(ConvolveC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

@@ -16,6 +16,7 @@
 
 #include "color_filter.hpp"
 #include "composite.hpp"
+#include "convolve.hpp"
 #include "launch.hpp"
 #include "morphology.hpp"
 #include "raster_params.hpp"
@@ -3217,6 +3218,84 @@ crh_status crh_image_morphology(const crh_image* src, uint32_t op, uint32_t radi
     }
     ok = hip_ok(r->sync(), "sync(morphology)") && ok; // (also behind a failure: the intermediate is read until the stream has drained)
     if (tmp) (void)hipFree(tmp);
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+namespace {
+static_assert(CRH_MAX_CONVOLVE_ORDER == kConvolveMaxOrder && CRH_CONVOLVE_MAX_GAIN == kConvolveMaxGain && CRH_BLUR_EDGE_TRANSPARENT == kConvolveTransparent,
+              "convolve.hpp's limits and edge are the header's");
+crh_status convolve_error(const char* what) {
+    g_error = std::string("crh_convolve_validate: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+// validates and quantises: the one check of the four entry points, and the one way from the caller's floats to the coefficients
+crh_status convolve_coefficients(const crh_convolve* how, ConvolveCoefficients* f) {
+    if (!how || !how->kernel) return convolve_error("a null argument");
+    if (how->order_x == 0u || how->order_y == 0u || how->order_x > CRH_MAX_CONVOLVE_ORDER || how->order_y > CRH_MAX_CONVOLVE_ORDER) return convolve_error("an order is outside [1, CRH_MAX_CONVOLVE_ORDER]");
+    if (how->target_x >= how->order_x || how->target_y >= how->order_y) return convolve_error("a target is not below its order");
+    if (how->edge > CRH_BLUR_EDGE_REFLECT) return convolve_error("edge is above CRH_BLUR_EDGE_REFLECT");
+    if (how->preserve_alpha > 1u) return convolve_error("preserve_alpha is above 1");
+    if (how->divisor == 0.0f) return convolve_error("divisor is 0");
+    if (std::isfinite(how->bias) && std::fabs(how->bias) > 1.0f) return convolve_error("bias is outside [-1, 1]");
+    switch (convolve_quantize(how->kernel, how->order_x, how->order_y, how->divisor, how->bias, f)) {
+    case kConvolveNonFinite: return CRH_ERR_NON_FINITE;
+    case kConvolveGain: return convolve_error("the kernel over the divisor exceeds CRH_CONVOLVE_MAX_GAIN: sum |k| is above 64 * 65536");
+    default: return CRH_OK;
+    }
+}
+crh_status convolve_size(uint32_t width, uint32_t height) {
+    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return convolve_error("width and height lie in [1, 16384]");
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_convolve_validate(const crh_convolve* how) {
+    ConvolveCoefficients f;
+    return convolve_coefficients(how, &f);
+}
+crh_status crh_convolve_coefficients(const crh_convolve* how, int32_t* k, uint32_t capacity, int32_t* bias_k) {
+    ConvolveCoefficients f;
+    const crh_status st = convolve_coefficients(how, &f);
+    if (st != CRH_OK) return st;
+    const uint32_t n = how->order_x * how->order_y;
+    if (k && capacity < n) return convolve_error("capacity is below order_x * order_y");
+    if (k) std::copy(f.k, f.k + n, k);
+    if (bias_k) *bias_k = f.bias_k;
+    return CRH_OK;
+}
+crh_status crh_convolve_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_convolve* how, void* out_rgba8) {
+    if (!rgba8 || !out_rgba8) return convolve_error("a null argument");
+    if (rgba8 == out_rgba8) return convolve_error("out_rgba8 is rgba8");
+    ConvolveCoefficients f;
+    crh_status st = convolve_coefficients(how, &f);
+    if (st != CRH_OK) return st;
+    st = convolve_size(width, height);
+    if (st != CRH_OK) return st;
+    const uint8_t* in = static_cast<const uint8_t*>(rgba8);
+    uint8_t* to = static_cast<uint8_t*>(out_rgba8);
+    if (how->preserve_alpha) convolve_run<true>(in, width, height, f, how->order_x, how->order_y, how->target_x, how->target_y, how->edge, to);
+    else convolve_run<false>(in, width, height, f, how->order_x, how->order_y, how->target_x, how->target_y, how->edge, to);
+    return CRH_OK;
+}
+crh_status crh_image_convolve(const crh_image* src, const crh_convolve* how, crh_image** out) {
+    if (!src || !src->renderer || !out) return convolve_error("a null argument");
+    ConvolveCoefficients f;
+    crh_status st = convolve_coefficients(how, &f);
+    if (st != CRH_OK) return st;
+    st = convolve_size(src->width, src->height);
+    if (st != CRH_OK) return st;
+    crh_renderer* r = src->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    st = new_image(r, src->width, src->height, &image);
+    if (st != CRH_OK) return st;
+    launch_image_convolve(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, f, how->order_x, how->order_y, how->target_x, how->target_y, how->edge, how->preserve_alpha != 0u,
+                          static_cast<uint32_t*>(image->pixels->p), r->stream);
+    bool ok = hip_ok(hipGetLastError(), "k_image_convolve");
+    ok = hip_ok(r->sync(), "sync(convolve)") && ok;
     if (!ok) {
         delete image;
         return CRH_ERR_HIP;

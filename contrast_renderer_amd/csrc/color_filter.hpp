@@ -56,6 +56,9 @@ __host__ __device__ __forceinline__ int32_t color_filter_mul(int32_t a, int32_t 
 #endif
 }
 
+// The load and the unpremultiply of one colour code c beside its alpha a, `ra` = R[a]: c = min(c, a), then (255 c + a / 2) / a, <= 255
+__host__ __device__ __forceinline__ uint32_t color_filter_unpremultiply(uint32_t code, uint32_t a, uint32_t ra) { return (composite_mul(code < a ? code : a, ra) + 32768u) >> 16; }
+
 // One texel (r | g << 8 | b << 16 | a << 24, as the texels are) -> the filtered texel. `recip` = UnpremultiplyTable::r (in LDS on the
 // device); `tables` = the 1024 bytes r[256] g[256] b[256] a[256] (in LDS on the device), read only when TABLES.
 template <bool TABLES>
@@ -65,7 +68,7 @@ __host__ __device__ __forceinline__ uint32_t color_filter_texel(uint32_t texel, 
 #pragma unroll
     for (uint32_t c = 0; c < 3u; ++c) {
         const uint32_t code = (texel >> (8u * c)) & 0xFFu;
-        u[c] = (int32_t)((composite_mul(code < a ? code : a, ra) + 32768u) >> 16); // load: c = min(c, a); unpremultiply: <= 255
+        u[c] = (int32_t)color_filter_unpremultiply(code, a, ra);
     }
     u[3] = (int32_t)a;
     uint32_t v[4];

@@ -5,12 +5,14 @@
 // crh_image_color_filter: k_image_color_filter maps every texel of an image with the rule of color_filter.hpp.
 // crh_image_morphology: k_image_morph_h and k_image_morph_v take the per-channel min or max over a rectangle with the rule of morphology.hpp,
 // at a cost per texel that does not grow linearly with the radius.
+// crh_image_convolve: k_image_convolve puts an image through a kernel matrix with the rule of convolve.hpp, a 2-D stencil over a tile and its halo in LDS.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "color_filter.hpp"
 #include "composite.hpp"
+#include "convolve.hpp"
 #include "launch.hpp"
 #include "morphology.hpp"
 
@@ -414,6 +416,113 @@ void launch_image_morph_v(const uint32_t* in, uint32_t in_h, uint32_t* out, uint
         else CRH_MORPH_V_LAUNCH(false, 2 * kMorphApron + 1);
     }
 #undef CRH_MORPH_V_LAUNCH
+}
+
+namespace {
+constexpr int kConvolveTileW = 64;  // output columns per workgroup, one per lane of a wave
+constexpr int kConvolveWaves = 4;   // waves per workgroup
+#ifndef CRH_CONVOLVE_ROWS
+#define CRH_CONVOLVE_ROWS 4 // (a build with -DCRH_CONVOLVE_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the register blocking was measured)
+#endif
+constexpr int kConvolveRows = CRH_CONVOLVE_ROWS; // adjacent output rows per lane: a staged texel's bytes are extracted once for all of them
+constexpr int kConvolveTileH = kConvolveWaves * kConvolveRows;      // 16 output rows per workgroup
+constexpr int kConvolveHalo = (int)kConvolveMaxOrder - 1;           // 14: the most texels staged beyond the tile per axis
+constexpr int kConvolvePitch = kConvolveTileW + kConvolveHalo;      // 78 words per staged row
+constexpr int kConvolveStagedRows = kConvolveTileH + kConvolveHalo; // 30
+constexpr int kConvolveTapRows = (int)kConvolveMaxOrder + 2 * (kConvolveRows - 1); // 21: the kernel's rows between kConvolveRows - 1 rows of zeros
+
+// The kernel matrix as k_image_convolve reads it: rotated, so that k[(dy + kConvolveRows - 1) * 15 + dx] multiplies the window's texel
+// (dx, dy) counted from the window's top left, and between rows of zeros, so that a lane's output row b takes row q - b + kConvolveRows - 1
+// for the staged row q of its block whether or not that staged row lies in b's window. `bias` = ConvolveCoefficients::bias.
+struct ConvolveTaps {
+    int32_t k[kConvolveTapRows * (int)kConvolveMaxOrder];
+    int32_t bias;
+};
+} // namespace
+
+// crh_image_convolve: a 2-D stencil. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the workgroup produces the tile of 64 x 16 texels at
+// (i0, j0). It stages the (64 + order_x - 1) x (16 + order_y - 1) source texels its windows read in LDS, once: wave v takes the staged rows
+// v, v + 4, ... (a wave-uniform row: its wrap is scalar arithmetic), a lane the staged columns lane and lane + 64, whose wrap it computes
+// once; the edge rule (morphology.hpp's wrap, or zero under TRANSPARENT) and the load stage (the clamp to alpha and, with PRESERVE, the
+// unpremultiply) are applied here, so the tap loop has no wrap, no clamp and no division. Every source address is a wrapped or clamped row
+// below h times w plus a wrapped or clamped column below w. Then lane l of wave v produces the four outputs of column l, tile rows
+// 4 v .. 4 v + 3: for each of the order_y + 3 staged rows under them and each kernel column it reads one word at lane + const (consecutive
+// lanes, consecutive banks: no conflict at the pitch of 78), extracts its bytes once and adds it into the four outputs' sums with the
+// coefficients of four rows of the padded table — 16 (with PRESERVE, 12) signed 24-bit multiply-adds per read. The coefficients are a
+// kernel argument and every index into them is wave-uniform: scalar loads, scalar operands. LDS: 9360 B (+ 1 KiB of reciprocals with
+// PRESERVE), so registers and the 32-wave cap, not LDS, bound the occupancy. LDS indices: row 4 v + q <= 12 + order_y + 2 =
+// (16 + order_y - 1) - 1, column l + dx <= 63 + order_x - 1 <= 77.
+template <bool PRESERVE>
+__global__ __launch_bounds__(kConvolveTileW* kConvolveWaves) void k_image_convolve(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, ConvolveTaps taps, uint32_t order_x, uint32_t order_y,
+                                                                                    uint32_t target_x, uint32_t target_y, uint32_t edge, uint32_t* __restrict__ out) {
+    __shared__ uint32_t staged[kConvolveStagedRows * kConvolvePitch];
+    __shared__ uint32_t recip[PRESERVE ? 256 : 1];
+    if (PRESERVE) {
+        recip[threadIdx.x] = k_unpremultiply.r[threadIdx.x];
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i0 = (int)(blockIdx.x * (uint32_t)kConvolveTileW), j0 = (int)(blockIdx.y * (uint32_t)kConvolveTileH);
+    const uint32_t staged_w = (uint32_t)kConvolveTileW + order_x - 1u, staged_h = (uint32_t)kConvolveTileH + order_y - 1u; // (orders <= 15: the host refuses more)
+    int column[2];
+    bool inside[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int x = i0 - (int)target_x + (int)lane + t * kConvolveTileW; // the source column of staged column lane + 64 t
+        column[t] = morphology_wrap(x, (int)w, edge);                      // (under TRANSPARENT: clamped, an address the lane may read)
+        inside[t] = edge != kConvolveTransparent || (uint32_t)x < w;
+    }
+    for (uint32_t q = wave; q < staged_h; q += (uint32_t)kConvolveWaves) {
+        const int y = j0 - (int)target_y + (int)q;
+        const uint32_t* line = src + (size_t)morphology_wrap(y, (int)h, edge) * w;
+        const bool row_inside = edge != kConvolveTransparent || (uint32_t)y < h;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint32_t s = lane + (uint32_t)(t * kConvolveTileW);
+            if (s < staged_w) {
+                const uint32_t texel = line[column[t]];
+                staged[q * (uint32_t)kConvolvePitch + s] = convolve_load<PRESERVE>(row_inside && inside[t] ? texel : 0u, recip);
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t y0 = wave * (uint32_t)kConvolveRows; // the tile row of the lane's first output
+    int32_t n[kConvolveRows][4];
+#pragma unroll
+    for (int b = 0; b < kConvolveRows; ++b)
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) n[b][ch] = taps.bias;
+    for (uint32_t q = 0; q < order_y + (uint32_t)(kConvolveRows - 1); ++q) {
+        const uint32_t* line = staged + (y0 + q) * (uint32_t)kConvolvePitch + lane;
+        const int32_t* row = taps.k + q * kConvolveMaxOrder; // output row b takes the table's row q - b + kConvolveRows - 1
+        for (uint32_t dx = 0; dx < order_x; ++dx) {
+            const uint32_t s = line[dx];
+#pragma unroll
+            for (int b = 0; b < kConvolveRows; ++b) convolve_mad<PRESERVE>(n[b], row[(uint32_t)(kConvolveRows - 1 - b) * kConvolveMaxOrder + dx], s);
+        }
+    }
+    const uint32_t i = (uint32_t)i0 + lane;
+    if (i >= w) return;
+#pragma unroll
+    for (int b = 0; b < kConvolveRows; ++b) {
+        const uint32_t j = (uint32_t)j0 + y0 + (uint32_t)b;
+        if (j >= h) break;
+        const uint32_t centre = staged[(y0 + (uint32_t)b + target_y) * (uint32_t)kConvolvePitch + lane + target_x]; // the loaded texel under the output
+        out[(size_t)j * w + i] = convolve_store<PRESERVE>(n[b], centre);
+    }
+}
+
+void launch_image_convolve(const uint32_t* src, uint32_t w, uint32_t h, const ConvolveCoefficients& f, uint32_t order_x, uint32_t order_y, uint32_t target_x, uint32_t target_y, uint32_t edge,
+                           bool preserve_alpha, uint32_t* out, hipStream_t stream) {
+    ConvolveTaps taps = {};
+    for (uint32_t dy = 0; dy < order_y; ++dy)
+        for (uint32_t dx = 0; dx < order_x; ++dx)
+            taps.k[(dy + (uint32_t)(kConvolveRows - 1)) * kConvolveMaxOrder + dx] = f.k[(order_y - 1u - dy) * order_x + (order_x - 1u - dx)];
+    taps.bias = f.bias;
+    const dim3 grid((w + (uint32_t)kConvolveTileW - 1u) / (uint32_t)kConvolveTileW, (h + (uint32_t)kConvolveTileH - 1u) / (uint32_t)kConvolveTileH); // <= 256 x 1024
+    const dim3 block(kConvolveTileW * kConvolveWaves);
+    if (preserve_alpha) hipLaunchKernelGGL(k_image_convolve<true>, grid, block, 0, stream, src, w, h, taps, order_x, order_y, target_x, target_y, edge, out);
+    else hipLaunchKernelGGL(k_image_convolve<false>, grid, block, 0, stream, src, w, h, taps, order_x, order_y, target_x, target_y, edge, out);
 }
 
 } // namespace crh

@@ -554,6 +554,85 @@ def morphology_texels(pixels, op, radius_x, radius_y=None, edge=BlurEdge.Transpa
     return out
 
 
+MAX_CONVOLVE_ORDER = 15    # CRH_MAX_CONVOLVE_ORDER
+CONVOLVE_MAX_GAIN = 64.0   # CRH_CONVOLVE_MAX_GAIN
+
+
+class ConvolveKernel:
+    """Kernel matrices of Image.convolve as lists of rows, in SVG's orientation (feConvolveMatrix's kernelMatrix carries over unchanged). With
+    divisor=None Image.convolve divides by the sum of the entries, or by 1 where that sum is 0, as SVG does."""
+
+    @staticmethod
+    def identity():
+        return [[1.0]]
+
+    @staticmethod
+    def sharpen(amount=1.0):
+        """The source plus `amount` times its difference from its four neighbours' mean: entries sum to 1"""
+        a = float(amount)
+        return [[0.0, -a, 0.0], [-a, 1.0 + 4.0 * a, -a], [0.0, -a, 0.0]]
+
+    @staticmethod
+    def box(n):
+        """The mean of n x n texels (divisor=None divides by n * n)"""
+        return [[1.0] * int(n) for _ in range(int(n))]
+
+    @staticmethod
+    def emboss():
+        return [[-2.0, -1.0, 0.0], [-1.0, 1.0, 1.0], [0.0, 1.0, 2.0]]
+
+    @staticmethod
+    def laplacian():
+        """5 of 9 taps; the entries sum to 0: use a bias of 0.5 to see both signs, preserve_alpha=True to keep the layer's shape"""
+        return [[0.0, 1.0, 0.0], [1.0, -4.0, 1.0], [0.0, 1.0, 0.0]]
+
+    @staticmethod
+    def sobel_x():
+        """6 of 9 taps: the horizontal gradient"""
+        return [[-1.0, 0.0, 1.0], [-2.0, 0.0, 2.0], [-1.0, 0.0, 1.0]]
+
+    @staticmethod
+    def sobel_y():
+        return [[-1.0, -2.0, -1.0], [0.0, 0.0, 0.0], [1.0, 2.0, 1.0]]
+
+
+def _convolve_arguments(kernel, divisor, bias, target, edge, preserve_alpha):
+    """-> (ConvolveC, the c_float array its kernel points to: keep it alive for as long as the struct is used)"""
+    k = np.asarray(kernel, dtype=np.float32)
+    if k.ndim != 2 or k.size == 0:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"a convolution kernel is a 2-D array of at least one entry, not {k.shape}")
+    order_y, order_x = k.shape
+    if divisor is None:  # SVG: the sum of the entries, or 1 if that is 0
+        total = float(np.float32(np.asarray(kernel, dtype=np.float64).sum()))
+        divisor = total if total != 0.0 else 1.0
+    target_x, target_y = (order_x // 2, order_y // 2) if target is None else target
+    values = (C.c_float * k.size)(*[float(v) for v in k.ravel()])
+    how = _ffi.ConvolveC(order_x, order_y, int(target_x), int(target_y), C.cast(values, C.POINTER(C.c_float)), float(divisor), float(bias), int(edge), int(preserve_alpha))
+    return how, values
+
+
+def convolve_coefficients(kernel, divisor=None, bias=0.0):
+    """crh_convolve_coefficients (host only) -> (k, bias_k): the quantised kernel as an int32 array of the kernel's shape, k = floor(kernel /
+    divisor * 65536 + 0.5), and floor(bias * 65536 + 0.5). Raises ContrastError for what Image.convolve refuses."""
+    how, values = _convolve_arguments(kernel, divisor, bias, None, BlurEdge.Pad, False)
+    k = np.zeros((how.order_y, how.order_x), dtype=np.int32)
+    bias_k = C.c_int32()
+    check(_ffi.load_library().crh_convolve_coefficients(C.byref(how), k.ctypes.data_as(C.POINTER(C.c_int32)), k.size, C.byref(bias_k)))
+    return k, int(bias_k.value)
+
+
+def convolve_texels(pixels, kernel, divisor=None, bias=0.0, target=None, edge=BlurEdge.Pad, preserve_alpha=False):
+    """crh_convolve_texels (host only): the rule of Image.convolve on a (height, width, 4) uint8 array -> a (height, width, 4) uint8 array
+    (include/contrast_hip.h crh_image_convolve states the rule)."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"convolve_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    how, values = _convolve_arguments(kernel, divisor, bias, target, edge, preserve_alpha)
+    out = np.empty_like(pixels)
+    check(_ffi.load_library().crh_convolve_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, C.byref(how), out.ctypes.data))
+    return out
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -684,6 +763,21 @@ class Image:
     def erode(self, radius_x, radius_y=None, edge=BlurEdge.Transparent):
         """morphology(MorphologyOp.Erode, ...): a choke, a negative spread."""
         return self.morphology(MorphologyOp.Erode, radius_x, radius_y, edge)
+
+    def convolve(self, kernel, divisor=None, bias=0.0, target=None, edge=BlurEdge.Pad, preserve_alpha=False):
+        """crh_image_convolve -> a new Image of one level, of this image's size and origin: this image's level 0 through the kernel matrix
+        `kernel` (a 2-D array of up to 15 x 15 entries, in SVG's orientation; ConvolveKernel has presets), integer and bit-exact, built on
+        the device and complete when this returns (a synchronous call). divisor=None means the sum of the entries, or 1 if that is 0;
+        target=None means (order_x // 2, order_y // 2); |bias| <= 1 is added in units of the full range. preserve_alpha=True keeps every
+        texel's alpha and convolves the unpremultiplied colours. The result has this image's size under every edge. This image is not modified."""
+        how, values = _convolve_arguments(kernel, divisor, bias, target, edge, preserve_alpha)
+        image = Image.__new__(Image)
+        image.renderer, image.lib = self.renderer, self.lib
+        handle = C.c_void_p()
+        check(self.lib.crh_image_convolve(self.handle, C.byref(how), C.byref(handle)))
+        image.handle = handle
+        image.width, image.height, image.origin = self.width, self.height, self.origin
+        return image
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

@@ -682,6 +682,62 @@ crh_status crh_morphology_size(uint32_t width, uint32_t height, uint32_t op, uin
 crh_status crh_morphology_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge,
                                  void* out_rgba8); /* host only: the rule on a whole image in host memory */
 crh_status crh_image_morphology(const crh_image* src, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, crh_image** out);
+/* Convolution: an image through a kernel matrix of up to 15 x 15 entries, on the device (SVG feConvolveMatrix) — sharpen and unsharp,
+ * emboss, Sobel, Prewitt and Laplacian edge detection, small box and tent filters, any 3 x 3 or 5 x 5 kernel of an image-processing text.
+ * The model is integer and bit-exact: all values are 8-bit codes, all arithmetic is signed 32-bit, and the tests check every byte.
+ *   coefficients k[r][c] = (int32) floor((double) kernel[r][c] / (double) divisor * 65536 + 0.5), bias_k = floor((double) bias * 65536 + 0.5).
+ *                The double quotient is compared with CRH_CONVOLVE_MAX_GAIN before the conversion, and sum |k[r][c]| <= 64 * 65536 = 2^22,
+ *                otherwise the call is refused (the gain limit). Hence |sum k c| <= 2^22 * 255 = 1 069 547 520; with 255 * 65536 of bias
+ *                and 32768 of rounding the largest magnitude is 1 086 291 968 < 2^31, and every |k| <= 2^22 is a signed 24-bit operand.
+ *   load         each colour code is clamped to its alpha, c = min(c, a), as compositing and the colour filter do.
+ *   window       n_ch(i, j) = sum_r sum_c k[r][c] * s_ch(i - target_x + (order_x - 1 - c), j - target_y + (order_y - 1 - r))
+ *                             + 255 * bias_k + 32768,
+ *                v_ch = clamp(n_ch >> 16, 0, 255) with an arithmetic shift: one rounding of the exact value. The kernel is rotated by
+ *                180 degrees, as SVG's is (a true convolution), so SVG kernels carry over unchanged; (target_x, target_y) is the kernel
+ *                cell that lies on the output texel (SVG targetX / targetY).
+ *   edge         a crh_blur_edge. PAD, REPEAT and REFLECT read wrap(i, n) by exactly the rules of the image-paint block above, any
+ *                number of periods out (an order of 15 on a 1-texel axis is legal); TRANSPARENT reads (0, 0, 0, 0) outside the source.
+ *   preserve_alpha == 0   s is the loaded premultiplied texel, all four channels; a' = v_a, c' = min(v_c, v_a).
+ *   preserve_alpha == 1   the alpha is not convolved: a' = a(i, j). The colour channels of s are the straight codes u_c of the colour
+ *                filter's unpremultiply, u_c = (255 c + a / 2) / a (0 for a = 0), and c' = (v_c * a' + 127) / 255, its premultiply.
+ * Hence: the 1 x 1 kernel [1] with divisor 1 and bias 0 returns every loaded texel exactly in both modes (under preserve_alpha by the
+ * colour filter's identity argument); a kernel with a single 1 at (r, c) is a translation, and under TRANSPARENT equals crh_image_composite
+ * COPY onto a transparent backdrop of the same size at the offset (c + target_x - (order_x - 1), r + target_y - (order_y - 1)), byte for
+ * byte; a kernel whose quantised entries sum to 65536 + e returns a constant image exactly under the three same-size edges when |e| <= 128
+ * (and |e| <= 112 always when the real entries sum to the divisor: each of at most 225 taps rounds by 1/2); c' <= a' always; and with
+ * preserve_alpha == 0 every result is within 1/2 + 255 (order_x order_y + 1) / 2^17 codes of the real-valued formula on the loaded codes.
+ * crh_convolve_validate, crh_convolve_coefficients and crh_convolve_texels are host only (no renderer, no device). coefficients: the
+ * quantised kernel, order_x * order_y entries row-major into k (k == NULL: validate only) and bias_k (may be NULL), as crh_blur_taps
+ * hands out taps. texels: the rule on a whole image in host memory, 1 <= width, height <= 16384, width * height * 4 bytes in the order
+ * r g b a at any alignment, row 0 first, into out_rgba8 of the same size; out_rgba8 == rgba8 is refused.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out untouched: a null argument or
+ * kernel is CRH_ERR_INVALID_ARGUMENT; a non-finite kernel entry, divisor or bias is CRH_ERR_NON_FINITE; an order of 0 or above
+ * CRH_MAX_CONVOLVE_ORDER, a target >= its order, divisor 0, |bias| > 1, edge > 3, preserve_alpha > 1, the gain limit, a size outside
+ * [1, 16384], out_rgba8 == rgba8, and a capacity below order_x * order_y given together with k are CRH_ERR_INVALID_ARGUMENT with a
+ * crh_last_error text. The source must belong to a renderer.
+ * crh_image_convolve gives a fresh image of the source's renderer and size with one level (crh_image_generate_mipmaps, blur, composite,
+ * colour filter, morphology, image paints and crh_frame_load_image work on it), complete when the call returns: k_image_convolve runs on
+ * the renderer's stream, a 2-D stencil that stages a tile and its halo in LDS with the edge and the load applied, the coefficients in
+ * scalar registers. Only level 0 of the source is read and the source is not modified. A failed allocation or launch frees everything
+ * and returns CRH_ERR_HIP.
+ * Limits: the call is synchronous, like its siblings — one wait per call; kernels are at most 15 x 15; the result has the source's size
+ * under every edge — unlike blur and dilate nothing grows, and a caller who wants a wide kernel's spill composites the source onto a
+ * larger transparent backdrop first; there is no kernelUnitLength; codes are taken as they are, with no gamma handling. */
+#define CRH_MAX_CONVOLVE_ORDER 15u
+#define CRH_CONVOLVE_MAX_GAIN 64.0f
+typedef struct crh_convolve {
+    uint32_t order_x, order_y;   /* 1 .. CRH_MAX_CONVOLVE_ORDER columns and rows of the kernel */
+    uint32_t target_x, target_y; /* < order: the kernel cell that lies on the output texel (SVG targetX / targetY) */
+    const float* kernel;         /* [order_y][order_x], row-major */
+    float divisor;               /* finite, not 0 */
+    float bias;                  /* |bias| <= 1 */
+    uint32_t edge;               /* crh_blur_edge */
+    uint32_t preserve_alpha;     /* 0 / 1 */
+} crh_convolve;
+crh_status crh_convolve_validate(const crh_convolve* how); /* host only */
+crh_status crh_convolve_coefficients(const crh_convolve* how, int32_t* k, uint32_t capacity, int32_t* bias_k); /* host only: the quantised kernel */
+crh_status crh_convolve_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_convolve* how, void* out_rgba8); /* host only */
+crh_status crh_image_convolve(const crh_image* src, const crh_convolve* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

@@ -693,6 +693,44 @@ inline std::vector<uint8_t> morphology_texels(uint32_t width, uint32_t height, c
     check(crh_morphology_texels(width, height, texels.data(), (uint32_t)op, radius_x, radius_y, (uint32_t)edge, out.data()));
     return out;
 }
+// Convolution (include/contrast_hip.h crh_image_convolve states the rule): a kernel matrix of order_x columns and order_y rows, row-major, in
+// SVG's orientation. The presets divide by 1 unless they say otherwise; target = the kernel cell on the output texel, the centre by default.
+struct ConvolveKernel {
+    uint32_t order_x = 1, order_y = 1;
+    std::vector<float> values = {1.0f};
+    float divisor = 1.0f, bias = 0.0f;
+    uint32_t target_x = 0, target_y = 0;
+    ConvolveKernel() = default;
+    ConvolveKernel(uint32_t ox, uint32_t oy, std::vector<float> v, float d = 1.0f, float b = 0.0f) : order_x(ox), order_y(oy), values(std::move(v)), divisor(d), bias(b), target_x(ox / 2u), target_y(oy / 2u) {}
+    static ConvolveKernel identity() { return ConvolveKernel(); }
+    static ConvolveKernel sharpen(float amount = 1.0f) { return ConvolveKernel(3, 3, {0, -amount, 0, -amount, 1.0f + 4.0f * amount, -amount, 0, -amount, 0}); }
+    static ConvolveKernel box(uint32_t n) { return ConvolveKernel(n, n, std::vector<float>((size_t)n * n, 1.0f), (float)(n * n)); } // the mean of n x n texels
+    static ConvolveKernel emboss() { return ConvolveKernel(3, 3, {-2, -1, 0, -1, 1, 1, 0, 1, 2}); }
+    static ConvolveKernel laplacian() { return ConvolveKernel(3, 3, {0, 1, 0, 1, -4, 1, 0, 1, 0}); }
+    static ConvolveKernel sobel_x() { return ConvolveKernel(3, 3, {-1, 0, 1, -2, 0, 2, -1, 0, 1}); }
+    static ConvolveKernel sobel_y() { return ConvolveKernel(3, 3, {-1, -2, -1, 0, 0, 0, 1, 2, 1}); }
+    // the C struct; it points into `values`, so it lives no longer than this kernel
+    crh_convolve to_c(BlurEdge edge, bool preserve_alpha) const {
+        if (values.size() != (size_t)order_x * order_y) throw Error(CRH_ERR_INVALID_ARGUMENT);
+        return crh_convolve{order_x, order_y, target_x, target_y, values.data(), divisor, bias, (uint32_t)edge, preserve_alpha ? 1u : 0u};
+    }
+};
+// crh_convolve_coefficients (host only) -> the quantised kernel, order_x * order_y entries row-major, and bias_k behind them
+inline std::vector<int32_t> convolve_coefficients(const ConvolveKernel& kernel) {
+    const crh_convolve how = kernel.to_c(BlurEdge::Pad, false);
+    std::vector<int32_t> out((size_t)kernel.order_x * kernel.order_y + 1u);
+    check(crh_convolve_coefficients(&how, out.data(), (uint32_t)out.size() - 1u, &out.back()));
+    return out;
+}
+// crh_convolve_texels (host only): the rule on a width x height image of RGBA8 in host memory -> the bytes of the result, of the same size
+inline std::vector<uint8_t> convolve_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, const ConvolveKernel& kernel, BlurEdge edge = BlurEdge::Pad,
+                                            bool preserve_alpha = false) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const crh_convolve how = kernel.to_c(edge, preserve_alpha);
+    std::vector<uint8_t> out(texels.size());
+    check(crh_convolve_texels(width, height, texels.data(), &how, out.data()));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -780,6 +818,16 @@ class Image {
     Image dilate(uint32_t radius) const { return morphology(MorphologyOp::Dilate, radius, radius); }
     Image erode(uint32_t radius_x, uint32_t radius_y, BlurEdge edge = BlurEdge::Transparent) const { return morphology(MorphologyOp::Erode, radius_x, radius_y, edge); }
     Image erode(uint32_t radius) const { return morphology(MorphologyOp::Erode, radius, radius); }
+    // crh_image_convolve -> a new Image of one level, of this image's size and origin: this image's level 0 through a kernel matrix of up to
+    // 15 x 15 entries; integer and bit-exact, complete on return (a synchronous call). preserve_alpha keeps every texel's alpha and convolves
+    // the unpremultiplied colours. The result has this image's size under every edge. This image is not modified.
+    Image convolve(const ConvolveKernel& kernel, BlurEdge edge = BlurEdge::Pad, bool preserve_alpha = false) const {
+        const crh_convolve how = kernel.to_c(edge, preserve_alpha);
+        Image image;
+        check(crh_image_convolve(handle_, &how, &image.handle_));
+        image.width_ = width_, image.height_ = height_, image.origin_ = origin_;
+        return image;
+    }
 
   private:
     Image() = default;

@@ -877,6 +877,74 @@ pub fn morphology_texels(width: u32, height: u32, texels: &[u8], op: MorphologyO
     status(unsafe { ffi::crh_morphology_texels(width, height, texels.as_ptr() as *const _, op as u32, radius_x, radius_y, edge as u32, out.as_mut_ptr() as *mut _) })?;
     Ok((w, h, out))
 }
+/// A kernel matrix of `Image::convolve` (`crh_convolve`): `order_x` columns and `order_y` rows, row-major, in SVG's orientation
+/// (feConvolveMatrix's kernelMatrix carries over unchanged); `target` = the kernel cell on the output texel.
+#[derive(Clone, PartialEq, Debug)]
+pub struct ConvolveKernel {
+    pub order_x: u32,
+    pub order_y: u32,
+    pub values: Vec<f32>,
+    pub divisor: f32,
+    pub bias: f32,
+    pub target: (u32, u32),
+}
+impl ConvolveKernel {
+    /// The target is the centre, the bias 0
+    pub fn new(order_x: u32, order_y: u32, values: Vec<f32>, divisor: f32) -> ConvolveKernel {
+        assert_eq!(values.len(), order_x as usize * order_y as usize);
+        ConvolveKernel { order_x, order_y, values, divisor, bias: 0.0, target: (order_x / 2, order_y / 2) }
+    }
+    pub fn identity() -> ConvolveKernel {
+        ConvolveKernel::new(1, 1, vec![1.0], 1.0)
+    }
+    pub fn sharpen(amount: f32) -> ConvolveKernel {
+        ConvolveKernel::new(3, 3, vec![0.0, -amount, 0.0, -amount, 1.0 + 4.0 * amount, -amount, 0.0, -amount, 0.0], 1.0)
+    }
+    /// The mean of n x n texels
+    pub fn box_filter(n: u32) -> ConvolveKernel {
+        ConvolveKernel::new(n, n, vec![1.0; (n * n) as usize], (n * n) as f32)
+    }
+    pub fn emboss() -> ConvolveKernel {
+        ConvolveKernel::new(3, 3, vec![-2.0, -1.0, 0.0, -1.0, 1.0, 1.0, 0.0, 1.0, 2.0], 1.0)
+    }
+    pub fn laplacian() -> ConvolveKernel {
+        ConvolveKernel::new(3, 3, vec![0.0, 1.0, 0.0, 1.0, -4.0, 1.0, 0.0, 1.0, 0.0], 1.0)
+    }
+    pub fn sobel_x() -> ConvolveKernel {
+        ConvolveKernel::new(3, 3, vec![-1.0, 0.0, 1.0, -2.0, 0.0, 2.0, -1.0, 0.0, 1.0], 1.0)
+    }
+    pub fn sobel_y() -> ConvolveKernel {
+        ConvolveKernel::new(3, 3, vec![-1.0, -2.0, -1.0, 0.0, 0.0, 0.0, 1.0, 2.0, 1.0], 1.0)
+    }
+    /// The C struct; it points into `values`, so it is used no longer than `self` lives
+    fn to_c(&self, edge: BlurEdge, preserve_alpha: bool) -> ffi::crh_convolve {
+        assert_eq!(self.values.len(), self.order_x as usize * self.order_y as usize);
+        ffi::crh_convolve { order_x: self.order_x, order_y: self.order_y, target_x: self.target.0, target_y: self.target.1, kernel: self.values.as_ptr(), divisor: self.divisor, bias: self.bias,
+                            edge: edge as u32, preserve_alpha: preserve_alpha as u32 }
+    }
+}
+/// `crh_convolve_validate` (host only): what `Image::convolve` would refuse
+pub fn convolve_validate(kernel: &ConvolveKernel, edge: BlurEdge, preserve_alpha: bool) -> Result<(), Error> {
+    let how = kernel.to_c(edge, preserve_alpha);
+    status(unsafe { ffi::crh_convolve_validate(&how) })
+}
+/// `crh_convolve_coefficients` (host only) -> (k, bias_k): the quantised kernel, order_x * order_y entries row-major
+pub fn convolve_coefficients(kernel: &ConvolveKernel) -> Result<(Vec<i32>, i32), Error> {
+    let how = kernel.to_c(BlurEdge::Pad, false);
+    let mut k = vec![0i32; kernel.values.len()];
+    let mut bias_k = 0i32;
+    status(unsafe { ffi::crh_convolve_coefficients(&how, k.as_mut_ptr(), k.len() as u32, &mut bias_k) })?;
+    Ok((k, bias_k))
+}
+/// `crh_convolve_texels` (host only): the rule on a width x height image of RGBA8 in host memory -> the texels of the result, of the same size
+/// (include/contrast_hip.h, `crh_image_convolve`, states the rule).
+pub fn convolve_texels(width: u32, height: u32, texels: &[u8], kernel: &ConvolveKernel, edge: BlurEdge, preserve_alpha: bool) -> Result<Vec<u8>, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    let how = kernel.to_c(edge, preserve_alpha);
+    let mut out = vec![0u8; texels.len()];
+    status(unsafe { ffi::crh_convolve_texels(width, height, texels.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -975,6 +1043,15 @@ impl Image {
     }
     pub fn erode(&self, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<Image, Error> {
         self.morphology(MorphologyOp::Erode, radius_x, radius_y, edge)
+    }
+    /// `crh_image_convolve` -> a new `Image` of one level, of this image's size and origin: this image's level 0 through a kernel matrix of
+    /// up to `CRH_MAX_CONVOLVE_ORDER` entries per axis; integer and bit-exact, complete on return (a synchronous call). `preserve_alpha` keeps
+    /// every texel's alpha and convolves the unpremultiplied colours. The size is the source's under every edge. This image is not modified.
+    pub fn convolve(&self, kernel: &ConvolveKernel, edge: BlurEdge, preserve_alpha: bool) -> Result<Image, Error> {
+        let how = kernel.to_c(edge, preserve_alpha);
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_convolve(self.raw, &how, &mut raw) })?;
+        Ok(Image { raw, width: self.width, height: self.height, origin: self.origin })
     }
 }
 impl Drop for Image {
