@@ -7,10 +7,11 @@ the reference's interface; it has no CPU fallback and never imports the oracle.
 from ._ffi import ContrastError, PathBatch  # noqa: F401
 from .path import (Cap, CurveApproximation, DashInterval, DynamicStrokeOptions, Join, Path, SegmentType, StrokeOptions,  # noqa: F401
                    batch_from_shapes)
-from .renderer import (BlendMode, BlurEdge, ColorMatrix, CompositeOp, ConvolveKernel, Filter, GradientStop, Image, ImagePaint, MorphologyOp, Paint,  # noqa: F401
-                       Spread, blur_taps, color_filter_texels, composite_texels, convolve_coefficients, convolve_texels, morphology_size, morphology_texels)
+from .renderer import (BlendMode, BlurEdge, ColorMatrix, CompositeOp, ConvolveKernel, DistantLight, Filter, GradientStop, Image, ImagePaint, LightingOp,  # noqa: F401
+                       MorphologyOp, Paint, PointLight, SpotLight, Spread, blur_taps, color_filter_texels, composite_texels, convolve_coefficients, convolve_texels,
+                       lighting_texels, morphology_size, morphology_texels)
 
 __all__ = ["ContrastError", "PathBatch", "Cap", "CurveApproximation", "DashInterval", "DynamicStrokeOptions", "Join", "Path", "SegmentType",
            "StrokeOptions", "batch_from_shapes", "GradientStop", "Paint", "Spread", "Filter", "Image", "ImagePaint", "BlurEdge", "blur_taps",
            "CompositeOp", "BlendMode", "composite_texels", "ColorMatrix", "color_filter_texels", "MorphologyOp", "morphology_size", "morphology_texels",
-           "ConvolveKernel", "convolve_coefficients", "convolve_texels"]
+           "ConvolveKernel", "convolve_coefficients", "convolve_texels", "LightingOp", "DistantLight", "PointLight", "SpotLight", "lighting_texels"]

@@ -234,6 +234,12 @@ class ConvolveC(C.Structure):  # crh_convolve
                 ("divisor", C.c_float), ("bias", C.c_float), ("edge", C.c_uint32), ("preserve_alpha", C.c_uint32)]
 
 
+class LightingC(C.Structure):  # crh_lighting
+    _fields_ = [("op", C.c_uint32), ("light", C.c_uint32), ("edge", C.c_uint32), ("surface_scale", C.c_float), ("constant", C.c_float), ("specular_exponent", C.c_float),
+                ("color", C.c_float * 3), ("azimuth", C.c_float), ("elevation", C.c_float), ("position", C.c_float * 3), ("points_at", C.c_float * 3),
+                ("spot_exponent", C.c_float), ("cone_angle", C.c_float)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -325,6 +331,9 @@ def load_library():
         "crh_convolve_coefficients": (C.c_int, [C.POINTER(ConvolveC), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32)]),
         "crh_convolve_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.POINTER(ConvolveC), V]),
         "crh_image_convolve": (C.c_int, [V, C.POINTER(ConvolveC), C.POINTER(V)]),
+        "crh_lighting_validate": (C.c_int, [C.POINTER(LightingC)]),
+        "crh_lighting_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.POINTER(LightingC), V]),
+        "crh_image_lighting": (C.c_int, [V, C.POINTER(LightingC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

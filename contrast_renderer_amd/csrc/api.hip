@@ -18,6 +18,7 @@
 #include "composite.hpp"
 #include "convolve.hpp"
 #include "launch.hpp"
+#include "lighting.hpp"
 #include "morphology.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
@@ -3296,6 +3297,96 @@ crh_status crh_image_convolve(const crh_image* src, const crh_convolve* how, crh
                           static_cast<uint32_t*>(image->pixels->p), r->stream);
     bool ok = hip_ok(hipGetLastError(), "k_image_convolve");
     ok = hip_ok(r->sync(), "sync(convolve)") && ok;
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+namespace {
+static_assert(CRH_LIGHTING_DIFFUSE == kLightingDiffuse && CRH_LIGHTING_SPECULAR == kLightingSpecular && CRH_LIGHT_DISTANT == kLightDistant && CRH_LIGHT_POINT == kLightPoint &&
+                  CRH_LIGHT_SPOT == kLightSpot && CRH_BLUR_EDGE_TRANSPARENT == kLightingTransparent,
+              "lighting.hpp's ops, lights and edge are the header's");
+crh_status lighting_error(const char* what) {
+    g_error = std::string("crh_lighting_validate: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+// validates and prepares: the one check of the three entry points, and the one way from the caller's floats to the rule's constants.
+// Only the fields that op and light use are read: first whether they are finite, then their ranges.
+crh_status lighting_constants(const crh_lighting* how, LightingConstants* f) {
+    if (!how) return lighting_error("a null argument");
+    if (how->op > CRH_LIGHTING_SPECULAR) return lighting_error("op is above CRH_LIGHTING_SPECULAR");
+    if (how->light > CRH_LIGHT_SPOT) return lighting_error("light is above CRH_LIGHT_SPOT");
+    if (how->edge > CRH_BLUR_EDGE_REFLECT) return lighting_error("edge is above CRH_BLUR_EDGE_REFLECT");
+    const bool specular = how->op == CRH_LIGHTING_SPECULAR, distant = how->light == CRH_LIGHT_DISTANT, spot = how->light == CRH_LIGHT_SPOT;
+    bool finite = std::isfinite(how->surface_scale) && std::isfinite(how->constant) && (!specular || std::isfinite(how->specular_exponent));
+    for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(how->color[c]);
+    if (distant) finite = finite && std::isfinite(how->azimuth) && std::isfinite(how->elevation);
+    else
+        for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(how->position[c]);
+    if (spot) {
+        for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(how->points_at[c]);
+        finite = finite && std::isfinite(how->spot_exponent) && std::isfinite(how->cone_angle);
+    }
+    if (!finite) return CRH_ERR_NON_FINITE;
+    if (std::fabs(how->surface_scale) > 256.0f) return lighting_error("surface_scale is outside [-256, 256]");
+    if (how->constant < 0.0f || how->constant > 256.0f) return lighting_error("constant is outside [0, 256]");
+    if (specular && (how->specular_exponent < 1.0f || how->specular_exponent > 128.0f)) return lighting_error("specular_exponent is outside [1, 128]");
+    for (int c = 0; c < 3; ++c)
+        if (how->color[c] < 0.0f || how->color[c] > 1.0f) return lighting_error("a colour is outside [0, 1]");
+    if (distant) {
+        if (std::fabs(how->azimuth) > 3600.0f || std::fabs(how->elevation) > 3600.0f) return lighting_error("azimuth or elevation is outside [-3600, 3600]");
+    } else {
+        for (int c = 0; c < 3; ++c)
+            if (std::fabs(how->position[c]) > 1048576.0f) return lighting_error("a position is outside [-2^20, 2^20]");
+    }
+    if (spot) {
+        for (int c = 0; c < 3; ++c)
+            if (std::fabs(how->points_at[c]) > 1048576.0f) return lighting_error("a points_at is outside [-2^20, 2^20]");
+        if (how->points_at[0] == how->position[0] && how->points_at[1] == how->position[1] && how->points_at[2] == how->position[2]) return lighting_error("points_at is position");
+        if (how->spot_exponent < 0.0f || how->spot_exponent > 128.0f) return lighting_error("spot_exponent is outside [0, 128]");
+        if (how->cone_angle < 0.0f || how->cone_angle > 90.0f) return lighting_error("cone_angle is neither 0 nor in (0, 90]");
+    }
+    lighting_prepare(how->op, how->light, how->surface_scale, how->constant, how->specular_exponent, how->color, how->azimuth, how->elevation, how->position, how->points_at,
+                     how->spot_exponent, how->cone_angle, f);
+    return CRH_OK;
+}
+crh_status lighting_size(uint32_t width, uint32_t height) {
+    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return lighting_error("width and height lie in [1, 16384]");
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_lighting_validate(const crh_lighting* how) {
+    LightingConstants f;
+    return lighting_constants(how, &f);
+}
+crh_status crh_lighting_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_lighting* how, void* out_rgba8) {
+    if (!rgba8 || !out_rgba8) return lighting_error("a null argument");
+    if (rgba8 == out_rgba8) return lighting_error("out_rgba8 is rgba8");
+    LightingConstants f;
+    crh_status st = lighting_constants(how, &f);
+    if (st != CRH_OK) return st;
+    st = lighting_size(width, height);
+    if (st != CRH_OK) return st;
+    lighting_run(static_cast<const uint8_t*>(rgba8), width, height, f, how->op, how->light, how->edge, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_lighting(const crh_image* src, const crh_lighting* how, crh_image** out) {
+    if (!src || !src->renderer || !out) return lighting_error("a null argument");
+    LightingConstants f;
+    crh_status st = lighting_constants(how, &f);
+    if (st != CRH_OK) return st;
+    st = lighting_size(src->width, src->height);
+    if (st != CRH_OK) return st;
+    crh_renderer* r = src->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    st = new_image(r, src->width, src->height, &image);
+    if (st != CRH_OK) return st;
+    launch_image_lighting(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, f, how->op, how->light, how->edge, static_cast<uint32_t*>(image->pixels->p), r->stream);
+    bool ok = hip_ok(hipGetLastError(), "k_image_lighting");
+    ok = hip_ok(r->sync(), "sync(lighting)") && ok;
     if (!ok) {
         delete image;
         return CRH_ERR_HIP;

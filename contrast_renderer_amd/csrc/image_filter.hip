@@ -6,6 +6,7 @@
 // crh_image_morphology: k_image_morph_h and k_image_morph_v take the per-channel min or max over a rectangle with the rule of morphology.hpp,
 // at a cost per texel that does not grow linearly with the radius.
 // crh_image_convolve: k_image_convolve puts an image through a kernel matrix with the rule of convolve.hpp, a 2-D stencil over a tile and its halo in LDS.
+// crh_image_lighting: k_image_lighting lights the alpha channel as a height field with the rule of lighting.hpp, binary64 arithmetic on a 3 x 3 stencil.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include "composite.hpp"
 #include "convolve.hpp"
 #include "launch.hpp"
+#include "lighting.hpp"
 #include "morphology.hpp"
 
 namespace crh {
@@ -523,6 +525,104 @@ void launch_image_convolve(const uint32_t* src, uint32_t w, uint32_t h, const Co
     const dim3 block(kConvolveTileW * kConvolveWaves);
     if (preserve_alpha) hipLaunchKernelGGL(k_image_convolve<true>, grid, block, 0, stream, src, w, h, taps, order_x, order_y, target_x, target_y, edge, out);
     else hipLaunchKernelGGL(k_image_convolve<false>, grid, block, 0, stream, src, w, h, taps, order_x, order_y, target_x, target_y, edge, out);
+}
+
+namespace {
+constexpr int kLightingTileW = 64; // output columns per workgroup, one per lane of a wave
+constexpr int kLightingWaves = 4;  // waves per workgroup
+#ifndef CRH_LIGHTING_ROWS
+#define CRH_LIGHTING_ROWS 4 // (a build with -DCRH_LIGHTING_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the row blocking was measured)
+#endif
+#ifndef CRH_LIGHTING_FLAT_SKIP
+#define CRH_LIGHTING_FLAT_SKIP 1 // (-DCRH_LIGHTING_FLAT_SKIP=0: a distant light's arithmetic on every texel, the comparison of DESIGN.md)
+#endif
+constexpr int kLightingRows = CRH_LIGHTING_ROWS;                   // adjacent output rows per lane: the column sums of a staged row serve three of them
+constexpr int kLightingTileH = kLightingWaves * kLightingRows;     // 16 output rows per workgroup
+constexpr int kLightingPitch = kLightingTileW + 2;                 // 66 words per staged row: the tile and one texel of halo on each side
+constexpr int kLightingStagedRows = kLightingTileH + 2;            // 18
+} // namespace
+
+// crh_image_lighting: a 3 x 3 stencil on the alpha channel under binary64 arithmetic. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the
+// workgroup produces the tile of 64 x 16 texels at (i0, j0). It stages the 66 x 18 alpha codes its gradients read in LDS, one word each,
+// once: wave v takes the staged rows v, v + 4, ... (a wave-uniform row: its wrap is scalar arithmetic), a lane the staged columns lane and
+// (lanes 0 and 1) lane + 64, whose wrap it computes once; the edge rule (morphology.hpp's wrap, or zero under TRANSPARENT) is applied here,
+// so the arithmetic never branches on position. Only the alpha byte of a source texel is loaded (one byte load at texel * 4 + 3). Every
+// source address is a wrapped or clamped row below h times w plus a wrapped or clamped column below w. Then lane l of wave v produces the
+// four outputs of column l, tile rows 4 v .. 4 v + 3, walking down the staged rows 4 v .. 4 v + 5: of each it reads the three codes at lane,
+// lane + 1, lane + 2 (consecutive lanes, consecutive banks: no conflict at the pitch of 66) and keeps their difference (right - left) and
+// their sum (left + 2 mid + right) for the three output rows that use them, so an output costs 3 LDS reads, not 9. gx and gy are integer
+// sums of those; the rest is lighting_texel, specialised on (OP, LIGHT): a distant diffuse call carries no per-texel L and no power.
+// Under a distant light the result depends on (gx, gy) alone, and lanes whose gradient is zero — most of any real layer — take the texel
+// the host computed with the same function (f.flat); a wave in which every lane does skips the arithmetic. LDS: 4752 B, so registers and
+// the 32-wave cap, not LDS, bound the occupancy. LDS indices: row 4 v + b + 2 <= 12 + 3 + 2 = 17, column l + 2 <= 65.
+template <uint32_t OP, uint32_t LIGHT>
+__global__ __launch_bounds__(kLightingTileW* kLightingWaves) void k_image_lighting(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, LightingConstants f, uint32_t edge,
+                                                                                    uint32_t* __restrict__ out) {
+    __shared__ uint32_t staged[kLightingStagedRows * kLightingPitch];
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i0 = (int)(blockIdx.x * (uint32_t)kLightingTileW), j0 = (int)(blockIdx.y * (uint32_t)kLightingTileH);
+    int column[2];
+    bool inside[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int x = i0 - 1 + (int)lane + t * kLightingTileW; // the source column of staged column lane + 64 t
+        column[t] = morphology_wrap(x, (int)w, edge);           // (under TRANSPARENT: clamped, an address the lane may read)
+        inside[t] = edge != kLightingTransparent || (uint32_t)x < w;
+    }
+    for (uint32_t q = wave; q < (uint32_t)kLightingStagedRows; q += (uint32_t)kLightingWaves) {
+        const int y = j0 - 1 + (int)q;
+        const uint8_t* line = src + (size_t)morphology_wrap(y, (int)h, edge) * w * 4u;
+        const bool row_inside = edge != kLightingTransparent || (uint32_t)y < h;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint32_t s = lane + (uint32_t)(t * kLightingTileW);
+            if (s < (uint32_t)kLightingPitch) {
+                const uint32_t alpha = line[(size_t)column[t] * 4u + 3u];
+                staged[q * (uint32_t)kLightingPitch + s] = row_inside && inside[t] ? alpha : 0u;
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t y0 = wave * (uint32_t)kLightingRows; // the tile row of the lane's first output
+    const uint32_t i = (uint32_t)i0 + lane;
+    // the staged rows above and on the first output: their differences, sums and the code under the output
+    const uint32_t* line = staged + y0 * (uint32_t)kLightingPitch + lane;
+    int diff_above = (int)line[2] - (int)line[0], sum_above = (int)(line[0] + 2u * line[1] + line[2]);
+    line += kLightingPitch;
+    int diff_here = (int)line[2] - (int)line[0], sum_here = (int)(line[0] + 2u * line[1] + line[2]);
+    uint32_t alpha = line[1];
+#pragma unroll
+    for (int b = 0; b < kLightingRows; ++b) {
+        line += kLightingPitch;
+        const uint32_t below = line[1];
+        const int diff_below = (int)line[2] - (int)line[0], sum_below = (int)(line[0] + 2u * below + line[2]);
+        const int gx = diff_above + 2 * diff_here + diff_below, gy = sum_below - sum_above;
+        const uint32_t j = (uint32_t)j0 + y0 + (uint32_t)b;
+        if (i < w && j < h) {
+            uint32_t texel;
+            if (CRH_LIGHTING_FLAT_SKIP && LIGHT == kLightDistant && gx == 0 && gy == 0) texel = f.flat;
+            else texel = lighting_texel<OP, LIGHT>(f, gx, gy, alpha, i, j);
+            out[(size_t)j * w + i] = texel;
+        }
+        diff_above = diff_here, diff_here = diff_below, sum_above = sum_here, sum_here = sum_below, alpha = below;
+    }
+}
+
+void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const LightingConstants& f, uint32_t op, uint32_t light, uint32_t edge, uint32_t* out, hipStream_t stream) {
+    const dim3 grid((w + (uint32_t)kLightingTileW - 1u) / (uint32_t)kLightingTileW, (h + (uint32_t)kLightingTileH - 1u) / (uint32_t)kLightingTileH); // <= 256 x 1024
+    const dim3 block(kLightingTileW * kLightingWaves);
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(src);
+#define CRH_LIGHTING_LAUNCH(OP, LIGHT) hipLaunchKernelGGL((k_image_lighting<OP, LIGHT>), grid, block, 0, stream, bytes, w, h, f, edge, out)
+    if (op == kLightingDiffuse) {
+        if (light == kLightDistant) CRH_LIGHTING_LAUNCH(kLightingDiffuse, kLightDistant);
+        else if (light == kLightPoint) CRH_LIGHTING_LAUNCH(kLightingDiffuse, kLightPoint);
+        else CRH_LIGHTING_LAUNCH(kLightingDiffuse, kLightSpot);
+    } else {
+        if (light == kLightDistant) CRH_LIGHTING_LAUNCH(kLightingSpecular, kLightDistant);
+        else if (light == kLightPoint) CRH_LIGHTING_LAUNCH(kLightingSpecular, kLightPoint);
+        else CRH_LIGHTING_LAUNCH(kLightingSpecular, kLightSpot);
+    }
+#undef CRH_LIGHTING_LAUNCH
 }
 
 } // namespace crh

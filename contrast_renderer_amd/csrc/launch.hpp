@@ -58,6 +58,9 @@ void launch_image_morph_v(const uint32_t* in, uint32_t in_h, uint32_t* out, uint
 struct ConvolveCoefficients;
 void launch_image_convolve(const uint32_t* src, uint32_t w, uint32_t h, const ConvolveCoefficients& f, uint32_t order_x, uint32_t order_y, uint32_t target_x, uint32_t target_y, uint32_t edge,
                            bool preserve_alpha, uint32_t* out, hipStream_t stream);
+// image_filter.hip: crh_image_lighting's kernel (lighting.hpp holds the rule; op < 2, light < 3, edge < 4). src and out: h rows of w texels.
+struct LightingConstants;
+void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const LightingConstants& f, uint32_t op, uint32_t light, uint32_t edge, uint32_t* out, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);

@@ -633,6 +633,76 @@ def convolve_texels(pixels, kernel, divisor=None, bias=0.0, target=None, edge=Bl
     return out
 
 
+class LightingOp(IntEnum):  # crh_lighting_op
+    Diffuse = 0
+    Specular = 1
+
+
+class LightKind(IntEnum):  # crh_light_kind
+    Distant = 0
+    Point = 1
+    Spot = 2
+
+
+@dataclass(frozen=True)
+class DistantLight:
+    """A light infinitely far away (SVG feDistantLight): azimuth in the image plane from the x axis towards y (down), elevation above the
+    plane, both in degrees."""
+    azimuth: float = 0.0
+    elevation: float = 0.0
+
+
+@dataclass(frozen=True)
+class PointLight:
+    """A light at (x, y, z) in the image's texel space, x right, y down, z towards the viewer (SVG fePointLight)."""
+    x: float = 0.0
+    y: float = 0.0
+    z: float = 0.0
+
+
+@dataclass(frozen=True)
+class SpotLight:
+    """A light at `position` that shines towards `points_at` (SVG feSpotLight): its colour falls off as the cosine to the axis raised to
+    `exponent`, and with cone_angle (degrees, in (0, 90]; 0 = no cone) is cut off outside the cone."""
+    position: Tuple[float, float, float] = (0.0, 0.0, 1.0)
+    points_at: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    exponent: float = 1.0
+    cone_angle: float = 0.0
+
+
+def _lighting_arguments(light, op, surface_scale, constant, specular_exponent, color, edge):
+    """-> LightingC; the fields the light does not use stay 0"""
+    how = _ffi.LightingC()
+    how.op, how.edge = int(op), int(edge)
+    how.surface_scale, how.constant, how.specular_exponent = float(surface_scale), float(constant), float(specular_exponent)
+    how.color = (C.c_float * 3)(*[float(v) for v in color])
+    if isinstance(light, DistantLight):
+        how.light, how.azimuth, how.elevation = LightKind.Distant, float(light.azimuth), float(light.elevation)
+    elif isinstance(light, PointLight):
+        how.light = LightKind.Point
+        how.position = (C.c_float * 3)(float(light.x), float(light.y), float(light.z))
+    elif isinstance(light, SpotLight):
+        how.light = LightKind.Spot
+        how.position = (C.c_float * 3)(*[float(v) for v in light.position])
+        how.points_at = (C.c_float * 3)(*[float(v) for v in light.points_at])
+        how.spot_exponent, how.cone_angle = float(light.exponent), float(light.cone_angle)
+    else:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"a light is a DistantLight, a PointLight or a SpotLight, not {type(light).__name__}")
+    return how
+
+
+def lighting_texels(pixels, light, op=LightingOp.Diffuse, surface_scale=1.0, constant=1.0, specular_exponent=1.0, color=(1.0, 1.0, 1.0), edge=BlurEdge.Pad):
+    """crh_lighting_texels (host only): the rule of Image.lighting on a (height, width, 4) uint8 array -> a (height, width, 4) uint8 array
+    (include/contrast_hip.h crh_image_lighting states the rule)."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"lighting_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    how = _lighting_arguments(light, op, surface_scale, constant, specular_exponent, color, edge)
+    out = np.empty_like(pixels)
+    check(_ffi.load_library().crh_lighting_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, C.byref(how), out.ctypes.data))
+    return out
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -778,6 +848,29 @@ class Image:
         image.handle = handle
         image.width, image.height, image.origin = self.width, self.height, self.origin
         return image
+
+    def lighting(self, light, op=LightingOp.Diffuse, surface_scale=1.0, constant=1.0, specular_exponent=1.0, color=(1.0, 1.0, 1.0), edge=BlurEdge.Pad):
+        """crh_image_lighting -> a new Image of one level, of this image's size and origin: this image's alpha as a height field (alpha 255 =
+        `surface_scale` texels high) lit by `light` (a DistantLight, a PointLight or a SpotLight) of colour `color`, built on the device and
+        complete when this returns (a synchronous call). LightingOp.Diffuse gives opaque texels constant * N.L * colour (MULTIPLY them onto
+        a layer); LightingOp.Specular gives premultiplied highlights constant * (N.H) ** specular_exponent * colour (PLUS them onto a
+        layer). Binary64 arithmetic in a fixed order, so every byte is defined. This image is not modified; its colours are not read."""
+        how = _lighting_arguments(light, op, surface_scale, constant, specular_exponent, color, edge)
+        image = Image.__new__(Image)
+        image.renderer, image.lib = self.renderer, self.lib
+        handle = C.c_void_p()
+        check(self.lib.crh_image_lighting(self.handle, C.byref(how), C.byref(handle)))
+        image.handle = handle
+        image.width, image.height, image.origin = self.width, self.height, self.origin
+        return image
+
+    def diffuse_lighting(self, light, surface_scale=1.0, constant=1.0, color=(1.0, 1.0, 1.0), edge=BlurEdge.Pad):
+        """lighting(light, LightingOp.Diffuse, ...): SVG feDiffuseLighting."""
+        return self.lighting(light, LightingOp.Diffuse, surface_scale, constant, 1.0, color, edge)
+
+    def specular_lighting(self, light, surface_scale=1.0, constant=1.0, specular_exponent=1.0, color=(1.0, 1.0, 1.0), edge=BlurEdge.Pad):
+        """lighting(light, LightingOp.Specular, ...): SVG feSpecularLighting."""
+        return self.lighting(light, LightingOp.Specular, surface_scale, constant, specular_exponent, color, edge)
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

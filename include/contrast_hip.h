@@ -738,6 +738,69 @@ crh_status crh_convolve_validate(const crh_convolve* how); /* host only */
 crh_status crh_convolve_coefficients(const crh_convolve* how, int32_t* k, uint32_t capacity, int32_t* bias_k); /* host only: the quantised kernel */
 crh_status crh_convolve_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_convolve* how, void* out_rgba8); /* host only */
 crh_status crh_image_convolve(const crh_image* src, const crh_convolve* how, crh_image** out);
+/* Lighting: an image's alpha as a height field, lit by one light, on the device (SVG feDiffuseLighting / feSpecularLighting with
+ * feDistantLight / fePointLight / feSpotLight) — bevels, embossed text, raised buttons, glossy highlights, spotlit panels. A frame's
+ * snapshot, blurred, is the bump map; CRH_COMPOSITE_SRC_IN masks the lit result to the shape, CRH_BLEND_MULTIPLY applies a diffuse term
+ * and CRH_COMPOSITE_PLUS adds a specular one. The result is integer in, integer out and the tests check every byte: all real arithmetic
+ * below is IEEE binary64 in exactly the written order and parenthesisation, with only + - * / sqrt and the functions of crh_fmath.h
+ * (pow = crh_d_pow, sincos = crh_d_sincos), never contracted, every float field widened to double first, and one rounding to a code at
+ * the end. rad(d) = d * (CRH_PI / 180.0); s = surface_scale.
+ *   height       A(i, j) = the alpha code of source texel (column i, row j). Outside the image (edge, a crh_blur_edge): TRANSPARENT
+ *                gives 0; PAD, REPEAT and REFLECT read wrap(i, n) by exactly the rules of the image-paint block above.
+ *   gradient     gx = (A(i+1,j-1) + 2 A(i+1,j) + A(i+1,j+1)) - (A(i-1,j-1) + 2 A(i-1,j) + A(i-1,j+1)), gy the same with rows and
+ *                columns exchanged: integers in [-1020, 1020].
+ *   normal       nx = (s * (double)(-gx)) / 1020.0, ny = (s * (double)(-gy)) / 1020.0, nz = 1; nlen = sqrt((nx nx + ny ny) + 1.0) >= 1.
+ *   light vector DISTANT, once per call: (sa, ca) = sincos(rad(azimuth)), (se, ce) = sincos(rad(elevation)), L = (ca ce, sa ce, se).
+ *                POINT, SPOT, per texel: d = (px - (i + 0.5), py - (j + 0.5), pz - (s * A(i,j)) / 255.0), len = sqrt((dx dx + dy dy) + dz dz),
+ *                L = d / len per component; len == 0 gives L = (0, 0, 0).
+ *   light colour DISTANT, POINT: C = color. SPOT, once per call: S = (points_at - position) / its length (the same sum and square root),
+ *                cc = cos(rad(cone_angle)) when cone_angle != 0; per texel m = -((Lx Sx + Ly Sy) + Lz Sz); m <= 0, or a cone with m < cc,
+ *                gives C = 0, otherwise C = color * pow(m, spot_exponent) per channel. The cut-off is hard: there is no smoothing band.
+ *   DIFFUSE      v = kd * max(((nx Lx + ny Ly) + Lz) / nlen, 0); each colour channel is code(v * C_c), alpha is 255.
+ *   SPECULAR     h = (Lx, Ly, Lz + 1.0), hlen = sqrt((hx hx + hy hy) + hz hz); hlen == 0 gives v = 0, otherwise
+ *                v = ks * pow(max(((nx hx + ny hy) + hz) / (nlen * hlen), 0), specular_exponent); each colour channel is code(v * C_c) and
+ *                alpha is the largest of the three colour codes.
+ *   code(t)      t >= 1 ? 255 : floor(t * 255.0 + 0.5). With validated inputs t is finite and not negative.
+ * Hence: a constant alpha under the three same-size edges, or s == 0, gives a constant image under a distant light, for DIFFUSE
+ * code(kd * max(Lz, 0) * C); an elevation of 90 on a flat field gives code(kd C) for DIFFUSE and code(ks C) for SPECULAR; constant == 0
+ * gives (0, 0, 0, 255) for DIFFUSE and (0, 0, 0, 0) for SPECULAR; the source's colour channels never enter the result; a SPECULAR colour
+ * never exceeds its alpha, so the texel is a valid premultiplied one; a point light at (w - px, py, pz) over the horizontally mirrored
+ * image gives the mirrored bytes exactly (every coordinate involved is exact in binary64); and every code is within 0.5 + 10^-6 of the
+ * real-valued SVG formula on the same inputs (at most 12 binary64 operations and one crh_d_pow, whose |y| <= 745 keeps its relative error
+ * below 10^-13, stand between the inputs and t: a few 10^-11 of a code).
+ * Fields that the chosen op / light does not use are not read and not validated. crh_lighting_validate and crh_lighting_texels are host
+ * only (no renderer, no device). texels: the rule on a whole image in host memory, 1 <= width, height <= 16384, width * height * 4 bytes
+ * in the order r g b a at any alignment, row 0 first, into out_rgba8 of the same size; out_rgba8 == rgba8 is refused.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out untouched: a null argument, an
+ * op above CRH_LIGHTING_SPECULAR, a light above CRH_LIGHT_SPOT, an edge above CRH_BLUR_EDGE_REFLECT are CRH_ERR_INVALID_ARGUMENT; then a
+ * non-finite used field is CRH_ERR_NON_FINITE; then a used value outside its range (below), points_at == position, a size outside
+ * [1, 16384] and out_rgba8 == rgba8 are CRH_ERR_INVALID_ARGUMENT, each with a crh_last_error text. The source must belong to a renderer.
+ * crh_image_lighting gives a fresh image of the source's renderer, size and origin with one level (mipmaps, blur, composite, colour
+ * filter, morphology, convolution, image paints and crh_frame_load_image work on it), complete when the call returns: k_image_lighting
+ * runs on the renderer's stream, a 3 x 3 stencil on alpha codes staged in LDS with the edge applied, specialised on (op, light). Only
+ * the alpha of level 0 of the source is read and the source is not modified. A failed allocation or launch frees everything and
+ * returns CRH_ERR_HIP.
+ * Limits: the edges are the library's four, not SVG's one-sided border kernels (PAD halves the border slope compared with SVG); one
+ * light per call — several lights are several calls joined by CRH_COMPOSITE_PLUS; there is no kernelUnitLength; the call is
+ * synchronous, like its siblings; light coordinates are in the image's own texel space (x right, y down, z towards the viewer) — a
+ * grown blur's origin is the caller's to add. */
+typedef enum crh_lighting_op { CRH_LIGHTING_DIFFUSE = 0, CRH_LIGHTING_SPECULAR = 1 } crh_lighting_op;
+typedef enum crh_light_kind { CRH_LIGHT_DISTANT = 0, CRH_LIGHT_POINT = 1, CRH_LIGHT_SPOT = 2 } crh_light_kind;
+typedef struct crh_lighting {
+    uint32_t op, light, edge;      /* edge: crh_blur_edge, what the height field is outside the image */
+    float surface_scale;           /* s: height of alpha 255 in texels; finite, |s| <= 256 */
+    float constant;                /* kd or ks; [0, 256] */
+    float specular_exponent;       /* SPECULAR: [1, 128]; DIFFUSE: ignored */
+    float color[3];                /* the light's colour, each in [0, 1] */
+    float azimuth, elevation;      /* DISTANT: degrees, |.| <= 3600 */
+    float position[3];             /* POINT, SPOT: texel coordinates (x right, y down, z towards the viewer), |.| <= 2^20 */
+    float points_at[3];            /* SPOT: |.| <= 2^20, must differ from position */
+    float spot_exponent;           /* SPOT: [0, 128] */
+    float cone_angle;              /* SPOT: degrees; 0 = no cone, otherwise in (0, 90] */
+} crh_lighting;
+crh_status crh_lighting_validate(const crh_lighting* how); /* host only */
+crh_status crh_lighting_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_lighting* how, void* out_rgba8); /* host only */
+crh_status crh_image_lighting(const crh_image* src, const crh_lighting* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

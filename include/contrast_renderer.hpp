@@ -731,6 +731,62 @@ inline std::vector<uint8_t> convolve_texels(uint32_t width, uint32_t height, con
     check(crh_convolve_texels(width, height, texels.data(), &how, out.data()));
     return out;
 }
+// Lighting (include/contrast_hip.h crh_image_lighting states the rule): an image's alpha as a height field under one light.
+enum class LightingOp : uint32_t { Diffuse = CRH_LIGHTING_DIFFUSE, Specular = CRH_LIGHTING_SPECULAR };
+// A light infinitely far away (SVG feDistantLight): azimuth in the image plane from the x axis towards y (down), elevation above it, in degrees
+struct DistantLight {
+    float azimuth = 0.0f, elevation = 0.0f;
+};
+// A light at (x, y, z) in the image's texel space, x right, y down, z towards the viewer (SVG fePointLight)
+struct PointLight {
+    float x = 0.0f, y = 0.0f, z = 0.0f;
+};
+// A light at `position` that shines towards `points_at` (SVG feSpotLight); cone_angle in degrees, 0 = no cone
+struct SpotLight {
+    std::array<float, 3> position = {0.0f, 0.0f, 1.0f}, points_at = {0.0f, 0.0f, 0.0f};
+    float exponent = 1.0f, cone_angle = 0.0f;
+};
+// What is lit and how: the fields of crh_lighting that do not describe the light
+struct Lighting {
+    LightingOp op = LightingOp::Diffuse;
+    float surface_scale = 1.0f, constant = 1.0f, specular_exponent = 1.0f;
+    std::array<float, 3> color = {1.0f, 1.0f, 1.0f};
+    BlurEdge edge = BlurEdge::Pad;
+    crh_lighting to_c(const DistantLight& light) const {
+        crh_lighting how = base(CRH_LIGHT_DISTANT);
+        how.azimuth = light.azimuth, how.elevation = light.elevation;
+        return how;
+    }
+    crh_lighting to_c(const PointLight& light) const {
+        crh_lighting how = base(CRH_LIGHT_POINT);
+        how.position[0] = light.x, how.position[1] = light.y, how.position[2] = light.z;
+        return how;
+    }
+    crh_lighting to_c(const SpotLight& light) const {
+        crh_lighting how = base(CRH_LIGHT_SPOT);
+        for (int c = 0; c < 3; ++c) how.position[c] = light.position[(size_t)c], how.points_at[c] = light.points_at[(size_t)c];
+        how.spot_exponent = light.exponent, how.cone_angle = light.cone_angle;
+        return how;
+    }
+
+  private:
+    crh_lighting base(uint32_t light) const {
+        crh_lighting how = {};
+        how.op = (uint32_t)op, how.light = light, how.edge = (uint32_t)edge;
+        how.surface_scale = surface_scale, how.constant = constant, how.specular_exponent = specular_exponent;
+        for (int c = 0; c < 3; ++c) how.color[c] = color[(size_t)c];
+        return how;
+    }
+};
+// crh_lighting_texels (host only): the rule on a width x height image of RGBA8 in host memory -> the bytes of the result, of the same size
+template <class Light>
+inline std::vector<uint8_t> lighting_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, const Light& light, const Lighting& lighting = Lighting()) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const crh_lighting how = lighting.to_c(light);
+    std::vector<uint8_t> out(texels.size());
+    check(crh_lighting_texels(width, height, texels.data(), &how, out.data()));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -827,6 +883,30 @@ class Image {
         check(crh_image_convolve(handle_, &how, &image.handle_));
         image.width_ = width_, image.height_ = height_, image.origin_ = origin_;
         return image;
+    }
+    // crh_image_lighting -> a new Image of one level, of this image's size and origin: this image's alpha as a height field lit by `light` (a
+    // DistantLight, a PointLight or a SpotLight); binary64 arithmetic in a fixed order, complete on return (a synchronous call). Diffuse
+    // results are opaque (MULTIPLY them onto a layer), specular ones premultiplied highlights (PLUS them). This image is not modified.
+    template <class Light>
+    Image lighting(const Light& light, const Lighting& lighting = Lighting()) const {
+        const crh_lighting how = lighting.to_c(light);
+        Image image;
+        check(crh_image_lighting(handle_, &how, &image.handle_));
+        image.width_ = width_, image.height_ = height_, image.origin_ = origin_;
+        return image;
+    }
+    template <class Light>
+    Image diffuse_lighting(const Light& light, float surface_scale = 1.0f, float constant = 1.0f, std::array<float, 3> color = {1.0f, 1.0f, 1.0f}, BlurEdge edge = BlurEdge::Pad) const {
+        Lighting how;
+        how.op = LightingOp::Diffuse, how.surface_scale = surface_scale, how.constant = constant, how.color = color, how.edge = edge;
+        return lighting(light, how);
+    }
+    template <class Light>
+    Image specular_lighting(const Light& light, float surface_scale = 1.0f, float constant = 1.0f, float specular_exponent = 1.0f, std::array<float, 3> color = {1.0f, 1.0f, 1.0f},
+                            BlurEdge edge = BlurEdge::Pad) const {
+        Lighting how;
+        how.op = LightingOp::Specular, how.surface_scale = surface_scale, how.constant = constant, how.specular_exponent = specular_exponent, how.color = color, how.edge = edge;
+        return lighting(light, how);
     }
 
   private:

@@ -945,6 +945,76 @@ pub fn convolve_texels(width: u32, height: u32, texels: &[u8], kernel: &Convolve
     status(unsafe { ffi::crh_convolve_texels(width, height, texels.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// `crh_lighting_op`
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum LightingOp {
+    Diffuse = 0,
+    Specular = 1,
+}
+/// The light of `Image::lighting` (`crh_light_kind` and its fields): coordinates in the image's texel space, x right, y down, z towards the
+/// viewer; angles in degrees (a `cone_angle` of 0 = no cone).
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub enum Light {
+    Distant { azimuth: f32, elevation: f32 },
+    Point { position: [f32; 3] },
+    Spot { position: [f32; 3], points_at: [f32; 3], exponent: f32, cone_angle: f32 },
+}
+/// What is lit and how: the fields of `crh_lighting` that do not describe the light
+#[derive(Clone, Copy, PartialEq, Debug)]
+pub struct Lighting {
+    pub op: LightingOp,
+    pub surface_scale: f32,
+    pub constant: f32,
+    pub specular_exponent: f32,
+    pub color: [f32; 3],
+    pub edge: BlurEdge,
+}
+impl Default for Lighting {
+    fn default() -> Lighting {
+        Lighting { op: LightingOp::Diffuse, surface_scale: 1.0, constant: 1.0, specular_exponent: 1.0, color: [1.0; 3], edge: BlurEdge::Pad }
+    }
+}
+impl Lighting {
+    /// The C struct; the fields the light does not use stay 0
+    fn to_c(&self, light: &Light) -> ffi::crh_lighting {
+        let mut how = ffi::crh_lighting { op: self.op as u32, light: 0, edge: self.edge as u32, surface_scale: self.surface_scale, constant: self.constant,
+                                          specular_exponent: self.specular_exponent, color: self.color, azimuth: 0.0, elevation: 0.0, position: [0.0; 3], points_at: [0.0; 3],
+                                          spot_exponent: 0.0, cone_angle: 0.0 };
+        match *light {
+            Light::Distant { azimuth, elevation } => {
+                how.light = ffi::CRH_LIGHT_DISTANT;
+                how.azimuth = azimuth;
+                how.elevation = elevation;
+            }
+            Light::Point { position } => {
+                how.light = ffi::CRH_LIGHT_POINT;
+                how.position = position;
+            }
+            Light::Spot { position, points_at, exponent, cone_angle } => {
+                how.light = ffi::CRH_LIGHT_SPOT;
+                how.position = position;
+                how.points_at = points_at;
+                how.spot_exponent = exponent;
+                how.cone_angle = cone_angle;
+            }
+        }
+        how
+    }
+}
+/// `crh_lighting_validate` (host only): what `Image::lighting` would refuse
+pub fn lighting_validate(light: &Light, lighting: &Lighting) -> Result<(), Error> {
+    let how = lighting.to_c(light);
+    status(unsafe { ffi::crh_lighting_validate(&how) })
+}
+/// `crh_lighting_texels` (host only): the rule on a width x height image of RGBA8 in host memory -> the texels of the result, of the same size
+/// (include/contrast_hip.h, `crh_image_lighting`, states the rule).
+pub fn lighting_texels(width: u32, height: u32, texels: &[u8], light: &Light, lighting: &Lighting) -> Result<Vec<u8>, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    let how = lighting.to_c(light);
+    let mut out = vec![0u8; texels.len()];
+    status(unsafe { ffi::crh_lighting_texels(width, height, texels.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -1052,6 +1122,23 @@ impl Image {
         let mut raw = ptr::null_mut();
         status(unsafe { ffi::crh_image_convolve(self.raw, &how, &mut raw) })?;
         Ok(Image { raw, width: self.width, height: self.height, origin: self.origin })
+    }
+    /// `crh_image_lighting` -> a new `Image` of one level, of this image's size and origin: this image's alpha as a height field lit by
+    /// `light`; binary64 arithmetic in a fixed order, complete on return (a synchronous call). Diffuse results are opaque (MULTIPLY them onto
+    /// a layer), specular ones premultiplied highlights (PLUS them). This image is not modified.
+    pub fn lighting(&self, light: &Light, lighting: &Lighting) -> Result<Image, Error> {
+        let how = lighting.to_c(light);
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_lighting(self.raw, &how, &mut raw) })?;
+        Ok(Image { raw, width: self.width, height: self.height, origin: self.origin })
+    }
+    /// `lighting` with `LightingOp::Diffuse`: SVG feDiffuseLighting
+    pub fn diffuse_lighting(&self, light: &Light, surface_scale: f32, constant: f32, color: [f32; 3], edge: BlurEdge) -> Result<Image, Error> {
+        self.lighting(light, &Lighting { op: LightingOp::Diffuse, surface_scale, constant, specular_exponent: 1.0, color, edge })
+    }
+    /// `lighting` with `LightingOp::Specular`: SVG feSpecularLighting
+    pub fn specular_lighting(&self, light: &Light, surface_scale: f32, constant: f32, specular_exponent: f32, color: [f32; 3], edge: BlurEdge) -> Result<Image, Error> {
+        self.lighting(light, &Lighting { op: LightingOp::Specular, surface_scale, constant, specular_exponent, color, edge })
     }
 }
 impl Drop for Image {
