@@ -1,6 +1,8 @@
 // csrc/api.hip — the C ABI of include/contrast_hip.h: host-side orchestration only (validation, HBM buffers, launches,
 // parity taps). Every arithmetic step of the hot path runs in the HIP kernels of tessellate.hip / raster.hip; there is no
 // CPU fallback here and nothing under oracle/ is referenced.
+// Streams of a renderer: raster (+ copies), tessellation (low priority), binning — one lane, or with CRH_BIN_LANES=2 two lanes that consecutive
+// passes take in turn (crh_renderer::bin_lane, render_impl's `steady`; DESIGN.md §4.6: measured slower, not the default) —, aux, upload.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -159,6 +161,18 @@ struct crh_renderer {
     int device;
     hipStream_t stream;       // raster kernel, copies
     hipStream_t bin_stream;   // primitive setup + tile binning: frame N + 1's overlap frame N's raster kernel (double-buffered records / lists)
+    // Two binning lanes (CRH_BIN_LANES=2; off by default: measured slower): pass number n of the renderer puts its binning-lane work on
+    // lane n % 2, so that the binning of frame k + 2 need not wait for the long, thinly occupied tail of frame k + 1's. Only two consecutive STEADY passes
+    // (render_impl) run unordered; every other pass first waits for lane_done of the pass before it, which orders it exactly as the single stream did.
+    hipStream_t bin_stream_b = nullptr; // (created with two lanes only)
+    int bin_lanes = 1;        // CRH_BIN_LANES (read when the renderer is created)
+    int bin_lane = 0;         // the lane of the pass being enqueued, then of the latest one
+    uint64_t bin_passes = 0;  // passes that have taken a lane
+    hipEvent_t lane_done[2] = {nullptr, nullptr}; // recorded on its lane behind the binning-lane work of every pass
+    bool lane_done_set[2] = {false, false};
+    bool last_pass_steady = false;        // the latest pass left nothing behind its binning kernel on its lane and wrote nothing a steady successor reads
+    crh_scene* last_pass_scene = nullptr; // ... and drew this Scene, of this upload, from this tessellation run
+    uint64_t last_pass_generation = 0, last_pass_tess_run = 0;
     hipStream_t tess_stream;  // tessellation: frame N + 1's (small, latency bound) kernels overlap frame N's binning and raster
     hipStream_t upload_stream; // instance data of the next frame, copied while the current one is being binned
     hipStream_t aux_stream;   // crh_composite_over: the multi-GPU slab composite of frame N while frame N + 1 is being rendered
@@ -189,7 +203,23 @@ struct crh_renderer {
     }
     // marks accumulate over calls (so a benchmark can time K steps without a sync per step); kernel_times() drains them
     hipStream_t tessellation_stream() const { return pipeline ? tess_stream : stream; }
-    hipStream_t binning_stream() const { return pipeline ? bin_stream : stream; }
+    bool two_lanes() const { return pipeline && bin_lanes == 2; }
+    hipStream_t lane(int k) const { return k ? bin_stream_b : bin_stream; }
+    hipStream_t binning_stream() const { return pipeline ? lane(bin_lane) : stream; } // of the pass being enqueued (its timing marks are recorded there too)
+    int next_bin_lane() const { return two_lanes() ? (int)(bin_passes & 1u) : 0; }
+    // Instance data for the NEXT pass goes on the lane that pass will take, behind everything both lanes hold so far: the single stream ordered the copy behind
+    // every earlier binning kernel, and slot.read_event alone names the latest reader only — with two lanes the reader before it may outlive that one.
+    hipError_t upload_lane(hipStream_t* out) {
+        if (!pipeline) return *out = stream, hipSuccess;
+        const int k = next_bin_lane();
+        *out = lane(k);
+        return two_lanes() ? order_behind_lane(k, k ^ 1) : hipSuccess;
+    }
+    // lane `k` waits for the end of the latest pass on lane `other` (asked on the host first: a wait packet costs a lane 5 - 10 us whether it is satisfied or not)
+    hipError_t order_behind_lane(int k, int other) {
+        if (!lane_done_set[other] || hipEventQuery(lane_done[other]) == hipSuccess) return hipSuccess;
+        return hipStreamWaitEvent(lane(k), lane_done[other], 0);
+    }
     hipStream_t lane_stream(int lane) const { return lane == 1 ? tessellation_stream() : (lane == 2 ? binning_stream() : stream); }
     void begin_marks(int lane = 0) {
         if (!(timing & (1u << lane))) return;
@@ -220,7 +250,11 @@ struct crh_renderer {
     MarkFn mark_fn_tess() const { return (timing & 2u) ? &crh_renderer::mark_cb_tess : nullptr; }
     hipError_t sync() { // every stream
         const hipError_t e = hipStreamSynchronize(tess_stream);
-        const hipError_t b = hipStreamSynchronize(bin_stream);
+        hipError_t b = hipStreamSynchronize(bin_stream);
+        if (bin_stream_b) {
+            const hipError_t b2 = hipStreamSynchronize(bin_stream_b);
+            if (b == hipSuccess) b = b2;
+        }
         const hipError_t a = hipStreamSynchronize(aux_stream);
         (void)hipStreamSynchronize(upload_stream);
         const hipError_t f = hipStreamSynchronize(stream);
@@ -248,8 +282,9 @@ struct InstanceSlot {
 };
 
 // how many frames the binning lane may run ahead of the raster lane: that many sets of tile lists per frame and of primitive records
-// per scene (S10k@4096^2: 13 MB + 60 MB per set). Measured: 3 is no faster than 2 — the step is bound by the GPU's total throughput, not by
-// the coupling of the lanes.
+// per scene (S10k@4096^2: 13 MB + 60 MB per set). Measured with one in-order binning stream: 3 is no faster than 2 — the step is bound by the
+// GPU's total throughput, not by the coupling of the lanes. Measured again with two binning lanes (CRH_BIN_LANES=2), where two binning kernels
+// do run at once: 3 is SLOWER, 0.384 - 0.399 ms per step against 0.306 - 0.332 at depth 2 (one lane: 0.378 - 0.385 against 0.281 - 0.291).
 #ifndef CRH_PIPELINE_DEPTH
 #define CRH_PIPELINE_DEPTH 2
 #endif
@@ -315,7 +350,8 @@ struct crh_frame {
     bool carry_recolor = false;    // the exchange wrote the frame's pixels behind the planes' back: the sample colours start from the image again
     // What the frame's last pass ran (crh_debug_frame_last_pass; the tests that pin a path check that they reached it): the formulation
     // (choose_pass' 1 / 2 / 3, + 256 when it is the Scene's measured choice), whether it was the general one, RasterVariant, and BinRoute
-    // + 256 with the lists in place (direct), + 512 in the heavy-first tile order, + items per binning workgroup << 16 (0: measured runs).
+    // + 256 with the lists in place (direct), + 512 in the heavy-first tile order, + 1024 when its binning was NOT ordered behind the binning of the pass
+    // before it (two lanes, two steady passes), + items per binning workgroup << 16 (0: measured runs).
     // All zero for a pass that launched nothing (forget_last_pass).
     uint32_t last_formulation = 0, last_general = 0, last_raster = 0, last_bin = 0;
     bool cleared = true;
@@ -492,6 +528,7 @@ struct crh_scene {
         uint64_t emitted_bytes = 0;
     } shadow;
     bool tessellated_once = false;
+    uint64_t tess_runs = 0; // tessellation runs so far: two passes that draw the same run read the same set, and its vertices_free names the later one only (render_impl: such a pass is ordered)
     // Which formulation draws this Scene's plain passes — boundary edges + backdrops (bin_edges.hip, raster_edges.hip) or the reference's strip triangles
     // (raster.hip) — is decided by MEASUREMENT: both give the same pixels, and which is faster depends on the content (long strips
     // across many tiles favour the edges, tens of thousands of glyph-sized Shapes the triangles: the edge pass pays per item and per
@@ -707,6 +744,7 @@ crh_status run_tessellation(crh_scene* sc, bool again) {
         if (st != CRH_OK) return st;
     }
     sc->tessellated_once = true;
+    sc->tess_runs += 1u;
     if (again) sc->bounds_generation = 0; // (boxes taken from the hulls of a run that did not fit are nobody's)
     if (again) sc->hull_queued_state = 0; // (the run that overflowed queued nothing: its hull kernels returned at once; the caller has synchronised)
     SceneDev& d = sc->d;
@@ -1130,6 +1168,16 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     HIP_TRY(hipSetDevice(r->device));
     // Three lanes: tessellation -> binning (setup, tile walks) -> raster. This frame is binned into the frame's other set of tile
     // buffers and the scene's other record buffer while the previous frame's raster kernel may still be reading its own.
+    // Two binning lanes: this pass takes the lane the pass before it did not. Whether it may run unordered beside that pass is known in two steps — what
+    // the call itself says here, what the frame's state says where the binning kernels are launched (`steady`, below); a pass that cannot is ordered behind
+    // lane_done of the pass before it, here or there (in between only wait packets go to the lane), and so runs exactly where the single stream had put it.
+    const bool two_lanes = r->two_lanes();
+    if (two_lanes) r->bin_lane = (int)(r->bin_passes++ & 1u);
+    const bool slab = f->slab_ty0 > 0u || std::min(f->slab_ty1, f->tiles_y) < f->tiles_y;
+    const bool may_be_steady = two_lanes && !again && !recorded && !sc->optimistic && !f->carry && !slab && !r->raster_exclusive;
+    bool unordered = may_be_steady && r->last_pass_steady && r->last_pass_scene == sc && r->last_pass_generation == sc->generation && r->last_pass_tess_run != sc->tess_runs;
+    r->last_pass_steady = false; // (until this pass is through: a pass that returns early leaves its successor ordered)
+    if (two_lanes && !unordered) HIP_TRY(r->order_behind_lane(r->bin_lane, r->bin_lane ^ 1));
     const hipStream_t bin = r->binning_stream();
     crh_frame::BinSet& set = f->sets[f->next_set];
     const int rec = sc->next_rec;
@@ -1344,6 +1392,16 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     }
     if (direct) f->pair_capacity_bytes = std::max<size_t>(f->pair_capacity_bytes, (size_t)f->direct_entries * 6); // (half as much again: the places move with the scene; a pass whose places do not fit says so, overflow[0])
     HIP_TRY(set.tile_list.ensure(f->pair_capacity_bytes));
+    // A STEADY pass: the same Scene's lists in known places, binned by k_bin_flat alone — nothing runs behind that kernel on its lane (one_event, below), nothing
+    // is read back, measured, uploaded or rewritten (no verified pass, no formulation trial, no new places: launch_tile_bases below), and everything it writes
+    // belongs to its own BinSet and record set, which it has waited for by their events above. Two such passes in a row share nothing the single stream
+    // ordered implicitly (DESIGN.md §4.6 lists what was checked), so the later one does not wait for the earlier one's lane.
+    const bool steady = may_be_steady && direct && p.item_cost == nullptr && trial == nullptr && timed < 0 && p.debug == 0u && p.n_items != 0u && !bin_itemwise(p) &&
+                        f->places_instances == sc->instances_version;
+    if (unordered && !steady) {
+        unordered = false;
+        HIP_TRY(r->order_behind_lane(r->bin_lane, r->bin_lane ^ 1));
+    }
     for (int attempt = 0; attempt < 6; ++attempt) { // (a region of the edge pass' pair stream may fill before the total does: each retry adds headroom)
         p.tile_list = set.tile_list.as<uint32_t>();
         p.pair_capacity = (uint32_t)(set.tile_list.cap / 4);
@@ -1462,6 +1520,11 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         launch_fill(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->ranges_free);
     }
     if (!one_event) HIP_TRY(hipEventRecord(set.bin_done, bin));
+    if (two_lanes) { // the end of this pass' work on its lane: what the next pass, on the other lane, waits for unless both are steady
+        HIP_TRY(hipEventRecord(r->lane_done[r->bin_lane], bin));
+        r->lane_done_set[r->bin_lane] = true;
+        r->last_pass_steady = steady, r->last_pass_scene = sc, r->last_pass_generation = sc->generation, r->last_pass_tess_run = sc->tess_runs;
+    }
     // ---- raster lane
     HIP_TRY(hipStreamWaitEvent(r->stream, one_event ? vertices_free_now : set.bin_done, 0));
     HIP_TRY(order_after_external(f, r->stream));
@@ -1492,6 +1555,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     f->last_formulation = (uint32_t)pass | (measured ? 256u : 0u), f->last_general = p.general | (r->pipeline ? 0u : 256u);
     if (direct) f->last_bin |= 256u;
     if (p.tile_order) f->last_bin |= 512u;
+    if (unordered) f->last_bin |= 1024u;
     HIP_TRY(hipEventRecord(set.raster_done, r->stream));
     HIP_TRY(hipEventRecord(sc->rec_raster_done[rec], r->stream));
     HIP_TRY(hipStreamWaitEvent(r->aux_stream, set.raster_done, 0));
@@ -1766,11 +1830,25 @@ crh_status crh_renderer_create_blended(const crh_config* config, const crh_color
             if ((c < front_cus) == (lane == 1)) mask[(size_t)c / 32] |= 1u << (c % 32);
         return hip_ok(hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()), "hipExtStreamCreateWithCUMask");
     };
-    if (!make_stream(&r->stream, 2, lane_priority[2]) || !make_stream(&r->tess_stream, 1, lane_priority[0]) || !make_stream(&r->bin_stream, 1, lane_priority[1]) || !make_stream(&r->aux_stream, 0) ||
-        !make_stream(&r->upload_stream, 0)) {
+    // CRH_BIN_LANES=2: two binning lanes. The default is ONE — the library as it was before the second lane existed: measured (DESIGN.md §4.6,
+    // profiles/bin_lanes_timeline_two_lanes.txt), a binning grid that starts in front of the next raster kernel keeps its register slots while that kernel
+    // runs, which stretches it from 142 to 190 - 230 us — more than the binning window gets shorter (0.316 against 0.298 ms per step).
+    if (const char* e = getenv("CRH_BIN_LANES")) r->bin_lanes = atoi(e) == 2 ? 2 : 1;
+    // The second lane is created right behind the first, in front of the aux and upload streams: a process has a handful of hardware queues per priority and the
+    // runtime deals them to streams in the order of creation — the raster stream and the two lanes must each get one of their own (the tessellation stream, at
+    // low priority, draws from a pool of its own); the aux and upload streams, idle in the steady loop, share what is left.
+    if (!make_stream(&r->stream, 2, lane_priority[2]) || !make_stream(&r->tess_stream, 1, lane_priority[0]) || !make_stream(&r->bin_stream, 1, lane_priority[1]) ||
+        (r->pipeline && r->bin_lanes == 2 && !make_stream(&r->bin_stream_b, 1, lane_priority[1])) || !make_stream(&r->aux_stream, 0) || !make_stream(&r->upload_stream, 0)) {
         delete r;
         return CRH_ERR_HIP;
     }
+    if (r->bin_stream_b)
+        for (hipEvent_t& e : r->lane_done)
+            if (!hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) {
+                delete r;
+                return CRH_ERR_HIP;
+            }
+    if (!r->bin_stream_b) r->bin_lanes = 1;
     r->raster_exclusive = getenv("CRH_RASTER_EXCLUSIVE") != nullptr;
 
     *out = r;
@@ -1790,6 +1868,9 @@ void crh_renderer_destroy(crh_renderer* r) {
     (void)hipStreamDestroy(r->stream);
     (void)hipStreamDestroy(r->tess_stream);
     (void)hipStreamDestroy(r->bin_stream);
+    if (r->bin_stream_b) (void)hipStreamDestroy(r->bin_stream_b);
+    for (hipEvent_t e : r->lane_done)
+        if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(r->aux_stream);
     (void)hipStreamDestroy(r->upload_stream);
     if (r->composite_table) (void)hipFree(r->composite_table);
@@ -2179,6 +2260,7 @@ void crh_scene_destroy(crh_scene* sc) {
     if (sc->renderer) {
         (void)settle_frames_of(sc, true);
         (void)sc->renderer->sync();
+        if (sc->renderer->last_pass_scene == sc) sc->renderer->last_pass_scene = nullptr, sc->renderer->last_pass_steady = false; // (a new Scene may get this address)
         for (hipEvent_t& seen : sc->renderer->raster_events) // (the events below are about to be destroyed)
             for (hipEvent_t mine : sc->rec_raster_done)
                 if (seen == mine) seen = nullptr;
@@ -2479,7 +2561,8 @@ crh_status crh_scene_set_instances(crh_scene* sc, const float* transforms, const
         // engine's event cost a consumed animation 0.05 ms per frame (tools/r05_host_calls.py: 0.357 against 0.308 ms per step of 10 000 paths).
         InstanceSlot& slot = sc->slot[next];
         HIP_TRY(slot.init());
-        const hipStream_t up = r->pipeline ? r->bin_stream : r->stream;
+        hipStream_t up = nullptr; // (the binning lane of the pass that reads the data next, behind both lanes' passes so far)
+        HIP_TRY(r->upload_lane(&up));
         if (slot.was_read) HIP_TRY(hipStreamWaitEvent(up, slot.read_event, 0)); // the setup that read this set two updates ago
         HIP_TRY(sc->upload_t.copy(tb.p, transforms, (size_t)sc->d.n_shapes * 64, up));
         HIP_TRY(sc->upload_c.copy(cb.p, colors, (size_t)sc->d.n_shapes * 16, up));
@@ -2762,7 +2845,8 @@ crh_status crh_scene_render_draws(crh_scene* sc, crh_frame* f, const float* tran
         HIP_TRY(cb.ensure((size_t)n_instances * 16 + 16));
         InstanceSlot& slot = f->item_slot[next];
         HIP_TRY(slot.init());
-        const hipStream_t up = r->pipeline ? r->bin_stream : r->stream;
+        hipStream_t up = nullptr; // (the binning lane of the pass that reads the data next, behind both lanes' passes so far)
+        HIP_TRY(r->upload_lane(&up));
         if (slot.was_read) HIP_TRY(hipStreamWaitEvent(up, slot.read_event, 0));
         HIP_TRY(f->item_upload_t.copy(tb.p, transforms, (size_t)n_instances * 64, up));
         HIP_TRY(f->item_upload_c.copy(cb.p, colors, (size_t)n_instances * 16, up));

@@ -1718,12 +1718,35 @@ void flat_batch_limits(uint32_t n_items, uint32_t limits[4]) {
     const FlatShape shape = flat_shape(flat_threads_for(n_items));
     limits[0] = shape.batch, limits[1] = shape.tris, limits[2] = shape.edges, limits[3] = shape.pool;
 }
+// The clear in front of a pass' binning kernels (tile counts, overflow words, cursors: 256 KB for 4096^2) as SINGLE-WAVE workgroups, for the reason k_tile_caps
+// has them (below): the runtime's fill kernel behind hipMemsetAsync has 256-thread workgroups — four wavefronts that must find room on ONE compute unit at
+// the same moment — and beside k_raster_fill's seven waves per SIMD it waited 121 us for them, k_bin_flat's dispatch behind it (profiles/r06_experiments.txt
+// item 7). One wavefront takes the first slot that frees. Eight dwords per lane, each store of a wavefront one contiguous 256 bytes.
+// CRH_NO_CLEAR_KERNEL=1 (A/B runs; read per launch): hipMemsetAsync, as before.
+constexpr uint32_t kClearWordsPerLane = 8u;
+__global__ __launch_bounds__(64) void k_clear_words(uint32_t* words, uint32_t n) {
+    const uint32_t first = blockIdx.x * (64u * kClearWordsPerLane) + threadIdx.x;
+#pragma unroll
+    for (uint32_t k = 0; k < kClearWordsPerLane; ++k) {
+        const uint32_t i = first + k * 64u;
+        if (i < n) words[i] = 0u;
+    }
+}
+void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream) {
+    if (n_words == 0) return;
+    if (getenv("CRH_NO_CLEAR_KERNEL") != nullptr || n_words > 0x7FFFFFFFu) {
+        (void)hipMemsetAsync(words, 0, n_words * sizeof(uint32_t), stream);
+        return;
+    }
+    const uint32_t per_group = 64u * kClearWordsPerLane;
+    hipLaunchKernelGGL(k_clear_words, dim3((uint32_t)((n_words + per_group - 1u) / per_group)), dim3(64), 0, stream, words, (uint32_t)n_words);
+}
 // The edge pass draws msaa 1 and 4 only (edge_pass_samples): for any other count its launchers launch nothing and return 0 (api.hip
 // render_impl refuses such a pass before it gets here; choose_pass sends msaa 2 and 8 to the triangle pass).
 uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin) {
     if (!edge_pass_samples(samples)) return 0u;
-    // tile_count and, right behind it, the overflow words (overflow[8 ...] are the cursors of the pair sub-streams): one memset (tile_cursor, in front, is the triangle pass')
-    (void)hipMemsetAsync(r.tile_count, 0, sizeof(uint32_t) * r.n_tiles + 32 + 4 * kSubStreams + 32, stream); // (... and kExtraTurnsWord behind them)
+    // tile_count and, right behind it, the overflow words (overflow[8 ...] are the cursors of the pair sub-streams): one clear (tile_cursor, in front, is the triangle pass')
+    launch_clear_words(r.tile_count, (size_t)r.n_tiles + 8u + kSubStreams + 8u, stream); // (... and kExtraTurnsWord behind them)
     // Items per workgroup. One is best while the grid is small (S10k: 0.169 ms; two: 0.189, four: 0.21 — an item is a chain of dependent
     // memory operations, and a wavefront that takes a second item doubles it); tens of thousands of small items are bound by workgroup
     // turnover instead (50 000 glyphs: one 0.45, two 0.31, four 0.31, eight 0.33 ms). So: about 12 000 workgroups.

@@ -917,8 +917,8 @@ static void launch_prim_setup_walk(const SceneDev& s, const RasterParams& r, hip
 // launchers of the triangle pass launch nothing for a sample count it does not draw (api.hip render_impl refuses such a pass up front).
 void launch_bin(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_setup) {
     if (!triangle_pass_samples(samples)) return;
-    // tile_cursor, tile_count and the overflow words are adjacent: one memset ([5] belongs to the edge pass (bin_edges.hip); cleared so that the host never sees a stale flag)
-    (void)hipMemsetAsync(r.tile_cursor, 0, sizeof(uint32_t) * 2u * r.n_tiles + 32, stream);
+    // tile_cursor, tile_count and the overflow words are adjacent: one clear ([5] belongs to the edge pass (bin_edges.hip); cleared so that the host never sees a stale flag)
+    launch_clear_words(r.tile_cursor, 2u * (size_t)r.n_tiles + 8u, stream); // (single-wave workgroups: bin_edges.hip)
     switch (samples) {
         case 1: launch_prim_setup_walk<1>(s, r, stream, mark, ctx, after_setup); break;
         case 2: launch_prim_setup_walk<2>(s, r, stream, mark, ctx, after_setup); break;
