@@ -386,6 +386,9 @@ crh_status crh_scene_render_draws(crh_scene* scene, crh_frame* frame, const floa
  *   stops        offsets non-decreasing in [0, 1]. In front of the first stop its colour, behind the last stop its colour; between stops i and
  *                i + 1 with o_i < o_i+1: c_i + f (c_i+1 - c_i), f = (t - o_i) / (o_i+1 - o_i), per straight-alpha channel — equal stop colours
  *                give that colour back exactly. Two stops with one offset make a hard edge; at t equal to it the later stop wins.
+ *   non-finite   p is not finite where a projective instance divides by W = 0 or a coordinate overflows f32, and t may then be NaN (REPEAT and
+ *                REFLECT of an infinite t are NaN as well). PAD's clamp takes NaN as 0; under REPEAT and REFLECT a NaN t compares below every
+ *                offset and gives the first stop's colour. Hence equal stop colours give that colour back exactly for every t, NaN included.
  *   source       paint(t) * instance colour per channel (straight alpha), premultiplied as the solid colour is (rgb * a, a), then blended with
  *                the renderer's blend state as crh_renderer_create_blended describes: source clamped to [0, 1], the frame format's rounding of
  *                writes, the write mask. Under the default "over" state a painted pass evaluates "over" in that same form: a painted cover is

@@ -37,7 +37,7 @@ def spread_t(t, spread):
     if spread == R.Spread.Reflect:
         u = t - 2.0 * np.floor(t / 2.0)
         return np.where(u <= 1.0, u, 2.0 - u)
-    return np.clip(t, 0.0, 1.0)
+    return np.clip(np.where(np.isnan(t), 0.0, t), 0.0, 1.0)  # PAD's clamp takes NaN as 0 (include/contrast_hip.h, `non-finite`)
 
 
 def raw_t(paint, p):
