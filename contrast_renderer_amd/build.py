@@ -15,7 +15,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
 # for the whole kernel, and the raster kernels spilled exactly those (k_raster_edges<4,1,true,false>: 100 B of scratch per lane -> 12, 96 -> 95 registers;
 # k_raster_fill 94 -> 76 registers; k_raster_rows 112 -> 95). Same results bit for bit (no contraction either way); S10k raster kernel 0.166 -> 0.151 ms alone,
 # dashed scene 1.557 -> 1.481 (profiles/r06_experiments.txt). CRH_FILE_FLAGS="file.hip:-flag,-flag;..." replaces the table (A/B runs).
-FILE_FLAGS = {"raster_edges.hip": ["-fno-slp-vectorize"], "bin_edges.hip": ["-fno-slp-vectorize"], "raster.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=65536"], "tessellate.hip": ["-fno-slp-vectorize"]}  # (raster.hip: k_raster_tile<4,1,true,true> 150 -> 127 registers; tessellate.hip: k_tess_runs<true> 182 -> 146)
+FILE_FLAGS = {"raster_edges.hip": ["-fno-slp-vectorize"], "bin_edges.hip": ["-fno-slp-vectorize", "-mllvm", "-disable-machine-licm"], "raster.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=65536"], "tessellate.hip": ["-fno-slp-vectorize"]}  # (raster.hip: k_raster_tile<4,1,true,true> 150 -> 127 registers; tessellate.hip: k_tess_runs<true> 182 -> 146)
+# bin_edges.hip without LLVM's machine-level loop-invariant code motion: k_bin_flat's body is a loop over the workgroup's batches that nearly always runs once,
+# and the pass moved some forty constants and table offsets in front of it, into vector registers that then lived through all eight phases — at 128 registers
+# (four waves per SIMD) the kernel spilled 28 B per lane for them; without the pass it needs 125 and no scratch memory.
 # raster.hip also raises LLVM's size limit for `#pragma unroll` (16384 by default): the body's turn loop in k_raster_mip<8, ...> is larger, and a loop that
 # stays rolled indexes the per-sample arrays at run time, which puts them in scratch (144 B per lane). The kernels that unrolled before are unchanged by it.
 OUT = os.path.join(HERE, "libcontrast_hip.so")

@@ -103,10 +103,19 @@ __global__ __launch_bounds__(256) void k_item_nslots(SceneDev s, RasterParams r,
 
 // ---------------------------------------------------------------------------------------------- triangle setup (plain instances)
 // oracle/raster.hpp setup_triangle + setup_attribute for candidate c of the Shape (lines, joints, curve lists); false: nothing to draw
-CRH_D bool setup_plain_triangle(const SceneDev& s, const RasterParams& r, const ItemCtx& ctx, uint32_t c, PrimRec& rec) {
+// In four steps, so that k_bin_flat can keep its global loads in front of its record stores and hold no more of a triangle than the step at hand
+// needs: the loads; the vertices on the frame (false: nothing to draw); the coverage half; the fragment half. setup_plain_triangle is all four.
+struct PlainTri {
+    float2 p[3];
+    float attr[3][4];
+    uint32_t kind, flat_u, desc;
+    float end_y;
+    int n_attr;
+    bool valid;
+};
+CRH_D void load_plain_triangle(const SceneDev& s, const ItemCtx& ctx, uint32_t c, PlainTri& out) {
     const uint32_t* cb = ctx.cb;
     const uint32_t dyn0 = ctx.dyn0;
-    const float W = (float)r.width, H = (float)r.height;
     float2 p[3];
     float attr[3][4] = {};
     uint32_t kind, flat_u = 0, desc = 0;
@@ -183,22 +192,39 @@ CRH_D bool setup_plain_triangle(const SceneDev& s, const RasterParams& r, const 
         n_attr = 0;
     }
 #pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        out.p[v] = p[v];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) out.attr[v][a] = attr[v][a];
+    }
+    out.kind = kind, out.flat_u = flat_u, out.desc = desc, out.end_y = end_y, out.n_attr = n_attr, out.valid = valid;
+}
+// the vertices on the frame (t.p), the determinant and the pixel box; false: nothing to draw
+CRH_D bool place_plain_triangle(const RasterParams& r, const ItemCtx& ctx, PlainTri& t, float& det_out, ushort4& box) {
+    const float W = (float)r.width, H = (float)r.height;
+    float2* p = t.p;
+#pragma unroll
     for (int v = 0; v < 3; ++v) p[v] = to_framebuffer(ctx, W, H, p[v].x, p[v].y);
     const float d1x = p[1].x - p[0].x, d1y = p[1].y - p[0].y;
     const float d2x = p[2].x - p[0].x, d2y = p[2].y - p[0].y;
     const float det = d1x * d2y - d2x * d1y;
-    if (!(valid && det != 0.0f && det == det && is_finite(det))) return false;
+    det_out = det;
+    if (!(t.valid && det != 0.0f && det == det && is_finite(det))) return false;
     const float minx = fminf(p[0].x, fminf(p[1].x, p[2].x)), maxx = fmaxf(p[0].x, fmaxf(p[1].x, p[2].x));
     const float miny = fminf(p[0].y, fminf(p[1].y, p[2].y)), maxy = fmaxf(p[0].y, fmaxf(p[1].y, p[2].y));
     const bool nan_free = minx == minx && maxx == maxx && miny == miny && maxy == maxy;
     const int x0 = (int)floorf(fminf(fmaxf(minx, 0.0f), W)), x1 = (int)floorf(fmaxf(fminf(maxx, W - 1.0f), -1.0f));
     const int y0 = (int)floorf(fminf(fmaxf(miny, 0.0f), H)), y1 = (int)floorf(fmaxf(fminf(maxy, H - 1.0f), -1.0f));
     if (!(nan_free && x0 <= x1 && y0 <= y1)) return false;
-    rec.cov.box = make_ushort4((unsigned short)x0, (unsigned short)x1, (unsigned short)y0, (unsigned short)y1);
-    const float inv_det = 1.0f / det;
+    box = make_ushort4((unsigned short)x0, (unsigned short)x1, (unsigned short)y0, (unsigned short)y1);
+    return true;
+}
+// (cov.box is the caller's: place_plain_triangle's)
+CRH_D void plain_triangle_coverage(const PlainTri& t, float det, PrimCoverage& cov) {
+    const float2* p = t.p;
     const bool front = det < 0.0f;
     const float2 nv[3] = {p[0], det < 0.0f ? p[2] : p[1], det < 0.0f ? p[1] : p[2]};
-    uint32_t flags = (front ? 8u : 0u) | (kind << 4);
+    uint32_t flags = (front ? 8u : 0u) | (t.kind << 4);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const float2 a = nv[i], b = nv[(i + 1) % 3];
@@ -207,30 +233,47 @@ CRH_D bool setup_plain_triangle(const SceneDev& s, const RasterParams& r, const 
         const bool flip = !(a.x < b.x || (a.x == b.x && a.y < b.y));
         const float2 el = flip ? b : a, eh = flip ? a : b;
         const float sg = flip ? -1.0f : 1.0f;
-        rec.cov.lo_x[i] = el.x;
-        rec.cov.lo_y[i] = el.y;
-        rec.cov.bx[i] = (eh.x - el.x) * sg;
-        rec.cov.nay[i] = -(eh.y - el.y) * sg;
+        cov.lo_x[i] = el.x;
+        cov.lo_y[i] = el.y;
+        cov.bx[i] = (eh.x - el.x) * sg;
+        cov.nay[i] = -(eh.y - el.y) * sg;
     }
+    cov.flags = flags;
+    cov.desc = t.desc;
+}
+CRH_D void plain_triangle_fragment(const ItemCtx& ctx, const PlainTri& t, float det, PrimFragment& frag) {
+    const float2* p = t.p;
+    const float d1x = p[1].x - p[0].x, d1y = p[1].y - p[0].y;
+    const float d2x = p[2].x - p[0].x, d2y = p[2].y - p[0].y;
+    const float inv_det = 1.0f / det;
+    const int n_attr = t.n_attr;
 #pragma unroll
     for (int a = 0; a < 4; ++a) { // selects, not branches on the run-time n_attr: those made the compiler index the record in scratch memory (40 B per lane,
         // and every scratch access is a vector-memory operation that waits for the record stores in flight)
-        const float da1 = attr[1][a] - attr[0][a], da2 = attr[2][a] - attr[0][a];
+        const float da1 = t.attr[1][a] - t.attr[0][a], da2 = t.attr[2][a] - t.attr[0][a];
         const bool on = a < n_attr;
-        rec.frag.a0[a] = on ? attr[0][a] : 0.0f;
-        rec.frag.gx[a] = on ? (da1 * d2y - da2 * d1y) * inv_det : 0.0f;
-        rec.frag.gy[a] = on ? (da2 * d1x - da1 * d2x) * inv_det : 0.0f;
+        frag.a0[a] = on ? t.attr[0][a] : 0.0f;
+        frag.gx[a] = on ? (da1 * d2y - da2 * d1y) * inv_det : 0.0f;
+        frag.gy[a] = on ? (da2 * d1x - da1 * d2x) * inv_det : 0.0f;
     }
-    if (kind == EK_COVER_TRI) { // color_cover: (rgb * a, a), shaders.wgsl:304-309
+    if (t.kind == EK_COVER_TRI) { // color_cover: (rgb * a, a), shaders.wgsl:304-309
         const float* color = ctx.col;
-        rec.frag.a0[0] = color[0] * color[3], rec.frag.a0[1] = color[1] * color[3], rec.frag.a0[2] = color[2] * color[3], rec.frag.a0[3] = color[3];
+        frag.a0[0] = color[0] * color[3], frag.a0[1] = color[1] * color[3], frag.a0[2] = color[2] * color[3], frag.a0[3] = color[3];
     }
-    rec.frag.v0x = p[0].x;
-    rec.frag.v0y = p[0].y;
-    rec.frag.flat_u = flat_u;
-    rec.frag.end_y = end_y;
-    rec.cov.flags = flags;
-    rec.cov.desc = desc;
+    frag.v0x = p[0].x;
+    frag.v0y = p[0].y;
+    frag.flat_u = t.flat_u;
+    frag.end_y = t.end_y;
+}
+CRH_D bool setup_plain_triangle(const SceneDev& s, const RasterParams& r, const ItemCtx& ctx, uint32_t c, PrimRec& rec) {
+    PlainTri t;
+    load_plain_triangle(s, ctx, c, t);
+    float det;
+    ushort4 box;
+    if (!place_plain_triangle(r, ctx, t, det, box)) return false;
+    rec.cov.box = box;
+    plain_triangle_coverage(t, det, rec.cov);
+    plain_triangle_fragment(ctx, t, det, rec.frag);
     return true;
 }
 
@@ -922,7 +965,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(CRH_BIN_WAV
 // kernel's time. Here a workgroup (kFlatThreads lanes) takes a batch of up to kFlatThreads / 8 consecutive items at once:
 //   0  lane = item: the item's record (ItemCtx, slot ranges, counts) into LDS — ONE round of dependent loads for the whole batch;
 //   A  lane = triangle / lane = edge over the batch (prefix sums of the items' counts in LDS, five-step search): set-up records written
-//      to the heap, the primitive kept in registers, the item's pixel box and the facing of its hull strip gathered with LDS atomics;
+//      to the heap, the triangle's tile test kept in registers, the edges in the LDS table of the walks, the item's pixel box and the facing of its hull strip gathered with LDS atomics;
 //   B  lane = item: the item's tile rectangle and its share of a pool of per-tile tables in LDS;
 //   C  (pass 1) every edge adds its backdrop terms and counts, per tile of its own box, whether it matters there; every triangle
 //      counts the tiles it reaches — the triangles use the item's table too, so no primitive needs a global atomic of its own;
@@ -933,14 +976,17 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(CRH_BIN_WAV
 // triangles or 512 edges in ONE item, a rectangle beyond the pool — is queued for k_bin_edges<S, true>, which has no such limits.
 // Slots, records and keys are exactly those of k_bin_edges; the order of a tile's entries in memory differs, the raster kernel sorts.
 #ifndef CRH_FLAT_WAVES
-#define CRH_FLAT_WAVES 3 // 168 registers: no scratch memory (at 4 waves = 128 registers the triangle set-up spills, and a scratch access is a vector-memory
-                         // operation that can only be waited for together with the record stores in flight); three workgroups per CU
+#define CRH_FLAT_WAVES 4 // wavefronts per SIMD the kernel is compiled for, as a minimum AND a maximum (the kernel descriptor asks for registers accordingly). 4 fits since
+                         // the set-up keeps no edge and no whole triangle record in registers and the tables take 19.4 KB per 128 lanes: 125 registers, no scratch
+                         // memory, eight workgroups per CU, the benchmark scene's 1 663 batches in ONE round of 2 048 resident workgroups. -DCRH_FLAT_WAVES=3
+                         // is the same code held at three waves (A/B runs): the step measures the same within its spread — what it gained over the 168-register
+                         // kernel it gained from the smaller footprint beside the raster grid, not from the fourth wave.
 #endif
 #ifndef CRH_FLAT_ROUNDS
 #define CRH_FLAT_ROUNDS 3
 #endif
 #ifndef CRH_FLAT_STAGE
-#define CRH_FLAT_STAGE 128
+#define CRH_FLAT_STAGE 64 // entries of a wavefront's pair stage: every append goes out at once (128, a flush per 65 to 128 entries, measured within 1.5 %: DESIGN.md §4.3)
 #endif
 #ifndef CRH_FLAT_THREADS
 #define CRH_FLAT_THREADS 128 // threads of a workgroup of k_bin_flat: 256 (four wavefronts, a batch of up to 32 items), 128 or 64 (ONE wavefront, a quarter of every table).
@@ -957,7 +1003,7 @@ static_assert(kFlatThreads == 64u || kFlatThreads == 128u || kFlatThreads == 256
 #define CRH_FLAT_BATCH (CRH_FLAT_THREADS / 8) // items of a batch at most
 #endif
 // kFlatItems: entries of the index tables (find_item searches 32); kFlatBatch: items a batch holds (their LDS records)
-constexpr uint32_t kFlatItems = 32, kFlatBatch = CRH_FLAT_BATCH, kFlatTris = kFlatThreads, kFlatEdgeRounds = CRH_FLAT_ROUNDS, kFlatEdges = kFlatThreads * kFlatEdgeRounds, kFlatPool = CRH_FLAT_POOL * kFlatThreads, kFlatStage = CRH_FLAT_STAGE; // 256 threads: 37 KB of LDS
+constexpr uint32_t kFlatItems = 32, kFlatBatch = CRH_FLAT_BATCH, kFlatTris = kFlatThreads, kFlatEdgeRounds = CRH_FLAT_ROUNDS, kFlatEdges = kFlatThreads * kFlatEdgeRounds, kFlatPool = CRH_FLAT_POOL * kFlatThreads, kFlatStage = CRH_FLAT_STAGE; // 128 threads: 19.4 KB of LDS, static_assert in the kernel
 static_assert(kFlatBatch >= 1u && kFlatBatch <= kFlatItems, "CRH_FLAT_BATCH");
 constexpr uint32_t kFiOpaque = 1u, kFiSkip = 2u, kFiHullTris = 4u, kFiQueue = 8u; // kFiQueue: not binned here but by k_bin_edges (handed on when the item's turn is over)
 struct FlatItem {
@@ -999,23 +1045,41 @@ CRH_D void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #endif
 }
-// A boundary edge between the passes of k_bin_flat: five registers instead of BinEdge's fourteen (the rest is recomputed with the very
-// expressions load_edge used, so the values are the same bits).
+// A boundary edge in the LDS tables of k_bin_flat: its end points (one 16-byte access) and, in a table of 16-bit words beside them, its flags —
+// five words instead of BinEdge's fourteen (the rest is recomputed with the very expressions load_edge used, so the values are the same bits).
 struct PackedEdge {
     float lo_x, lo_y, hi_x, hi_y;
-    uint32_t flags; // bit 0 valid, 1 top-left, 2 hull, 3 sigma > 0, 4 down; bits 8-12: the item of the batch (in the LDS table of k_bin_flat)
 };
-CRH_D PackedEdge pack_edge(const BinEdge& e) {
-    return PackedEdge{e.lo_x, e.lo_y, e.hi_x, e.hi_y, (e.valid ? 1u : 0u) | (e.tl ? 2u : 0u) | (e.hull ? 4u : 0u) | (e.sigma > 0 ? 8u : 0u) | (e.down ? 16u : 0u)};
+// bit 0 valid, 1 top-left, 2 hull, 3 sigma > 0, 4 down; 5 / 6: the strip triangle that starts at a hull edge's position faces front / back
+// (the sign of BinEdge::strip_det; neither: none); bits 8-12: the item of the batch
+constexpr uint32_t kPeValid = 1u, kPeStripFront = 32u, kPeStripBack = 64u;
+CRH_D PackedEdge pack_edge(const BinEdge& e) { return PackedEdge{e.lo_x, e.lo_y, e.hi_x, e.hi_y}; }
+CRH_D uint32_t pack_edge_flags(const BinEdge& e, uint32_t item) {
+    return (e.valid ? kPeValid : 0u) | (e.tl ? 2u : 0u) | (e.hull ? 4u : 0u) | (e.sigma > 0 ? 8u : 0u) | (e.down ? 16u : 0u) |
+           (e.strip_det != 0.0f ? (e.strip_det < 0.0f ? kPeStripFront : kPeStripBack) : 0u) | (item << 8);
 }
-CRH_D BinEdge unpack_edge(const PackedEdge& p) {
+CRH_D BinEdge unpack_edge(const PackedEdge& p, uint32_t flags) {
     BinEdge e = {};
     e.lo_x = p.lo_x, e.lo_y = p.lo_y, e.hi_x = p.hi_x, e.hi_y = p.hi_y;
     e.bx = p.hi_x - p.lo_x;
     e.nay = -(p.hi_y - p.lo_y);
     e.ymin = fminf(p.lo_y, p.hi_y), e.ymax = fmaxf(p.lo_y, p.hi_y);
-    e.valid = (p.flags & 1u) != 0u, e.tl = (p.flags >> 1) & 1u, e.hull = (p.flags >> 2) & 1u, e.sigma = (p.flags & 8u) ? 1 : -1, e.down = (int)((p.flags >> 4) & 1u);
+    e.valid = (flags & kPeValid) != 0u, e.tl = (flags >> 1) & 1u, e.hull = (flags >> 2) & 1u, e.sigma = (flags & 8u) ? 1 : -1, e.down = (int)((flags >> 4) & 1u);
     return e;
+}
+// The value, but as one the compiler cannot know to be the same in every turn of a loop (_v: a vector register, _s: a scalar one): what is computed
+// from it stays inside the turn instead of being hoisted in front of the loop and kept in registers across all of it.
+CRH_D uint32_t per_turn_v(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+CRH_D uint32_t per_turn_s(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(v));
+#endif
+    return v;
 }
 struct FlatTri { // a set-up triangle between the passes: its tile test and tile box
     TileTest test;
@@ -1043,25 +1107,32 @@ template <int S, uint32_t THREADS>
 #else
 #define CRH_FLAT_BUDGET
 #endif
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLAT_WAVES))) CRH_FLAT_BUDGET void k_bin_flat(SceneDev s, RasterParams r, uint32_t items_per_group) {
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLAT_WAVES, CRH_FLAT_WAVES))) CRH_FLAT_BUDGET void k_bin_flat(SceneDev s, RasterParams r, uint32_t items_per_group) {
     // (the namespace's constants of these names describe the default shape; inside the kernel they are this instantiation's)
     constexpr uint32_t kFlatThreads = THREADS, kFlatWaveCount = THREADS / 64u, kFlatBatch = THREADS / 8u, kFlatTris = THREADS, kFlatEdges = THREADS * kFlatEdgeRounds, kFlatPool = CRH_FLAT_POOL * THREADS;
     static_assert(kFlatBatch >= 1u && kFlatBatch <= kFlatItems, "a batch's index tables hold 32 items");
     __shared__ uint32_t stage_tile[kFlatWaveCount][kFlatStage], stage_pos[kFlatWaveCount][kFlatStage], stage_key[kFlatWaveCount][kFlatStage];
     __shared__ FlatItem items[kFlatBatch];
     __shared__ uint32_t tri_begin[kFlatItems + 1], edge_begin[kFlatItems + 1], pool_begin[kFlatItems + 1];
-    __shared__ int pool_bd[kFlatPool], pool_hbd[kFlatPool];
+    // Both backdrop sums of a pool cell in one word, bd + 65536 * hbd: a cell's sums — and every partial sum along its row — are bounded by the batch's edges
+    // (one unit per edge and tile row), so each fits sixteen bits and a sum of such words is the word of the sums. Pass 2 puts the tile's verdict there.
+    static_assert(kFlatEdges < 32768u, "a backdrop sum of a pool cell fits sixteen bits");
+    __shared__ int pool_back[kFlatPool];
     __shared__ uint32_t pool_cursor[kFlatPool]; // pass 1: the entries the item's edges and triangles have in the tile (bits 0-19; bits 20-31: the hull edges among them), then the next list position
     __shared__ uint32_t batch[6];               // items in the batch, its triangles, its edges, tiles of its pool, items of the batch that are binned in this turn, (edge, tile row) pairs
     __shared__ uint32_t wave_opaque[kFlatWaveCount];         // opaque whole-tile covers every wavefront found in pass 2
     __shared__ uint32_t wave_entries[2u * kFlatWaveCount];        // entries every wavefront appends in pass 3 ([0..3]) and in pass 2 ([4..7]); then where its share of the pair stream begins
-    __shared__ PackedEdge edge_table[kFlatEdges]; // the batch's boundary edges: the walks are balanced over (edge, tile row) pairs, whoever loaded the edge
+    __shared__ PackedEdge edge_table[kFlatEdges]; // the batch's boundary edges, from phase A on: the walks are balanced over (edge, tile row) pairs, whoever loaded the edge
+    __shared__ uint16_t edge_flags[kFlatEdges];   // (kPe*)
     __shared__ uint32_t row_begin[kFlatEdges + 1]; // exclusive prefix of the tile rows every edge walks
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    Stage st = {stage_tile[wave], stage_pos[wave], stage_key[wave], 0u, 0u, kFlatStage, 0xFFFFFFFFu};
+    // Everything above, against a compute unit's 160 KiB shared by the workgroups its four SIMDs hold at CRH_FLAT_WAVES wavefronts each (128 threads
+    // at four waves: eight workgroups of 20 480 B). The hardware hands LDS out in blocks, so the compiler's own occupancy figure is the last word.
+    constexpr uint32_t kFlatLds = sizeof(stage_tile) + sizeof(stage_pos) + sizeof(stage_key) + sizeof(items) + sizeof(tri_begin) + sizeof(edge_begin) + sizeof(pool_begin) + sizeof(pool_back) +
+                                  sizeof(pool_cursor) + sizeof(batch) + sizeof(wave_opaque) + sizeof(wave_entries) + sizeof(edge_table) + sizeof(edge_flags) + sizeof(row_begin);
+    static_assert(kFlatLds <= 160u * 1024u / (4u * CRH_FLAT_WAVES / kFlatWaveCount), "k_bin_flat's LDS tables keep it from CRH_FLAT_WAVES wavefronts per SIMD");
+    const uint32_t tid0 = threadIdx.x;
     uint32_t turn = 0; // batches this workgroup has binned (the pair sub-stream of a batch follows from it)
     const float ry_first = S == 1 ? 0.5f : 0.125f, r_last = (float)(kTile - 1) + (S == 1 ? 0.5f : 0.875f); // extreme sample offsets inside a tile
-    const float W = (float)r.width, H = (float)r.height;
     const uint32_t first_item = r.bin_batches ? r.bin_batches[2u * blockIdx.x] : blockIdx.x * items_per_group;
     const uint32_t last_item = r.bin_batches ? r.bin_batches[2u * blockIdx.x + 1u] : min(r.n_items, first_item + items_per_group);
     const bool all_queued = (r.debug & (1u | 2u | 4194304u)) != 0u; // debug bits 0, 1 (tests of k_bin_edges' own code paths), 22: every item takes that kernel
@@ -1071,6 +1142,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
     uint32_t dump_items = 0, dump_tris = 0, dump_edges = 0, dump_pool = 0, dump_work = 0, dump_walk = 0; // (... and what every workgroup held, CRH_BIN_DUMP)
 #endif
     for (uint32_t next = first_item; next < last_item;) {
+        // What follows from the lane's number and the frame's size is made anew in every turn (nearly every workgroup takes one): computed once in front
+        // of the loop, the table addresses of every phase and the frame's size as floats lived in some forty vector registers from the first phase to the last.
+        const uint32_t tid = per_turn_v(tid0), lane = tid & 63u, wave = tid >> 6;
+        Stage st = {stage_tile[wave], stage_pos[wave], stage_key[wave], 0u, 0u, kFlatStage, 0xFFFFFFFFu}; // (empty between turns: every turn flushes what it staged)
+        RasterParams rt = r; // (the set-up functions make the frame's size a float themselves)
+        rt.width = per_turn_s(r.width), rt.height = per_turn_s(r.height);
+        const float W = (float)rt.width, H = (float)rt.height;
         lds_barrier(); // (the previous batch's readers of the LDS records are through)
         // ---------------- 0: the records of the next items
         const uint32_t n_cand = min(kFlatBatch, last_item - next);
@@ -1117,68 +1195,80 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         // All loads first, all stores last: gfx950 counts vector loads and stores with ONE counter, in order — a load issued behind the 128-byte
         // record stores can only be waited for together with them, and those take tens of microseconds to drain when every workgroup
         // writes its records at once.
-        PackedEdge kept[kFlatEdgeRounds];
-        float strip_det[kFlatEdgeRounds];
-        uint32_t edge_item[kFlatEdgeRounds], edge_key[kFlatEdgeRounds];
+        // A lane keeps nothing of its edges across the triangle's set-up: they go to the LDS tables the walks read anyway as soon as they are loaded
+        // (LDS accesses are counted apart from the vector-memory ones) and come back from there for the record stores.
 #pragma unroll
         for (int k = 0; k < (int)kFlatEdgeRounds; ++k) {
             const uint32_t e = tid + kFlatThreads * (uint32_t)k;
-            kept[k] = PackedEdge{0.0f, 0.0f, 0.0f, 0.0f, 0u};
-            strip_det[k] = 0.0f;
-            edge_item[k] = 0u, edge_key[k] = 0u;
             if (e < n_edges) {
                 const uint32_t j = find_item(edge_begin, e), i = e - edge_begin[j];
                 const FlatItem& fi = items[j];
-                const BinEdge loaded = load_edge(s, r, fi.ctx, fi.n_fe, fi.n_hull, i);
-                kept[k] = pack_edge(loaded), strip_det[k] = loaded.strip_det;
-                edge_item[k] = j;
-                edge_key[k] = i < fi.n_fe ? fi.fe_slot0 + i : fi.hull_slot0 + (i - fi.n_fe);
+                const BinEdge loaded = load_edge(s, rt, fi.ctx, fi.n_fe, fi.n_hull, i);
+                edge_table[e] = pack_edge(loaded);
+                edge_flags[e] = (uint16_t)pack_edge_flags(loaded, j);
             }
         }
         CRH_FLAT_PHASE(1) // edge set-up
         FlatTri tri;
         tri.nt = 0u, tri.item = 0u, tri.key = 0u, tri.bx0 = tri.bx1 = tri.by0 = 0u;
         tri.test = TileTest{};
-        PrimRec rec = {};
-        bool tri_drawn = false;
+        PlainTri corners;
+        corners.valid = false;
         if (tid < n_tris) {
             const uint32_t j = find_item(tri_begin, tid), t = tid - tri_begin[j];
             const FlatItem& fi = items[j];
             const ItemCtx& ctx = fi.ctx;
             const uint32_t c = t < ctx.cb[1] ? t : t - ctx.cb[1] + ctx.cb[2]; // the Shape's candidate numbering without the solid strips
-            tri_drawn = setup_plain_triangle(s, r, ctx, c, rec);
+            load_plain_triangle(s, ctx, c, corners);
             tri.key = fi.slot0 + 4u * t, tri.item = j;
         }
-        // ---- stores and LDS
+        // ---- stores and LDS. The triangle's record in two halves whose values do not live at the same time: the coverage half, which the tile test
+        // and the boxes are taken from before it is stored, then the fragment half.
 #ifdef CRH_ABLATE
         const bool store_records = (r.debug & 8388608u) == 0u; // tools/ablate_flat.sh: no record stores
 #else
         constexpr bool store_records = true;
 #endif
-        if (tri_drawn) {
-            if (store_records) *reinterpret_cast<PrimRec*>(r.slots + (size_t)tri.key * 32u) = rec;
-            tri.test.set(rec.cov, ry_first, r_last);
-            tri.bx0 = rec.cov.box.x / kTile, tri.bx1 = rec.cov.box.y / kTile, tri.by0 = rec.cov.box.z / kTile;
-            tri.nt = (tri.bx1 - tri.bx0 + 1u) * (rec.cov.box.w / kTile - tri.by0 + 1u);
+        if (tid < n_tris) {
             FlatItem& fi = items[tri.item];
-            atomicMin(&fi.box[0], ordered_int((float)rec.cov.box.x)), atomicMin(&fi.box[1], ordered_int((float)rec.cov.box.z));
-            atomicMax(&fi.box[2], ordered_int((float)rec.cov.box.y)), atomicMax(&fi.box[3], ordered_int((float)rec.cov.box.w));
+            float det;
+            ushort4 box;
+            if (place_plain_triangle(rt, fi.ctx, corners, det, box)) {
+                PrimRec* out = reinterpret_cast<PrimRec*>(r.slots + (size_t)tri.key * 32u);
+                { // (what the coverage half is made of goes on living as the tile test and the tile box)
+                    PrimCoverage cov;
+                    cov.box = box;
+                    plain_triangle_coverage(corners, det, cov);
+                    tri.test.set(cov, ry_first, r_last);
+                    tri.bx0 = box.x / kTile, tri.bx1 = box.y / kTile, tri.by0 = box.z / kTile;
+                    tri.nt = (tri.bx1 - tri.bx0 + 1u) * (box.w / kTile - tri.by0 + 1u);
+                    atomicMin(&fi.box[0], ordered_int((float)box.x)), atomicMin(&fi.box[1], ordered_int((float)box.z));
+                    atomicMax(&fi.box[2], ordered_int((float)box.y)), atomicMax(&fi.box[3], ordered_int((float)box.w));
+                    if (store_records) out->cov = cov;
+                }
+                PrimFragment frag;
+                plain_triangle_fragment(fi.ctx, corners, det, frag);
+                if (store_records) out->frag = frag;
+            }
         }
 #pragma unroll
         for (int k = 0; k < (int)kFlatEdgeRounds; ++k) {
-            if (tid + kFlatThreads * (uint32_t)k < n_edges) {
-                FlatItem& fi = items[edge_item[k]];
-                const BinEdge e = unpack_edge(kept[k]);
+            const uint32_t at = tid + kFlatThreads * (uint32_t)k;
+            if (at < n_edges) {
+                const uint32_t flags = edge_flags[at], j = (flags >> 8) & 31u;
+                FlatItem& fi = items[j];
+                const BinEdge e = unpack_edge(edge_table[at], flags);
                 if (e.valid) {
                     EdgeRec er;
                     er.flags = (EK_EDGE << 4) | (e.tl ? kEdgeTl : 0u) | (e.sigma > 0 ? kEdgeSigmaPos : 0u) | (e.hull ? kEdgeHull : 0u), er.pad0 = 0u;
                     er.lo_x = e.lo_x, er.lo_y = e.lo_y, er.hi_x = e.hi_x, er.hi_y = e.hi_y, er.bx = e.bx, er.nay = e.nay;
-                    if (store_records) *reinterpret_cast<EdgeRec*>(r.slots + (size_t)edge_key[k] * 32u) = er;
+                    const uint32_t i = at - edge_begin[j];
+                    if (store_records) *reinterpret_cast<EdgeRec*>(r.slots + (size_t)(i < fi.n_fe ? fi.fe_slot0 + i : fi.hull_slot0 + (i - fi.n_fe)) * 32u) = er;
                     atomicMin(&fi.box[0], ordered_int(e.lo_x)), atomicMin(&fi.box[1], ordered_int(e.ymin));
                     atomicMax(&fi.box[2], ordered_int(e.hi_x)), atomicMax(&fi.box[3], ordered_int(e.ymax));
                 }
                 // (a strip triangle is judged at its first position whether or not that position's chain edge is valid)
-                if (strip_det[k] != 0.0f) atomicOr(&fi.faces, strip_det[k] < 0.0f ? 1u : 2u);
+                if (flags & (kPeStripFront | kPeStripBack)) atomicOr(&fi.faces, (flags & kPeStripFront) ? 1u : 2u);
             }
         }
         CRH_FLAT_PHASE(2) // triangle set-up, record stores
@@ -1241,7 +1331,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         }
         lds_barrier();
         const uint32_t n_pool = batch[3], n_turn = batch[4]; // (items n_turn .. n_batch - 1 are set up but not binned: n_rect == 0)
-        for (uint32_t q = tid; q < n_pool; q += kFlatThreads) pool_bd[q] = 0, pool_hbd[q] = 0, pool_cursor[q] = 0u;
+        for (uint32_t q = tid; q < n_pool; q += kFlatThreads) pool_back[q] = 0, pool_cursor[q] = 0u;
         lds_barrier();
         CRH_FLAT_PHASE(4) // rectangles, pool cleared
         // ---------------- the edges' walks are balanced over (edge, tile row) pairs. A lane that walked ITS edge kept its wavefront in the loop
@@ -1264,18 +1354,17 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         for (int k = 0; k < (int)kFlatEdgeRounds; ++k) {
             const uint32_t e = tid + kFlatThreads * (uint32_t)k;
             if (e < n_edges) {
-                PackedEdge pe = kept[k];
-                const FlatItem& fi = items[edge_item[k]];
+                const uint32_t flags = edge_flags[e];
+                const FlatItem& fi = items[(flags >> 8) & 31u];
                 // the edge takes part: valid, its item is drawn here, and — a hull edge — its hull is binned as a chain
-                bool live = (pe.flags & 1u) != 0u && fi.n_rect != 0u && !((pe.flags & 4u) != 0u && (fi.flags & kFiHullTris) != 0u);
+                bool live = (flags & kPeValid) != 0u && fi.n_rect != 0u && !((flags & 4u) != 0u && (fi.flags & kFiHullTris) != 0u);
                 uint32_t rows = 0;
                 if (live) {
-                    const EdgeBox box = edge_box(unpack_edge(pe), fi);
+                    const EdgeBox box = edge_box(unpack_edge(edge_table[e], flags), fi);
                     live = box.by0 <= box.by1; // (an edge left of the rectangle — a Shape that sticks out of the frame — has no tile to walk but still crosses the rows' backdrop lines)
                     if (live) rows = (uint32_t)(box.by1 - box.by0 + 1);
                 }
-                pe.flags = (pe.flags & (live ? ~0u : ~1u)) | (edge_item[k] << 8);
-                edge_table[e] = pe;
+                if (!live) edge_flags[e] = (uint16_t)(flags & ~kPeValid);
                 row_begin[e] = rows;
             }
         }
@@ -1307,9 +1396,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
 #pragma unroll
                 for (uint32_t step = kFlatEdges >= 512u ? 512u : (kFlatEdges >= 256u ? 256u : 128u); step > 0u; step >>= 1)
                     if (ei + step < n_edges && row_begin[ei + step] <= w) ei += step;
-                const PackedEdge pe = edge_table[active ? ei : 0u];
-                const BinEdge e = unpack_edge(pe);
-                const uint32_t j = (pe.flags >> 8) & 31u;
+                const uint32_t pe_flags = edge_flags[active ? ei : 0u];
+                const BinEdge e = unpack_edge(edge_table[active ? ei : 0u], pe_flags);
+                const uint32_t j = (pe_flags >> 8) & 31u;
                 const FlatItem& fi = items[j];
                 const EdgeBox box = edge_box(e, fi);
                 const int ty = box.by0 + (int)(w - row_begin[ei]);
@@ -1368,7 +1457,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
                         if (nonzero) hi = mid; else lo = mid + 1u;
                     }
                 }
-                if (crosses && lo < nx) atomicAdd(&(e.hull ? pool_hbd : pool_bd)[base + lo], e.down ? -e.sigma : e.sigma);
+                if (crosses && lo < nx) atomicAdd(&pool_back[base + lo], (e.down ? -e.sigma : e.sigma) * (e.hull ? 65536 : 1));
             }
             const uint32_t cols = wave_max_u32(active && x0 <= x1 ? (uint32_t)(x1 - x0 + 1) : 0u);
             for (uint32_t c = 0; c < cols; ++c) {
@@ -1400,7 +1489,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
                 const uint32_t j = find_item(pool_begin, p);
                 const uint32_t q = p - pool_begin[j], nx = items[j].nx;
                 if (q % nx == 0u)
-                    for (uint32_t c = 1; c < nx; ++c) pool_bd[p + c] += pool_bd[p + c - 1u], pool_hbd[p + c] += pool_hbd[p + c - 1u];
+                    for (uint32_t c = 1; c < nx; ++c) pool_back[p + c] += pool_back[p + c - 1u];
             }
         }
         lds_barrier();
@@ -1416,7 +1505,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
                 const FlatItem& fi = items[j];
                 const uint32_t q = p - pool_begin[j], qy = q / fi.nx, qx = q - qy * fi.nx;
                 const uint32_t tile = (fi.ty_a + qy) * r.tiles_x + fi.tx_a + qx;
-                const int bd = pool_bd[p], hbd = pool_hbd[p];
+                const int both = pool_back[p], bd = (int)(short)(both & 0xFFFF), hbd = (both - bd) >> 16;
                 const uint32_t counted = pool_cursor[p];
                 const uint32_t n_touching = counted & 0x000FFFFFu; // entries of the item's edges and triangles in this tile
                 const bool hull_touch = (counted >> 20) != 0u;
@@ -1425,16 +1514,16 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
                 const int cbd = bd > 0 ? 1 : (bd < 0 ? -1 : 0), chbd = hbd > 0 ? 1 : (hbd < 0 ? -1 : 0);
                 const bool hull_over_tile = cover && hbd != 0 && !hull_touch;
                 const bool replaces_tile = hull_over_tile && (fi.flags & kFiOpaque) != 0u && n_touching == 0u && (bd & (int)r.winding_mask) != 0;
-                const uint32_t cover_key = fi.synth_b + (uint32_t)(cbd + 1) + 3u * (uint32_t)(chbd + 1) + (replaces_tile ? kCoverOpaque : (hull_over_tile ? kCoverHull : 0u));
                 const uint32_t n_bd = cover ? (abd ? abd - 1u : 0u) : abd, n_hbd = cover ? (ahbd ? ahbd - 1u : 0u) : 0u;
                 const uint32_t left = (cover ? 1u : 0u) + n_bd + n_hbd;
                 lefts[ch] = left;
                 my_synth += left;
                 my_opaque += replaces_tile ? 1u : 0u;
                 if (left + n_touching) reserved[ch] = atomicAdd(&r.tile_count[tile], left + n_touching);
-                // the verdict, for 2b: left (bits 0-11), backdrop units (12-23), COVER entry (24), bd > 0 (25), hbd > 0 (26) | the COVER key
-                pool_bd[p] = (int)(left | (n_bd << 12) | (cover ? 1u << 24 : 0u) | (bd > 0 ? 1u << 25 : 0u) | (hbd > 0 ? 1u << 26 : 0u));
-                pool_hbd[p] = (int)cover_key;
+                // the verdict, for 2b: left (bits 0-11), backdrop units (12-23), COVER entry (24), bd > 0 (25), hbd > 0 (26), bd < 0 (27), hbd < 0 (28),
+                // the COVER entry replaces the tile (29) or lies over all of it (30) — 2b makes the COVER key of the last six
+                pool_back[p] = (int)(left | (n_bd << 12) | (cover ? 1u << 24 : 0u) | (cbd > 0 ? 1u << 25 : 0u) | (chbd > 0 ? 1u << 26 : 0u) | (cbd < 0 ? 1u << 27 : 0u) | (chbd < 0 ? 1u << 28 : 0u) |
+                                     (replaces_tile ? 1u << 29 : 0u) | (hull_over_tile ? 1u << 30 : 0u));
             }
 #pragma unroll
             for (uint32_t ch = 0; ch < kChunks; ++ch)
@@ -1480,7 +1569,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             const FlatItem& fi = items[j];
             const uint32_t q = active ? p - pool_begin[j] : 0u, row_len = max(fi.nx, 1u), qy = q / row_len, qx = q - qy * row_len;
             const uint32_t tile = (fi.ty_a + qy) * r.tiles_x + fi.tx_a + qx;
-            const uint32_t verdict = active ? (uint32_t)pool_bd[p] : 0u, cover_key = active ? (uint32_t)pool_hbd[p] : 0u;
+            const uint32_t verdict = active ? (uint32_t)pool_back[p] : 0u;
+            const uint32_t cbd1 = 1u + ((verdict >> 25) & 1u) - ((verdict >> 27) & 1u), chbd1 = 1u + ((verdict >> 26) & 1u) - ((verdict >> 28) & 1u); // sign of either backdrop + 1
+            const uint32_t cover_key = fi.synth_b + cbd1 + 3u * chbd1 + ((verdict >> 29) & 1u ? kCoverOpaque : ((verdict >> 30) & 1u ? kCoverHull : 0u));
             const uint32_t bd_key = fi.synth_a + ((verdict >> 25) & 1u ? 0u : 1u), hbd_key = fi.synth_a + ((verdict >> 26) & 1u ? 2u : 3u);
             uint32_t left = verdict & 4095u, n_bd = (verdict >> 12) & 4095u, pos = active ? pool_cursor[p] - left : 0u;
             bool cover = (verdict >> 24) & 1u;
@@ -1563,15 +1654,15 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         CRH_FLAT_PHASE(8) // folded hulls
     }
     // (a run the host cut for one turn needed more: the costs it was cut by are stale — the host counts these and measures again, api.hip)
-    if (r.bin_batches && turn > 1u && tid == 0u) atomicAdd(&r.overflow[kExtraTurnsWord], turn - 1u);
+    if (r.bin_batches && turn > 1u && tid0 == 0u) atomicAdd(&r.overflow[kExtraTurnsWord], turn - 1u);
 #ifdef CRH_ABLATE
-    if ((r.debug & 65536u) && tid == 0u) {
+    if ((r.debug & 65536u) && tid0 == 0u) {
         const unsigned long long life = __builtin_amdgcn_s_memtime() - born_t;
         atomicMax(reinterpret_cast<unsigned long long*>(r.overflow + 120), life);
         atomicAdd(reinterpret_cast<unsigned long long*>(r.overflow + 122), life);
         atomicAdd(r.overflow + 124, 1u);
     }
-    if ((r.debug & 65536u) && r.item_cost && lane == 0u && wave == 0u) { // CRH_BIN_DUMP: the workgroup's record behind the items' costs
+    if ((r.debug & 65536u) && r.item_cost && tid0 == 0u) { // CRH_BIN_DUMP: the workgroup's record behind the items' costs
         uint32_t* rec = r.item_cost + 2u * (size_t)(r.n_items + 1u) + 8u * (size_t)blockIdx.x;
         rec[0] = (uint32_t)(__builtin_amdgcn_s_memtime() - born_t), rec[1] = turn, rec[2] = dump_items, rec[3] = dump_tris, rec[4] = dump_edges, rec[5] = dump_pool, rec[6] = dump_work, rec[7] = dump_walk;
     }
