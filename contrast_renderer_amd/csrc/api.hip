@@ -351,7 +351,8 @@ struct crh_frame {
     // What the frame's last pass ran (crh_debug_frame_last_pass; the tests that pin a path check that they reached it): the formulation
     // (choose_pass' 1 / 2 / 3, + 256 when it is the Scene's measured choice), whether it was the general one, RasterVariant, and BinRoute
     // + 256 with the lists in place (direct), + 512 in the heavy-first tile order, + 1024 when its binning was NOT ordered behind the binning of the pass
-    // before it (two lanes, two steady passes), + items per binning workgroup << 16 (0: measured runs).
+    // before it (two lanes, two steady passes), + 2048 when k_bin_flat's pass 3 replayed pass 1's hits (kBinReplayed; + 4096, kBinFellBack, is added by the tap
+    // itself from the pass' flag words), + items per binning workgroup << 16 (0: measured runs).
     // All zero for a pass that launched nothing (forget_last_pass).
     uint32_t last_formulation = 0, last_general = 0, last_raster = 0, last_bin = 0;
     bool cleared = true;
@@ -3493,9 +3494,12 @@ extern "C" crh_status crh_debug_frame_counters16(crh_frame* f, uint32_t out[16])
     HIP_TRY(hipMemset(static_cast<uint8_t*>(f->sets[f->last_set].overflow_p) + 32, 0, 32));
     return CRH_OK;
 }
-extern "C" crh_status crh_debug_frame_last_pass(crh_frame* f, uint32_t out[4]) { // tests only (host fields, no device): what the frame's last pass ran
+extern "C" crh_status crh_debug_frame_last_pass(crh_frame* f, uint32_t out[4]) { // tests only (host fields, nothing is waited for): what the frame's last pass ran
     if (!f || !out) return CRH_ERR_INVALID_ARGUMENT;
     out[0] = f->last_formulation, out[1] = f->last_general, out[2] = f->last_raster, out[3] = f->last_bin;
+    // (kBinFellBack is the one bit the device decides: reported once the pass' flag words are on the host — after a download or a synchronize —, never waited for here)
+    const crh_frame::BinSet& set = f->sets[f->last_set];
+    if ((f->last_bin & kBinReplayed) && set.used && set.flags_host && hipEventQuery(set.flags_ready) == hipSuccess && set.flags_host[kReplayFallbackWord] != 0u) out[3] |= kBinFellBack;
     return CRH_OK;
 }
 extern "C" crh_status crh_debug_frame_words(crh_frame* f, uint32_t out[128]) { // tools only: the whole 512-byte flag / counter block of the last set

@@ -5,8 +5,9 @@
 //                      hull chain) over the item's tile rectangle; per tile they count entries (one atomic), sum the backdrop (one lane per
 //                      edge, ballots) and append (tile, key) pairs to a wave-private LDS stage that is flushed to the pair stream in blocks
 //                      (one atomic per block). Q: the items k_bin_flat queued.
-//   k_bin_flat<S, T>   the same binning with the lanes packed ACROSS draw items: a batch of consecutive items per workgroup of T threads;
+//   k_bin_flat<S, T, R> the same binning with the lanes packed ACROSS draw items: a batch of consecutive items per workgroup of T threads;
 //                      the host cuts a pass into batches (flat_batches, flat_batch_limits, flat_threads_for) or sends it item by item (bin_itemwise).
+//                      R: the entries' places are taken from records of the first walk's hits instead of from a second walk (CRH_BIN_REPLAY).
 //   k_scatter          pair -> its slot in the tile's list (offsets from the scan of the counts).
 //   the ranges         k_item_nslots / k_shape_counts and the single-wave scans: slots per item or Shape and their prefixes (launch_slot_ranges,
 //                      launch_plain_ranges); k_tile_caps: the places of the next frames' lists (launch_tile_bases); k_shape_bounds, k_slab_items:
@@ -971,7 +972,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(CRH_BIN_WAV
 //      counts the tiles it reaches — the triangles use the item's table too, so no primitive needs a global atomic of its own;
 //   D  (pass 2) lane = tile of the pool: ONE returning atomic on the tile's global counter reserves the list positions of everything the
 //      item has there, the synthetic entries (COVER / backdrop units) are emitted;
-//   E  (pass 3) edges and triangles walk again and take their positions from the LDS cursors.
+//   E  (pass 3) edges and triangles walk again and take their positions from the LDS cursors — or, in the instantiations that replay, pass 1 has
+//      kept every hit as a 32-bit record in LDS (key, pool cell, index in the cell) and pass 3 is a loop over the records: lane = record.
 // A hull strip that folds (k_bin_edges) has its triangles binned the old way at the end. What does not fit a batch — more than 256
 // triangles or 512 edges in ONE item, a rectangle beyond the pool — is queued for k_bin_edges<S, true>, which has no such limits.
 // Slots, records and keys are exactly those of k_bin_edges; the order of a tile's entries in memory differs, the raster kernel sorts.
@@ -1002,6 +1004,13 @@ static_assert(kFlatThreads == 64u || kFlatThreads == 128u || kFlatThreads == 256
 #ifndef CRH_FLAT_BATCH
 #define CRH_FLAT_BATCH (CRH_FLAT_THREADS / 8) // items of a batch at most
 #endif
+#ifndef CRH_FLAT_HITS
+#define CRH_FLAT_HITS 400 // hit records per wavefront in the table of a workgroup that replays (k_bin_flat<S, T, true>): what the 128-thread tables leave of 160 KiB / 7, in whole
+                          // LDS blocks — 23 024 of 23 040 B. The batch's free edge places come on top (10 000 paths need up to 1 109 records a batch, glyphs 733).
+#endif
+// A hit of pass 1 as pass 3 replays it, in 32 bits: the index among the item's edge and triangle entries of its pool cell (bits 0-8: every edge
+// and every triangle of a batch enters a cell once at most), the pool cell (9-18), the key relative to the first slot of the batch's first item (19-31).
+constexpr uint32_t kHitIndexBits = 9, kHitCellBits = 10, kHitKeyBits = 32u - kHitIndexBits - kHitCellBits;
 // kFlatItems: entries of the index tables (find_item searches 32); kFlatBatch: items a batch holds (their LDS records)
 constexpr uint32_t kFlatItems = 32, kFlatBatch = CRH_FLAT_BATCH, kFlatTris = kFlatThreads, kFlatEdgeRounds = CRH_FLAT_ROUNDS, kFlatEdges = kFlatThreads * kFlatEdgeRounds, kFlatPool = CRH_FLAT_POOL * kFlatThreads, kFlatStage = CRH_FLAT_STAGE; // 128 threads: 19.4 KB of LDS, static_assert in the kernel
 static_assert(kFlatBatch >= 1u && kFlatBatch <= kFlatItems, "CRH_FLAT_BATCH");
@@ -1101,13 +1110,17 @@ struct FlatShape {
     uint32_t threads, batch, tris, edges, pool;
 };
 constexpr FlatShape flat_shape(uint32_t threads) { return FlatShape{threads, threads / 8u, threads, threads * CRH_FLAT_ROUNDS, CRH_FLAT_POOL * threads}; }
-template <int S, uint32_t THREADS>
+constexpr bool flat_replays(uint32_t threads) { return threads == 128u && kFlatThreads == 128u; } // the instantiations of k_bin_flat whose pass 3 is a replay (k_bin_flat's REPLAY)
+// REPLAY: pass 1 keeps every hit of an edge or a triangle as a 32-bit record in LDS and pass 3 is a loop over those records instead of the geometric
+// walk a second time; replay_cap: the records a wavefront may keep (CRH_BIN_REPLAY_CAP; at most what its table holds). A batch in which a wavefront
+// finds more, or whose keys outgrow the record, walks again — the whole batch: places from the records and places from cursor atomics never mix.
+template <int S, uint32_t THREADS, bool REPLAY>
 #ifdef CRH_FLAT_VGPRS
 #define CRH_FLAT_BUDGET __attribute__((amdgpu_num_vgpr(CRH_FLAT_VGPRS)))
 #else
 #define CRH_FLAT_BUDGET
 #endif
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLAT_WAVES, CRH_FLAT_WAVES))) CRH_FLAT_BUDGET void k_bin_flat(SceneDev s, RasterParams r, uint32_t items_per_group) {
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLAT_WAVES, CRH_FLAT_WAVES))) CRH_FLAT_BUDGET void k_bin_flat(SceneDev s, RasterParams r, uint32_t items_per_group, uint32_t replay_cap) {
     // (the namespace's constants of these names describe the default shape; inside the kernel they are this instantiation's)
     constexpr uint32_t kFlatThreads = THREADS, kFlatWaveCount = THREADS / 64u, kFlatBatch = THREADS / 8u, kFlatTris = THREADS, kFlatEdges = THREADS * kFlatEdgeRounds, kFlatPool = CRH_FLAT_POOL * THREADS;
     static_assert(kFlatBatch >= 1u && kFlatBatch <= kFlatItems, "a batch's index tables hold 32 items");
@@ -1125,11 +1138,27 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
     __shared__ PackedEdge edge_table[kFlatEdges]; // the batch's boundary edges, from phase A on: the walks are balanced over (edge, tile row) pairs, whoever loaded the edge
     __shared__ uint16_t edge_flags[kFlatEdges];   // (kPe*)
     __shared__ uint32_t row_begin[kFlatEdges + 1]; // exclusive prefix of the tile rows every edge walks
+    // The hits pass 1 keeps for pass 3 (REPLAY). An instantiation whose cells or entries per cell outgrow the record's fields, or with more than two
+    // wavefronts, does not replay. The table is this array and, behind it, whatever the batch leaves free of the edge table (four records per edge the batch
+    // does not have: a batch is full when ONE of its tables is, and with 10 000 cubic paths that is the triangles' — 162 of 384 edges on average, so the
+    // 800 records here become 1 690, and the largest batch of that scene has 1 109 hits; 800 alone hold two batches in three). The two wavefronts share it —
+    // the first fills it from the bottom, the second from the top, neither knows of the other —, so a wavefront that finds few leaves its share to its
+    // neighbour; whether the two have met is seen behind pass 1's barrier from their counts (hit_count), and a batch in which they have walks again.
+    constexpr bool kReplay = REPLAY && kFlatWaveCount <= 2u && kFlatPool <= (1u << kHitCellBits) && kFlatEdges + kFlatTris <= (1u << kHitIndexBits);
+    constexpr uint32_t kHitRegion = kReplay ? CRH_FLAT_HITS * kFlatWaveCount : 1u;
+    static_assert(sizeof(PackedEdge) == 16u, "four hit records in the place of an edge");
+    __shared__ uint32_t hit_rec[kHitRegion];
+    __shared__ uint32_t hit_count[kFlatWaveCount]; // records every wavefront wanted to keep
+    __shared__ uint32_t replay_off;                // a key of this batch does not fit the record: the batch walks again
     // Everything above, against a compute unit's 160 KiB shared by the workgroups its four SIMDs hold at CRH_FLAT_WAVES wavefronts each (128 threads
-    // at four waves: eight workgroups of 20 480 B). The hardware hands LDS out in blocks, so the compiler's own occupancy figure is the last word.
+    // at four waves: eight workgroups of 20 480 B). The hardware hands LDS out in blocks of 1 280 B, so the compiler's own occupancy figure is the last word.
+    // A kernel that replays gives one of those workgroups up for its records (128 threads: seven of 23 040 B, which still hold the 1 663 batches of 10 000
+    // paths at 4096^2 in one round of 1 792).
     constexpr uint32_t kFlatLds = sizeof(stage_tile) + sizeof(stage_pos) + sizeof(stage_key) + sizeof(items) + sizeof(tri_begin) + sizeof(edge_begin) + sizeof(pool_begin) + sizeof(pool_back) +
-                                  sizeof(pool_cursor) + sizeof(batch) + sizeof(wave_opaque) + sizeof(wave_entries) + sizeof(edge_table) + sizeof(edge_flags) + sizeof(row_begin);
-    static_assert(kFlatLds <= 160u * 1024u / (4u * CRH_FLAT_WAVES / kFlatWaveCount), "k_bin_flat's LDS tables keep it from CRH_FLAT_WAVES wavefronts per SIMD");
+                                  sizeof(pool_cursor) + sizeof(batch) + sizeof(wave_opaque) + sizeof(wave_entries) + sizeof(edge_table) + sizeof(edge_flags) + sizeof(row_begin) +
+                                  sizeof(hit_rec) + sizeof(hit_count) + sizeof(replay_off);
+    constexpr uint32_t kFlatGroupsPerCu = 4u * CRH_FLAT_WAVES / kFlatWaveCount - (kReplay ? 1u : 0u), kLdsBlock = 1280u;
+    static_assert(kFlatLds <= 160u * 1024u / kFlatGroupsPerCu / kLdsBlock * kLdsBlock, "k_bin_flat's LDS tables keep it from CRH_FLAT_WAVES wavefronts per SIMD (one workgroup per CU less where it replays)");
     const uint32_t tid0 = threadIdx.x;
     uint32_t turn = 0; // batches this workgroup has binned (the pair sub-stream of a batch follows from it)
     const float ry_first = S == 1 ? 0.5f : 0.125f, r_last = (float)(kTile - 1) + (S == 1 ? 0.5f : 0.875f); // extreme sample offsets inside a tile
@@ -1139,7 +1168,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
 #ifdef CRH_ABLATE
     unsigned long long phase_t = __builtin_amdgcn_s_memtime();
     const unsigned long long born_t = phase_t; // (tools/bin_phases.py: the longest-lived workgroup, overflow[120..121], and the sum, [122..123])
-    uint32_t dump_items = 0, dump_tris = 0, dump_edges = 0, dump_pool = 0, dump_work = 0, dump_walk = 0; // (... and what every workgroup held, CRH_BIN_DUMP)
+    uint32_t dump_items = 0, dump_tris = 0, dump_edges = 0, dump_pool = 0, dump_work = 0, dump_walk = 0, dump_wave_hits = 0, dump_batch_hits = 0; // (... and what every workgroup held, CRH_BIN_DUMP)
 #endif
     for (uint32_t next = first_item; next < last_item;) {
         // What follows from the lane's number and the frame's size is made anew in every turn (nearly every workgroup takes one): computed once in front
@@ -1152,6 +1181,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         lds_barrier(); // (the previous batch's readers of the LDS records are through)
         // ---------------- 0: the records of the next items
         const uint32_t n_cand = min(kFlatBatch, last_item - next);
+        if (kReplay && tid == 0u) replay_off = 0u;
         if (tid < n_cand) {
             const uint32_t item = next + tid;
             const DrawItem it = item_of(r, item);
@@ -1437,7 +1467,28 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         };
         // ---------------- C: pass 1
         uint32_t my_entries = 0; // what this lane will append in pass 3
-        for_edge_rows([&](bool active, const BinEdge& e, uint32_t j, const FlatItem& fi, int ty, int x0, int x1, uint32_t) {
+        // (REPLAY) ... and what the wavefront has found so far (uniform). A hit is kept with what the cell's counter held in front of it — the counter's
+        // atomic returns it —, which is the entry's index among the item's edge and triangle entries of that tile: pass 2 turns the counter into the first
+        // place of those entries in the tile's list, and first place + index is where pass 3 puts the key.
+        uint32_t n_hits = 0;
+        const uint32_t key0 = kReplay ? items[0].slot0 : 0u; // (a batch's items are consecutive, so are their slots: no key of the batch lies below the first item's first slot)
+        const uint32_t hit_room = kReplay ? kHitRegion + 4u * (kFlatEdges - n_edges) : 0u; // records the table holds in this batch: hit_rec, then the edge table behind the batch's edges
+        // record `at` of this wavefront (at < hit_room): counted from the bottom of the table by the first wavefront, from its top by the second
+        auto hit_slot = [&](uint32_t at) -> uint32_t* {
+            const uint32_t place = (wave & 1u) ? hit_room - 1u - at : at;
+            return place < kHitRegion ? &hit_rec[place] : reinterpret_cast<uint32_t*>(edge_table + n_edges) + (place - kHitRegion);
+        };
+        auto remember = [&](bool hit, uint32_t cell, uint32_t counted, uint32_t key) {
+            const unsigned long long ballot = __ballot(hit);
+            if (!ballot) return;
+            const uint32_t at = n_hits + lanes_below(ballot, lane), rel = key - key0;
+            if (hit) {
+                if (rel >> kHitKeyBits) replay_off = 1u;
+                else if (at < hit_room) *hit_slot(at) = (rel << (kHitIndexBits + kHitCellBits)) | (cell << kHitIndexBits) | (counted & ((1u << kHitIndexBits) - 1u));
+            }
+            n_hits += (uint32_t)__popcll(ballot);
+        };
+        for_edge_rows([&](bool active, const BinEdge& e, uint32_t j, const FlatItem& fi, int ty, int x0, int x1, uint32_t key) {
             const uint32_t base = pool_begin[j] + ((uint32_t)ty - fi.ty_a) * fi.nx, nx = fi.nx, tx_a = fi.tx_a;
             // Along a tile row the backdrop term of an edge that crosses the row's line is 0 left of the edge and +-1 from some column on (the
             // edge function is monotone in x under fmaf, so the very predicate a tile would evaluate switches once): that column is found
@@ -1462,7 +1513,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             const uint32_t cols = wave_max_u32(active && x0 <= x1 ? (uint32_t)(x1 - x0 + 1) : 0u);
             for (uint32_t c = 0; c < cols; ++c) {
                 const int tx = x0 + (int)c;
-                if (active && tx <= x1 && matters(e, tx, ty)) atomicAdd(&pool_cursor[base + ((uint32_t)tx - tx_a)], e.hull ? 0x00100001u : 1u), ++my_entries;
+                if (kReplay) {
+                    const bool hit = active && tx <= x1 && matters(e, tx, ty);
+                    const uint32_t cell = base + ((uint32_t)tx - tx_a);
+                    uint32_t counted = 0;
+                    if (hit) counted = atomicAdd(&pool_cursor[cell], e.hull ? 0x00100001u : 1u), ++my_entries;
+                    remember(hit, cell, counted, key);
+                } else if (active && tx <= x1 && matters(e, tx, ty)) atomicAdd(&pool_cursor[base + ((uint32_t)tx - tx_a)], e.hull ? 0x00100001u : 1u), ++my_entries;
             }
         });
         if (n_tris) {
@@ -1470,10 +1527,31 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             const bool live = tri.nt != 0u && fi.n_rect != 0u;
             const uint32_t base = pool_begin[tri.item], nx = fi.nx, tx_a = fi.tx_a, ty_a = fi.ty_a;
             walk_tri(tri, live, [&](bool hit, uint32_t tx, uint32_t ty) {
-                if (hit) atomicAdd(&pool_cursor[base + (ty - ty_a) * nx + (tx - tx_a)], 1u), ++my_entries;
+                if (kReplay) {
+                    const uint32_t cell = base + (ty - ty_a) * nx + (tx - tx_a);
+                    uint32_t counted = 0;
+                    if (hit) counted = atomicAdd(&pool_cursor[cell], 1u), ++my_entries;
+                    remember(hit, cell, counted, tri.key);
+                } else if (hit) atomicAdd(&pool_cursor[base + (ty - ty_a) * nx + (tx - tx_a)], 1u), ++my_entries;
             });
         }
+        if (kReplay && lane == 0u) hit_count[wave] = n_hits;
         lds_barrier();
+        // (REPLAY) does the batch replay? (uniform over the workgroup: LDS words and a kernel argument)
+        bool replay = kReplay;
+        if (kReplay) {
+            replay = replay_off == 0u;
+            uint32_t together = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kFlatWaveCount; ++w) {
+                const uint32_t n = hit_count[w];
+                together += n;
+                replay = replay && n <= replay_cap;
+            }
+            replay = replay && together <= hit_room;
+            replay = __builtin_amdgcn_readfirstlane((int)replay) != 0; // (a scalar: what depends on it is a branch, not a mask)
+            if (!replay && tid == 0u) atomicAdd(&r.overflow[kReplayFallbackWord], 1u);
+        }
         CRH_FLAT_PHASE(5) // pass 1
         // ---------------- D: pass 2, lane = tile of the pool (the COVER entry carries one unit of either backdrop).
         // Pass 1 left every edge's backdrop unit at the first column it applies to: summed along the rows first, in place (the lane of a row's
@@ -1539,6 +1617,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         if (tid == 0u) { // the workgroup's range of the pair stream: wavefront w's pass-2 entries, then its pass-3 entries
             uint32_t total = 0;
             for (uint32_t w = 0; w < 2u * kFlatWaveCount; ++w) total += wave_entries[w];
+#ifdef CRH_ABLATE
+            { // (tools/bin_phases.py: the hits of pass 1 — pass 3's entries — per wavefront and per batch, the largest of the workgroup's turns)
+                uint32_t hits = 0;
+                for (uint32_t w = 0; w < kFlatWaveCount; ++w) hits += wave_entries[w], dump_wave_hits = max(dump_wave_hits, wave_entries[w]);
+                dump_batch_hits = max(dump_batch_hits, hits);
+            }
+#endif
             uint32_t opaque = 0;
             for (uint32_t w = 0; w < kFlatWaveCount; ++w) opaque += wave_opaque[w];
             if (opaque) atomicAdd(&r.overflow[4], opaque); // the host's statistic: are there tiles to start late in?
@@ -1575,6 +1660,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             const uint32_t bd_key = fi.synth_a + ((verdict >> 25) & 1u ? 0u : 1u), hbd_key = fi.synth_a + ((verdict >> 26) & 1u ? 2u : 3u);
             uint32_t left = verdict & 4095u, n_bd = (verdict >> 12) & 4095u, pos = active ? pool_cursor[p] - left : 0u;
             bool cover = (verdict >> 24) & 1u;
+            if (replay && active) pool_back[p] = (int)tile; // (the verdict is read: the cell's word now tells the replay which tile the cell is)
             for (;;) {
                 const unsigned long long ballot = __ballot(left != 0u);
                 if (!ballot) break;
@@ -1593,7 +1679,28 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         }
         lds_barrier(); // (pass 3 moves the cursors 2b has just read)
         CRH_FLAT_PHASE(6) // pass 2
-        // ---------------- E: pass 3: the same walk, every entry with its place in the tile's list
+        // ---------------- E: pass 3: every entry of an edge or a triangle with its place in the tile's list. A replay of the records pass 1 kept, lane = record:
+        // no search, no edge box, no exact test, no LDS atomic — the keys go where stage_append<true> would have put them, the wavefront's own
+        // records to the wavefront's own share of the workgroup's range ...
+        if (replay) {
+            stage_flush_reserved(st, r, lane); // (the synthetic entries of 2b)
+            for (uint32_t i = lane; i < n_hits; i += 64u) {
+                const uint32_t rec = *hit_slot(i), cell = (rec >> kHitIndexBits) & ((1u << kHitCellBits) - 1u);
+                const uint32_t tile = (uint32_t)pool_back[cell], pos = pool_cursor[cell] + (rec & ((1u << kHitIndexBits) - 1u)), key = key0 + (rec >> (kHitIndexBits + kHitCellBits));
+#ifdef CRH_ABLATE
+                if (r.debug & 512u) continue;
+#endif
+                if (r.direct) { // (stage_flush_direct's store)
+                    const uint32_t place = r.tile_base[tile];
+                    if (pos < r.tile_base[tile + 1u] - place && place + pos < r.pair_capacity) r.tile_list[place + pos] = key;
+                    else r.overflow[0] = 1u; // the tile has outgrown the place the previous frame left it
+                } else if (st.at != 0xFFFFFFFFu) {
+                    r.pair_tile[st.at + i] = tile, r.pair_pos[st.at + i] = pos, r.pair_key[st.at + i] = key;
+                }
+            }
+            if (st.at != 0xFFFFFFFFu) st.at += n_hits;
+        } else {
+        // ... or, in a batch that does not replay, the same walk again, the places from the cursors
         for_edge_rows([&](bool active, const BinEdge& e, uint32_t j, const FlatItem& fi, int ty, int x0, int x1, uint32_t key) {
             const uint32_t base = pool_begin[j] + ((uint32_t)ty - fi.ty_a) * fi.nx, tx_a = fi.tx_a;
             const uint32_t cols = wave_max_u32(active && x0 <= x1 ? (uint32_t)(x1 - x0 + 1) : 0u);
@@ -1622,6 +1729,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             });
         }
         stage_flush_reserved(st, r, lane); // (the batch's range is used up exactly)
+        }
         CRH_FLAT_PHASE(7) // pass 3
         // ---------------- hull strips that fold: triangle by triangle, as cover triangles (keys behind the fill chain and the backdrop slots);
         // their entries take the ordinary way into the pair stream (a cursor atomic per block)
@@ -1664,7 +1772,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
     }
     if ((r.debug & 65536u) && r.item_cost && tid0 == 0u) { // CRH_BIN_DUMP: the workgroup's record behind the items' costs
         uint32_t* rec = r.item_cost + 2u * (size_t)(r.n_items + 1u) + 8u * (size_t)blockIdx.x;
-        rec[0] = (uint32_t)(__builtin_amdgcn_s_memtime() - born_t), rec[1] = turn, rec[2] = dump_items, rec[3] = dump_tris, rec[4] = dump_edges, rec[5] = dump_pool, rec[6] = dump_work, rec[7] = dump_walk;
+        rec[0] = (uint32_t)(__builtin_amdgcn_s_memtime() - born_t), rec[1] = min(turn, 255u) | (min(dump_wave_hits, 4095u) << 8) | (min(dump_batch_hits, 4095u) << 20), rec[2] = dump_items, rec[3] = dump_tris, rec[4] = dump_edges, rec[5] = dump_pool, rec[6] = dump_work, rec[7] = dump_walk; // ([1]: turns | the most hits of a wavefront << 8 | of a batch << 20)
     }
 #endif
 }
@@ -1866,9 +1974,17 @@ uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t sam
         const uint32_t items_per_group = pinned ? min(pinned, shape.batch) : min(fitting, max(1u, (r.n_items + resident - 1u) / resident));
         const uint32_t flat_grid = r.bin_batches ? r.n_bin_batches : (r.n_items + items_per_group - 1u) / items_per_group, queue_grid = min(r.n_items, 4096u);
         if (!r.bin_batches) route |= min(items_per_group, 255u) << 16;
+        // Pass 3 as a replay of pass 1's hits, where the instantiation has the LDS for the records: the default workgroup of 128 threads (the 64-thread
+        // kernel is at its LDS limit for four waves per SIMD without them). CRH_BIN_REPLAY=0: the walk again, as before; CRH_BIN_REPLAY_CAP=<n> (tests):
+        // a wavefront keeps at most n records, 0 makes every batch walk again. Both read per launch.
+        const char* const replay_env = getenv("CRH_BIN_REPLAY");
+        const bool replay = flat_replays(shape.threads) && !(replay_env && atoi(replay_env) == 0);
+        const uint32_t replay_cap = getenv("CRH_BIN_REPLAY_CAP") ? (uint32_t)max(0, atoi(getenv("CRH_BIN_REPLAY_CAP"))) : 0xFFFFFFFFu;
+        if (replay) route |= kBinReplayed;
         by_samples([&](auto S) {
-            if (shape.threads == 64u) hipLaunchKernelGGL((k_bin_flat<S(), 64u>), dim3(flat_grid), dim3(64), 0, stream, s, r, items_per_group);
-            else hipLaunchKernelGGL((k_bin_flat<S(), kFlatThreads>), dim3(flat_grid), dim3(kFlatThreads), 0, stream, s, r, items_per_group);
+            if (shape.threads == 64u) hipLaunchKernelGGL((k_bin_flat<S(), 64u, false>), dim3(flat_grid), dim3(64), 0, stream, s, r, items_per_group, replay_cap);
+            else if (replay) hipLaunchKernelGGL((k_bin_flat<S(), kFlatThreads, kFlatThreads == 128u>), dim3(flat_grid), dim3(kFlatThreads), 0, stream, s, r, items_per_group, replay_cap);
+            else hipLaunchKernelGGL((k_bin_flat<S(), kFlatThreads, false>), dim3(flat_grid), dim3(kFlatThreads), 0, stream, s, r, items_per_group, replay_cap);
             if (!r.skip_queue) hipLaunchKernelGGL((k_bin_edges<S(), true>), dim3(queue_grid), dim3(128), 0, stream, s, r);
         });
     }

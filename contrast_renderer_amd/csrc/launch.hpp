@@ -65,7 +65,7 @@ void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const Li
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream); // zeroes n_words 32-bit words with single-wave workgroups (the clear in front of both passes' binning kernels)
 void launch_slot_ranges(const SceneDev& s, const RasterParams& r, uint32_t n_items, uint32_t* item_nslots, uint32_t* slot_begin, uint32_t* scratch, hipStream_t stream);
-uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin); // -> BinRoute | items per workgroup << 16
+uint32_t launch_bin_edges(const SceneDev& s, const RasterParams& r, uint32_t samples, hipStream_t stream, MarkFn mark, void* ctx, hipEvent_t after_bin); // -> BinRoute | kBinReplayed | items per workgroup << 16
 void launch_scatter(const RasterParams& r, hipStream_t stream, MarkFn mark, void* ctx);
 void launch_shape_bounds(const SceneDev& s, float* bounds, hipStream_t stream);
 void launch_slab_items(const RasterParams& r, uint8_t* elsewhere, hipStream_t stream);

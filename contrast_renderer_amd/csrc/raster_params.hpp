@@ -35,6 +35,9 @@ enum RasterVariant : uint32_t { kRasterFill = 1, kRasterEdges = 2, kRasterEdgesL
 // ... and its binning route (the triangle pass' k_prim_setup / k_tile_walk, k_bin_flat over a count of items per workgroup or over the runs
 // a verified pass measured, k_bin_edges item by item)
 enum BinRoute : uint32_t { kBinTriangles = 1, kBinFlatItems = 2, kBinFlatBatches = 3, kBinItemwise = 4 };
+// ... with kBinReplayed when k_bin_flat's pass 3 replayed the hits pass 1 kept (CRH_BIN_REPLAY), and kBinFellBack once the pass' flag words have
+// reached the host and say that some batch of it walked again instead (its hits outgrew the table: overflow[kReplayFallbackWord] counts those batches)
+constexpr uint32_t kBinReplayed = 2048u, kBinFellBack = 4096u;
 
 // Configuration::blending of the colour cover (renderer.rs:380-382, :736-754) when it is not premultiplied "over": a kernel argument of its own
 // behind RasterParams, read by k_raster_blend only (api.hip blend_form builds it; a larger RasterParams changed the code of the existing kernels).
@@ -125,6 +128,7 @@ struct ImageArgs {
 
 constexpr uint32_t kTessStatusWord = 126; // ... the status word of the optimistic tessellation a pass drew (api.hip: crh_scene::optimistic), copied in by the host side
 constexpr uint32_t kExtraTurnsWord = 76; // of RasterParams::overflow: behind the 8 flag words and the 64 cursors of the pair sub-streams
+constexpr uint32_t kReplayFallbackWord = 77; // ... and behind it: batches of k_bin_flat whose pass 3 walked again because pass 1's hits did not fit their table (cleared with the flag words)
 struct RasterParams {
     uint32_t width, height, tiles_x, tiles_y, n_tiles; // 16x16-pixel tiles
     uint32_t winding_mask;

@@ -7,8 +7,9 @@ os.environ["CRH_RASTER_DEBUG"] = "65536"
 os.environ["CRH_EDGE_PASS"] = "1"
 from contrast_renderer_amd import renderer as R, scenes
 w = sys.argv[1] if len(sys.argv) > 1 else "cubic"
-sc = {"cubic": lambda: scenes.scene_cubic_fill(10000), "glyphs": lambda: scenes.scene_glyphs(50000, (2048, 2048)), "dashed": lambda: scenes.scene_dashed_strokes(2000)}[w]()
-size = {"cubic": 4096, "glyphs": 2048, "dashed": 4096}[w]
+sc = {"cubic": lambda: scenes.scene_cubic_fill(10000), "glyphs": lambda: scenes.scene_glyphs(50000, (2048, 2048)), "dashed": lambda: scenes.scene_dashed_strokes(2000),
+      "s100k": lambda: scenes.scene_cubic_fill(100000, (8192, 8192), config_index=2)}[w]()
+size = {"cubic": 4096, "glyphs": 2048, "dashed": 4096, "s100k": 8192}[w]
 r = R.Renderer(R.Configuration(4 if w == "dashed" else 1, 4, 4), 0)
 scene = R.Scene(r, sc["batch"]); scene.check(); scene.set_instances(sc["transforms"], sc["colors"])
 frame = R.Frame(r, size, size)
@@ -25,6 +26,7 @@ if not os.environ.get("CRH_BIN_ITEMWISE"):  # k_bin_flat: wavefront 0 of every w
     for name, v in zip(names, vals):
         print(f"{name:40s} {v / groups:10.0f} ticks per workgroup ({100.0 * v / max(1, sum(vals)):4.1f} %)")
     print(f"total {sum(vals) / groups:.0f} ticks per workgroup of {ipg} items, {groups} workgroups")
+    print(f"batches whose pass 3 walked again instead of replaying pass 1's hits: {out[77]}")
     longest, total, n_wg = out[120] | (out[121] << 32), out[122] | (out[123] << 32), out[124]
     if n_wg:
         print(f"workgroup lifetimes: {n_wg} workgroups, mean {total / n_wg:.0f} ticks, longest {longest} ticks = {longest * n_wg / max(1, total):.2f} x the mean")
@@ -35,6 +37,14 @@ if not os.environ.get("CRH_BIN_ITEMWISE"):  # k_bin_flat: wavefront 0 of every w
         r.lib.crh_debug_frame_bin_dump.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
         assert r.lib.crh_debug_frame_bin_dump(frame.handle, buf, words) == 0
         rec = np.frombuffer(buf, dtype=np.uint32)[2 * (n + 1):].reshape(-1, 8)[:n_wg].astype(np.float64)
+        # (word 1: turns | the most hits — entries of pass 3 — one wavefront found in a batch << 8 | the most a whole batch found << 20)
+        packed = rec[:, 1].astype(np.int64)
+        wave_hits, batch_hits = (packed >> 8) & 4095, (packed >> 20) & 4095
+        rec[:, 1] = packed & 255
+        for nm, v in (("hits per wavefront", wave_hits), ("hits per batch", batch_hits)):
+            print(f"{nm}: mean {v.mean():.0f}, " + ", ".join(f"p{q} {np.percentile(v, q):.0f}" for q in (50, 90, 99)) + f", max {v.max()}")
+        for cap in (128, 192, 256, 320, 400, 512):
+            print(f"  batches with a wavefront above {cap} hits: {(wave_hits > cap).sum()}; with more than {2 * cap} hits in all: {(batch_hits > 2 * cap).sum()} of {len(rec)}")
         names = ["life", "turns", "items", "tris", "edges", "cells", "edge rows", "longest tri walk"]
         print("per workgroup: " + ", ".join(f"{nm} mean {rec[:, k].mean():.0f} max {rec[:, k].max():.0f}" for k, nm in enumerate(names)))
         A = np.concatenate([np.ones((len(rec), 1)), rec[:, 1:]], axis=1)
