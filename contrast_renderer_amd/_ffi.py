@@ -240,6 +240,11 @@ class LightingC(C.Structure):  # crh_lighting
                 ("spot_exponent", C.c_float), ("cone_angle", C.c_float)]
 
 
+class TurbulenceC(C.Structure):  # crh_turbulence
+    _fields_ = [("kind", C.c_uint32), ("octaves", C.c_uint32), ("seed", C.c_int32), ("stitch", C.c_uint32), ("opaque", C.c_uint32), ("base_frequency", C.c_float * 2),
+                ("offset", C.c_float * 2)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -334,6 +339,10 @@ def load_library():
         "crh_lighting_validate": (C.c_int, [C.POINTER(LightingC)]),
         "crh_lighting_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.POINTER(LightingC), V]),
         "crh_image_lighting": (C.c_int, [V, C.POINTER(LightingC), C.POINTER(V)]),
+        "crh_turbulence_validate": (C.c_int, [C.POINTER(TurbulenceC)]),
+        "crh_turbulence_tables": (C.c_int, [C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double)]),
+        "crh_turbulence_texels": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(TurbulenceC), V]),
+        "crh_image_turbulence": (C.c_int, [V, C.c_uint32, C.c_uint32, C.POINTER(TurbulenceC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

@@ -24,6 +24,7 @@
 #include "morphology.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
+#include "turbulence.hpp"
 
 using namespace crh;
 
@@ -3472,6 +3473,86 @@ crh_status crh_image_lighting(const crh_image* src, const crh_lighting* how, crh
     launch_image_lighting(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, f, how->op, how->light, how->edge, static_cast<uint32_t*>(image->pixels->p), r->stream);
     bool ok = hip_ok(hipGetLastError(), "k_image_lighting");
     ok = hip_ok(r->sync(), "sync(lighting)") && ok;
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
+namespace {
+static_assert(CRH_TURBULENCE_FRACTAL_NOISE == kTurbulenceFractalNoise && CRH_TURBULENCE_TURBULENCE == kTurbulenceTurbulence && CRH_MAX_TURBULENCE_OCTAVES == kTurbulenceMaxOctaves,
+              "turbulence.hpp's kinds and limit are the header's");
+crh_status turbulence_error(const char* what) {
+    g_error = std::string("crh_turbulence_validate: ") + what;
+    return CRH_ERR_INVALID_ARGUMENT;
+}
+// the one check of the fields, for the four entry points
+crh_status turbulence_fields(const crh_turbulence* how) {
+    if (!how) return turbulence_error("a null argument");
+    if (how->kind > CRH_TURBULENCE_TURBULENCE) return turbulence_error("kind is above CRH_TURBULENCE_TURBULENCE");
+    if (how->stitch > 1u) return turbulence_error("stitch is neither 0 nor 1");
+    if (how->opaque > 1u) return turbulence_error("opaque is neither 0 nor 1");
+    if (how->octaves > CRH_MAX_TURBULENCE_OCTAVES) return turbulence_error("octaves is above CRH_MAX_TURBULENCE_OCTAVES");
+    for (int c = 0; c < 2; ++c)
+        if (!std::isfinite(how->base_frequency[c]) || !std::isfinite(how->offset[c])) {
+            g_error = "crh_turbulence_validate: a frequency or an offset is not finite";
+            return CRH_ERR_NON_FINITE;
+        }
+    for (int c = 0; c < 2; ++c)
+        if (how->base_frequency[c] < 0.0f || how->base_frequency[c] > CRH_TURBULENCE_MAX_FREQUENCY) return turbulence_error("a base_frequency is outside [0, 4]");
+    for (int c = 0; c < 2; ++c)
+        if (std::fabs(how->offset[c]) > CRH_TURBULENCE_MAX_OFFSET) return turbulence_error("an offset is outside [-65536, 65536]");
+    return CRH_OK;
+}
+// validates a whole call and prepares it: the one way from the caller's floats to the rule's constants
+crh_status turbulence_constants(uint32_t width, uint32_t height, const crh_turbulence* how, TurbulenceConstants* f) {
+    const crh_status st = turbulence_fields(how);
+    if (st != CRH_OK) return st;
+    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return turbulence_error("width and height lie in [1, 16384]");
+    turbulence_prepare(width, height, how->octaves, how->stitch != 0u, how->base_frequency, how->offset, f);
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_turbulence_validate(const crh_turbulence* how) { return turbulence_fields(how); }
+crh_status crh_turbulence_tables(int32_t seed, uint8_t lattice[256], double gradient[4 * 256 * 2]) {
+    if (!lattice || !gradient) return turbulence_error("a null argument");
+    TurbulenceTables t;
+    turbulence_make_tables(seed, &t);
+    std::memcpy(lattice, t.lattice, sizeof(t.lattice));
+    std::memcpy(gradient, t.gradient, sizeof(t.gradient));
+    return CRH_OK;
+}
+crh_status crh_turbulence_texels(uint32_t width, uint32_t height, const crh_turbulence* how, void* out_rgba8) {
+    if (!out_rgba8) return turbulence_error("a null argument");
+    TurbulenceConstants f;
+    const crh_status st = turbulence_constants(width, height, how, &f);
+    if (st != CRH_OK) return st;
+    TurbulenceTables t;
+    turbulence_make_tables(how->seed, &t);
+    turbulence_run(t, f, how->kind, how->opaque != 0u, width, height, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_turbulence(crh_renderer* r, uint32_t width, uint32_t height, const crh_turbulence* how, crh_image** out) {
+    if (!r || !out) return turbulence_error("a null argument");
+    TurbulenceConstants f;
+    crh_status st = turbulence_constants(width, height, how, &f);
+    if (st != CRH_OK) return st;
+    TurbulenceTables t;
+    turbulence_make_tables(how->seed, &t);
+    HIP_TRY(hipSetDevice(r->device));
+    crh_image* image = nullptr;
+    st = new_image(r, width, height, &image);
+    if (st != CRH_OK) return st;
+    void* tables_dev = nullptr;
+    bool ok = hip_ok(hipMalloc(&tables_dev, sizeof(t)), "hipMalloc(turbulence tables)") &&
+              hip_ok(hipMemcpyAsync(tables_dev, &t, sizeof(t), hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(turbulence tables)");
+    if (ok) {
+        launch_image_turbulence(static_cast<const TurbulenceTables*>(tables_dev), width, height, f, how->kind, how->opaque != 0u, static_cast<uint32_t*>(image->pixels->p), r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_turbulence");
+    }
+    ok = hip_ok(r->sync(), "sync(turbulence)") && ok; // (also behind a failure: `t` is read by the copy until the stream has drained)
+    if (tables_dev) (void)hipFree(tables_dev);
     if (!ok) {
         delete image;
         return CRH_ERR_HIP;

@@ -7,6 +7,7 @@
 // at a cost per texel that does not grow linearly with the radius.
 // crh_image_convolve: k_image_convolve puts an image through a kernel matrix with the rule of convolve.hpp, a 2-D stencil over a tile and its halo in LDS.
 // crh_image_lighting: k_image_lighting lights the alpha channel as a height field with the rule of lighting.hpp, binary64 arithmetic on a 3 x 3 stencil.
+// crh_image_turbulence: k_image_turbulence makes a noise image with the rule of turbulence.hpp, binary64 arithmetic on gradients gathered from LDS.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
+#include "turbulence.hpp"
 
 namespace crh {
 namespace {
@@ -623,6 +625,90 @@ void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const Li
         else CRH_LIGHTING_LAUNCH(kLightingSpecular, kLightSpot);
     }
 #undef CRH_LIGHTING_LAUNCH
+}
+
+namespace {
+constexpr int kTurbulenceTileW = 64; // output columns per workgroup, one per lane of a wave
+constexpr int kTurbulenceWaves = 4;  // waves per workgroup
+#ifndef CRH_TURBULENCE_ROWS
+#define CRH_TURBULENCE_ROWS 4 // (a build with -DCRH_TURBULENCE_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the row blocking is measured)
+#endif
+constexpr int kTurbulenceRows = CRH_TURBULENCE_ROWS;                   // adjacent output rows per lane: one column half serves them all
+constexpr int kTurbulenceTileH = kTurbulenceWaves * kTurbulenceRows;   // 16 output rows per workgroup
+} // namespace
+
+// crh_image_turbulence: procedural noise, bound by binary64 arithmetic and LDS gathers. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the
+// workgroup produces the tile of 64 x 16 texels at (i0, j0). It first copies the call's tables into LDS: the gradients of the channels it
+// evaluates, 16 bytes per (channel, lattice value) — 16 KB, or 12 KB when OPAQUE — and the 256 lattice bytes; lane t copies entry t of
+// every channel and (the first wave) word t of the lattice. Then lane l of wave v produces the four outputs of column l, tile rows
+// 4 v .. 4 v + 3. The octaves are the outer loop: per octave the lane computes its column's half of the cell once (floor, fractions,
+// s-curve, the wrap when STITCH, lat[bx0] and lat[bx1]) and then, for each of its rows, the row's half (the same function), the four
+// corner indices — once for all channels — and per channel four 16-byte gradients (ds_read_b128: consecutive lattice values lie in
+// consecutive bank quads, so only lanes of one 16-lane group whose corners differ by a multiple of 16 collide) and the 21 operations of
+// the interpolation. The sums of the rows stay in registers (rows x channels doubles). A lane outside the image computes like any other —
+// every LDS index is masked to 8 bits — and does not store. Periods, their reciprocals and the ratio of octave o are the kernel
+// arguments of octave 0 shifted or halved o times, which is exact. The specialisation without STITCH carries no wrap at all.
+template <uint32_t KIND, bool OPAQUE, bool STITCH>
+__global__ __launch_bounds__(kTurbulenceTileW* kTurbulenceWaves) void k_image_turbulence(const TurbulenceTables* __restrict__ tables, uint32_t w, uint32_t h, TurbulenceConstants f,
+                                                                                          uint32_t* __restrict__ out) {
+    constexpr int CH = OPAQUE ? 3 : 4;
+    __shared__ __attribute__((aligned(16))) double gradient[CH * 512];
+    __shared__ __attribute__((aligned(16))) uint8_t lattice[256];
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+        const uint32_t e = ((uint32_t)k * 256u + threadIdx.x) * 2u;
+        gradient[e] = tables->gradient[e], gradient[e + 1u] = tables->gradient[e + 1u];
+    }
+    if (wave == 0u) reinterpret_cast<uint32_t*>(lattice)[lane] = reinterpret_cast<const uint32_t*>(tables->lattice)[lane];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * (uint32_t)kTurbulenceTileW + lane;
+    const uint32_t j0 = blockIdx.y * (uint32_t)kTurbulenceTileH + wave * (uint32_t)kTurbulenceRows;
+    double vx = (f.ox + (double)i) * f.fx, vy[kTurbulenceRows];
+#pragma unroll
+    for (int b = 0; b < kTurbulenceRows; ++b) vy[b] = (f.oy + (double)(j0 + (uint32_t)b)) * f.fy;
+    TurbulenceSums<CH> sums[kTurbulenceRows] = {};
+    double inv_ratio = 1.0, inv_px = f.inv_px, inv_py = f.inv_py;
+    int32_t px = f.px, py = f.py;
+    for (uint32_t o = 0; o < f.octaves; ++o) {
+        const TurbulenceAxis x = turbulence_axis<STITCH>(vx, px, inv_px);
+        const uint32_t a0 = lattice[x.b0], a1 = lattice[x.b1];
+#pragma unroll
+        for (int b = 0; b < kTurbulenceRows; ++b) {
+            const TurbulenceAxis y = turbulence_axis<STITCH>(vy[b], py, inv_py);
+            turbulence_add<KIND, CH>(lattice, gradient, a0, a1, x, y, inv_ratio, &sums[b]);
+            vy[b] = vy[b] * 2.0;
+        }
+        vx = vx * 2.0;
+        inv_ratio = inv_ratio * 0.5, inv_px = inv_px * 0.5, inv_py = inv_py * 0.5;
+        px <<= 1, py <<= 1;
+    }
+    if (i < w) {
+#pragma unroll
+        for (int b = 0; b < kTurbulenceRows; ++b) {
+            const uint32_t j = j0 + (uint32_t)b;
+            if (j < h) out[(size_t)j * w + i] = turbulence_texel<KIND, CH>(sums[b]);
+        }
+    }
+}
+
+void launch_image_turbulence(const TurbulenceTables* tables, uint32_t w, uint32_t h, const TurbulenceConstants& f, uint32_t kind, bool opaque, uint32_t* out, hipStream_t stream) {
+    const dim3 grid((w + (uint32_t)kTurbulenceTileW - 1u) / (uint32_t)kTurbulenceTileW, (h + (uint32_t)kTurbulenceTileH - 1u) / (uint32_t)kTurbulenceTileH); // <= 256 x 1024
+    const dim3 block(kTurbulenceTileW * kTurbulenceWaves);
+    const bool stitch = f.px != 0 || f.py != 0;
+#define CRH_TURBULENCE_LAUNCH(KIND, OPAQUE)                                                                                                 \
+    do {                                                                                                                                    \
+        if (stitch) hipLaunchKernelGGL((k_image_turbulence<KIND, OPAQUE, true>), grid, block, 0, stream, tables, w, h, f, out);             \
+        else hipLaunchKernelGGL((k_image_turbulence<KIND, OPAQUE, false>), grid, block, 0, stream, tables, w, h, f, out);                  \
+    } while (0)
+    if (kind == kTurbulenceFractalNoise) {
+        if (opaque) CRH_TURBULENCE_LAUNCH(kTurbulenceFractalNoise, true);
+        else CRH_TURBULENCE_LAUNCH(kTurbulenceFractalNoise, false);
+    } else {
+        if (opaque) CRH_TURBULENCE_LAUNCH(kTurbulenceTurbulence, true);
+        else CRH_TURBULENCE_LAUNCH(kTurbulenceTurbulence, false);
+    }
+#undef CRH_TURBULENCE_LAUNCH
 }
 
 } // namespace crh

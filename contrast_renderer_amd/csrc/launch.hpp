@@ -61,6 +61,10 @@ void launch_image_convolve(const uint32_t* src, uint32_t w, uint32_t h, const Co
 // image_filter.hip: crh_image_lighting's kernel (lighting.hpp holds the rule; op < 2, light < 3, edge < 4). src and out: h rows of w texels.
 struct LightingConstants;
 void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const LightingConstants& f, uint32_t op, uint32_t light, uint32_t edge, uint32_t* out, hipStream_t stream);
+// image_filter.hip: crh_image_turbulence's kernel (turbulence.hpp holds the rule; kind < 2). tables: the seeded tables on the device; out: h rows of w texels.
+struct TurbulenceTables;
+struct TurbulenceConstants;
+void launch_image_turbulence(const TurbulenceTables* tables, uint32_t w, uint32_t h, const TurbulenceConstants& f, uint32_t kind, bool opaque, uint32_t* out, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream); // zeroes n_words 32-bit words with single-wave workgroups (the clear in front of both passes' binning kernels)

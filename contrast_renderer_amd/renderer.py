@@ -703,6 +703,44 @@ def lighting_texels(pixels, light, op=LightingOp.Diffuse, surface_scale=1.0, con
     return out
 
 
+class TurbulenceKind(IntEnum):  # crh_turbulence_kind
+    FractalNoise = 0
+    Turbulence = 1
+
+
+MAX_TURBULENCE_OCTAVES = 12  # CRH_MAX_TURBULENCE_OCTAVES
+
+
+def _turbulence_arguments(base_frequency, octaves, seed, kind, stitch, opaque, offset):
+    """-> TurbulenceC; a scalar base_frequency serves both axes"""
+    fx, fy = (base_frequency, base_frequency) if np.isscalar(base_frequency) else base_frequency
+    how = _ffi.TurbulenceC()
+    how.kind, how.octaves, how.seed, how.stitch, how.opaque = int(kind), int(octaves), int(seed), int(bool(stitch)), int(bool(opaque))
+    how.base_frequency = (C.c_float * 2)(float(fx), float(fy))
+    how.offset = (C.c_float * 2)(float(offset[0]), float(offset[1]))
+    return how
+
+
+def turbulence_texels(width, height, base_frequency, octaves=1, seed=0, kind=TurbulenceKind.Turbulence, stitch=False, opaque=False, offset=(0, 0)):
+    """crh_turbulence_texels (host only): the rule of Image.turbulence -> a (height, width, 4) uint8 array (include/contrast_hip.h
+    crh_image_turbulence states the rule)."""
+    how = _turbulence_arguments(base_frequency, octaves, seed, kind, stitch, opaque, offset)
+    width, height = int(width), int(height)
+    if not (0 < width <= 16384 and 0 < height <= 16384):
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"turbulence_texels takes a width and a height in [1, 16384], not {width} x {height}")
+    out = np.empty((height, width, 4), dtype=np.uint8)
+    check(_ffi.load_library().crh_turbulence_texels(width, height, C.byref(how), out.ctypes.data))
+    return out
+
+
+def turbulence_tables(seed):
+    """crh_turbulence_tables (host only) -> (lattice, gradient): the permutation of 0..255 as 256 uint8 and the unit gradients as a
+    (4, 256, 2) float64 array, gradient[channel, lattice value] = (x, y), that `seed` gives."""
+    lattice, gradient = np.empty(256, dtype=np.uint8), np.empty((4, 256, 2), dtype=np.float64)
+    check(_ffi.load_library().crh_turbulence_tables(int(seed), lattice.ctypes.data_as(C.POINTER(C.c_uint8)), gradient.ctypes.data_as(C.POINTER(C.c_double))))
+    return lattice, gradient
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -734,6 +772,23 @@ class Image:
         w, h = C.c_uint32(), C.c_uint32()
         check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
         image.width, image.height = int(w.value), int(h.value)
+        return image
+
+    @classmethod
+    def turbulence(cls, renderer: Renderer, width, height, base_frequency, octaves=1, seed=0, kind=TurbulenceKind.Turbulence, stitch=False, opaque=False, offset=(0, 0)):
+        """crh_image_turbulence -> a new Image of one level, width x height, origin (0, 0): procedural noise made on the device (SVG
+        feTurbulence), complete when this returns (a synchronous call). `base_frequency` = lattice cells per texel, a scalar or (x, y), each
+        in [0, 4]; `octaves` in [0, MAX_TURBULENCE_OCTAVES], each of twice the frequency and half the weight; TurbulenceKind.FractalNoise is
+        signed noise around the middle grey, TurbulenceKind.Turbulence the sum of absolute values; `stitch` makes the image tile with
+        itself; `opaque` gives alpha 255 and three channels of noise instead of SVG's four; `offset` = the noise-space position of texel
+        (0, 0), so a large texture can be made in pieces. Binary64 arithmetic in a fixed order, so every byte is defined."""
+        how = _turbulence_arguments(base_frequency, octaves, seed, kind, stitch, opaque, offset)
+        image = cls.__new__(cls)
+        image.renderer, image.lib = renderer, renderer.lib
+        handle = C.c_void_p()
+        check(image.lib.crh_image_turbulence(renderer.handle, int(width), int(height), C.byref(how), C.byref(handle)))
+        image.handle = handle
+        image.width, image.height = int(width), int(height)
         return image
 
     def generate_mipmaps(self):

@@ -804,6 +804,75 @@ typedef struct crh_lighting {
 crh_status crh_lighting_validate(const crh_lighting* how); /* host only */
 crh_status crh_lighting_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_lighting* how, void* out_rgba8); /* host only */
 crh_status crh_image_lighting(const crh_image* src, const crh_lighting* how, crh_image** out);
+/* Turbulence: an image made of procedural noise on the device (SVG feTurbulence, Perlin's fractalNoise and turbulence) — paper grain,
+ * clouds, marble, wood, the bump map of rough metal under crh_image_lighting, a dissolve mask for CRH_COMPOSITE_DST_IN, film grain with
+ * CRH_BLEND_OVERLAY. The only image call that makes pixels instead of changing them. Integer tables in, one rounding to a code out, and
+ * the tests check every byte: all real arithmetic below is IEEE binary64 in exactly the written order and parenthesisation, with only
+ * + - * /, sqrt and crh_floor_d, never contracted, every float field widened to double first; ceil(x) = -floor(-x).
+ *   seed         in 64-bit integers: s = seed; s <= 0 gives s = (|s| mod 2147483646) + 1; s > 2147483646 gives s = 2147483646.
+ *   random step  rnd(s) = 16807 * (s mod 127773) - 2836 * (s div 127773), plus 2147483647 when that is <= 0. Every draw below first does
+ *                s = rnd(s) and then uses s.
+ *   gradients    for k = 0..3 (r, g, b, a) outermost and i = 0..255 inside, two draws: gx = (double)((s mod 512) - 256) / 256.0, then gy
+ *                the same way; n = sqrt(gx gx + gy gy); G[k][i] = (gx / n, gy / n), and (0, 0) when n == 0 (seed 346: k = 1, i = 164).
+ *   lattice      after all gradients: lat[i] = i for 0..255; then for i = 255 down to 1: a draw, j = s mod 256, swap lat[i] and lat[j].
+ *   frequency    per axis, n = width or height, f = the widened base frequency. stitch == 0 or f == 0: the frequency is f and the period
+ *                P = 0. Otherwise lo = floor(n f) / n, hi = ceil(n f) / n, f' = (f / lo < hi / f) ? lo : hi (lo == 0: the quotient is
+ *                +inf, so hi), P = (int)floor(n f' + 0.5) >= 1. Octave o uses the period P << o.
+ *   point        texel (column i, row j): vx = ((double)offset[0] + (double)i) * fx, vy likewise with j and fy; after each octave
+ *                vx = vx * 2.0 and vy = vy * 2.0.
+ *   noise(k, vx, vy, Px, Py)
+ *                flx = floor(vx), ix = (int)flx, rx0 = vx - flx, rx1 = rx0 - 1.0; the y axis the same. wrap(i, P) = (P == 0 ? i : i mod P,
+ *                taken non-negative) & 255, applied to ix, ix + 1, iy and iy + 1 separately: bx0, bx1, by0, by1. a0 = lat[bx0],
+ *                a1 = lat[bx1]; b00 = lat[(a0 + by0) & 255], b10 = lat[(a1 + by0) & 255], b01 = lat[(a0 + by1) & 255],
+ *                b11 = lat[(a1 + by1) & 255]. sx = (rx0 rx0) * (3.0 - (2.0 rx0)), sy likewise. With q = G[k][b]:
+ *                u = (rx0 q00.x) + (ry0 q00.y), v = (rx1 q10.x) + (ry0 q10.y), a = u + (sx * (v - u));
+ *                u = (rx0 q01.x) + (ry1 q01.y), v = (rx1 q11.x) + (ry1 q11.y), b = u + (sx * (v - u)); the noise is a + (sy * (b - a)).
+ *   sum          sum = 0, ratio = 1; per octave sum = sum + (N / ratio), N = the noise for FRACTAL_NOISE and its absolute value for
+ *                TURBULENCE; then ratio = ratio * 2.0.
+ *   code         t = (sum + 1.0) * 0.5 for FRACTAL_NOISE, t = sum for TURBULENCE; code = t >= 1 ? 255 : t > 0 ? (int)floor(t * 255.0 + 0.5) : 0.
+ *   texel        premultiplied, as every image here: A = opaque ? 255 : code_a (with opaque, channel 3 is not evaluated); each colour
+ *                byte is (code_c * A + 127) / 255 in integers; the alpha byte is A.
+ * With the validated ranges |vx| <= (65536 + 16384) * 4 * 2^11 < 2^31: lattice coordinates and periods fit 32 bits and crh_floor_d's
+ * precondition holds.
+ * Hence: rgb <= a in every texel; octaves == 0, or both frequencies 0, or integer-valued offsets with integer frequencies (every point
+ * is a lattice point) give a constant image — FRACTAL_NOISE (64, 64, 64, 128), with opaque (128, 128, 128, 255); TURBULENCE
+ * (0, 0, 0, 0), with opaque (0, 0, 0, 255); seeds 0 and 1 give the same image, seed -1 that of seed 2; window: with stitch == 0 an image
+ * of any size at offset (x + dx, y + dy) equals the window at (dx, dy) of the image at offset (x, y) for integer dx, dy and
+ * float-representable sums, so a large texture can be made in pieces; period: with stitch == 1, a power-of-two width and height and
+ * integer offsets, the image at offset (x + w, y + h) is byte-equal to the one at (x, y) (all products are then exact; without stitch it
+ * is not); base_frequency[1] does not enter when height == 1 and offset[1] makes vy an integer, and likewise for x.
+ * crh_turbulence_validate, crh_turbulence_tables (the seeded tables, gradient[(k * 256 + i) * 2 + c]) and crh_turbulence_texels (the rule
+ * on a whole image in host memory, width * height * 4 bytes in the order r g b a at any alignment, row 0 first) are host only: no
+ * renderer, no device.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out untouched: first a null
+ * argument, a kind above CRH_TURBULENCE_TURBULENCE, stitch or opaque above 1 and octaves above CRH_MAX_TURBULENCE_OCTAVES are
+ * CRH_ERR_INVALID_ARGUMENT; then a non-finite frequency or offset is CRH_ERR_NON_FINITE; then a frequency outside
+ * [0, CRH_TURBULENCE_MAX_FREQUENCY], an offset outside +-CRH_TURBULENCE_MAX_OFFSET and a size outside [1, 16384] are
+ * CRH_ERR_INVALID_ARGUMENT, each with a crh_last_error text "crh_turbulence_validate: ...".
+ * crh_image_turbulence gives a fresh image of the renderer with one level and origin (0, 0) (mipmaps, blur, composite, colour filter,
+ * morphology, convolution, lighting, image paints and crh_frame_load_image work on it), complete when the call returns: the tables are
+ * built on the host and uploaded once per call, and k_image_turbulence runs on the renderer's stream, specialised on (kind, opaque,
+ * stitched), the tables in LDS. A failed allocation or launch frees everything and returns CRH_ERR_HIP.
+ * Limits: lattice coordinates are taken with floor and stitching is a true modulo, so values differ from a browser's, which follows the
+ * SVG sample code's +4096 offset and its wrap bookkeeping — the statistics and the look are the same; the stitch tile is the image
+ * itself; the output is linear codes with no colour-space handling; the call is synchronous, like its siblings. */
+#define CRH_MAX_TURBULENCE_OCTAVES 12u
+#define CRH_TURBULENCE_MAX_FREQUENCY 4.0f
+#define CRH_TURBULENCE_MAX_OFFSET 65536.0f
+typedef enum crh_turbulence_kind { CRH_TURBULENCE_FRACTAL_NOISE = 0, CRH_TURBULENCE_TURBULENCE = 1 } crh_turbulence_kind;
+typedef struct crh_turbulence {
+    uint32_t kind;              /* crh_turbulence_kind */
+    uint32_t octaves;           /* 0 .. CRH_MAX_TURBULENCE_OCTAVES */
+    int32_t  seed;              /* any */
+    uint32_t stitch;            /* 0 or 1: the image tiles seamlessly with itself */
+    uint32_t opaque;            /* 0: alpha is the fourth noise channel (SVG); 1: alpha = 255, three channels of noise */
+    float base_frequency[2];    /* lattice cells per texel, x and y; each in [0, CRH_TURBULENCE_MAX_FREQUENCY] */
+    float offset[2];            /* noise-space position of texel (0, 0); each |.| <= CRH_TURBULENCE_MAX_OFFSET */
+} crh_turbulence;
+crh_status crh_turbulence_validate(const crh_turbulence* how);                                        /* host only */
+crh_status crh_turbulence_tables(int32_t seed, uint8_t lattice[256], double gradient[4 * 256 * 2]);   /* host only: gradient[(k*256 + i)*2 + c] */
+crh_status crh_turbulence_texels(uint32_t width, uint32_t height, const crh_turbulence* how, void* out_rgba8); /* host only */
+crh_status crh_image_turbulence(crh_renderer* renderer, uint32_t width, uint32_t height, const crh_turbulence* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

@@ -787,6 +787,43 @@ inline std::vector<uint8_t> lighting_texels(uint32_t width, uint32_t height, con
     check(crh_lighting_texels(width, height, texels.data(), &how, out.data()));
     return out;
 }
+// Turbulence (include/contrast_hip.h crh_image_turbulence states the rule): an image of procedural noise, SVG feTurbulence.
+enum class TurbulenceKind : uint32_t { FractalNoise = CRH_TURBULENCE_FRACTAL_NOISE, Turbulence = CRH_TURBULENCE_TURBULENCE };
+// The fields of crh_turbulence: lattice cells per texel on each axis, octaves of twice the frequency and half the weight each, the seed of
+// the tables, whether the image tiles with itself, whether alpha is 255 instead of a fourth channel of noise, and the noise-space position of texel (0, 0).
+struct Turbulence {
+    std::array<float, 2> base_frequency = {0.0f, 0.0f};
+    uint32_t octaves = 1;
+    int32_t seed = 0;
+    TurbulenceKind kind = TurbulenceKind::Turbulence;
+    bool stitch = false, opaque = false;
+    std::array<float, 2> offset = {0.0f, 0.0f};
+    crh_turbulence to_c() const {
+        crh_turbulence how = {};
+        how.kind = (uint32_t)kind, how.octaves = octaves, how.seed = seed, how.stitch = stitch ? 1u : 0u, how.opaque = opaque ? 1u : 0u;
+        for (int c = 0; c < 2; ++c) how.base_frequency[c] = base_frequency[(size_t)c], how.offset[c] = offset[(size_t)c];
+        return how;
+    }
+};
+// crh_turbulence_texels (host only): the rule -> the width * height * 4 bytes of the image
+inline std::vector<uint8_t> turbulence_texels(uint32_t width, uint32_t height, const Turbulence& turbulence) {
+    const crh_turbulence how = turbulence.to_c();
+    check(crh_turbulence_validate(&how));
+    if (width == 0u || height == 0u || width > 16384u || height > 16384u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    std::vector<uint8_t> out((size_t)width * height * 4u);
+    check(crh_turbulence_texels(width, height, &how, out.data()));
+    return out;
+}
+// crh_turbulence_tables (host only): the permutation of 0..255 and the unit gradients, gradient[(k * 256 + i) * 2 + c], that `seed` gives
+struct TurbulenceTables {
+    std::array<uint8_t, 256> lattice;
+    std::array<double, 4 * 256 * 2> gradient;
+};
+inline TurbulenceTables turbulence_tables(int32_t seed) {
+    TurbulenceTables tables;
+    check(crh_turbulence_tables(seed, tables.lattice.data(), tables.gradient.data()));
+    return tables;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -798,6 +835,15 @@ class Image {
         Image image;
         check(crh_image_create_from_frame(frame.raw(), &image.handle_));
         check(crh_image_size(image.handle_, &image.width_, &image.height_));
+        return image;
+    }
+    // crh_image_turbulence -> a new Image of one level, width x height, origin (0, 0): procedural noise made on the device; binary64 arithmetic
+    // in a fixed order, complete on return (a synchronous call).
+    static Image turbulence(const Renderer& renderer, uint32_t width, uint32_t height, const Turbulence& turbulence) {
+        const crh_turbulence how = turbulence.to_c();
+        Image image;
+        check(crh_image_turbulence(renderer.raw(), width, height, &how, &image.handle_));
+        image.width_ = width, image.height_ = height;
         return image;
     }
     ~Image() {

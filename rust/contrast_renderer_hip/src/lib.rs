@@ -1015,6 +1015,56 @@ pub fn lighting_texels(width: u32, height: u32, texels: &[u8], light: &Light, li
     status(unsafe { ffi::crh_lighting_texels(width, height, texels.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// `crh_turbulence_kind`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum TurbulenceKind {
+    FractalNoise = 0,
+    Turbulence = 1,
+}
+/// The fields of `crh_turbulence` (include/contrast_hip.h, `crh_image_turbulence`, states the rule): lattice cells per texel on each axis,
+/// octaves of twice the frequency and half the weight each, the seed of the tables, whether the image tiles with itself, whether alpha is
+/// 255 instead of a fourth channel of noise, and the noise-space position of texel (0, 0).
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct Turbulence {
+    pub base_frequency: [f32; 2],
+    pub octaves: u32,
+    pub seed: i32,
+    pub kind: TurbulenceKind,
+    pub stitch: bool,
+    pub opaque: bool,
+    pub offset: [f32; 2],
+}
+impl Default for Turbulence {
+    fn default() -> Turbulence {
+        Turbulence { base_frequency: [0.0; 2], octaves: 1, seed: 0, kind: TurbulenceKind::Turbulence, stitch: false, opaque: false, offset: [0.0; 2] }
+    }
+}
+impl Turbulence {
+    fn to_c(&self) -> ffi::crh_turbulence {
+        ffi::crh_turbulence { kind: self.kind as u32, octaves: self.octaves, seed: self.seed, stitch: self.stitch as u32, opaque: self.opaque as u32,
+                              base_frequency: self.base_frequency, offset: self.offset }
+    }
+}
+/// `crh_turbulence_validate` (host only): what `Image::turbulence` would refuse of the fields
+pub fn turbulence_validate(turbulence: &Turbulence) -> Result<(), Error> {
+    let how = turbulence.to_c();
+    status(unsafe { ffi::crh_turbulence_validate(&how) })
+}
+/// `crh_turbulence_tables` (host only) -> (the permutation of 0..255, the unit gradients as gradient[(k * 256 + i) * 2 + c]) that `seed` gives
+pub fn turbulence_tables(seed: i32) -> Result<(Vec<u8>, Vec<f64>), Error> {
+    let (mut lattice, mut gradient) = (vec![0u8; 256], vec![0f64; 4 * 256 * 2]);
+    status(unsafe { ffi::crh_turbulence_tables(seed, lattice.as_mut_ptr(), gradient.as_mut_ptr()) })?;
+    Ok((lattice, gradient))
+}
+/// `crh_turbulence_texels` (host only): the rule -> the width * height * 4 bytes of the image
+pub fn turbulence_texels(width: u32, height: u32, turbulence: &Turbulence) -> Result<Vec<u8>, Error> {
+    let how = turbulence.to_c();
+    status(unsafe { ffi::crh_turbulence_validate(&how) })?;
+    assert!(width >= 1 && height >= 1 && width <= 16384 && height <= 16384);
+    let mut out = vec![0u8; width as usize * height as usize * 4];
+    status(unsafe { ffi::crh_turbulence_texels(width, height, &how, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -1029,6 +1079,14 @@ impl Image {
         assert_eq!(rgba8.len(), width as usize * height as usize * 4);
         let mut raw = ptr::null_mut();
         status(unsafe { ffi::crh_image_create(renderer.raw, width, height, rgba8.as_ptr() as *const _, &mut raw) })?;
+        Ok(Image { raw, width, height, origin: (0, 0) })
+    }
+    /// `crh_image_turbulence` -> a new `Image` of one level, width x height, origin (0, 0): procedural noise made on the device (SVG
+    /// feTurbulence); binary64 arithmetic in a fixed order, complete on return (a synchronous call).
+    pub fn turbulence(renderer: &Renderer, width: u32, height: u32, turbulence: &Turbulence) -> Result<Image, Error> {
+        let how = turbulence.to_c();
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_turbulence(renderer.raw, width, height, &how, &mut raw) })?;
         Ok(Image { raw, width, height, origin: (0, 0) })
     }
     /// A snapshot of what the frame shows (an RGBA8 or RGBA8-attachment frame), copied on the device
