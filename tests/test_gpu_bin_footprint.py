@@ -92,14 +92,20 @@ def batch_limits(lib):
     return tuple(int(v) for v in limits)
 
 
-def item_costs(frame, n):
-    """Per item (triangles, edges, tile cells) as the frame's first pass counted them (RasterParams::item_cost)."""
+def cost_words(frame, n):
+    """The two cost words per item that the frame's latest verified pass left (RasterParams::item_cost), as crh_debug_flat_batches takes them."""
     from contrast_renderer_amd import _ffi
     lib = frame.lib
     lib.crh_debug_frame_bin_dump.restype = C.c_int
     lib.crh_debug_frame_bin_dump.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
     words = (C.c_uint32 * (2 * n))()
     _ffi.check(lib.crh_debug_frame_bin_dump(frame.handle, words, 2 * n))
+    return words
+
+
+def item_costs(frame, n):
+    """Per item (triangles, edges, tile cells) as the frame's first pass counted them (RasterParams::item_cost)."""
+    words = cost_words(frame, n)
     out = []
     for i in range(n):
         cells, w = int(words[2 * i]), int(words[2 * i + 1])

@@ -58,15 +58,20 @@ def cubic_scene():
     return scenes.scene_cubic_fill(200, (SIZE, SIZE), r_lo=8.0, r_hi=128.0)
 
 
-def fallbacks(frame):
-    """Batches of the frame's last pass that walked again (the flag words of its binning set; waits for the renderer)."""
+def flag_words(frame):
+    """The 128 flag and counter words of the binning set of the frame's last pass (waits for the renderer)."""
     from contrast_renderer_amd import _ffi
     lib = frame.lib
     lib.crh_debug_frame_words.restype = C.c_int
     lib.crh_debug_frame_words.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     out = (C.c_uint32 * 128)()
     _ffi.check(lib.crh_debug_frame_words(frame.handle, out))
-    return int(out[FALLBACK_WORD])
+    return [int(w) for w in out]
+
+
+def fallbacks(frame):
+    """Batches of the frame's last pass that walked again."""
+    return flag_words(frame)[FALLBACK_WORD]
 
 
 def draw(gpu, msaa=1, frames=FRAMES, rows=None, views=None, **env):  # noqa: F811
