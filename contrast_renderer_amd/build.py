@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ("tessellate.hip", "raster.hip", "bin_edges.hip", "raster_edges.hip", "image_filter.hip", "api.hip", "comm.hip", "text.cpp", "path.cpp")  # text.cpp / path.cpp: host-only (text.rs, path.rs:639-708)
+SOURCES = ("tessellate.hip", "raster.hip", "bin_edges.hip", "raster_edges.hip", "image_filter.hip", "api.hip", "image.hip", "comm.hip", "text.cpp", "path.cpp")  # text.cpp / path.cpp: host-only (text.rs, path.rs:639-708)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-bitwise-instead-of-logical"]
 # Per-file flags. raster_edges.hip and bin_edges.hip (one file when this was measured) without LLVM's SLP vectorizer (round 6): it packs pairs of independent f32 operations of the per-sample code into
 # v_pk_* instructions, whose operands are register PAIRS — lane-invariant values (sample positions, the tile's origin) end up duplicated in pairs that live

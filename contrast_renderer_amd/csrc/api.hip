@@ -1,6 +1,7 @@
 // csrc/api.hip — the C ABI of include/contrast_hip.h: host-side orchestration only (validation, HBM buffers, launches,
 // parity taps). Every arithmetic step of the hot path runs in the HIP kernels of tessellate.hip / raster.hip; there is no
-// CPU fallback here and nothing under oracle/ is referenced.
+// CPU fallback here and nothing under oracle/ is referenced. The host half of crh_image (create, mipmaps, the filters) is image.hip; what
+// of an image is about a frame or a paint table (crh_image_create_from_frame, crh_frame_load_image, crh_image_paint_validate) is here.
 // Streams of a renderer: raster (+ copies), tessellation (low priority), binning — one lane, or with CRH_BIN_LANES=2 two lanes that consecutive
 // passes take in turn (crh_renderer::bin_lane, render_impl's `steady`; DESIGN.md §4.6: measured slower, not the default) —, aux, upload.
 #include <hip/hip_runtime.h>
@@ -16,30 +17,15 @@
 #include <string>
 #include <vector>
 
-#include "color_filter.hpp"
-#include "composite.hpp"
-#include "convolve.hpp"
+#include "api_internal.hpp"
 #include "launch.hpp"
-#include "lighting.hpp"
-#include "morphology.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
-#include "turbulence.hpp"
 
 using namespace crh;
 
 namespace {
 thread_local std::string g_error;
-
-bool hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    g_error = std::string(what) + ": " + hipGetErrorString(e);
-    return false;
-}
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        if (!hip_ok((expr), #expr)) return CRH_ERR_HIP; \
-    } while (0)
 
 struct DevBuf {
     void* p = nullptr;
@@ -418,24 +404,6 @@ struct crh_frame {
 };
 
 constexpr int kTessBufs = 33; // buffers a tessellation run writes (crh_scene::tess_bufs)
-// The texels of a crh_image on the device, shared by the image and by every paint table that names it (crh_scene_set_paints_with_images):
-// freed with the last of them, so that no kernel of a pass reads an image its caller has destroyed.
-// Its mipmaps (crh_image_generate_mipmaps) are one more allocation of the same object — the level table at its head, the levels >= 1 behind it —
-// so a table keeps them alive exactly as it keeps level 0.
-struct ImagePixels {
-    void* p = nullptr;
-    void* chain = nullptr;          // [kImageLevelTableWords | level 1 | level 2 | ...] 32-bit words, or nullptr: one level
-    std::vector<ImageLevel> levels; // the table as the host wrote it (empty: one level)
-    ~ImagePixels() {
-        if (p) (void)hipFree(p);
-        if (chain) (void)hipFree(chain);
-    }
-};
-struct crh_image {
-    crh_renderer* renderer = nullptr;
-    uint32_t width = 0, height = 0;
-    std::shared_ptr<ImagePixels> pixels;
-};
 
 struct crh_scene {
     crh_renderer* renderer; // nullptr once the renderer has been destroyed (only crh_scene_destroy is valid then)
@@ -1760,7 +1728,9 @@ BlendForm blend_form(const crh_color_target_state& b) {
 } // namespace
 
 namespace crh {
-void set_last_error(const std::string& text) { g_error = text; } // used by csrc/text.cpp
+void set_last_error(const std::string& text) { g_error = text; } // for image.hip, comm.hip and text.cpp
+hipStream_t renderer_stream(crh_renderer* r) { return r->stream; }
+hipError_t renderer_sync(crh_renderer* r) { return r->sync(); }
 } // namespace crh
 
 extern "C" {
@@ -2905,30 +2875,6 @@ crh_status download_pixels(crh_frame* f, void* out, uint32_t format) {
 }
 } // namespace
 crh_status crh_frame_download(crh_frame* f, void* rgba8) { return download_pixels(f, rgba8, CRH_FORMAT_RGBA8); }
-namespace {
-constexpr uint32_t kMaxImageSize = 16384;
-crh_status new_image(crh_renderer* r, uint32_t width, uint32_t height, crh_image** out) {
-    auto pixels = std::make_shared<ImagePixels>();
-    HIP_TRY(hipMalloc(&pixels->p, (size_t)width * height * 4));
-    crh_image* image = new crh_image;
-    image->renderer = r, image->width = width, image->height = height, image->pixels = std::move(pixels);
-    *out = image;
-    return CRH_OK;
-}
-} // namespace
-crh_status crh_image_create(crh_renderer* r, uint32_t width, uint32_t height, const void* rgba8, crh_image** out) {
-    if (!r || !rgba8 || !out || width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return CRH_ERR_INVALID_ARGUMENT;
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    const crh_status st = new_image(r, width, height, &image);
-    if (st != CRH_OK) return st;
-    if (!hip_ok(hipMemcpy(image->pixels->p, rgba8, (size_t)width * height * 4, hipMemcpyHostToDevice), "hipMemcpy(image)")) { // (returns with the bytes copied)
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
 crh_status crh_image_create_from_frame(crh_frame* f, crh_image** out) {
     if (!f || !f->renderer || !out) return CRH_ERR_INVALID_ARGUMENT;
     if ((f->format != CRH_FORMAT_RGBA8 && f->format != CRH_FORMAT_RGBA8_ATTACHMENT) || f->slab_ty0 != 0u || f->slab_ty1 != 0xFFFFFFFFu) return CRH_ERR_UNSUPPORTED;
@@ -2955,612 +2901,6 @@ crh_status crh_image_create_from_frame(crh_frame* f, crh_image** out) {
     *out = image;
     return CRH_OK;
 }
-crh_status crh_image_size(const crh_image* image, uint32_t* width, uint32_t* height) {
-    if (!image || !width || !height) return CRH_ERR_INVALID_ARGUMENT;
-    *width = image->width, *height = image->height;
-    return CRH_OK;
-}
-crh_status crh_image_generate_mipmaps(crh_image* image) {
-    if (!image || !image->renderer) return CRH_ERR_INVALID_ARGUMENT;
-    ImagePixels& px = *image->pixels;
-    if (px.chain) return CRH_OK; // (the levels are what they were: level 0 never changes)
-    crh_renderer* r = image->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    std::vector<ImageLevel> levels;
-    uint32_t w = image->width, h = image->height, words = kImageLevelTableWords;
-    for (;;) {
-        ImageLevel l = {};
-        l.offset = levels.empty() ? 0u : words, l.width = w, l.height = h;
-        l.sx = (float)w / (float)image->width, l.sy = (float)h / (float)image->height;
-        if (!levels.empty()) words += w * h; // (< 2^27 + 2^25 ...: the levels >= 1 of a 16384^2 image are a third of its 2^28 texels)
-        levels.push_back(l);
-        if (w == 1u && h == 1u) break;
-        w = std::max(1u, w >> 1), h = std::max(1u, h >> 1);
-    }
-    void* chain = nullptr;
-    HIP_TRY(hipMalloc(&chain, (size_t)words * 4));
-    bool ok = hip_ok(hipMemsetAsync(chain, 0, (size_t)kImageLevelTableWords * 4, r->stream), "hipMemsetAsync(levels)") &&
-              hip_ok(hipMemcpyAsync(chain, levels.data(), levels.size() * sizeof(ImageLevel), hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(levels)");
-    for (size_t l = 1; ok && l < levels.size(); ++l) {
-        const uint32_t* src = l == 1 ? static_cast<const uint32_t*>(px.p) : static_cast<const uint32_t*>(chain) + levels[l - 1].offset;
-        launch_image_downsample(src, levels[l - 1].width, levels[l - 1].height, static_cast<uint32_t*>(chain) + levels[l].offset, levels[l].width, levels[l].height, r->stream);
-        ok = hip_ok(hipGetLastError(), "k_image_downsample");
-    }
-    ok = hip_ok(r->sync(), "sync(mipmaps)") && ok; // (also behind a failed launch: `levels` is read by the copy above until the stream has drained)
-    if (!ok) {
-        (void)hipFree(chain);
-        return CRH_ERR_HIP;
-    }
-    px.chain = chain, px.levels = std::move(levels);
-    return CRH_OK;
-}
-crh_status crh_image_level_count(const crh_image* image, uint32_t* count) {
-    if (!image || !count) return CRH_ERR_INVALID_ARGUMENT;
-    *count = image->pixels->chain ? (uint32_t)image->pixels->levels.size() : 1u;
-    return CRH_OK;
-}
-crh_status crh_image_download_level(const crh_image* image, uint32_t level, void* rgba8, uint32_t* width, uint32_t* height) {
-    if (!image || !image->renderer) return CRH_ERR_INVALID_ARGUMENT;
-    const ImagePixels& px = *image->pixels;
-    if (level >= (px.chain ? (uint32_t)px.levels.size() : 1u)) return CRH_ERR_INVALID_ARGUMENT;
-    const uint32_t w = level ? px.levels[level].width : image->width, h = level ? px.levels[level].height : image->height;
-    if (width) *width = w;
-    if (height) *height = h;
-    if (!rgba8) return CRH_OK; // the size alone
-    crh_renderer* r = image->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    const void* src = level ? static_cast<const void*>(static_cast<const uint32_t*>(px.chain) + px.levels[level].offset) : px.p;
-    HIP_TRY(hipMemcpyAsync(rgba8, src, (size_t)w * h * 4, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r->sync());
-    return CRH_OK;
-}
-namespace {
-static_assert(CRH_MAX_BLUR_RADIUS == kBlurMaxRadius, "k_image_blur_h's apron is the largest radius");
-crh_status blur_error(const char* what) {
-    g_error = std::string("crh_blur_taps: ") + what;
-    return CRH_ERR_INVALID_ARGUMENT;
-}
-// The tap rule of include/contrast_hip.h (crh_image_blur), in double: q[0 .. R] of one axis, summing to exactly 65536 over the 2 R + 1 positions.
-crh_status blur_taps(float sigma, std::vector<uint32_t>& q) {
-    if (!std::isfinite(sigma)) return CRH_ERR_NON_FINITE;
-    if (sigma < 0.0f) return blur_error("sigma is negative");
-    if (sigma > CRH_MAX_BLUR_SIGMA) return blur_error("sigma exceeds CRH_MAX_BLUR_SIGMA");
-    const double s = (double)sigma;
-    const uint32_t R = (uint32_t)std::ceil(3.0 * s);
-    q.assign(R + 1u, 0u);
-    if (R == 0u) {
-        q[0] = 65536u;
-        return CRH_OK;
-    }
-    std::vector<double> w(R + 1u);
-    for (uint32_t k = 0; k <= R; ++k) w[k] = std::exp(-(double)(k * k) / (2.0 * s * s));
-    double S = w[0];
-    for (uint32_t k = 1; k <= R; ++k) S += 2.0 * w[k];
-    int64_t total = 0;
-    for (uint32_t k = 0; k <= R; ++k) {
-        q[k] = (uint32_t)std::floor(w[k] / S * 65536.0 + 0.5);
-        total += k == 0u ? (int64_t)q[k] : 2 * (int64_t)q[k];
-    }
-    // the rounding's deficit d goes to the taps next to the centre in pairs, its odd unit to the centre (|d| / 2 <= R: |d| <= 27 over (0, 64])
-    const int64_t d = 65536 - total, g = d < 0 ? -1 : 1, m = std::min<int64_t>((d < 0 ? -d : d) / 2, (int64_t)R);
-    for (int64_t k = 1; k <= m; ++k) q[k] = (uint32_t)((int64_t)q[k] + g);
-    q[0] = (uint32_t)((int64_t)q[0] + d - 2 * g * m);
-    return CRH_OK;
-}
-} // namespace
-crh_status crh_blur_taps(float sigma, uint32_t* taps, uint32_t capacity, uint32_t* radius) {
-    std::vector<uint32_t> q;
-    const crh_status st = blur_taps(sigma, q);
-    if (st != CRH_OK) return st;
-    if (taps) {
-        if (capacity < (uint32_t)q.size()) return blur_error("capacity is below radius + 1");
-        std::copy(q.begin(), q.end(), taps);
-    }
-    if (radius) *radius = (uint32_t)q.size() - 1u;
-    return CRH_OK;
-}
-crh_status crh_image_blur(const crh_image* src, float sigma_x, float sigma_y, uint32_t edge, crh_image** out) {
-    if (!src || !src->renderer || !out || edge > CRH_BLUR_EDGE_REFLECT) return CRH_ERR_INVALID_ARGUMENT;
-    std::vector<uint32_t> qx, qy;
-    crh_status st = blur_taps(sigma_x, qx);
-    if (st == CRH_OK) st = blur_taps(sigma_y, qy);
-    if (st != CRH_OK) return st;
-    const uint32_t rx = (uint32_t)qx.size() - 1u, ry = (uint32_t)qy.size() - 1u;
-    const bool grows = edge == CRH_BLUR_EDGE_TRANSPARENT;
-    const uint32_t out_w = src->width + (grows ? 2u * rx : 0u), out_h = src->height + (grows ? 2u * ry : 0u);
-    if (out_w > kMaxImageSize || out_h > kMaxImageSize) {
-        g_error = "crh_image_blur: a side of the grown result exceeds 16384";
-        return CRH_ERR_UNSUPPORTED;
-    }
-    // The kernels take 16-bit taps two to a word (v_dot2_u32_u16). Only q[0] = 65536 does not fit, and then every other tap is 0: that axis is the
-    // identity, which the kernels do with radius 0 (the result still grows by the axis's radius under TRANSPARENT).
-    const uint32_t kx = qx[0] == 65536u ? 0u : rx, ky = qy[0] == 65536u ? 0u : ry;
-    // one upload, at the head of the intermediate's allocation: [q_x[0] | q_x[2 p + 1] | q_x[2 p + 2] << 16 ...] for k_image_blur_h, then, unless
-    // the vertical axis is the identity, F[n] | F[n - 1] << 16 over F = q_y[|d|], d = -ky .. ky, between kBlurTapPad zeros on either side
-    std::vector<uint32_t> words(1u + (kx + 1u) / 2u, 0u);
-    words[0] = qx[0];
-    for (uint32_t k = 1; k <= kx; ++k) words[(k + 1u) / 2u] |= qx[k] << (k % 2u ? 0 : 16);
-    const size_t vertical = words.size();
-    if (qy[0] != 65536u) {
-        std::vector<uint32_t> F(2u * ky + 1u + 2u * kBlurTapPad, 0u);
-        for (uint32_t k = 0; k <= ky; ++k) F[kBlurTapPad + ky - k] = F[kBlurTapPad + ky + k] = qy[k];
-        for (size_t n = 0; n < F.size(); ++n) words.push_back(F[n] | (n ? F[n - 1] << 16 : 0u));
-    }
-    const size_t taps_bytes = (words.size() * 4 + 255) / 256 * 256; // (the intermediate behind them stays 256-byte aligned)
-    crh_renderer* r = src->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    st = new_image(r, out_w, out_h, &image);
-    if (st != CRH_OK) return st;
-    void* scratch = nullptr; // [the taps | the intermediate: four 16-bit values per texel, the source's rows at the result's width]
-    bool ok = hip_ok(hipMalloc(&scratch, taps_bytes + (size_t)out_w * src->height * 8), "hipMalloc(blur intermediate)") &&
-              hip_ok(hipMemcpyAsync(scratch, words.data(), words.size() * 4, hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(blur taps)");
-    const uint32_t* taps_dev = static_cast<const uint32_t*>(scratch);
-    void* tmp = static_cast<char*>(scratch) + taps_bytes;
-    if (ok) {
-        launch_image_blur_h(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, tmp, out_w, taps_dev, kx, grows ? rx : 0u, edge, r->stream);
-        ok = hip_ok(hipGetLastError(), "k_image_blur_h");
-    }
-    if (ok) {
-        launch_image_blur_v(tmp, src->height, static_cast<uint32_t*>(image->pixels->p), out_w, out_h, qy[0] != 65536u ? taps_dev + vertical : nullptr, ky, grows ? ry : 0u, edge, r->stream);
-        ok = hip_ok(hipGetLastError(), "k_image_blur_v");
-    }
-    ok = hip_ok(r->sync(), "sync(blur)") && ok; // (also behind a failure: `words` is read by the copy until the stream has drained)
-    if (scratch) (void)hipFree(scratch);
-    if (!ok) {
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
-namespace {
-static_assert(CRH_COMPOSITE_PLUS + 1 == kCompositeOps && CRH_BLEND_EXCLUSION + 1 == kBlendModes, "composite.hpp's table and modes are the header's");
-static_assert(CRH_BLEND_NORMAL == kBlendNormal && CRH_BLEND_MULTIPLY == kBlendMultiply && CRH_BLEND_SCREEN == kBlendScreen && CRH_BLEND_OVERLAY == kBlendOverlay && CRH_BLEND_DARKEN == kBlendDarken &&
-                  CRH_BLEND_LIGHTEN == kBlendLighten && CRH_BLEND_HARD_LIGHT == kBlendHardLight && CRH_BLEND_DIFFERENCE == kBlendDifference && CRH_BLEND_EXCLUSION == kBlendExclusion,
-              "composite.hpp's modes are the header's");
-crh_status composite_error(const char* what) {
-    g_error = std::string("crh_composite_validate: ") + what;
-    return CRH_ERR_INVALID_ARGUMENT;
-}
-uint32_t opacity_code(float opacity) { return (uint32_t)std::floor((double)opacity * 255.0 + 0.5); }
-} // namespace
-crh_status crh_composite_validate(const crh_composite* how) {
-    if (!how) return CRH_ERR_INVALID_ARGUMENT;
-    if (how->op > CRH_COMPOSITE_PLUS) return composite_error("op is above CRH_COMPOSITE_PLUS");
-    if (how->mode > CRH_BLEND_EXCLUSION) return composite_error("mode is above CRH_BLEND_EXCLUSION");
-    if (!std::isfinite(how->opacity)) return CRH_ERR_NON_FINITE;
-    if (how->opacity < 0.0f || how->opacity > 1.0f) return composite_error("opacity is outside [0, 1]");
-    return CRH_OK;
-}
-crh_status crh_composite_texels(const crh_composite* how, const void* source_rgba8, const void* backdrop_rgba8, uint64_t n, void* out_rgba8) {
-    const crh_status st = crh_composite_validate(how);
-    if (st != CRH_OK) return st;
-    if (n == 0u) return CRH_OK;
-    if (!source_rgba8 || !backdrop_rgba8 || !out_rgba8) return CRH_ERR_INVALID_ARGUMENT;
-    const uint8_t* source = static_cast<const uint8_t*>(source_rgba8);
-    const uint8_t* backdrop = static_cast<const uint8_t*>(backdrop_rgba8);
-    uint8_t* out = static_cast<uint8_t*>(out_rgba8);
-    const uint32_t o = opacity_code(how->opacity);
-    const CompositeFactors f = composite_factors(how->op);
-#define CRH_COMPOSITE_RUN(M) composite_run<M>(source, backdrop, n, o, f, out)
-    CRH_COMPOSITE_MODES(how->mode, CRH_COMPOSITE_RUN)
-#undef CRH_COMPOSITE_RUN
-    return CRH_OK;
-}
-crh_status crh_image_composite(const crh_image* backdrop, const crh_image* source, const crh_composite* how, crh_image** out) {
-    if (!backdrop || !backdrop->renderer || !source || !how || !out) return CRH_ERR_INVALID_ARGUMENT;
-    crh_status st = crh_composite_validate(how);
-    if (st != CRH_OK) return st;
-    if (source->renderer != backdrop->renderer) {
-        g_error = "crh_image_composite: the images belong to different renderers";
-        return CRH_ERR_INVALID_ARGUMENT;
-    }
-    crh_renderer* r = backdrop->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    st = new_image(r, backdrop->width, backdrop->height, &image);
-    if (st != CRH_OK) return st;
-    launch_image_composite(static_cast<const uint32_t*>(backdrop->pixels->p), backdrop->width, backdrop->height, static_cast<const uint32_t*>(source->pixels->p), source->width, source->height,
-                           how->x, how->y, opacity_code(how->opacity), how->mode, how->op, static_cast<uint32_t*>(image->pixels->p), r->stream);
-    bool ok = hip_ok(hipGetLastError(), "k_image_composite");
-    ok = hip_ok(r->sync(), "sync(composite)") && ok;
-    if (!ok) {
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
-namespace {
-static_assert(CRH_COLOR_MATRIX_MAX == kColorMatrixMax, "color_filter.hpp's bound is the header's");
-// validates and quantises: the one way from the caller's floats to the coefficients, for the host rule and the kernel alike
-crh_status color_filter_coefficients(const float* matrix, ColorFilterCoefficients* f) {
-    switch (color_filter_quantize(matrix, f)) {
-    case kColorFilterNonFinite: return CRH_ERR_NON_FINITE;
-    case kColorFilterTooLarge: g_error = "crh_color_filter_validate: a coefficient is outside [-CRH_COLOR_MATRIX_MAX, CRH_COLOR_MATRIX_MAX]"; return CRH_ERR_INVALID_ARGUMENT;
-    default: return CRH_OK;
-    }
-}
-} // namespace
-crh_status crh_color_filter_validate(const float* matrix, const uint8_t* tables) {
-    (void)tables; // (every byte is a legal entry)
-    ColorFilterCoefficients f;
-    return color_filter_coefficients(matrix, &f);
-}
-crh_status crh_color_filter_texels(const float* matrix, const uint8_t* tables, const void* rgba8, uint64_t n, void* out) {
-    ColorFilterCoefficients f;
-    const crh_status st = color_filter_coefficients(matrix, &f);
-    if (st != CRH_OK) return st;
-    if (n == 0u) return CRH_OK;
-    if (!rgba8 || !out) return CRH_ERR_INVALID_ARGUMENT;
-    if (tables) color_filter_run<true>(static_cast<const uint8_t*>(rgba8), n, f, tables, static_cast<uint8_t*>(out));
-    else color_filter_run<false>(static_cast<const uint8_t*>(rgba8), n, f, nullptr, static_cast<uint8_t*>(out));
-    return CRH_OK;
-}
-crh_status crh_image_color_filter(const crh_image* src, const float* matrix, const uint8_t* tables, crh_image** out) {
-    if (!src || !src->renderer || !out) return CRH_ERR_INVALID_ARGUMENT;
-    ColorFilterCoefficients f;
-    crh_status st = color_filter_coefficients(matrix, &f);
-    if (st != CRH_OK) return st;
-    crh_renderer* r = src->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    st = new_image(r, src->width, src->height, &image);
-    if (st != CRH_OK) return st;
-    void* tables_dev = nullptr; // the caller's 1024 bytes, as they are
-    bool ok = true;
-    if (tables)
-        ok = hip_ok(hipMalloc(&tables_dev, 1024), "hipMalloc(colour tables)") && hip_ok(hipMemcpyAsync(tables_dev, tables, 1024, hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(colour tables)");
-    if (ok) {
-        launch_image_color_filter(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, f, static_cast<const uint32_t*>(tables_dev), static_cast<uint32_t*>(image->pixels->p), r->stream);
-        ok = hip_ok(hipGetLastError(), "k_image_color_filter");
-    }
-    ok = hip_ok(r->sync(), "sync(colour filter)") && ok; // (also behind a failure: `tables` is read by the copy until the stream has drained)
-    if (tables_dev) (void)hipFree(tables_dev);
-    if (!ok) {
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
-namespace {
-static_assert(CRH_MAX_MORPHOLOGY_RADIUS == kMorphologyMaxRadius && CRH_MORPHOLOGY_ERODE == kMorphologyErode && CRH_MORPHOLOGY_DILATE == kMorphologyDilate &&
-                  CRH_BLUR_EDGE_TRANSPARENT == kMorphologyTransparent,
-              "morphology.hpp's limit, operators and edge are the header's");
-crh_status morphology_error(const char* what) {
-    g_error = std::string("crh_morphology_size: ") + what;
-    return CRH_ERR_INVALID_ARGUMENT;
-}
-// validates, and gives the size of the result: the one check of crh_morphology_size, crh_morphology_texels and crh_image_morphology
-crh_status morphology_size(uint32_t width, uint32_t height, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, uint32_t* out_width, uint32_t* out_height) {
-    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return morphology_error("width and height lie in [1, 16384]");
-    if (op > CRH_MORPHOLOGY_DILATE) return morphology_error("op is above CRH_MORPHOLOGY_DILATE");
-    if (edge > CRH_BLUR_EDGE_REFLECT) return morphology_error("edge is above CRH_BLUR_EDGE_REFLECT");
-    if (radius_x > CRH_MAX_MORPHOLOGY_RADIUS || radius_y > CRH_MAX_MORPHOLOGY_RADIUS) return morphology_error("a radius exceeds CRH_MAX_MORPHOLOGY_RADIUS");
-    const bool grows = morphology_grows(op, edge);
-    const uint32_t w = width + (grows ? 2u * radius_x : 0u), h = height + (grows ? 2u * radius_y : 0u);
-    if (w > kMaxImageSize || h > kMaxImageSize) {
-        g_error = "crh_morphology_size: a side of the grown result exceeds 16384";
-        return CRH_ERR_UNSUPPORTED;
-    }
-    *out_width = w, *out_height = h;
-    return CRH_OK;
-}
-} // namespace
-crh_status crh_morphology_size(uint32_t width, uint32_t height, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, uint32_t* out_width, uint32_t* out_height) {
-    if (!out_width || !out_height) return morphology_error("a null argument");
-    uint32_t w = 0u, h = 0u;
-    const crh_status st = morphology_size(width, height, op, radius_x, radius_y, edge, &w, &h);
-    if (st != CRH_OK) return st;
-    *out_width = w, *out_height = h;
-    return CRH_OK;
-}
-crh_status crh_morphology_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, void* out_rgba8) {
-    if (!rgba8 || !out_rgba8) return morphology_error("a null argument");
-    if (rgba8 == out_rgba8) return morphology_error("out_rgba8 is rgba8");
-    uint32_t w = 0u, h = 0u;
-    const crh_status st = morphology_size(width, height, op, radius_x, radius_y, edge, &w, &h);
-    if (st != CRH_OK) return st;
-    if (op == CRH_MORPHOLOGY_DILATE) morphology_run<true>(static_cast<const uint8_t*>(rgba8), width, height, radius_x, radius_y, edge, static_cast<uint8_t*>(out_rgba8));
-    else morphology_run<false>(static_cast<const uint8_t*>(rgba8), width, height, radius_x, radius_y, edge, static_cast<uint8_t*>(out_rgba8));
-    return CRH_OK;
-}
-crh_status crh_image_morphology(const crh_image* src, uint32_t op, uint32_t radius_x, uint32_t radius_y, uint32_t edge, crh_image** out) {
-    if (!src || !src->renderer || !out) return morphology_error("a null argument");
-    uint32_t out_w = 0u, out_h = 0u;
-    crh_status st = morphology_size(src->width, src->height, op, radius_x, radius_y, edge, &out_w, &out_h);
-    if (st != CRH_OK) return st;
-    const bool grows = morphology_grows(op, edge);
-    crh_renderer* r = src->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    st = new_image(r, out_w, out_h, &image);
-    if (st != CRH_OK) return st;
-    const uint32_t* from = static_cast<const uint32_t*>(src->pixels->p);
-    uint32_t* to = static_cast<uint32_t*>(image->pixels->p);
-    // A zero radius skips its pass (and does not grow its axis): no pass is a copy, one pass goes from the source to the result, and only two
-    // passes need the intermediate — packed RGBA8, the result's width and the source's height.
-    void* tmp = nullptr;
-    bool ok = true;
-    if (radius_x == 0u && radius_y == 0u) {
-        ok = hip_ok(hipMemcpyAsync(to, from, (size_t)out_w * out_h * 4, hipMemcpyDeviceToDevice, r->stream), "hipMemcpyAsync(morphology copy)");
-    } else if (radius_y == 0u) {
-        launch_image_morph_h(from, src->width, src->height, to, out_w, op, radius_x, grows ? radius_x : 0u, edge, r->stream);
-        ok = hip_ok(hipGetLastError(), "k_image_morph_h");
-    } else if (radius_x == 0u) {
-        launch_image_morph_v(from, src->height, to, out_w, out_h, op, radius_y, grows ? radius_y : 0u, edge, r->stream);
-        ok = hip_ok(hipGetLastError(), "k_image_morph_v");
-    } else {
-        ok = hip_ok(hipMalloc(&tmp, (size_t)out_w * src->height * 4), "hipMalloc(morphology intermediate)");
-        if (ok) {
-            launch_image_morph_h(from, src->width, src->height, static_cast<uint32_t*>(tmp), out_w, op, radius_x, grows ? radius_x : 0u, edge, r->stream);
-            ok = hip_ok(hipGetLastError(), "k_image_morph_h");
-        }
-        if (ok) {
-            launch_image_morph_v(static_cast<const uint32_t*>(tmp), src->height, to, out_w, out_h, op, radius_y, grows ? radius_y : 0u, edge, r->stream);
-            ok = hip_ok(hipGetLastError(), "k_image_morph_v");
-        }
-    }
-    ok = hip_ok(r->sync(), "sync(morphology)") && ok; // (also behind a failure: the intermediate is read until the stream has drained)
-    if (tmp) (void)hipFree(tmp);
-    if (!ok) {
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
-namespace {
-static_assert(CRH_MAX_CONVOLVE_ORDER == kConvolveMaxOrder && CRH_CONVOLVE_MAX_GAIN == kConvolveMaxGain && CRH_BLUR_EDGE_TRANSPARENT == kConvolveTransparent,
-              "convolve.hpp's limits and edge are the header's");
-crh_status convolve_error(const char* what) {
-    g_error = std::string("crh_convolve_validate: ") + what;
-    return CRH_ERR_INVALID_ARGUMENT;
-}
-// validates and quantises: the one check of the four entry points, and the one way from the caller's floats to the coefficients
-crh_status convolve_coefficients(const crh_convolve* how, ConvolveCoefficients* f) {
-    if (!how || !how->kernel) return convolve_error("a null argument");
-    if (how->order_x == 0u || how->order_y == 0u || how->order_x > CRH_MAX_CONVOLVE_ORDER || how->order_y > CRH_MAX_CONVOLVE_ORDER) return convolve_error("an order is outside [1, CRH_MAX_CONVOLVE_ORDER]");
-    if (how->target_x >= how->order_x || how->target_y >= how->order_y) return convolve_error("a target is not below its order");
-    if (how->edge > CRH_BLUR_EDGE_REFLECT) return convolve_error("edge is above CRH_BLUR_EDGE_REFLECT");
-    if (how->preserve_alpha > 1u) return convolve_error("preserve_alpha is above 1");
-    if (how->divisor == 0.0f) return convolve_error("divisor is 0");
-    if (std::isfinite(how->bias) && std::fabs(how->bias) > 1.0f) return convolve_error("bias is outside [-1, 1]");
-    switch (convolve_quantize(how->kernel, how->order_x, how->order_y, how->divisor, how->bias, f)) {
-    case kConvolveNonFinite: return CRH_ERR_NON_FINITE;
-    case kConvolveGain: return convolve_error("the kernel over the divisor exceeds CRH_CONVOLVE_MAX_GAIN: sum |k| is above 64 * 65536");
-    default: return CRH_OK;
-    }
-}
-crh_status convolve_size(uint32_t width, uint32_t height) {
-    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return convolve_error("width and height lie in [1, 16384]");
-    return CRH_OK;
-}
-} // namespace
-crh_status crh_convolve_validate(const crh_convolve* how) {
-    ConvolveCoefficients f;
-    return convolve_coefficients(how, &f);
-}
-crh_status crh_convolve_coefficients(const crh_convolve* how, int32_t* k, uint32_t capacity, int32_t* bias_k) {
-    ConvolveCoefficients f;
-    const crh_status st = convolve_coefficients(how, &f);
-    if (st != CRH_OK) return st;
-    const uint32_t n = how->order_x * how->order_y;
-    if (k && capacity < n) return convolve_error("capacity is below order_x * order_y");
-    if (k) std::copy(f.k, f.k + n, k);
-    if (bias_k) *bias_k = f.bias_k;
-    return CRH_OK;
-}
-crh_status crh_convolve_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_convolve* how, void* out_rgba8) {
-    if (!rgba8 || !out_rgba8) return convolve_error("a null argument");
-    if (rgba8 == out_rgba8) return convolve_error("out_rgba8 is rgba8");
-    ConvolveCoefficients f;
-    crh_status st = convolve_coefficients(how, &f);
-    if (st != CRH_OK) return st;
-    st = convolve_size(width, height);
-    if (st != CRH_OK) return st;
-    const uint8_t* in = static_cast<const uint8_t*>(rgba8);
-    uint8_t* to = static_cast<uint8_t*>(out_rgba8);
-    if (how->preserve_alpha) convolve_run<true>(in, width, height, f, how->order_x, how->order_y, how->target_x, how->target_y, how->edge, to);
-    else convolve_run<false>(in, width, height, f, how->order_x, how->order_y, how->target_x, how->target_y, how->edge, to);
-    return CRH_OK;
-}
-crh_status crh_image_convolve(const crh_image* src, const crh_convolve* how, crh_image** out) {
-    if (!src || !src->renderer || !out) return convolve_error("a null argument");
-    ConvolveCoefficients f;
-    crh_status st = convolve_coefficients(how, &f);
-    if (st != CRH_OK) return st;
-    st = convolve_size(src->width, src->height);
-    if (st != CRH_OK) return st;
-    crh_renderer* r = src->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    st = new_image(r, src->width, src->height, &image);
-    if (st != CRH_OK) return st;
-    launch_image_convolve(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, f, how->order_x, how->order_y, how->target_x, how->target_y, how->edge, how->preserve_alpha != 0u,
-                          static_cast<uint32_t*>(image->pixels->p), r->stream);
-    bool ok = hip_ok(hipGetLastError(), "k_image_convolve");
-    ok = hip_ok(r->sync(), "sync(convolve)") && ok;
-    if (!ok) {
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
-namespace {
-static_assert(CRH_LIGHTING_DIFFUSE == kLightingDiffuse && CRH_LIGHTING_SPECULAR == kLightingSpecular && CRH_LIGHT_DISTANT == kLightDistant && CRH_LIGHT_POINT == kLightPoint &&
-                  CRH_LIGHT_SPOT == kLightSpot && CRH_BLUR_EDGE_TRANSPARENT == kLightingTransparent,
-              "lighting.hpp's ops, lights and edge are the header's");
-crh_status lighting_error(const char* what) {
-    g_error = std::string("crh_lighting_validate: ") + what;
-    return CRH_ERR_INVALID_ARGUMENT;
-}
-// validates and prepares: the one check of the three entry points, and the one way from the caller's floats to the rule's constants.
-// Only the fields that op and light use are read: first whether they are finite, then their ranges.
-crh_status lighting_constants(const crh_lighting* how, LightingConstants* f) {
-    if (!how) return lighting_error("a null argument");
-    if (how->op > CRH_LIGHTING_SPECULAR) return lighting_error("op is above CRH_LIGHTING_SPECULAR");
-    if (how->light > CRH_LIGHT_SPOT) return lighting_error("light is above CRH_LIGHT_SPOT");
-    if (how->edge > CRH_BLUR_EDGE_REFLECT) return lighting_error("edge is above CRH_BLUR_EDGE_REFLECT");
-    const bool specular = how->op == CRH_LIGHTING_SPECULAR, distant = how->light == CRH_LIGHT_DISTANT, spot = how->light == CRH_LIGHT_SPOT;
-    bool finite = std::isfinite(how->surface_scale) && std::isfinite(how->constant) && (!specular || std::isfinite(how->specular_exponent));
-    for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(how->color[c]);
-    if (distant) finite = finite && std::isfinite(how->azimuth) && std::isfinite(how->elevation);
-    else
-        for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(how->position[c]);
-    if (spot) {
-        for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(how->points_at[c]);
-        finite = finite && std::isfinite(how->spot_exponent) && std::isfinite(how->cone_angle);
-    }
-    if (!finite) return CRH_ERR_NON_FINITE;
-    if (std::fabs(how->surface_scale) > 256.0f) return lighting_error("surface_scale is outside [-256, 256]");
-    if (how->constant < 0.0f || how->constant > 256.0f) return lighting_error("constant is outside [0, 256]");
-    if (specular && (how->specular_exponent < 1.0f || how->specular_exponent > 128.0f)) return lighting_error("specular_exponent is outside [1, 128]");
-    for (int c = 0; c < 3; ++c)
-        if (how->color[c] < 0.0f || how->color[c] > 1.0f) return lighting_error("a colour is outside [0, 1]");
-    if (distant) {
-        if (std::fabs(how->azimuth) > 3600.0f || std::fabs(how->elevation) > 3600.0f) return lighting_error("azimuth or elevation is outside [-3600, 3600]");
-    } else {
-        for (int c = 0; c < 3; ++c)
-            if (std::fabs(how->position[c]) > 1048576.0f) return lighting_error("a position is outside [-2^20, 2^20]");
-    }
-    if (spot) {
-        for (int c = 0; c < 3; ++c)
-            if (std::fabs(how->points_at[c]) > 1048576.0f) return lighting_error("a points_at is outside [-2^20, 2^20]");
-        if (how->points_at[0] == how->position[0] && how->points_at[1] == how->position[1] && how->points_at[2] == how->position[2]) return lighting_error("points_at is position");
-        if (how->spot_exponent < 0.0f || how->spot_exponent > 128.0f) return lighting_error("spot_exponent is outside [0, 128]");
-        if (how->cone_angle < 0.0f || how->cone_angle > 90.0f) return lighting_error("cone_angle is neither 0 nor in (0, 90]");
-    }
-    lighting_prepare(how->op, how->light, how->surface_scale, how->constant, how->specular_exponent, how->color, how->azimuth, how->elevation, how->position, how->points_at,
-                     how->spot_exponent, how->cone_angle, f);
-    return CRH_OK;
-}
-crh_status lighting_size(uint32_t width, uint32_t height) {
-    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return lighting_error("width and height lie in [1, 16384]");
-    return CRH_OK;
-}
-} // namespace
-crh_status crh_lighting_validate(const crh_lighting* how) {
-    LightingConstants f;
-    return lighting_constants(how, &f);
-}
-crh_status crh_lighting_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_lighting* how, void* out_rgba8) {
-    if (!rgba8 || !out_rgba8) return lighting_error("a null argument");
-    if (rgba8 == out_rgba8) return lighting_error("out_rgba8 is rgba8");
-    LightingConstants f;
-    crh_status st = lighting_constants(how, &f);
-    if (st != CRH_OK) return st;
-    st = lighting_size(width, height);
-    if (st != CRH_OK) return st;
-    lighting_run(static_cast<const uint8_t*>(rgba8), width, height, f, how->op, how->light, how->edge, static_cast<uint8_t*>(out_rgba8));
-    return CRH_OK;
-}
-crh_status crh_image_lighting(const crh_image* src, const crh_lighting* how, crh_image** out) {
-    if (!src || !src->renderer || !out) return lighting_error("a null argument");
-    LightingConstants f;
-    crh_status st = lighting_constants(how, &f);
-    if (st != CRH_OK) return st;
-    st = lighting_size(src->width, src->height);
-    if (st != CRH_OK) return st;
-    crh_renderer* r = src->renderer;
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    st = new_image(r, src->width, src->height, &image);
-    if (st != CRH_OK) return st;
-    launch_image_lighting(static_cast<const uint32_t*>(src->pixels->p), src->width, src->height, f, how->op, how->light, how->edge, static_cast<uint32_t*>(image->pixels->p), r->stream);
-    bool ok = hip_ok(hipGetLastError(), "k_image_lighting");
-    ok = hip_ok(r->sync(), "sync(lighting)") && ok;
-    if (!ok) {
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
-namespace {
-static_assert(CRH_TURBULENCE_FRACTAL_NOISE == kTurbulenceFractalNoise && CRH_TURBULENCE_TURBULENCE == kTurbulenceTurbulence && CRH_MAX_TURBULENCE_OCTAVES == kTurbulenceMaxOctaves,
-              "turbulence.hpp's kinds and limit are the header's");
-crh_status turbulence_error(const char* what) {
-    g_error = std::string("crh_turbulence_validate: ") + what;
-    return CRH_ERR_INVALID_ARGUMENT;
-}
-// the one check of the fields, for the four entry points
-crh_status turbulence_fields(const crh_turbulence* how) {
-    if (!how) return turbulence_error("a null argument");
-    if (how->kind > CRH_TURBULENCE_TURBULENCE) return turbulence_error("kind is above CRH_TURBULENCE_TURBULENCE");
-    if (how->stitch > 1u) return turbulence_error("stitch is neither 0 nor 1");
-    if (how->opaque > 1u) return turbulence_error("opaque is neither 0 nor 1");
-    if (how->octaves > CRH_MAX_TURBULENCE_OCTAVES) return turbulence_error("octaves is above CRH_MAX_TURBULENCE_OCTAVES");
-    for (int c = 0; c < 2; ++c)
-        if (!std::isfinite(how->base_frequency[c]) || !std::isfinite(how->offset[c])) {
-            g_error = "crh_turbulence_validate: a frequency or an offset is not finite";
-            return CRH_ERR_NON_FINITE;
-        }
-    for (int c = 0; c < 2; ++c)
-        if (how->base_frequency[c] < 0.0f || how->base_frequency[c] > CRH_TURBULENCE_MAX_FREQUENCY) return turbulence_error("a base_frequency is outside [0, 4]");
-    for (int c = 0; c < 2; ++c)
-        if (std::fabs(how->offset[c]) > CRH_TURBULENCE_MAX_OFFSET) return turbulence_error("an offset is outside [-65536, 65536]");
-    return CRH_OK;
-}
-// validates a whole call and prepares it: the one way from the caller's floats to the rule's constants
-crh_status turbulence_constants(uint32_t width, uint32_t height, const crh_turbulence* how, TurbulenceConstants* f) {
-    const crh_status st = turbulence_fields(how);
-    if (st != CRH_OK) return st;
-    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) return turbulence_error("width and height lie in [1, 16384]");
-    turbulence_prepare(width, height, how->octaves, how->stitch != 0u, how->base_frequency, how->offset, f);
-    return CRH_OK;
-}
-} // namespace
-crh_status crh_turbulence_validate(const crh_turbulence* how) { return turbulence_fields(how); }
-crh_status crh_turbulence_tables(int32_t seed, uint8_t lattice[256], double gradient[4 * 256 * 2]) {
-    if (!lattice || !gradient) return turbulence_error("a null argument");
-    TurbulenceTables t;
-    turbulence_make_tables(seed, &t);
-    std::memcpy(lattice, t.lattice, sizeof(t.lattice));
-    std::memcpy(gradient, t.gradient, sizeof(t.gradient));
-    return CRH_OK;
-}
-crh_status crh_turbulence_texels(uint32_t width, uint32_t height, const crh_turbulence* how, void* out_rgba8) {
-    if (!out_rgba8) return turbulence_error("a null argument");
-    TurbulenceConstants f;
-    const crh_status st = turbulence_constants(width, height, how, &f);
-    if (st != CRH_OK) return st;
-    TurbulenceTables t;
-    turbulence_make_tables(how->seed, &t);
-    turbulence_run(t, f, how->kind, how->opaque != 0u, width, height, static_cast<uint8_t*>(out_rgba8));
-    return CRH_OK;
-}
-crh_status crh_image_turbulence(crh_renderer* r, uint32_t width, uint32_t height, const crh_turbulence* how, crh_image** out) {
-    if (!r || !out) return turbulence_error("a null argument");
-    TurbulenceConstants f;
-    crh_status st = turbulence_constants(width, height, how, &f);
-    if (st != CRH_OK) return st;
-    TurbulenceTables t;
-    turbulence_make_tables(how->seed, &t);
-    HIP_TRY(hipSetDevice(r->device));
-    crh_image* image = nullptr;
-    st = new_image(r, width, height, &image);
-    if (st != CRH_OK) return st;
-    void* tables_dev = nullptr;
-    bool ok = hip_ok(hipMalloc(&tables_dev, sizeof(t)), "hipMalloc(turbulence tables)") &&
-              hip_ok(hipMemcpyAsync(tables_dev, &t, sizeof(t), hipMemcpyHostToDevice, r->stream), "hipMemcpyAsync(turbulence tables)");
-    if (ok) {
-        launch_image_turbulence(static_cast<const TurbulenceTables*>(tables_dev), width, height, f, how->kind, how->opaque != 0u, static_cast<uint32_t*>(image->pixels->p), r->stream);
-        ok = hip_ok(hipGetLastError(), "k_image_turbulence");
-    }
-    ok = hip_ok(r->sync(), "sync(turbulence)") && ok; // (also behind a failure: `t` is read by the copy until the stream has drained)
-    if (tables_dev) (void)hipFree(tables_dev);
-    if (!ok) {
-        delete image;
-        return CRH_ERR_HIP;
-    }
-    *out = image;
-    return CRH_OK;
-}
-void crh_image_destroy(crh_image* image) { delete image; } // (the pixels and their mipmaps stay while a Scene's paint table names them)
 crh_status crh_frame_download_f16(crh_frame* f, void* rgba16f) { return download_pixels(f, rgba16f, CRH_FORMAT_RGBA16F); }
 extern "C" crh_status crh_debug_frame_counters(crh_frame* f, uint32_t out[8]) { // tools only (not in the public header)
     HIP_TRY(hipSetDevice(f->renderer->device));
@@ -3619,7 +2959,7 @@ crh_status crh_frame_device_pointer(crh_frame* f, void** out) {
     *out = f->rgba8.p;
     return CRH_OK;
 }
-// ---- internal accessors for csrc/comm.hip (the multi-GPU exchange); not part of the public header
+// ---- internal accessors for csrc/comm.hip (the multi-GPU exchange), declared in api_internal.hpp; not part of the public header
 crh_status crh_internal_frame_geometry(crh_frame* f, uint32_t* width, uint32_t* height, uint32_t* format, int* device) { // no waiting, cannot fail for a live frame
     if (!f || !f->renderer || !width || !height || !format || !device) return CRH_ERR_INVALID_ARGUMENT;
     *width = f->width, *height = f->height, *format = f->format, *device = f->renderer->device;

@@ -1,5 +1,5 @@
 // csrc/color_filter.hpp — the colour-filter rule of crh_image_color_filter (include/contrast_hip.h states it), written once:
-// k_image_color_filter (image_filter.hip) and crh_color_filter_texels (api.hip, on the host) both call color_filter_texel, and both take
+// k_image_color_filter (image_filter.hip) and crh_color_filter_texels (image.hip, on the host) both call color_filter_texel, and both take
 // their coefficients from color_filter_quantize. All values are 8-bit codes, all arithmetic is signed 32-bit; nothing here divides by
 // anything but the constant 255: the unpremultiply is one multiply by an entry of a 256-word table.
 #pragma once

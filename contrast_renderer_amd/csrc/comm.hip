@@ -30,22 +30,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/contrast_hip.h"
-
-namespace crh {
-void set_last_error(const std::string& text);
-}
-// internal accessors of api.hip (not part of the public header)
-extern "C" crh_status crh_internal_frame_geometry(crh_frame* f, uint32_t* width, uint32_t* height, uint32_t* format, int* device);
-extern "C" crh_status crh_internal_frame_info(crh_frame* f, void** rgba8, uint32_t* width, uint32_t* height, int* device);
-extern "C" crh_status crh_internal_frame_touched(crh_frame* f, void* stream, int written);
-extern "C" crh_status crh_internal_frame_order(crh_frame* f, void* stream, int will_write);
-extern "C" crh_status crh_internal_frame_slab(crh_frame* f, uint32_t* row_begin, uint32_t* row_end);
-extern "C" crh_status crh_internal_frame_tile_counts(crh_frame* f, const uint32_t** counts, uint32_t* n_tiles, uint32_t* first_tile, uint32_t* end_tile);
-extern "C" int crh_internal_renderer_device(crh_renderer* r);
-extern "C" int crh_internal_frame_blends_over(crh_frame* f);
+#include "api_internal.hpp" // set_last_error, hip_ok / HIP_TRY and api.hip's crh_internal_* accessors
 
 namespace {
+using crh::hip_ok;
 using crh::set_last_error;
 
 struct Rccl { // the entry points used, resolved with dlsym
@@ -111,15 +99,6 @@ Rccl* rccl() {
     return api.lib ? &api : nullptr;
 }
 
-bool hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-    return false;
-}
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        if (!hip_ok((expr), #expr)) return CRH_ERR_HIP; \
-    } while (0)
 bool nccl_ok(ncclResult_t rc, const char* what) {
     if (rc == ncclSuccess) return true;
     Rccl* api = rccl();

@@ -1,5 +1,5 @@
 // csrc/composite.hpp — the compositing rule of crh_image_composite (include/contrast_hip.h states it), written once: k_image_composite
-// (image_filter.hip) and crh_composite_texels (api.hip, on the host) both call composite_texel. All values are 8-bit codes, all arithmetic is
+// (image_filter.hip) and crh_composite_texels (image.hip, on the host) both call composite_texel. All values are 8-bit codes, all arithmetic is
 // unsigned 32-bit; nothing here divides by anything but the constants 255 and 65025.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // csrc/convolve.hpp — the convolution rule of crh_image_convolve (include/contrast_hip.h states it), written once: the quantisation of the
 // kernel matrix, the load of one texel (the clamp to alpha and, under preserve_alpha, the unpremultiply of color_filter.hpp) and the output
-// stage. k_image_convolve (image_filter.hip) and crh_convolve_texels (api.hip, on the host) both call convolve_load, convolve_mad and
+// stage. k_image_convolve (image_filter.hip) and crh_convolve_texels (image.hip, on the host) both call convolve_load, convolve_mad and
 // convolve_store, and both take their coefficients from convolve_quantize; the wrap is morphology.hpp's. All values are 8-bit codes, all
 // arithmetic is signed 32-bit: sum |k| <= 2^22, so |sum k s| <= 2^22 * 255, and with 255 * 65536 of bias and the rounding half the largest
 // magnitude is 1 086 291 968 < 2^31. Every partial sum obeys the same bound, so the order of the taps is free.

@@ -1,5 +1,5 @@
-// csrc/launch.hpp — the interface between the translation units: what api.hip calls in tessellate.hip, raster.hip, image_filter.hip, bin_edges.hip and raster_edges.hip, and
-// what those call in each other. Included by the callers AND by every file that defines one of these, so that the compiler checks each
+// csrc/launch.hpp — the interface to the kernels: what api.hip and image.hip call in tessellate.hip, raster.hip, image_filter.hip, bin_edges.hip and raster_edges.hip, and
+// what those call in each other (api_internal.hpp is the interface between the host files). Included by the callers AND by every file that defines one of these, so that the compiler checks each
 // definition against its declaration.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // csrc/lighting.hpp — the lighting rule of crh_image_lighting (include/contrast_hip.h states it), written once: the per-call constants from
 // the caller's floats, the Sobel gradient of the height field and the lit texel. k_image_lighting (image_filter.hip) and
-// crh_lighting_texels (api.hip, on the host) both call lighting_prepare, lighting_gradient and lighting_texel; the wrap is morphology.hpp's.
+// crh_lighting_texels (image.hip, on the host) both call lighting_prepare, lighting_gradient and lighting_texel; the wrap is morphology.hpp's.
 // All real arithmetic is IEEE binary64 in the written order and parenthesisation, with only + - * / sqrt and the functions of
 // include/crh_fmath.h, compiled without contraction (-ffp-contract=off), and one rounding to a code at the end: the same bytes on x86-64 and
 // on gfx950.

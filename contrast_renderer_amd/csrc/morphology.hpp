@@ -1,6 +1,6 @@
 // csrc/morphology.hpp — the morphology rule of crh_image_morphology (include/contrast_hip.h states it), written once: the wrap of an index by
 // an edge and the per-channel min / max of two packed RGBA8 texels. k_image_morph_h and k_image_morph_v (image_filter.hip) and
-// crh_morphology_texels (api.hip, on the host) all call morphology_wrap and morphology_extreme. Min and max do not round, so there is no
+// crh_morphology_texels (image.hip, on the host) all call morphology_wrap and morphology_extreme. Min and max do not round, so there is no
 // arithmetic to state beyond them: the values are the 8-bit codes as they are.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -21,10 +21,7 @@
 #include <vector>
 
 #include "../../include/contrast_hip.h"
-
-namespace crh {
-void set_last_error(const std::string& text); // api.hip
-}
+#include "last_error.hpp"
 
 namespace {
 

@@ -1,6 +1,6 @@
 // csrc/turbulence.hpp — the noise rule of crh_image_turbulence (include/contrast_hip.h states it), written once: the seeded tables, the per-call
 // constants from the caller's floats, one axis of one octave's lattice cell, the noise of every channel at a point and the texel of the sums.
-// k_image_turbulence (image_filter.hip) and crh_turbulence_texels (api.hip, on the host) both call turbulence_axis, turbulence_corners,
+// k_image_turbulence (image_filter.hip) and crh_turbulence_texels (image.hip, on the host) both call turbulence_axis, turbulence_corners,
 // turbulence_noise, turbulence_add and turbulence_texel; the tables and the constants are made on the host alone.
 // All real arithmetic is IEEE binary64 in the written order and parenthesisation, with only + - * / sqrt and a floor, compiled without
 // contraction (-ffp-contract=off), and one rounding to a code at the end: the same bytes on x86-64 and on gfx950. Three things are written

@@ -760,19 +760,25 @@ class Image:
         self.handle = handle
         self.width, self.height = int(data.shape[1]), int(data.shape[0])
 
+    @classmethod
+    def _adopt(cls, renderer, handle, size=None):
+        """A new Image around a handle the library has just returned; `size` = (width, height) where the caller knows it, crh_image_size otherwise."""
+        image = cls.__new__(cls)
+        image.renderer, image.lib, image.handle = renderer, renderer.lib, handle
+        if size is None:
+            w, h = C.c_uint32(), C.c_uint32()
+            check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
+            size = (w.value, h.value)
+        image.width, image.height = int(size[0]), int(size[1])
+        return image
+
     @staticmethod
     def from_frame(frame: Frame):
         """crh_image_create_from_frame: a snapshot of what the frame shows (an RGBA8 or RGBA8-attachment frame, not restricted by
         set_tile_rows), copied on the device; later passes into the frame do not change it."""
-        image = Image.__new__(Image)
-        image.renderer, image.lib = frame.renderer, frame.lib
         handle = C.c_void_p()
-        check(image.lib.crh_image_create_from_frame(frame.handle, C.byref(handle)))
-        image.handle = handle
-        w, h = C.c_uint32(), C.c_uint32()
-        check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
-        image.width, image.height = int(w.value), int(h.value)
-        return image
+        check(frame.lib.crh_image_create_from_frame(frame.handle, C.byref(handle)))
+        return Image._adopt(frame.renderer, handle)
 
     @classmethod
     def turbulence(cls, renderer: Renderer, width, height, base_frequency, octaves=1, seed=0, kind=TurbulenceKind.Turbulence, stitch=False, opaque=False, offset=(0, 0)):
@@ -783,13 +789,9 @@ class Image:
         itself; `opaque` gives alpha 255 and three channels of noise instead of SVG's four; `offset` = the noise-space position of texel
         (0, 0), so a large texture can be made in pieces. Binary64 arithmetic in a fixed order, so every byte is defined."""
         how = _turbulence_arguments(base_frequency, octaves, seed, kind, stitch, opaque, offset)
-        image = cls.__new__(cls)
-        image.renderer, image.lib = renderer, renderer.lib
         handle = C.c_void_p()
-        check(image.lib.crh_image_turbulence(renderer.handle, int(width), int(height), C.byref(how), C.byref(handle)))
-        image.handle = handle
-        image.width, image.height = int(width), int(height)
-        return image
+        check(renderer.lib.crh_image_turbulence(renderer.handle, int(width), int(height), C.byref(how), C.byref(handle)))
+        return cls._adopt(renderer, handle, (width, height))
 
     def generate_mipmaps(self):
         """crh_image_generate_mipmaps: the levels below the image, each the rounded 2 x 2 mean of the one above, built on the device; complete
@@ -818,14 +820,9 @@ class Image:
         (Rx, Ry); the other edges keep the size. This image is not modified."""
         sigma_x = float(sigma_x)
         sigma_y = sigma_x if sigma_y is None else float(sigma_y)
-        image = Image.__new__(Image)
-        image.renderer, image.lib = self.renderer, self.lib
         handle = C.c_void_p()
         check(self.lib.crh_image_blur(self.handle, sigma_x, sigma_y, int(edge), C.byref(handle)))
-        image.handle = handle
-        w, h = C.c_uint32(), C.c_uint32()
-        check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
-        image.width, image.height = int(w.value), int(h.value)
+        image = Image._adopt(self.renderer, handle)
         if int(edge) == BlurEdge.Transparent:
             image.origin = ((image.width - self.width) // 2, (image.height - self.height) // 2)
         return image
@@ -838,13 +835,9 @@ class Image:
         blurred from would lie at (dx, dy): offset = (dx - source.origin[0], dy - source.origin[1]). Neither image is modified; `source` may
         be this image."""
         how = _ffi.CompositeC(int(op), int(mode), float(opacity), int(offset[0]), int(offset[1]))
-        image = Image.__new__(Image)
-        image.renderer, image.lib = self.renderer, self.lib
         handle = C.c_void_p()
         check(self.lib.crh_image_composite(self.handle, source.handle, C.byref(how), C.byref(handle)))
-        image.handle = handle
-        image.width, image.height = self.width, self.height
-        return image
+        return Image._adopt(self.renderer, handle, (self.width, self.height))
 
     def color_filter(self, matrix=None, tables=None):
         """crh_image_color_filter -> a new Image of one level, of this image's size and origin: every texel unpremultiplied, through the
@@ -853,12 +846,10 @@ class Image:
         the device and complete when this returns. A blurred snapshot through ColorMatrix.flood(r, g, b, a) is a drop shadow in that colour.
         This image is not modified."""
         m, t = _color_filter_arguments(matrix, tables)
-        image = Image.__new__(Image)
-        image.renderer, image.lib = self.renderer, self.lib
         handle = C.c_void_p()
         check(self.lib.crh_image_color_filter(self.handle, m, None if t is None else t.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(handle)))
-        image.handle = handle
-        image.width, image.height, image.origin = self.width, self.height, self.origin
+        image = Image._adopt(self.renderer, handle, (self.width, self.height))
+        image.origin = self.origin
         return image
 
     def morphology(self, op, radius_x, radius_y=None, edge=BlurEdge.Transparent):
@@ -869,14 +860,9 @@ class Image:
         keeps the size and origin (0, 0). This image is not modified."""
         radius_x = int(radius_x)
         radius_y = radius_x if radius_y is None else int(radius_y)
-        image = Image.__new__(Image)
-        image.renderer, image.lib = self.renderer, self.lib
         handle = C.c_void_p()
         check(self.lib.crh_image_morphology(self.handle, int(op), radius_x, radius_y, int(edge), C.byref(handle)))
-        image.handle = handle
-        w, h = C.c_uint32(), C.c_uint32()
-        check(image.lib.crh_image_size(handle, C.byref(w), C.byref(h)))
-        image.width, image.height = int(w.value), int(h.value)
+        image = Image._adopt(self.renderer, handle)
         if int(op) == MorphologyOp.Dilate and int(edge) == BlurEdge.Transparent:
             image.origin = (radius_x, radius_y)
         return image
@@ -896,12 +882,10 @@ class Image:
         target=None means (order_x // 2, order_y // 2); |bias| <= 1 is added in units of the full range. preserve_alpha=True keeps every
         texel's alpha and convolves the unpremultiplied colours. The result has this image's size under every edge. This image is not modified."""
         how, values = _convolve_arguments(kernel, divisor, bias, target, edge, preserve_alpha)
-        image = Image.__new__(Image)
-        image.renderer, image.lib = self.renderer, self.lib
         handle = C.c_void_p()
         check(self.lib.crh_image_convolve(self.handle, C.byref(how), C.byref(handle)))
-        image.handle = handle
-        image.width, image.height, image.origin = self.width, self.height, self.origin
+        image = Image._adopt(self.renderer, handle, (self.width, self.height))
+        image.origin = self.origin
         return image
 
     def lighting(self, light, op=LightingOp.Diffuse, surface_scale=1.0, constant=1.0, specular_exponent=1.0, color=(1.0, 1.0, 1.0), edge=BlurEdge.Pad):
@@ -911,12 +895,10 @@ class Image:
         a layer); LightingOp.Specular gives premultiplied highlights constant * (N.H) ** specular_exponent * colour (PLUS them onto a
         layer). Binary64 arithmetic in a fixed order, so every byte is defined. This image is not modified; its colours are not read."""
         how = _lighting_arguments(light, op, surface_scale, constant, specular_exponent, color, edge)
-        image = Image.__new__(Image)
-        image.renderer, image.lib = self.renderer, self.lib
         handle = C.c_void_p()
         check(self.lib.crh_image_lighting(self.handle, C.byref(how), C.byref(handle)))
-        image.handle = handle
-        image.width, image.height, image.origin = self.width, self.height, self.origin
+        image = Image._adopt(self.renderer, handle, (self.width, self.height))
+        image.origin = self.origin
         return image
 
     def diffuse_lighting(self, light, surface_scale=1.0, constant=1.0, color=(1.0, 1.0, 1.0), edge=BlurEdge.Pad):
