@@ -245,6 +245,10 @@ class TurbulenceC(C.Structure):  # crh_turbulence
                 ("offset", C.c_float * 2)]
 
 
+class DisplaceC(C.Structure):  # crh_displace
+    _fields_ = [("scale", C.c_float * 2), ("x_channel", C.c_uint32), ("y_channel", C.c_uint32), ("filter", C.c_uint32), ("edge", C.c_uint32)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -343,6 +347,10 @@ def load_library():
         "crh_turbulence_tables": (C.c_int, [C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double)]),
         "crh_turbulence_texels": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(TurbulenceC), V]),
         "crh_image_turbulence": (C.c_int, [V, C.c_uint32, C.c_uint32, C.POINTER(TurbulenceC), C.POINTER(V)]),
+        "crh_displace_validate": (C.c_int, [C.POINTER(DisplaceC)]),
+        "crh_displace_offset": (C.c_int, [C.POINTER(DisplaceC), C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
+        "crh_displace_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, V, C.POINTER(DisplaceC), V]),
+        "crh_image_displace": (C.c_int, [V, V, C.POINTER(DisplaceC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

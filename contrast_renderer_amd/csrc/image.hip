@@ -1,5 +1,5 @@
-// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, and the seven
-// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence) with their host rules (crh_*_texels) and validators.
+// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, and the eight
+// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace) with their host rules (crh_*_texels) and validators.
 // Host code only: the kernels are image_filter.hip's and raster.hip's (launch.hpp), the rules are the filters' headers. Of a renderer it
 // uses its device, its stream and "wait for every stream" (api_internal.hpp); what is about a frame or a paint table stays in api.hip.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include "color_filter.hpp"
 #include "composite.hpp"
 #include "convolve.hpp"
+#include "displace.hpp"
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
@@ -570,5 +571,63 @@ crh_status crh_image_turbulence(crh_renderer* r, uint32_t width, uint32_t height
     return filter_call("crh_image_turbulence", r, width, height, out, [&](FilterJob& job) {
         const TurbulenceTables* tables_dev = static_cast<const TurbulenceTables*>(job.scratch(sizeof(t), &t, sizeof(t)));
         job.launch("k_image_turbulence", [&] { launch_image_turbulence(tables_dev, width, height, f, how->kind, how->opaque != 0u, job.texels(), job.stream); });
+    });
+}
+// ---- displace
+namespace {
+static_assert(CRH_MAX_DISPLACE_SCALE == kDisplaceMaxScale && CRH_FILTER_NEAREST == kDisplaceNearest && CRH_FILTER_LINEAR == kDisplaceLinear && CRH_CHANNEL_A == kDisplaceAlpha &&
+                  CRH_BLUR_EDGE_TRANSPARENT == kDisplaceTransparent,
+              "displace.hpp's limit, filters, alpha channel and edge are the header's");
+constexpr const char* kDisplace = "crh_displace_validate";
+// validates the fields and prepares them: the one check of the four entry points, and the one way from the caller's floats to the rule's constants
+crh_status displace_constants(const crh_displace* how, DisplaceConstants* f) {
+    if (!how) return refuse(kDisplace, "a null argument");
+    if (how->x_channel > CRH_CHANNEL_A || how->y_channel > CRH_CHANNEL_A) return refuse(kDisplace, "a channel is above CRH_CHANNEL_A");
+    if (how->filter != CRH_FILTER_NEAREST && how->filter != CRH_FILTER_LINEAR) return refuse(kDisplace, "filter is neither CRH_FILTER_NEAREST nor CRH_FILTER_LINEAR");
+    if (how->edge > CRH_BLUR_EDGE_REFLECT) return refuse(kDisplace, "edge is above CRH_BLUR_EDGE_REFLECT");
+    if (!std::isfinite(how->scale[0]) || !std::isfinite(how->scale[1])) return refuse(kDisplace, "a scale is not finite", CRH_ERR_NON_FINITE);
+    if (std::fabs(how->scale[0]) > CRH_MAX_DISPLACE_SCALE || std::fabs(how->scale[1]) > CRH_MAX_DISPLACE_SCALE) return refuse(kDisplace, "a scale is outside [-1024, 1024]");
+    f->k[0] = displace_k(how->scale[0]), f->k[1] = displace_k(how->scale[1]);
+    f->channel[0] = how->x_channel, f->channel[1] = how->y_channel, f->filter = how->filter, f->edge = how->edge;
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_displace_validate(const crh_displace* how) {
+    DisplaceConstants f;
+    return displace_constants(how, &f);
+}
+crh_status crh_displace_offset(const crh_displace* how, uint32_t code_x, uint32_t code_y, int32_t q[2]) {
+    if (!q) return refuse(kDisplace, "a null argument");
+    DisplaceConstants f;
+    const crh_status st = displace_constants(how, &f);
+    if (st != CRH_OK) return st;
+    if (code_x > 255u || code_y > 255u) return refuse(kDisplace, "a code is above 255");
+    q[0] = displace_q(f.k[0], code_x), q[1] = displace_q(f.k[1], code_y);
+    return CRH_OK;
+}
+crh_status crh_displace_texels(uint32_t width, uint32_t height, const void* rgba8, const void* map_rgba8, const crh_displace* how, void* out_rgba8) {
+    if (!rgba8 || !map_rgba8 || !out_rgba8) return refuse(kDisplace, "a null argument");
+    DisplaceConstants f;
+    crh_status st = displace_constants(how, &f);
+    if (st == CRH_OK) st = check_size(kDisplace, width, height);
+    if (st != CRH_OK) return st;
+    if (out_rgba8 == rgba8 || out_rgba8 == map_rgba8) return refuse(kDisplace, "out_rgba8 is rgba8 or map_rgba8");
+    const uint8_t* in = static_cast<const uint8_t*>(rgba8);
+    const uint8_t* map = static_cast<const uint8_t*>(map_rgba8);
+    if (f.filter == kDisplaceLinear) displace_run<kDisplaceLinear>(in, map, width, height, f, static_cast<uint8_t*>(out_rgba8));
+    else displace_run<kDisplaceNearest>(in, map, width, height, f, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_displace(const crh_image* src, const crh_image* map, const crh_displace* how, crh_image** out) {
+    if (!src || !map || !out) return refuse(kDisplace, "a null argument");
+    DisplaceConstants f;
+    crh_status st = displace_constants(how, &f); // (the fields before the images: a refused `how` does not look at them)
+    if (st == CRH_OK && !src->renderer) st = refuse(kDisplace, "a null argument");
+    if (st == CRH_OK) st = check_size(kDisplace, src->width, src->height);
+    if (st != CRH_OK) return st;
+    if (map->width != src->width || map->height != src->height) return refuse(kDisplace, "the map is of another size");
+    if (map->renderer != src->renderer) return refuse(kDisplace, "the images belong to different renderers");
+    return filter_call("crh_image_displace", src->renderer, src->width, src->height, out, [&](FilterJob& job) {
+        job.launch("k_image_displace", [&] { launch_image_displace(texels_of(src), texels_of(map), src->width, src->height, f, job.texels(), job.stream); });
     });
 }

@@ -8,6 +8,7 @@
 // crh_image_convolve: k_image_convolve puts an image through a kernel matrix with the rule of convolve.hpp, a 2-D stencil over a tile and its halo in LDS.
 // crh_image_lighting: k_image_lighting lights the alpha channel as a height field with the rule of lighting.hpp, binary64 arithmetic on a 3 x 3 stencil.
 // crh_image_turbulence: k_image_turbulence makes a noise image with the rule of turbulence.hpp, binary64 arithmetic on gradients gathered from LDS.
+// crh_image_displace: k_image_displace reads an image through per-texel offsets taken from a second one with the rule of displace.hpp, a gather from global memory.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "color_filter.hpp"
 #include "composite.hpp"
 #include "convolve.hpp"
+#include "displace.hpp"
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
@@ -709,6 +711,114 @@ void launch_image_turbulence(const TurbulenceTables* tables, uint32_t w, uint32_
         else CRH_TURBULENCE_LAUNCH(kTurbulenceTurbulence, false);
     }
 #undef CRH_TURBULENCE_LAUNCH
+}
+
+namespace {
+constexpr int kDisplaceTileW = 64; // output columns per workgroup, one per lane of a wave
+constexpr int kDisplaceWaves = 4;  // waves per workgroup
+#ifndef CRH_DISPLACE_ROWS
+#define CRH_DISPLACE_ROWS 4 // (a build with -DCRH_DISPLACE_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the row blocking is measured)
+#endif
+#ifndef CRH_DISPLACE_EDGE_TEMPLATE
+#define CRH_DISPLACE_EDGE_TEMPLATE 0 // (a build with -DCRH_DISPLACE_EDGE_TEMPLATE=1 instantiates the kernel per wrapping edge: DESIGN.md's comparison)
+#endif
+constexpr int kDisplaceRows = CRH_DISPLACE_ROWS;                  // adjacent output rows per lane: their fetches are in flight together
+constexpr int kDisplaceTileH = kDisplaceWaves * kDisplaceRows;   // 16 output rows per workgroup
+constexpr uint32_t kDisplaceRuntimeEdge = 4;                     // EDGE of the kernel that takes its wrapping edge (1..3) from the constants
+
+// One index of a tap against its axis of n texels -> an index the lane may read, and whether the tap is the source's texel there: always
+// under a wrapping edge; under TRANSPARENT the index is clamped and the test says whether the value counts.
+template <bool WRAPPED>
+__device__ __forceinline__ uint32_t displace_index(int i, int n, uint32_t edge, bool* inside) {
+    if (WRAPPED) {
+        *inside = true;
+        return (uint32_t)blur_wrap(i, n, edge);
+    }
+    *inside = (uint32_t)i < (uint32_t)n;
+    return (uint32_t)(i < 0 ? 0 : i >= n ? n - 1 : i);
+}
+} // namespace
+
+// crh_image_displace: a data-dependent gather, bound by the latency of its fetches. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the
+// workgroup produces the tile of 64 x 16 texels at (i0, j0); lane l of wave v the four outputs of column l, tile rows 4 v .. 4 v + 3, so
+// a wave's map load and its store are 256 contiguous bytes per instruction and only the source read is a gather. No halo can be staged:
+// an offset reaches 512 texels either way. A lane works in four steps so that its loads are in flight together: (1) the map texels of
+// its rows; (2) per row the offsets by displace.hpp's rule (the unpremultiply's 256 reciprocals are in LDS, one word staged per lane),
+// the taps, and for each tap a texel index formed ONLY from wrapped (blur_wrap) or clamped indices, with under TRANSPARENT a bit that
+// says whether the tap lies inside; (3) all fetches, 4 per row under LINEAR and 1 under NEAREST — 16 or 4 loads issued before the first
+// is consumed; (4) the taps outside zeroed, the blend, the store. A lane outside the image reads the map's last column or row, computes
+// like any other and does not store. Every index is below w h <= 2^28. EDGE = 0 is TRANSPARENT, 1..3 a wrapping edge as a constant,
+// kDisplaceRuntimeEdge the wrapping edge of the constants (wave-uniform: blur_wrap branches on an SGPR).
+template <uint32_t FILTER, uint32_t EDGE>
+__global__ __launch_bounds__(kDisplaceTileW* kDisplaceWaves) void k_image_displace(const uint32_t* __restrict__ src, const uint32_t* __restrict__ map, uint32_t w, uint32_t h, DisplaceConstants f,
+                                                                                    uint32_t* __restrict__ out) {
+    constexpr int TAPS = FILTER == kDisplaceLinear ? 4 : 1;
+    constexpr bool WRAPPED = EDGE != kDisplaceTransparent;
+    __shared__ uint32_t recip[256];
+    recip[threadIdx.x] = k_unpremultiply.r[threadIdx.x];
+    __syncthreads();
+    const uint32_t edge = EDGE == kDisplaceRuntimeEdge ? f.edge : EDGE;
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t i = blockIdx.x * (uint32_t)kDisplaceTileW + lane;
+    const uint32_t j0 = blockIdx.y * (uint32_t)kDisplaceTileH + wave * (uint32_t)kDisplaceRows;
+    const uint32_t column = i < w ? i : w - 1u;
+    uint32_t m[kDisplaceRows];
+#pragma unroll
+    for (int b = 0; b < kDisplaceRows; ++b) {
+        const uint32_t j = j0 + (uint32_t)b;
+        m[b] = map[(j < h ? j : h - 1u) * w + column];
+    }
+    DisplaceTaps taps[kDisplaceRows];
+    uint32_t at[kDisplaceRows][TAPS], inside[kDisplaceRows];
+#pragma unroll
+    for (int b = 0; b < kDisplaceRows; ++b) {
+        int32_t q[2];
+        displace_offsets(m[b], f, recip, q);
+        taps[b] = displace_taps<FILTER>(displace_position(i, q[0]), displace_position(j0 + (uint32_t)b, q[1]));
+        bool in_x0, in_y0;
+        const uint32_t x0 = displace_index<WRAPPED>(taps[b].i0, (int)w, edge, &in_x0), y0 = displace_index<WRAPPED>(taps[b].j0, (int)h, edge, &in_y0) * w;
+        at[b][0] = y0 + x0, inside[b] = in_x0 && in_y0 ? 1u : 0u;
+        if constexpr (FILTER == kDisplaceLinear) {
+            bool in_x1, in_y1;
+            const uint32_t x1 = displace_index<WRAPPED>(taps[b].i0 + 1, (int)w, edge, &in_x1), y1 = displace_index<WRAPPED>(taps[b].j0 + 1, (int)h, edge, &in_y1) * w;
+            at[b][1] = y0 + x1, at[b][2] = y1 + x0, at[b][3] = y1 + x1;
+            inside[b] |= (in_x1 && in_y0 ? 2u : 0u) | (in_x0 && in_y1 ? 4u : 0u) | (in_x1 && in_y1 ? 8u : 0u);
+        }
+    }
+    uint32_t s[kDisplaceRows][TAPS];
+#pragma unroll
+    for (int b = 0; b < kDisplaceRows; ++b)
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) s[b][t] = src[at[b][t]];
+    if (i >= w) return;
+#pragma unroll
+    for (int b = 0; b < kDisplaceRows; ++b) {
+        const uint32_t j = j0 + (uint32_t)b;
+        if (!WRAPPED) {
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) s[b][t] = (inside[b] >> t) & 1u ? s[b][t] : 0u;
+        }
+        if (j < h) out[j * w + i] = displace_blend<FILTER>(s[b], taps[b]);
+    }
+}
+
+void launch_image_displace(const uint32_t* src, const uint32_t* map, uint32_t w, uint32_t h, const DisplaceConstants& f, uint32_t* out, hipStream_t stream) {
+    const dim3 grid((w + (uint32_t)kDisplaceTileW - 1u) / (uint32_t)kDisplaceTileW, (h + (uint32_t)kDisplaceTileH - 1u) / (uint32_t)kDisplaceTileH); // <= 256 x 1024 with four rows per lane
+    const dim3 block(kDisplaceTileW * kDisplaceWaves);
+#define CRH_DISPLACE_LAUNCH(EDGE)                                                                                                              \
+    do {                                                                                                                                       \
+        if (f.filter == kDisplaceLinear) hipLaunchKernelGGL((k_image_displace<kDisplaceLinear, EDGE>), grid, block, 0, stream, src, map, w, h, f, out); \
+        else hipLaunchKernelGGL((k_image_displace<kDisplaceNearest, EDGE>), grid, block, 0, stream, src, map, w, h, f, out);                    \
+    } while (0)
+    if (f.edge == kDisplaceTransparent) CRH_DISPLACE_LAUNCH(kDisplaceTransparent);
+#if CRH_DISPLACE_EDGE_TEMPLATE
+    else if (f.edge == 1u) CRH_DISPLACE_LAUNCH(1u);
+    else if (f.edge == 2u) CRH_DISPLACE_LAUNCH(2u);
+    else CRH_DISPLACE_LAUNCH(3u);
+#else
+    else CRH_DISPLACE_LAUNCH(kDisplaceRuntimeEdge);
+#endif
+#undef CRH_DISPLACE_LAUNCH
 }
 
 } // namespace crh

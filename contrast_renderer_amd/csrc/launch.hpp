@@ -65,6 +65,9 @@ void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const Li
 struct TurbulenceTables;
 struct TurbulenceConstants;
 void launch_image_turbulence(const TurbulenceTables* tables, uint32_t w, uint32_t h, const TurbulenceConstants& f, uint32_t kind, bool opaque, uint32_t* out, hipStream_t stream);
+// image_filter.hip: crh_image_displace's kernel (displace.hpp holds the rule; f.filter < 2, f.edge < 4, f.channel < 4). src, map and out: h rows of w texels; out is neither input.
+struct DisplaceConstants;
+void launch_image_displace(const uint32_t* src, const uint32_t* map, uint32_t w, uint32_t h, const DisplaceConstants& f, uint32_t* out, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream); // zeroes n_words 32-bit words with single-wave workgroups (the clear in front of both passes' binning kernels)

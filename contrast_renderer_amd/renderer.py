@@ -741,6 +741,49 @@ def turbulence_tables(seed):
     return lattice, gradient
 
 
+class Channel(IntEnum):  # crh_channel: the channel of a displacement map that moves an axis
+    R = 0
+    G = 1
+    B = 2
+    A = 3
+
+
+MAX_DISPLACE_SCALE = 1024.0  # CRH_MAX_DISPLACE_SCALE
+
+
+def _displace_arguments(scale, x_channel, y_channel, filter, edge):
+    """-> DisplaceC; a scalar scale serves both axes (SVG has one)"""
+    sx, sy = (scale, scale) if np.isscalar(scale) else scale
+    how = _ffi.DisplaceC()
+    how.scale = (C.c_float * 2)(float(sx), float(sy))
+    how.x_channel, how.y_channel, how.filter, how.edge = int(x_channel), int(y_channel), int(filter), int(edge)
+    return how
+
+
+def displace_texels(pixels, map, scale, x_channel=Channel.A, y_channel=Channel.A, filter=Filter.Linear, edge=BlurEdge.Transparent):
+    """crh_displace_texels (host only): the rule of Image.displace on two (height, width, 4) uint8 arrays of one size, the source and the
+    map -> a (height, width, 4) uint8 array (include/contrast_hip.h crh_image_displace states the rule)."""
+    pixels, map = np.ascontiguousarray(pixels), np.ascontiguousarray(map)
+    for a in (pixels, map):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"displace_texels takes (height, width, 4) uint8 arrays, not {a.shape} {a.dtype}")
+    if pixels.shape != map.shape:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"displace_texels takes a map of the source's size, not {map.shape} beside {pixels.shape}")
+    how = _displace_arguments(scale, x_channel, y_channel, filter, edge)
+    out = np.empty_like(pixels)
+    check(_ffi.load_library().crh_displace_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, map.ctypes.data, C.byref(how), out.ctypes.data))
+    return out
+
+
+def displace_offset(scale, code_x, code_y, x_channel=Channel.A, y_channel=Channel.A, filter=Filter.Linear, edge=BlurEdge.Transparent):
+    """crh_displace_offset (host only) -> (qx, qy): the offsets, in 1/256 texel, that the straight map codes `code_x` and `code_y` (each
+    <= 255) give under `scale`."""
+    how = _displace_arguments(scale, x_channel, y_channel, filter, edge)
+    q = (C.c_int32 * 2)()
+    check(_ffi.load_library().crh_displace_offset(C.byref(how), int(code_x), int(code_y), q))
+    return int(q[0]), int(q[1])
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -908,6 +951,18 @@ class Image:
     def specular_lighting(self, light, surface_scale=1.0, constant=1.0, specular_exponent=1.0, color=(1.0, 1.0, 1.0), edge=BlurEdge.Pad):
         """lighting(light, LightingOp.Specular, ...): SVG feSpecularLighting."""
         return self.lighting(light, LightingOp.Specular, surface_scale, constant, specular_exponent, color, edge)
+
+    def displace(self, map, scale, x_channel=Channel.A, y_channel=Channel.A, filter=Filter.Linear, edge=BlurEdge.Transparent):
+        """crh_image_displace -> a new Image of one level, of this image's size, origin (0, 0): this image read through the per-texel offsets
+        of `map`, an Image of the same size and renderer (SVG feDisplacementMap; Image.turbulence makes the usual map), integer and
+        bit-exact, built on the device and complete when this returns (a synchronous call). A map texel moves its texel by
+        scale * (u / 255 - 1/2) texels on each axis, u = the straight code of `x_channel` / `y_channel`; a scalar `scale` serves both
+        axes, each |.| <= MAX_DISPLACE_SCALE. `filter` is Filter.Nearest or Filter.Linear, `edge` what THIS image is outside itself.
+        The defaults are SVG's. Neither image is modified."""
+        how = _displace_arguments(scale, x_channel, y_channel, filter, edge)
+        handle = C.c_void_p()
+        check(self.lib.crh_image_displace(self.handle, map.handle, C.byref(how), C.byref(handle)))
+        return Image._adopt(self.renderer, handle, (self.width, self.height))
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

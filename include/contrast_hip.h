@@ -873,6 +873,57 @@ crh_status crh_turbulence_validate(const crh_turbulence* how);                  
 crh_status crh_turbulence_tables(int32_t seed, uint8_t lattice[256], double gradient[4 * 256 * 2]);   /* host only: gradient[(k*256 + i)*2 + c] */
 crh_status crh_turbulence_texels(uint32_t width, uint32_t height, const crh_turbulence* how, void* out_rgba8); /* host only */
 crh_status crh_image_turbulence(crh_renderer* renderer, uint32_t width, uint32_t height, const crh_turbulence* how, crh_image** out);
+/* Displacement: a new image that reads `src` through a per-texel offset taken from a second image, the map (SVG feDisplacementMap) —
+ * water, heat haze, torn edges, wobbly text, a frosted backdrop from a blurred snapshot; crh_image_turbulence makes the usual map. All
+ * values are 8-bit codes, everything is integer and bit-exact, and the tests check every byte.
+ *   size      src and map have one size (w, h); the result has that size, one level, origin (0, 0), and belongs to the source's renderer.
+ *   map code  the map texel (i, j) is loaded as the colour filter loads a texel: c = min(c, a). A colour channel gives the straight code
+ *             u = (255 c + a / 2) / a, and 0 for a = 0; CRH_CHANNEL_A gives u = a. ux comes from x_channel, uy from y_channel.
+ *   offset    per axis, in units of 1/256 texel: K = (int32) floor((double) scale * 256 + 0.5), so |K| <= 2^18; n = K (2 u - 255), so
+ *             |n| < 2^26; q = floor((n + 255) / 510), a true floor, also for negative n: scale (u / 255 - 1/2) rounded half up,
+ *             |q| <= 2^17.
+ *   position  X = 256 i + 128 + qx and Y = 256 j + 128 + qy, both below 2^23 in magnitude.
+ *   NEAREST   the value is S(X >> 8, Y >> 8), with arithmetic shifts.
+ *   LINEAR    ax = X - 128, i0 = ax >> 8, fx = ax & 255, the y axis the same. Per channel top = S(i0, j0) (256 - fx) + S(i0 + 1, j0) fx,
+ *             bottom the same with j0 + 1; value = (top (256 - fy) + bottom fy + 32768) >> 16: one rounding, the largest numerator is
+ *             16 744 448 < 2^24.
+ *   S(i, j)   the source's codes as they are, with no load clamp, as morphology reads them. Under PAD, REPEAT and REFLECT each index
+ *             goes separately through the image-paint block's wrap(i, n); the index may lie any number of periods out: 513 texels
+ *             beyond a 1-texel axis. Under TRANSPARENT the value is (0, 0, 0, 0) when either index is outside. Every address is formed
+ *             from wrapped or tested indices only: no map value reads outside the source.
+ * Hence: scales (0, 0) give a byte-for-byte copy under both filters and every edge, and a zero scale on one axis leaves that axis
+ * exactly unmoved; equal texels come back exactly; rgb <= a survives (the weights are shared and the rounding is monotone); scale 510
+ * gives q = 256 (2 u - 255) exactly, so each texel reads the source 2 u - 255 whole texels away, both filters agree and the result is
+ * S(i + 2 ux - 255, j + 2 uy - 255); a constant map whose q is a multiple of 256 is a translation, under TRANSPARENT byte for byte
+ * crh_image_composite's COPY of the source onto a transparent backdrop of the same size at offset (-qx / 256, -qy / 256); as in SVG no
+ * code gives a zero offset: u = 127 gives -scale / 510, u = 128 gives +scale / 510, and a transparent map texel has u = 0 and moves by
+ * -scale / 2; q is within 3/4 of a 1/256 texel of the real scale (u / 255 - 1/2) * 256: 1/2 from the rounding plus 1/4 from K.
+ * crh_displace_validate, crh_displace_offset (the q of two straight codes <= 255, as crh_blur_taps hands out taps; a code above 255 is
+ * CRH_ERR_INVALID_ARGUMENT) and crh_displace_texels (the rule on whole images in host memory, width * height * 4 bytes each in the
+ * order r g b a at any alignment, row 0 first) are host only: no renderer, no device.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out untouched: first a null argument
+ * is CRH_ERR_INVALID_ARGUMENT; then a channel above CRH_CHANNEL_A, a filter other than CRH_FILTER_NEAREST or CRH_FILTER_LINEAR (the
+ * MIPMAP flag is refused) and an edge above CRH_BLUR_EDGE_REFLECT are CRH_ERR_INVALID_ARGUMENT; then a non-finite scale is
+ * CRH_ERR_NON_FINITE; then, in this order, a |scale| above CRH_MAX_DISPLACE_SCALE, a size outside [1, 16384], a map of another size,
+ * images of different renderers, and in crh_displace_texels an out_rgba8 equal to either input are CRH_ERR_INVALID_ARGUMENT, each with a
+ * crh_last_error text "crh_displace_validate: ...".
+ * crh_image_displace runs k_image_displace on the renderer's stream, specialised on the filter and on TRANSPARENT against the wrapping
+ * edges; it allocates nothing but the result. A failed allocation or launch frees everything and returns CRH_ERR_HIP.
+ * Limits: the call is synchronous, like its siblings; map and source must have one size — composite onto a backdrop first if they do
+ * not; the footprint is a point or a 2 x 2 bilinear one, so strong local compression of the map aliases; the map is used in its own
+ * codes, with no colour-space handling; this is not a per-draw effect of the raster path. */
+typedef enum crh_channel { CRH_CHANNEL_R = 0, CRH_CHANNEL_G = 1, CRH_CHANNEL_B = 2, CRH_CHANNEL_A = 3 } crh_channel;
+#define CRH_MAX_DISPLACE_SCALE 1024.0f
+typedef struct crh_displace {
+    float scale[2];                 /* x and y; finite, |.| <= CRH_MAX_DISPLACE_SCALE (SVG has one scale: give it twice) */
+    uint32_t x_channel, y_channel;  /* crh_channel of the map that moves x, and y */
+    uint32_t filter;                /* CRH_FILTER_NEAREST or CRH_FILTER_LINEAR (the MIPMAP flag is refused) */
+    uint32_t edge;                  /* crh_blur_edge: what the SOURCE is outside itself */
+} crh_displace;
+crh_status crh_displace_validate(const crh_displace* how);                                             /* host only */
+crh_status crh_displace_offset(const crh_displace* how, uint32_t code_x, uint32_t code_y, int32_t q[2]); /* host only: q of two straight codes <= 255 */
+crh_status crh_displace_texels(uint32_t width, uint32_t height, const void* rgba8, const void* map_rgba8, const crh_displace* how, void* out_rgba8); /* host only */
+crh_status crh_image_displace(const crh_image* src, const crh_image* map, const crh_displace* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

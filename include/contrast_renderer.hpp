@@ -824,6 +824,37 @@ inline TurbulenceTables turbulence_tables(int32_t seed) {
     check(crh_turbulence_tables(seed, tables.lattice.data(), tables.gradient.data()));
     return tables;
 }
+// Displacement (include/contrast_hip.h crh_image_displace states the rule): an image read through the per-texel offsets of a second one, SVG feDisplacementMap.
+enum class Channel : uint32_t { R = CRH_CHANNEL_R, G = CRH_CHANNEL_G, B = CRH_CHANNEL_B, A = CRH_CHANNEL_A };
+// The fields of crh_displace: the scale of each axis in texels (SVG has one: give it twice), the map's channels that move x and y, the
+// filter (Nearest or Linear) and what the SOURCE is outside itself. The defaults are SVG's.
+struct Displace {
+    std::array<float, 2> scale = {0.0f, 0.0f};
+    Channel x_channel = Channel::A, y_channel = Channel::A;
+    Filter filter = Filter::Linear;
+    BlurEdge edge = BlurEdge::Transparent;
+    crh_displace to_c() const {
+        crh_displace how = {};
+        how.scale[0] = scale[0], how.scale[1] = scale[1];
+        how.x_channel = (uint32_t)x_channel, how.y_channel = (uint32_t)y_channel, how.filter = (uint32_t)filter, how.edge = (uint32_t)edge;
+        return how;
+    }
+};
+// crh_displace_texels (host only): the rule on two width * height * 4 byte arrays, the source and the map -> the bytes of the result
+inline std::vector<uint8_t> displace_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, const std::vector<uint8_t>& map, const Displace& displace) {
+    if (texels.size() != (size_t)width * height * 4u || map.size() != texels.size()) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const crh_displace how = displace.to_c();
+    std::vector<uint8_t> out(texels.size());
+    check(crh_displace_texels(width, height, texels.data(), map.data(), &how, out.data()));
+    return out;
+}
+// crh_displace_offset (host only): the offsets (qx, qy), in 1/256 texel, of two straight map codes <= 255
+inline std::array<int32_t, 2> displace_offset(const Displace& displace, uint32_t code_x, uint32_t code_y) {
+    const crh_displace how = displace.to_c();
+    std::array<int32_t, 2> q = {0, 0};
+    check(crh_displace_offset(&how, code_x, code_y, q.data()));
+    return q;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -939,6 +970,15 @@ class Image {
         Image image;
         check(crh_image_lighting(handle_, &how, &image.handle_));
         image.width_ = width_, image.height_ = height_, image.origin_ = origin_;
+        return image;
+    }
+    // crh_image_displace -> a new Image of one level, of this image's size, origin (0, 0): this image read through the per-texel offsets of
+    // `map`, an image of the same size and renderer; integer and bit-exact, complete on return (a synchronous call). Neither image is modified.
+    Image displace(const Image& map, const Displace& displace) const {
+        const crh_displace how = displace.to_c();
+        Image image;
+        check(crh_image_displace(handle_, map.handle_, &how, &image.handle_));
+        image.width_ = width_, image.height_ = height_;
         return image;
     }
     template <class Light>

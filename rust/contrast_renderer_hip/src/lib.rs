@@ -1065,6 +1065,56 @@ pub fn turbulence_texels(width: u32, height: u32, turbulence: &Turbulence) -> Re
     status(unsafe { ffi::crh_turbulence_texels(width, height, &how, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// `crh_channel`: the channel of a displacement map that moves an axis
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Channel {
+    R = 0,
+    G = 1,
+    B = 2,
+    A = 3,
+}
+/// The fields of `crh_displace` (include/contrast_hip.h, `crh_image_displace`, states the rule): the scale of each axis in texels (SVG has
+/// one: give it twice), the map's channels that move x and y, the filter (`Nearest` or `Linear`) and what the SOURCE is outside itself.
+/// The defaults are SVG's.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct Displace {
+    pub scale: [f32; 2],
+    pub x_channel: Channel,
+    pub y_channel: Channel,
+    pub filter: Filter,
+    pub edge: BlurEdge,
+}
+impl Default for Displace {
+    fn default() -> Displace {
+        Displace { scale: [0.0; 2], x_channel: Channel::A, y_channel: Channel::A, filter: Filter::Linear, edge: BlurEdge::Transparent }
+    }
+}
+impl Displace {
+    fn to_c(&self) -> ffi::crh_displace {
+        ffi::crh_displace { scale: self.scale, x_channel: self.x_channel as u32, y_channel: self.y_channel as u32, filter: self.filter as u32, edge: self.edge as u32 }
+    }
+}
+/// `crh_displace_validate` (host only): what `Image::displace` would refuse of the fields
+pub fn displace_validate(displace: &Displace) -> Result<(), Error> {
+    let how = displace.to_c();
+    status(unsafe { ffi::crh_displace_validate(&how) })
+}
+/// `crh_displace_offset` (host only) -> the offsets (qx, qy), in 1/256 texel, of two straight map codes <= 255
+pub fn displace_offset(displace: &Displace, code_x: u32, code_y: u32) -> Result<[i32; 2], Error> {
+    let how = displace.to_c();
+    let mut q = [0i32; 2];
+    status(unsafe { ffi::crh_displace_offset(&how, code_x, code_y, q.as_mut_ptr()) })?;
+    Ok(q)
+}
+/// `crh_displace_texels` (host only): the rule on two width * height * 4 byte slices, the source and the map -> the bytes of the result
+pub fn displace_texels(width: u32, height: u32, texels: &[u8], map: &[u8], displace: &Displace) -> Result<Vec<u8>, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    assert_eq!(map.len(), texels.len());
+    let how = displace.to_c();
+    let mut out = vec![0u8; texels.len()];
+    status(unsafe { ffi::crh_displace_texels(width, height, texels.as_ptr() as *const _, map.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -1180,6 +1230,15 @@ impl Image {
         let mut raw = ptr::null_mut();
         status(unsafe { ffi::crh_image_convolve(self.raw, &how, &mut raw) })?;
         Ok(Image { raw, width: self.width, height: self.height, origin: self.origin })
+    }
+    /// `crh_image_displace` -> a new `Image` of one level, of this image's size, origin (0, 0): this image read through the per-texel
+    /// offsets of `map`, an image of the same size and renderer (SVG feDisplacementMap); integer and bit-exact, complete on return (a
+    /// synchronous call). Neither image is modified.
+    pub fn displace(&self, map: &Image, displace: &Displace) -> Result<Image, Error> {
+        let how = displace.to_c();
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_displace(self.raw, map.raw, &how, &mut raw) })?;
+        Ok(Image { raw, width: self.width, height: self.height, origin: (0, 0) })
     }
     /// `crh_image_lighting` -> a new `Image` of one level, of this image's size and origin: this image's alpha as a height field lit by
     /// `light`; binary64 arithmetic in a fixed order, complete on return (a synchronous call). Diffuse results are opaque (MULTIPLY them onto
