@@ -958,7 +958,7 @@ class Image:
         bit-exact, built on the device and complete when this returns (a synchronous call). A map texel moves its texel by
         scale * (u / 255 - 1/2) texels on each axis, u = the straight code of `x_channel` / `y_channel`; a scalar `scale` serves both
         axes, each |.| <= MAX_DISPLACE_SCALE. `filter` is Filter.Nearest or Filter.Linear, `edge` what THIS image is outside itself.
-        The defaults are SVG's. Neither image is modified."""
+        The defaults are SVG's. Neither image is modified; the map may be this image."""
         how = _displace_arguments(scale, x_channel, y_channel, filter, edge)
         handle = C.c_void_p()
         check(self.lib.crh_image_displace(self.handle, map.handle, C.byref(how), C.byref(handle)))

@@ -877,6 +877,7 @@ crh_status crh_image_turbulence(crh_renderer* renderer, uint32_t width, uint32_t
  * water, heat haze, torn edges, wobbly text, a frosted backdrop from a blurred snapshot; crh_image_turbulence makes the usual map. All
  * values are 8-bit codes, everything is integer and bit-exact, and the tests check every byte.
  *   size      src and map have one size (w, h); the result has that size, one level, origin (0, 0), and belongs to the source's renderer.
+ *             Neither image is modified, and the map may be the source itself: map == src is legal.
  *   map code  the map texel (i, j) is loaded as the colour filter loads a texel: c = min(c, a). A colour channel gives the straight code
  *             u = (255 c + a / 2) / a, and 0 for a = 0; CRH_CHANNEL_A gives u = a. ux comes from x_channel, uy from y_channel.
  *   offset    per axis, in units of 1/256 texel: K = (int32) floor((double) scale * 256 + 0.5), so |K| <= 2^18; n = K (2 u - 255), so

@@ -1,8 +1,9 @@
 """The generator and the host model of the stateful image and layer fuzz (tests/test_gpu_layers_fuzz.py): random sequences over one Renderer,
 two frames (RGBA8 and RGBA8_ATTACHMENT), a pool of images, a solid Scene and a blit Scene per frame — images created, snapshot from frames,
-blurred, composited, colour filtered, mipmapped, loaded back into frames, drawn as image paints through tables that outlive their images,
-between clears, uploads, plain passes and re-uploads of the solid Scene. Every image operation has an integer model (blur_model,
-composite_model, color_filter_model, mip_model) and every pass an exact expectation (the oracle for the solid Scene, the image's own bytes for
+made of noise, blurred, composited, colour filtered, eroded and dilated, convolved, lit, displaced, mipmapped, loaded back into frames, drawn
+as image paints through tables that outlive their images, between clears, uploads, plain passes and re-uploads of the solid Scene. Every
+image operation has an exact model (blur_model, composite_model, color_filter_model, morphology_model, convolve_model, lighting_model,
+turbulence_model, displace_model, mip_model) and every pass an exact expectation (the oracle for the solid Scene, the image's own bytes for
 an identity blit), so every check is of bytes. No GPU and no library call in here: the oracle alone."""
 import numpy as np
 
@@ -11,17 +12,32 @@ from contrast_renderer_amd import scenes
 import blur_model as BM
 import color_filter_model as FM
 import composite_model as CM
+import convolve_model as CV
+import displace_model as DM
+import lighting_model as LM
 import mip_model as MM
+import morphology_model as MO
+import turbulence_model as TM
 
 FORMATS = (0, 2)  # FORMAT_RGBA8, FORMAT_RGBA8_ATTACHMENT: frame 0 and frame 1
 MAX_POOL = 8
-MAX_SIDE = 300  # a TRANSPARENT blur is given another edge when it would grow an image beyond this (the sigma-64 blur apart)
+MAX_SIDE = 300  # a TRANSPARENT blur or dilate is given another edge when it would grow an image beyond this (the sigma-64 blur and the one radius above 64 apart)
 SIGMAS = (0.0, 0.01, 0.3, 1.0, 2.5, 6.0)
 NEAREST, LINEAR, MIPMAP = 0, 1, 0x100
 STENCIL, COLOR = 0, 3  # RenderOperation.Stencil, RenderOperation.Color
 KINDS = ("create", "snapshot", "blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image", "clear", "solid", "upload", "load_image",
-         "download", "set_table", "replace_table", "clear_table", "blit", "blit_mip", "white_paint", "reupload")
-WEIGHTS = (0.06, 0.07, 0.11, 0.09, 0.08, 0.04, 0.08, 0.04, 0.01, 0.09, 0.06, 0.05, 0.06, 0.03, 0.05, 0.04, 0.06, 0.03, 0.03, 0.03)
+         "download", "set_table", "replace_table", "clear_table", "blit", "blit_mip", "white_paint", "reupload",
+         "morphology", "convolve", "lighting", "turbulence", "displace")
+WEIGHTS = (0.06, 0.07, 0.11, 0.09, 0.08, 0.04, 0.08, 0.04, 0.01, 0.09, 0.06, 0.05, 0.06, 0.03, 0.05, 0.04, 0.06, 0.03, 0.03, 0.03,
+           0.10, 0.07, 0.07, 0.04, 0.09)
+NEW = ("morphology", "convolve", "lighting", "turbulence", "displace")  # the filters that came after the fuzz was written
+READS = ("blur", "composite", "color_filter", "check_image", "load_image", "set_table", "replace_table", "blit_mip") + tuple(k for k in NEW if k != "turbulence")
+GROWN_DILATE = "grown dilate"  # beside the kinds in an image's `via`: a DILATE under TRANSPARENT with a non-zero radius is behind it
+# every route of crh_image_morphology and every instantiation of k_image_morph_v: 0 skips an axis's pass ((0, 0) is the copy), and a vertical
+# window 2 radius + 1 of at most 33, at most 129 and above selects one of the three
+RADII = (0, 1, 2, 5, 16, 17, 64, 65, 192)
+ROUTES = ("copy", "horizontal", "vertical", "both")
+DISPLACE_SCALES = ((0.0, 0.0), (1024.0, 1024.0), (-1024.0, -1024.0), (1024.0, -1024.0), (-1024.0, 333.25), (0.0, 37.5), (-20.0, 20.0), (3.25, -7.5), (510.0, 510.0), (0.3, 64.0))
 
 
 def master_case(seed):
@@ -72,6 +88,35 @@ def step_color_filter(pixels, matrix, tables):
     return FM.texels(pixels, matrix, tables)
 
 
+def step_morphology(pixels, op, radius, edge):
+    return MO.morphology(pixels, op, radius[0], radius[1], edge)
+
+
+def step_convolve(pixels, kernel, divisor, bias, target, edge, preserve_alpha):
+    return CV.convolve(pixels, kernel, divisor, bias, target, edge, preserve_alpha)
+
+
+def step_lighting(pixels, light, op, surface_scale, constant, specular_exponent, color, edge):
+    """light: the keyword arguments of lighting_model.Light"""
+    return LM.lighting(pixels, LM.Light(**light), op, surface_scale, constant, specular_exponent, color, edge)
+
+
+def step_turbulence(size, frequency, octaves, seed, noise, stitch, opaque, offset):
+    return TM.turbulence(size[0], size[1], tuple(frequency), octaves, seed, noise, stitch, opaque, tuple(offset))
+
+
+def step_displace(pixels, map, scale, channels, filter, edge):
+    return DM.displace(pixels, map, tuple(scale), channels[0], channels[1], filter, edge)
+
+
+def morphology_route(radius):
+    return ROUTES[int(radius[0] > 0) + 2 * int(radius[1] > 0)]
+
+
+def f32(v):
+    return float(np.float32(v))
+
+
 class Model:
     """What every frame and every pool image must hold. apply(op) -> the arrays the device's answers to the op are compared with (empty for
     an op that checks nothing)."""
@@ -83,10 +128,23 @@ class Model:
         self.oracle = Oracle(self.batch) if oracle is None else oracle
         w, h = setup["width"], setup["height"]
         self.frame = [dict(image=np.zeros((h, w, 4), np.uint8), cleared=True, last="clear") for _ in FORMATS]
-        self.pool = []  # dict(pixels, mip, depth): depth = the device operations behind the image
-        self.table = [None, None]  # of the blit Scene of each frame: dict(pixels, filter, destroyed, index)
+        # dict(pixels, mip, depth, origin, by, via): depth = the device operations behind the image, origin = what Image.origin must be, by = the
+        # kind that made it, via = the kinds in its history (and GROWN_DILATE)
+        self.pool = []
+        self.table = [None, None]  # of the blit Scene of each frame: dict(pixels, filter, destroyed, index, via)
         self.slice = tuple(setup["slice"])
         self.instances = None
+
+    def add(self, pixels, by, inputs=(), origin=(0, 0), mark=()):
+        """A new pool image made by `by` from the pool entries `inputs`. The origin follows the Image docstrings: blur and dilate set it, the
+        colour filter, convolve and lighting inherit it (the caller passes the source's), everything else has (0, 0)."""
+        via = frozenset((by,) + tuple(mark)).union(*[e["via"] for e in inputs])
+        depth = max([e["depth"] for e in inputs], default=0) + int(by != "create")
+        self.pool.append(dict(pixels=pixels, mip=False, depth=depth, origin=tuple(int(v) for v in origin), by=by, via=via))
+
+    def name(self, j, index, filter):
+        e = self.pool[index]
+        self.table[j] = dict(pixels=e["pixels"], filter=filter, destroyed=False, index=index, via=e["via"])
 
     # ---- passes
     def solid_pass(self, j, instances):
@@ -109,23 +167,42 @@ class Model:
     def apply(self, op):
         kind = op["kind"]
         if kind == "create":
-            self.pool.append(dict(pixels=op["pixels"], mip=False, depth=0))
+            self.add(op["pixels"], kind)
         elif kind == "snapshot":
-            self.pool.append(dict(pixels=self.frame[op["frame"]]["image"].copy(), mip=False, depth=1))
+            self.add(self.frame[op["frame"]]["image"].copy(), kind)
         elif kind == "blur":
             src = self.pool[op["image"]]
-            self.pool.append(dict(pixels=step_blur(src["pixels"], op["sigma"][0], op["sigma"][1], op["edge"]), mip=False, depth=src["depth"] + 1))
+            grown = op["edge"] == BM.TRANSPARENT
+            self.add(step_blur(src["pixels"], op["sigma"][0], op["sigma"][1], op["edge"]), kind, [src],
+                     (BM.radius_of(op["sigma"][0]), BM.radius_of(op["sigma"][1])) if grown else (0, 0))
         elif kind == "composite":
             back, src = self.pool[op["image"]], self.pool[op["source"]]
-            self.pool.append(dict(pixels=step_composite(back["pixels"], src["pixels"], op["op"], op["mode"], op["opacity"], op["offset"]), mip=False,
-                                  depth=max(back["depth"], src["depth"]) + 1))
+            self.add(step_composite(back["pixels"], src["pixels"], op["op"], op["mode"], op["opacity"], op["offset"]), kind, [back, src])
         elif kind == "color_filter":
             src = self.pool[op["image"]]
-            self.pool.append(dict(pixels=step_color_filter(src["pixels"], op["matrix"], op["tables"]), mip=False, depth=src["depth"] + 1))
+            self.add(step_color_filter(src["pixels"], op["matrix"], op["tables"]), kind, [src], src["origin"])
+        elif kind == "morphology":
+            src = self.pool[op["image"]]
+            grown = MO.grows(op["op"], op["edge"])
+            self.add(step_morphology(src["pixels"], op["op"], op["radius"], op["edge"]), kind, [src], op["radius"] if grown else (0, 0),
+                     (GROWN_DILATE,) if grown and max(op["radius"]) > 0 else ())
+        elif kind == "convolve":
+            src = self.pool[op["image"]]
+            self.add(step_convolve(src["pixels"], op["kernel"], op["divisor"], op["bias"], op["target"], op["edge"], op["preserve_alpha"]), kind, [src], src["origin"])
+        elif kind == "lighting":
+            src = self.pool[op["image"]]
+            self.add(step_lighting(src["pixels"], op["light"], op["op"], op["surface_scale"], op["constant"], op["specular_exponent"], op["color"], op["edge"]), kind, [src],
+                     src["origin"])
+        elif kind == "turbulence":
+            self.add(step_turbulence(op["size"], op["frequency"], op["octaves"], op["seed"], op["noise"], op["stitch"], op["opaque"], op["offset"]), kind)
+        elif kind == "displace":
+            src, map = self.pool[op["image"]], self.pool[op["map"]]
+            self.add(step_displace(src["pixels"], map["pixels"], op["scale"], op["channels"], op["filter"], op["edge"]), kind, [src, map])
         elif kind == "mipmaps":
             self.pool[op["image"]]["mip"] = True
         elif kind == "check_image":
             e = self.pool[op["image"]]
+            assert op["origin"] == e["origin"]
             return MM.chain(e["pixels"]) if e["mip"] else [e["pixels"]]
         elif kind == "destroy_image":
             self.pool.pop(op["image"])
@@ -147,14 +224,14 @@ class Model:
         elif kind == "download":
             return [self.frame[op["frame"]]["image"]]
         elif kind in ("set_table", "replace_table"):
-            self.table[op["frame"]] = dict(pixels=self.pool[op["image"]]["pixels"], filter=op["filter"], destroyed=False, index=op["image"])
+            self.name(op["frame"], op["image"], op["filter"])
         elif kind == "clear_table":
             self.table[op["frame"]] = None
         elif kind == "blit":
             self.blit(op["frame"])
         elif kind == "blit_mip":
             assert self.pool[op["image"]]["mip"]
-            self.table[op["frame"]] = dict(pixels=self.pool[op["image"]]["pixels"], filter=op["filter"], destroyed=False, index=op["image"])
+            self.name(op["frame"], op["image"], op["filter"])
             self.blit(op["frame"])
         elif kind == "white_paint":  # a white image paint is the solid colour, byte for byte; the table is cleared behind the pass
             f = self.frame[op["frame"]]
@@ -228,14 +305,45 @@ def generate(seed):
     setup = dict(seed=seed, width=width, height=height, msaa=int(rng.choice([1, 4])), slice=new_slice())
     model = Model(setup, sc["batch"])
     ops = []
-    big_blur_left = 1
+    big_blur_left = big_morphology_left = heavy_convolve_left = 1
 
     def emit(op):
+        """Every op that reads pool images also says what they were when it ran: `by` and `straight` per image, in the order image, source,
+        map; the union of their `via`; the largest depth; whether the first has mipmaps. The conditions of test_layers_model_cpu.py read these."""
+        if op["kind"] in READS:
+            used = [model.pool[op[k]] for k in ("image", "source", "map") if k in op]
+            op.update(by=tuple(e["by"] for e in used), straight=tuple(not premultiplied(e["pixels"]) for e in used), via=tuple(sorted(frozenset().union(*[e["via"] for e in used]))),
+                      depth=max(e["depth"] for e in used), mip=used[0]["mip"])
+            if op["kind"] == "check_image":
+                op["origin"] = used[0]["origin"]
         model.apply(op)
         ops.append(op)
 
     def pick(indices):
         return indices[int(rng.randint(0, len(indices)))]
+
+    def a_source(prefer_wide=False):
+        """The input of one of the newer filters: mostly any pool image; an image wider than 256, the segment of k_image_morph_h, where asked;
+        often one that device operations made, and now and then one that has, or now gets, a mip chain (the filter must read level 0)."""
+        pool = model.pool
+        wide = [k for k, e in enumerate(pool) if e["pixels"].shape[1] > 256] if prefer_wide else []
+        deep = [k for k, e in enumerate(pool) if e["depth"] >= 2]
+        straight = [k for k, e in enumerate(pool) if not premultiplied(e["pixels"])]  # colours above their alpha: few images have them, so they are sought
+        how = rng.uniform()
+        i = pick(straight) if straight and how < 0.15 else pick(wide) if wide and how < 0.8 else pick(deep) if deep and how < 0.9 and rng.uniform() < 0.5 else int(rng.randint(0, len(pool)))
+        if not pool[i]["mip"] and rng.uniform() < 0.08:
+            emit(dict(kind="mipmaps", image=i))
+        return i
+
+    def after_filter(i, kind):
+        """Now and then the source is destroyed right behind the call that read it."""
+        if rng.uniform() < 0.12:
+            emit(dict(kind="destroy_image", image=i, behind=kind))
+
+    def newer(indices):
+        """Of the images a frame may show, often one that one of the newer filters is behind."""
+        made = [i for i in indices if model.pool[i]["via"].intersection(NEW)]
+        return pick(made) if made and rng.uniform() < 0.5 else pick(indices)
 
     def frame_sized(extra=lambda e: True):
         return [i for i, e in enumerate(model.pool) if e["pixels"].shape[:2] == (height, width) and extra(e)]
@@ -245,8 +353,8 @@ def generate(seed):
         over = not model.frame[j]["cleared"]
         return frame_sized(lambda e: premultiplied(e["pixels"]) and (not over or binary_alpha(e["pixels"])))
 
-    def room():
-        while len(model.pool) >= MAX_POOL:
+    def room(n=1):
+        while len(model.pool) > MAX_POOL - n:
             emit(dict(kind="destroy_image", image=int(rng.randint(0, len(model.pool)))))
 
     def white_image():
@@ -262,14 +370,21 @@ def generate(seed):
     def a_filter():
         return int(rng.choice([NEAREST, LINEAR])) if setup["msaa"] == 1 else NEAREST  # (a LINEAR sample off the pixel centre mixes texels)
 
-    n_steps = int(rng.randint(40, 61))
+    def turbulence_op(size):
+        """Noise of a size: mostly a few lattice cells across the image, now and then a frequency of 0 (a constant axis) or up to the limit, 4."""
+        frequency = [0.0 if t < 0.1 else f32(rng.uniform(0.3, 4.0)) if t < 0.25 else f32(rng.uniform(0.01, 0.3)) for t in rng.uniform(size=2)]
+        return dict(kind="turbulence", size=[int(size[0]), int(size[1])], frequency=frequency, octaves=int(rng.randint(0, 5)), seed=int(rng.randint(-100000, 100000)),
+                    noise=int(rng.randint(0, 2)), stitch=bool(rng.randint(0, 2)), opaque=bool(rng.randint(0, 2)),
+                    offset=[0.0, 0.0] if rng.uniform() < 0.3 else [f32(v) for v in rng.uniform(-100, 100, 2)])
+
+    n_steps = int(rng.randint(80, 116))
     emit(dict(kind="upload", frame=0, pixels=BM.random_premultiplied(rng, width, height)))  # (the frames show something from the start)
     emit(instances_for(dict(kind="solid", frame=1)))
     while len(ops) < n_steps:
         kind = KINDS[int(rng.choice(len(KINDS), p=np.float64(WEIGHTS) / np.sum(WEIGHTS)))]
         j = int(rng.randint(0, 2))
         pool = model.pool
-        if kind == "create" or (not pool and kind in ("blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image")):
+        if kind == "create" or (not pool and kind in ("blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image", "morphology", "convolve", "lighting", "displace")):
             room()
             w, h = (width, height) if rng.uniform() < 0.5 else (int(rng.randint(1, 41)), int(rng.randint(1, 31)))
             how = TEXELS[int(rng.randint(0, len(TEXELS)))]
@@ -319,6 +434,80 @@ def generate(seed):
                 matrix = listed[int(rng.randint(0, len(listed)))][1] if how < 0.7 else [float(np.float32(v)) for v in rng.uniform(-FM.MATRIX_MAX, FM.MATRIX_MAX, 20) * rng.choice([1.0, 0.1], 20)]
                 tables = rng.randint(0, 256, 1024).astype(np.uint8) if rng.uniform() < 0.4 else None
             emit(dict(kind="color_filter", image=i, matrix=matrix, tables=tables, width=pool[i]["pixels"].shape[1]))
+        elif kind == "morphology":
+            room(2)
+            i = a_source(prefer_wide=True)
+            h, w = pool[i]["pixels"].shape[:2]
+            mop, edge = int(rng.randint(0, 2)), int(rng.randint(0, 4))
+            route = int(rng.choice(4, p=[0.1, 0.25, 0.25, 0.4]))  # ROUTES: bit 0 = a horizontal pass, bit 1 = a vertical one
+            radius = [int(rng.choice(RADII[1:7])) if route & 1 else 0, int(rng.choice(RADII[1:7])) if route & 2 else 0]
+            big = bool(route and big_morphology_left and max(w, h) <= 260 and rng.uniform() < 0.4)
+            if big:  # once per seed: a radius above 64 (65 or the largest, 192) on one axis with a pass
+                radius[pick([a for a in (0, 1) if radius[a]])] = int(rng.choice(RADII[7:]))
+                big_morphology_left -= 1
+            elif MO.grows(mop, edge) and (w + 2 * radius[0] > MAX_SIDE or h + 2 * radius[1] > MAX_SIDE):
+                edge = int(rng.randint(1, 4))
+            if max(MO.size(w, h, mop, radius[0], radius[1], edge)) > 16384:
+                continue  # (the library refuses it)
+            emit(dict(kind="morphology", image=i, op=mop, radius=radius, edge=edge, width=w))
+            grown = MO.grows(mop, edge) and route
+            if big and pool[-1]["pixels"].shape[1] > 256 and rng.uniform() < 0.7:  # the grown row, wider than k_image_morph_h's segment, along itself
+                emit(dict(kind="morphology", image=len(pool) - 1, op=int(rng.randint(0, 2)), radius=[int(rng.choice(RADII[1:7])), int(rng.choice(RADII[:4]))], edge=int(rng.randint(1, 4)),
+                          width=pool[-1]["pixels"].shape[1]))
+            elif grown and rng.uniform() < 0.5:  # an outline's way: the grown result with the image it grew from, placed by its origin
+                emit(dict(kind="composite", image=i, source=len(pool) - 1, op=int(rng.randint(0, 13)), mode=int(rng.randint(0, 9)), opacity=float(rng.choice([1.0, rng.uniform()])),
+                          offset=[-radius[0], -radius[1]], width=w))
+            after_filter(i, kind)
+        elif kind == "convolve":
+            room()
+            i = a_source()
+            h, w = pool[i]["pixels"].shape[:2]
+            order = [1 if t < 0.15 else 15 if t < 0.3 else int(rng.randint(2, 15)) for t in rng.uniform(size=2)]
+            if order[0] * order[1] * w * h > 2000000:  # (the host model's time goes with the taps times the texels: one such call per seed)
+                if heavy_convolve_left:
+                    heavy_convolve_left -= 1
+                else:
+                    order[int(order[0] >= order[1])] = int(rng.randint(1, 4))
+            kernel, divisor = CV.random_kernel(rng, order[0], order[1])
+            t = rng.uniform()
+            target = None if t < 0.3 else [int(rng.choice([0, order[0] - 1])), int(rng.choice([0, order[1] - 1]))] if t < 0.6 else [int(rng.randint(0, order[0])), int(rng.randint(0, order[1]))]
+            emit(dict(kind="convolve", image=i, kernel=kernel, divisor=divisor, bias=0.0 if rng.uniform() < 0.5 else f32(rng.uniform(-0.1, 0.1)), target=target, edge=int(rng.randint(0, 4)),
+                      preserve_alpha=bool(rng.randint(0, 2)), order=order, width=w, texels=w * h))
+            after_filter(i, kind)
+        elif kind == "lighting":
+            room()
+            i = a_source()
+            h, w = pool[i]["pixels"].shape[:2]
+            which = int(rng.randint(0, 3))
+            if which == LM.DISTANT:
+                light = dict(kind=which, azimuth=f32(rng.uniform(-360, 360)), elevation=f32(rng.uniform(-10, 90)))
+            elif which == LM.POINT:  # above the image or a little beside it
+                light = dict(kind=which, position=[f32(rng.uniform(-0.2, 1.2) * w), f32(rng.uniform(-0.2, 1.2) * h), f32(rng.uniform(0.5, 0.3 * max(w, h) + 4.0))])
+            else:  # from beside a corner into the image, so that the cone's border cuts through it
+                light = dict(kind=which, position=[f32(rng.uniform(-0.3, 0.3) * w - 2.0), f32(rng.uniform(-0.3, 0.3) * h - 1.0), f32(rng.uniform(3, 12))],
+                             points_at=[f32(rng.uniform(0.2, 0.8) * w), f32(rng.uniform(0.2, 0.8) * h), 0.0],
+                             spot_exponent=f32(rng.choice([0.0, 1.0, 3.0, rng.uniform(0, 8)])), cone_angle=f32(rng.choice([0.0, 25.0, 60.0, 90.0, rng.uniform(5, 90)])))
+            emit(dict(kind="lighting", image=i, light=light, op=int(rng.randint(0, 2)), surface_scale=f32(rng.uniform(0.5, 8) * rng.choice([1.0, 1.0, -1.0])), constant=f32(rng.uniform(0.3, 2)),
+                      specular_exponent=f32(rng.uniform(1, 40)), color=[f32(v) for v in np.minimum(rng.uniform(0, 1.3, 3), 1.0)], edge=int(rng.randint(0, 4)), width=w))
+            after_filter(i, kind)
+        elif kind == "turbulence":
+            room()
+            emit(turbulence_op((width, height) if rng.uniform() < 0.5 else (rng.randint(1, 41), rng.randint(1, 31))))
+        elif kind == "displace":
+            room(2)
+            i = a_source()
+            h, w = pool[i]["pixels"].shape[:2]
+            same = [k for k, e in enumerate(pool) if k != i and e["pixels"].shape == pool[i]["pixels"].shape]
+            if rng.uniform() < 0.2:
+                m = i  # the source is its own map
+            elif same and rng.uniform() < 0.7:
+                m = pick(same)
+            else:  # the usual map: noise of the source's size
+                emit(turbulence_op((w, h)))
+                m = len(pool) - 1
+            emit(dict(kind="displace", image=i, map=m, scale=list(DISPLACE_SCALES[int(rng.randint(0, len(DISPLACE_SCALES)))]), channels=[int(v) for v in rng.randint(0, 4, 2)],
+                      filter=int(rng.randint(0, 2)), edge=int(rng.randint(0, 4)), width=w))
+            after_filter(i, kind)
         elif kind == "mipmaps":
             emit(dict(kind="mipmaps", image=int(rng.randint(0, len(pool)))))
         elif kind == "check_image":
@@ -339,7 +528,7 @@ def generate(seed):
             sized = frame_sized(lambda e: premultiplied(e["pixels"]))
             if not sized:
                 continue
-            emit(dict(kind="load_image", frame=j, image=pick(sized)))
+            emit(dict(kind="load_image", frame=j, image=newer(sized)))
         elif kind == "download":
             if model.frame[j]["cleared"] and rng.uniform() < 0.7:
                 j = 1 - j
@@ -349,7 +538,7 @@ def generate(seed):
             if not sized or (model.table[j] is None) != (kind == "set_table"):
                 continue
             binary = [i for i in sized if binary_alpha(pool[i]["pixels"])]
-            emit(dict(kind=kind, frame=j, image=pick(binary) if binary and rng.uniform() < 0.5 else pick(sized), filter=a_filter()))
+            emit(dict(kind=kind, frame=j, image=pick(binary) if binary and rng.uniform() < 0.5 else newer(sized), filter=a_filter()))
         elif kind == "clear_table":
             if model.table[j] is not None:
                 emit(dict(kind="clear_table", frame=j))
@@ -358,20 +547,20 @@ def generate(seed):
                 sized = frame_sized(lambda e: premultiplied(e["pixels"]))
                 if not sized:
                     continue
-                emit(dict(kind="set_table", frame=j, image=pick(sized), filter=a_filter()))
+                emit(dict(kind="set_table", frame=j, image=newer(sized), filter=a_filter()))
             table = model.table[j]
             if table["index"] is not None and rng.uniform() < 0.3:
                 emit(dict(kind="destroy_image", image=table["index"]))  # the table keeps the pixels
             if not model.frame[j]["cleared"] and not (binary_alpha(table["pixels"]) and rng.uniform() < 0.8):
                 emit(dict(kind="clear", frame=j))
-            emit(dict(kind="blit", frame=j, destroyed=table["destroyed"], over=not model.frame[j]["cleared"]))
+            emit(dict(kind="blit", frame=j, destroyed=table["destroyed"], over=not model.frame[j]["cleared"], via=tuple(sorted(table["via"]))))
         elif kind == "blit_mip":
             if not model.frame[j]["cleared"] and rng.uniform() < 0.5:
                 emit(dict(kind="clear", frame=j))
             usable = blittable(j)
             if not usable:
                 continue
-            i = pick(usable)
+            i = newer(usable)
             if not pool[i]["mip"]:
                 emit(dict(kind="mipmaps", image=i))
             emit(dict(kind="blit_mip", frame=j, image=i, filter=a_filter() | MIPMAP))

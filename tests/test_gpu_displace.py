@@ -1,7 +1,7 @@
 """crh_image_displace (include/contrast_hip.h) on the GPU: k_image_displace byte for byte against the numpy model of
 tests/displace_model.py, with no tolerance and no excluded texel — every specialisation (filter x edge) with three channel pairs, sizes
 inside one tile, one tile exactly, sizes that cross tile borders with fetches far into other workgroups' tiles and many periods out, the
-widest index range — the host function against the device, a chain of image calls step by step, the refused calls, and the mipmaps of a
+widest index range, texels that are not premultiplied, the source as its own map — the host function against the device, a chain of image calls step by step, the refused calls, and the mipmaps of a
 result and its use as an image paint."""
 import ctypes as C
 import itertools
@@ -15,6 +15,7 @@ from contrast_renderer_amd.renderer import Filter, Image
 
 import blur_model
 import composite_model as CM
+import convolve_model as CVM
 import displace_model as M
 import turbulence_model as TM
 from test_gpu_blending import no_pins  # noqa: F401
@@ -73,6 +74,46 @@ def test_every_specialisation_equals_the_model(size, renderer, no_pins):
             if scale == (0.0, 0.0):
                 assert np.array_equal(got, src)
         assert np.array_equal(source.download_level(0), src) and np.array_equal(map_image.download_level(0), map)  # no input was modified
+
+
+def straight_images(w, h, seed):
+    """(source, map) of convolve_model.random_pixels: about one texel in ten has a colour above its alpha"""
+    rng = np.random.RandomState(seed)
+    src, map = CVM.random_pixels(rng, w, h), CVM.random_pixels(rng, w, h)
+    for a in (src, map):
+        assert 0.05 < (a[..., :3] > a[..., 3:]).any(axis=2).mean() < 0.5
+    return src, map
+
+
+@pytest.mark.parametrize("size", [(33, 15), (65, 16)], ids=["33x15", "65x16"])
+def test_maps_and_sources_that_are_not_premultiplied(size, renderer, no_pins):
+    """A map colour above its alpha is loaded as min(c, a), as the colour filter loads it, and so gives the code 255; a source's codes are
+    read as they are, with no clamp. Inside one tile, and one texel across the first tile border."""
+    src, map = straight_images(size[0], size[1], 31 + size[0])
+    clamped = map.copy()
+    clamped[..., :3] = np.minimum(map[..., :3], map[..., 3:])
+    assert all(np.array_equal(M.codes(map, c), M.codes(clamped, c)) for c in range(4)) and (M.codes(map, M.R)[(map[..., 0] > map[..., 3]) & (map[..., 3] > 0)] == 255).all()
+    source, map_image = Image(renderer, src), Image(renderer, map)
+    carried = False
+    for filter, edge, (cx, cy), scale in itertools.product(FILTERS, M.EDGES, PAIRS, SCALES):
+        got = run_and_check(source, map_image, src, map, scale, cx, cy, filter, edge)
+        if scale == (0.0, 0.0):
+            assert np.array_equal(got, src)  # the copy keeps the colours above their alpha
+        carried = carried or bool((got[..., :3] > got[..., 3:]).any())
+    assert carried
+    assert np.array_equal(source.download_level(0), src) and np.array_equal(map_image.download_level(0), map)  # no input was modified
+
+
+@pytest.mark.parametrize("filter", FILTERS, ids=["nearest", "linear"])
+def test_the_source_as_its_own_map(filter, renderer, no_pins):
+    """source.displace(source, ...): one device image behind both of the kernel's pointers, which it only reads. One texel across the first
+    tile border, premultiplied texels and texels that are not."""
+    for src in (images(65, 16, 12, True)[0], straight_images(65, 16, 13)[0]):
+        source = Image(renderer, src)
+        for edge, (cx, cy), scale in itertools.product(M.EDGES, PAIRS, SCALES):
+            expect = M.displace(src, src, scale, cx, cy, filter, edge)
+            check(source.displace(source, scale, Channel(cx), Channel(cy), Filter(filter), BlurEdge(edge)), expect, ("self", scale, cx, cy, filter, edge))
+        assert np.array_equal(source.download_level(0), src) and source.levels == 1  # the source is unchanged
 
 
 @pytest.mark.parametrize("size", LARGE, ids=[f"{w}x{h}" for w, h in LARGE])

@@ -1,6 +1,6 @@
 """Stateful fuzz of the image and layer pipeline on the GPU: the op sequences of tests/layers_model.py replayed on one Renderer — images created,
-snapshot from frames in whatever state, blurred, composited, colour filtered, mipmapped, loaded back into frames and drawn as image paints
-through tables that outlive their images, between clears, uploads, plain passes and re-uploads of a Scene that holds a paint table. The host
+snapshot from frames in whatever state, made of noise, blurred, composited, colour filtered, eroded and dilated, convolved, lit, displaced,
+mipmapped, destroyed behind the call that read them, loaded back into frames and drawn as image paints through tables that outlive their images, between clears, uploads, plain passes and re-uploads of a Scene that holds a paint table. The host
 model has an exact expectation for every step, so every download is compared byte for byte, with no tolerance and no excluded texel."""
 import os
 
@@ -9,9 +9,11 @@ import pytest
 
 from contrast_renderer_amd import Path, batch_from_shapes
 from contrast_renderer_amd import renderer as R
-from contrast_renderer_amd.renderer import BlurEdge, Filter, Image, ImagePaint
+from contrast_renderer_amd.renderer import (BlurEdge, Channel, DistantLight, Filter, Image, ImagePaint, LightingOp, MorphologyOp, PointLight, SpotLight,
+                                            TurbulenceKind)
 
 import layers_model as L
+import lighting_model as LM
 from test_gpu_blending import last_pass, no_pins  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +37,15 @@ def white_paint_of(r, white):
     if white["mip"]:
         image.generate_mipmaps()
     return image, ImagePaint(image, white["matrix"], white["filter"], *white["spreads"])
+
+
+def light_of(light):
+    """The library's light of an op's `light`, the keyword arguments of lighting_model.Light."""
+    if light["kind"] == LM.DISTANT:
+        return DistantLight(light["azimuth"], light["elevation"])
+    if light["kind"] == LM.POINT:
+        return PointLight(*light["position"])
+    return SpotLight(tuple(light["position"]), tuple(light["points_at"]), light["spot_exponent"], light["cone_angle"])
 
 
 def describe(op):
@@ -86,10 +97,21 @@ def test_random_layer_pipelines_against_a_host_model(seed, oracle_lib, no_pins):
             pool.append(pool[op["image"]].composite(pool[op["source"]], op["op"], op["mode"], op["opacity"], op["offset"]))
         elif kind == "color_filter":
             pool.append(pool[op["image"]].color_filter(op["matrix"], op["tables"]))
+        elif kind == "morphology":
+            pool.append(pool[op["image"]].morphology(MorphologyOp(op["op"]), op["radius"][0], op["radius"][1], BlurEdge(op["edge"])))
+        elif kind == "convolve":
+            pool.append(pool[op["image"]].convolve(op["kernel"], op["divisor"], op["bias"], op["target"], BlurEdge(op["edge"]), op["preserve_alpha"]))
+        elif kind == "lighting":
+            pool.append(pool[op["image"]].lighting(light_of(op["light"]), LightingOp(op["op"]), op["surface_scale"], op["constant"], op["specular_exponent"], op["color"], BlurEdge(op["edge"])))
+        elif kind == "turbulence":
+            pool.append(Image.turbulence(r, op["size"][0], op["size"][1], op["frequency"], op["octaves"], op["seed"], TurbulenceKind(op["noise"]), op["stitch"], op["opaque"], op["offset"]))
+        elif kind == "displace":
+            pool.append(pool[op["image"]].displace(pool[op["map"]], op["scale"], Channel(op["channels"][0]), Channel(op["channels"][1]), Filter(op["filter"]), BlurEdge(op["edge"])))
         elif kind == "mipmaps":
             pool[op["image"]].generate_mipmaps()
         elif kind == "check_image":
             image = pool[op["image"]]
+            assert image.origin == op["origin"], f"{where}: the origin is {image.origin}, not {op['origin']}"
             assert image.levels == len(expect), f"{where}: {image.levels} levels, not {len(expect)}"
             for level, e in enumerate(expect):
                 compare(image.download_level(level), e, step, op, f"level {level}")

@@ -89,6 +89,37 @@ def test_the_morphology_equals_the_model(size, op, edge, renderer, no_pins):
             assert np.array_equal(expect, pixels)  # a copy
 
 
+def straight_of(w, h):
+    """Texels whose red lies above their alpha everywhere (alpha below 200), green and blue anywhere: not premultiplied ones."""
+    def make():
+        rng = np.random.RandomState(5 * w + h)
+        t = rng.randint(0, 256, (h, w, 4))
+        t[..., 3] = rng.randint(0, 200, (h, w))
+        t[..., 0] = np.maximum(t[..., 0], t[..., 3] + 1)
+        return t.astype(np.uint8)
+    return made_once(("straight", w, h), make)
+
+
+@pytest.mark.parametrize("edge", EDGES, ids=[e.name for e in EDGES])
+@pytest.mark.parametrize("op", OPS, ids=[o.name for o in OPS])
+@pytest.mark.parametrize("size", [(1, 7), (33, 17)], ids=["1x7", "33x17"])
+def test_colours_above_their_alpha_go_through_every_route(size, op, edge, renderer, no_pins):
+    """The rule is per channel on the codes as they are, with no load clamp (compositing, the colour filter and convolution clamp c to a): the
+    copy, the horizontal pass alone, the vertical pass alone and both, on texels whose red exceeds their alpha. Every red of a window
+    exceeds its own alpha, so the window's extreme red exceeds its extreme alpha: the result keeps red > alpha everywhere — but for Erode
+    under Transparent, where a window that reaches outside the source holds (0, 0, 0, 0) and gives it."""
+    pixels = straight_of(*size)
+    assert (pixels[..., 0] > pixels[..., 3]).all()
+    for rx, ry in ((0, 0), (2, 0), (0, 1), (1, 2)):
+        expect = run_and_check(renderer, pixels, op, rx, ry, edge, ("straight", size, op.name, edge.name, rx, ry))
+        above = expect[..., 0] > expect[..., 3]
+        if (rx, ry) == (0, 0) or not (op == MorphologyOp.Erode and edge == BlurEdge.Transparent):
+            assert above.all(), (rx, ry, float(above.mean()))
+        else:
+            h, w = pixels.shape[:2]
+            assert above[ry:h - ry, rx:w - rx].all() and not expect[:ry].any() and not expect[:, :rx].any(), (rx, ry)
+
+
 def large_input(kind, size, radii):
     w, h = size
     if kind == "ramps":

@@ -11,6 +11,7 @@ from contrast_renderer_amd.renderer import Filter, Spread
 
 import blur_model as BM
 import composite_model as CM
+import convolve_model as CV
 import image_paint_model as IM
 import layers_model as L
 
@@ -60,6 +61,119 @@ def test_the_layer_generator_meets_its_conditions(generated):
     assert dense >= 0.6 * arrays, (dense, arrays)
 
 
+def test_the_newer_filters_meet_their_conditions(generated):
+    """What keeps morphology, convolve, lighting, turbulence and displace from degenerating inside the sequences: every route and
+    instantiation, every edge and operand class, inputs with colours above their alpha, inputs that the device made, sources with a mip
+    chain, sources destroyed behind the call, and results that reach a frame — also through a table that outlives them."""
+    n = Counter()
+    routes, windows, lights = Counter(), Counter(), set()
+    edges = {kind: set() for kind in L.NEW if kind != "turbulence"}
+    seen = {name: set() for name in ("morphology op", "preserve_alpha", "displace filter", "convolve width", "noise", "stitch", "opaque", "octaves")}
+    for setup, ops in generated:
+        assert sum(1 for op in ops if op["kind"] == "morphology" and max(op["radius"]) > 64) <= 1
+        assert sum(1 for op in ops if op["kind"] == "convolve" and min(op["order"]) > 3 and op["order"][0] * op["order"][1] * op["texels"] > 2000000) <= 1
+        for op in ops:
+            kind = op["kind"]
+            if kind in edges:
+                edges[kind].add(op["edge"])
+                n[kind, "deep"] += int(op["depth"] >= 2)
+                n["mipmapped source"] += int(op["mip"])
+            if kind in L.READS and kind != "check_image" and "turbulence" in op["by"]:
+                n["turbulence", "deep"] += 1  # its result is consumed
+            if kind == "morphology":
+                rx, ry = op["radius"]
+                assert rx in L.RADII and ry in L.RADII
+                routes[L.morphology_route(op["radius"])] += 1
+                windows[33 if 2 * ry + 1 <= 33 else 129 if 2 * ry + 1 <= 129 else 385] += int(ry > 0)
+                n["wide morphology"] += int(op["width"] > 256 and rx > 0)
+                n["straight morphology"] += int(op["straight"][0])
+                seen["morphology op"].add(op["op"])
+            elif kind == "convolve":
+                assert all(1 <= v <= 15 for v in op["order"]) and op["kernel"].shape == (op["order"][1], op["order"][0]) and op["kernel"].dtype == np.float32
+                n["order 15"] += int(15 in op["order"])
+                n["order 1"] += int(1 in op["order"])
+                n["corner target"] += int(op["target"] is not None and op["target"][0] in (0, op["order"][0] - 1) and op["target"][1] in (0, op["order"][1] - 1))
+                n["no target"] += int(op["target"] is None)
+                n["bias"] += int(op["bias"] != 0.0)
+                n["straight convolve"] += int(op["straight"][0])
+                seen["preserve_alpha"].add(op["preserve_alpha"])
+                seen["convolve width"].add(op["width"] % 4)
+            elif kind == "lighting":
+                lights.add((op["light"]["kind"], op["op"]))
+                n["negative surface_scale"] += int(op["surface_scale"] < 0.0)
+            elif kind == "turbulence":
+                n["frame-sized noise"] += int(tuple(op["size"]) == (setup["width"], setup["height"]))
+                n["negative seed"] += int(op["seed"] < 0)
+                n["offset"] += int(op["offset"] != [0.0, 0.0])
+                for name in ("noise", "stitch", "opaque", "octaves"):
+                    seen[name].add(op[name])
+            elif kind == "displace":
+                n["self-map"] += int(op["map"] == op["image"])
+                n["noise map"] += int(op["by"][1] == "turbulence")
+                n["scale 1024"] += int(max(abs(v) for v in op["scale"]) == 1024.0)
+                n["scale 0"] += int(op["scale"] == [0.0, 0.0])
+                n["straight displace source"] += int(op["straight"][0])
+                n["straight displace map"] += int(op["straight"][1])
+                seen["displace filter"].add(op["filter"])
+            elif kind == "composite":
+                n["grown dilate drawn on"] += int(L.GROWN_DILATE in op["via"])
+            elif kind in ("blit", "blit_mip", "load_image") and set(op["via"]) & set(L.NEW):
+                n["reaches a frame"] += 1
+                n["reaches a frame destroyed"] += int(kind == "blit" and op["destroyed"])
+            elif kind == "destroy_image" and op.get("behind") in L.NEW:
+                n["source destroyed behind the call"] += 1
+    print(dict(n), dict(routes), dict(windows))
+    assert set(routes) == set(L.ROUTES) and min(routes.values()) >= 2, routes
+    assert set(windows) == {33, 129, 385} and min(windows.values()) >= 1, windows
+    assert n["wide morphology"] >= 2 and seen["morphology op"] == {0, 1} and n["grown dilate drawn on"] >= 1, n
+    assert all(found == {0, 1, 2, 3} for found in edges.values()), edges
+    assert seen["preserve_alpha"] == {False, True} and n["order 15"] >= 1 and n["order 1"] >= 1 and seen["convolve width"] == {0, 1, 2, 3}, (n, seen)
+    assert n["corner target"] >= 1 and n["no target"] >= 1 and n["bias"] >= 1, n
+    assert len(lights) == 6 and n["negative surface_scale"] >= 1, (lights, n)
+    assert n["frame-sized noise"] >= 1 and n["negative seed"] >= 1 and n["offset"] >= 1 and seen["noise"] == {0, 1} and seen["stitch"] == seen["opaque"] == {False, True}, (n, seen)
+    assert seen["octaves"] == {0, 1, 2, 3, 4}, seen
+    assert n["self-map"] >= 2 and n["noise map"] >= 2 and seen["displace filter"] == {0, 1} and n["scale 1024"] >= 1 and n["scale 0"] >= 1, (n, seen)
+    assert min(n["straight morphology"], n["straight convolve"], n["straight displace source"], n["straight displace map"]) >= 1, n
+    assert all(n[kind, "deep"] >= 2 for kind in L.NEW), n
+    assert n["mipmapped source"] >= 3 and n["reaches a frame"] >= 3 and n["reaches a frame destroyed"] >= 1 and n["source destroyed behind the call"] >= 2, n
+
+
+def host_rule(op, pool):
+    """What the library's host function (crh_<filter>_texels) makes of an op of one of the newer kinds on the model's bytes."""
+    kind = op["kind"]
+    if kind == "turbulence":
+        return R.turbulence_texels(op["size"][0], op["size"][1], op["frequency"], op["octaves"], op["seed"], op["noise"], op["stitch"], op["opaque"], op["offset"])
+    pixels = pool[op["image"]]["pixels"]
+    if kind == "morphology":
+        return R.morphology_texels(pixels, op["op"], op["radius"][0], op["radius"][1], op["edge"])
+    if kind == "convolve":
+        return R.convolve_texels(pixels, op["kernel"], op["divisor"], op["bias"], op["target"], op["edge"], op["preserve_alpha"])
+    if kind == "displace":
+        return R.displace_texels(pixels, pool[op["map"]]["pixels"], tuple(op["scale"]), op["channels"][0], op["channels"][1], op["filter"], op["edge"])
+    light = op["light"]
+    mirror = (R.DistantLight(light["azimuth"], light["elevation"]) if light["kind"] == 0 else R.PointLight(*light["position"]) if light["kind"] == 1 else
+              R.SpotLight(tuple(light["position"]), tuple(light["points_at"]), light["spot_exponent"], light["cone_angle"]))
+    return R.lighting_texels(pixels, mirror, op["op"], op["surface_scale"], op["constant"], op["specular_exponent"], op["color"], op["edge"])
+
+
+def test_the_generated_ops_of_the_newer_kinds_equal_the_host_rules(generated, oracle_lib):
+    """Every morphology, convolve, lighting, turbulence and displace op of the default seeds, with the arguments and on the inputs the
+    sequence gives it — grown, filtered, snapshot and straight images among them: the model's bytes are the host rule's, so the library
+    accepts every generated call, and a difference on the GPU is the device's."""
+    import __graft_entry__ as entry
+    entry.build()
+    compared = Counter()
+    for setup, ops in generated:
+        model = L.Model(setup)
+        for k, op in enumerate(ops):
+            host = host_rule(op, model.pool) if op["kind"] in L.NEW else None
+            model.apply(op)
+            if host is not None:
+                assert np.array_equal(model.pool[-1]["pixels"], host), (setup["seed"], k, {name: value for name, value in op.items() if not isinstance(value, np.ndarray)})
+                compared[op["kind"]] += 1
+    assert set(compared) == set(L.NEW) and min(compared.values()) >= 3, compared
+
+
 def test_the_layer_generator_is_deterministic(generated):
     for seed in (0, 5):
         setup, ops = L.generate(seed)
@@ -101,7 +215,7 @@ def test_a_code_decodes_and_encodes_to_itself():
 
 def test_the_models_steps_equal_the_librarys_host_rules(oracle_lib):
     """Three chained images — a blur, a composite of it over its source, a colour filter of that — by the Python models the fuzz replays and
-    by the library's host mirrors: crh_blur_taps, crh_composite_texels, crh_color_filter_texels."""
+    by the library's host mirrors: crh_blur_taps, crh_composite_texels, crh_color_filter_texels; then a chain through the five newer steps."""
     import __graft_entry__ as entry
     entry.build()
     rng = np.random.RandomState(8)
@@ -121,3 +235,31 @@ def test_the_models_steps_equal_the_librarys_host_rules(oracle_lib):
     for matrix, t in ((None, L.threshold_tables()), ([float(np.float32(v)) for v in rng.uniform(-16, 16, 20)], tables), (R.ColorMatrix.saturate(2), None)):
         filtered = L.step_color_filter(composed, matrix, t)
         assert np.array_equal(filtered, R.color_filter_texels(composed.reshape(-1, 4), matrix, t).reshape(composed.shape)), matrix
+    # The five newer steps as one chain on the same straight texels — noise of their size, the texels eroded and dilated, convolved,
+    # displaced by the noise and by themselves, lit — by the models the fuzz replays and by crh_turbulence_texels, crh_morphology_texels,
+    # crh_convolve_texels, crh_displace_texels and crh_lighting_texels.
+    assert not L.premultiplied(base)
+    for noise_kind, stitch, opaque in ((0, True, False), (1, False, True)):
+        how = dict(frequency=[L.f32(0.07), L.f32(0.31)], octaves=3, seed=-5, stitch=stitch, opaque=opaque, offset=[L.f32(3.4), L.f32(-2.25)])
+        noise = L.step_turbulence([21, 13], noise=noise_kind, **how)
+        assert np.array_equal(noise, R.turbulence_texels(21, 13, how["frequency"], 3, -5, noise_kind, stitch, opaque, how["offset"])), (noise_kind, stitch, opaque)
+    for op, radius, edge in ((1, [2, 1], 0), (1, [0, 0], 0), (0, [0, 5], 3), (0, [17, 0], 2), (1, [64, 65], 1)):
+        morphed = L.step_morphology(base, op, radius, edge)
+        assert np.array_equal(morphed, R.morphology_texels(base, op, radius[0], radius[1], edge)), (op, radius, edge)
+        assert morphed.shape == ((13 + 2, 21 + 4, 4) if (op, edge, radius) == (1, 0, [2, 1]) else base.shape)
+    morphed = L.step_morphology(base, 0, [1, 1], 1)
+    assert not L.premultiplied(morphed)  # colours above their alpha go through: the rule is per channel, with no clamp
+    for order, target, bias, edge, preserve_alpha in (((15, 1), None, 0.0, 0, False), ((1, 15), [0, 14], L.f32(0.04), 3, True), ((4, 3), [3, 0], L.f32(-0.07), 2, False)):
+        kernel, divisor = CV.random_kernel(rng, *order)
+        convolved = L.step_convolve(morphed, kernel, divisor, bias, target, edge, preserve_alpha)
+        assert np.array_equal(convolved, R.convolve_texels(morphed, kernel, divisor, bias, target, edge, preserve_alpha)), (order, target)
+    for map, scale, channels, filter, edge in ((noise, [1024.0, -1024.0], [0, 1], 0, 2), (noise, [3.25, -7.5], [3, 2], 1, 0), (morphed, [-20.0, 20.0], [0, 3], 1, 3), (base, [0.3, 64.0], [2, 1], 1, 1)):
+        displaced = L.step_displace(morphed, map, scale, channels, filter, edge)
+        assert np.array_equal(displaced, R.displace_texels(morphed, map, tuple(scale), channels[0], channels[1], filter, edge)), (scale, channels, filter, edge)
+    for light, mirror in ((dict(kind=0, azimuth=L.f32(225.5), elevation=L.f32(35.25)), R.DistantLight(L.f32(225.5), L.f32(35.25))),
+                          (dict(kind=1, position=[L.f32(6.3), L.f32(7.8), 4.5]), R.PointLight(L.f32(6.3), L.f32(7.8), 4.5)),
+                          (dict(kind=2, position=[-2.0, -1.0, 6.0], points_at=[L.f32(12.6), 6.5, 0.0], spot_exponent=3.0, cone_angle=25.0), R.SpotLight((-2.0, -1.0, 6.0), (L.f32(12.6), 6.5, 0.0), 3.0, 25.0))):
+        for op, surface_scale in ((0, 3.0), (1, -2.0)):
+            how = (surface_scale, L.f32(0.9), 12.0, [1.0, 0.5, L.f32(0.3)], op + 1)
+            lit = L.step_lighting(displaced, light, op, *how)
+            assert np.array_equal(lit, R.lighting_texels(displaced, mirror, op, *how)), (light, op)
