@@ -81,7 +81,7 @@ def build_library(force=False, verbose=False):
 
 
 DEBUG_TAPS = ("crh_debug_frame_counters", "crh_debug_frame_counters16", "crh_debug_frame_words", "crh_debug_frame_bin_dump", "crh_debug_flat_batches", "crh_debug_pass_leaves_state",
-              "crh_debug_frame_last_pass")  # tools/ and the tests read the raster kernels' counters through these
+              "crh_debug_frame_last_pass", "crh_debug_frame_tile_place")  # tools/ and the tests read the raster kernels' counters through these
 
 
 def declared_entry_points():

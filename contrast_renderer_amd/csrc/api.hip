@@ -2937,6 +2937,17 @@ extern "C" crh_status crh_debug_frame_bin_dump(crh_frame* f, uint32_t* out, uint
     HIP_TRY(hipMemcpy(out, f->item_cost.p, (size_t)n_words * 4, hipMemcpyDeviceToHost));
     return CRH_OK;
 }
+// tests only: where the next pass with the lists in place puts the list of `tile` — out[0] its first entry in the tile lists, out[1] the first entry of the next
+// tile's place (their difference is the room the list has) —, and in out[2] the entries the frame's last pass counted in the tile; CRH_ERR_INVALID_ARGUMENT while
+// the frame has no places
+extern "C" crh_status crh_debug_frame_tile_place(crh_frame* f, uint32_t tile, uint32_t out[3]) {
+    if (!f || !out || !f->direct_ready || tile >= f->n_tiles || !f->sets[f->last_set].used) return CRH_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(f->renderer->device));
+    HIP_TRY(f->renderer->sync());
+    HIP_TRY(hipMemcpy(out, (f->base_cur ? f->tile_base_b : f->tile_base).as<uint32_t>() + tile, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out + 2, f->sets[f->last_set].tile_count_cursor.as<uint32_t>() + f->n_tiles + tile, 4, hipMemcpyDeviceToHost));
+    return CRH_OK;
+}
 // tests only (host code, no device): the runs flat_batches cuts `n_items` items of the given costs into — runs[2 k], runs[2 k + 1] — and
 // the limits of a batch (items, triangles, edges, tile cells) in limits[4]; returns the number of runs, or -1 if `cap_runs` is too small
 extern "C" int crh_debug_flat_batches(const uint32_t* cost, uint32_t n_items, uint32_t* runs, uint32_t cap_runs, uint32_t limits[4]) {

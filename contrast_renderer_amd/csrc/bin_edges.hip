@@ -114,6 +114,99 @@ struct PlainTri {
     int n_attr;
     bool valid;
 };
+#ifndef CRH_BIN_LOADS_TRIS
+#define CRH_BIN_LOADS_TRIS 1 // 0: a branch per kind with its own loads and its own wait (A/B runs)
+#endif
+// The values the compiler is told nothing about any more: they are in their registers HERE. Behind the last of a group of global loads this keeps
+// the loads in front of it and together — left alone the compiler sinks every load to its first use, into whatever branch consumes it, and a
+// wavefront then waits for memory once per branch instead of once per group.
+template <class T>
+CRH_D void held(T& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(sizeof(T) == 4, "one vector register");
+    asm volatile("" : "+v"(v));
+#endif
+}
+#if CRH_BIN_LOADS_TRIS
+// A triangle's three vertices as they lie in memory, whatever its kind: the seven vertex streams differ in base and stride only (2, 4, 5 or 6 words
+// a vertex), and a triangle is three consecutive vertices of one of them. Every lane issues the same nine 8-byte loads — words 0-1 of each vertex, the
+// pair that holds words 2-3, the pair that ends with the vertex' last word — at addresses chosen with selects, so a wavefront of mixed kinds waits
+// once, and no pair reaches beyond its own vertex (the last vertex of a stream is the last thing allocated).
+struct __attribute__((may_alias)) WordPair {
+    float a, b;
+};
+struct TriRaw {
+    WordPair xy[3], mid[3], end[3];
+    uint32_t cut, which; // line_pair_cut of a stroke line's pair; which: 0 line, 1 joint, 2 IQ, 3 IC, 4 RQ, 5 RC, 6 hull strip
+};
+CRH_D uint32_t tri_stride(uint32_t which) { // words per vertex: Vertex2f1i, Vertex3f1i, Vertex2f, Vertex3f, Vertex3f, Vertex4f, Vertex0
+    return which == 6u ? 2u : (which == 2u ? 4u : ((which == 1u || which == 5u) ? 6u : 5u));
+}
+CRH_D void issue_plain_triangle(const SceneDev& s, const ItemCtx& ctx, uint32_t c, TriRaw& raw) {
+    const uint32_t* cb = ctx.cb;
+    const uint32_t which = (c >= cb[0] ? 1u : 0u) + (c >= cb[1] ? 1u : 0u) + (c >= cb[3] ? 1u : 0u) + (c >= cb[4] ? 1u : 0u) + (c >= cb[5] ? 1u : 0u) + (c >= cb[6] ? 1u : 0u);
+    const uint32_t q = c - cb[0], jn = q / 3u, jk = q - 3u * jn;
+    // the first vertex and the strip position's parity (strips: odd positions take their last two vertices swapped)
+    const uint32_t first = which == 0u ? ctx.lv0 + c
+                         : which == 1u ? 5u * (ctx.jn0 + jn) + jk
+                         : which == 2u ? 3u * (ctx.iq0 + (c - cb[2]))
+                         : which == 3u ? ctx.ic0 + 3u * (c - cb[3])
+                         : which == 4u ? 3u * (ctx.rq0 + (c - cb[4]))
+                         : which == 5u ? ctx.rc0 + 3u * (c - cb[5])
+                                       : ctx.hull0 + (c - cb[6]);
+    const uint32_t odd = which == 0u ? (c & 1u) : (which == 1u ? (jk & 1u) : (which == 6u ? ((c - cb[6]) & 1u) : 0u));
+    const float* base = which == 0u ? reinterpret_cast<const float*>(s.line_v)
+                      : which == 1u ? reinterpret_cast<const float*>(s.joint_v)
+                      : which == 2u ? reinterpret_cast<const float*>(s.iq_v)
+                      : which == 3u ? reinterpret_cast<const float*>(s.ic_v)
+                      : which == 4u ? reinterpret_cast<const float*>(s.rq_v)
+                      : which == 5u ? reinterpret_cast<const float*>(s.rc_v)
+                                    : reinterpret_cast<const float*>(s.hull_v);
+    const uint32_t stride = tri_stride(which), mid = min(2u, stride - 2u), end = min(4u, stride - 2u);
+    const uint32_t at[3] = {first, first + 1u + odd, first + 2u - odd};
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const float* pv = base + (size_t)at[v] * stride;
+        raw.xy[v] = *reinterpret_cast<const WordPair*>(pv);
+        raw.mid[v] = *reinterpret_cast<const WordPair*>(pv + mid);
+        raw.end[v] = *reinterpret_cast<const WordPair*>(pv + end);
+    }
+    raw.cut = 0u;
+    if (which == 0u) raw.cut = s.line_pair_cut[(ctx.lv0 + c) >> 1];
+    raw.which = which;
+}
+CRH_D void hold_plain_triangle(TriRaw& raw) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) held(raw.xy[v].a), held(raw.xy[v].b), held(raw.mid[v].a), held(raw.mid[v].b), held(raw.end[v].a), held(raw.end[v].b);
+    held(raw.cut);
+}
+// the fields by kind (the words themselves: a record keeps its bits)
+CRH_D void finish_plain_triangle(const ItemCtx& ctx, const TriRaw& raw, PlainTri& out) {
+    const uint32_t which = raw.which, stride = tri_stride(which);
+    const int n_attr = which == 6u ? 0 : (which == 5u ? 4 : ((which == 0u || which == 2u) ? 2 : 3));
+    const bool stroke = which <= 1u;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        out.p[v] = make_float2(raw.xy[v].a, raw.xy[v].b);
+        out.attr[v][0] = n_attr > 0 ? raw.mid[v].a : 0.0f;
+        out.attr[v][1] = n_attr > 1 ? raw.mid[v].b : 0.0f;
+        out.attr[v][2] = n_attr > 2 ? (stride == 6u ? raw.end[v].a : raw.end[v].b) : 0.0f;
+        out.attr[v][3] = n_attr > 3 ? raw.end[v].b : 0.0f;
+    }
+    out.flat_u = stroke ? __float_as_uint(raw.end[0].b) : 0u; // (the provoking vertex' integer is its last word)
+    out.end_y = which == 0u ? raw.mid[0].b : 0.0f;
+    out.desc = stroke ? ctx.dyn0 + (out.flat_u & 65535u) : 0u;
+    out.kind = which == 0u ? (uint32_t)KIND_LINE : which == 1u ? (uint32_t)KIND_JOINT : which == 2u ? (uint32_t)KIND_IQ : which == 3u ? (uint32_t)KIND_IC : which == 4u ? (uint32_t)KIND_RQ : which == 5u ? (uint32_t)KIND_RC : EK_COVER_TRI;
+    out.n_attr = n_attr;
+    out.valid = raw.cut == 0u;
+}
+CRH_D void load_plain_triangle(const SceneDev& s, const ItemCtx& ctx, uint32_t c, PlainTri& out) {
+    TriRaw raw;
+    issue_plain_triangle(s, ctx, c, raw);
+    hold_plain_triangle(raw);
+    finish_plain_triangle(ctx, raw, out);
+}
+#else
 CRH_D void load_plain_triangle(const SceneDev& s, const ItemCtx& ctx, uint32_t c, PlainTri& out) {
     const uint32_t* cb = ctx.cb;
     const uint32_t dyn0 = ctx.dyn0;
@@ -200,6 +293,7 @@ CRH_D void load_plain_triangle(const SceneDev& s, const ItemCtx& ctx, uint32_t c
     }
     out.kind = kind, out.flat_u = flat_u, out.desc = desc, out.end_y = end_y, out.n_attr = n_attr, out.valid = valid;
 }
+#endif
 // the vertices on the frame (t.p), the determinant and the pixel box; false: nothing to draw
 CRH_D bool place_plain_triangle(const RasterParams& r, const ItemCtx& ctx, PlainTri& t, float& det_out, ushort4& box) {
     const float W = (float)r.width, H = (float)r.height;
@@ -385,6 +479,107 @@ struct BinEdge { // one boundary edge of the item, canonical orientation
 // `n_fe` fill chain edges, then `n_hull_chain` hull chain edges. An endpoint that is not finite on the frame (finite vertices times a
 // finite matrix can overflow) sets *broken: the chain is not closed any more, so its backdrops mean nothing — the frame is then drawn by
 // the triangle pass, which skips exactly the strip triangles with a non-finite determinant as the reference's rasterizer would.
+#ifndef CRH_BIN_LOADS_EDGES
+#define CRH_BIN_LOADS_EDGES 1 // 0: the loads where the compiler puts them — in the branches that choose among them, five waits an edge (A/B runs)
+#endif
+#if CRH_BIN_LOADS_EDGES
+// load_edge in four steps, so that a caller with several edges per lane (k_bin_flat: kFlatEdgeRounds) waits for memory twice whatever it holds: the
+// flags of a fill edge and its neighbours; where the edge's vertices are — a fill edge's target follows from the three flags, a hull edge's from its
+// position, both with selects —; the vertices (the end points and, for a hull edge, the other two of the strip triangle that starts at its position);
+// the edge. Indices are clamped to the item's own vertices; what is selected always exists.
+struct EdgeFlags {
+    uint32_t f, f_prev, f_next;
+};
+CRH_D EdgeFlags load_edge_flags(const SceneDev& s, const ItemCtx& ctx, uint32_t n_fe, uint32_t i, bool fill) { // fill: the lane has a fill edge (i < n_fe)
+    EdgeFlags o = {0u, 0u, 0u};
+    if (fill) {
+        const uint32_t g = ctx.sv0 + i, g_last = ctx.sv0 + n_fe - 1u;
+        o.f = s.solid_flag[g], o.f_prev = s.solid_flag[i >= 1u ? g - 1u : g], o.f_next = s.solid_flag[min(g + 1u, g_last)];
+    }
+    return o;
+}
+CRH_D void hold_edge_flags(EdgeFlags& o) { held(o.f), held(o.f_prev), held(o.f_next); }
+constexpr uint32_t kEwHull = 1u, kEwStrip = 2u, kEwNone = 4u; // a hull edge; ... with a strip triangle at its position; a strip of one vertex: no edge
+struct EdgeWhere {
+    const Vertex0* v;
+    uint32_t a, b, c1, c2, bits;
+};
+CRH_D EdgeWhere edge_where(const SceneDev& s, const ItemCtx& ctx, uint32_t n_fe, uint32_t n_hull_chain, uint32_t i, const EdgeFlags& fl) {
+    const bool fill = i < n_fe;
+    const uint32_t g = ctx.sv0 + i, g_last = ctx.sv0 + n_fe - 1u;
+    const uint32_t gm1 = i >= 1u ? g - 1u : g, gm2 = i >= 2u ? g - 2u : g, gp1 = min(g + 1u, g_last), gp2 = min(g + 2u, g_last);
+    const bool odd = (fl.f & 1u) != 0u, last = (fl.f & 2u) != 0u;
+    const bool first = !odd && (i == 0u || (fl.f_prev & 2u) != 0u);
+    const uint32_t fill_b = first ? gp1 : (!odd ? gm2 : (last ? gm1 : ((fl.f_next & 2u) ? gp1 : gp2)));
+    const uint32_t pos = i - n_fe, n = n_hull_chain, hull0 = ctx.hull0;
+    const uint32_t target = pos == 0u ? 1u : ((pos & 1u) == 0u ? pos - 2u : (pos + 1u == n ? pos - 1u : (pos + 2u == n ? pos + 1u : pos + 2u)));
+    const bool strip = !fill && pos + 2u < n; // strip triangle `pos` = (pos, pos + 1, pos + 2), odd ones with the last two swapped
+    EdgeWhere w;
+    w.v = fill ? s.solid_v : s.hull_v;
+    w.a = fill ? g : hull0 + pos;
+    w.b = fill ? fill_b : hull0 + target;
+    w.c1 = strip ? hull0 + ((pos & 1u) ? pos + 2u : pos + 1u) : w.a;
+    w.c2 = strip ? hull0 + ((pos & 1u) ? pos + 1u : pos + 2u) : w.a;
+    w.bits = (fill ? 0u : kEwHull) | (strip ? kEwStrip : 0u) | ((fill && first && last) ? kEwNone : 0u);
+    return w;
+}
+struct EdgeVerts {
+    Vertex0 a, b, c1, c2;
+};
+CRH_D EdgeVerts load_edge_verts(const EdgeWhere& w, bool active) { // active: the lane has an edge
+    EdgeVerts o = {};
+    if (active) o.a = w.v[w.a], o.b = w.v[w.b], o.c1 = w.v[w.c1], o.c2 = w.v[w.c2];
+    return o;
+}
+CRH_D void hold_edge_verts(EdgeVerts& o) { held(o.a.x), held(o.a.y), held(o.b.x), held(o.b.y), held(o.c1.x), held(o.c1.y), held(o.c2.x), held(o.c2.y); }
+CRH_D BinEdge finish_edge(const RasterParams& r, const ItemCtx& ctx, uint32_t bits, const EdgeVerts& v) {
+    BinEdge e = {};
+    e.valid = false;
+    if (bits & kEwNone) return e; // a strip of one vertex
+    float2 a = make_float2(v.a.x, v.a.y), b = make_float2(v.b.x, v.b.y);
+    const float W = (float)r.width, H = (float)r.height;
+    if (bits & kEwHull) {
+        e.hull = 1u;
+        if (bits & kEwStrip) { // which way does the strip triangle face?
+            const float2 p0 = to_framebuffer(ctx, W, H, v.a.x, v.a.y), p1 = to_framebuffer(ctx, W, H, v.c1.x, v.c1.y), p2 = to_framebuffer(ctx, W, H, v.c2.x, v.c2.y);
+            const float d1x = p1.x - p0.x, d1y = p1.y - p0.y, d2x = p2.x - p0.x, d2y = p2.y - p0.y;
+            const float det = d1x * d2y - d2x * d1y; // setup_plain_triangle's det
+            e.strip_det = (det == det && is_finite(det)) ? det : 0.0f;
+        }
+    }
+    a = to_framebuffer(ctx, W, H, a.x, a.y);
+    b = to_framebuffer(ctx, W, H, b.x, b.y);
+    if (!(is_finite(a.x) && is_finite(a.y) && is_finite(b.x) && is_finite(b.y))) {
+        r.overflow[7] = 1u; // (see above; the host draws the frame again with the triangle pass)
+        return e;
+    }
+    if (a.x == b.x && a.y == b.y) return e;
+    const bool flip = !(a.x < b.x || (a.x == b.x && a.y < b.y)); // canonical (lexicographic) endpoint order
+    const float2 lo = flip ? b : a, hi = flip ? a : b;
+    e.lo_x = lo.x, e.lo_y = lo.y, e.hi_x = hi.x, e.hi_y = hi.y;
+    e.bx = hi.x - lo.x;
+    e.nay = -(hi.y - lo.y);
+    const float dx = hi.x - lo.x, dy = hi.y - lo.y;
+    e.tl = (dy < 0.0f || (dy == 0.0f && dx > 0.0f)) ? 1u : 0u;
+    e.down = dy > 0.0f ? 1 : 0;
+    e.sigma = flip ? 1 : -1; // -1: the chain runs in the canonical direction
+    e.ymin = fminf(lo.y, hi.y), e.ymax = fmaxf(lo.y, hi.y);
+    e.valid = true;
+    return e;
+}
+CRH_D BinEdge load_edge(const SceneDev& s, const RasterParams& r, const ItemCtx& ctx, uint32_t n_fe, uint32_t n_hull_chain, uint32_t i) {
+    const bool active = i < n_fe + n_hull_chain;
+    EdgeFlags fl = load_edge_flags(s, ctx, n_fe, i, active && i < n_fe);
+    hold_edge_flags(fl);
+    const EdgeWhere w = edge_where(s, ctx, n_fe, n_hull_chain, i, fl);
+    EdgeVerts v = load_edge_verts(w, active);
+    hold_edge_verts(v);
+    BinEdge e = {};
+    e.valid = false;
+    if (active) e = finish_edge(r, ctx, w.bits, v);
+    return e;
+}
+#else
 CRH_D BinEdge load_edge(const SceneDev& s, const RasterParams& r, const ItemCtx& ctx, uint32_t n_fe, uint32_t n_hull_chain, uint32_t i) {
     BinEdge e = {};
     e.valid = false;
@@ -452,6 +647,7 @@ CRH_D BinEdge load_edge(const SceneDev& s, const RasterParams& r, const ItemCtx&
     e.valid = true;
     return e;
 }
+#endif
 CRH_D float wave_min(float v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
@@ -1004,6 +1200,12 @@ static_assert(kFlatThreads == 64u || kFlatThreads == 128u || kFlatThreads == 256
 #ifndef CRH_FLAT_BATCH
 #define CRH_FLAT_BATCH (CRH_FLAT_THREADS / 8) // items of a batch at most
 #endif
+#ifndef CRH_BIN_LOADS_ITEMS
+#define CRH_BIN_LOADS_ITEMS 1 // k_bin_flat's item records: the item_elsewhere byte with the item's other words (0: in front of them, a round trip of its own)
+#endif
+#ifndef CRH_BIN_LOADS_DIRECT
+#define CRH_BIN_LOADS_DIRECT 1 // direct tile lists in a batch that replays: a tile's place and room are fetched once per pool cell, beside the cell's atomic; 0: per entry
+#endif
 #ifndef CRH_FLAT_HITS
 #define CRH_FLAT_HITS 400 // hit records per wavefront in the table of a workgroup that replays (k_bin_flat<S, T, true>): what the 128-thread tables leave of 160 KiB / 7, in whole
                           // LDS blocks — 23 024 of 23 040 B. The batch's free edge places come on top (10 000 paths need up to 1 109 records a batch, glyphs 733).
@@ -1184,8 +1386,16 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         if (kReplay && tid == 0u) replay_off = 0u;
         if (tid < n_cand) {
             const uint32_t item = next + tid;
+#if CRH_BIN_LOADS_ITEMS
+            // (a pass with a slab: the item has no tile row in it — neither binned here nor queued.) The byte is asked for with the item's other words, not in
+            // front of them: its address is a select — without the table, a byte of the item's slot_begin word, which is read anyway —, its use is the last here.
+            const uint8_t* const elsewhere_at = r.item_elsewhere ? r.item_elsewhere + item : reinterpret_cast<const uint8_t*>(r.slot_begin + item);
+            const uint32_t elsewhere_byte = *elsewhere_at;
+            const DrawItem it = item_of(r, item);
+#else
             const DrawItem it = item_of(r, item);
             const bool elsewhere = r.item_elsewhere && r.item_elsewhere[item] != 0u; // (a pass with a slab: the item has no tile row in it — neither binned here nor queued)
+#endif
             const ItemSlots k = item_slots(s, it);
             FlatItem& fi = items[tid];
             fi.ctx = item_ctx(s, r, it, k.cb);
@@ -1194,6 +1404,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             fi.n_tri = k.n_tri, fi.n_fe = k.n_fe, fi.n_hull = k.n_hull, fi.n_hull_chain = k.n_hull;
             const float* c = fi.ctx.col;
             const bool opaque = c[3] == 1.0f && is_finite(c[0]) && is_finite(c[1]) && is_finite(c[2]) && r.occlude != 0u && (r.debug & 32768u) == 0u;
+#if CRH_BIN_LOADS_ITEMS
+            const bool elsewhere = r.item_elsewhere && elsewhere_byte != 0u;
+#endif
             const bool oversize = k.n_tri > kFlatTris || k.n_fe + k.n_hull > kFlatEdges || all_queued || slot0 + k.total > r.slot_capacity;
             fi.flags = (opaque ? kFiOpaque : 0u) | ((oversize || elsewhere) ? kFiSkip : 0u) | ((oversize && !elsewhere && slot0 + k.total <= r.slot_capacity) ? kFiQueue : 0u);
             fi.box[0] = fi.box[1] = 0x7FFFFFFF, fi.box[2] = fi.box[3] = (int)0x80000000;
@@ -1227,6 +1440,66 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         // writes its records at once.
         // A lane keeps nothing of its edges across the triangle's set-up: they go to the LDS tables the walks read anyway as soon as they are loaded
         // (LDS accesses are counted apart from the vector-memory ones) and come back from there for the record stores.
+        FlatTri tri;
+        tri.nt = 0u, tri.item = 0u, tri.key = 0u, tri.bx0 = tri.bx1 = tri.by0 = 0u;
+        tri.test = TileTest{};
+        PlainTri corners;
+        corners.valid = false;
+#if CRH_BIN_LOADS_TRIS
+        TriRaw tri_raw = {};
+#endif
+#if CRH_BIN_LOADS_EDGES
+        // Two waits for all of it: the flags of every round's fill edges; then every round's vertices and — issued behind them, in front of the
+        // wait — the triangle's.
+        {
+            uint32_t edge_item[kFlatEdgeRounds], edge_bits[kFlatEdgeRounds];
+            EdgeFlags edge_fl[kFlatEdgeRounds];
+            EdgeVerts edge_v[kFlatEdgeRounds];
+#pragma unroll
+            for (int k = 0; k < (int)kFlatEdgeRounds; ++k) {
+                const uint32_t e = tid + kFlatThreads * (uint32_t)k;
+                const bool active = e < n_edges;
+                const uint32_t j = active ? find_item(edge_begin, e) : 0u, i = e - edge_begin[j];
+                const FlatItem& fi = items[j];
+                edge_item[k] = j;
+                edge_fl[k] = load_edge_flags(s, fi.ctx, fi.n_fe, i, active && i < fi.n_fe);
+            }
+#pragma unroll
+            for (int k = 0; k < (int)kFlatEdgeRounds; ++k) hold_edge_flags(edge_fl[k]);
+#pragma unroll
+            for (int k = 0; k < (int)kFlatEdgeRounds; ++k) {
+                const uint32_t e = tid + kFlatThreads * (uint32_t)k, j = edge_item[k];
+                const FlatItem& fi = items[j];
+                const EdgeWhere w = edge_where(s, fi.ctx, fi.n_fe, fi.n_hull, e - edge_begin[j], edge_fl[k]);
+                edge_bits[k] = w.bits;
+                edge_v[k] = load_edge_verts(w, e < n_edges);
+            }
+#if CRH_BIN_LOADS_TRIS
+            if (tid < n_tris) {
+                const uint32_t j = find_item(tri_begin, tid), t = tid - tri_begin[j];
+                const FlatItem& fi = items[j];
+                const ItemCtx& ctx = fi.ctx;
+                const uint32_t c = t < ctx.cb[1] ? t : t - ctx.cb[1] + ctx.cb[2]; // the Shape's candidate numbering without the solid strips
+                issue_plain_triangle(s, ctx, c, tri_raw);
+                tri.key = fi.slot0 + 4u * t, tri.item = j;
+            }
+#endif
+#pragma unroll
+            for (int k = 0; k < (int)kFlatEdgeRounds; ++k) hold_edge_verts(edge_v[k]);
+#if CRH_BIN_LOADS_TRIS
+            hold_plain_triangle(tri_raw);
+#endif
+#pragma unroll
+            for (int k = 0; k < (int)kFlatEdgeRounds; ++k) {
+                const uint32_t e = tid + kFlatThreads * (uint32_t)k, j = edge_item[k];
+                if (e < n_edges) {
+                    const BinEdge loaded = finish_edge(rt, items[j].ctx, edge_bits[k], edge_v[k]);
+                    edge_table[e] = pack_edge(loaded);
+                    edge_flags[e] = (uint16_t)pack_edge_flags(loaded, j);
+                }
+            }
+        }
+#else
 #pragma unroll
         for (int k = 0; k < (int)kFlatEdgeRounds; ++k) {
             const uint32_t e = tid + kFlatThreads * (uint32_t)k;
@@ -1238,12 +1511,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
                 edge_flags[e] = (uint16_t)pack_edge_flags(loaded, j);
             }
         }
-        CRH_FLAT_PHASE(1) // edge set-up
-        FlatTri tri;
-        tri.nt = 0u, tri.item = 0u, tri.key = 0u, tri.bx0 = tri.bx1 = tri.by0 = 0u;
-        tri.test = TileTest{};
-        PlainTri corners;
-        corners.valid = false;
+#endif
+        CRH_FLAT_PHASE(1) // edge set-up (with CRH_BIN_LOADS_TRIS: the wait for the triangle's vertices too)
+#if CRH_BIN_LOADS_TRIS && CRH_BIN_LOADS_EDGES
+        if (tid < n_tris) finish_plain_triangle(items[tri.item].ctx, tri_raw, corners);
+#else
         if (tid < n_tris) {
             const uint32_t j = find_item(tri_begin, tid), t = tid - tri_begin[j];
             const FlatItem& fi = items[j];
@@ -1252,6 +1524,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             load_plain_triangle(s, ctx, c, corners);
             tri.key = fi.slot0 + 4u * t, tri.item = j;
         }
+#endif
         // ---- stores and LDS. The triangle's record in two halves whose values do not live at the same time: the coverage half, which the tile test
         // and the boxes are taken from before it is stored, then the fragment half.
 #ifdef CRH_ABLATE
@@ -1572,11 +1845,26 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         }
         lds_barrier();
         uint32_t my_synth = 0, my_opaque = 0;
+        // Direct tile lists in a batch that replays: where a tile's list lies (r.tile_base) is a property of the pool cell, so 2a asks for it beside the cell's
+        // atomic — all of a lane's cells in flight together — and leaves the cell two addresses instead of a position and a tile: where the first entry of the
+        // item's edges and triangles goes in r.tile_list (pool_cursor) and where the tile's place ends (pool_back). The synthetic entries are stored then and
+        // there, 2b has nothing left to do, and pass 3 is LDS reads and stores: no entry waits for a load. (stage_flush_direct's test, entry by entry, as ever:
+        // every position below the room is written, none beyond it or beyond pair_capacity, and an entry that finds no room raises overflow[0].)
+        const bool direct_cells = kReplay && CRH_BIN_LOADS_DIRECT != 0 && replay && r.direct != 0u; // (uniform)
+        // the keys of a cell's synthetic entries from its verdict (below)
+        struct SynthKeys {
+            uint32_t cover, bd, hbd;
+        };
+        auto synth_keys = [&](const FlatItem& fi, uint32_t verdict) {
+            const uint32_t cbd1 = 1u + ((verdict >> 25) & 1u) - ((verdict >> 27) & 1u), chbd1 = 1u + ((verdict >> 26) & 1u) - ((verdict >> 28) & 1u); // sign of either backdrop + 1
+            return SynthKeys{fi.synth_b + cbd1 + 3u * chbd1 + ((verdict >> 29) & 1u ? kCoverOpaque : ((verdict >> 30) & 1u ? kCoverHull : 0u)),
+                             fi.synth_a + ((verdict >> 25) & 1u ? 0u : 1u), fi.synth_a + ((verdict >> 26) & 1u ? 2u : 3u)};
+        };
         {
-            uint32_t reserved[kChunks], lefts[kChunks];
+            uint32_t reserved[kChunks], lefts[kChunks], place[kChunks], place_end[kChunks];
 #pragma unroll
             for (uint32_t ch = 0; ch < kChunks; ++ch) { // 2a
-                reserved[ch] = 0u, lefts[ch] = 0u;
+                reserved[ch] = 0u, lefts[ch] = 0u, place[ch] = 0u, place_end[ch] = 0u;
                 const uint32_t p = ch * kFlatThreads + tid;
                 if (p >= n_pool) continue;
                 const uint32_t j = find_item(pool_begin, p);
@@ -1598,14 +1886,43 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
                 my_synth += left;
                 my_opaque += replaces_tile ? 1u : 0u;
                 if (left + n_touching) reserved[ch] = atomicAdd(&r.tile_count[tile], left + n_touching);
+                if (direct_cells) place[ch] = r.tile_base[tile], place_end[ch] = r.tile_base[tile + 1u];
                 // the verdict, for 2b: left (bits 0-11), backdrop units (12-23), COVER entry (24), bd > 0 (25), hbd > 0 (26), bd < 0 (27), hbd < 0 (28),
                 // the COVER entry replaces the tile (29) or lies over all of it (30) — 2b makes the COVER key of the last six
                 pool_back[p] = (int)(left | (n_bd << 12) | (cover ? 1u << 24 : 0u) | (cbd > 0 ? 1u << 25 : 0u) | (chbd > 0 ? 1u << 26 : 0u) | (cbd < 0 ? 1u << 27 : 0u) | (chbd < 0 ? 1u << 28 : 0u) |
                                      (replaces_tile ? 1u << 29 : 0u) | (hull_over_tile ? 1u << 30 : 0u));
             }
+            // ONE wait for all of it, here, in front of the first key store (behind a store, every wait for a load is a wait for that store too) and on either
+            // path (a register still marked as a load's target at the join below would make the next instruction that touches it wait there)
+#pragma unroll
+            for (uint32_t ch = 0; ch < kChunks; ++ch) held(reserved[ch]), held(place[ch]), held(place_end[ch]);
+            if (direct_cells) {
+#pragma unroll
+                for (uint32_t ch = 0; ch < kChunks; ++ch) {
+                    const uint32_t p = ch * kFlatThreads + tid;
+                    if (p >= n_pool) continue;
+                    const uint32_t base = place[ch], room = min(place_end[ch] - base, r.pair_capacity > base ? r.pair_capacity - base : 0u), limit = base + room;
+                    const uint32_t verdict = (uint32_t)pool_back[p];
+                    const SynthKeys keys = synth_keys(items[find_item(pool_begin, p)], verdict);
+                    uint32_t at = base + reserved[ch], n_bd = (verdict >> 12) & 4095u;
+                    bool cover = (verdict >> 24) & 1u, outgrown = false;
+                    for (uint32_t left = lefts[ch]; left != 0u; --left, ++at) {
+                        uint32_t key = keys.hbd;
+                        if (cover)
+                            cover = false, key = keys.cover;
+                        else if (n_bd)
+                            --n_bd, key = keys.bd;
+                        if (at < limit) r.tile_list[at] = key;
+                        else outgrown = true;
+                    }
+                    if (outgrown) r.overflow[0] = 1u; // the tile has outgrown the place the previous frame left it
+                    pool_cursor[p] = at, pool_back[p] = (int)limit;
+                }
+            } else {
 #pragma unroll
             for (uint32_t ch = 0; ch < kChunks; ++ch)
                 if (ch * kFlatThreads + tid < n_pool) pool_cursor[ch * kFlatThreads + tid] = reserved[ch] + lefts[ch]; // where the edges' and triangles' entries go
+            }
         }
         {
             uint32_t a = my_entries, b = my_synth | (my_opaque << 22); // (6 cells per lane, < 4096 entries each: a wavefront's sums stay below 2^22 and 2^10)
@@ -1647,7 +1964,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
         lds_barrier();
         st.at = wave_entries[wave];
 #pragma unroll 1
-        for (uint32_t ch = 0; ch * kFlatThreads < n_pool; ++ch) { // 2b
+        for (uint32_t ch = 0; !direct_cells && ch * kFlatThreads < n_pool; ++ch) { // 2b
             const uint32_t p = ch * kFlatThreads + tid;
             const bool active = p < n_pool;
             const uint32_t j = active ? find_item(pool_begin, p) : 0u;
@@ -1655,9 +1972,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             const uint32_t q = active ? p - pool_begin[j] : 0u, row_len = max(fi.nx, 1u), qy = q / row_len, qx = q - qy * row_len;
             const uint32_t tile = (fi.ty_a + qy) * r.tiles_x + fi.tx_a + qx;
             const uint32_t verdict = active ? (uint32_t)pool_back[p] : 0u;
-            const uint32_t cbd1 = 1u + ((verdict >> 25) & 1u) - ((verdict >> 27) & 1u), chbd1 = 1u + ((verdict >> 26) & 1u) - ((verdict >> 28) & 1u); // sign of either backdrop + 1
-            const uint32_t cover_key = fi.synth_b + cbd1 + 3u * chbd1 + ((verdict >> 29) & 1u ? kCoverOpaque : ((verdict >> 30) & 1u ? kCoverHull : 0u));
-            const uint32_t bd_key = fi.synth_a + ((verdict >> 25) & 1u ? 0u : 1u), hbd_key = fi.synth_a + ((verdict >> 26) & 1u ? 2u : 3u);
+            const SynthKeys keys = synth_keys(fi, verdict);
+            const uint32_t cover_key = keys.cover, bd_key = keys.bd, hbd_key = keys.hbd;
             uint32_t left = verdict & 4095u, n_bd = (verdict >> 12) & 4095u, pos = active ? pool_cursor[p] - left : 0u;
             bool cover = (verdict >> 24) & 1u;
             if (replay && active) pool_back[p] = (int)tile; // (the verdict is read: the cell's word now tells the replay which tile the cell is)
@@ -1686,11 +2002,15 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(CRH_FLA
             stage_flush_reserved(st, r, lane); // (the synthetic entries of 2b)
             for (uint32_t i = lane; i < n_hits; i += 64u) {
                 const uint32_t rec = *hit_slot(i), cell = (rec >> kHitIndexBits) & ((1u << kHitCellBits) - 1u);
+                // (direct_cells: `pos` is the entry's address in r.tile_list and `tile` the end of the tile's place there)
                 const uint32_t tile = (uint32_t)pool_back[cell], pos = pool_cursor[cell] + (rec & ((1u << kHitIndexBits) - 1u)), key = key0 + (rec >> (kHitIndexBits + kHitCellBits));
 #ifdef CRH_ABLATE
                 if (r.debug & 512u) continue;
 #endif
-                if (r.direct) { // (stage_flush_direct's store)
+                if (direct_cells) {
+                    if (pos < tile) r.tile_list[pos] = key;
+                    else r.overflow[0] = 1u; // the tile has outgrown the place the previous frame left it
+                } else if (r.direct) { // (stage_flush_direct's store)
                     const uint32_t place = r.tile_base[tile];
                     if (pos < r.tile_base[tile + 1u] - place && place + pos < r.pair_capacity) r.tile_list[place + pos] = key;
                     else r.overflow[0] = 1u; // the tile has outgrown the place the previous frame left it
