@@ -9,11 +9,13 @@ from .path import (Cap, CurveApproximation, DashInterval, DynamicStrokeOptions, 
                    batch_from_shapes)
 from .renderer import (BlendMode, BlurEdge, ColorMatrix, CompositeOp, ConvolveKernel, DistantLight, Filter, GradientStop, Image, ImagePaint, LightingOp,  # noqa: F401
                        MorphologyOp, Paint, PointLight, SpotLight, Spread, blur_taps, color_filter_texels, composite_texels, convolve_coefficients, convolve_texels,
-                       lighting_texels, morphology_size, morphology_texels, TurbulenceKind, turbulence_tables, turbulence_texels, Channel, displace_offset, displace_texels)
+                       lighting_texels, morphology_size, morphology_texels, TurbulenceKind, turbulence_tables, turbulence_texels, Channel, displace_offset, displace_texels,
+                       DistanceMode, distance_code, distance_size, distance_texels)
 
 __all__ = ["ContrastError", "PathBatch", "Cap", "CurveApproximation", "DashInterval", "DynamicStrokeOptions", "Join", "Path", "SegmentType",
            "StrokeOptions", "batch_from_shapes", "GradientStop", "Paint", "Spread", "Filter", "Image", "ImagePaint", "BlurEdge", "blur_taps",
            "CompositeOp", "BlendMode", "composite_texels", "ColorMatrix", "color_filter_texels", "MorphologyOp", "morphology_size", "morphology_texels",
            "ConvolveKernel", "convolve_coefficients", "convolve_texels", "LightingOp", "DistantLight", "PointLight", "SpotLight", "lighting_texels",
            "TurbulenceKind", "turbulence_tables", "turbulence_texels",
-           "Channel", "displace_offset", "displace_texels"]
+           "Channel", "displace_offset", "displace_texels",
+           "DistanceMode", "distance_code", "distance_size", "distance_texels"]

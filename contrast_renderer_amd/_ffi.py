@@ -249,6 +249,10 @@ class DisplaceC(C.Structure):  # crh_displace
     _fields_ = [("scale", C.c_float * 2), ("x_channel", C.c_uint32), ("y_channel", C.c_uint32), ("filter", C.c_uint32), ("edge", C.c_uint32)]
 
 
+class DistanceC(C.Structure):  # crh_distance
+    _fields_ = [("mode", C.c_uint32), ("channel", C.c_uint32), ("threshold", C.c_uint32), ("spread", C.c_uint32), ("edge", C.c_uint32)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -351,6 +355,11 @@ def load_library():
         "crh_displace_offset": (C.c_int, [C.POINTER(DisplaceC), C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
         "crh_displace_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, V, C.POINTER(DisplaceC), V]),
         "crh_image_displace": (C.c_int, [V, V, C.POINTER(DisplaceC), C.POINTER(V)]),
+        "crh_distance_validate": (C.c_int, [C.POINTER(DistanceC)]),
+        "crh_distance_code": (C.c_int, [C.POINTER(DistanceC), C.c_uint64, C.POINTER(C.c_uint32)]),
+        "crh_distance_size": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(DistanceC), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "crh_distance_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.POINTER(DistanceC), V]),
+        "crh_image_distance_field": (C.c_int, [V, C.POINTER(DistanceC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

@@ -1,5 +1,5 @@
-// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, and the eight
-// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace) with their host rules (crh_*_texels) and validators.
+// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, and the nine
+// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field) with their host rules (crh_*_texels) and validators.
 // Host code only: the kernels are image_filter.hip's and raster.hip's (launch.hpp), the rules are the filters' headers. Of a renderer it
 // uses its device, its stream and "wait for every stream" (api_internal.hpp); what is about a frame or a paint table stays in api.hip.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "composite.hpp"
 #include "convolve.hpp"
 #include "displace.hpp"
+#include "distance.hpp"
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
@@ -629,5 +630,88 @@ crh_status crh_image_displace(const crh_image* src, const crh_image* map, const 
     if (map->renderer != src->renderer) return refuse(kDisplace, "the images belong to different renderers");
     return filter_call("crh_image_displace", src->renderer, src->width, src->height, out, [&](FilterJob& job) {
         job.launch("k_image_displace", [&] { launch_image_displace(texels_of(src), texels_of(map), src->width, src->height, f, job.texels(), job.stream); });
+    });
+}
+// ---- distance field
+namespace {
+static_assert(CRH_MAX_DISTANCE_SPREAD == kDistanceMaxSpread && CRH_DISTANCE_OUTSIDE == kDistanceOutside && CRH_DISTANCE_INSIDE == kDistanceInside && CRH_BLUR_EDGE_TRANSPARENT == kDistanceTransparent &&
+                  CRH_CHANNEL_A == 3,
+              "distance.hpp's limit, modes, edge and channel shift are the header's");
+constexpr const char* kDistance = "crh_distance_validate";
+// validates the fields and prepares them: the one check of the five entry points
+crh_status distance_constants(const crh_distance* how, DistanceConstants* f) {
+    if (!how) return refuse(kDistance, "a null argument");
+    if (how->mode > CRH_DISTANCE_INSIDE) return refuse(kDistance, "mode is above CRH_DISTANCE_INSIDE");
+    if (how->channel > CRH_CHANNEL_A) return refuse(kDistance, "channel is above CRH_CHANNEL_A");
+    if (how->threshold < 1u || how->threshold > 255u) return refuse(kDistance, "threshold is outside [1, 255]");
+    if (how->spread < 1u || how->spread > CRH_MAX_DISTANCE_SPREAD) return refuse(kDistance, "spread is outside [1, CRH_MAX_DISTANCE_SPREAD]");
+    if (how->edge > CRH_BLUR_EDGE_REFLECT) return refuse(kDistance, "edge is above CRH_BLUR_EDGE_REFLECT");
+    f->mode = how->mode, f->shift = 8u * how->channel, f->threshold = how->threshold, f->spread = how->spread, f->edge = how->edge;
+    return CRH_OK;
+}
+// The checks after the null arguments, in the header's order, in two steps, so that crh_distance_texels can name an output that is
+// its input between them: the fields and the source's size, then the result's size (written on success only).
+crh_status distance_source(uint32_t width, uint32_t height, const crh_distance* how, DistanceConstants* f) {
+    const crh_status st = distance_constants(how, f);
+    return st != CRH_OK ? st : check_size(kDistance, width, height);
+}
+crh_status distance_result(uint32_t width, uint32_t height, const DistanceConstants& f, uint32_t* out_width, uint32_t* out_height) {
+    const uint32_t grown = distance_grows(f.mode, f.edge) ? 2u * f.spread : 0u;
+    if (width + grown > kMaxImageSize || height + grown > kMaxImageSize) return refuse(kDistance, "a side of the grown result exceeds 16384", CRH_ERR_UNSUPPORTED);
+    *out_width = width + grown, *out_height = height + grown;
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_distance_validate(const crh_distance* how) {
+    DistanceConstants f;
+    return distance_constants(how, &f);
+}
+crh_status crh_distance_code(const crh_distance* how, uint64_t squared_distance, uint32_t* code) {
+    if (!how || !code) return refuse(kDistance, "a null argument");
+    DistanceConstants f;
+    const crh_status st = distance_constants(how, &f);
+    if (st != CRH_OK) return st;
+    DistanceThresholds thresholds;
+    distance_thresholds(f.spread, &thresholds);
+    const uint64_t cap = (uint64_t)f.spread * f.spread; // every D2 >= spread^2 gives 255
+    *code = distance_texel(distance_code(thresholds.t, (uint32_t)(squared_distance < cap ? squared_distance : cap)), f.mode) & 0xFFu;
+    return CRH_OK;
+}
+crh_status crh_distance_size(uint32_t width, uint32_t height, const crh_distance* how, uint32_t* out_width, uint32_t* out_height) {
+    if (!how || !out_width || !out_height) return refuse(kDistance, "a null argument");
+    DistanceConstants f;
+    const crh_status st = distance_source(width, height, how, &f);
+    return st != CRH_OK ? st : distance_result(width, height, f, out_width, out_height);
+}
+crh_status crh_distance_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_distance* how, void* out_rgba8) {
+    if (!rgba8 || !how || !out_rgba8) return refuse(kDistance, "a null argument");
+    DistanceConstants f;
+    uint32_t w = 0u, h = 0u;
+    crh_status st = distance_source(width, height, how, &f);
+    if (st != CRH_OK) return st;
+    if (out_rgba8 == rgba8) return refuse(kDistance, "out_rgba8 is rgba8");
+    st = distance_result(width, height, f, &w, &h);
+    if (st != CRH_OK) return st;
+    distance_run(static_cast<const uint8_t*>(rgba8), width, height, f, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_distance_field(const crh_image* src, const crh_distance* how, crh_image** out) {
+    if (!src || !how || !out) return refuse(kDistance, "a null argument");
+    DistanceConstants f;
+    crh_status st = distance_constants(how, &f); // (the fields before the image: a refused `how` does not look at it)
+    if (st == CRH_OK && !src->renderer) st = refuse(kDistance, "a null argument");
+    uint32_t out_w = 0u, out_h = 0u;
+    if (st == CRH_OK) st = check_size(kDistance, src->width, src->height);
+    if (st == CRH_OK) st = distance_result(src->width, src->height, f, &out_w, &out_h);
+    if (st != CRH_OK) return st;
+    const uint32_t origin = distance_grows(f.mode, f.edge) ? f.spread : 0u;
+    DistanceThresholds thresholds; // (alive until filter_call returns: the staged bytes of the scratch)
+    distance_thresholds(f.spread, &thresholds);
+    // one scratch: the thresholds at its head, then g, a byte of column distance per texel of the result
+    return filter_call("crh_image_distance_field", src->renderer, out_w, out_h, out, [&](FilterJob& job) {
+        uint8_t* scratch = static_cast<uint8_t*>(job.scratch(sizeof thresholds + (size_t)out_w * out_h, &thresholds, sizeof thresholds));
+        uint8_t* g = scratch ? scratch + sizeof thresholds : nullptr; // (a failed allocation: no launch follows)
+        job.launch("k_image_distance_v", [&] { launch_image_distance_v(texels_of(src), src->width, src->height, g, out_w, out_h, origin, f, job.stream); });
+        job.launch("k_image_distance_h", [&] { launch_image_distance_h(g, out_w, out_h, reinterpret_cast<const uint32_t*>(scratch), f, job.texels(), job.stream); });
     });
 }

@@ -9,6 +9,7 @@
 // crh_image_lighting: k_image_lighting lights the alpha channel as a height field with the rule of lighting.hpp, binary64 arithmetic on a 3 x 3 stencil.
 // crh_image_turbulence: k_image_turbulence makes a noise image with the rule of turbulence.hpp, binary64 arithmetic on gradients gathered from LDS.
 // crh_image_displace: k_image_displace reads an image through per-texel offsets taken from a second one with the rule of displace.hpp, a gather from global memory.
+// crh_image_distance_field: k_image_distance_v and k_image_distance_h code the exact Euclidean distance to a shape with the rule of distance.hpp, separably through a byte of column distance per texel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include "composite.hpp"
 #include "convolve.hpp"
 #include "displace.hpp"
+#include "distance.hpp"
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
@@ -819,6 +821,136 @@ void launch_image_displace(const uint32_t* src, const uint32_t* map, uint32_t w,
     else CRH_DISPLACE_LAUNCH(kDisplaceRuntimeEdge);
 #endif
 #undef CRH_DISPLACE_LAUNCH
+}
+
+namespace {
+constexpr int kDistanceColumns = 64;   // vertical: columns per workgroup, one per lane of its single wave
+constexpr int kDistanceSegment = 256;  // horizontal: output texels of one row per workgroup, one per lane (k_image_morph_h's segment)
+constexpr int kDistanceApron = 255;    // CRH_MAX_DISTANCE_SPREAD: column distances staged beyond the segment on either side
+constexpr int kDistanceOwned = (kDistanceSegment + 2 * kDistanceApron + kDistanceSegment - 1) / kDistanceSegment; // 3: staged bytes per lane
+static_assert(kDistanceApron == (int)kDistanceMaxSpread, "the apron holds the largest spread");
+} // namespace
+
+// Vertical pass: the source to g, one byte per texel of the result: the distance along the column to the nearest target (distance.hpp:
+// a texel inside the shape for OUTSIDE, one that is not for INSIDE), 0 .. spread - 1, or 255 where there is none within reach. Grid
+// (ceil(out_w / 64), ceil(out_h / ROWS)), one wave: lanes run along x, so every global and LDS access of the wave is 64 consecutive
+// words or bytes. The workgroup owns the output rows j0 .. j0 + ROWS - 1 of 64 columns. A lane first walks its column UP, from
+// spread - 1 rows below its last row to its first, counting the rows since the last target, and stores the count of each of its own rows
+// in LDS (its own byte: no lane reads another's, so no barrier; a count of 0 is a target); then DOWN from spread - 1 rows above its
+// first row, counting again, over its own rows from the LDS bytes alone: g is the smaller of the two counts. ROWS + 2 (spread - 1) rows
+// read for ROWS outputs, at any ROWS; the launcher takes 32 rows for spreads up to 16 and 128 above. `origin`: the source texel
+// under result texel (0, 0) is (-origin, -origin) (the spread for a growing result, else 0). The row index is wave-uniform: the wrap is
+// scalar arithmetic, its one remainder per walk is taken at the walk's first row (morphology.hpp's phase), and the address always comes
+// from a wrapped or clamped row and column, so the loads of an unrolled stretch are unconditional and in flight together.
+template <bool INSIDE, int ROWS>
+__global__ __launch_bounds__(kDistanceColumns) void k_image_distance_v(const uint32_t* __restrict__ src, uint32_t src_w, uint32_t src_h, uint8_t* __restrict__ g, uint32_t out_w, uint32_t out_h,
+                                                                        uint32_t origin, DistanceConstants f) {
+    __shared__ uint8_t below[ROWS][kDistanceColumns];
+    constexpr uint32_t MODE = INSIDE ? kDistanceInside : kDistanceOutside;
+    const uint32_t lane = threadIdx.x, x = blockIdx.x * (uint32_t)kDistanceColumns + lane;
+    if (x >= out_w) return; // (no barrier below: a lane shares nothing with its neighbours)
+    const uint32_t j0 = blockIdx.y * (uint32_t)ROWS;
+    const uint32_t rows = out_h - j0 < (uint32_t)ROWS ? out_h - j0 : (uint32_t)ROWS; // (j0 < out_h by the grid): every LDS index is below ROWS
+    const uint32_t reach = (f.spread < kDistanceMaxSpread ? f.spread : kDistanceMaxSpread) - 1u;
+    const int n = (int)src_h, period = morphology_period(n, f.edge);
+    const int xs = (int)x - (int)origin;
+    const bool in_x = f.edge != kDistanceTransparent || (uint32_t)xs < src_w;
+    const uint32_t* column = src + morphology_wrap(xs, (int)src_w, f.edge); // (TRANSPARENT clamps: an address the lane may read)
+    auto target_of = [&](int i, int phase) {
+        const uint32_t texel = column[(size_t)morphology_wrap_at(i, phase, n, f.edge) * src_w];
+        const bool inside = distance_inside(texel, f) && (f.edge != kDistanceTransparent || ((uint32_t)i < src_h && in_x));
+        return distance_target(inside, MODE);
+    };
+    const int first = (int)j0 - (int)origin, last = first + (int)rows - 1; // the source rows under the workgroup's first and last row
+    uint32_t d = kDistanceNone;
+    int i = last + (int)reach, phase = morphology_phase(i, n, f.edge);
+#pragma unroll 8
+    for (uint32_t k = 0u; k < reach; ++k, --i) {
+        d = distance_step(d, target_of(i, phase));
+        phase = morphology_phase_before(phase, period);
+    }
+#pragma unroll 8
+    for (uint32_t m = rows; m-- > 0u; --i) {
+        d = distance_step(d, target_of(i, phase));
+        phase = morphology_phase_before(phase, period);
+        below[m][lane] = (uint8_t)d;
+    }
+    d = kDistanceNone;
+    i = first - (int)reach, phase = morphology_phase(i, n, f.edge);
+#pragma unroll 8
+    for (uint32_t k = 0u; k < reach; ++k, ++i) {
+        d = distance_step(d, target_of(i, phase));
+        phase = morphology_phase_next(phase, period);
+    }
+    for (uint32_t m = 0u; m < rows; ++m) {
+        const uint32_t b = below[m][lane];
+        d = distance_step(d, b == 0u);
+        g[(size_t)(j0 + m) * out_w + x] = (uint8_t)distance_column(d < b ? d : b, f.spread);
+    }
+}
+
+// Horizontal pass: g to the result, D2(x, y) = min over dx of dx^2 + g(x + dx, y)^2. Grid (ceil(out_w / 256), out_h), 256 lanes: the
+// workgroup stages the 256 + 2 spread bytes of g its segment of one row reads (at most 766, lane l the bytes l, l + 256 and l + 512) and
+// the 255 thresholds of the spread (distance.hpp; made on the host, one word per lane). Under a same-size edge a column outside the
+// row is read through the wrap; under TRANSPARENT it is "none" (OUTSIDE: nothing out there) or 0 (INSIDE: off the image is off the
+// shape). A segment whose staged bytes are all "none" writes its bytes without scanning (the barrier that publishes the bytes also
+// votes). Otherwise a lane scans dx = 0, 1, .. and stops as soon as dx^2 reaches the best value found (distance_scan): two LDS bytes at
+// lane +- dx per step, consecutive lanes consecutive bytes; neighbouring texels' distances differ by at most one, so a wave's lanes
+// stop within a few steps of each other. Then c(D2) by eight halvings over the thresholds in LDS: no square root. Every LDS index is
+// lane + spread +- dx with dx < spread, inside the staged bytes; every address of g comes from a wrapped or range-checked column.
+template <bool INSIDE>
+__global__ __launch_bounds__(kDistanceSegment) void k_image_distance_h(const uint8_t* __restrict__ g, uint32_t out_w, const uint32_t* __restrict__ thresholds, DistanceConstants f,
+                                                                        uint32_t* __restrict__ out) {
+    __shared__ uint8_t staged[kDistanceOwned * kDistanceSegment];
+    __shared__ uint32_t codes[256];
+    constexpr uint32_t MODE = INSIDE ? kDistanceInside : kDistanceOutside;
+    const uint32_t j = blockIdx.y, o0 = blockIdx.x * (uint32_t)kDistanceSegment, lane = threadIdx.x;
+    const uint32_t spread = f.spread < kDistanceMaxSpread ? f.spread : kDistanceMaxSpread; // (the host refuses more: the bound keeps every LDS index staged)
+    const uint8_t* row = g + (size_t)j * out_w;
+    const uint32_t n_staged = (uint32_t)kDistanceSegment + 2u * spread;
+    const int first = (int)o0 - (int)spread; // the column of staged byte 0
+    codes[lane] = thresholds[lane];
+    int any = 0;
+#pragma unroll
+    for (int t = 0; t < kDistanceOwned; ++t) {
+        const uint32_t at = lane + (uint32_t)(t * kDistanceSegment);
+        if (at < n_staged) {
+            const int i = first + (int)at;
+            uint32_t v = INSIDE ? 0u : kDistanceNone;
+            if (f.edge != kDistanceTransparent) v = row[morphology_wrap(i, (int)out_w, f.edge)];
+            else if ((uint32_t)i < out_w) v = row[i];
+            staged[at] = (uint8_t)v;
+            any |= v != kDistanceNone;
+        }
+    }
+    const bool scan = __syncthreads_or(any) != 0;
+    const uint32_t o = o0 + lane;
+    if (o >= out_w) return;
+    uint32_t c = 255u; // nothing within the spread
+    if (scan) {
+        const uint8_t* centre = staged + lane + spread;
+        c = distance_code(codes, distance_scan(spread, [&](int dx) -> uint32_t { return centre[dx]; }));
+    }
+    out[(size_t)j * out_w + o] = distance_texel(c, MODE);
+}
+
+void launch_image_distance_v(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint8_t* g, uint32_t out_w, uint32_t out_h, uint32_t origin, const DistanceConstants& f, hipStream_t stream) {
+    const uint32_t columns = (out_w + (uint32_t)kDistanceColumns - 1u) / (uint32_t)kDistanceColumns;
+#define CRH_DISTANCE_V_LAUNCH(ROWS)                                                                                                                                                  \
+    do {                                                                                                                                                                             \
+        const dim3 grid(columns, (out_h + (ROWS) - 1u) / (ROWS)); /* <= 256 x 512 */                                                                                                 \
+        if (f.mode == kDistanceInside) hipLaunchKernelGGL((k_image_distance_v<true, ROWS>), grid, dim3(kDistanceColumns), 0, stream, src, src_w, src_h, g, out_w, out_h, origin, f); \
+        else hipLaunchKernelGGL((k_image_distance_v<false, ROWS>), grid, dim3(kDistanceColumns), 0, stream, src, src_w, src_h, g, out_w, out_h, origin, f);                          \
+    } while (0)
+    if (f.spread <= 16u) CRH_DISTANCE_V_LAUNCH(32);
+    else CRH_DISTANCE_V_LAUNCH(128); // (more workgroups beat fewer rows read: 256 and 512 rows were measured at spread 255 and dropped)
+#undef CRH_DISTANCE_V_LAUNCH
+}
+
+void launch_image_distance_h(const uint8_t* g, uint32_t out_w, uint32_t out_h, const uint32_t* thresholds, const DistanceConstants& f, uint32_t* out, hipStream_t stream) {
+    const dim3 grid((out_w + (uint32_t)kDistanceSegment - 1u) / (uint32_t)kDistanceSegment, out_h); // out_h <= 16384 rows: below the grid's limit of 65535
+    if (f.mode == kDistanceInside) hipLaunchKernelGGL(k_image_distance_h<true>, grid, dim3(kDistanceSegment), 0, stream, g, out_w, thresholds, f, out);
+    else hipLaunchKernelGGL(k_image_distance_h<false>, grid, dim3(kDistanceSegment), 0, stream, g, out_w, thresholds, f, out);
 }
 
 } // namespace crh

@@ -68,6 +68,11 @@ void launch_image_turbulence(const TurbulenceTables* tables, uint32_t w, uint32_
 // image_filter.hip: crh_image_displace's kernel (displace.hpp holds the rule; f.filter < 2, f.edge < 4, f.channel < 4). src, map and out: h rows of w texels; out is neither input.
 struct DisplaceConstants;
 void launch_image_displace(const uint32_t* src, const uint32_t* map, uint32_t w, uint32_t h, const DisplaceConstants& f, uint32_t* out, hipStream_t stream);
+// image_filter.hip: crh_image_distance_field's kernels (distance.hpp holds the rule; f.mode < 2, f.shift = 0, 8, 16 or 24, 1 <= f.spread <= 255, f.edge < 4). `g`: out_h rows of out_w bytes, the
+// column distances between the two passes; `origin`: the source texel under result texel (0, 0) is (-origin, -origin); `thresholds`: the 256 words of distance_thresholds(f.spread) on the device.
+struct DistanceConstants;
+void launch_image_distance_v(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint8_t* g, uint32_t out_w, uint32_t out_h, uint32_t origin, const DistanceConstants& f, hipStream_t stream);
+void launch_image_distance_h(const uint8_t* g, uint32_t out_w, uint32_t out_h, const uint32_t* thresholds, const DistanceConstants& f, uint32_t* out, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream); // zeroes n_words 32-bit words with single-wave workgroups (the clear in front of both passes' binning kernels)

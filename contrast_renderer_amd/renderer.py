@@ -784,6 +784,53 @@ def displace_offset(scale, code_x, code_y, x_channel=Channel.A, y_channel=Channe
     return int(q[0]), int(q[1])
 
 
+class DistanceMode(IntEnum):  # crh_distance_mode: what the distance is measured to
+    Outside = 0  # to the shape: 255 on it, falling to 0 at the spread (glow, outline, spread)
+    Inside = 1   # to what is not the shape: 0 off it, rising into it (chisel, inner glow)
+
+
+MAX_DISTANCE_SPREAD = 255  # CRH_MAX_DISTANCE_SPREAD
+
+
+def _distance_arguments(spread, mode, channel, threshold, edge):
+    """-> DistanceC"""
+    how = _ffi.DistanceC()
+    how.mode, how.channel, how.threshold, how.spread, how.edge = int(mode), int(channel), int(threshold), int(spread), int(edge)
+    return how
+
+
+def distance_code(spread, squared_distance, mode=DistanceMode.Outside):
+    """crh_distance_code (host only) -> the result byte of one squared distance D2 between texel centres under `spread`: v = 255 - c
+    (DistanceMode.Outside) or c (DistanceMode.Inside), c = min(255, floor(255 sqrt(D2) / spread + 1/2)) by the integer statement."""
+    how = _distance_arguments(spread, mode, Channel.A, 128, BlurEdge.Transparent)
+    code = C.c_uint32()
+    check(_ffi.load_library().crh_distance_code(C.byref(how), int(squared_distance), C.byref(code)))
+    return int(code.value)
+
+
+def distance_size(width, height, spread, mode=DistanceMode.Outside, channel=Channel.A, threshold=128, edge=BlurEdge.Transparent):
+    """crh_distance_size (host only) -> (width, height) of the result of Image.distance_field on a width x height image: grown by the
+    spread on every side for DistanceMode.Outside under BlurEdge.Transparent, else the same. Raises ContrastError for what
+    Image.distance_field refuses."""
+    how = _distance_arguments(spread, mode, channel, threshold, edge)
+    w, h = C.c_uint32(), C.c_uint32()
+    check(_ffi.load_library().crh_distance_size(int(width), int(height), C.byref(how), C.byref(w), C.byref(h)))
+    return int(w.value), int(h.value)
+
+
+def distance_texels(pixels, spread, mode=DistanceMode.Outside, channel=Channel.A, threshold=128, edge=BlurEdge.Transparent):
+    """crh_distance_texels (host only): the rule of Image.distance_field on a (height, width, 4) uint8 array -> the (height', width', 4)
+    uint8 result (include/contrast_hip.h crh_image_distance_field states the rule)."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"distance_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    w, h = distance_size(pixels.shape[1], pixels.shape[0], spread, mode, channel, threshold, edge)
+    how = _distance_arguments(spread, mode, channel, threshold, edge)
+    out = np.empty((h, w, 4), dtype=np.uint8)
+    check(_ffi.load_library().crh_distance_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, C.byref(how), out.ctypes.data))
+    return out
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -963,6 +1010,22 @@ class Image:
         handle = C.c_void_p()
         check(self.lib.crh_image_displace(self.handle, map.handle, C.byref(how), C.byref(handle)))
         return Image._adopt(self.renderer, handle, (self.width, self.height))
+
+    def distance_field(self, spread, mode=DistanceMode.Outside, channel=Channel.A, threshold=128, edge=BlurEdge.Transparent):
+        """crh_image_distance_field -> a new Image of one level: for every texel the exact Euclidean distance between texel centres to the
+        shape {stored code of `channel` >= `threshold`} (DistanceMode.Outside: 255 on the shape, falling to 0 at `spread` texels) or to
+        what is not the shape (DistanceMode.Inside: 0 off the shape, rising into it), one rounding by an integer statement, on all four
+        channels; built on the device and complete when this returns (a synchronous call). `spread` is an integer in
+        [1, MAX_DISTANCE_SPREAD]. Outside under BlurEdge.Transparent grows the result by the spread on every side, and the result's
+        `origin` is (spread, spread), by blur()'s convention; everything else keeps the size and origin (0, 0). A round outline of 8
+        texels: distance_field(8), a table through color_filter, composite DstOver at the grown origin. This image is not modified."""
+        how = _distance_arguments(spread, mode, channel, threshold, edge)
+        handle = C.c_void_p()
+        check(self.lib.crh_image_distance_field(self.handle, C.byref(how), C.byref(handle)))
+        image = Image._adopt(self.renderer, handle)
+        if int(mode) == DistanceMode.Outside and int(edge) == BlurEdge.Transparent:
+            image.origin = (int(spread), int(spread))
+        return image
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

@@ -673,7 +673,8 @@ crh_status crh_image_color_filter(const crh_image* src, const float* matrix, con
  * of the source is read and the source is not modified. The intermediate (packed RGBA8, the result's width and the source's height) is
  * freed before the call returns; a zero radius on an axis skips that axis's pass. A failed allocation or launch frees everything and
  * returns CRH_ERR_HIP.
- * Limits: the call is synchronous, like its siblings — one wait per call; the structuring element is a rectangle: no disc; the radii are
+ * Limits: the call is synchronous, like its siblings — one wait per call; the structuring element is a rectangle: no disc (a round outline or
+ * spread is crh_image_distance_field under a table of crh_image_color_filter); the radii are
  * integers; the operator acts per channel on premultiplied codes, as SVG does; images are immutable, so there is no in-place variant. */
 #define CRH_MAX_MORPHOLOGY_RADIUS 192u
 typedef enum crh_morphology_op {
@@ -925,6 +926,62 @@ crh_status crh_displace_validate(const crh_displace* how);                      
 crh_status crh_displace_offset(const crh_displace* how, uint32_t code_x, uint32_t code_y, int32_t q[2]); /* host only: q of two straight codes <= 255 */
 crh_status crh_displace_texels(uint32_t width, uint32_t height, const void* rgba8, const void* map_rgba8, const crh_displace* how, void* out_rgba8); /* host only */
 crh_status crh_image_displace(const crh_image* src, const crh_image* map, const crh_displace* how, crh_image** out);
+/* Distance fields: a new image that holds, for every texel, the exact Euclidean distance to a shape, coded into 8 bits over a chosen
+ * spread — the round outline, glow and spread that crh_image_morphology's rectangle cannot make, and the chiselled bevel that a blurred
+ * height field cannot: a 256-entry table of crh_image_color_filter turns the distance into an outline of any width or a falloff of any
+ * profile, CRH_COMPOSITE_DST_OVER puts it under the layer at the grown origin, crh_image_lighting lights the INSIDE distance as a
+ * chisel, an image paint's tint colours it. Squared distances between texel centres are integers and the code is one rounding with an
+ * integer statement, so every byte is defined and the tests check every byte.
+ *   inside(x, y)  for any integer position: under PAD, REPEAT and REFLECT code(wrap(x, w), wrap(y, h)) >= threshold, code the stored
+ *             (premultiplied) code of `channel` as it is and wrap the image-paint block's, any number of periods out; under
+ *             TRANSPARENT a position outside the source is not inside.
+ *   D2(p)     OUTSIDE: 0 if inside(p), otherwise the least |p - q|^2 over the positions q with inside(q), or "none" if there is no
+ *             such q. INSIDE: 0 if not inside(p), otherwise the least |p - q|^2 over the q with not inside(q). Texel centres sit at
+ *             integer coordinates, so D2 is an integer.
+ *   c(D2)     min(255, floor(255 sqrt(D2) / spread + 1/2)), in integers: c(0) = 0, otherwise the largest c in [0, 255] with
+ *             (2 c - 1)^2 spread^2 <= 260100 D2 (64-bit arithmetic; a tie rounds up); "none" gives 255. Every D2 >= spread^2 gives 255,
+ *             so no q farther than `spread` from p can change a byte: this is what bounds the kernels' windows.
+ *   result    v = 255 - c (OUTSIDE: 255 on the shape, falling to 0 at `spread` — glow, outline, spread) or c (INSIDE: 0 off the
+ *             shape, rising into it — chisel, inner glow); the texel is (v, v, v, v): premultiplied-valid, a mask, a table's input,
+ *             a tint's, a height field.
+ *   size      OUTSIDE under TRANSPARENT grows the result to (w + 2 spread, h + 2 spread), texel (i, j) centred on the source's
+ *             (i - spread, j - spread), as blur and dilate grow; a grown side above 16384 is CRH_ERR_UNSUPPORTED. INSIDE keeps (w, h)
+ *             under every edge (growing would add zeros only), and so do the other edges. One level; the mirrors carry the origin.
+ * Hence: with spread 4, OUTSIDE and one inside texel, D2 = 1, 2, 4, 5, 9, 16 give c = 64, 90, 128, 143, 191, 255 (D2 = 4 is a tie:
+ * 255 * 4 = 510 * 2) and the bytes 191, 165, 127, 112, 64, 0; an inside texel is 255 (OUTSIDE) and at least c(1) (INSIDE); INSIDE of an
+ * image is 255 - OUTSIDE of its complement (code -> 255 - code, threshold t -> 256 - t) under the three same-size edges; the transpose
+ * of the result is the result of the transpose; under REPEAT a roll of the source rolls the result; neighbouring bytes differ by at most
+ * c(1) + 1; on a binarised image under PAD {v >= 255 - c(r^2)} lies within crh_image_morphology's dilate(r, r) and contains
+ * dilate(k, k) for 2 k^2 <= r^2.
+ * crh_distance_validate, crh_distance_code (the result byte v of one D2 under how's mode and spread, as crh_blur_taps hands out taps), crh_distance_size and crh_distance_texels
+ * (the rule on a whole image in host memory, width * height * 4 bytes in, the result's size out, r g b a at any alignment, row 0
+ * first; not quadratic in the spread) are host only: no renderer, no device.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out and the out buffers untouched:
+ * first a null argument; then a mode above CRH_DISTANCE_INSIDE, a channel above CRH_CHANNEL_A, a threshold outside [1, 255], a spread
+ * outside [1, CRH_MAX_DISTANCE_SPREAD] and an edge above CRH_BLUR_EDGE_REFLECT; then a size outside [1, 16384] and, in
+ * crh_distance_texels, an out_rgba8 equal to rgba8 are CRH_ERR_INVALID_ARGUMENT; then a grown side above 16384 is
+ * CRH_ERR_UNSUPPORTED; each with a crh_last_error text "crh_distance_validate: ...".
+ * crh_image_distance_field runs two kernels on the renderer's stream with one scratch allocation (the thresholds of c and one byte per
+ * texel of the result): k_image_distance_v takes the source to g, the distance along the column (0 .. spread - 1, or "nothing within
+ * reach"), k_image_distance_h takes g to the result by D2(x, y) = min over dx of dx^2 + g(x + dx, y)^2, which is exact. Only level 0
+ * of the source is read and the source is not modified. A failed allocation or launch frees everything and returns CRH_ERR_HIP.
+ * Limits: the call is synchronous, like its siblings; the source is binarised, so there is no sub-texel refinement from antialiased
+ * coverage; distances are between texel centres, not to the boundary between texels; there is no signed mode: INSIDE and OUTSIDE are
+ * two calls; the spread is an integer and at most 255. */
+#define CRH_MAX_DISTANCE_SPREAD 255u
+typedef enum crh_distance_mode { CRH_DISTANCE_OUTSIDE = 0, CRH_DISTANCE_INSIDE = 1 } crh_distance_mode;
+typedef struct crh_distance {
+    uint32_t mode;      /* crh_distance_mode */
+    uint32_t channel;   /* crh_channel; the stored (premultiplied) code as it is */
+    uint32_t threshold; /* 1..255: a texel is inside iff code >= threshold */
+    uint32_t spread;    /* 1..CRH_MAX_DISTANCE_SPREAD, in texels */
+    uint32_t edge;      /* crh_blur_edge */
+} crh_distance;
+crh_status crh_distance_validate(const crh_distance* how);                                               /* host only */
+crh_status crh_distance_code(const crh_distance* how, uint64_t squared_distance, uint32_t* code);        /* host only: the result byte of one D2 */
+crh_status crh_distance_size(uint32_t width, uint32_t height, const crh_distance* how, uint32_t* out_width, uint32_t* out_height); /* host only */
+crh_status crh_distance_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_distance* how, void* out_rgba8);      /* host only */
+crh_status crh_image_distance_field(const crh_image* src, const crh_distance* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

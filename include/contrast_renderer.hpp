@@ -855,6 +855,46 @@ inline std::array<int32_t, 2> displace_offset(const Displace& displace, uint32_t
     check(crh_displace_offset(&how, code_x, code_y, q.data()));
     return q;
 }
+// Distance fields (include/contrast_hip.h crh_image_distance_field states the rule): the exact Euclidean distance to a shape in 8 bits over a spread.
+enum class DistanceMode : uint32_t { Outside = CRH_DISTANCE_OUTSIDE, Inside = CRH_DISTANCE_INSIDE };
+// The fields of crh_distance: what the distance is measured to (Outside: the shape, 255 on it and 0 at the spread; Inside: what is not the
+// shape, 0 off it and rising into it), the channel whose stored code against the threshold makes the shape, the spread in texels
+// (1..CRH_MAX_DISTANCE_SPREAD) and what the source is outside itself.
+struct Distance {
+    uint32_t spread = 1;
+    DistanceMode mode = DistanceMode::Outside;
+    Channel channel = Channel::A;
+    uint32_t threshold = 128;
+    BlurEdge edge = BlurEdge::Transparent;
+    crh_distance to_c() const {
+        crh_distance how = {};
+        how.mode = (uint32_t)mode, how.channel = (uint32_t)channel, how.threshold = threshold, how.spread = spread, how.edge = (uint32_t)edge;
+        return how;
+    }
+};
+// crh_distance_code (host only): the result byte of one squared distance between texel centres
+inline uint32_t distance_code(const Distance& distance, uint64_t squared_distance) {
+    const crh_distance how = distance.to_c();
+    uint32_t code = 0;
+    check(crh_distance_code(&how, squared_distance, &code));
+    return code;
+}
+// crh_distance_size (host only) -> the size of Image::distance_field's result on a width x height image; throws what it would refuse
+inline std::array<uint32_t, 2> distance_size(uint32_t width, uint32_t height, const Distance& distance) {
+    const crh_distance how = distance.to_c();
+    std::array<uint32_t, 2> out = {0, 0};
+    check(crh_distance_size(width, height, &how, &out[0], &out[1]));
+    return out;
+}
+// crh_distance_texels (host only): the rule on a width x height image of RGBA8 in host memory -> the bytes of the result, of distance_size's size
+inline std::vector<uint8_t> distance_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, const Distance& distance) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const std::array<uint32_t, 2> size = distance_size(width, height, distance);
+    const crh_distance how = distance.to_c();
+    std::vector<uint8_t> out((size_t)size[0] * size[1] * 4u);
+    check(crh_distance_texels(width, height, texels.data(), &how, out.data()));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -979,6 +1019,18 @@ class Image {
         Image image;
         check(crh_image_displace(handle_, map.handle_, &how, &image.handle_));
         image.width_ = width_, image.height_ = height_;
+        return image;
+    }
+    // crh_image_distance_field -> a new Image of one level: per texel the exact Euclidean distance between texel centres to the shape (or,
+    // Inside, to what is not the shape), coded over the spread on all four channels; complete on return (a synchronous call). Outside under
+    // BlurEdge::Transparent grows the result by the spread on every side and its origin() is (spread, spread), as blur() grows; everything
+    // else keeps the size and origin (0, 0). This image is not modified.
+    Image distance_field(const Distance& distance) const {
+        const crh_distance how = distance.to_c();
+        Image image;
+        check(crh_image_distance_field(handle_, &how, &image.handle_));
+        check(crh_image_size(image.handle_, &image.width_, &image.height_));
+        if (distance.mode == DistanceMode::Outside && distance.edge == BlurEdge::Transparent) image.origin_ = {distance.spread, distance.spread};
         return image;
     }
     template <class Light>

@@ -1115,6 +1115,62 @@ pub fn displace_texels(width: u32, height: u32, texels: &[u8], map: &[u8], displ
     status(unsafe { ffi::crh_displace_texels(width, height, texels.as_ptr() as *const _, map.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// `crh_distance_mode`: what the distance is measured to
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum DistanceMode {
+    /// to the shape: 255 on it, falling to 0 at the spread (glow, outline, spread)
+    Outside = 0,
+    /// to what is not the shape: 0 off it, rising into it (chisel, inner glow)
+    Inside = 1,
+}
+/// The fields of `crh_distance` (include/contrast_hip.h, `crh_image_distance_field`, states the rule): the mode, the channel whose stored
+/// code against the threshold makes the shape, the spread in texels (1..=255) and what the source is outside itself.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct Distance {
+    pub spread: u32,
+    pub mode: DistanceMode,
+    pub channel: Channel,
+    pub threshold: u32,
+    pub edge: BlurEdge,
+}
+impl Default for Distance {
+    fn default() -> Distance {
+        Distance { spread: 1, mode: DistanceMode::Outside, channel: Channel::A, threshold: 128, edge: BlurEdge::Transparent }
+    }
+}
+impl Distance {
+    fn to_c(&self) -> ffi::crh_distance {
+        ffi::crh_distance { mode: self.mode as u32, channel: self.channel as u32, threshold: self.threshold, spread: self.spread, edge: self.edge as u32 }
+    }
+}
+/// `crh_distance_validate` (host only): what `Image::distance_field` would refuse of the fields
+pub fn distance_validate(distance: &Distance) -> Result<(), Error> {
+    let how = distance.to_c();
+    status(unsafe { ffi::crh_distance_validate(&how) })
+}
+/// `crh_distance_code` (host only) -> the result byte of one squared distance between texel centres
+pub fn distance_code(distance: &Distance, squared_distance: u64) -> Result<u32, Error> {
+    let how = distance.to_c();
+    let mut code = 0u32;
+    status(unsafe { ffi::crh_distance_code(&how, squared_distance, &mut code) })?;
+    Ok(code)
+}
+/// `crh_distance_size` (host only) -> (width, height) of the result of `Image::distance_field` on a width x height image
+pub fn distance_size(width: u32, height: u32, distance: &Distance) -> Result<(u32, u32), Error> {
+    let how = distance.to_c();
+    let (mut w, mut h) = (0u32, 0u32);
+    status(unsafe { ffi::crh_distance_size(width, height, &how, &mut w, &mut h) })?;
+    Ok((w, h))
+}
+/// `crh_distance_texels` (host only): the rule on a width x height image of RGBA8 in host memory -> (width, height, texels) of the result
+pub fn distance_texels(width: u32, height: u32, texels: &[u8], distance: &Distance) -> Result<(u32, u32, Vec<u8>), Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    let (w, h) = distance_size(width, height, distance)?;
+    let how = distance.to_c();
+    let mut out = vec![0u8; w as usize * h as usize * 4];
+    status(unsafe { ffi::crh_distance_texels(width, height, texels.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
+    Ok((w, h, out))
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -1214,6 +1270,18 @@ impl Image {
         let (mut width, mut height) = (0u32, 0u32);
         status(unsafe { ffi::crh_image_size(raw, &mut width, &mut height) })?;
         let origin = if op == MorphologyOp::Dilate && edge == BlurEdge::Transparent { (radius_x, radius_y) } else { (0, 0) };
+        Ok(Image { raw, width, height, origin })
+    }
+    /// `crh_image_distance_field` -> a new `Image` of one level: per texel the exact Euclidean distance between texel centres to the shape
+    /// (or, `Inside`, to what is not the shape), coded over the spread on all four channels; complete on return (a synchronous call).
+    /// `Outside` under `BlurEdge::Transparent` grows the result by the spread on every side and its origin is (spread, spread).
+    pub fn distance_field(&self, distance: &Distance) -> Result<Image, Error> {
+        let how = distance.to_c();
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_distance_field(self.raw, &how, &mut raw) })?;
+        let (mut width, mut height) = (0u32, 0u32);
+        status(unsafe { ffi::crh_image_size(raw, &mut width, &mut height) })?;
+        let origin = if distance.mode == DistanceMode::Outside && distance.edge == BlurEdge::Transparent { (distance.spread, distance.spread) } else { (0, 0) };
         Ok(Image { raw, width, height, origin })
     }
     pub fn dilate(&self, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<Image, Error> {
