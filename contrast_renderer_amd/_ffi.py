@@ -360,6 +360,9 @@ def load_library():
         "crh_distance_size": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(DistanceC), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "crh_distance_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.POINTER(DistanceC), V]),
         "crh_image_distance_field": (C.c_int, [V, C.POINTER(DistanceC), C.POINTER(V)]),
+        "crh_resize_taps": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.POINTER(C.c_int16), C.c_uint64, C.POINTER(C.c_uint64)]),
+        "crh_resize_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.c_uint32, C.c_uint32, C.c_uint32, V]),
+        "crh_image_resize": (C.c_int, [V, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

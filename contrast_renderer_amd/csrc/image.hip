@@ -1,5 +1,5 @@
-// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, and the nine
-// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field) with their host rules (crh_*_texels) and validators.
+// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, and the ten
+// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field, resize) with their host rules (crh_*_texels) and validators.
 // Host code only: the kernels are image_filter.hip's and raster.hip's (launch.hpp), the rules are the filters' headers. Of a renderer it
 // uses its device, its stream and "wait for every stream" (api_internal.hpp); what is about a frame or a paint table stays in api.hip.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
+#include "resize.hpp"
 #include "turbulence.hpp"
 
 using namespace crh;
@@ -713,5 +714,76 @@ crh_status crh_image_distance_field(const crh_image* src, const crh_distance* ho
         uint8_t* g = scratch ? scratch + sizeof thresholds : nullptr; // (a failed allocation: no launch follows)
         job.launch("k_image_distance_v", [&] { launch_image_distance_v(texels_of(src), src->width, src->height, g, out_w, out_h, origin, f, job.stream); });
         job.launch("k_image_distance_h", [&] { launch_image_distance_h(g, out_w, out_h, reinterpret_cast<const uint32_t*>(scratch), f, job.texels(), job.stream); });
+    });
+}
+// ---- resize
+namespace {
+static_assert(CRH_MAX_RESIZE_TAPS == kResizeMaxTaps && CRH_RESIZE_BOX == kResizeBox && CRH_RESIZE_TRIANGLE == kResizeTriangle && CRH_RESIZE_CATMULL_ROM == kResizeCatmullRom &&
+                  CRH_RESIZE_MITCHELL == kResizeMitchell && CRH_RESIZE_LANCZOS3 == kResizeLanczos3 && CRH_RESIZE_LANCZOS3 + 1 == kResizeFilters,
+              "resize.hpp's cap and filters are the header's");
+constexpr const char* kResize = "crh_resize_taps";
+// validates an axis and builds its taps: the one check of the three entry points behind their null arguments
+crh_status resize_taps(uint32_t n, uint32_t m, uint32_t filter, ResizeAxis* axis) {
+    if (n == 0u || m == 0u || n > kMaxImageSize || m > kMaxImageSize) return refuse(kResize, "a side lies outside [1, 16384]");
+    if (filter > CRH_RESIZE_LANCZOS3) return refuse(kResize, "filter is above CRH_RESIZE_LANCZOS3");
+    switch (resize_axis(n, m, filter, axis, nullptr)) {
+    case kResizeAxisTaps: return refuse(kResize, "an output's window exceeds CRH_MAX_RESIZE_TAPS texels: chain two calls", CRH_ERR_UNSUPPORTED);
+    case kResizeAxisGain: return refuse(kResize, "an output's taps exceed sum |q| <= 32768", CRH_ERR_UNSUPPORTED);
+    default: return CRH_OK;
+    }
+}
+// both axes of a call: the sizes and the filter are checked for both before either axis is built, in the header's order
+crh_status resize_axes(uint32_t width, uint32_t height, uint32_t out_width, uint32_t out_height, uint32_t filter, ResizeAxis* ax, ResizeAxis* ay) {
+    crh_status st = check_size(kResize, width, height);
+    if (st == CRH_OK) st = check_size(kResize, out_width, out_height);
+    if (st == CRH_OK) st = resize_taps(width, out_width, filter, ax);
+    if (st == CRH_OK && height == width && out_height == out_width) *ay = *ax; // (the same axis: its taps are built once)
+    else if (st == CRH_OK) st = resize_taps(height, out_height, filter, ay);
+    return st;
+}
+} // namespace
+crh_status crh_resize_taps(uint32_t n, uint32_t m, uint32_t filter, int32_t* first, uint16_t* count, int16_t* taps, uint64_t capacity, uint64_t* total) {
+    const bool arrays = first && count && taps;
+    if ((!arrays && (first || count || taps)) || (!arrays && !total)) return refuse(kResize, "a null argument");
+    ResizeAxis axis;
+    const crh_status st = resize_taps(n, m, filter, &axis);
+    if (st != CRH_OK) return st;
+    if (arrays) {
+        if (capacity < axis.taps.size()) return refuse(kResize, "capacity is below the total");
+        std::copy(axis.first.begin(), axis.first.end(), first);
+        std::copy(axis.count.begin(), axis.count.end(), count);
+        std::copy(axis.taps.begin(), axis.taps.end(), taps);
+    }
+    if (total) *total = axis.taps.size();
+    return CRH_OK;
+}
+crh_status crh_resize_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t out_width, uint32_t out_height, uint32_t filter, void* out_rgba8) {
+    if (!rgba8 || !out_rgba8) return refuse(kResize, "a null argument");
+    if (rgba8 == out_rgba8) return refuse(kResize, "out_rgba8 is rgba8");
+    ResizeAxis ax, ay;
+    const crh_status st = resize_axes(width, height, out_width, out_height, filter, &ax, &ay);
+    if (st != CRH_OK) return st;
+    resize_run(static_cast<const uint8_t*>(rgba8), width, height, ax, ay, out_width, out_height, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_resize(const crh_image* src, uint32_t width, uint32_t height, uint32_t filter, crh_image** out) {
+    if (!src || !src->renderer || !out) return refuse(kResize, "a null argument");
+    ResizeAxis ax, ay;
+    const crh_status st = resize_axes(src->width, src->height, width, height, filter, &ax, &ay);
+    if (st != CRH_OK) return st;
+    ResizeTable tx, ty;
+    if (!resize_table(ax, src->width, &tx) || !resize_table(ay, src->height, &ty)) return refuse(kResize, "a tap lies outside the source", CRH_ERR_UNSUPPORTED); // (the builder's assertion: never met)
+    // one upload, at the head of the intermediate's allocation: [the horizontal table | the vertical table], resize.hpp's layout
+    std::vector<uint32_t> words(tx.words);
+    words.insert(words.end(), ty.words.begin(), ty.words.end());
+    const size_t tables_bytes = (words.size() * 4 + 255) / 256 * 256; // (the intermediate behind them stays 256-byte aligned)
+    return filter_call("crh_image_resize", src->renderer, width, height, out, [&](FilterJob& job) {
+        // [the tables | the intermediate: four 16-bit values per texel, the source's rows at the result's width]
+        void* scratch = job.scratch(tables_bytes + (size_t)width * src->height * 8, words.data(), words.size() * 4);
+        const uint32_t* table_x = static_cast<const uint32_t*>(scratch);
+        const uint32_t* table_y = table_x + tx.words.size();
+        void* tmp = static_cast<char*>(scratch) + tables_bytes;
+        job.launch("k_image_resize_h", [&] { launch_image_resize_h(texels_of(src), src->width, src->height, tmp, width, table_x, tx.pairs, job.stream); });
+        job.launch("k_image_resize_v", [&] { launch_image_resize_v(tmp, src->height, job.texels(), width, height, table_y, ty.pairs, job.stream); });
     });
 }

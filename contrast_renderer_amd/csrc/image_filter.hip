@@ -10,6 +10,7 @@
 // crh_image_turbulence: k_image_turbulence makes a noise image with the rule of turbulence.hpp, binary64 arithmetic on gradients gathered from LDS.
 // crh_image_displace: k_image_displace reads an image through per-texel offsets taken from a second one with the rule of displace.hpp, a gather from global memory.
 // crh_image_distance_field: k_image_distance_v and k_image_distance_h code the exact Euclidean distance to a shape with the rule of distance.hpp, separably through a byte of column distance per texel.
+// crh_image_resize: k_image_resize_h and k_image_resize_v resample an image to any size with the rule of resize.hpp, separably, with per-output integer taps.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
+#include "resize.hpp"
 #include "turbulence.hpp"
 
 namespace crh {
@@ -951,6 +953,128 @@ void launch_image_distance_h(const uint8_t* g, uint32_t out_w, uint32_t out_h, c
     const dim3 grid((out_w + (uint32_t)kDistanceSegment - 1u) / (uint32_t)kDistanceSegment, out_h); // out_h <= 16384 rows: below the grid's limit of 65535
     if (f.mode == kDistanceInside) hipLaunchKernelGGL(k_image_distance_h<true>, grid, dim3(kDistanceSegment), 0, stream, g, out_w, thresholds, f, out);
     else hipLaunchKernelGGL(k_image_distance_h<false>, grid, dim3(kDistanceSegment), 0, stream, g, out_w, thresholds, f, out);
+}
+
+namespace {
+constexpr int kResizeRows = 64;     // horizontal: source rows per workgroup, one per lane of a wave
+constexpr int kResizeWaves = 4;     // waves per workgroup, both passes
+constexpr int kResizeGroup = 32;    // horizontal: output columns per workgroup
+constexpr int kResizePerWave = kResizeGroup / kResizeWaves; // horizontal: output columns per wave, each four accumulators per lane
+constexpr int kResizeChunk = 64;    // horizontal: source columns staged in LDS at a time; even, so a tap pair never straddles two chunks
+constexpr int kResizeColumns = 64;  // vertical: columns per workgroup, one per lane of a wave
+constexpr int kResizeBlockRows = 32; // vertical: output rows per workgroup, eight per wave
+static_assert(kResizeChunk == kResizeColumns && kResizeRows == kResizeColumns && kResizeChunk % 2 == 0 && kResizeGroup % kResizeWaves == 0 && kResizeBlockRows % kResizeWaves == 0, "resize tiles");
+
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+// acc + v.i16[0] * q.i16[0] + v.i16[1] * q.i16[1] in signed 32 bits (v_dot2_i32_i16): two taps of one channel per instruction
+__device__ __forceinline__ int32_t sdot2(uint32_t v, uint32_t q, int32_t acc) { return __builtin_amdgcn_sdot2(__builtin_bit_cast(i16x2, v), __builtin_bit_cast(i16x2, q), acc, false); }
+// byte k of two texels as two 16-bit fields, (a.u8[k], b.u8[k]): one v_perm_b32 (selector 0x0C = a zero byte)
+template <int K> __device__ __forceinline__ uint32_t channel_pair(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x0C040C00u + (uint32_t)K * 0x00010001u); }
+} // namespace
+
+// crh_image_resize, horizontal pass: the source to the intermediate, four 16-bit values per texel, the result's width and the source's
+// height (resize.hpp: the rule, and the layout of `table`, whose windows start on an even column and hold an even number of taps).
+// The taps differ per output COLUMN, so lanes run along y: grid (ceil(out_w / 32), ceil(src_h / 64)), 4 waves. A workgroup owns 32 output
+// columns of 64 rows; wave w owns columns 8 w .. 8 w + 7 of them, lane l row l: an output column's first index, count and taps are
+// wave-uniform and come through the scalar cache. The source columns the 32 outputs read — from the first window's start to the last
+// window's end; both rise with the output — are staged 64 at a time, TRANSPOSED: wave w loads rows w, w + 4, .. with lanes along x (64
+// consecutive words) and writes tile[column][row], 65 words per column, so the stores and the reads tile[column][lane] are both
+// conflict-free. A column beyond the source (only the one under a padding zero tap) and the columns beyond the span are staged as
+// zeros, a row beyond the source repeats the last row and is never stored. Per chunk a wave adds, for each of its 8 outputs, the part of
+// the window inside the chunk: a tap pair is one scalar word, two LDS words, four v_perm_b32 that regroup the two texels by channel and
+// four v_dot2_i32_i16. The 32 accumulators live across chunks (an output's window may span up to nine of them). The results go back
+// through LDS, so a row's 32 outputs leave as 256 consecutive bytes. Every global address is (a row clamped to src_h - 1) * src_w + (a
+// column tested against src_w); every LDS column index is below 64: chunk + 64 bounds the inner loop, and pairs are even-aligned.
+__global__ __launch_bounds__(kResizeColumns * kResizeWaves) void k_image_resize_h(const uint32_t* __restrict__ src, uint32_t src_w, uint32_t src_h, uint2* __restrict__ tmp, uint32_t out_w,
+                                                                                  const uint32_t* __restrict__ table, uint32_t pairs) {
+    __shared__ uint32_t tile[kResizeChunk][kResizeRows + 1];
+    __shared__ uint2 done[kResizeRows][kResizeGroup + 1];
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t o0 = blockIdx.x * (uint32_t)kResizeGroup, j0 = blockIdx.y * (uint32_t)kResizeRows;
+    const uint32_t o_last = min(o0 + (uint32_t)kResizeGroup, out_w) - 1u; // (o0 < out_w by the grid)
+    const uint32_t* first = table;
+    const uint32_t* count = table + out_w;
+    const uint32_t* taps = table + 2u * (size_t)out_w;
+    const uint32_t span_lo = first[o0], span_hi = first[o_last] + count[o_last]; // both even; span_hi <= src_w + 1
+    int32_t acc[kResizePerWave][4];
+#pragma unroll
+    for (int k = 0; k < kResizePerWave; ++k) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0;
+    for (uint32_t chunk = span_lo; chunk < span_hi; chunk += (uint32_t)kResizeChunk) {
+        const uint32_t chunk_hi = min(chunk + (uint32_t)kResizeChunk, span_hi); // even
+        __syncthreads(); // (the columns of the chunk before have been read)
+        for (uint32_t r = wave; r < (uint32_t)kResizeRows; r += (uint32_t)kResizeWaves) {
+            const uint32_t row = min(j0 + r, src_h - 1u), column = chunk + lane;
+            uint32_t texel = 0u;
+            if (column < chunk_hi && column < src_w) texel = src[(size_t)row * src_w + column];
+            tile[lane][r] = texel;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kResizePerWave; ++k) {
+            const uint32_t o = o0 + wave * (uint32_t)kResizePerWave + (uint32_t)k; // wave-uniform
+            if (o > o_last) break;
+            const uint32_t f = first[o], from = max(f, chunk), to = min(f + count[o], chunk_hi); // all even
+            const uint32_t* q = taps + (size_t)o * pairs;
+            for (uint32_t i = from; i < to; i += 2u) {
+                const uint32_t qq = q[(i - f) >> 1];
+                const uint32_t a = tile[i - chunk][lane], b = tile[i - chunk + 1u][lane];
+                acc[k][0] = sdot2(channel_pair<0>(a, b), qq, acc[k][0]), acc[k][1] = sdot2(channel_pair<1>(a, b), qq, acc[k][1]);
+                acc[k][2] = sdot2(channel_pair<2>(a, b), qq, acc[k][2]), acc[k][3] = sdot2(channel_pair<3>(a, b), qq, acc[k][3]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kResizePerWave; ++k)
+        done[lane][wave * (uint32_t)kResizePerWave + (uint32_t)k] =
+            make_uint2(resize_intermediate(acc[k][0]) | resize_intermediate(acc[k][1]) << 16, resize_intermediate(acc[k][2]) | resize_intermediate(acc[k][3]) << 16);
+    __syncthreads();
+    const uint32_t column = threadIdx.x % (uint32_t)kResizeGroup, o = o0 + column;
+    for (uint32_t r = threadIdx.x / (uint32_t)kResizeGroup; r < (uint32_t)kResizeRows; r += (uint32_t)(kResizeColumns * kResizeWaves / kResizeGroup))
+        if (o < out_w && j0 + r < src_h) tmp[(size_t)(j0 + r) * out_w + o] = done[r][column];
+}
+
+// crh_image_resize, vertical pass: the intermediate to the result. Grid (ceil(out_w / 64), ceil(out_h / 32)), 4 waves: lanes run along x, so
+// every global access of a wave is 64 consecutive 8- or 4-byte words, and an output row's first index, count and taps are wave-uniform
+// and come through the scalar cache. Wave w owns the output rows w, w + 4, .. w + 28 of the workgroup's 32, so the four waves walk through
+// the intermediate together: neighbouring output rows' windows overlap by the factor 2 r when minifying and coincide when magnifying, and
+// the overlap is served by the CU's vector cache, not staged. The rows of a window are taken in pairs: the 16-bit values are biased to
+// signed (t - 32768: one v_xor_b32 per word), the two rows regrouped by channel (four v_perm_b32) and each channel takes both taps in one
+// v_dot2_i32_i16. The taps sum to 16384, so the biased sum is the true one minus 2^29, |.| <= 32768 * 32768; 2^29 goes back on before
+// the rounding. The second row of a pair is clamped to tmp_h - 1: it is one past the source only under a padding zero tap. Every address
+// is (a row below tmp_h) * out_w + (a column clamped to out_w - 1); the store is behind the column's test.
+__global__ __launch_bounds__(kResizeColumns * kResizeWaves) void k_image_resize_v(const uint2* __restrict__ tmp, uint32_t tmp_h, uint32_t* __restrict__ out, uint32_t out_w, uint32_t out_h,
+                                                                                  const uint32_t* __restrict__ table, uint32_t pairs) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t x = blockIdx.x * (uint32_t)kResizeColumns + lane, xc = min(x, out_w - 1u);
+    const uint32_t* first = table;
+    const uint32_t* count = table + out_h;
+    const uint32_t* taps = table + 2u * (size_t)out_h;
+    for (uint32_t i = blockIdx.y * (uint32_t)kResizeBlockRows + wave; i < min((blockIdx.y + 1u) * (uint32_t)kResizeBlockRows, out_h); i += (uint32_t)kResizeWaves) {
+        const uint32_t f = first[i], n = count[i] >> 1;
+        const uint32_t* q = taps + (size_t)i * pairs;
+        int32_t r = 0, g = 0, b = 0, a = 0;
+#pragma unroll 2
+        for (uint32_t p = 0; p < n; ++p) {
+            const uint32_t row0 = f + 2u * p, row1 = min(row0 + 1u, tmp_h - 1u); // row0 <= tmp_h - 1: a window's first tap of a pair is inside the source
+            const uint2 t0 = tmp[(size_t)row0 * out_w + xc], t1 = tmp[(size_t)row1 * out_w + xc];
+            const uint32_t rg0 = t0.x ^ 0x80008000u, ba0 = t0.y ^ 0x80008000u, rg1 = t1.x ^ 0x80008000u, ba1 = t1.y ^ 0x80008000u;
+            const uint32_t qq = q[p];
+            r = sdot2(low_halves(rg0, rg1), qq, r), g = sdot2(high_halves(rg0, rg1), qq, g);
+            b = sdot2(low_halves(ba0, ba1), qq, b), a = sdot2(high_halves(ba0, ba1), qq, a);
+        }
+        const int32_t bias = 1 << 29;
+        if (x < out_w) out[(size_t)i * out_w + x] = resize_texel(resize_code(r + bias), resize_code(g + bias), resize_code(b + bias), resize_code(a + bias));
+    }
+}
+
+void launch_image_resize_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, void* tmp, uint32_t out_w, const uint32_t* table, uint32_t pairs, hipStream_t stream) {
+    const dim3 grid((out_w + (uint32_t)kResizeGroup - 1u) / (uint32_t)kResizeGroup, (src_h + (uint32_t)kResizeRows - 1u) / (uint32_t)kResizeRows); // <= 512 x 256
+    hipLaunchKernelGGL(k_image_resize_h, grid, dim3(kResizeColumns * kResizeWaves), 0, stream, src, src_w, src_h, static_cast<uint2*>(tmp), out_w, table, pairs);
+}
+
+void launch_image_resize_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* table, uint32_t pairs, hipStream_t stream) {
+    const dim3 grid((out_w + (uint32_t)kResizeColumns - 1u) / (uint32_t)kResizeColumns, (out_h + (uint32_t)kResizeBlockRows - 1u) / (uint32_t)kResizeBlockRows); // <= 256 x 512
+    hipLaunchKernelGGL(k_image_resize_v, grid, dim3(kResizeColumns * kResizeWaves), 0, stream, static_cast<const uint2*>(tmp), tmp_h, out, out_w, out_h, table, pairs);
 }
 
 } // namespace crh

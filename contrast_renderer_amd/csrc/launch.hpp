@@ -73,6 +73,10 @@ void launch_image_displace(const uint32_t* src, const uint32_t* map, uint32_t w,
 struct DistanceConstants;
 void launch_image_distance_v(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint8_t* g, uint32_t out_w, uint32_t out_h, uint32_t origin, const DistanceConstants& f, hipStream_t stream);
 void launch_image_distance_h(const uint8_t* g, uint32_t out_w, uint32_t out_h, const uint32_t* thresholds, const DistanceConstants& f, uint32_t* out, hipStream_t stream);
+// image_filter.hip: crh_image_resize's two passes (resize.hpp holds the rule and the layout of `table`, an axis's ResizeTable on the device, `pairs` its words of taps per output).
+// h: src_h rows of src_w texels -> `tmp`, src_h rows of out_w texels of four 16-bit values; v: tmp_h rows of `tmp` -> out_h rows of out_w texels.
+void launch_image_resize_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, void* tmp, uint32_t out_w, const uint32_t* table, uint32_t pairs, hipStream_t stream);
+void launch_image_resize_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* table, uint32_t pairs, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream); // zeroes n_words 32-bit words with single-wave workgroups (the clear in front of both passes' binning kernels)

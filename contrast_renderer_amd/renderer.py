@@ -831,6 +831,43 @@ def distance_texels(pixels, spread, mode=DistanceMode.Outside, channel=Channel.A
     return out
 
 
+class ResizeFilter(IntEnum):  # crh_resize_filter: the reconstruction filter of Image.resize, widened by the ratio when minifying
+    Box = 0         # support 0.5: nearest when magnifying, the exact area mean at integer ratios
+    Triangle = 1    # support 1: bilinear when magnifying
+    CatmullRom = 2  # support 2: the interpolating cubic (B = 0, C = 1/2)
+    Mitchell = 3    # support 2: Mitchell-Netravali B = C = 1/3; softer, not interpolating
+    Lanczos3 = 4    # support 3: the sharpest, with ringing at hard edges
+
+
+MAX_RESIZE_TAPS = 512  # CRH_MAX_RESIZE_TAPS
+
+
+def resize_taps(n, m, filter=ResizeFilter.Lanczos3):
+    """crh_resize_taps (host only) -> (first, count, taps) of one axis of Image.resize from n source texels to m: output o reads the source
+    indices first[o] .. first[o] + count[o] - 1 with the signed integer taps that follow each other in `taps` (int32, uint16 and int16
+    arrays); an output's taps sum to exactly 16384 (include/contrast_hip.h crh_image_resize states the rule). Raises ContrastError for
+    what Image.resize refuses of an axis."""
+    lib = _ffi.load_library()
+    total = C.c_uint64()
+    check(lib.crh_resize_taps(int(n), int(m), int(filter), None, None, None, 0, C.byref(total)))
+    first, count, taps = np.zeros(int(m), dtype=np.int32), np.zeros(int(m), dtype=np.uint16), np.zeros(int(total.value), dtype=np.int16)
+    check(lib.crh_resize_taps(int(n), int(m), int(filter), first.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_uint16)),
+                              taps.ctypes.data_as(C.POINTER(C.c_int16)), len(taps), None))
+    return first, count, taps
+
+
+def resize_texels(pixels, width, height, filter=ResizeFilter.Lanczos3):
+    """crh_resize_texels (host only): the rule of Image.resize on a (height', width', 4) uint8 array -> the (height, width, 4) uint8 result."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"resize_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    width, height = int(width), int(height)
+    legal = 1 <= width <= 16384 and 1 <= height <= 16384  # (a size the library refuses gets a texel's room and the library's status)
+    out = np.empty((height, width, 4) if legal else (1, 1, 4), dtype=np.uint8)
+    check(_ffi.load_library().crh_resize_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, width & 0xFFFFFFFF, height & 0xFFFFFFFF, int(filter), out.ctypes.data))
+    return out
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -1026,6 +1063,16 @@ class Image:
         if int(mode) == DistanceMode.Outside and int(edge) == BlurEdge.Transparent:
             image.origin = (int(spread), int(spread))
         return image
+
+    def resize(self, width, height, filter=ResizeFilter.Lanczos3):
+        """crh_image_resize -> a new Image of one level, width x height, that holds the whole of this image resampled with `filter`, widened
+        by the ratio on an axis that shrinks, so nothing aliases; integer taps per output texel, bit-exact (include/contrast_hip.h
+        crh_image_resize states the rule); built on the device and complete when this returns (a synchronous call). Both sides lie in
+        [1, 16384]; an axis that shrinks by more than its filter's cap (about 85 under Lanczos3, 500 under Box) is refused: chain two
+        calls. The result's origin is (0, 0) whatever this image's is. This image is not modified."""
+        handle = C.c_void_p()
+        check(self.lib.crh_image_resize(self.handle, int(width) & 0xFFFFFFFF, int(height) & 0xFFFFFFFF, int(filter) & 0xFFFFFFFF, C.byref(handle)))
+        return Image._adopt(self.renderer, handle, (int(width), int(height)))
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

@@ -982,6 +982,61 @@ crh_status crh_distance_code(const crh_distance* how, uint64_t squared_distance,
 crh_status crh_distance_size(uint32_t width, uint32_t height, const crh_distance* how, uint32_t* out_width, uint32_t* out_height); /* host only */
 crh_status crh_distance_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_distance* how, void* out_rgba8);      /* host only */
 crh_status crh_image_distance_field(const crh_image* src, const crh_distance* how, crh_image** out);
+/* Resize: a new image of any size in [1, 16384]^2 that holds the whole source, resampled — "this layer at 37 % size", a 2x supersampled
+ * frame down to the display's size, a thumbnail, the half-resolution blur (down, blur, up). The filter widens with the ratio when it
+ * minifies, so it does not alias at any ratio, and it is separable: one table of integer taps per axis, which differ per output texel.
+ * Integer on the texels and bit-exact, so every byte is defined and the tests check every byte.
+ * An axis of n source texels and m result texels, both in [1, 16384]; per output index o, all real arithmetic in binary64 exactly in the
+ * order and parenthesisation written, never contracted, floor and / the IEEE operations:
+ *   s         max(1.0, (double)n / m): the filter widens when minifying and not when magnifying.
+ *   c         ((o + 0.5) * n) / m: the whole source maps onto the whole result, texel centres at half-integers.
+ *   f, r      the filter and its support; a = |x|, f = 0 where no case applies:
+ *               BOX          r = 0.5   1 for -0.5 <= x < 0.5 (nearest when magnifying, the area mean at integer ratios)
+ *               TRIANGLE     r = 1     1 - a for a < 1 (bilinear when magnifying)
+ *               CATMULL_ROM  r = 2     ((1.5 a - 2.5) a) a + 1 for a < 1; ((-0.5 a + 2.5) a - 4) a + 2 for a < 2
+ *               MITCHELL     r = 2     (((21 a - 36) a) a + 16) / 18 for a < 1; (((-7 a + 36) a - 60) a + 32) / 18 for a < 2
+ *                                      (Mitchell-Netravali with B = C = 1/3; Catmull-Rom is B = 0, C = 1/2)
+ *               LANCZOS3     r = 3     1 at a = 0; ((3 s1) s3) / (p p) for a < 3 with p = CRH_PI a, s1 = sin p, s3 = sin(p / 3),
+ *                                      both sines from crh_d_sincos of include/crh_fmath.h
+ *   window    lo = max(0, (int)floor(c - r s)), hi = min(n - 1, (int)floor(c + r s)), count = hi - lo + 1 >= 1. Taps that fall outside
+ *             the source are dropped and the rest renormalised: this is the edge rule. There are no edge modes and nothing outside the
+ *             image is ever read.
+ *   weights   w[t] = f((((lo + t) + 0.5) - c) / s), t = 0 .. count - 1; S = the sum of w in ascending t, from 0.0;
+ *             q[t] = (int)floor(w[t] / S * 16384 + 0.5), signed.
+ *   deficit   d = 16384 - sum q. The |d| taps nearest the centre each take sign(d): nearest is ascending |((lo + t) + 0.5) - c|, ties to
+ *             the lower t. So sum q = 16384 exactly.
+ *   checked   count <= CRH_MAX_RESIZE_TAPS, else the axis is CRH_ERR_UNSUPPORTED; and |d| <= count and sum |q| <= 32768 (the largest seen is
+ *             25748: LANCZOS3, 4 to 5, output 2), else CRH_ERR_UNSUPPORTED as well, which no pair of sizes is known to meet.
+ * Texels, per channel on the stored 8-bit codes as they are (premultiplied; no gamma), in signed 32-bit arithmetic, >> arithmetic (floor):
+ *   horizontal  t(o, j) = clamp((sum_t qx[t] c(lo + t, j) + 32) >> 6, 0, 65280): units of 1/256 code in 16 bits; |sum| <= 255 * 32768 < 2^23.
+ *               The intermediate has the result's width and the source's height.
+ *   vertical    v(o, i) = clamp((sum_t qy[t] t(o, lo + t) + 2^21) >> 22, 0, 255); |sum| + 2^21 <= 65280 * 32768 + 2^21 < 2^31, which is what
+ *               the bound on sum |q| is for.
+ *   result      alpha = v_a; each colour = min(v, alpha): negative lobes do not keep rgb <= a on their own.
+ * Hence: a constant image comes back exactly at every size and filter; n == m on both axes is a copy, byte for byte, under every filter
+ * but MITCHELL, which is not interpolating (its taps there are 1/18, 8/9, 1/18: 910, 14564, 910); BOX at an integer ratio is within 0.51
+ * code of the real mean of its n/m x n/m texels; rgb <= a always holds; under BOX and TRIANGLE no tap is negative and no clamp binds.
+ * crh_resize_taps (the taps of one axis: first[m], count[m], and sum of count signed taps back to back in `taps`, whose number goes to
+ * *total if total is not null; with all three arrays null it only reports *total; capacity is the room in `taps`) and crh_resize_texels
+ * (the rule on a whole image in host memory, width * height * 4 bytes in, out_width * out_height * 4 out, r g b a at any alignment, row 0
+ * first) are host only: no renderer, no device.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out and the out buffers untouched:
+ * first a null argument (crh_resize_taps: some but not all of the arrays null, or no array and no total); then a side of 0 or above
+ * 16384, a filter above CRH_RESIZE_LANCZOS3, in crh_resize_texels an out_rgba8 equal to rgba8 and in crh_resize_taps a capacity below
+ * the total are CRH_ERR_INVALID_ARGUMENT; then an axis over the tap cap is CRH_ERR_UNSUPPORTED; each with a crh_last_error text
+ * "crh_resize_taps: ...".
+ * crh_image_resize runs two kernels on the renderer's stream with one scratch allocation (both axes' tables in one upload at its head,
+ * then the intermediate, 8 bytes per texel): k_image_resize_h and k_image_resize_v. The result is a fresh one-level image of the
+ * source's renderer, complete on return, with origin (0, 0); only level 0 of the source is read and the source is not modified. A
+ * failed allocation or launch frees everything and returns CRH_ERR_HIP.
+ * Limits: the call is synchronous, like its siblings; one call minifies an axis by at most the ratio whose window holds 512 texels,
+ * about 500 (BOX), 250 (TRIANGLE), 127 (CATMULL_ROM, MITCHELL) and 85 (LANCZOS3): beyond it chain two calls or take a mip level first;
+ * the codes are filtered as they are, with no gamma handling; the scale is axis-aligned: rotation and perspective stay with image paints. */
+#define CRH_MAX_RESIZE_TAPS 512u
+typedef enum crh_resize_filter { CRH_RESIZE_BOX = 0, CRH_RESIZE_TRIANGLE = 1, CRH_RESIZE_CATMULL_ROM = 2, CRH_RESIZE_MITCHELL = 3, CRH_RESIZE_LANCZOS3 = 4 } crh_resize_filter;
+crh_status crh_resize_taps(uint32_t n, uint32_t m, uint32_t filter, int32_t* first, uint16_t* count, int16_t* taps, uint64_t capacity, uint64_t* total); /* host only */
+crh_status crh_resize_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t out_width, uint32_t out_height, uint32_t filter, void* out_rgba8); /* host only */
+crh_status crh_image_resize(const crh_image* src, uint32_t width, uint32_t height, uint32_t filter, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

@@ -895,6 +895,32 @@ inline std::vector<uint8_t> distance_texels(uint32_t width, uint32_t height, con
     check(crh_distance_texels(width, height, texels.data(), &how, out.data()));
     return out;
 }
+// Resize (include/contrast_hip.h crh_image_resize states the rule): the reconstruction filter, widened by the ratio on an axis that shrinks.
+enum class ResizeFilter : uint32_t { Box = CRH_RESIZE_BOX, Triangle = CRH_RESIZE_TRIANGLE, CatmullRom = CRH_RESIZE_CATMULL_ROM, Mitchell = CRH_RESIZE_MITCHELL, Lanczos3 = CRH_RESIZE_LANCZOS3 };
+// crh_resize_taps (host only): the taps of one axis from n source texels to m; output o reads first[o] .. first[o] + count[o] - 1 with the
+// signed taps that follow each other in `taps`, and an output's taps sum to 16384
+struct ResizeTaps {
+    std::vector<int32_t> first;
+    std::vector<uint16_t> count;
+    std::vector<int16_t> taps;
+};
+inline ResizeTaps resize_taps(uint32_t n, uint32_t m, ResizeFilter filter = ResizeFilter::Lanczos3) {
+    uint64_t total = 0;
+    check(crh_resize_taps(n, m, (uint32_t)filter, nullptr, nullptr, nullptr, 0, &total));
+    ResizeTaps out;
+    out.first.resize(m), out.count.resize(m), out.taps.resize((size_t)total + 1u); // (+ 1: data() of an empty vector may be null)
+    check(crh_resize_taps(n, m, (uint32_t)filter, out.first.data(), out.count.data(), out.taps.data(), total, nullptr));
+    out.taps.resize((size_t)total);
+    return out;
+}
+// crh_resize_texels (host only): the rule on a width x height image of RGBA8 in host memory -> the out_width x out_height result's bytes
+inline std::vector<uint8_t> resize_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, uint32_t out_width, uint32_t out_height, ResizeFilter filter = ResizeFilter::Lanczos3) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const bool legal = out_width >= 1u && out_width <= 16384u && out_height >= 1u && out_height <= 16384u; // (what the library refuses gets a texel's room and the library's status)
+    std::vector<uint8_t> out(legal ? (size_t)out_width * out_height * 4u : 4u);
+    check(crh_resize_texels(width, height, texels.data(), out_width, out_height, (uint32_t)filter, out.data()));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -1031,6 +1057,15 @@ class Image {
         check(crh_image_distance_field(handle_, &how, &image.handle_));
         check(crh_image_size(image.handle_, &image.width_, &image.height_));
         if (distance.mode == DistanceMode::Outside && distance.edge == BlurEdge::Transparent) image.origin_ = {distance.spread, distance.spread};
+        return image;
+    }
+    // crh_image_resize -> a new Image of one level, width x height, the whole of this image resampled; complete on return (a synchronous
+    // call). Its origin() is (0, 0) whatever this image's is. An axis that shrinks by more than the filter's cap (about 85 under Lanczos3)
+    // is refused: chain two calls. This image is not modified.
+    Image resize(uint32_t width, uint32_t height, ResizeFilter filter = ResizeFilter::Lanczos3) const {
+        Image image;
+        check(crh_image_resize(handle_, width, height, (uint32_t)filter, &image.handle_));
+        check(crh_image_size(image.handle_, &image.width_, &image.height_));
         return image;
     }
     template <class Light>

@@ -1171,6 +1171,38 @@ pub fn distance_texels(width: u32, height: u32, texels: &[u8], distance: &Distan
     status(unsafe { ffi::crh_distance_texels(width, height, texels.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
     Ok((w, h, out))
 }
+/// `crh_resize_filter`: the reconstruction filter of `Image::resize`, widened by the ratio on an axis that shrinks
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ResizeFilter {
+    /// support 0.5: nearest when magnifying, the exact area mean at integer ratios
+    Box = 0,
+    /// support 1: bilinear when magnifying
+    Triangle = 1,
+    /// support 2: the interpolating cubic (B = 0, C = 1/2)
+    CatmullRom = 2,
+    /// support 2: Mitchell-Netravali with B = C = 1/3; softer, not interpolating
+    Mitchell = 3,
+    /// support 3: the sharpest, with ringing at hard edges
+    Lanczos3 = 4,
+}
+/// `crh_resize_taps` (host only) -> (first, count, taps) of one axis of `Image::resize` from n source texels to m: output o reads the source
+/// indices first[o] .. first[o] + count[o] - 1 with the signed taps that follow each other in `taps`; an output's taps sum to exactly
+/// 16384 (include/contrast_hip.h, `crh_image_resize`, states the rule).
+pub fn resize_taps(n: u32, m: u32, filter: ResizeFilter) -> Result<(Vec<i32>, Vec<u16>, Vec<i16>), Error> {
+    let mut total = 0u64;
+    status(unsafe { ffi::crh_resize_taps(n, m, filter as u32, ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), 0, &mut total) })?;
+    let (mut first, mut count, mut taps) = (vec![0i32; m as usize], vec![0u16; m as usize], vec![0i16; total as usize]);
+    status(unsafe { ffi::crh_resize_taps(n, m, filter as u32, first.as_mut_ptr(), count.as_mut_ptr(), taps.as_mut_ptr(), total, ptr::null_mut()) })?;
+    Ok((first, count, taps))
+}
+/// `crh_resize_texels` (host only): the rule on a width x height image of RGBA8 in host memory -> the out_width x out_height result's bytes
+pub fn resize_texels(width: u32, height: u32, texels: &[u8], out_width: u32, out_height: u32, filter: ResizeFilter) -> Result<Vec<u8>, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    let legal = (1..=16384).contains(&out_width) && (1..=16384).contains(&out_height); // (what the library refuses gets a texel's room and the library's status)
+    let mut out = vec![0u8; if legal { out_width as usize * out_height as usize * 4 } else { 4 }];
+    status(unsafe { ffi::crh_resize_texels(width, height, texels.as_ptr() as *const _, out_width, out_height, filter as u32, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -1283,6 +1315,14 @@ impl Image {
         status(unsafe { ffi::crh_image_size(raw, &mut width, &mut height) })?;
         let origin = if distance.mode == DistanceMode::Outside && distance.edge == BlurEdge::Transparent { (distance.spread, distance.spread) } else { (0, 0) };
         Ok(Image { raw, width, height, origin })
+    }
+    /// `crh_image_resize` -> a new `Image` of one level, width x height, the whole of this image resampled; complete on return (a
+    /// synchronous call); its origin is (0, 0). An axis that shrinks by more than the filter's cap (about 85 under `Lanczos3`) is refused
+    /// with `CRH_ERR_UNSUPPORTED`: chain two calls.
+    pub fn resize(&self, width: u32, height: u32, filter: ResizeFilter) -> Result<Image, Error> {
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_resize(self.raw, width, height, filter as u32, &mut raw) })?;
+        Ok(Image { raw, width, height, origin: (0, 0) })
     }
     pub fn dilate(&self, radius_x: u32, radius_y: u32, edge: BlurEdge) -> Result<Image, Error> {
         self.morphology(MorphologyOp::Dilate, radius_x, radius_y, edge)
