@@ -872,7 +872,7 @@ class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
     its texels aliases unless it has mipmaps and its paint's filter is Filter.NearestMipmap or Filter.LinearMipmap. `origin` = the texel of this
-    image that lies over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless blur() or morphology() grew it."""
+    image that lies over texel (0, 0) of the image it was made from: (0, 0) unless blur(), morphology() or distance_field() grew it."""
 
     origin = (0, 0)
 

@@ -1,10 +1,11 @@
 """The generator and the host model of the stateful image and layer fuzz (tests/test_gpu_layers_fuzz.py): random sequences over one Renderer,
 two frames (RGBA8 and RGBA8_ATTACHMENT), a pool of images, a solid Scene and a blit Scene per frame — images created, snapshot from frames,
-made of noise, blurred, composited, colour filtered, eroded and dilated, convolved, lit, displaced, mipmapped, loaded back into frames, drawn
-as image paints through tables that outlive their images, between clears, uploads, plain passes and re-uploads of the solid Scene. Every
-image operation has an exact model (blur_model, composite_model, color_filter_model, morphology_model, convolve_model, lighting_model,
-turbulence_model, displace_model, mip_model) and every pass an exact expectation (the oracle for the solid Scene, the image's own bytes for
-an identity blit), so every check is of bytes. No GPU and no library call in here: the oracle alone."""
+made of noise, blurred, composited, colour filtered, eroded and dilated, convolved, lit, displaced, turned into distance fields, resized,
+mipmapped, loaded back into frames, drawn as image paints through tables that outlive their images, between clears, uploads, plain passes,
+re-uploads of the solid Scene and calls that the library refuses. Every image operation has an exact model (blur_model, composite_model,
+color_filter_model, morphology_model, convolve_model, lighting_model, turbulence_model, displace_model, distance_model, resize_model,
+mip_model) and every pass an exact expectation (the oracle for the solid Scene, the image's own bytes for an identity blit), so every
+check is of bytes. No GPU and no library call in here: the oracle alone."""
 import numpy as np
 
 from contrast_renderer_amd import scenes
@@ -14,25 +15,38 @@ import color_filter_model as FM
 import composite_model as CM
 import convolve_model as CV
 import displace_model as DM
+import distance_model as DF
 import lighting_model as LM
 import mip_model as MM
 import morphology_model as MO
+import resize_model as RS
 import turbulence_model as TM
 
 FORMATS = (0, 2)  # FORMAT_RGBA8, FORMAT_RGBA8_ATTACHMENT: frame 0 and frame 1
 MAX_POOL = 8
-MAX_SIDE = 300  # a TRANSPARENT blur or dilate is given another edge when it would grow an image beyond this (the sigma-64 blur and the one radius above 64 apart)
+MAX_SIDE = 300  # a TRANSPARENT blur, dilate or distance field is given another edge when it would grow an image beyond this (the sigma-64 blur, the one radius above 64 and the one spread above 64 apart); no resize has a side above it
 SIGMAS = (0.0, 0.01, 0.3, 1.0, 2.5, 6.0)
 NEAREST, LINEAR, MIPMAP = 0, 1, 0x100
 STENCIL, COLOR = 0, 3  # RenderOperation.Stencil, RenderOperation.Color
 KINDS = ("create", "snapshot", "blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image", "clear", "solid", "upload", "load_image",
          "download", "set_table", "replace_table", "clear_table", "blit", "blit_mip", "white_paint", "reupload",
-         "morphology", "convolve", "lighting", "turbulence", "displace")
+         "morphology", "convolve", "lighting", "turbulence", "displace", "distance_field", "resize", "refused")
 WEIGHTS = (0.06, 0.07, 0.11, 0.09, 0.08, 0.04, 0.08, 0.04, 0.01, 0.09, 0.06, 0.05, 0.06, 0.03, 0.05, 0.04, 0.06, 0.03, 0.03, 0.03,
-           0.10, 0.07, 0.07, 0.04, 0.09)
-NEW = ("morphology", "convolve", "lighting", "turbulence", "displace")  # the filters that came after the fuzz was written
+           0.10, 0.07, 0.07, 0.04, 0.09, 0.10, 0.11, 0.03)
+NEW = ("morphology", "convolve", "lighting", "turbulence", "displace", "distance_field", "resize")  # the filters that came after the fuzz was written
 READS = ("blur", "composite", "color_filter", "check_image", "load_image", "set_table", "replace_table", "blit_mip") + tuple(k for k in NEW if k != "turbulence")
 GROWN_DILATE = "grown dilate"  # beside the kinds in an image's `via`: a DILATE under TRANSPARENT with a non-zero radius is behind it
+GROWN_DISTANCE = "grown distance"  # likewise: an OUTSIDE distance field under TRANSPARENT, grown by its spread, is behind it
+# the spreads of a distance field: 16 and 17 are the two sides of launch_image_distance_v's switch from 32-row to 128-row blocks (drawn more
+# often than the others), and once per seed one of SPREADS_BIG: above 64, above 128 (k_image_distance_h stages more than a segment on either side), the largest
+SPREADS = (1, 2, 3, 8, 16, 16, 17, 17, 40, 64)
+SPREADS_BIG = (65, 128, 255)
+# the sides a resize aims at beside the frame's, the source's and the small ones: round k_image_resize_h's group of 32 output columns,
+# its chunk and tile of 64 and k_image_resize_v's block of 32 rows and 64 columns
+RESIZE_SIDES = (1, 31, 32, 33, 63, 64, 65, 127, 128, 129)
+RESIZE_TARGETS = ("frame", "small", "same", "up and down", "sides")
+ERR_UNSUPPORTED, ERR_INVALID_ARGUMENT = 8, 10  # crh_status, what a refused call must raise
+REFUSALS = ("spread 0", "spread 256", "threshold 0", "width 0", "height 16385", "filter 5", "taps")  # "taps" needs a pool image with a side above 512
 # every route of crh_image_morphology and every instantiation of k_image_morph_v: 0 skips an axis's pass ((0, 0) is the copy), and a vertical
 # window 2 radius + 1 of at most 33, at most 129 and above selects one of the three
 RADII = (0, 1, 2, 5, 16, 17, 64, 65, 192)
@@ -109,6 +123,25 @@ def step_displace(pixels, map, scale, channels, filter, edge):
     return DM.displace(pixels, map, tuple(scale), channels[0], channels[1], filter, edge)
 
 
+def step_distance_field(pixels, spread, mode, channel, threshold, edge):
+    return DF.distance_field(pixels, spread, mode, channel, threshold, edge)
+
+
+def step_resize(pixels, width, height, filter, counters=None):
+    return RS.resize(pixels, width, height, filter, counters)
+
+
+def outline_tables(k, spread):
+    """An outline k texels wide of an OUTSIDE distance field: every code from 255 - c(k^2) upward becomes opaque, everything farther
+    transparent, on all four channels."""
+    return np.tile(np.where(np.arange(256) >= 255 - DF.code(k * k, spread), 255, 0).astype(np.uint8), 4)
+
+
+def contrast(pixels):
+    """The mean step between neighbouring texels along a row, in codes: what a tap moved from one texel to its neighbour can change."""
+    return float(np.abs(np.diff(pixels.astype(np.int64), axis=1)).mean()) if pixels.shape[1] > 1 else 0.0
+
+
 def morphology_route(radius):
     return ROUTES[int(radius[0] > 0) + 2 * int(radius[1] > 0)]
 
@@ -128,19 +161,23 @@ class Model:
         self.oracle = Oracle(self.batch) if oracle is None else oracle
         w, h = setup["width"], setup["height"]
         self.frame = [dict(image=np.zeros((h, w, 4), np.uint8), cleared=True, last="clear") for _ in FORMATS]
-        # dict(pixels, mip, depth, origin, by, via): depth = the device operations behind the image, origin = what Image.origin must be, by = the
-        # kind that made it, via = the kinds in its history (and GROWN_DILATE)
+        # dict(pixels, mip, depth, origin, by, via, uid): depth = the device operations behind the image, origin = what Image.origin must be,
+        # by = the kind that made it, via = the kinds in its history (and GROWN_DILATE, GROWN_DISTANCE), uid = its number among all images made
         self.pool = []
+        self.made = 0
+        self.counters = {}  # of the last resize: resize_model's clamp and min(v, alpha) counts
         self.table = [None, None]  # of the blit Scene of each frame: dict(pixels, filter, destroyed, index, via)
         self.slice = tuple(setup["slice"])
         self.instances = None
 
     def add(self, pixels, by, inputs=(), origin=(0, 0), mark=()):
-        """A new pool image made by `by` from the pool entries `inputs`. The origin follows the Image docstrings: blur and dilate set it, the
-        colour filter, convolve and lighting inherit it (the caller passes the source's), everything else has (0, 0)."""
+        """A new pool image made by `by` from the pool entries `inputs`. The origin follows the Image docstrings: blur, dilate and the
+        distance field set it, the colour filter, convolve and lighting inherit it (the caller passes the source's), everything else,
+        resize too, has (0, 0)."""
         via = frozenset((by,) + tuple(mark)).union(*[e["via"] for e in inputs])
         depth = max([e["depth"] for e in inputs], default=0) + int(by != "create")
-        self.pool.append(dict(pixels=pixels, mip=False, depth=depth, origin=tuple(int(v) for v in origin), by=by, via=via))
+        self.pool.append(dict(pixels=pixels, mip=False, depth=depth, origin=tuple(int(v) for v in origin), by=by, via=via, uid=self.made))
+        self.made += 1
 
     def name(self, j, index, filter):
         e = self.pool[index]
@@ -198,6 +235,17 @@ class Model:
         elif kind == "displace":
             src, map = self.pool[op["image"]], self.pool[op["map"]]
             self.add(step_displace(src["pixels"], map["pixels"], op["scale"], op["channels"], op["filter"], op["edge"]), kind, [src, map])
+        elif kind == "distance_field":
+            src = self.pool[op["image"]]
+            grown = DF.grows(op["mode"], op["edge"])
+            self.add(step_distance_field(src["pixels"], op["spread"], op["mode"], op["channel"], op["threshold"], op["edge"]), kind, [src],
+                     (op["spread"], op["spread"]) if grown else (0, 0), (GROWN_DISTANCE,) if grown else ())
+        elif kind == "resize":
+            src = self.pool[op["image"]]
+            self.counters = {}
+            self.add(step_resize(src["pixels"], op["size"][0], op["size"][1], op["filter"], self.counters), kind, [src])
+        elif kind == "refused":  # the pool is as it was, and so is the image the call named
+            return [self.pool[op["image"]]["pixels"]]
         elif kind == "mipmaps":
             self.pool[op["image"]]["mip"] = True
         elif kind == "check_image":
@@ -305,18 +353,27 @@ def generate(seed):
     setup = dict(seed=seed, width=width, height=height, msaa=int(rng.choice([1, 4])), slice=new_slice())
     model = Model(setup, sc["batch"])
     ops = []
-    big_blur_left = big_morphology_left = heavy_convolve_left = 1
+    big_blur_left = big_morphology_left = heavy_convolve_left = big_distance_left = 1
 
     def emit(op):
         """Every op that reads pool images also says what they were when it ran: `by` and `straight` per image, in the order image, source,
-        map; the union of their `via`; the largest depth; whether the first has mipmaps. The conditions of test_layers_model_cpu.py read these."""
+        map; the union of their `via`; the largest depth; whether the first has mipmaps; the first's uid. A distance_field and a resize also say
+        their source's size and origin, their result's size and uid, and what resize_model counted. The conditions of test_layers_model_cpu.py
+        read these."""
         if op["kind"] in READS:
             used = [model.pool[op[k]] for k in ("image", "source", "map") if k in op]
             op.update(by=tuple(e["by"] for e in used), straight=tuple(not premultiplied(e["pixels"]) for e in used), via=tuple(sorted(frozenset().union(*[e["via"] for e in used]))),
-                      depth=max(e["depth"] for e in used), mip=used[0]["mip"])
+                      depth=max(e["depth"] for e in used), mip=used[0]["mip"], uid=used[0]["uid"])
             if op["kind"] == "check_image":
                 op["origin"] = used[0]["origin"]
+            if op["kind"] in ("distance_field", "resize"):
+                op.update(source_size=(used[0]["pixels"].shape[1], used[0]["pixels"].shape[0]), source_origin=used[0]["origin"], contrast=contrast(used[0]["pixels"]))
         model.apply(op)
+        if op["kind"] in ("distance_field", "resize"):  # which image the result is (a later check_image says which it reads), and what the model counted
+            op["result"] = model.pool[-1]["uid"]
+            op["size"] = [int(model.pool[-1]["pixels"].shape[1]), int(model.pool[-1]["pixels"].shape[0])]
+        if op["kind"] == "resize":
+            op.update(min_alpha=model.counters["min_alpha"], split_ties=model.counters["split_ties"])
         ops.append(op)
 
     def pick(indices):
@@ -377,14 +434,15 @@ def generate(seed):
                     noise=int(rng.randint(0, 2)), stitch=bool(rng.randint(0, 2)), opaque=bool(rng.randint(0, 2)),
                     offset=[0.0, 0.0] if rng.uniform() < 0.3 else [f32(v) for v in rng.uniform(-100, 100, 2)])
 
-    n_steps = int(rng.randint(80, 116))
+    n_steps = int(rng.randint(100, 141))
     emit(dict(kind="upload", frame=0, pixels=BM.random_premultiplied(rng, width, height)))  # (the frames show something from the start)
     emit(instances_for(dict(kind="solid", frame=1)))
     while len(ops) < n_steps:
         kind = KINDS[int(rng.choice(len(KINDS), p=np.float64(WEIGHTS) / np.sum(WEIGHTS)))]
         j = int(rng.randint(0, 2))
         pool = model.pool
-        if kind == "create" or (not pool and kind in ("blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image", "morphology", "convolve", "lighting", "displace")):
+        if kind == "create" or (not pool and kind in ("blur", "composite", "color_filter", "mipmaps", "check_image", "destroy_image", "morphology", "convolve", "lighting", "displace",
+                                                      "distance_field", "resize", "refused")):
             room()
             w, h = (width, height) if rng.uniform() < 0.5 else (int(rng.randint(1, 41)), int(rng.randint(1, 31)))
             how = TEXELS[int(rng.randint(0, len(TEXELS)))]
@@ -508,6 +566,120 @@ def generate(seed):
             emit(dict(kind="displace", image=i, map=m, scale=list(DISPLACE_SCALES[int(rng.randint(0, len(DISPLACE_SCALES)))]), channels=[int(v) for v in rng.randint(0, 4, 2)],
                       filter=int(rng.randint(0, 2)), edge=int(rng.randint(0, 4)), width=w))
             after_filter(i, kind)
+        elif kind == "distance_field":
+            outline = rng.uniform() < 0.5  # (what a grown result is followed by, decided here: room() renumbers the pool)
+            room(3 if outline else 1)
+            soft = [k for k, e in enumerate(pool) if e["via"].intersection(("blur", "turbulence"))]  # soft alpha and blobby shapes: long runs, where the scans of a wave's lanes stop far apart
+            straight = [k for k, e in enumerate(pool) if not premultiplied(e["pixels"])]
+            sized = frame_sized()  # (a same-size result of one of these is an image the frames take)
+            how = rng.uniform()
+            i = pick(straight) if straight and how < 0.2 else pick(soft) if soft and 0.2 <= how < 0.4 else pick(sized) if sized and 0.4 <= how < 0.6 else a_source(prefer_wide=True)
+            h, w = pool[i]["pixels"].shape[:2]
+            spread, mode, edge = int(rng.choice(SPREADS)), int(rng.randint(0, 2)), int(rng.randint(0, 4))
+            # the shape's channel: on colours above their alpha mostly a colour, whose inside map is not alpha's
+            channel = int(rng.randint(0, 3)) if not premultiplied(pool[i]["pixels"]) and rng.uniform() < 0.7 else int(rng.randint(0, 4))
+            threshold = int(rng.choice([1, 128, 255, rng.randint(1, 256)], p=[0.3, 0.3, 0.15, 0.25]))
+            if not DF.inside_map(pool[i]["pixels"], channel, threshold).any() and rng.uniform() < 0.7:
+                threshold = 1  # (mostly a shape with something in it; none at all where the channel is 0 everywhere)
+            big = bool(big_distance_left and max(w, h) <= 260 and rng.uniform() < 0.4)
+            if big:  # once per seed: a spread above 64, the three in turn over the seeds (the host model takes up to about 2 s for such a call)
+                spread = SPREADS_BIG[seed % len(SPREADS_BIG)]
+                big_distance_left -= 1
+            elif DF.grows(mode, edge) and max(DF.size(w, h, spread, mode, edge)) > MAX_SIDE:
+                edge = int(rng.randint(1, 4))
+            if max(DF.size(w, h, spread, mode, edge)) > 16384:
+                continue  # (the library refuses it)
+            inside = DF.inside_map(pool[i]["pixels"], channel, threshold)
+            emit(dict(kind="distance_field", image=i, spread=spread, mode=mode, channel=channel, threshold=threshold, edge=edge, width=w, inside=[int(inside.sum()), int(inside.size)]))
+            field = len(pool) - 1
+            outline = outline and DF.grows(mode, edge)
+            if outline:  # an outline's way: the grown field through a table, then with the image it grew from, placed by its origin
+                emit(dict(kind="color_filter", image=len(pool) - 1, matrix=None, tables=outline_tables(int(rng.randint(1, min(spread, 12) + 1)), spread), width=pool[-1]["pixels"].shape[1]))
+                emit(dict(kind="composite", image=i, source=len(pool) - 1, op=int(rng.randint(0, 13)), mode=int(rng.randint(0, 9)), opacity=float(rng.choice([1.0, rng.uniform()])),
+                          offset=[-spread, -spread], width=w))
+            if pool[field]["pixels"].shape[0] * pool[field]["pixels"].shape[1] > 120000:
+                # a large spread grew both axes: checked and destroyed at once, since every later reader's host model would pay for its texels
+                emit(dict(kind="check_image", image=field, depth=pool[field]["depth"]))
+                for k in (field + 1, field) if outline else (field,):
+                    emit(dict(kind="destroy_image", image=k))
+            after_filter(i, kind)
+        elif kind == "resize":
+            chain = rng.choice(["half", "ninth", None], p=[0.12, 0.08, 0.8])  # (decided here: room() renumbers the pool)
+            room(3 if chain else 1)
+            grown = [k for k, e in enumerate(pool) if e["origin"] != (0, 0)]  # the result's origin is (0, 0) whatever the source's is
+            i = pick(grown) if grown and rng.uniform() < 0.2 else a_source()
+            h, w = pool[i]["pixels"].shape[:2]
+            filter = int(rng.randint(0, len(RS.FILTERS)))
+            if chain == "half" and 4 <= min(w, h) and max(w, h) <= MAX_SIDE:  # the half-resolution blur: down by about 2, blurred, back up
+                half = [(w + 1) // 2, (h + 1) // 2]
+                emit(dict(kind="resize", image=i, size=half, filter=filter, target="half", chain="down", width=w))
+                emit(dict(kind="blur", image=len(pool) - 1, sigma=[float(rng.choice(SIGMAS[2:5])), float(rng.choice(SIGMAS[2:5]))], edge=int(rng.randint(1, 4)), width=half[0]))
+                emit(dict(kind="resize", image=len(pool) - 1, size=[w, h], filter=int(rng.randint(0, len(RS.FILTERS))), target="half", chain="up", width=half[0]))
+                after_filter(i, kind)
+                continue
+            if chain == "ninth":
+                # (one unit of one tap moves 1/16384 of the step between two texels: only rough texels show where it went)
+                rough = [k for k, e in enumerate(pool) if min(e["pixels"].shape[:2]) >= 45 and contrast(e["pixels"]) >= 40.0]
+                if rough:
+                    i = pick(rough)
+                else:  # none in the pool: random texels, a multiple of 9 on both axes from the start
+                    how = TEXELS[int(rng.randint(0, 2))]
+                    emit(dict(kind="create", how=how, pixels=random_texels(rng, how, 9 * int(rng.randint(5, 26)), 9 * int(rng.randint(4, 17)))))
+                    i = len(pool) - 1
+                h, w = pool[i]["pixels"].shape[:2]
+                # Down by exactly 9, by way of a multiple of 9 on both axes: every output's centre lies on a texel's centre, the taps on
+                # either side of it are pairs at equal distances, and 16384 / 9 leaves BOX a deficit of 4 — the centre, a pair and one tap
+                # of the next pair — so every output's taps hang on the rule's "ties to the lower index" (LANCZOS3: most outputs).
+                ninth = [int(np.clip((w + 4) // 9, 1, MAX_SIDE // 9)), int(np.clip((h + 4) // 9, 1, MAX_SIDE // 9))]
+                if (w, h) != (9 * ninth[0], 9 * ninth[1]):
+                    emit(dict(kind="resize", image=i, size=[9 * ninth[0], 9 * ninth[1]], filter=int(rng.choice([RS.BOX, RS.CATMULL_ROM])), target="ninth", chain="to a multiple", width=w))
+                    i = len(pool) - 1
+                emit(dict(kind="resize", image=i, size=ninth, filter=int(rng.choice([RS.BOX, RS.LANCZOS3])), target="ninth", chain="down by 9", width=9 * ninth[0]))
+                after_filter(i, kind)
+                continue
+            target = RESIZE_TARGETS[int(rng.choice(len(RESIZE_TARGETS), p=[0.28, 0.15, 0.17, 0.2, 0.2]))]
+            up = [a for a in (0, 1) if (w, h)[a] < MAX_SIDE and (w, h)[1 - a] > 1]  # the axes that can go up while the other goes down
+            if target == "same" and max(w, h) > MAX_SIDE:
+                target = "frame"
+            if target == "up and down" and not up:
+                target = "small"
+            up = pick(up) if target == "up and down" else None
+
+            def side(axis, n):
+                """a side of the target's class for the axis of n source texels"""
+                if target == "frame":  # results that load_image, set_table and the blits take
+                    return (width, height)[axis]
+                if target == "small":
+                    return int(rng.randint(1, (41, 31)[axis]))
+                if target == "same":
+                    return n
+                if target == "sides":
+                    return int(rng.choice(RESIZE_SIDES))
+                return int(rng.randint(n + 1, min(MAX_SIDE, 2 * n + 2) + 1)) if axis == up else int(rng.randint(1, min(n, MAX_SIDE + 1)))
+
+            size = [side(0, w), side(1, h)]
+            for axis, n in enumerate((w, h)):
+                while RS.max_count(n, size[axis], filter) > RS.MAX_TAPS:  # (the library refuses it: the axis is drawn again)
+                    assert target in ("small", "sides", "up and down")
+                    size[axis] = side(axis, n)
+            emit(dict(kind="resize", image=i, size=size, filter=filter, target=target, width=w))
+            if pool[i]["origin"] != (0, 0):
+                emit(dict(kind="check_image", image=len(pool) - 1, depth=pool[-1]["depth"]))
+            after_filter(i, kind)
+        elif kind == "refused":
+            # a call with an argument the header refuses, on a pool image: the status, and nothing else happens
+            long = [k for k, e in enumerate(pool) if max(e["pixels"].shape[:2]) > RS.MAX_TAPS]
+            sort = REFUSALS[int(rng.randint(0, len(REFUSALS) - (0 if long else 1)))]
+            i = pick(long) if sort == "taps" else int(rng.randint(0, len(pool)))
+            h, w = pool[i]["pixels"].shape[:2]
+            distance, size = dict(spread=4, mode=0, channel=3, threshold=128, edge=1), [8, 8]
+            if sort == "taps":  # BOX to one texel along the long side: more than 512 taps
+                size = [1, h] if w > RS.MAX_TAPS else [w, 1]
+            arguments = {"spread 0": dict(distance, spread=0), "spread 256": dict(distance, spread=256), "threshold 0": dict(distance, threshold=0),
+                         "width 0": dict(size=[0, 8], filter=RS.TRIANGLE), "height 16385": dict(size=[8, 16385], filter=RS.TRIANGLE), "filter 5": dict(size=size, filter=5),
+                         "taps": dict(size=size, filter=RS.BOX)}[sort]
+            emit(dict(kind="refused", image=i, sort=sort, call="distance_field" if "spread" in arguments else "resize", arguments=arguments,
+                      status=ERR_UNSUPPORTED if sort == "taps" else ERR_INVALID_ARGUMENT))
         elif kind == "mipmaps":
             emit(dict(kind="mipmaps", image=int(rng.randint(0, len(pool)))))
         elif kind == "check_image":

@@ -1,8 +1,8 @@
 """The model of crh_image_resize (include/contrast_hip.h states it), written from the header's text and not from the library: the taps of an
 axis in pure Python floats (IEEE binary64, one rounding per operation, never fused), with lighting_model's transcription of
 crh_d_sincos for the Lanczos sines, and the two integer passes in numpy int64 (every sum is far inside it, so the model cannot
-overflow where the library must not). `resize` also counts how often each clamp binds and how many texels min(v, alpha) changes, so that a
-test can assert that its input reaches those paths. Nothing here touches the library."""
+overflow where the library must not). `resize` also counts how often each clamp binds, how many texels min(v, alpha) changes and how many
+outputs' deficits end between two taps equally near the centre, so that a test can assert that its input reaches those paths. Nothing here touches the library."""
 import math
 
 import numpy as np
@@ -67,8 +67,10 @@ def max_count(n, m, filter):
     return max(window(n, m, filter, o)[1] for o in range(m))
 
 
-def axis_taps(n, m, filter):
-    """-> (first, count, taps): lists of m ints, m ints and m lists of signed ints. Raises Unsupported as the rule refuses."""
+def axis_taps(n, m, filter, tally=None):
+    """-> (first, count, taps): lists of m ints, m ints and m lists of signed ints. Raises Unsupported as the rule refuses. `tally`, a dict,
+    has its "split_ties" raised for every output whose deficit takes one of two taps equally near the centre and leaves the other: the
+    rule's "ties to the lower index" decides its taps."""
     first, count, taps = [], [], []
     for o in range(m):
         lo, k, c, s = window(n, m, filter, o)
@@ -83,6 +85,8 @@ def axis_taps(n, m, filter):
         if abs(d) > k:
             raise Unsupported(f"{NAMES[filter]} {n} -> {m}: output {o} has a deficit of {d} over {k} taps")
         nearest = sorted(range(k), key=lambda t: (abs(((lo + t) + 0.5) - c), t))
+        if tally is not None and 0 < abs(d) < k:
+            tally["split_ties"] += int(abs(((lo + nearest[abs(d) - 1]) + 0.5) - c) == abs(((lo + nearest[abs(d)]) + 0.5) - c))
         for t in nearest[:abs(d)]:
             q[t] += 1 if d > 0 else -1
         if sum(abs(v) for v in q) > MAX_GAIN:
@@ -108,12 +112,12 @@ def _pass(values, first, count, taps, add, shift, top, counters, name):
 
 def resize(pixels, width, height, filter, counters=None):
     """pixels: (h, w, 4) uint8 -> the (height, width, 4) uint8 result. `counters`, a dict, receives h_low, h_high, v_low, v_high (the
-    channel values each clamp changed) and min_alpha (the colour values min(v, alpha) lowered)."""
+    channel values each clamp changed), min_alpha (the colour values min(v, alpha) lowered) and split_ties (axis_taps, both axes)."""
     pixels = np.asarray(pixels)
     h, w = pixels.shape[:2]
-    tally = {"h_low": 0, "h_high": 0, "v_low": 0, "v_high": 0, "min_alpha": 0}
-    fx, cx, qx = axis_taps(w, width, filter)
-    fy, cy, qy = axis_taps(h, height, filter)
+    tally = {"h_low": 0, "h_high": 0, "v_low": 0, "v_high": 0, "min_alpha": 0, "split_ties": 0}
+    fx, cx, qx = axis_taps(w, width, filter, tally)
+    fy, cy, qy = axis_taps(h, height, filter, tally)
     t = _pass(pixels.astype(np.int64), fx, cx, qx, 32, 6, 65280, tally, "h")  # [h, width, 4]
     v = _pass(np.ascontiguousarray(t.transpose(1, 0, 2)), fy, cy, qy, 1 << 21, 22, 255, tally, "v").transpose(1, 0, 2)  # [height, width, 4]
     alpha = v[:, :, 3:4]

@@ -1,7 +1,9 @@
 """crh_image_distance_field (include/contrast_hip.h) on the GPU: k_image_distance_v and k_image_distance_h byte for byte against the numpy
 model of tests/distance_model.py, with no tolerance and no excluded texel, at the smallest shapes where the kernels can go wrong — widths
-round a wave and a row segment, heights round the vertical kernel's row blocks, aprons larger than the image, blocks with nothing in them,
-the grown origin, the last squared distance that counts, the longest axes — and the result as a source of the other image calls."""
+round a wave and a row segment, heights round the vertical kernel's row blocks on both sides of the launcher's switch between them, aprons
+larger than the image and the largest aprons on rows wider than a segment, blocks with nothing in them, colours above their alpha as the
+shape's channel, filled shapes and noise with long scans, the grown origin, the last squared distance that counts, the longest axes — and
+the result as a source of the other image calls."""
 import ctypes as C
 import itertools
 
@@ -15,8 +17,10 @@ from contrast_renderer_amd.renderer import Image
 import color_filter_model as FM
 import composite_model as CM
 import distance_model as M
+import layers_model
 import lighting_model as LM
 import mip_model
+import turbulence_model as TM
 from test_gpu_blending import no_pins  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -79,6 +83,69 @@ def test_heights_round_the_window_and_the_row_blocks(spread, renderer, no_pins):
         source = Image(renderer, src)
         for mode, edge in ((M.OUTSIDE, M.TRANSPARENT), (M.OUTSIDE, M.REFLECT), (M.INSIDE, M.TRANSPARENT), (M.INSIDE, M.REPEAT)):
             run_and_check(source, src, spread, mode, edge, M.A, 1)
+
+
+@pytest.mark.parametrize("spread", (16, 17))
+def test_row_blocks_on_both_sides_of_the_launchers_switch(spread, renderer, no_pins):
+    """launch_image_distance_v takes 32-row blocks up to spread 16 and 128-row blocks from 17: both spreads on heights one row less than,
+    exactly and one row more than either block, so each kernel runs a last block of one row, a full one and, for the other's heights,
+    blocks it would not have been given. Width 65: two column blocks, the second of one lane."""
+    for height in (31, 32, 33, 127, 128, 129):
+        src = mask(65, height, 1000 * spread + height, 0.1)
+        src[height // 2, 64] = 255  # (never empty, and the lone lane's column has a target)
+        source = Image(renderer, src)
+        for mode, edge in ((M.OUTSIDE, M.TRANSPARENT), (M.OUTSIDE, M.REFLECT), (M.INSIDE, M.TRANSPARENT), (M.INSIDE, M.REPEAT)):
+            run_and_check(source, src, spread, mode, edge, M.A, 1)
+
+
+@pytest.mark.parametrize("size", [(300, 3), (513, 2)], ids=["300x3", "513x2"])
+def test_the_largest_aprons_on_rows_wider_than_a_segment(size, renderer, no_pins):
+    """Spreads 129 and 255 under the three same-size edges on rows of two and of three segments: a segment of k_image_distance_h stages
+    bytes from beyond both its neighbours, the first and the last one through the wrap (at 255 more than a whole 300-texel row of it).
+    One inside texel at column 0, one at the last column — each is seen from the other end of the row only through REPEAT — and a
+    sparse mask."""
+    w, h = size
+    first, last = np.zeros((h, w, 4), dtype=np.uint8), np.zeros((h, w, 4), dtype=np.uint8)
+    first[0, 0], last[h - 1, w - 1] = 255, 255
+    for src in (first, last, mask(w, h, w, 0.01)):
+        assert src[..., 3].any()
+        source = Image(renderer, src)
+        for spread, mode, edge in itertools.product((129, 255), MODES, (M.PAD, M.REPEAT, M.REFLECT)):
+            run_and_check(source, src, spread, mode, edge)
+
+
+def test_a_colour_above_its_alpha_is_the_shape_as_it_is_stored(renderer, no_pins):
+    """Straight texels, alpha 0 .. 199 and colours above it: the shape's channel is R, G or B, "the stored code, as it is" — no clamp to
+    alpha, and not alpha's inside map, which differs from the channel's in every case here."""
+    src = layers_model.random_texels(np.random.RandomState(31), "straight", 70, 37)
+    assert not layers_model.premultiplied(src) and src[..., 3].max() <= 199
+    source = Image(renderer, src)
+    for channel, threshold in itertools.product((M.R, M.G, M.B), (1, 128, 255)):
+        assert not np.array_equal(M.inside_map(src, channel, threshold), M.inside_map(src, M.A, threshold)), (channel, threshold)
+        assert not np.array_equal(M.inside_map(src, channel, threshold), M.inside_map(np.minimum(src, src[..., 3:]), channel, threshold)), (channel, threshold)
+        for mode, edge in itertools.product(MODES, (M.TRANSPARENT, M.REFLECT)):
+            expect = M.distance_field(src, 5, mode, channel, threshold, edge)
+            assert not np.array_equal(expect, M.distance_field(src, 5, mode, M.A, threshold, edge))  # reading alpha instead cannot pass
+            run_and_check(source, src, 5, mode, edge, channel, threshold)
+
+
+@pytest.mark.parametrize("shape", ("disc", "complement", "noise"))
+def test_long_scans_over_filled_shapes_and_noise(shape, renderer, no_pins):
+    """130 x 70 with long runs of inside and of outside texels: a filled disc of radius 25, its complement, and fractal noise as the
+    device makes it, thresholded on R. Deep inside a run distance_scan goes many steps before dx^2 reaches the best value, at a run's rim
+    it stops at once: the lanes of a wave stop far apart, at spreads below and above half a segment."""
+    w, h = 130, 70
+    j, i = np.mgrid[0:h, 0:w]
+    if shape == "noise":
+        src = TM.turbulence(w, h, (0.03, 0.05), 2, 7, TM.FRACTAL_NOISE, False, True, (0.0, 0.0))  # opaque: R lies round 128
+    else:
+        inside = (np.hypot(i - 60, j - 33) < 25) == (shape == "disc")
+        src = np.repeat((inside * 255).astype(np.uint8)[:, :, None], 4, axis=2)
+    inside = M.inside_map(src, M.R, 128)
+    assert 0.1 < inside.mean() < 0.9, inside.mean()
+    source = Image(renderer, src)
+    for spread, mode, edge in itertools.product((40, 128), MODES, (M.TRANSPARENT, M.REFLECT)):
+        run_and_check(source, src, spread, mode, edge, M.R, 128)
 
 
 @pytest.mark.parametrize("size", [(1, 1), (2, 3), (40, 40)], ids=["1x1", "2x3", "40x40"])

@@ -1,7 +1,9 @@
 """Stateful fuzz of the image and layer pipeline on the GPU: the op sequences of tests/layers_model.py replayed on one Renderer — images created,
 snapshot from frames in whatever state, made of noise, blurred, composited, colour filtered, eroded and dilated, convolved, lit, displaced,
-mipmapped, destroyed behind the call that read them, loaded back into frames and drawn as image paints through tables that outlive their images, between clears, uploads, plain passes and re-uploads of a Scene that holds a paint table. The host
-model has an exact expectation for every step, so every download is compared byte for byte, with no tolerance and no excluded texel."""
+turned into distance fields, resized, mipmapped, destroyed behind the call that read them, loaded back into frames and drawn as image paints
+through tables that outlive their images, between clears, uploads, plain passes, re-uploads of a Scene that holds a paint table and calls
+that the library refuses, which must leave the pool and the image they named as they were. The host model has an exact expectation for
+every step, so every download is compared byte for byte, with no tolerance and no excluded texel."""
 import os
 
 import numpy as np
@@ -9,8 +11,8 @@ import pytest
 
 from contrast_renderer_amd import Path, batch_from_shapes
 from contrast_renderer_amd import renderer as R
-from contrast_renderer_amd.renderer import (BlurEdge, Channel, DistantLight, Filter, Image, ImagePaint, LightingOp, MorphologyOp, PointLight, SpotLight,
-                                            TurbulenceKind)
+from contrast_renderer_amd.renderer import (BlurEdge, Channel, ContrastError, DistanceMode, DistantLight, Filter, Image, ImagePaint, LightingOp, MorphologyOp, PointLight,
+                                            ResizeFilter, SpotLight, TurbulenceKind)
 
 import layers_model as L
 import lighting_model as LM
@@ -107,6 +109,20 @@ def test_random_layer_pipelines_against_a_host_model(seed, oracle_lib, no_pins):
             pool.append(Image.turbulence(r, op["size"][0], op["size"][1], op["frequency"], op["octaves"], op["seed"], TurbulenceKind(op["noise"]), op["stitch"], op["opaque"], op["offset"]))
         elif kind == "displace":
             pool.append(pool[op["image"]].displace(pool[op["map"]], op["scale"], Channel(op["channels"][0]), Channel(op["channels"][1]), Filter(op["filter"]), BlurEdge(op["edge"])))
+        elif kind == "distance_field":
+            pool.append(pool[op["image"]].distance_field(op["spread"], DistanceMode(op["mode"]), Channel(op["channel"]), op["threshold"], BlurEdge(op["edge"])))
+        elif kind == "resize":
+            pool.append(pool[op["image"]].resize(op["size"][0], op["size"][1], ResizeFilter(op["filter"])))
+        elif kind == "refused":  # plain integers: the enumerations have no member for what the header refuses
+            image, how = pool[op["image"]], op["arguments"]
+            with pytest.raises(ContrastError) as refused:
+                if op["call"] == "distance_field":
+                    image.distance_field(how["spread"], how["mode"], how["channel"], how["threshold"], how["edge"])
+                else:
+                    image.resize(how["size"][0], how["size"][1], how["filter"])
+            assert refused.value.status == op["status"], f"{where}: the status is {refused.value.status}"
+            assert len(pool) == len(model.pool), where
+            compare(image.download_level(0), expect[0], step, op, "the image a refused call named")
         elif kind == "mipmaps":
             pool[op["image"]].generate_mipmaps()
         elif kind == "check_image":

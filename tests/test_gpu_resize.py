@@ -2,7 +2,8 @@
 tests/resize_model.py, with no tolerance and no excluded texel, at the smallest shapes where the kernels can go wrong — widths round a
 wave, the horizontal kernel's group of output columns and its chunk of staged source columns, heights round its 64-row tile and the
 vertical kernel's row block, one texel on either side of the call, odd and even windows at both image ends, prime ratios in both
-directions at once, the longest windows, the input that binds every clamp — and the result as a source of the other image calls."""
+directions at once, the longest windows, the input that binds every clamp, colours above their alpha, where min(v, alpha) binds on most
+texels — and the result as a source of the other image calls."""
 import ctypes as C
 import itertools
 
@@ -15,6 +16,7 @@ from contrast_renderer_amd.renderer import Image
 
 import blur_model as BM
 import composite_model as CM
+import layers_model
 import mip_model
 import resize_model as M
 from test_gpu_blending import no_pins  # noqa: F401
@@ -132,6 +134,21 @@ def test_the_checker_binds_every_clamp(renderer, no_pins):
         counters = {}
         run_and_check(Image(renderer, src), src, 5, 4, filter, counters)
         assert counters["min_alpha"] > 0, (M.NAMES[filter], counters)  # min(v, alpha) lowers a colour
+
+
+def test_straight_sources_where_min_alpha_binds_on_most_texels(renderer, no_pins):
+    """Colours above their alpha (alpha 0 .. 199, R above it everywhere): resize_texel's min(v, alpha) lowers a colour on most texels, not
+    only where a filter overshoots; to the source's own size, up on one axis and down on the other both ways, under every filter. The
+    result is premultiplied whatever the source was."""
+    src = layers_model.random_texels(np.random.RandomState(23), "straight", 70, 37)
+    assert not layers_model.premultiplied(src)
+    source = Image(renderer, src)
+    for filter, (width, height) in itertools.product(M.FILTERS, ((70, 37), (13, 90), (150, 5))):
+        counters = {}
+        got = run_and_check(source, src, width, height, filter, counters)
+        assert counters["min_alpha"] > 0, (M.NAMES[filter], width, height, counters)
+        assert layers_model.premultiplied(got), (M.NAMES[filter], width, height)
+    assert np.array_equal(source.download_level(0), src)
 
 
 def test_constants_and_copies(renderer, no_pins):

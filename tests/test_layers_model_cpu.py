@@ -1,5 +1,6 @@
-"""The generator and the host model of the image and layer fuzz (tests/layers_model.py) without a GPU: the conditions that keep the fuzz from
-degenerating, its determinism, the blit rule against the float64 model of image paints, and the model's steps against the library's host rules."""
+"""The generator and the host model of the image and layer fuzz (tests/layers_model.py) without a GPU — its kinds: create, snapshot, blur,
+composite, color_filter, morphology, convolve, lighting, turbulence, displace, distance_field, resize, mipmaps, the frame and table ops and
+the refused calls: the conditions that keep the fuzz from degenerating, its determinism, the blit rule against the float64 model of image paints, and the model's steps against the library's host rules."""
 import os
 from collections import Counter
 
@@ -67,7 +68,8 @@ def test_the_newer_filters_meet_their_conditions(generated):
     chain, sources destroyed behind the call, and results that reach a frame — also through a table that outlives them."""
     n = Counter()
     routes, windows, lights = Counter(), Counter(), set()
-    edges = {kind: set() for kind in L.NEW if kind != "turbulence"}
+    five = L.NEW[:5]  # this test's kinds: its counters count them alone (test_distance_and_resize_meet_their_conditions has the two that came later)
+    edges = {kind: set() for kind in five if kind != "turbulence"}
     seen = {name: set() for name in ("morphology op", "preserve_alpha", "displace filter", "convolve width", "noise", "stitch", "opaque", "octaves")}
     for setup, ops in generated:
         assert sum(1 for op in ops if op["kind"] == "morphology" and max(op["radius"]) > 64) <= 1
@@ -78,6 +80,8 @@ def test_the_newer_filters_meet_their_conditions(generated):
                 edges[kind].add(op["edge"])
                 n[kind, "deep"] += int(op["depth"] >= 2)
                 n["mipmapped source"] += int(op["mip"])
+            elif kind in L.NEW and kind != "turbulence":
+                n[kind, "deep"] += int(op["depth"] >= 2)
             if kind in L.READS and kind != "check_image" and "turbulence" in op["by"]:
                 n["turbulence", "deep"] += 1  # its result is consumed
             if kind == "morphology":
@@ -117,10 +121,10 @@ def test_the_newer_filters_meet_their_conditions(generated):
                 seen["displace filter"].add(op["filter"])
             elif kind == "composite":
                 n["grown dilate drawn on"] += int(L.GROWN_DILATE in op["via"])
-            elif kind in ("blit", "blit_mip", "load_image") and set(op["via"]) & set(L.NEW):
+            elif kind in ("blit", "blit_mip", "load_image") and set(op["via"]) & set(five):
                 n["reaches a frame"] += 1
                 n["reaches a frame destroyed"] += int(kind == "blit" and op["destroyed"])
-            elif kind == "destroy_image" and op.get("behind") in L.NEW:
+            elif kind == "destroy_image" and op.get("behind") in five:
                 n["source destroyed behind the call"] += 1
     print(dict(n), dict(routes), dict(windows))
     assert set(routes) == set(L.ROUTES) and min(routes.values()) >= 2, routes
@@ -138,6 +142,85 @@ def test_the_newer_filters_meet_their_conditions(generated):
     assert n["mipmapped source"] >= 3 and n["reaches a frame"] >= 3 and n["reaches a frame destroyed"] >= 1 and n["source destroyed behind the call"] >= 2, n
 
 
+def test_distance_and_resize_meet_their_conditions(generated):
+    """What keeps distance_field and resize from degenerating inside the sequences, as floors on what the generator feeds them: every mode,
+    edge, channel, filter and target class; both sides of launch_image_distance_v's switch of row blocks on results of more than one
+    block; the large spreads; grown results composited at their origin; sources wider than k_image_distance_h's segment, straight ones
+    read on a colour channel, soft and blobby ones, empty and full ones; straight sources where resize's min(v, alpha) binds, grown
+    sources whose origin the result must drop, the half-resolution chain; deep, mipmapped and destroyed sources, results that reach a
+    frame, also through a table that outlives them; and the calls the library refuses."""
+    n = Counter()
+    seen = {name: set() for name in ("mode", "edge", "channel", "filter", "refused")}
+    large, targets = Counter(), Counter()
+    for setup, ops in generated:
+        big = [op["spread"] for op in ops if op["kind"] == "distance_field" and op["spread"] > 64]
+        assert len(big) <= 1 and set(big) <= set(L.SPREADS_BIG), big
+        large.update(big)
+        checked = {op["uid"] for op in ops if op["kind"] == "check_image"}
+        for op in ops:
+            kind = op["kind"]
+            if kind in ("distance_field", "resize"):
+                w, h = op["source_size"]
+                n[kind, "deep"] += int(op["depth"] >= 2)
+                n[kind, "mipmapped source"] += int(op["mip"])
+            if kind == "distance_field":
+                grown = op["mode"] == 0 and op["edge"] == 0
+                assert op["spread"] in L.SPREADS + L.SPREADS_BIG and 1 <= op["threshold"] <= 255
+                assert tuple(op["size"]) == ((w + 2 * op["spread"], h + 2 * op["spread"]) if grown else (w, h)) and max(op["size"]) <= 16384
+                assert op["spread"] > 64 or max(op["size"]) <= max(L.MAX_SIDE, w, h), op["size"]
+                for name in ("mode", "edge", "channel"):
+                    seen[name].add(op[name])
+                for spread in (16, 17):
+                    n["spread", spread, "over 32 rows"] += int(op["spread"] == spread and op["size"][1] > 32)
+                n["grown"] += int(grown)
+                n["wide source"] += int(w > 256)
+                n["straight source on a colour"] += int(op["straight"][0] and op["channel"] != 3)
+                n["soft source"] += int(bool({"blur", "turbulence"} & set(op["via"])))
+                n["nothing inside"] += int(op["inside"][0] == 0)
+                n["everything inside"] += int(op["inside"][0] == op["inside"][1])
+            elif kind == "resize":
+                assert op["filter"] in range(5) and 1 <= min(op["size"]) and max(op["size"]) <= L.MAX_SIDE, op["size"]
+                seen["filter"].add(op["filter"])
+                is_class = {"frame": tuple(op["size"]) == (setup["width"], setup["height"]), "small": op["size"][0] <= 40 and op["size"][1] <= 30, "same": tuple(op["size"]) == (w, h),
+                            "up and down": (op["size"][0] - w) * (op["size"][1] - h) < 0, "sides": set(op["size"]) <= set(L.RESIZE_SIDES),
+                            "half": op.get("chain") in ("down", "up"), "ninth": op.get("chain") == "to a multiple" or (w, h) == (9 * op["size"][0], 9 * op["size"][1])}
+                assert is_class[op["target"]], (op["target"], op["size"], op["source_size"])
+                targets[op["target"]] += 1
+                n["half-resolution chains"] += int(op.get("chain") == "up")
+                n["most outputs split a tie, on rough texels"] += int(2 * op["split_ties"] > op["size"][0] + op["size"][1] and op["contrast"] >= 20.0)
+                if op["straight"][0]:
+                    assert op["min_alpha"] > 0, (setup["seed"], op["size"], op["source_size"])
+                    n["straight resize source"] += 1
+                n["grown resize source, result checked"] += int(op["source_origin"] != (0, 0) and op["result"] in checked)
+            elif kind == "composite":
+                n["grown distance drawn on"] += int(L.GROWN_DISTANCE in op["via"] and op["offset"][0] == op["offset"][1] < 0)
+            elif kind == "refused":
+                assert op["status"] == (L.ERR_UNSUPPORTED if op["sort"] == "taps" else L.ERR_INVALID_ARGUMENT)
+                n["refused"] += 1
+                seen["refused"].add(op["sort"])
+            elif kind == "destroy_image" and op.get("behind") in ("distance_field", "resize"):
+                n[op["behind"], "source destroyed behind the call"] += 1
+            if kind in ("blit", "blit_mip", "load_image"):
+                for made in ("distance_field", "resize"):
+                    if made in op["via"]:
+                        n[made, "reaches a frame"] += 1
+                        n[made, "reaches a frame destroyed"] += int(kind == "blit" and op["destroyed"])
+    print(dict(n), dict(large), dict(targets), {name: sorted(found) for name, found in seen.items()})
+    assert seen["mode"] == {0, 1} and seen["edge"] == seen["channel"] == {0, 1, 2, 3}, seen
+    assert n["spread", 16, "over 32 rows"] >= 1 and n["spread", 17, "over 32 rows"] >= 1, n
+    assert set(large) == set(L.SPREADS_BIG), large
+    assert n["grown"] >= 3 and n["grown distance drawn on"] >= 2 and n["wide source"] >= 2 and n["straight source on a colour"] >= 2 and n["soft source"] >= 3, n
+    assert n["nothing inside"] >= 1 and n["everything inside"] >= 1, n
+    assert seen["filter"] == {0, 1, 2, 3, 4} and all(targets[name] >= 2 for name in L.RESIZE_TARGETS), (seen, targets)
+    assert n["straight resize source"] >= 2 and n["grown resize source, result checked"] >= 1 and n["half-resolution chains"] >= 2, n
+    # the deficit ends between two taps equally near the centre: only the rule's tie order places it, and only a step between the two texels shows it
+    assert n["most outputs split a tie, on rough texels"] >= 2, n
+    for kind in ("distance_field", "resize"):
+        assert n[kind, "deep"] >= 2 and n[kind, "mipmapped source"] >= 1 and n[kind, "source destroyed behind the call"] >= 2, (kind, n)
+        assert n[kind, "reaches a frame"] >= 3 and n[kind, "reaches a frame destroyed"] >= 1, (kind, n)
+    assert n["refused"] >= 3 and len(seen["refused"]) >= 3, (n, seen)
+
+
 def host_rule(op, pool):
     """What the library's host function (crh_<filter>_texels) makes of an op of one of the newer kinds on the model's bytes."""
     kind = op["kind"]
@@ -150,6 +233,10 @@ def host_rule(op, pool):
         return R.convolve_texels(pixels, op["kernel"], op["divisor"], op["bias"], op["target"], op["edge"], op["preserve_alpha"])
     if kind == "displace":
         return R.displace_texels(pixels, pool[op["map"]]["pixels"], tuple(op["scale"]), op["channels"][0], op["channels"][1], op["filter"], op["edge"])
+    if kind == "distance_field":
+        return R.distance_texels(pixels, op["spread"], op["mode"], op["channel"], op["threshold"], op["edge"])
+    if kind == "resize":
+        return R.resize_texels(pixels, op["size"][0], op["size"][1], op["filter"])
     light = op["light"]
     mirror = (R.DistantLight(light["azimuth"], light["elevation"]) if light["kind"] == 0 else R.PointLight(*light["position"]) if light["kind"] == 1 else
               R.SpotLight(tuple(light["position"]), tuple(light["points_at"]), light["spot_exponent"], light["cone_angle"]))
@@ -157,8 +244,8 @@ def host_rule(op, pool):
 
 
 def test_the_generated_ops_of_the_newer_kinds_equal_the_host_rules(generated, oracle_lib):
-    """Every morphology, convolve, lighting, turbulence and displace op of the default seeds, with the arguments and on the inputs the
-    sequence gives it — grown, filtered, snapshot and straight images among them: the model's bytes are the host rule's, so the library
+    """Every morphology, convolve, lighting, turbulence, displace, distance_field and resize op of the default seeds, with the arguments and
+    on the inputs the sequence gives it — grown, filtered, snapshot and straight images among them: the model's bytes are the host rule's, so the library
     accepts every generated call, and a difference on the GPU is the device's."""
     import __graft_entry__ as entry
     entry.build()
@@ -215,7 +302,7 @@ def test_a_code_decodes_and_encodes_to_itself():
 
 def test_the_models_steps_equal_the_librarys_host_rules(oracle_lib):
     """Three chained images — a blur, a composite of it over its source, a colour filter of that — by the Python models the fuzz replays and
-    by the library's host mirrors: crh_blur_taps, crh_composite_texels, crh_color_filter_texels; then a chain through the five newer steps."""
+    by the library's host mirrors: crh_blur_taps, crh_composite_texels, crh_color_filter_texels; then a chain through the five newer steps, and a distance field and a resize of the same straight texels."""
     import __graft_entry__ as entry
     entry.build()
     rng = np.random.RandomState(8)
@@ -263,3 +350,15 @@ def test_the_models_steps_equal_the_librarys_host_rules(oracle_lib):
             how = (surface_scale, L.f32(0.9), 12.0, [1.0, 0.5, L.f32(0.3)], op + 1)
             lit = L.step_lighting(displaced, light, op, *how)
             assert np.array_equal(lit, R.lighting_texels(displaced, mirror, op, *how)), (light, op)
+    # The two newest steps on the straight texels: the shape read on a colour channel, as it is (its inside map is not alpha's), and a
+    # resize whose min(v, alpha) binds — by the models the fuzz replays and by crh_distance_texels and crh_resize_texels.
+    for spread, mode, channel, threshold, edge in ((3, 0, 0, 128, 0), (17, 1, 1, 1, 2), (16, 0, 2, 255, 3), (255, 1, 3, 100, 1)):
+        field = L.step_distance_field(base, spread, mode, channel, threshold, edge)
+        assert np.array_equal(field, R.distance_texels(base, spread, mode, channel, threshold, edge)), (spread, mode, channel, threshold, edge)
+        assert field.shape == ((13 + 2 * spread, 21 + 2 * spread, 4) if (mode, edge) == (0, 0) else base.shape)
+    assert not np.array_equal(base[..., 0] >= 128, base[..., 3] >= 128)
+    for size, filter in (((21, 13), 4), ((8, 30), 0), ((40, 5), 2), ((1, 1), 3), ((33, 14), 1)):
+        counters = {}
+        resized = L.step_resize(field if filter == 1 else base, size[0], size[1], filter, counters)
+        assert np.array_equal(resized, R.resize_texels(field if filter == 1 else base, size[0], size[1], filter)), (size, filter)
+        assert L.premultiplied(resized) and resized.shape == (size[1], size[0], 4) and (filter == 1 or counters["min_alpha"] > 0), (size, filter, counters)
