@@ -708,37 +708,17 @@ CRH_D int sub_lane_bit(int v, unsigned long long mask) { // v - (this lane's bit
 }
 // "over" on the lanes of mask[b] only (sample row b), the others keep their colour: the blends run under the masks as the EXEC mask — no
 // select per channel —, dst = src + dst * (1 - alpha) as a multiply and an add (Rust does not contract), or dst = src for an opaque source.
-// One asm statement for the four rows: the colour registers are updated in place (per row, the compiler moved them to temporaries and back).
-CRH_D void blend_rows(float (&c)[4][4], const unsigned long long (&mask)[4], float s0, float s1, float s2, float s3, float one_minus_a, bool replace) {
+// ONE asm statement for the four rows and for BOTH variants, the choice between them a uniform scalar branch inside it: the colour registers are
+// updated in place. (Per row, the compiler moved them to temporaries and back. As one statement per variant under an if / else, the structurizer's
+// flow block between the arms kept the sixteen colours alive beside the first arm's results: registers of their own for each arm, and copies where
+// they meet — 36 moves a cover with the ones that followed from them.) Register operands only; EXEC is restored on both ways through.
+CRH_D void blend_rows(float (&c)[4][4], const unsigned long long (&mask)[4], float s0, float s1, float s2, float s3, float one_minus_a, uint32_t replace) { // replace: 0 or 1, uniform
 #if defined(__HIP_DEVICE_COMPILE__)
     unsigned long long saved;
-    if (replace) {
-        asm volatile("s_mov_b64 %[saved], exec\n\t"
-                 "s_mov_b64 exec, %[m0]\n\t"
-                 "v_mov_b32 %[c00], %[s0]\n\t"
-                 "v_mov_b32 %[c01], %[s1]\n\t"
-                 "v_mov_b32 %[c02], %[s2]\n\t"
-                 "v_mov_b32 %[c03], %[s3]\n\t"
-                 "s_mov_b64 exec, %[m1]\n\t"
-                 "v_mov_b32 %[c10], %[s0]\n\t"
-                 "v_mov_b32 %[c11], %[s1]\n\t"
-                 "v_mov_b32 %[c12], %[s2]\n\t"
-                 "v_mov_b32 %[c13], %[s3]\n\t"
-                 "s_mov_b64 exec, %[m2]\n\t"
-                 "v_mov_b32 %[c20], %[s0]\n\t"
-                 "v_mov_b32 %[c21], %[s1]\n\t"
-                 "v_mov_b32 %[c22], %[s2]\n\t"
-                 "v_mov_b32 %[c23], %[s3]\n\t"
-                 "s_mov_b64 exec, %[m3]\n\t"
-                 "v_mov_b32 %[c30], %[s0]\n\t"
-                 "v_mov_b32 %[c31], %[s1]\n\t"
-                 "v_mov_b32 %[c32], %[s2]\n\t"
-                 "v_mov_b32 %[c33], %[s3]\n\t"
-                 "s_mov_b64 exec, %[saved]"
-                 : [c00] "+v"(c[0][0]), [c01] "+v"(c[0][1]), [c02] "+v"(c[0][2]), [c03] "+v"(c[0][3]), [c10] "+v"(c[1][0]), [c11] "+v"(c[1][1]), [c12] "+v"(c[1][2]), [c13] "+v"(c[1][3]), [c20] "+v"(c[2][0]), [c21] "+v"(c[2][1]), [c22] "+v"(c[2][2]), [c23] "+v"(c[2][3]), [c30] "+v"(c[3][0]), [c31] "+v"(c[3][1]), [c32] "+v"(c[3][2]), [c33] "+v"(c[3][3]), [saved] "=&s"(saved)
-                 : [m0] "s"(mask[0]), [m1] "s"(mask[1]), [m2] "s"(mask[2]), [m3] "s"(mask[3]), [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3));
-    } else {
-        asm volatile("s_mov_b64 %[saved], exec\n\t"
+    const uint32_t variant = __builtin_amdgcn_readfirstlane(replace); // (a scalar register for the compare; the callers decide it on scalars, so this is no instruction)
+    asm volatile("s_mov_b64 %[saved], exec\n\t"
+                 "s_cmp_lg_u32 %[variant], 0\n\t"
+                 "s_cbranch_scc1 .Lblend_replace_%=\n\t"
                  "s_mov_b64 exec, %[m0]\n\t"
                  "v_mul_f32 %[c00], %[c00], %[oma]\n\t"
                  "v_mul_f32 %[c01], %[c01], %[oma]\n\t"
@@ -775,10 +755,33 @@ CRH_D void blend_rows(float (&c)[4][4], const unsigned long long (&mask)[4], flo
                  "v_add_f32 %[c31], %[s1], %[c31]\n\t"
                  "v_add_f32 %[c32], %[s2], %[c32]\n\t"
                  "v_add_f32 %[c33], %[s3], %[c33]\n\t"
+                 "s_branch .Lblend_done_%=\n"
+                 ".Lblend_replace_%=:\n\t"
+                 "s_mov_b64 exec, %[m0]\n\t"
+                 "v_mov_b32 %[c00], %[s0]\n\t"
+                 "v_mov_b32 %[c01], %[s1]\n\t"
+                 "v_mov_b32 %[c02], %[s2]\n\t"
+                 "v_mov_b32 %[c03], %[s3]\n\t"
+                 "s_mov_b64 exec, %[m1]\n\t"
+                 "v_mov_b32 %[c10], %[s0]\n\t"
+                 "v_mov_b32 %[c11], %[s1]\n\t"
+                 "v_mov_b32 %[c12], %[s2]\n\t"
+                 "v_mov_b32 %[c13], %[s3]\n\t"
+                 "s_mov_b64 exec, %[m2]\n\t"
+                 "v_mov_b32 %[c20], %[s0]\n\t"
+                 "v_mov_b32 %[c21], %[s1]\n\t"
+                 "v_mov_b32 %[c22], %[s2]\n\t"
+                 "v_mov_b32 %[c23], %[s3]\n\t"
+                 "s_mov_b64 exec, %[m3]\n\t"
+                 "v_mov_b32 %[c30], %[s0]\n\t"
+                 "v_mov_b32 %[c31], %[s1]\n\t"
+                 "v_mov_b32 %[c32], %[s2]\n\t"
+                 "v_mov_b32 %[c33], %[s3]\n"
+                 ".Lblend_done_%=:\n\t"
                  "s_mov_b64 exec, %[saved]"
                  : [c00] "+v"(c[0][0]), [c01] "+v"(c[0][1]), [c02] "+v"(c[0][2]), [c03] "+v"(c[0][3]), [c10] "+v"(c[1][0]), [c11] "+v"(c[1][1]), [c12] "+v"(c[1][2]), [c13] "+v"(c[1][3]), [c20] "+v"(c[2][0]), [c21] "+v"(c[2][1]), [c22] "+v"(c[2][2]), [c23] "+v"(c[2][3]), [c30] "+v"(c[3][0]), [c31] "+v"(c[3][1]), [c32] "+v"(c[3][2]), [c33] "+v"(c[3][3]), [saved] "=&s"(saved)
-                 : [m0] "s"(mask[0]), [m1] "s"(mask[1]), [m2] "s"(mask[2]), [m3] "s"(mask[3]), [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [oma] "v"(one_minus_a));
-    }
+                 : [m0] "s"(mask[0]), [m1] "s"(mask[1]), [m2] "s"(mask[2]), [m3] "s"(mask[3]), [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [oma] "v"(one_minus_a), [variant] "s"(variant)
+                 : "scc");
 #else
     (void)c, (void)mask, (void)s0, (void)s1, (void)s2, (void)s3, (void)one_minus_a, (void)replace;
 #endif
@@ -1077,14 +1080,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
                         cell[b] = add_lane_bit(cell[b] ^ back, filled) ^ back; // ~(~c + bit) = c - bit
                     }
                 };
-                if (kind == KIND_IQ)
-                    curve(std::integral_constant<uint32_t, KIND_IQ>{});
-                else if (kind == KIND_IC)
-                    curve(std::integral_constant<uint32_t, KIND_IC>{});
-                else if (kind == KIND_RQ)
-                    curve(std::integral_constant<uint32_t, KIND_RQ>{});
-                else
-                    curve(std::integral_constant<uint32_t, KIND_RC>{});
+                // Four ifs side by side, not an if / else chain, and each on a copy of `kind` the compiler cannot see through (it would thread them back
+                // into the chain): behind the structurizer an else arm is a second guarded block BEHIND the first, and the cells as they came in stay
+                // alive beside the first arm's results for it — every arm then worked on copies: a move in front of each skipped row, four at the
+                // loop's back edge and four more where the edge loop ends. A lone if that updates the cells joins them with themselves.
+                auto is_kind = [&](uint32_t k) {
+                    uint32_t mine = kind;
+#if defined(__HIP_DEVICE_COMPILE__)
+                    asm volatile("" : "+s"(mine));
+#endif
+                    return mine == k;
+                };
+                if (is_kind(KIND_IQ)) curve(std::integral_constant<uint32_t, KIND_IQ>{});
+                if (is_kind(KIND_IC)) curve(std::integral_constant<uint32_t, KIND_IC>{});
+                if (is_kind(KIND_RQ)) curve(std::integral_constant<uint32_t, KIND_RQ>{});
+                if (is_kind(KIND_RC)) curve(std::integral_constant<uint32_t, KIND_RC>{});
             }
             if (end >= 64u) break; // (the group runs on into the next chunk)
             rest = end >= 63u ? 0ull : rest & (~0ull << (end + 1u));
@@ -1099,9 +1109,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
             float cs0, cs1, cs2, cs3;
             // replace: an opaque source over finite colours — src + dst * (1 - 1) is the source (r.occlude: every colour of the pass is tame; a source
             // component that is -0 would come out as +0 through the arithmetic, so it takes the arithmetic)
-            bool replace;
+            uint32_t replace; // (0 or 1, put together from scalar words: as a bool it came to the blend through a vector register)
             if (kind == EK_SYNTH) { // COVER over the samples inside the hull, one unit of both backdrops folded in
-                replace = r.occlude != 0u && (flags & (1u << 20)) != 0u;
+                replace = (r.occlude != 0u ? 1u : 0u) & (flags >> 20);
                 const float4 ea4 = entries[end * 3u + 0u];
                 const uint32_t code_all = (flags >> 8) & 31u;
                 const int add = ((int)((flags >> 16) & 3u) - 1) + ((int)((flags >> 18) & 3u) - 1) * 65536;
@@ -1145,7 +1155,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
                 const float4 ea4 = entries[end * 3u + 0u], eb4 = entries[end * 3u + 1u], ec4 = entries[end * 3u + 2u];
                 const TriCoverage cov = tri_coverage(ea4, eb4, ec4, flags);
                 cs0 = frag.a0[0], cs1 = frag.a0[1], cs2 = frag.a0[2], cs3 = frag.a0[3];
-                replace = r.occlude != 0u && cs3 == 1.0f && __float_as_uint(cs0) != 0x80000000u && __float_as_uint(cs1) != 0x80000000u && __float_as_uint(cs2) != 0x80000000u;
+                replace = __builtin_amdgcn_readfirstlane((r.occlude != 0u && cs3 == 1.0f && __float_as_uint(cs0) != 0x80000000u && __float_as_uint(cs1) != 0x80000000u && __float_as_uint(cs2) != 0x80000000u) ? 1u : 0u); // (the float compare is a vector instruction: back to a scalar here, on the rare path)
 #pragma unroll
                 for (int b = 0; b < ROWS; ++b) {
                     const unsigned long long inside = inside_row(cov, b);
@@ -1703,7 +1713,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRH_ROW_TILE
                             col[i][2] = blend[i] ? cs2 : col[i][2];
                             col[i][3] = blend[i] ? cs3 : col[i][3];
                         }
-                    } else {
+                    }
+                    // (a second if on a value the compiler cannot see through, not an else: as k_raster_fill's curve kinds — the else arm kept the
+                    // sixteen colours alive beside the first arm's results, sixteen copies a cover where the arms meet)
+                    uint32_t arithmetic = replace ? 0u : 1u;
+#if defined(__HIP_DEVICE_COMPILE__)
+                    asm volatile("" : "+v"(arithmetic));
+#endif
+                    if (arithmetic != 0u) {
                         const float one_minus_a = 1.0f - cs3;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
