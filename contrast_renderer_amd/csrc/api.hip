@@ -2901,6 +2901,38 @@ crh_status crh_image_create_from_frame(crh_frame* f, crh_image** out) {
     *out = image;
     return CRH_OK;
 }
+// crh_image_crop of that snapshot without the snapshot: the same refusals and the same settling, then k_image_crop on the frame's resolved bytes
+// (a cleared frame is a source that the region misses: zeros). The size limit is the region's; a frame's side is at most 65535.
+crh_status crh_image_create_from_frame_region(crh_frame* f, int32_t x, int32_t y, uint32_t width, uint32_t height, crh_image** out) {
+    if (!f || !out || !f->renderer) {
+        g_error = "crh_crop_texels: a null argument";
+        return CRH_ERR_INVALID_ARGUMENT;
+    }
+    if (width == 0u || height == 0u || width > kMaxImageSize || height > kMaxImageSize) {
+        g_error = "crh_crop_texels: width and height lie in [1, 16384]";
+        return CRH_ERR_INVALID_ARGUMENT;
+    }
+    if ((f->format != CRH_FORMAT_RGBA8 && f->format != CRH_FORMAT_RGBA8_ATTACHMENT) || f->slab_ty0 != 0u || f->slab_ty1 != 0xFFFFFFFFu) return CRH_ERR_UNSUPPORTED;
+    crh_renderer* r = f->renderer;
+    HIP_TRY(hipSetDevice(r->device));
+    const crh_status settled = settle_frame(f);
+    if (settled != CRH_OK) return settled;
+    crh_image* image = nullptr;
+    const crh_status st = new_image(r, width, height, &image);
+    if (st != CRH_OK) return st;
+    bool ok = f->cleared || hip_ok(order_after_external(f, r->stream), "order_after_external(image)");
+    if (ok) {
+        launch_image_crop(static_cast<const uint32_t*>(f->rgba8.p), f->width, f->cleared ? 0u : f->height, x, y, static_cast<uint32_t*>(image->pixels->p), width, height, r->stream);
+        ok = hip_ok(hipGetLastError(), "k_image_crop");
+    }
+    ok = hip_ok(r->sync(), "sync(image)") && ok; // a snapshot: the next pass into the frame may start as soon as this returns
+    if (!ok) {
+        delete image;
+        return CRH_ERR_HIP;
+    }
+    *out = image;
+    return CRH_OK;
+}
 crh_status crh_frame_download_f16(crh_frame* f, void* rgba16f) { return download_pixels(f, rgba16f, CRH_FORMAT_RGBA16F); }
 extern "C" crh_status crh_debug_frame_counters(crh_frame* f, uint32_t out[8]) { // tools only (not in the public header)
     HIP_TRY(hipSetDevice(f->renderer->device));

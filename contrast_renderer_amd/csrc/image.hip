@@ -1,11 +1,12 @@
-// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, and the ten
-// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field, resize) with their host rules (crh_*_texels) and validators.
+// csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, the ten
+// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field, resize), crop and statistics, with their host rules (crh_*_texels) and validators.
 // Host code only: the kernels are image_filter.hip's and raster.hip's (launch.hpp), the rules are the filters' headers. Of a renderer it
 // uses its device, its stream and "wait for every stream" (api_internal.hpp); what is about a frame or a paint table stays in api.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -20,6 +21,7 @@
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
+#include "regions.hpp"
 #include "resize.hpp"
 #include "turbulence.hpp"
 
@@ -786,4 +788,66 @@ crh_status crh_image_resize(const crh_image* src, uint32_t width, uint32_t heigh
         job.launch("k_image_resize_h", [&] { launch_image_resize_h(texels_of(src), src->width, src->height, tmp, width, table_x, tx.pairs, job.stream); });
         job.launch("k_image_resize_v", [&] { launch_image_resize_v(tmp, src->height, job.texels(), width, height, table_y, ty.pairs, job.stream); });
     });
+}
+// ---- regions and statistics
+namespace {
+static_assert(sizeof(crh_image_stats) == kStatsWords * sizeof(uint32_t) && offsetof(crh_image_stats, x0) == kStatsX0 * sizeof(uint32_t) && offsetof(crh_image_stats, count) == kStatsCount * sizeof(uint32_t),
+              "regions.hpp's words are the header's struct");
+constexpr const char* kCrop = "crh_crop_texels";
+constexpr const char* kStatistics = "crh_statistics_texels";
+// The checks after the null arguments, in the header's order: the channel, the threshold, then the size
+crh_status statistics_constants(uint32_t width, uint32_t height, uint32_t channel, uint32_t threshold, StatsConstants* f) {
+    if (channel > CRH_CHANNEL_A) return refuse(kStatistics, "channel is above CRH_CHANNEL_A");
+    if (threshold < 1u || threshold > 255u) return refuse(kStatistics, "threshold is outside [1, 255]");
+    f->shift = 8u * channel, f->threshold = threshold;
+    return check_size(kStatistics, width, height);
+}
+} // namespace
+crh_status crh_crop_texels(uint32_t width, uint32_t height, const void* rgba8, int32_t x, int32_t y, uint32_t out_width, uint32_t out_height, void* out_rgba8) {
+    if (!rgba8 || !out_rgba8) return refuse(kCrop, "a null argument");
+    crh_status st = check_size(kCrop, width, height);
+    if (st == CRH_OK) st = check_size(kCrop, out_width, out_height);
+    if (st != CRH_OK) return st;
+    if (out_rgba8 == rgba8) return refuse(kCrop, "out_rgba8 is rgba8");
+    crop_run(static_cast<const uint8_t*>(rgba8), width, height, x, y, out_width, out_height, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_crop(const crh_image* src, int32_t x, int32_t y, uint32_t width, uint32_t height, crh_image** out) {
+    if (!src || !src->renderer || !out) return refuse(kCrop, "a null argument");
+    const crh_status st = check_size(kCrop, width, height);
+    if (st != CRH_OK) return st;
+    return filter_call("crh_image_crop", src->renderer, width, height, out, [&](FilterJob& job) {
+        job.launch("k_image_crop", [&] { launch_image_crop(texels_of(src), src->width, src->height, x, y, job.texels(), width, height, job.stream); });
+    });
+}
+crh_status crh_statistics_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t channel, uint32_t threshold, crh_image_stats* out) {
+    if (!rgba8 || !out) return refuse(kStatistics, "a null argument");
+    StatsConstants f;
+    const crh_status st = statistics_constants(width, height, channel, threshold, &f);
+    if (st != CRH_OK) return st;
+    statistics_run(static_cast<const uint8_t*>(rgba8), width, height, f, out->histogram);
+    return CRH_OK;
+}
+crh_status crh_image_statistics(const crh_image* src, uint32_t channel, uint32_t threshold, crh_image_stats* out) {
+    if (!src || !src->renderer || !out) return refuse(kStatistics, "a null argument");
+    StatsConstants f;
+    const crh_status st = statistics_constants(src->width, src->height, channel, threshold, &f);
+    if (st != CRH_OK) return st;
+    // filter_call's frame without a result image: the device, the one scratch — [a partial result per workgroup | the result] —, the two
+    // kernels, the 4116 bytes to a host copy of the struct, the wait also behind a failed step, the scratch freed; *out is written last.
+    crh_renderer* r = src->renderer;
+    HIP_TRY(hipSetDevice(crh_internal_renderer_device(r)));
+    FilterJob job{"crh_image_statistics", renderer_stream(r)};
+    const uint32_t partials = image_stats_partials(src->width, src->height);
+    uint32_t* scratch = static_cast<uint32_t*>(job.scratch((size_t)(partials + 1u) * sizeof(crh_image_stats)));
+    uint32_t* result = scratch ? scratch + (size_t)partials * kStatsWords : nullptr; // (a failed allocation: no launch follows)
+    crh_image_stats stats;
+    job.launch("k_image_stats", [&] { launch_image_stats(texels_of(src), src->width, src->height, f, scratch, job.stream); });
+    job.launch("k_image_stats_merge", [&] { launch_image_stats_merge(scratch, partials, result, job.stream); });
+    if (job.ok) job.step(hipMemcpyAsync(&stats, result, sizeof stats, hipMemcpyDeviceToHost, job.stream), "hipMemcpyAsync(statistics)");
+    job.step(renderer_sync(r), "sync");
+    if (job.scratch_p) (void)hipFree(job.scratch_p);
+    if (!job.ok) return CRH_ERR_HIP;
+    *out = stats;
+    return CRH_OK;
 }

@@ -11,9 +11,12 @@
 // crh_image_displace: k_image_displace reads an image through per-texel offsets taken from a second one with the rule of displace.hpp, a gather from global memory.
 // crh_image_distance_field: k_image_distance_v and k_image_distance_h code the exact Euclidean distance to a shape with the rule of distance.hpp, separably through a byte of column distance per texel.
 // crh_image_resize: k_image_resize_h and k_image_resize_v resample an image to any size with the rule of resize.hpp, separably, with per-output integer taps.
+// crh_image_crop and crh_image_create_from_frame_region: k_image_crop copies a rectangle of an image or of a frame, zeros outside it, with the index rule of regions.hpp.
+// crh_image_statistics: k_image_stats and k_image_stats_merge reduce an image to its per-channel histograms and the bounds of its content with the rule of regions.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 
 #include "color_filter.hpp"
 #include "composite.hpp"
@@ -23,6 +26,7 @@
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
+#include "regions.hpp"
 #include "resize.hpp"
 #include "turbulence.hpp"
 
@@ -1075,6 +1079,247 @@ void launch_image_resize_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, 
 void launch_image_resize_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* table, uint32_t pairs, hipStream_t stream) {
     const dim3 grid((out_w + (uint32_t)kResizeColumns - 1u) / (uint32_t)kResizeColumns, (out_h + (uint32_t)kResizeBlockRows - 1u) / (uint32_t)kResizeBlockRows); // <= 256 x 512
     hipLaunchKernelGGL(k_image_resize_v, grid, dim3(kResizeColumns * kResizeWaves), 0, stream, static_cast<const uint2*>(tmp), tmp_h, out, out_w, out_h, table, pairs);
+}
+
+// crh_image_crop and crh_image_create_from_frame_region. A copy: 4 bytes read (inside the source) and 4 written per texel, k_image_composite's
+// geometry without the backdrop: a workgroup owns the row segment blockIdx.x of 256 V texels of the RESULT and strides over its rows; a lane
+// owns V consecutive texels, V = 4, 2 or 1 with w % V == 0, one aligned store. The source's group is one load of 4 V bytes only where
+// `source_wide` says that its rows and the shift keep it aligned (source_w % V == 0 and x % V == 0: then a group is wholly inside the source
+// or wholly outside); otherwise V loads of 4 bytes. Every source address is formed behind region_source's range check (regions.hpp: the
+// wrapped sum is below the source's size exactly when the true one is in range, for any int32 x and y), and every texel of the result is
+// written exactly once, the zeros outside the source included: nothing clears the result first.
+template <int V>
+__global__ __launch_bounds__(kCompositeLanes) void k_image_crop(const uint32_t* __restrict__ source, uint32_t source_w, uint32_t source_h, uint32_t x, uint32_t y, uint32_t source_wide,
+                                                                 uint32_t* __restrict__ out, uint32_t w, uint32_t h) {
+    typedef typename TexelGroup<V>::type Group;
+    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
+    if (i >= w) return; // (w % V == 0 and i % V == 0: the whole group is outside)
+    for (uint32_t j = blockIdx.y; j < h; j += gridDim.y) {
+        Group r = 0u;
+        uint32_t sj = 0u, si = 0u;
+        if (region_source(j, y, source_h, &sj)) {
+            const uint32_t* line = source + (size_t)sj * source_w;
+            if (source_wide) {
+                if (region_source(i, x, source_w, &si)) r = *reinterpret_cast<const Group*>(line + si); // (si % V == 0 and source_w % V == 0: si + V - 1 < source_w)
+            } else {
+#pragma unroll
+                for (int t = 0; t < V; ++t)
+                    if (region_source(i + (uint32_t)t, x, source_w, &si)) r[t] = line[si];
+            }
+        }
+        *reinterpret_cast<Group*>(out + (size_t)j * w + i) = r;
+    }
+}
+
+void launch_image_crop(const uint32_t* source, uint32_t source_w, uint32_t source_h, int32_t x, int32_t y, uint32_t* out, uint32_t w, uint32_t h, hipStream_t stream) {
+    const uint32_t v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
+    // (uint32_t)x % v is x mod v for a negative x as well: v divides 2^32
+    const uint32_t wide = v > 1u && source_w % v == 0u && (uint32_t)x % v == 0u ? 1u : 0u;
+    const uint32_t segments = (w + (uint32_t)kCompositeLanes * v - 1u) / ((uint32_t)kCompositeLanes * v); // <= 64
+    const dim3 grid(segments, std::min(h, std::max(1u, kCompositeBlocks / segments)));
+    if (v == 4u) hipLaunchKernelGGL(k_image_crop<4>, grid, dim3(kCompositeLanes), 0, stream, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, out, w, h);
+    else if (v == 2u) hipLaunchKernelGGL(k_image_crop<2>, grid, dim3(kCompositeLanes), 0, stream, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, out, w, h);
+    else hipLaunchKernelGGL(k_image_crop<1>, grid, dim3(kCompositeLanes), 0, stream, source, source_w, source_h, (uint32_t)x, (uint32_t)y, 0u, out, w, h);
+}
+
+namespace {
+// crh_image_statistics' grid cap, chosen for it: every workgroup leaves a partial result of kStatsWords words (4116 bytes), so kCompositeBlocks
+// of them would write half of what a 4096^2 image holds. 512 = 256 CUs x 2 workgroups of eight waves, 256 lanes along the row by two rows;
+// a lane takes its rows two at a time, so that it has two loads in flight where k_image_color_filter has two workgroups on the SIMD. The
+// partials of a 4096^2 image are 2 MB written and read once: 3 % of its bytes.
+constexpr uint32_t kStatsBlocks = 512;
+constexpr int kStatsRows = 2;                                  // rows of lanes in a workgroup (threadIdx.y)
+constexpr int kStatsWaves = kStatsRows * kCompositeLanes / 64; // a histogram each: 32 KB of LDS
+constexpr int kStatsMergeWords = 64, kStatsMergeSlices = 16; // k_image_stats_merge: words per workgroup, one per lane of a wave; partials in flight per word
+enum { kStatsPlain = 0, kStatsZeros = 1, kStatsRuns = 2 }; // what k_image_stats does about contention: DESIGN.md §7 "Regions and statistics" has the measurement
+} // namespace
+
+// crh_image_statistics, the pass over the texels. Streaming, 4 bytes read per texel: k_image_color_filter's geometry — a workgroup owns the row
+// segment blockIdx.x of 256 V texels; its lanes of threadIdx.y = s stride over the rows 2 blockIdx.y + s, + 2 gridDim.y, ..., two per turn; a
+// lane owns V consecutive texels, V = 4, 2 or 1 with w % V == 0: every address is (row j < h) * w + (column i < w). Histograms accumulate
+// in LDS, one of 4 x 256 words per wave (no wave contends with another; 32 KB per workgroup), by ds_add_u32 without return. A lane's columns are fixed, so the
+// bounds are kept per lane as a mask of its V columns that were hit, the first and last row with a hit, and the number of hits, joined
+// across the wave by shuffles at the end. What this does about the input the call is for — a layer that is almost all (0, 0, 0, 0), where
+// a plain histogram sends 64 lanes to one LDS address four times per texel:
+//   M >= kStatsZeros  a texel that is 0 costs one register increment per lane; the wave adds them to bin 0 of each channel once, at the end.
+//   M == kStatsRuns   a row's groups that are ONE texel value across the whole wave (one readfirstlane, V compares, one ballot) are counted
+//                     in a wave-uniform run (value, length) that goes to LDS only when the value changes: a constant layer, opaque or
+//                     transparent, issues four LDS adds per wave per run.
+// Workgroups never wait for one another: each writes its partial result (regions.hpp's words, the bounds still in their "empty" form) to
+// its own slab; k_image_stats_merge below sums the slabs.
+template <int V, int M>
+__global__ __launch_bounds__(kCompositeLanes * kStatsRows) void k_image_stats(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, StatsConstants f, uint32_t* __restrict__ partial) {
+    typedef typename TexelGroup<V>::type Group;
+    __shared__ uint32_t hist[kStatsWaves][kStatsHistogramWords];
+    __shared__ uint32_t edge[kStatsWaves][5];
+    const uint32_t lane = threadIdx.y * (uint32_t)kCompositeLanes + threadIdx.x; // of the workgroup
+    for (uint32_t k = lane; k < (uint32_t)kStatsWaves * kStatsHistogramWords; k += (uint32_t)(kCompositeLanes * kStatsRows)) (&hist[0][0])[k] = 0u;
+    __syncthreads();
+    const uint32_t wave = lane >> 6;
+    uint32_t* mine = hist[wave];
+    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
+    const bool live = i < w; // (w % V == 0 and i % V == 0: the whole group is inside or outside)
+    const uint64_t live_lanes = __ballot(live);
+    uint32_t columns = 0u, row0 = 0xFFFFFFFFu, row1 = 0u, hits = 0u, zeros = 0u;
+    uint32_t run_texel = 0u, run_length = 0u; // wave-uniform
+    if (live_lanes != 0ull) { // (a wave's lanes are consecutive columns: lane 0 of a wave with a live lane is live)
+        const uint32_t stride = (uint32_t)kStatsRows * gridDim.y;
+        for (uint32_t j0 = (uint32_t)kStatsRows * blockIdx.y + threadIdx.y; j0 < h; j0 += 2u * stride) {
+            const uint32_t j1 = j0 + stride;
+            Group g[2];
+            g[0] = 0u, g[1] = 0u;
+            if (live) {
+                g[0] = *reinterpret_cast<const Group*>(src + (size_t)j0 * w + i);
+                if (j1 < h) g[1] = *reinterpret_cast<const Group*>(src + (size_t)j1 * w + i);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const uint32_t j = u ? j1 : j0;
+                if (j >= h) break; // (the same for the whole wave)
+                const Group t = g[u];
+                uint32_t hit = 0u;
+#pragma unroll
+                for (int k = 0; k < V; ++k) hit |= stats_inside(t[k], f) ? 1u << k : 0u;
+                if (live && hit != 0u) columns |= hit, hits += (uint32_t)__popc(hit), row0 = stats_min(row0, j), row1 = stats_max(row1, j + 1u);
+                bool counted = false;
+                if (M == kStatsRuns) {
+                    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)t[0]);
+                    bool same = true;
+#pragma unroll
+                    for (int k = 0; k < V; ++k) same = same && t[k] == first;
+                    if (__ballot(live && same) == live_lanes) { // the row's part in this wave is one value
+                        const uint32_t n = (uint32_t)__popcll(live_lanes) * (uint32_t)V;
+                        if (first != run_texel && run_length != 0u) {
+                            if ((threadIdx.x & 63u) == 0u)
+                                for (uint32_t c = 0; c < 4u; ++c) atomicAdd(&mine[256u * c + stats_code(run_texel, c)], run_length);
+                            run_length = 0u;
+                        }
+                        run_texel = first, run_length += n;
+                        counted = true;
+                    }
+                }
+                if (!counted && live) {
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        if (M >= kStatsZeros && t[k] == 0u) {
+                            zeros += 1u;
+                        } else {
+#pragma unroll
+                            for (uint32_t c = 0; c < 4u; ++c) atomicAdd(&mine[256u * c + stats_code(t[k], c)], 1u);
+                        }
+                    }
+                }
+            }
+        }
+        if (run_length != 0u && (threadIdx.x & 63u) == 0u)
+            for (uint32_t c = 0; c < 4u; ++c) atomicAdd(&mine[256u * c + stats_code(run_texel, c)], run_length);
+        if (zeros != 0u)
+            for (uint32_t c = 0; c < 4u; ++c) atomicAdd(&mine[256u * c], zeros);
+    }
+    // the lane's bounds, joined across the wave, then across the workgroup's waves
+    StatsBounds b;
+    if (hits != 0u) b.x0 = i + (uint32_t)__builtin_ctz(columns), b.x1 = i + 32u - (uint32_t)__builtin_clz(columns), b.y0 = row0, b.y1 = row1, b.count = hits;
+#pragma unroll
+    for (int d = 32; d != 0; d >>= 1) {
+        StatsBounds o;
+        o.x0 = __shfl_xor(b.x0, d), o.y0 = __shfl_xor(b.y0, d), o.x1 = __shfl_xor(b.x1, d), o.y1 = __shfl_xor(b.y1, d), o.count = __shfl_xor(b.count, d);
+        stats_join(b, o);
+    }
+    if ((threadIdx.x & 63u) == 0u) edge[wave][0] = b.x0, edge[wave][1] = b.y0, edge[wave][2] = b.x1, edge[wave][3] = b.y1, edge[wave][4] = b.count;
+    __syncthreads();
+    uint32_t* slab = partial + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kStatsWords;
+    for (uint32_t at = lane; at < kStatsHistogramWords; at += (uint32_t)(kCompositeLanes * kStatsRows)) {
+        uint32_t sum = 0u;
+#pragma unroll
+        for (int v = 0; v < kStatsWaves; ++v) sum += hist[v][at];
+        slab[at] = sum;
+    }
+    if (lane == 0u) {
+        StatsBounds all;
+        for (int v = 0; v < kStatsWaves; ++v) {
+            StatsBounds o;
+            o.x0 = edge[v][0], o.y0 = edge[v][1], o.x1 = edge[v][2], o.y1 = edge[v][3], o.count = edge[v][4];
+            stats_join(all, o);
+        }
+        slab[kStatsX0] = all.x0, slab[kStatsY0] = all.y0, slab[kStatsX1] = all.x1, slab[kStatsY1] = all.y1, slab[kStatsCount] = all.count;
+    }
+}
+
+// crh_image_statistics, the sum of the n partial results: word `at` of the result is the sum (the histogram, the count), the minimum
+// (x0, y0) or the maximum (x1, y1) of word `at` of every slab; a minimum that is still "empty" is the header's 0. A workgroup owns 64
+// consecutive words, a lane of threadIdx.y = s the slabs s, s + 16, ...: 64 consecutive words of a slab are one 256-byte load of a wave.
+__global__ __launch_bounds__(kStatsMergeWords * kStatsMergeSlices) void k_image_stats_merge(const uint32_t* __restrict__ partial, uint32_t n, uint32_t* __restrict__ out) {
+    __shared__ uint32_t part[kStatsMergeSlices][kStatsMergeWords];
+    const uint32_t at = blockIdx.x * (uint32_t)kStatsMergeWords + threadIdx.x;
+    const bool lowest = at == kStatsX0 || at == kStatsY0, highest = at == kStatsX1 || at == kStatsY1;
+    uint32_t v = lowest ? 0xFFFFFFFFu : 0u;
+    if (at < kStatsWords) {
+        // eight slabs' words at a time: the loads are independent, and taken one by one each would wait out the last one's latency
+        for (uint32_t p = threadIdx.y; p < n; p += 8u * (uint32_t)kStatsMergeSlices) {
+            uint32_t o[8];
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; ++k) {
+                const uint32_t q = p + k * (uint32_t)kStatsMergeSlices;
+                const uint32_t word = partial[(size_t)stats_min(q, n - 1u) * kStatsWords + at]; // (every load is issued: a slab beyond the last reads the last and is not counted)
+                o[k] = q < n ? word : lowest ? 0xFFFFFFFFu : 0u;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; ++k) v = lowest ? stats_min(v, o[k]) : highest ? stats_max(v, o[k]) : v + o[k];
+        }
+    }
+    part[threadIdx.y][threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.y != 0u || at >= kStatsWords) return;
+    for (int s = 1; s < kStatsMergeSlices; ++s) {
+        const uint32_t o = part[s][threadIdx.x];
+        v = lowest ? stats_min(v, o) : highest ? stats_max(v, o) : v + o;
+    }
+    out[at] = lowest && v == 0xFFFFFFFFu ? 0u : v;
+}
+
+namespace {
+void stats_grid(uint32_t w, uint32_t h, uint32_t* v, dim3* grid) {
+    *v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
+    const uint32_t segments = (w + (uint32_t)kCompositeLanes * *v - 1u) / ((uint32_t)kCompositeLanes * *v); // <= 64
+    *grid = dim3(segments, std::min((h + (uint32_t)kStatsRows - 1u) / (uint32_t)kStatsRows, std::max(1u, kStatsBlocks / segments)));
+}
+} // namespace
+
+uint32_t image_stats_partials(uint32_t w, uint32_t h) {
+    uint32_t v;
+    dim3 grid;
+    stats_grid(w, h, &v, &grid);
+    return grid.x * grid.y;
+}
+
+void launch_image_stats(const uint32_t* src, uint32_t w, uint32_t h, const StatsConstants& f, uint32_t* partial, hipStream_t stream) {
+    uint32_t v;
+    dim3 grid;
+    stats_grid(w, h, &v, &grid);
+    // CRH_STATS_VARIANT = 0 (a plain LDS histogram) or 1 (+ the zero texels in a register) builds the measurement's other arms; anything else is the default
+    static const int variant = [] {
+        const char* e = std::getenv("CRH_STATS_VARIANT");
+        return e && (e[0] == '0' || e[0] == '1') && e[1] == 0 ? e[0] - '0' : (int)kStatsRuns;
+    }();
+#define CRH_STATS_LAUNCH(V, M) hipLaunchKernelGGL((k_image_stats<V, M>), grid, dim3(kCompositeLanes, kStatsRows), 0, stream, src, w, h, f, partial)
+#define CRH_STATS_WIDTHS(M)                \
+    if (v == 4u) CRH_STATS_LAUNCH(4, M);   \
+    else if (v == 2u) CRH_STATS_LAUNCH(2, M); \
+    else CRH_STATS_LAUNCH(1, M)
+    if (variant == kStatsPlain) {
+        CRH_STATS_WIDTHS(kStatsPlain);
+    } else if (variant == kStatsZeros) {
+        CRH_STATS_WIDTHS(kStatsZeros);
+    } else {
+        CRH_STATS_WIDTHS(kStatsRuns);
+    }
+#undef CRH_STATS_WIDTHS
+#undef CRH_STATS_LAUNCH
+}
+
+void launch_image_stats_merge(const uint32_t* partial, uint32_t n, uint32_t* out, hipStream_t stream) {
+    const uint32_t blocks = (kStatsWords + (uint32_t)kStatsMergeWords - 1u) / (uint32_t)kStatsMergeWords;
+    hipLaunchKernelGGL(k_image_stats_merge, dim3(blocks), dim3(kStatsMergeWords, kStatsMergeSlices), 0, stream, partial, n, out);
 }
 
 } // namespace crh

@@ -77,6 +77,15 @@ void launch_image_distance_h(const uint8_t* g, uint32_t out_w, uint32_t out_h, c
 // h: src_h rows of src_w texels -> `tmp`, src_h rows of out_w texels of four 16-bit values; v: tmp_h rows of `tmp` -> out_h rows of out_w texels.
 void launch_image_resize_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, void* tmp, uint32_t out_w, const uint32_t* table, uint32_t pairs, hipStream_t stream);
 void launch_image_resize_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_t out_w, uint32_t out_h, const uint32_t* table, uint32_t pairs, hipStream_t stream);
+// image_filter.hip: the kernel of crh_image_crop and crh_image_create_from_frame_region (regions.hpp holds the index rule). out: h rows of w texels, 1 <= w, h <= 16384, each written
+// once; its texel (i, j) is the source's (x + i, y + j), (0, 0, 0, 0) outside source_w x source_h (each <= 65535, a frame's limit); x, y: any int32. out is not the source.
+void launch_image_crop(const uint32_t* source, uint32_t source_w, uint32_t source_h, int32_t x, int32_t y, uint32_t* out, uint32_t w, uint32_t h, hipStream_t stream);
+// image_filter.hip: crh_image_statistics' kernels (regions.hpp holds the rule and the kStatsWords words of a result). launch_image_stats leaves one partial result per workgroup in
+// `partial`, image_stats_partials(w, h) slabs of kStatsWords words; launch_image_stats_merge joins n of them into the kStatsWords words at `out`. Nothing needs clearing first.
+struct StatsConstants;
+uint32_t image_stats_partials(uint32_t w, uint32_t h); // <= 1024
+void launch_image_stats(const uint32_t* src, uint32_t w, uint32_t h, const StatsConstants& f, uint32_t* partial, hipStream_t stream);
+void launch_image_stats_merge(const uint32_t* partial, uint32_t n, uint32_t* out, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream); // zeroes n_words 32-bit words with single-wave workgroups (the clear in front of both passes' binning kernels)

@@ -868,11 +868,58 @@ def resize_texels(pixels, width, height, filter=ResizeFilter.Lanczos3):
     return out
 
 
+@dataclass(frozen=True, eq=False)
+class ImageStatistics:
+    """crh_image_stats: `histogram` is a (4, 256) uint32 array, [r, g, b, a][code] = how many texels store that code in that channel,
+    over all texels; `bounds` = (x0, y0, x1, y1), half-open, the smallest rectangle that holds every texel inside (stored code of the
+    chosen channel >= the threshold), (0, 0, 0, 0) if none is; `count` = the texels inside."""
+    histogram: np.ndarray
+    bounds: tuple
+    count: int
+
+
+def _statistics_of(stats):
+    """ImageStatsC -> ImageStatistics"""
+    return ImageStatistics(np.ctypeslib.as_array(stats.histogram).astype(np.uint32).reshape(4, 256), (int(stats.x0), int(stats.y0), int(stats.x1), int(stats.y1)), int(stats.count))
+
+
+def _int32(v):
+    """an offset as the C ABI takes it; what does not fit an int32 is refused here, where ctypes would wrap it"""
+    v = int(v)
+    if not -2 ** 31 <= v < 2 ** 31:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"an offset is an int32, not {v}")
+    return v
+
+
+def crop_texels(pixels, x, y, width, height):
+    """crh_crop_texels (host only): the rule of Image.crop on a (height', width', 4) uint8 array -> the (height, width, 4) uint8 result,
+    texel (i, j) = the source's (x + i, y + j), zeros outside the source."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"crop_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    width, height = int(width), int(height)
+    legal = 1 <= width <= 16384 and 1 <= height <= 16384  # (a size the library refuses gets a texel's room and the library's status)
+    out = np.empty((height, width, 4) if legal else (1, 1, 4), dtype=np.uint8)
+    check(_ffi.load_library().crh_crop_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, _int32(x), _int32(y), width & 0xFFFFFFFF, height & 0xFFFFFFFF, out.ctypes.data))
+    return out
+
+
+def statistics_texels(pixels, channel=Channel.A, threshold=1):
+    """crh_statistics_texels (host only): the rule of Image.statistics on a (height, width, 4) uint8 array -> ImageStatistics."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"statistics_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    stats = _ffi.ImageStatsC()
+    check(_ffi.load_library().crh_statistics_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, int(channel) & 0xFFFFFFFF, int(threshold) & 0xFFFFFFFF, C.byref(stats)))
+    return _statistics_of(stats)
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
     its texels aliases unless it has mipmaps and its paint's filter is Filter.NearestMipmap or Filter.LinearMipmap. `origin` = the texel of this
-    image that lies over texel (0, 0) of the image it was made from: (0, 0) unless blur(), morphology() or distance_field() grew it."""
+    image that lies over texel (0, 0) of the image it was made from: (0, 0) unless blur(), morphology() or distance_field() grew it, or
+    crop(), trim() or from_frame(region=...) cut it: a crop at (x, y) moves the origin by (-x, -y), so it can be negative."""
 
     origin = (0, 0)
 
@@ -900,12 +947,20 @@ class Image:
         return image
 
     @staticmethod
-    def from_frame(frame: Frame):
+    def from_frame(frame: Frame, region=None):
         """crh_image_create_from_frame: a snapshot of what the frame shows (an RGBA8 or RGBA8-attachment frame, not restricted by
-        set_tile_rows), copied on the device; later passes into the frame do not change it."""
+        set_tile_rows), copied on the device; later passes into the frame do not change it. region = (x, y, width, height) is
+        crh_image_create_from_frame_region: byte for byte from_frame(frame).crop(x, y, width, height), origin (-x, -y), without the
+        full-size copy; the rectangle may leave the frame (zeros there) and only its own size is limited to 16384."""
         handle = C.c_void_p()
-        check(frame.lib.crh_image_create_from_frame(frame.handle, C.byref(handle)))
-        return Image._adopt(frame.renderer, handle)
+        if region is None:
+            check(frame.lib.crh_image_create_from_frame(frame.handle, C.byref(handle)))
+            return Image._adopt(frame.renderer, handle)
+        x, y, width, height = (int(v) for v in region)
+        check(frame.lib.crh_image_create_from_frame_region(frame.handle, _int32(x), _int32(y), width & 0xFFFFFFFF, height & 0xFFFFFFFF, C.byref(handle)))
+        image = Image._adopt(frame.renderer, handle, (width, height))
+        image.origin = (-x, -y)
+        return image
 
     @classmethod
     def turbulence(cls, renderer: Renderer, width, height, base_frequency, octaves=1, seed=0, kind=TurbulenceKind.Turbulence, stitch=False, opaque=False, offset=(0, 0)):
@@ -1073,6 +1128,43 @@ class Image:
         handle = C.c_void_p()
         check(self.lib.crh_image_resize(self.handle, int(width) & 0xFFFFFFFF, int(height) & 0xFFFFFFFF, int(filter) & 0xFFFFFFFF, C.byref(handle)))
         return Image._adopt(self.renderer, handle, (int(width), int(height)))
+
+    def crop(self, x, y, width, height):
+        """crh_image_crop -> a new Image of one level, width x height (each in [1, 16384]): texel (i, j) is this image's texel
+        (x + i, y + j), the bytes as stored, and (0, 0, 0, 0) outside this image; built on the device and complete when this returns (a
+        synchronous call). x and y are any int32: a rectangle that misses this image gives a transparent canvas, a larger one the
+        transparent backdrop around it. The result's `origin` is (origin[0] - x, origin[1] - y), which can be negative. This image is
+        not modified."""
+        x, y, width, height = _int32(x), _int32(y), int(width), int(height)
+        handle = C.c_void_p()
+        check(self.lib.crh_image_crop(self.handle, x, y, width & 0xFFFFFFFF, height & 0xFFFFFFFF, C.byref(handle)))
+        image = Image._adopt(self.renderer, handle, (width, height))
+        image.origin = (self.origin[0] - x, self.origin[1] - y)
+        return image
+
+    def statistics(self, channel=Channel.A, threshold=1):
+        """crh_image_statistics -> ImageStatistics: the per-channel histograms of the stored codes over all texels, and the bounds and
+        the number of the texels inside — stored code of `channel` >= `threshold` (1..255), distance_field()'s definition. Reduced on
+        the device; 4116 bytes come back (a synchronous call). Tables for color_filter (auto-levels, a percentile stretch), "is this
+        layer empty" and the covered area all come from it. This image is not modified."""
+        stats = _ffi.ImageStatsC()
+        check(self.lib.crh_image_statistics(self.handle, int(channel) & 0xFFFFFFFF, int(threshold) & 0xFFFFFFFF, C.byref(stats)))
+        return _statistics_of(stats)
+
+    def bounds(self, channel=Channel.A, threshold=1):
+        """statistics(channel, threshold).bounds: (x0, y0, x1, y1), half-open, (0, 0, 0, 0) if no texel is inside."""
+        return self.statistics(channel, threshold).bounds
+
+    def trim(self, channel=Channel.A, threshold=1, margin=0):
+        """statistics(), then crop() to the bounds grown by `margin` texels on every side and clipped to this image: the layer without
+        its empty surroundings, with the `origin` that puts it back (by composite()'s rule: offset = (dx - origin[0], dy - origin[1])
+        of the result). An image with nothing inside trims to the 1 x 1 crop at (0, 0)."""
+        x0, y0, x1, y1 = self.bounds(channel, threshold)
+        if x1 == x0:
+            return self.crop(0, 0, 1, 1)
+        margin = int(margin)
+        x0, y0, x1, y1 = max(0, x0 - margin), max(0, y0 - margin), min(self.width, x1 + margin), min(self.height, y1 + margin)
+        return self.crop(x0, y0, x1 - x0, y1 - y0)
 
     def destroy(self):
         """crh_image_destroy. Legal while a Scene's paint table names the image: the table keeps the pixels until it is replaced."""

@@ -725,8 +725,8 @@ crh_status crh_image_morphology(const crh_image* src, uint32_t op, uint32_t radi
  * scalar registers. Only level 0 of the source is read and the source is not modified. A failed allocation or launch frees everything
  * and returns CRH_ERR_HIP.
  * Limits: the call is synchronous, like its siblings — one wait per call; kernels are at most 15 x 15; the result has the source's size
- * under every edge — unlike blur and dilate nothing grows, and a caller who wants a wide kernel's spill composites the source onto a
- * larger transparent backdrop first; there is no kernelUnitLength; codes are taken as they are, with no gamma handling. */
+ * under every edge — unlike blur and dilate nothing grows, and a caller who wants a wide kernel's spill takes a larger
+ * crh_image_crop of the source first; there is no kernelUnitLength; codes are taken as they are, with no gamma handling. */
 #define CRH_MAX_CONVOLVE_ORDER 15u
 #define CRH_CONVOLVE_MAX_GAIN 64.0f
 typedef struct crh_convolve {
@@ -911,8 +911,8 @@ crh_status crh_image_turbulence(crh_renderer* renderer, uint32_t width, uint32_t
  * crh_last_error text "crh_displace_validate: ...".
  * crh_image_displace runs k_image_displace on the renderer's stream, specialised on the filter and on TRANSPARENT against the wrapping
  * edges; it allocates nothing but the result. A failed allocation or launch frees everything and returns CRH_ERR_HIP.
- * Limits: the call is synchronous, like its siblings; map and source must have one size — composite onto a backdrop first if they do
- * not; the footprint is a point or a 2 x 2 bilinear one, so strong local compression of the map aliases; the map is used in its own
+ * Limits: the call is synchronous, like its siblings; map and source must have one size — crh_image_crop brings one to the other's if
+ * they do not; the footprint is a point or a 2 x 2 bilinear one, so strong local compression of the map aliases; the map is used in its own
  * codes, with no colour-space handling; this is not a per-draw effect of the raster path. */
 typedef enum crh_channel { CRH_CHANNEL_R = 0, CRH_CHANNEL_G = 1, CRH_CHANNEL_B = 2, CRH_CHANNEL_A = 3 } crh_channel;
 #define CRH_MAX_DISPLACE_SCALE 1024.0f
@@ -1037,6 +1037,53 @@ typedef enum crh_resize_filter { CRH_RESIZE_BOX = 0, CRH_RESIZE_TRIANGLE = 1, CR
 crh_status crh_resize_taps(uint32_t n, uint32_t m, uint32_t filter, int32_t* first, uint16_t* count, int16_t* taps, uint64_t capacity, uint64_t* total); /* host only */
 crh_status crh_resize_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t out_width, uint32_t out_height, uint32_t filter, void* out_rgba8); /* host only */
 crh_status crh_image_resize(const crh_image* src, uint32_t width, uint32_t height, uint32_t filter, crh_image** out);
+/* Regions and statistics: part of an image or of a frame as a new image, and where an image's content is — so that the drop shadow of a
+ * 300 x 200 button in a 4096 x 4096 frame filters 300 x 200 texels, not 64 MB four times, and nothing goes through the host to find the
+ * button. A crop is a copy and the statistics are counts: every byte and every counter is defined, and the tests check each.
+ *   crop        the result is width x height, each in [1, 16384], one level; its texel (i, j) is the source's texel (x + i, y + j), the
+ *               bytes exactly as stored (a copy: nothing is clamped to alpha), and (0, 0, 0, 0) where that lies outside the source. x and
+ *               y are any int32. A rectangle that misses the source entirely is legal and gives a transparent image: this is how an
+ *               empty canvas is made, and a rectangle larger than the source is the larger transparent backdrop that a filter's spill
+ *               or a map of another size needs. The mirrors give the result the origin (origin.x - x, origin.y - y), which may be negative.
+ *   frame region  crh_image_create_from_frame_region is, byte for byte, crh_image_crop of what crh_image_create_from_frame would return,
+ *               without the full-size copy: one kernel reads the frame's resolved bytes. It settles the frame as that call does and
+ *               refuses what it refuses (a format other than CRH_FORMAT_RGBA8 and CRH_FORMAT_RGBA8_ATTACHMENT, a frame restricted by
+ *               crh_frame_set_tile_rows: CRH_ERR_UNSUPPORTED); a cleared frame gives zeros. The size limit is the region's, not the
+ *               frame's: a frame of more than 16384 texels on a side is snapshotted in regions.
+ *   inside      a texel is inside iff its stored (premultiplied) code of `channel`, a crh_channel, is >= `threshold`, 1..255:
+ *               crh_distance's definition.
+ *   statistics  histogram[256 * c + v], c = 0..3 for r, g, b, a, is the number of texels whose stored code of channel c is v, over all
+ *               texels, whatever the channel and the threshold: [r, g, b, a][code] as one array of 1024, and each channel's 256 counts sum
+ *               to width * height (16384^2 < 2^32: 32 bits hold every count). [x0, x1) x [y0, y1) is the smallest rectangle that holds
+ *               every texel inside, 0, 0, 0, 0 if none is; count is the number of texels inside, which is also the sum of the channel's
+ *               histogram from `threshold` up.
+ * Hence: the statistics of a crop to the bounds have the bounds (0, 0, x1 - x0, y1 - y0) and the same count; a crop at (a, b) of a crop
+ * at (x, y) whose rectangle lies inside the first result is the crop at (x + a, y + b); the statistics of a crop that misses the source
+ * are width * height in bin 0 of each channel and no bounds.
+ * crh_crop_texels and crh_statistics_texels (the rules on whole images in host memory, width * height * 4 bytes in the order r g b a at
+ * any alignment, row 0 first; the crop writes out_width * out_height * 4) are host only: no renderer, no device.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out and the out buffers untouched:
+ * first a null argument; then a channel above CRH_CHANNEL_A; then a threshold outside [1, 255]; then a size (the source's, the result's,
+ * the region's) outside [1, 16384]; then, in crh_crop_texels, an out_rgba8 equal to rgba8 are CRH_ERR_INVALID_ARGUMENT, each with a
+ * crh_last_error text "crh_crop_texels: ..." (the three crops) or "crh_statistics_texels: ..." (the two statistics); then what
+ * crh_image_create_from_frame refuses of a frame is CRH_ERR_UNSUPPORTED.
+ * crh_image_crop and crh_image_create_from_frame_region run k_image_crop on the renderer's stream, which writes every texel of the result
+ * once, zeros included, and allocate nothing but the result. crh_image_statistics runs k_image_stats, which leaves a partial result
+ * per workgroup in the call's one scratch allocation (no workgroup waits for another), and k_image_stats_merge, which sums them; the 4116
+ * bytes are then copied to the host. All three are synchronous, like their siblings; only level 0 of the source is read and the source
+ * is not modified. A failed allocation or launch frees everything, writes nothing to *out and returns CRH_ERR_HIP.
+ * Limits: the calls are synchronous and none works in place; the statistics of a frame need a snapshot first; the bounds are one
+ * rectangle, not one per connected component; the histogram is of the stored codes, premultiplied as they are. */
+typedef struct crh_image_stats {
+    uint32_t histogram[1024];   /* [r, g, b, a][code] as uint32_t[4][256]: entry 256 * c + v = how many texels store code v in channel c */
+    uint32_t x0, y0, x1, y1;    /* half-open: the smallest rectangle that holds every texel inside; 0, 0, 0, 0 if none is */
+    uint32_t count;             /* texels inside */
+} crh_image_stats;
+crh_status crh_crop_texels(uint32_t width, uint32_t height, const void* rgba8, int32_t x, int32_t y, uint32_t out_width, uint32_t out_height, void* out_rgba8); /* host only */
+crh_status crh_statistics_texels(uint32_t width, uint32_t height, const void* rgba8, uint32_t channel, uint32_t threshold, crh_image_stats* out);                /* host only */
+crh_status crh_image_crop(const crh_image* src, int32_t x, int32_t y, uint32_t width, uint32_t height, crh_image** out);
+crh_status crh_image_create_from_frame_region(crh_frame* frame, int32_t x, int32_t y, uint32_t width, uint32_t height, crh_image** out);
+crh_status crh_image_statistics(const crh_image* src, uint32_t channel, uint32_t threshold, crh_image_stats* out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

@@ -921,6 +921,24 @@ inline std::vector<uint8_t> resize_texels(uint32_t width, uint32_t height, const
     check(crh_resize_texels(width, height, texels.data(), out_width, out_height, (uint32_t)filter, out.data()));
     return out;
 }
+// crh_image_stats as it is: histogram[256 * c + v] = how many texels store code v in channel c (r, g, b, a), [x0, x1) x [y0, y1) around the
+// texels inside (all 0 if none is), count = their number
+typedef crh_image_stats ImageStatistics;
+// crh_crop_texels (host only): the rule of Image::crop on a width x height image of RGBA8 in host memory -> the out_width x out_height result's bytes
+inline std::vector<uint8_t> crop_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, int32_t x, int32_t y, uint32_t out_width, uint32_t out_height) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const bool legal = out_width >= 1u && out_width <= 16384u && out_height >= 1u && out_height <= 16384u; // (what the library refuses gets a texel's room and the library's status)
+    std::vector<uint8_t> out(legal ? (size_t)out_width * out_height * 4u : 4u);
+    check(crh_crop_texels(width, height, texels.data(), x, y, out_width, out_height, out.data()));
+    return out;
+}
+// crh_statistics_texels (host only): the rule of Image::statistics on a width x height image of RGBA8 in host memory
+inline ImageStatistics statistics_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, Channel channel = Channel::A, uint32_t threshold = 1u) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    ImageStatistics out;
+    check(crh_statistics_texels(width, height, texels.data(), (uint32_t)channel, threshold, &out));
+    return out;
+}
 // crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame::download hands out. One level until
 // generate_mipmaps(); a minified image wants its mipmaps and Filter::NearestMipmap / LinearMipmap (include/contrast_hip.h crh_image_generate_mipmaps).
 // Destroying it while a Scene's paint table names it is legal: the table keeps the pixels.
@@ -979,7 +997,8 @@ class Image {
         if (edge == BlurEdge::Transparent) image.origin_ = {(image.width_ - width_) / 2u, (image.height_ - height_) / 2u};
         return image;
     }
-    // the texel of this image over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless blur() or morphology() grew it
+    // the texel of this image over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless blur() or morphology() grew it,
+    // or crop(), trim() or a frame region cut it: then it may be negative, a signed value in these 32 bits (cast each to int32_t)
     std::array<uint32_t, 2> origin() const { return origin_; }
     // crh_image_composite, called on the backdrop -> a new Image of one level, of this image's size, origin (0, 0): `source` combined with this
     // image texel by texel by a Porter-Duff operator, a blend mode and a group opacity in [0, 1]; integer and bit-exact, complete on return.
@@ -1067,6 +1086,44 @@ class Image {
         check(crh_image_resize(handle_, width, height, (uint32_t)filter, &image.handle_));
         check(crh_image_size(image.handle_, &image.width_, &image.height_));
         return image;
+    }
+    // crh_image_create_from_frame_region: byte for byte from_frame(frame).crop(x, y, width, height), without the full-size copy; the
+    // rectangle may leave the frame (zeros there) and only its own size is limited to 16384. Its origin() is (-x, -y).
+    static Image from_frame(Frame& frame, int32_t x, int32_t y, uint32_t width, uint32_t height) {
+        Image image;
+        check(crh_image_create_from_frame_region(frame.raw(), x, y, width, height, &image.handle_));
+        image.width_ = width, image.height_ = height, image.origin_ = {0u - (uint32_t)x, 0u - (uint32_t)y};
+        return image;
+    }
+    // crh_image_crop -> a new Image of one level, width x height (each in [1, 16384]): texel (i, j) is this image's (x + i, y + j), the bytes
+    // as stored, (0, 0, 0, 0) outside this image; complete on return (a synchronous call). x and y are any int32: a rectangle that misses
+    // this image is a transparent canvas, a larger one the transparent backdrop around it. Its origin() is this image's minus (x, y): a
+    // signed value in origin()'s 32 bits, read through (int32_t) as composite()'s rule does. This image is not modified.
+    Image crop(int32_t x, int32_t y, uint32_t width, uint32_t height) const {
+        Image image;
+        check(crh_image_crop(handle_, x, y, width, height, &image.handle_));
+        image.width_ = width, image.height_ = height, image.origin_ = {origin_[0] - (uint32_t)x, origin_[1] - (uint32_t)y};
+        return image;
+    }
+    // crh_image_statistics -> the per-channel histograms of the stored codes over all texels, and the bounds and the number of the texels
+    // inside: stored code of `channel` >= `threshold` (1..255), distance_field()'s definition. Reduced on the device (a synchronous call).
+    ImageStatistics statistics(Channel channel = Channel::A, uint32_t threshold = 1u) const {
+        ImageStatistics out;
+        check(crh_image_statistics(handle_, (uint32_t)channel, threshold, &out));
+        return out;
+    }
+    // statistics(channel, threshold)'s x0, y0, x1, y1: half-open, all 0 if no texel is inside
+    std::array<uint32_t, 4> bounds(Channel channel = Channel::A, uint32_t threshold = 1u) const {
+        const ImageStatistics s = statistics(channel, threshold);
+        return {s.x0, s.y0, s.x1, s.y1};
+    }
+    // statistics(), then crop() to the bounds grown by `margin` on every side and clipped to this image; nothing inside: the 1 x 1 crop at (0, 0)
+    Image trim(Channel channel = Channel::A, uint32_t threshold = 1u, uint32_t margin = 0u) const {
+        const std::array<uint32_t, 4> b = bounds(channel, threshold);
+        if (b[2] == b[0]) return crop(0, 0, 1u, 1u);
+        const uint32_t x0 = b[0] > margin ? b[0] - margin : 0u, y0 = b[1] > margin ? b[1] - margin : 0u;
+        const uint32_t x1 = b[2] + margin < width_ ? b[2] + margin : width_, y1 = b[3] + margin < height_ ? b[3] + margin : height_;
+        return crop((int32_t)x0, (int32_t)y0, x1 - x0, y1 - y0);
     }
     template <class Light>
     Image diffuse_lighting(const Light& light, float surface_scale = 1.0f, float constant = 1.0f, std::array<float, 3> color = {1.0f, 1.0f, 1.0f}, BlurEdge edge = BlurEdge::Pad) const {

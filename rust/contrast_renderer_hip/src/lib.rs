@@ -1203,6 +1203,24 @@ pub fn resize_texels(width: u32, height: u32, texels: &[u8], out_width: u32, out
     status(unsafe { ffi::crh_resize_texels(width, height, texels.as_ptr() as *const _, out_width, out_height, filter as u32, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// `crh_image_stats` as it is: `histogram[256 * c + v]` = how many texels store code v in channel c (r, g, b, a), [x0, x1) x [y0, y1) around
+/// the texels inside (all 0 if none is), `count` = their number
+pub type ImageStatistics = ffi::crh_image_stats;
+/// `crh_crop_texels` (host only): the rule of `Image::crop` on a width x height image of RGBA8 in host memory -> the out_width x out_height result's bytes
+pub fn crop_texels(width: u32, height: u32, texels: &[u8], x: i32, y: i32, out_width: u32, out_height: u32) -> Result<Vec<u8>, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    let legal = (1..=16384).contains(&out_width) && (1..=16384).contains(&out_height); // (what the library refuses gets a texel's room and the library's status)
+    let mut out = vec![0u8; if legal { out_width as usize * out_height as usize * 4 } else { 4 }];
+    status(unsafe { ffi::crh_crop_texels(width, height, texels.as_ptr() as *const _, x, y, out_width, out_height, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
+/// `crh_statistics_texels` (host only): the rule of `Image::statistics` on a width x height image of RGBA8 in host memory
+pub fn statistics_texels(width: u32, height: u32, texels: &[u8], channel: Channel, threshold: u32) -> Result<ImageStatistics, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    let mut out = ImageStatistics { histogram: [0u32; 1024], x0: 0, y0: 0, x1: 0, y1: 0, count: 0 };
+    status(unsafe { ffi::crh_statistics_texels(width, height, texels.as_ptr() as *const _, channel as u32, threshold, &mut out) })?;
+    Ok(out)
+}
 /// `crh_image`: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes `Frame::download` hands out. One level
 /// until `generate_mipmaps`. Dropping it while a Scene's paint table names it is legal: the table keeps the pixels and their mipmaps.
 pub struct Image {
@@ -1268,9 +1286,48 @@ impl Image {
         let origin = if edge == BlurEdge::Transparent { ((width - self.width) / 2, (height - self.height) / 2) } else { (0, 0) };
         Ok(Image { raw, width, height, origin })
     }
-    /// The texel of this image over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless `blur` or `morphology` grew it
+    /// The texel of this image over texel (0, 0) of the image it was blurred or dilated from: (0, 0) unless `blur` or `morphology` grew it,
+    /// or `crop`, `trim` or `from_frame_region` cut it: a crop at (x, y) moves the origin by (-x, -y), so it can be negative — a signed value
+    /// in these 32 bits (`as i32`), as `composite`'s offset rule reads it
     pub fn origin(&self) -> (u32, u32) {
         self.origin
+    }
+    /// `crh_image_create_from_frame_region`: byte for byte `from_frame(frame)?.crop(x, y, width, height)`, origin (-x, -y), without the
+    /// full-size copy; the rectangle may leave the frame (zeros there) and only its own size is limited to 16384.
+    pub fn from_frame_region(frame: &Frame, x: i32, y: i32, width: u32, height: u32) -> Result<Image, Error> {
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_create_from_frame_region(frame.raw, x, y, width, height, &mut raw) })?;
+        Ok(Image { raw, width, height, origin: ((x as u32).wrapping_neg(), (y as u32).wrapping_neg()) })
+    }
+    /// `crh_image_crop` -> a new `Image` of one level, width x height (each in [1, 16384]): texel (i, j) is this image's (x + i, y + j), the
+    /// bytes as stored, (0, 0, 0, 0) outside this image; complete on return (a synchronous call). x and y are any i32: a rectangle that
+    /// misses this image is a transparent canvas, a larger one the transparent backdrop around it. Its origin is this image's minus (x, y).
+    pub fn crop(&self, x: i32, y: i32, width: u32, height: u32) -> Result<Image, Error> {
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_crop(self.raw, x, y, width, height, &mut raw) })?;
+        Ok(Image { raw, width, height, origin: (self.origin.0.wrapping_sub(x as u32), self.origin.1.wrapping_sub(y as u32)) })
+    }
+    /// `crh_image_statistics` -> the per-channel histograms of the stored codes over all texels, and the bounds and the number of the texels
+    /// inside: stored code of `channel` >= `threshold` (1..=255), `distance_field`'s definition. Reduced on the device (a synchronous call).
+    pub fn statistics(&self, channel: Channel, threshold: u32) -> Result<ImageStatistics, Error> {
+        let mut out = ImageStatistics { histogram: [0u32; 1024], x0: 0, y0: 0, x1: 0, y1: 0, count: 0 };
+        status(unsafe { ffi::crh_image_statistics(self.raw, channel as u32, threshold, &mut out) })?;
+        Ok(out)
+    }
+    /// `statistics(channel, threshold)`'s (x0, y0, x1, y1): half-open, all 0 if no texel is inside
+    pub fn bounds(&self, channel: Channel, threshold: u32) -> Result<(u32, u32, u32, u32), Error> {
+        let s = self.statistics(channel, threshold)?;
+        Ok((s.x0, s.y0, s.x1, s.y1))
+    }
+    /// `statistics`, then `crop` to the bounds grown by `margin` on every side and clipped to this image; nothing inside: the 1 x 1 crop at (0, 0)
+    pub fn trim(&self, channel: Channel, threshold: u32, margin: u32) -> Result<Image, Error> {
+        let (x0, y0, x1, y1) = self.bounds(channel, threshold)?;
+        if x1 == x0 {
+            return self.crop(0, 0, 1, 1);
+        }
+        let (x0, y0) = (x0.saturating_sub(margin), y0.saturating_sub(margin));
+        let (x1, y1) = ((x1 + margin).min(self.width), (y1 + margin).min(self.height));
+        self.crop(x0 as i32, y0 as i32, x1 - x0, y1 - y0)
     }
     /// `crh_image_composite`, called on the backdrop -> a new `Image` of one level, of this image's size, origin (0, 0): `source` combined
     /// with this image texel by texel by a Porter-Duff operator, a blend mode and a group opacity in [0, 1]; integer and bit-exact, complete
