@@ -257,6 +257,10 @@ class ImageStatsC(C.Structure):  # crh_image_stats: 4116 bytes
     _fields_ = [("histogram", C.c_uint32 * 1024), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32), ("count", C.c_uint32)]
 
 
+class VariableBlurC(C.Structure):  # crh_variable_blur
+    _fields_ = [("sigma_x", C.c_float * 2), ("sigma_y", C.c_float * 2), ("channel", C.c_uint32), ("edge", C.c_uint32)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -372,6 +376,10 @@ def load_library():
         "crh_image_crop": (C.c_int, [V, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(V)]),
         "crh_image_create_from_frame_region": (C.c_int, [V, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(V)]),
         "crh_image_statistics": (C.c_int, [V, C.c_uint32, C.c_uint32, C.POINTER(ImageStatsC)]),
+        "crh_variable_blur_validate": (C.c_int, [C.POINTER(VariableBlurC)]),
+        "crh_variable_blur_sigma": (C.c_int, [C.POINTER(VariableBlurC), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "crh_variable_blur_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, V, C.POINTER(VariableBlurC), V]),
+        "crh_image_variable_blur": (C.c_int, [V, V, C.POINTER(VariableBlurC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

@@ -1,5 +1,5 @@
 // csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, the ten
-// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field, resize), crop and statistics, with their host rules (crh_*_texels) and validators.
+// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field, resize), crop, statistics and the variable blur, with their host rules (crh_*_texels) and validators.
 // Host code only: the kernels are image_filter.hip's and raster.hip's (launch.hpp), the rules are the filters' headers. Of a renderer it
 // uses its device, its stream and "wait for every stream" (api_internal.hpp); what is about a frame or a paint table stays in api.hip.
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 #include "regions.hpp"
 #include "resize.hpp"
 #include "turbulence.hpp"
+#include "variable_blur.hpp"
 
 using namespace crh;
 
@@ -850,4 +851,75 @@ crh_status crh_image_statistics(const crh_image* src, uint32_t channel, uint32_t
     if (!job.ok) return CRH_ERR_HIP;
     *out = stats;
     return CRH_OK;
+}
+// ---- variable blur
+namespace {
+static_assert(CRH_MAX_BLUR_RADIUS == kVariableBlurMaxRadius && CRH_BLUR_EDGE_TRANSPARENT == kVariableBlurTransparent, "variable_blur.hpp's largest radius and edge are the header's");
+constexpr const char* kVariableBlur = "crh_variable_blur_validate";
+// the checks of the fields behind the null arguments, in the header's order: the one check of the four entry points
+crh_status variable_blur_fields(const crh_variable_blur* how) {
+    if (!how) return refuse(kVariableBlur, "a null argument");
+    const float sigmas[4] = {how->sigma_x[0], how->sigma_x[1], how->sigma_y[0], how->sigma_y[1]};
+    for (float s : sigmas)
+        if (!std::isfinite(s)) return refuse(kVariableBlur, "a sigma is not finite", CRH_ERR_NON_FINITE);
+    for (float s : sigmas)
+        if (s < 0.0f || s > CRH_MAX_BLUR_SIGMA) return refuse(kVariableBlur, "a sigma is outside [0, CRH_MAX_BLUR_SIGMA]");
+    if (how->channel > CRH_CHANNEL_A) return refuse(kVariableBlur, "channel is above CRH_CHANNEL_A");
+    if (how->edge > CRH_BLUR_EDGE_REFLECT) return refuse(kVariableBlur, "edge is above CRH_BLUR_EDGE_REFLECT");
+    return CRH_OK;
+}
+// the 256 tap sets of both axes, by the blur's own tap rule (validated fields: blur_taps refuses none of their sigmas)
+crh_status variable_blur_axes(const crh_variable_blur* how, VariableBlurAxis* ax, VariableBlurAxis* ay) {
+    const auto taps = [](float sigma, std::vector<uint32_t>& q) { return (int)blur_taps(sigma, q); };
+    if (variable_blur_axis(how->sigma_x[0], how->sigma_x[1], taps, ax) != 0 || variable_blur_axis(how->sigma_y[0], how->sigma_y[1], taps, ay) != 0)
+        return refuse(kVariableBlur, "a level's taps leave the kernels' fields", CRH_ERR_UNSUPPORTED); // (the builder's assertion: never met)
+    return CRH_OK;
+}
+} // namespace
+crh_status crh_variable_blur_validate(const crh_variable_blur* how) { return variable_blur_fields(how); }
+crh_status crh_variable_blur_sigma(const crh_variable_blur* how, uint32_t code, float* sigma_x, float* sigma_y) {
+    if (!how || !sigma_x || !sigma_y) return refuse(kVariableBlur, "a null argument");
+    const crh_status st = variable_blur_fields(how);
+    if (st != CRH_OK) return st;
+    if (code > 255u) return refuse(kVariableBlur, "a code is above 255");
+    *sigma_x = variable_blur_sigma(how->sigma_x[0], how->sigma_x[1], code), *sigma_y = variable_blur_sigma(how->sigma_y[0], how->sigma_y[1], code);
+    return CRH_OK;
+}
+crh_status crh_variable_blur_texels(uint32_t width, uint32_t height, const void* rgba8, const void* mask_rgba8, const crh_variable_blur* how, void* out_rgba8) {
+    if (!rgba8 || !mask_rgba8 || !how || !out_rgba8) return refuse(kVariableBlur, "a null argument");
+    crh_status st = variable_blur_fields(how);
+    if (st == CRH_OK) st = check_size(kVariableBlur, width, height);
+    if (st != CRH_OK) return st;
+    if (out_rgba8 == rgba8 || out_rgba8 == mask_rgba8) return refuse(kVariableBlur, "out_rgba8 is rgba8 or mask_rgba8");
+    VariableBlurAxis ax, ay;
+    st = variable_blur_axes(how, &ax, &ay);
+    if (st != CRH_OK) return st;
+    variable_blur_run(static_cast<const uint8_t*>(rgba8), static_cast<const uint8_t*>(mask_rgba8), width, height, ax, ay, how->channel, how->edge, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_variable_blur(const crh_image* src, const crh_image* mask, const crh_variable_blur* how, crh_image** out) {
+    if (!src || !mask || !how || !out) return refuse(kVariableBlur, "a null argument");
+    crh_status st = variable_blur_fields(how); // (the fields before the images: a refused `how` does not look at them)
+    if (st == CRH_OK && !src->renderer) st = refuse(kVariableBlur, "a null argument");
+    if (st == CRH_OK) st = check_size(kVariableBlur, src->width, src->height);
+    if (st != CRH_OK) return st;
+    if (mask->width != src->width || mask->height != src->height) return refuse(kVariableBlur, "the mask is of another size");
+    if (mask->renderer != src->renderer) return refuse(kVariableBlur, "the images belong to different renderers");
+    VariableBlurAxis ax, ay;
+    st = variable_blur_axes(how, &ax, &ay);
+    if (st != CRH_OK) return st;
+    // one upload, at the head of the intermediate's allocation: [the x axis's entries and taps | the y axis's], variable_blur.hpp's layout
+    std::vector<uint32_t> words(ax.words);
+    words.insert(words.end(), ay.words.begin(), ay.words.end());
+    const size_t tables_bytes = (words.size() * 4 + 255) / 256 * 256; // (the intermediate behind them stays 256-byte aligned)
+    const uint32_t w = src->width, h = src->height, shift = 8u * how->channel, edge = how->edge;
+    return filter_call("crh_image_variable_blur", src->renderer, w, h, out, [&](FilterJob& job) {
+        // [the tables | the intermediate: four 16-bit values per texel]
+        void* scratch = job.scratch(tables_bytes + (size_t)w * h * 8, words.data(), words.size() * 4);
+        const uint32_t* table_x = static_cast<const uint32_t*>(scratch);
+        const uint32_t* table_y = table_x + ax.words.size();
+        void* tmp = static_cast<char*>(scratch) + tables_bytes;
+        job.launch("k_image_variable_blur_h", [&] { launch_image_variable_blur_h(texels_of(src), texels_of(mask), w, h, tmp, table_x, ax.radius, shift, edge, job.stream); });
+        job.launch("k_image_variable_blur_v", [&] { launch_image_variable_blur_v(tmp, texels_of(mask), job.texels(), w, h, table_y, shift, edge, job.stream); });
+    });
 }

@@ -13,6 +13,7 @@
 // crh_image_resize: k_image_resize_h and k_image_resize_v resample an image to any size with the rule of resize.hpp, separably, with per-output integer taps.
 // crh_image_crop and crh_image_create_from_frame_region: k_image_crop copies a rectangle of an image or of a frame, zeros outside it, with the index rule of regions.hpp.
 // crh_image_statistics: k_image_stats and k_image_stats_merge reduce an image to its per-channel histograms and the bounds of its content with the rule of regions.hpp.
+// crh_image_variable_blur: k_image_variable_blur_h and k_image_variable_blur_v blur with the taps of each texel's own mask level, with the rule of variable_blur.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +30,7 @@
 #include "regions.hpp"
 #include "resize.hpp"
 #include "turbulence.hpp"
+#include "variable_blur.hpp"
 
 namespace crh {
 namespace {
@@ -189,7 +191,215 @@ void launch_image_blur_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_
 }
 
 namespace {
-constexpr int kCompositeLanes = 256;        // lanes per workgroup: one group of V texels of a row each
+static_assert(kBlurApron == (int)kVariableBlurMaxRadius, "the variable blur's apron holds the largest radius of any level");
+
+// sum_k q[|k|] row[centre + k] over one level's taps, acc = (r, b, g, a): the two texels of a tap are added in their 16-bit fields first.
+// Called with q and R in SGPRs (a wave of one level: the taps come through the scalar cache, the loop does not diverge) or per lane.
+__device__ __forceinline__ void variable_blur_row_sum(const uint2* row, uint32_t centre, const uint32_t* __restrict__ q, uint32_t R, uint32_t acc[4]) {
+    const uint2 c = row[centre];
+    variable_blur_mad(acc, q[0], VariableBlurFields{c.x, c.y});
+    for (uint32_t k = 1; k <= R; ++k) {
+        const uint2 l = row[centre - k], h = row[centre + k];
+        variable_blur_mad(acc, q[k], VariableBlurFields{l.x + h.x, l.y + h.y});
+    }
+}
+
+// One staged row i of the intermediate against a lane's kBlurRows output rows j0 + m: row m takes q_m[|i - (j0 + m)|] if that lies within
+// its own radius (R[m] = -1: no such row or column) and nothing beyond. UNIFORM: every lane of the wave holds the same R and offset per
+// row, so they are read from the first lane: scalar compares, scalar tap loads.
+template <bool UNIFORM>
+__device__ __forceinline__ void variable_blur_column_rows(const uint2 (*rows)[kBlurColumns], uint32_t lane, int chunk, int from, int to, int j0, const uint32_t* __restrict__ table, const int (&R)[kBlurRows],
+                                                          const uint32_t (&offset)[kBlurRows], uint32_t (&acc)[kBlurRows][4]) {
+    int Rm[kBlurRows];
+    uint32_t om[kBlurRows];
+#pragma unroll
+    for (int m = 0; m < kBlurRows; ++m) Rm[m] = UNIFORM ? __builtin_amdgcn_readfirstlane(R[m]) : R[m], om[m] = UNIFORM ? __builtin_amdgcn_readfirstlane(offset[m]) : offset[m];
+    for (int i = from; i <= to; ++i) {
+        const uint2 t = rows[i - chunk][lane];
+#pragma unroll
+        for (int m = 0; m < kBlurRows; ++m) {
+            const int d = abs(i - (j0 + m));
+            if (d <= Rm[m]) variable_blur_mad(acc[m], table[om[m] + (uint32_t)d], VariableBlurFields{t.x, t.y});
+        }
+    }
+}
+
+// The same for a wave whose rows all hold ONE level (a mask of one value, the bands of a ramp along y): q = that level's taps and R its
+// radius, in SGPRs. A pair of staged rows (i, i + 1) that lies wholly above the wave's rows, or wholly below them, and within R of all
+// eight, meets them with consecutive taps q[a - 1 .. a + 7], each >= q[1] and so 16 bits wide: the pair is regrouped by channel and
+// added with one v_dot2_u32_u16 per row and channel, k_image_blur_v's inner loop, the tap pairs packed from the scalar loads. The few
+// rows beside or among the wave's own (and an odd one at a run's end) go one at a time as above.
+__device__ __forceinline__ void variable_blur_column_one_level(const uint2 (*rows)[kBlurColumns], uint32_t lane, int chunk, int from, int to, int j0, const uint32_t* __restrict__ q, int R,
+                                                               uint32_t (&acc)[kBlurRows][4]) {
+    // the rows [from, to] in five runs, in any order (the sums are exact): [from, a0) one at a time, `na` rows from a0 in pairs above the
+    // wave's rows, [a0 + na, b0) one at a time, `nb` rows from b0 in pairs below them, the rest one at a time
+    const int a0 = min(max(j0 + kBlurRows - 1 - R, from), to + 1), na = max(min(to, j0 - 1) - a0 + 1, 0) & ~1;
+    const int b0 = min(max(j0 + kBlurRows, from), to + 1), nb = max(min(to, j0 + R) - b0 + 1, 0) & ~1;
+    const auto singles = [&](int lo, int hi) {
+        for (int i = lo; i <= hi; ++i) {
+            const uint2 t = rows[i - chunk][lane];
+#pragma unroll
+            for (int m = 0; m < kBlurRows; ++m) {
+                const int d = abs(i - (j0 + m));
+                if (d <= R) variable_blur_mad(acc[m], q[d], VariableBlurFields{t.x, t.y});
+            }
+        }
+    };
+    singles(from, a0 - 1);
+    for (int i = a0; i < a0 + na; i += 2) { // row i is j0 - i + m >= 2 from row m, row i + 1 one less; j0 - i + 7 <= R
+        const uint2 t0 = rows[i - chunk][lane], t1 = rows[i + 1 - chunk][lane];
+        const uint32_t rr = low_halves(t0.x, t1.x), gg = high_halves(t0.x, t1.x), bb = low_halves(t0.y, t1.y), aa = high_halves(t0.y, t1.y);
+        const uint32_t* p = q + (j0 - i - 1);
+#pragma unroll
+        for (int m = 0; m < kBlurRows; ++m) {
+            const uint32_t pair = p[m + 1] | p[m] << 16;
+            acc[m][0] = dot2(rr, pair, acc[m][0]), acc[m][1] = dot2(gg, pair, acc[m][1]), acc[m][2] = dot2(bb, pair, acc[m][2]), acc[m][3] = dot2(aa, pair, acc[m][3]);
+        }
+    }
+    singles(a0 + na, b0 - 1);
+    for (int i = b0; i < b0 + nb; i += 2) { // row i is i - j0 - m >= 1 from row m, row i + 1 one more; i + 1 - j0 <= R
+        const uint2 t0 = rows[i - chunk][lane], t1 = rows[i + 1 - chunk][lane];
+        const uint32_t rr = low_halves(t0.x, t1.x), gg = high_halves(t0.x, t1.x), bb = low_halves(t0.y, t1.y), aa = high_halves(t0.y, t1.y);
+        const uint32_t* p = q + (i - j0 - (kBlurRows - 1));
+#pragma unroll
+        for (int m = 0; m < kBlurRows; ++m) {
+            const uint32_t pair = p[kBlurRows - 1 - m] | p[kBlurRows - m] << 16;
+            acc[m][0] = dot2(rr, pair, acc[m][0]), acc[m][1] = dot2(gg, pair, acc[m][1]), acc[m][2] = dot2(bb, pair, acc[m][2]), acc[m][3] = dot2(aa, pair, acc[m][3]);
+        }
+    }
+    singles(b0 + nb, to);
+}
+} // namespace
+
+// crh_image_variable_blur, horizontal pass. k_image_blur_h's geometry — grid (ceil(w / 256), h), 256 lanes, the segment and an apron
+// staged in LDS with the edge applied, 8 bytes a texel, lane l reads l + const — but the apron is the CALL's largest radius and every
+// lane sums over its own level's taps: u = the mask's code at the lane's own texel, table[u] = offset << 8 | radius, the taps at
+// table[offset ..]. A wave whose lanes all hold one level (a smooth mask, a ramp along y) takes its taps with a wave-uniform index, as
+// k_image_blur_h does; any other wave loads them per lane and runs to its largest radius. Both give the same sums. The result keeps the
+// source's size under every edge. No mask byte indexes outside the 256 entries; no radius reaches outside the apron (clamped here too).
+__global__ __launch_bounds__(kBlurSegment) void k_image_variable_blur_h(const uint32_t* __restrict__ src, const uint32_t* __restrict__ mask, uint32_t w, uint2* __restrict__ tmp,
+                                                                         const uint32_t* __restrict__ table, uint32_t apron, uint32_t shift, uint32_t edge) {
+    __shared__ uint2 row[kBlurSegment + 2 * kBlurApron];
+    const uint32_t j = blockIdx.y, o0 = blockIdx.x * (uint32_t)kBlurSegment, lane = threadIdx.x;
+    const uint32_t* line = src + (size_t)j * w;
+    apron = min(apron, (uint32_t)kBlurApron);
+    const int first = (int)o0 - (int)apron; // the source column of row[0]
+    for (uint32_t at = lane; at < (uint32_t)kBlurSegment + 2u * apron; at += (uint32_t)kBlurSegment) {
+        const int i = first + (int)at;
+        uint32_t texel = 0u;
+        if (edge != 0u) texel = line[blur_wrap(i, (int)w, edge)];
+        else if ((uint32_t)i < w) texel = line[i];
+        const VariableBlurFields f = variable_blur_split(texel);
+        row[at] = make_uint2(f.x, f.y);
+    }
+    __syncthreads();
+    const uint32_t o = o0 + lane;
+    if (o >= w) return;
+    const uint32_t u = variable_blur_level(mask[(size_t)j * w + o], shift);
+    const uint32_t u0 = __builtin_amdgcn_readfirstlane(u);
+    uint32_t acc[4] = {0u, 0u, 0u, 0u};
+    if (__ballot(u != u0) == 0ull) {
+        const uint32_t entry = table[u0];
+        variable_blur_row_sum(row, lane + apron, table + variable_blur_offset(entry), min(variable_blur_radius(entry), apron), acc);
+    } else {
+        const uint32_t entry = table[u];
+        variable_blur_row_sum(row, lane + apron, table + variable_blur_offset(entry), min(variable_blur_radius(entry), apron), acc);
+    }
+    const VariableBlurFields t = variable_blur_intermediate(acc);
+    tmp[(size_t)j * w + o] = make_uint2(t.x, t.y);
+}
+
+// crh_image_variable_blur, vertical pass. k_image_blur_v's geometry — grid (ceil(w / 64), ceil(h / 32)), 4 waves, lanes along x, wave
+// w owns output rows 8 w .. 8 w + 7 of the block's 32, eight rows per lane in 32 accumulators; the intermediate rows are staged 32 at
+// a time in LDS with the edge applied. Every (lane, row) has its own level, read from the mask at the output's own texel; the block
+// stages the rows within its largest radius, a wave walks the rows within its own, and a lane's row takes a staged row only within that
+// row's radius. Three tap paths, chosen per wave: one level in the whole wave (a uniform mask, the bands of a ramp along y) takes
+// k_image_blur_v's inner loop on row pairs (variable_blur_column_one_level); one level per row across the lanes reads radii, offsets
+// and taps through the scalar cache; any other wave loads a tap per lane. All three give the same sums.
+//   out = (sum_k q_u[|k|] t(i, j + k) + 2^23) >> 24 per channel; the sum is < 2^32 (65280 * 65536).
+__global__ __launch_bounds__(kBlurColumns * kBlurWaves) void k_image_variable_blur_v(const uint2* __restrict__ tmp, const uint32_t* __restrict__ mask, uint32_t* __restrict__ out, uint32_t w, uint32_t h,
+                                                                                     const uint32_t* __restrict__ table, uint32_t shift, uint32_t edge) {
+    __shared__ uint2 rows[kBlurChunk][kBlurColumns];
+    __shared__ int wave_radius[kBlurWaves];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t x = blockIdx.x * (uint32_t)kBlurColumns + lane;
+    const int block_j0 = (int)(blockIdx.y * (uint32_t)kBlurBlockRows);
+    const int j0 = block_j0 + (int)(wave * (uint32_t)kBlurRows); // this wave's first output row
+    int R[kBlurRows], reach = -1;                                // (reach: the largest radius of this lane's rows)
+    uint32_t offset[kBlurRows];
+    bool uniform = true;
+#pragma unroll
+    for (int m = 0; m < kBlurRows; ++m) {
+        const bool mine = x < w && j0 + m < (int)h;
+        const uint32_t u = mine ? variable_blur_level(mask[(size_t)(j0 + m) * w + x], shift) : 0u;
+        uniform = uniform && __ballot(mine && u != (uint32_t)__builtin_amdgcn_readfirstlane(u)) == 0ull; // (lane 0's column lies inside the image)
+        const uint32_t entry = table[u];
+        R[m] = mine ? (int)min(variable_blur_radius(entry), (uint32_t)kBlurApron) : -1;
+        offset[m] = variable_blur_offset(entry);
+        reach = max(reach, R[m]);
+    }
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1) reach = max(reach, __shfl_xor(reach, step));
+    if (lane == 0u) wave_radius[wave] = reach;
+    __syncthreads();
+    int block_reach = wave_radius[0];
+#pragma unroll
+    for (int k = 1; k < kBlurWaves; ++k) block_reach = max(block_reach, wave_radius[k]);
+    block_reach = __builtin_amdgcn_readfirstlane(block_reach), reach = __builtin_amdgcn_readfirstlane(reach);
+    // one level in the whole wave: every row inside the image has the first row's tap set (and so its radius, the wave's reach)
+    const uint32_t level_offset = __builtin_amdgcn_readfirstlane(offset[0]);
+    bool one_level = uniform;
+#pragma unroll
+    for (int m = 1; m < kBlurRows; ++m) one_level = one_level && (j0 + m >= (int)h || (uint32_t)__builtin_amdgcn_readfirstlane(offset[m]) == level_offset);
+    // intermediate rows: the block reads [block_lo, block_hi], this wave [lo, hi] (empty for a wave with no row: reach = -1)
+    const int last_row = min(block_j0 + kBlurBlockRows, (int)h) - 1;
+    const int block_lo = block_j0 - block_reach, block_hi = last_row + block_reach;
+    const int lo = j0 - reach, hi = reach < 0 ? lo - 1 : min(j0 + kBlurRows, (int)h) - 1 + reach;
+    uint32_t acc[kBlurRows][4];
+#pragma unroll
+    for (int m = 0; m < kBlurRows; ++m) acc[m][0] = acc[m][1] = acc[m][2] = acc[m][3] = 0u;
+    // The staging loop once per path, the path chosen outside it: the three paths in one loop cost 134 VGPRs, apart the largest of them.
+    // Every wave of the block runs the same chunks, so the barriers of the three copies pair up whichever copy a wave is in.
+    const auto chunks = [&](auto&& accumulate) {
+        for (int chunk = block_lo; chunk <= block_hi; chunk += kBlurChunk) {
+            __syncthreads(); // (the rows of the chunk before have been read)
+            for (int s = (int)wave; s < kBlurChunk; s += kBlurWaves) { // every row of the chunk is written: zeros beyond block_hi
+                const int i = chunk + s;
+                uint2 t = make_uint2(0u, 0u);
+                if (x < w && i <= block_hi) {
+                    if (edge != 0u) t = tmp[(size_t)blur_wrap(i, (int)h, edge) * w + x];
+                    else if ((uint32_t)i < h) t = tmp[(size_t)i * w + x];
+                }
+                rows[s][lane] = t;
+            }
+            __syncthreads();
+            accumulate(chunk, max(chunk, lo), min(min(chunk + kBlurChunk - 1, block_hi), hi)); // [from, to]: wave-uniform, inside the chunk
+        }
+    };
+    if (one_level) chunks([&](int chunk, int from, int to) { variable_blur_column_one_level(rows, lane, chunk, from, to, j0, table + level_offset, reach, acc); });
+    else if (uniform) chunks([&](int chunk, int from, int to) { variable_blur_column_rows<true>(rows, lane, chunk, from, to, j0, table, R, offset, acc); });
+    else chunks([&](int chunk, int from, int to) { variable_blur_column_rows<false>(rows, lane, chunk, from, to, j0, table, R, offset, acc); });
+    if (x >= w) return;
+#pragma unroll
+    for (int m = 0; m < kBlurRows; ++m) {
+        const int j = j0 + m;
+        if (j >= (int)h) break;
+        out[(size_t)j * w + x] = variable_blur_texel(acc[m]);
+    }
+}
+
+void launch_image_variable_blur_h(const uint32_t* src, const uint32_t* mask, uint32_t w, uint32_t h, void* tmp, const uint32_t* table, uint32_t apron, uint32_t shift, uint32_t edge, hipStream_t stream) {
+    const dim3 grid((w + (uint32_t)kBlurSegment - 1u) / (uint32_t)kBlurSegment, h);
+    hipLaunchKernelGGL(k_image_variable_blur_h, grid, dim3(kBlurSegment), 0, stream, src, mask, w, static_cast<uint2*>(tmp), table, apron, shift, edge);
+}
+
+void launch_image_variable_blur_v(const void* tmp, const uint32_t* mask, uint32_t* out, uint32_t w, uint32_t h, const uint32_t* table, uint32_t shift, uint32_t edge, hipStream_t stream) {
+    const dim3 grid((w + (uint32_t)kBlurColumns - 1u) / (uint32_t)kBlurColumns, (h + (uint32_t)kBlurBlockRows - 1u) / (uint32_t)kBlurBlockRows);
+    hipLaunchKernelGGL(k_image_variable_blur_v, grid, dim3(kBlurColumns * kBlurWaves), 0, stream, static_cast<const uint2*>(tmp), mask, out, w, h, table, shift, edge);
+}
+
+namespace {
+constexpr int kCompositeLanes = 256;       // lanes per workgroup: one group of V texels of a row each
 constexpr uint32_t kCompositeBlocks = 8192; // the grid's cap: four rounds of 256 CUs x 8 workgroups (measured against 2048 and none: DESIGN.md); the rows beyond it are strided over
 template <int V> struct TexelGroup { typedef uint32_t type __attribute__((ext_vector_type(V))); }; // V texels: one access of 4 V bytes
 } // namespace

@@ -914,6 +914,41 @@ def statistics_texels(pixels, channel=Channel.A, threshold=1):
     return _statistics_of(stats)
 
 
+def _variable_blur_arguments(sigma, sigma_at_zero, channel, edge):
+    """-> VariableBlurC; a scalar sigma serves both axes, as blur() takes sigma_y=None; a pair is (x, y)"""
+    x1, y1 = (sigma, sigma) if np.isscalar(sigma) else sigma
+    x0, y0 = (sigma_at_zero, sigma_at_zero) if np.isscalar(sigma_at_zero) else sigma_at_zero
+    how = _ffi.VariableBlurC()
+    how.sigma_x = (C.c_float * 2)(float(x0), float(x1))
+    how.sigma_y = (C.c_float * 2)(float(y0), float(y1))
+    how.channel, how.edge = int(channel) & 0xFFFFFFFF, int(edge) & 0xFFFFFFFF
+    return how
+
+
+def variable_blur_texels(pixels, mask, sigma, sigma_at_zero=0.0, channel=Channel.A, edge=BlurEdge.Pad):
+    """crh_variable_blur_texels (host only): the rule of Image.variable_blur on two (height, width, 4) uint8 arrays of one size, the
+    source and the mask -> a (height, width, 4) uint8 array (include/contrast_hip.h crh_image_variable_blur states the rule)."""
+    pixels, mask = np.ascontiguousarray(pixels), np.ascontiguousarray(mask)
+    for a in (pixels, mask):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+            raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"variable_blur_texels takes (height, width, 4) uint8 arrays, not {a.shape} {a.dtype}")
+    if pixels.shape != mask.shape:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"variable_blur_texels takes a mask of the source's size, not {mask.shape} beside {pixels.shape}")
+    how = _variable_blur_arguments(sigma, sigma_at_zero, channel, edge)
+    out = np.empty_like(pixels)
+    check(_ffi.load_library().crh_variable_blur_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, mask.ctypes.data, C.byref(how), out.ctypes.data))
+    return out
+
+
+def variable_blur_sigma(code, sigma, sigma_at_zero=0.0):
+    """crh_variable_blur_sigma (host only) -> (sigma_x, sigma_y): the sigmas, as float32 values, of the mask code `code` (<= 255) between
+    `sigma_at_zero` at code 0 and `sigma` at code 255, each a scalar or an (x, y) pair."""
+    how = _variable_blur_arguments(sigma, sigma_at_zero, Channel.A, BlurEdge.Pad)
+    sx, sy = C.c_float(), C.c_float()
+    check(_ffi.load_library().crh_variable_blur_sigma(C.byref(how), int(code) & 0xFFFFFFFF, C.byref(sx), C.byref(sy)))
+    return float(sx.value), float(sy.value)
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -1101,6 +1136,20 @@ class Image:
         how = _displace_arguments(scale, x_channel, y_channel, filter, edge)
         handle = C.c_void_p()
         check(self.lib.crh_image_displace(self.handle, map.handle, C.byref(how), C.byref(handle)))
+        return Image._adopt(self.renderer, handle, (self.width, self.height))
+
+    def variable_blur(self, mask, sigma, sigma_at_zero=0.0, channel=Channel.A, edge=BlurEdge.Pad):
+        """crh_image_variable_blur -> a new Image of one level, of this image's size under every edge, origin (0, 0): blur() with a
+        strength that changes across the image. `mask` is an Image of the same size and renderer; the stored code u of its `channel`
+        at a texel chooses that texel's own Gaussian: `sigma_at_zero` at u = 0, `sigma` at u = 255, linear in u between (either may be
+        the larger), each a scalar or an (x, y) pair in [0, MAX_BLUR_SIGMA]; the taps of a level are blur()'s. Integer and bit-exact,
+        built on the device and complete when this returns (a synchronous call). A mask of one value gives blur()'s bytes; a texel
+        whose level has sigma 0 comes back exactly. `edge` is what THIS image is outside itself; the default is BlurEdge.Pad because
+        the call keeps the size and a backdrop should not darken at its rim. A progressive backdrop blur: a mask whose alpha ramps
+        from 0 to 255 down the panel, variable_blur(ramp, 24). Neither image is modified; the mask may be this image."""
+        how = _variable_blur_arguments(sigma, sigma_at_zero, channel, edge)
+        handle = C.c_void_p()
+        check(self.lib.crh_image_variable_blur(self.handle, mask.handle, C.byref(how), C.byref(handle)))
         return Image._adopt(self.renderer, handle, (self.width, self.height))
 
     def distance_field(self, spread, mode=DistanceMode.Outside, channel=Channel.A, threshold=128, edge=BlurEdge.Transparent):

@@ -1084,6 +1084,58 @@ crh_status crh_statistics_texels(uint32_t width, uint32_t height, const void* rg
 crh_status crh_image_crop(const crh_image* src, int32_t x, int32_t y, uint32_t width, uint32_t height, crh_image** out);
 crh_status crh_image_create_from_frame_region(crh_frame* frame, int32_t x, int32_t y, uint32_t width, uint32_t height, crh_image** out);
 crh_status crh_image_statistics(const crh_image* src, uint32_t channel, uint32_t threshold, crh_image_stats* out);
+/* Variable blur: crh_image_blur with a strength that changes across the image — a progressive backdrop blur under a bar, tilt-shift,
+ * depth of field from a depth layer, a soft vignette, focus on one widget. A second image of the source's size, the mask, gives every
+ * texel a level, and the level chooses the texel's own taps. Integer and bit-exact like the blur, of which it is the general case.
+ *   level        u(i, j) = the stored code of how->channel (a crh_channel) of mask texel (i, j), 0 <= u <= 255, as it is: no
+ *                unpremultiply, as crh_image_distance_field reads its channel. The mask has the source's size and is read at the
+ *                output's own (i, j); no edge rule applies to it.
+ *   sigma        per axis, with s0 = sigma[0] (at code 0) and s1 = sigma[1] (at code 255), each in [0, CRH_MAX_BLUR_SIGMA]: u == 0 gives
+ *                s0 and u == 255 gives s1, the caller's floats exactly; any other u gives
+ *                (float)((double)s0 + ((double)s1 - (double)s0) * (double)u / 255.0), evaluated in that order. s0 > s1 is legal.
+ *   taps         exactly crh_blur_taps(sigma of the level): R_u, q_u[0 .. R_u]. There is no second tap rule.
+ *   horizontal   with u = u(i, j): t(i, j) = (sum_{k = -Rx_u .. Rx_u} qx_u[|k|] c(i + k, j) + 128) >> 8 per channel, c the source under `edge`.
+ *   vertical     with u = u(i, j): out(i, j) = (sum_{k = -Ry_u .. Ry_u} qy_u[|k|] t(i, j + k) + 2^23) >> 24. t <= 65280, the sum < 2^32.
+ *   edge         a crh_blur_edge: what the SOURCE is outside itself. PAD, REPEAT and REFLECT wrap a source index in the horizontal pass
+ *                and a row index of t in the vertical pass by exactly the blur's wrap(i, n); TRANSPARENT takes what lies outside as
+ *                zero. The result has the source's size under EVERY edge, origin (0, 0), as crh_image_convolve keeps it: with growth
+ *                the mask would need an edge rule of its own. A caller who wants the spill takes a larger crh_image_crop of the
+ *                source and of the mask first, which pads with zeros.
+ * Hence: (1) a mask whose chosen channel is one value u everywhere gives, byte for byte, crh_image_blur(src, sigma_x(u), sigma_y(u), edge)
+ * under PAD, REPEAT and REFLECT, and under TRANSPARENT that blur's result cropped to (Rx, Ry, w, h); (2) a texel whose level has sigma 0
+ * on both axes comes back exactly, whatever its neighbours' levels are (t = 256 c, then (65536 * 256 c + 2^23) >> 24 = c); (3) a constant
+ * image comes back exactly under the three same-size edges, because every tap set sums to 65536; (4) rgb <= a survives, because one
+ * texel's four channels share its weights and both roundings are monotone; (5) the result does not depend on which of sigma[0] and
+ * sigma[1] is the larger beyond what the formula says: a descending ramp over the inverted mask is the ascending one wherever the two
+ * formulas give one float.
+ * crh_variable_blur_validate, crh_variable_blur_sigma (the two sigmas of one code <= 255, as crh_blur_taps hands out taps; a code above
+ * 255 is CRH_ERR_INVALID_ARGUMENT) and crh_variable_blur_texels (the rule on whole images in host memory, width * height * 4 bytes each in
+ * the order r g b a at any alignment, row 0 first) are host only: no renderer, no device.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out and the out buffer untouched:
+ * first a null argument; then a sigma that is not finite (CRH_ERR_NON_FINITE); then a sigma that is negative or above
+ * CRH_MAX_BLUR_SIGMA; then a channel above CRH_CHANNEL_A; then an edge above CRH_BLUR_EDGE_REFLECT; then a size outside [1, 16384];
+ * then, in crh_variable_blur_texels, an out_rgba8 equal to either input; then, in crh_image_variable_blur, a mask of another size than
+ * the source, then images of different renderers: CRH_ERR_INVALID_ARGUMENT but for the one named, each with a crh_last_error text
+ * "crh_variable_blur_validate: ...". mask == src is legal.
+ * crh_image_variable_blur builds the 256 tap sets of each axis on the host (consecutive levels of one sigma share a set), uploads them
+ * with a 256-entry table of (offset, radius) per axis at the head of the one scratch allocation that also holds the 16-bit intermediate,
+ * and runs k_image_variable_blur_h and k_image_variable_blur_v on the renderer's stream: the blur's geometry, an apron of the call's
+ * largest radius, every lane summing over its own level's taps; a wave whose lanes share one level reads its taps as the blur does.
+ * The result has one level (crh_image_generate_mipmaps works on it); only level 0 of the source and of the mask is read and neither is
+ * modified. A failed allocation or launch frees everything, writes nothing to *out and returns CRH_ERR_HIP.
+ * Limits: this is a gather — each output picks its own kernel, the form every UI toolkit ships — not the scatter a physical lens gives;
+ * the profile between the two sigmas is linear in the code: any other profile is a crh_image_color_filter table on the mask first; the
+ * call is synchronous, like its siblings. */
+typedef struct crh_variable_blur {
+    float sigma_x[2];   /* the x sigma at mask code 0 and at mask code 255, each in [0, CRH_MAX_BLUR_SIGMA] */
+    float sigma_y[2];   /* the same for y */
+    uint32_t channel;   /* crh_channel: which STORED code of the mask's texel is the level */
+    uint32_t edge;      /* crh_blur_edge: what the SOURCE is outside itself */
+} crh_variable_blur;
+crh_status crh_variable_blur_validate(const crh_variable_blur* how);                                                          /* host only */
+crh_status crh_variable_blur_sigma(const crh_variable_blur* how, uint32_t code, float* sigma_x, float* sigma_y);              /* host only */
+crh_status crh_variable_blur_texels(uint32_t width, uint32_t height, const void* rgba8, const void* mask_rgba8, const crh_variable_blur* how, void* out_rgba8); /* host only: the rule */
+crh_status crh_image_variable_blur(const crh_image* src, const crh_image* mask, const crh_variable_blur* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

@@ -855,6 +855,41 @@ inline std::array<int32_t, 2> displace_offset(const Displace& displace, uint32_t
     check(crh_displace_offset(&how, code_x, code_y, q.data()));
     return q;
 }
+// Variable blur (include/contrast_hip.h crh_image_variable_blur states the rule): a blur whose sigma a mask sets per texel.
+// The fields of crh_variable_blur: per axis the sigma at mask code 0 and at code 255 (linear in the code between; either may be the
+// larger), the mask's channel whose STORED code is the level, and what the SOURCE is outside itself. The edge's default is Pad because
+// the call keeps the size and a backdrop should not darken at its rim.
+struct VariableBlur {
+    std::array<float, 2> sigma_x = {0.0f, 0.0f}, sigma_y = {0.0f, 0.0f};
+    Channel channel = Channel::A;
+    BlurEdge edge = BlurEdge::Pad;
+    crh_variable_blur to_c() const {
+        crh_variable_blur how = {};
+        how.sigma_x[0] = sigma_x[0], how.sigma_x[1] = sigma_x[1], how.sigma_y[0] = sigma_y[0], how.sigma_y[1] = sigma_y[1];
+        how.channel = (uint32_t)channel, how.edge = (uint32_t)edge;
+        return how;
+    }
+};
+// crh_variable_blur_texels (host only): the rule on two width * height * 4 byte arrays, the source and the mask -> the bytes of the result
+inline std::vector<uint8_t> variable_blur_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, const std::vector<uint8_t>& mask, const VariableBlur& blur) {
+    if (texels.size() != (size_t)width * height * 4u || mask.size() != texels.size()) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const crh_variable_blur how = blur.to_c();
+    std::vector<uint8_t> out(texels.size());
+    check(crh_variable_blur_texels(width, height, texels.data(), mask.data(), &how, out.data()));
+    return out;
+}
+// crh_variable_blur_sigma (host only): the sigmas (x, y) of one mask code <= 255
+inline std::array<float, 2> variable_blur_sigma(const VariableBlur& blur, uint32_t code) {
+    const crh_variable_blur how = blur.to_c();
+    std::array<float, 2> sigma = {0.0f, 0.0f};
+    check(crh_variable_blur_sigma(&how, code, &sigma[0], &sigma[1]));
+    return sigma;
+}
+// crh_variable_blur_validate (host only): throws what Image::variable_blur would refuse of the fields
+inline void variable_blur_validate(const VariableBlur& blur) {
+    const crh_variable_blur how = blur.to_c();
+    check(crh_variable_blur_validate(&how));
+}
 // Distance fields (include/contrast_hip.h crh_image_distance_field states the rule): the exact Euclidean distance to a shape in 8 bits over a spread.
 enum class DistanceMode : uint32_t { Outside = CRH_DISTANCE_OUTSIDE, Inside = CRH_DISTANCE_INSIDE };
 // The fields of crh_distance: what the distance is measured to (Outside: the shape, 255 on it and 0 at the spread; Inside: what is not the
@@ -1063,6 +1098,16 @@ class Image {
         const crh_displace how = displace.to_c();
         Image image;
         check(crh_image_displace(handle_, map.handle_, &how, &image.handle_));
+        image.width_ = width_, image.height_ = height_;
+        return image;
+    }
+    // crh_image_variable_blur -> a new Image of one level, of this image's size under every edge, origin (0, 0): blur() with the taps of each
+    // texel's own level, the stored code of `blur.channel` of `mask`, an image of the same size and renderer; integer and bit-exact,
+    // complete on return (a synchronous call). A mask of one value gives blur()'s bytes. Neither image is modified; the mask may be this image.
+    Image variable_blur(const Image& mask, const VariableBlur& blur) const {
+        const crh_variable_blur how = blur.to_c();
+        Image image;
+        check(crh_image_variable_blur(handle_, mask.handle_, &how, &image.handle_));
         image.width_ = width_, image.height_ = height_;
         return image;
     }

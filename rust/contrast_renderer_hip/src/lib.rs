@@ -1115,6 +1115,47 @@ pub fn displace_texels(width: u32, height: u32, texels: &[u8], map: &[u8], displ
     status(unsafe { ffi::crh_displace_texels(width, height, texels.as_ptr() as *const _, map.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// The fields of `crh_variable_blur` (include/contrast_hip.h, `crh_image_variable_blur`, states the rule): per axis the sigma at mask code 0
+/// and at code 255 (linear in the code between; either may be the larger), the mask's channel whose STORED code is the level, and what
+/// the SOURCE is outside itself. The edge's default is `Pad` because the call keeps the size and a backdrop should not darken at its rim.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct VariableBlur {
+    pub sigma_x: [f32; 2],
+    pub sigma_y: [f32; 2],
+    pub channel: Channel,
+    pub edge: BlurEdge,
+}
+impl Default for VariableBlur {
+    fn default() -> VariableBlur {
+        VariableBlur { sigma_x: [0.0; 2], sigma_y: [0.0; 2], channel: Channel::A, edge: BlurEdge::Pad }
+    }
+}
+impl VariableBlur {
+    fn to_c(&self) -> ffi::crh_variable_blur {
+        ffi::crh_variable_blur { sigma_x: self.sigma_x, sigma_y: self.sigma_y, channel: self.channel as u32, edge: self.edge as u32 }
+    }
+}
+/// `crh_variable_blur_validate` (host only): what `Image::variable_blur` would refuse of the fields
+pub fn variable_blur_validate(blur: &VariableBlur) -> Result<(), Error> {
+    let how = blur.to_c();
+    status(unsafe { ffi::crh_variable_blur_validate(&how) })
+}
+/// `crh_variable_blur_sigma` (host only) -> the sigmas (x, y) of one mask code <= 255
+pub fn variable_blur_sigma(blur: &VariableBlur, code: u32) -> Result<[f32; 2], Error> {
+    let how = blur.to_c();
+    let (mut sigma_x, mut sigma_y) = (0f32, 0f32);
+    status(unsafe { ffi::crh_variable_blur_sigma(&how, code, &mut sigma_x, &mut sigma_y) })?;
+    Ok([sigma_x, sigma_y])
+}
+/// `crh_variable_blur_texels` (host only): the rule on two width * height * 4 byte slices, the source and the mask -> the bytes of the result
+pub fn variable_blur_texels(width: u32, height: u32, texels: &[u8], mask: &[u8], blur: &VariableBlur) -> Result<Vec<u8>, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    assert_eq!(mask.len(), texels.len());
+    let how = blur.to_c();
+    let mut out = vec![0u8; texels.len()];
+    status(unsafe { ffi::crh_variable_blur_texels(width, height, texels.as_ptr() as *const _, mask.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_distance_mode`: what the distance is measured to
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum DistanceMode {
@@ -1403,6 +1444,15 @@ impl Image {
         let how = displace.to_c();
         let mut raw = ptr::null_mut();
         status(unsafe { ffi::crh_image_displace(self.raw, map.raw, &how, &mut raw) })?;
+        Ok(Image { raw, width: self.width, height: self.height, origin: (0, 0) })
+    }
+    /// `crh_image_variable_blur` -> a new `Image` of one level, of this image's size under every edge, origin (0, 0): `blur` with the taps
+    /// of each texel's own level, the stored code of `blur.channel` of `mask`, an image of the same size and renderer; integer and
+    /// bit-exact, complete on return (a synchronous call). A mask of one value gives `blur`'s bytes. Neither image is modified.
+    pub fn variable_blur(&self, mask: &Image, blur: &VariableBlur) -> Result<Image, Error> {
+        let how = blur.to_c();
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_variable_blur(self.raw, mask.raw, &how, &mut raw) })?;
         Ok(Image { raw, width: self.width, height: self.height, origin: (0, 0) })
     }
     /// `crh_image_lighting` -> a new `Image` of one level, of this image's size and origin: this image's alpha as a height field lit by
