@@ -1,7 +1,7 @@
 // csrc/convolve.hpp — the convolution rule of crh_image_convolve (include/contrast_hip.h states it), written once: the quantisation of the
 // kernel matrix, the load of one texel (the clamp to alpha and, under preserve_alpha, the unpremultiply of color_filter.hpp) and the output
 // stage. k_image_convolve (image_filter.hip) and crh_convolve_texels (image.hip, on the host) both call convolve_load, convolve_mad and
-// convolve_store, and both take their coefficients from convolve_quantize; the wrap is morphology.hpp's. All values are 8-bit codes, all
+// convolve_store, and both take their coefficients from convolve_quantize; the wrap is edge.hpp's. All values are 8-bit codes, all
 // arithmetic is signed 32-bit: sum |k| <= 2^22, so |sum k s| <= 2^22 * 255, and with 255 * 65536 of bias and the rounding half the largest
 // magnitude is 1 086 291 968 < 2^31. Every partial sum obeys the same bound, so the order of the taps is free.
 #pragma once
@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "color_filter.hpp"
-#include "morphology.hpp"
+#include "edge.hpp"
 
 namespace crh {
 
@@ -114,13 +114,13 @@ inline void convolve_run(const uint8_t* in, uint32_t w, uint32_t h, const Convol
         for (uint32_t i = 0; i < w; ++i) {
             for (uint32_t c = 0; c < order_x; ++c) {
                 const int x = (int)i - (int)target_x + (int)(order_x - 1u - c);
-                columns[c] = edge != kConvolveTransparent ? morphology_wrap(x, (int)w, edge) : (uint32_t)x < w ? x : -1;
+                columns[c] = edge != kConvolveTransparent ? edge_wrap(x, (int)w, edge) : (uint32_t)x < w ? x : -1;
             }
             int32_t n[4] = {f.bias, f.bias, f.bias, f.bias};
             for (uint32_t r = 0; r < order_y; ++r) {
                 const int y = (int)j - (int)target_y + (int)(order_y - 1u - r);
                 if (edge == kConvolveTransparent && (uint32_t)y >= h) continue;
-                const uint32_t* line = loaded.data() + (size_t)(edge != kConvolveTransparent ? morphology_wrap(y, (int)h, edge) : y) * w;
+                const uint32_t* line = loaded.data() + (size_t)(edge != kConvolveTransparent ? edge_wrap(y, (int)h, edge) : y) * w;
                 for (uint32_t c = 0; c < order_x; ++c)
                     if (columns[c] >= 0) convolve_mad<PRESERVE>(n, f.k[r * order_x + c], line[columns[c]]);
             }

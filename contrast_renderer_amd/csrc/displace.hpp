@@ -3,7 +3,7 @@
 // the last two around a texel-fetch functor. k_image_displace (image_filter.hip) and crh_displace_texels (image.hip, on the host, through
 // displace_run) both call displace_offsets, displace_taps and displace_blend; the host goes through displace_texel, the kernel calls its
 // two halves itself so that every fetch of a lane's rows is issued before the first blend. All values are 8-bit codes and all arithmetic
-// is 32-bit integer: the same bytes on x86-64 and on gfx950. The map's unpremultiply is color_filter.hpp's, the host's wrap morphology.hpp's.
+// is 32-bit integer: the same bytes on x86-64 and on gfx950. The map's unpremultiply is color_filter.hpp's, the host's wrap edge.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,7 +11,7 @@
 #include <cmath>
 
 #include "color_filter.hpp"
-#include "morphology.hpp"
+#include "edge.hpp"
 
 namespace crh {
 
@@ -96,7 +96,7 @@ __host__ __device__ __forceinline__ uint32_t displace_texel(int32_t X, int32_t Y
 
 // The rule on a whole image on the host (crh_displace_texels): w x h texels of `in` through the map `map` of the same size into `out`,
 // which is neither of them; the caller's bytes at any alignment, a texel's word assembled from its four bytes in memory order, r first.
-// S: under TRANSPARENT zero when either index is outside, otherwise the texel at morphology.hpp's wrap of each index — every address is
+// S: under TRANSPARENT zero when either index is outside, otherwise the texel at edge.hpp's wrap of each index — every address is
 // formed from a tested or wrapped index.
 template <uint32_t FILTER>
 inline void displace_run(const uint8_t* in, const uint8_t* map, uint32_t w, uint32_t h, const DisplaceConstants& f, uint8_t* out) {
@@ -107,7 +107,7 @@ inline void displace_run(const uint8_t* in, const uint8_t* map, uint32_t w, uint
         if (edge == kDisplaceTransparent) {
             if ((uint32_t)i >= w || (uint32_t)j >= h) return 0u;
         } else {
-            i = morphology_wrap(i, (int)w, edge), j = morphology_wrap(j, (int)h, edge);
+            i = edge_wrap(i, (int)w, edge), j = edge_wrap(j, (int)h, edge);
         }
         return word(in + ((size_t)j * w + (size_t)i) * 4u);
     };

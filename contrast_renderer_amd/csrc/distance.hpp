@@ -3,14 +3,14 @@
 // scan along a row of column distances. k_image_distance_v and k_image_distance_h (image_filter.hip) and crh_distance_texels (image.hip,
 // on the host, through distance_run) all call distance_target, distance_scan and distance_code. Everything is integer: squared distances
 // between texel centres are integers, and the one rounding is the integer statement (2 c - 1)^2 spread^2 <= 260100 D2, taken in 64 bits
-// on the host where the 255 thresholds of a spread are made. The same bytes on x86-64 and on gfx950. The wrap is morphology.hpp's.
+// on the host where the 255 thresholds of a spread are made. The same bytes on x86-64 and on gfx950. The wrap is edge.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
 
-#include "morphology.hpp"
+#include "edge.hpp"
 
 namespace crh {
 
@@ -91,7 +91,7 @@ inline void distance_run(const uint8_t* in, uint32_t w, uint32_t h, const Distan
     distance_thresholds(f.spread, &thresholds);
     const auto target = [&](int i, int j) { // any position, in source coordinates
         bool inside = false;
-        if (f.edge != kDistanceTransparent) i = morphology_wrap(i, (int)w, f.edge), j = morphology_wrap(j, (int)h, f.edge);
+        if (f.edge != kDistanceTransparent) i = edge_wrap(i, (int)w, f.edge), j = edge_wrap(j, (int)h, f.edge);
         if ((uint32_t)i < w && (uint32_t)j < h) {
             const uint8_t* t = in + ((size_t)j * w + (size_t)i) * 4u;
             inside = distance_inside(t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24, f);
@@ -119,7 +119,7 @@ inline void distance_run(const uint8_t* in, uint32_t w, uint32_t h, const Distan
         for (int x = 0; x < out_w; ++x) {
             const uint32_t d2 = distance_scan(f.spread, [&](int dx) -> uint32_t {
                 const int i = x + dx; // a column of g: under a same-size edge through the wrap; under TRANSPARENT nothing (OUTSIDE) or off the shape (INSIDE) outside
-                if (f.edge != kDistanceTransparent) return row[morphology_wrap(i, out_w, f.edge)];
+                if (f.edge != kDistanceTransparent) return row[edge_wrap(i, out_w, f.edge)];
                 return (uint32_t)i < (uint32_t)out_w ? row[i] : f.mode == kDistanceInside ? 0u : kDistanceNone;
             });
             const uint32_t r = distance_texel(distance_code(thresholds.t, d2), f.mode);

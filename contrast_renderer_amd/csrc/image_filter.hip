@@ -1,19 +1,14 @@
-// csrc/image_filter.hip — crh_image_blur: a separable Gaussian blur of a premultiplied RGBA8 image as two kernels, integer and bit-exact
-// (include/contrast_hip.h states the model). k_image_blur_h filters rows of the source into an intermediate of four 16-bit values per
-// texel; k_image_blur_v filters the columns of that into packed RGBA8. Nothing here touches a raster kernel: the wrap helper is this file's own.
-// crh_image_composite: k_image_composite combines two images texel by texel with the rule of composite.hpp.
-// crh_image_color_filter: k_image_color_filter maps every texel of an image with the rule of color_filter.hpp.
-// crh_image_morphology: k_image_morph_h and k_image_morph_v take the per-channel min or max over a rectangle with the rule of morphology.hpp,
-// at a cost per texel that does not grow linearly with the radius.
-// crh_image_convolve: k_image_convolve puts an image through a kernel matrix with the rule of convolve.hpp, a 2-D stencil over a tile and its halo in LDS.
-// crh_image_lighting: k_image_lighting lights the alpha channel as a height field with the rule of lighting.hpp, binary64 arithmetic on a 3 x 3 stencil.
-// crh_image_turbulence: k_image_turbulence makes a noise image with the rule of turbulence.hpp, binary64 arithmetic on gradients gathered from LDS.
-// crh_image_displace: k_image_displace reads an image through per-texel offsets taken from a second one with the rule of displace.hpp, a gather from global memory.
-// crh_image_distance_field: k_image_distance_v and k_image_distance_h code the exact Euclidean distance to a shape with the rule of distance.hpp, separably through a byte of column distance per texel.
-// crh_image_resize: k_image_resize_h and k_image_resize_v resample an image to any size with the rule of resize.hpp, separably, with per-output integer taps.
-// crh_image_crop and crh_image_create_from_frame_region: k_image_crop copies a rectangle of an image or of a frame, zeros outside it, with the index rule of regions.hpp.
-// crh_image_statistics: k_image_stats and k_image_stats_merge reduce an image to its per-channel histograms and the bounds of its content with the rule of regions.hpp.
-// crh_image_variable_blur: k_image_variable_blur_h and k_image_variable_blur_v blur with the taps of each texel's own mask level, with the rule of variable_blur.hpp.
+// csrc/image_filter.hip — every kernel of the image API (image.hip makes the calls, launch.hpp declares the launchers), one family after
+// another. Each filter's rule is in its own header, shared with its host model; the edge rule is edge.hpp's, and the workgroup geometries
+// that several families share are image_geometry.hpp's. Nothing here touches a raster kernel.
+//   blur, variable blur                 k_image_blur_h / _v, k_image_variable_blur_h / _v   row and chunk staging, row pairs
+//   composite, colour filter            k_image_composite, k_image_color_filter             streaming
+//   morphology                          k_image_morph_h / _v                                doubling in LDS; van Herk / Gil-Werman
+//   convolve, lighting                  k_image_convolve, k_image_lighting                  tile with a halo
+//   turbulence, displace                k_image_turbulence, k_image_displace                tile
+//   distance field                      k_image_distance_v / _h                             column walks; a scan in LDS
+//   resize                              k_image_resize_h / _v                               transposed chunks; row pairs from cache
+//   crop, frame regions, statistics     k_image_crop, k_image_stats, k_image_stats_merge    streaming; a merge of partials
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,6 +19,7 @@
 #include "convolve.hpp"
 #include "displace.hpp"
 #include "distance.hpp"
+#include "image_geometry.hpp"
 #include "launch.hpp"
 #include "lighting.hpp"
 #include "morphology.hpp"
@@ -34,43 +30,14 @@
 
 namespace crh {
 namespace {
-
-constexpr int kBlurSegment = 256; // horizontal: output texels of one row per workgroup, one per lane
-constexpr int kBlurApron = 192;   // CRH_MAX_BLUR_RADIUS: texels staged beyond the segment on either side
-constexpr int kBlurColumns = 64;  // vertical: columns per workgroup, one per lane of a wave
-constexpr int kBlurWaves = 4;     // vertical: waves per workgroup
-constexpr int kBlurRows = 8;      // vertical: output rows per lane
-constexpr int kBlurBlockRows = kBlurWaves * kBlurRows; // vertical: output rows per workgroup
-constexpr int kBlurChunk = 32;    // vertical: intermediate rows staged in LDS at a time
 static_assert(kBlurRows == (int)kBlurTapPad, "a row pair may start one row early: the vertical table holds kBlurTapPad = rows per lane zeros on either side");
-static_assert(kBlurApron == (int)kBlurMaxRadius, "the apron holds the largest radius");
-
-// The image-paint block's wrap(i, n) for edges 1..3 (PAD, REPEAT, REFLECT), any int32 i, 1 <= n <= 16384: -> [0, n).
-// |i| may be many times n (a radius of 192 on a one-texel axis), so REPEAT and REFLECT reduce with a remainder, not a single fold.
-__device__ __forceinline__ int blur_wrap(int i, int n, uint32_t edge) {
-    if ((uint32_t)i < (uint32_t)n) return i; // (inside: every edge agrees)
-    if (edge == 1u) return i < 0 ? 0 : n - 1;
-    const int p = edge == 2u ? n : 2 * n;
-    int k = i % p;
-    if (k < 0) k += p;
-    return k < n ? k : p - 1 - k;
-}
-
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-// (lo.u16[0], hi.u16[0]) and (lo.u16[1], hi.u16[1]) of two words: one v_perm_b32 each
-__device__ __forceinline__ uint32_t low_halves(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x05040100u); }
-__device__ __forceinline__ uint32_t high_halves(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
-// acc + v.u16[0] * q.u16[0] + v.u16[1] * q.u16[1] in 32 bits (v_dot2_u32_u16): two taps of one channel per instruction
-__device__ __forceinline__ uint32_t dot2(uint32_t v, uint32_t q, uint32_t acc) { return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, v), __builtin_bit_cast(u16x2, q), acc, false); }
-
+static_assert(kBlurApron == (int)kBlurMaxRadius && kBlurApron == (int)kVariableBlurMaxRadius, "the apron holds the largest radius of either blur");
 } // namespace
 
 // Horizontal pass. Grid (ceil(out_w / 256), src_h), 256 lanes: the workgroup stages the texels its segment of one row reads — the segment and
-// an apron of radius + 1 on either side, wrapped or zero by the edge — in LDS, each texel unpacked to two words of two 16-bit fields
-// (r | b << 16, g | a << 16); then every lane forms its own output from LDS. Lane l reads the 8 bytes at l + const: consecutive lanes,
-// consecutive banks. The taps are read with a wave-uniform index, so they come through the scalar cache into SGPRs: taps[0] = q[0] as a
-// 32-bit word (65536 when the axis is the identity), taps[1 + p] = q[2 p + 1] | q[2 p + 2] << 16, a pair of 16-bit taps (q[radius + 1] = 0
-// pads an odd radius: hence the apron's extra texel). The sum runs over tap PAIRS, q[k] (c(i - k) + c(i + k)): the two texels are added in
+// an apron of radius + 1 on either side (stage_row) — then every lane forms its own output from LDS. The taps are read with a wave-uniform
+// index, so they come through the scalar cache into SGPRs: taps[0] = q[0] as a 32-bit word (65536 when the axis is the identity),
+// taps[1 + p] = q[2 p + 1] | q[2 p + 2] << 16, a pair of 16-bit taps (q[radius + 1] = 0 pads an odd radius: hence the apron's extra texel). The sum runs over tap PAIRS, q[k] (c(i - k) + c(i + k)): the two texels are added in
 // their 16-bit fields (<= 510), the sums of taps k and k + 1 are regrouped by channel (v_perm_b32) and each channel takes both taps in one
 // v_dot2_u32_u16: 12 vector instructions and four 8-byte LDS reads for 16 multiply-adds.
 //   t = (sum_k q[|k|] c(i + k) + 128) >> 8 per channel, <= 65280; four of them are one 8-byte store.
@@ -81,15 +48,7 @@ __global__ __launch_bounds__(kBlurSegment) void k_image_blur_h(const uint32_t* _
     const uint32_t j = blockIdx.y, o0 = blockIdx.x * (uint32_t)kBlurSegment, lane = threadIdx.x;
     const uint32_t* line = src + (size_t)j * src_w;
     const uint32_t apron = radius + 1u; // (radius <= kBlurApron: the host refuses more)
-    const int first = (int)o0 - (int)origin - (int)apron; // the source column of row[0]
-    for (uint32_t at = lane; at < (uint32_t)kBlurSegment + 2u * apron; at += (uint32_t)kBlurSegment) {
-        const int i = first + (int)at;
-        uint32_t texel = 0u;
-        if (edge != 0u) texel = line[blur_wrap(i, (int)src_w, edge)];
-        else if ((uint32_t)i < src_w) texel = line[i];
-        row[at] = make_uint2(texel & 0x00FF00FFu, (texel >> 8) & 0x00FF00FFu);
-    }
-    __syncthreads();
+    stage_row(row, line, (int)o0 - (int)origin - (int)apron, (uint32_t)kBlurSegment + 2u * apron, src_w, edge);
     const uint32_t o = o0 + lane;
     if (o >= out_w) return;
     const uint32_t centre = lane + apron;
@@ -109,9 +68,8 @@ __global__ __launch_bounds__(kBlurSegment) void k_image_blur_h(const uint32_t* _
 
 // Vertical pass. Grid (ceil(out_w / 64), ceil(out_h / 32)), 4 waves: lanes run along x, so every global and LDS access of a wave is 64
 // consecutive 4- or 8-byte words. The workgroup covers 32 output rows of 64 columns; wave w owns rows 8 w .. 8 w + 7 of them, eight rows per
-// lane in 32 accumulators. The 32 + 2 radius intermediate rows the block reads are staged once, 32 rows (16 KiB) at a time. The staged rows
-// are taken in PAIRS (i, i + 1): a lane reads its 8 bytes of each once, regroups the two rows by channel (four v_perm_b32) and adds the pair
-// to each of its eight rows with one v_dot2_u32_u16 per channel — 36 vector instructions for 64 multiply-adds. `pairs` is the table
+// lane in 32 accumulators. The 32 + 2 radius intermediate rows the block reads are staged once, 32 rows (16 KiB) at a time (stage_chunk). The
+// staged rows are taken in PAIRS (i, i + 1), which a lane adds to each of its eight rows (row_pair, pair_mad). `pairs` is the table
 // F[n] | F[n - 1] << 16 of 16-bit taps, F = the symmetric q[|d|], d = -radius .. radius, between 8 zeros on either side: row i meets output
 // row m with F[8 + 2 radius - (i - lo) + m] and row i + 1 with the word before, so the eight tap pairs of a row pair are eight consecutive
 // words at a wave-uniform index — one scalar load, no branch — and a row outside an output's window meets a zero.
@@ -121,17 +79,15 @@ __global__ __launch_bounds__(kBlurSegment) void k_image_blur_h(const uint32_t* _
 __global__ __launch_bounds__(kBlurColumns * kBlurWaves) void k_image_blur_v(const uint2* __restrict__ tmp, uint32_t tmp_h, uint32_t* __restrict__ out, uint32_t out_w, uint32_t out_h,
                                                                             const uint32_t* __restrict__ pairs, uint32_t radius, uint32_t origin, uint32_t edge) {
     __shared__ uint2 rows[kBlurChunk][kBlurColumns];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, wave = wave_of_workgroup();
     const uint32_t x = blockIdx.x * (uint32_t)kBlurColumns + lane;
     const int block_j0 = (int)(blockIdx.y * (uint32_t)kBlurBlockRows);
     const int j0 = block_j0 + (int)(wave * (uint32_t)kBlurRows); // this wave's first output row
     if (pairs == nullptr) { // the identity: a texel of the intermediate, rounded
         if (x >= out_w) return;
+#pragma unroll
         for (int m = 0; m < kBlurRows && j0 + m < (int)out_h; ++m) {
-            const int i = j0 + m - (int)origin;
-            uint2 t = make_uint2(0u, 0u);
-            if (edge != 0u) t = tmp[(size_t)blur_wrap(i, (int)tmp_h, edge) * out_w + x];
-            else if ((uint32_t)i < tmp_h) t = tmp[(size_t)i * out_w + x];
+            const uint2 t = edge_load<true>(tmp, j0 + m - (int)origin, (int)tmp_h, edge, out_w, x);
             out[(size_t)(j0 + m) * out_w + x] = (((t.x & 0xFFFFu) + 128u) >> 8) | ((((t.x >> 16) + 128u) >> 8) << 8) | ((((t.y & 0xFFFFu) + 128u) >> 8) << 16) | ((((t.y >> 16) + 128u) >> 8) << 24);
         }
         return;
@@ -145,29 +101,15 @@ __global__ __launch_bounds__(kBlurColumns * kBlurWaves) void k_image_blur_v(cons
 #pragma unroll
     for (int m = 0; m < kBlurRows; ++m) acc[m][0] = acc[m][1] = acc[m][2] = acc[m][3] = 0u;
     for (int chunk = block_lo; chunk <= block_hi; chunk += kBlurChunk) {
-        __syncthreads(); // (the rows of the chunk before have been read)
-        for (int s = (int)wave; s < kBlurChunk; s += kBlurWaves) { // every row of the chunk is written: zeros beyond block_hi
-            const int i = chunk + s;
-            uint2 t = make_uint2(0u, 0u);
-            if (x < out_w && i <= block_hi) {
-                if (edge != 0u) t = tmp[(size_t)blur_wrap(i, (int)tmp_h, edge) * out_w + x];
-                else if ((uint32_t)i < tmp_h) t = tmp[(size_t)i * out_w + x];
-            }
-            rows[s][lane] = t;
-        }
-        __syncthreads();
+        stage_chunk(rows, tmp, x, out_w, tmp_h, chunk, block_hi, edge, lane, wave);
         // this wave's rows of the chunk, [from, to], in pairs that start on an even row of the chunk (16 pairs: none leaves it). The pair's
         // first row may be lo - 1 and its second hi + 1: both meet zeros of the table (F's indices run from 0 to 2 R + 16).
         const int from = max(chunk, lo), to = min(min(chunk + kBlurChunk - 1, block_hi), hi); // wave-uniform
         for (int i = chunk + ((from - chunk) & ~1); i <= to; i += 2) {
-            const uint2 t0 = rows[i - chunk][lane], t1 = rows[i + 1 - chunk][lane];
-            const uint32_t rr = low_halves(t0.x, t1.x), gg = high_halves(t0.x, t1.x), bb = low_halves(t0.y, t1.y), aa = high_halves(t0.y, t1.y);
+            const RowPair pair = row_pair(rows[i - chunk][lane], rows[i + 1 - chunk][lane]);
             const uint32_t* q = pairs + (uint32_t)((int)kBlurTapPad + 2 * R - (i - lo)); // ascending in m
 #pragma unroll
-            for (int m = 0; m < kBlurRows; ++m) {
-                const uint32_t qm = q[m];
-                acc[m][0] = dot2(rr, qm, acc[m][0]), acc[m][1] = dot2(gg, qm, acc[m][1]), acc[m][2] = dot2(bb, qm, acc[m][2]), acc[m][3] = dot2(aa, qm, acc[m][3]);
-            }
+            for (int m = 0; m < kBlurRows; ++m) pair_mad(acc[m], pair, q[m]);
         }
     }
     if (x >= out_w) return;
@@ -191,8 +133,6 @@ void launch_image_blur_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint32_
 }
 
 namespace {
-static_assert(kBlurApron == (int)kVariableBlurMaxRadius, "the variable blur's apron holds the largest radius of any level");
-
 // sum_k q[|k|] row[centre + k] over one level's taps, acc = (r, b, g, a): the two texels of a tap are added in their 16-bit fields first.
 // Called with q and R in SGPRs (a wave of one level: the taps come through the scalar cache, the loop does not diverge) or per lane.
 __device__ __forceinline__ void variable_blur_row_sum(const uint2* row, uint32_t centre, const uint32_t* __restrict__ q, uint32_t R, uint32_t acc[4]) {
@@ -226,9 +166,9 @@ __device__ __forceinline__ void variable_blur_column_rows(const uint2 (*rows)[kB
 
 // The same for a wave whose rows all hold ONE level (a mask of one value, the bands of a ramp along y): q = that level's taps and R its
 // radius, in SGPRs. A pair of staged rows (i, i + 1) that lies wholly above the wave's rows, or wholly below them, and within R of all
-// eight, meets them with consecutive taps q[a - 1 .. a + 7], each >= q[1] and so 16 bits wide: the pair is regrouped by channel and
-// added with one v_dot2_u32_u16 per row and channel, k_image_blur_v's inner loop, the tap pairs packed from the scalar loads. The few
-// rows beside or among the wave's own (and an odd one at a run's end) go one at a time as above.
+// eight, meets them with consecutive taps q[a - 1 .. a + 7], each >= q[1] and so 16 bits wide: k_image_blur_v's inner loop (row_pair,
+// pair_mad), the tap pairs packed from the scalar loads. The few rows beside or among the wave's own (and an odd one at a run's end) go
+// one at a time as above.
 __device__ __forceinline__ void variable_blur_column_one_level(const uint2 (*rows)[kBlurColumns], uint32_t lane, int chunk, int from, int to, int j0, const uint32_t* __restrict__ q, int R,
                                                                uint32_t (&acc)[kBlurRows][4]) {
     // the rows [from, to] in five runs, in any order (the sums are exact): [from, a0) one at a time, `na` rows from a0 in pairs above the
@@ -247,52 +187,35 @@ __device__ __forceinline__ void variable_blur_column_one_level(const uint2 (*row
     };
     singles(from, a0 - 1);
     for (int i = a0; i < a0 + na; i += 2) { // row i is j0 - i + m >= 2 from row m, row i + 1 one less; j0 - i + 7 <= R
-        const uint2 t0 = rows[i - chunk][lane], t1 = rows[i + 1 - chunk][lane];
-        const uint32_t rr = low_halves(t0.x, t1.x), gg = high_halves(t0.x, t1.x), bb = low_halves(t0.y, t1.y), aa = high_halves(t0.y, t1.y);
+        const RowPair pair = row_pair(rows[i - chunk][lane], rows[i + 1 - chunk][lane]);
         const uint32_t* p = q + (j0 - i - 1);
 #pragma unroll
-        for (int m = 0; m < kBlurRows; ++m) {
-            const uint32_t pair = p[m + 1] | p[m] << 16;
-            acc[m][0] = dot2(rr, pair, acc[m][0]), acc[m][1] = dot2(gg, pair, acc[m][1]), acc[m][2] = dot2(bb, pair, acc[m][2]), acc[m][3] = dot2(aa, pair, acc[m][3]);
-        }
+        for (int m = 0; m < kBlurRows; ++m) pair_mad(acc[m], pair, p[m + 1] | p[m] << 16);
     }
     singles(a0 + na, b0 - 1);
     for (int i = b0; i < b0 + nb; i += 2) { // row i is i - j0 - m >= 1 from row m, row i + 1 one more; i + 1 - j0 <= R
-        const uint2 t0 = rows[i - chunk][lane], t1 = rows[i + 1 - chunk][lane];
-        const uint32_t rr = low_halves(t0.x, t1.x), gg = high_halves(t0.x, t1.x), bb = low_halves(t0.y, t1.y), aa = high_halves(t0.y, t1.y);
+        const RowPair pair = row_pair(rows[i - chunk][lane], rows[i + 1 - chunk][lane]);
         const uint32_t* p = q + (i - j0 - (kBlurRows - 1));
 #pragma unroll
-        for (int m = 0; m < kBlurRows; ++m) {
-            const uint32_t pair = p[kBlurRows - 1 - m] | p[kBlurRows - m] << 16;
-            acc[m][0] = dot2(rr, pair, acc[m][0]), acc[m][1] = dot2(gg, pair, acc[m][1]), acc[m][2] = dot2(bb, pair, acc[m][2]), acc[m][3] = dot2(aa, pair, acc[m][3]);
-        }
+        for (int m = 0; m < kBlurRows; ++m) pair_mad(acc[m], pair, p[kBlurRows - 1 - m] | p[kBlurRows - m] << 16);
     }
     singles(b0 + nb, to);
 }
 } // namespace
 
 // crh_image_variable_blur, horizontal pass. k_image_blur_h's geometry — grid (ceil(w / 256), h), 256 lanes, the segment and an apron
-// staged in LDS with the edge applied, 8 bytes a texel, lane l reads l + const — but the apron is the CALL's largest radius and every
-// lane sums over its own level's taps: u = the mask's code at the lane's own texel, table[u] = offset << 8 | radius, the taps at
-// table[offset ..]. A wave whose lanes all hold one level (a smooth mask, a ramp along y) takes its taps with a wave-uniform index, as
-// k_image_blur_h does; any other wave loads them per lane and runs to its largest radius. Both give the same sums. The result keeps the
-// source's size under every edge. No mask byte indexes outside the 256 entries; no radius reaches outside the apron (clamped here too).
+// staged in LDS (stage_row) — but the apron is the CALL's largest radius and every lane sums over its own level's taps: u = the mask's
+// code at the lane's own texel, table[u] = offset << 8 | radius, the taps at table[offset ..]. A wave whose lanes all hold one level (a
+// smooth mask, a ramp along y) takes its taps with a wave-uniform index, as k_image_blur_h does; any other wave loads them per lane and
+// runs to its largest radius. Both give the same sums. The result keeps the source's size under every edge. No mask byte indexes outside
+// the 256 entries; no radius reaches outside the apron (clamped here too).
 __global__ __launch_bounds__(kBlurSegment) void k_image_variable_blur_h(const uint32_t* __restrict__ src, const uint32_t* __restrict__ mask, uint32_t w, uint2* __restrict__ tmp,
                                                                          const uint32_t* __restrict__ table, uint32_t apron, uint32_t shift, uint32_t edge) {
     __shared__ uint2 row[kBlurSegment + 2 * kBlurApron];
     const uint32_t j = blockIdx.y, o0 = blockIdx.x * (uint32_t)kBlurSegment, lane = threadIdx.x;
     const uint32_t* line = src + (size_t)j * w;
     apron = min(apron, (uint32_t)kBlurApron);
-    const int first = (int)o0 - (int)apron; // the source column of row[0]
-    for (uint32_t at = lane; at < (uint32_t)kBlurSegment + 2u * apron; at += (uint32_t)kBlurSegment) {
-        const int i = first + (int)at;
-        uint32_t texel = 0u;
-        if (edge != 0u) texel = line[blur_wrap(i, (int)w, edge)];
-        else if ((uint32_t)i < w) texel = line[i];
-        const VariableBlurFields f = variable_blur_split(texel);
-        row[at] = make_uint2(f.x, f.y);
-    }
-    __syncthreads();
+    stage_row(row, line, (int)o0 - (int)apron, (uint32_t)kBlurSegment + 2u * apron, w, edge); // (variable_blur_split's fields)
     const uint32_t o = o0 + lane;
     if (o >= w) return;
     const uint32_t u = variable_blur_level(mask[(size_t)j * w + o], shift);
@@ -311,7 +234,7 @@ __global__ __launch_bounds__(kBlurSegment) void k_image_variable_blur_h(const ui
 
 // crh_image_variable_blur, vertical pass. k_image_blur_v's geometry — grid (ceil(w / 64), ceil(h / 32)), 4 waves, lanes along x, wave
 // w owns output rows 8 w .. 8 w + 7 of the block's 32, eight rows per lane in 32 accumulators; the intermediate rows are staged 32 at
-// a time in LDS with the edge applied. Every (lane, row) has its own level, read from the mask at the output's own texel; the block
+// a time in LDS (stage_chunk). Every (lane, row) has its own level, read from the mask at the output's own texel; the block
 // stages the rows within its largest radius, a wave walks the rows within its own, and a lane's row takes a staged row only within that
 // row's radius. Three tap paths, chosen per wave: one level in the whole wave (a uniform mask, the bands of a ramp along y) takes
 // k_image_blur_v's inner loop on row pairs (variable_blur_column_one_level); one level per row across the lanes reads radii, offsets
@@ -321,7 +244,7 @@ __global__ __launch_bounds__(kBlurColumns * kBlurWaves) void k_image_variable_bl
                                                                                      const uint32_t* __restrict__ table, uint32_t shift, uint32_t edge) {
     __shared__ uint2 rows[kBlurChunk][kBlurColumns];
     __shared__ int wave_radius[kBlurWaves];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, wave = wave_of_workgroup();
     const uint32_t x = blockIdx.x * (uint32_t)kBlurColumns + lane;
     const int block_j0 = (int)(blockIdx.y * (uint32_t)kBlurBlockRows);
     const int j0 = block_j0 + (int)(wave * (uint32_t)kBlurRows); // this wave's first output row
@@ -362,17 +285,7 @@ __global__ __launch_bounds__(kBlurColumns * kBlurWaves) void k_image_variable_bl
     // Every wave of the block runs the same chunks, so the barriers of the three copies pair up whichever copy a wave is in.
     const auto chunks = [&](auto&& accumulate) {
         for (int chunk = block_lo; chunk <= block_hi; chunk += kBlurChunk) {
-            __syncthreads(); // (the rows of the chunk before have been read)
-            for (int s = (int)wave; s < kBlurChunk; s += kBlurWaves) { // every row of the chunk is written: zeros beyond block_hi
-                const int i = chunk + s;
-                uint2 t = make_uint2(0u, 0u);
-                if (x < w && i <= block_hi) {
-                    if (edge != 0u) t = tmp[(size_t)blur_wrap(i, (int)h, edge) * w + x];
-                    else if ((uint32_t)i < h) t = tmp[(size_t)i * w + x];
-                }
-                rows[s][lane] = t;
-            }
-            __syncthreads();
+            stage_chunk(rows, tmp, x, w, h, chunk, block_hi, edge, lane, wave);
             accumulate(chunk, max(chunk, lo), min(min(chunk + kBlurChunk - 1, block_hi), hi)); // [from, to]: wave-uniform, inside the chunk
         }
     };
@@ -398,28 +311,19 @@ void launch_image_variable_blur_v(const void* tmp, const uint32_t* mask, uint32_
     hipLaunchKernelGGL(k_image_variable_blur_v, grid, dim3(kBlurColumns * kBlurWaves), 0, stream, static_cast<const uint2*>(tmp), mask, out, w, h, table, shift, edge);
 }
 
-namespace {
-constexpr int kCompositeLanes = 256;       // lanes per workgroup: one group of V texels of a row each
-constexpr uint32_t kCompositeBlocks = 8192; // the grid's cap: four rounds of 256 CUs x 8 workgroups (measured against 2048 and none: DESIGN.md); the rows beyond it are strided over
-template <int V> struct TexelGroup { typedef uint32_t type __attribute__((ext_vector_type(V))); }; // V texels: one access of 4 V bytes
-} // namespace
-
-// crh_image_composite. Streaming: 4 + 4 bytes read and 4 written per texel. A workgroup owns the row segment blockIdx.x of 256 V texels and
-// strides over the rows blockIdx.y, blockIdx.y + gridDim.y, ...; a lane owns V consecutive texels of it, V = 4, 2 or 1: the most for which
-// every row of the backdrop (and so of the result) starts on a multiple of 4 V bytes, w % V == 0, so that the group is one aligned load
-// and one aligned store and lies wholly inside the row or wholly outside it. The source is shifted by (x, y) against the result: its group
-// is one load of 4 V bytes only where `source_wide` says that its rows and the shift keep it aligned (source_w % V == 0 and x % V == 0:
-// then a group is wholly inside the source or wholly outside, too); otherwise V loads of 4 bytes. Every source address is formed behind
+// crh_image_composite. Streaming (image_geometry.hpp) over the backdrop and the result: 4 + 4 bytes read and 4 written per texel. The source
+// is shifted by (x, y) against the result: its group is one load of 4 V bytes only where `source_wide` says so (stream_wide); otherwise V
+// loads of 4 bytes. Every source address is formed behind
 // the range check, in unsigned arithmetic: i - x and j - y wrap modulo 2^32 for any int32 shift, and the true difference lies in
 // (-2^31 - 1, 2^31 + 16384), so the wrapped value is below the source's size (<= 16384) exactly when the true one is in range.
 // The operator is four wave-uniform integers (composite.hpp CompositeFactors), the mode one branch outside the texel and channel loops.
 template <int V>
-__global__ __launch_bounds__(kCompositeLanes) void k_image_composite(const uint32_t* __restrict__ backdrop, uint32_t w, uint32_t h, const uint32_t* __restrict__ source, uint32_t source_w,
+__global__ __launch_bounds__(kStreamLanes) void k_image_composite(const uint32_t* __restrict__ backdrop, uint32_t w, uint32_t h, const uint32_t* __restrict__ source, uint32_t source_w,
                                                                       uint32_t source_h, uint32_t x, uint32_t y, uint32_t source_wide, uint32_t o, uint32_t mode, CompositeFactors f,
                                                                       uint32_t* __restrict__ out) {
     typedef typename TexelGroup<V>::type Group;
-    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
-    if (i >= w) return; // (w % V == 0 and i % V == 0: the whole group is outside)
+    const uint32_t i = stream_column<V>();
+    if (i >= w) return; // (the whole group is outside)
     const uint32_t si = i - x;
     for (uint32_t j = blockIdx.y; j < h; j += gridDim.y) {
         const size_t at = (size_t)j * w + i;
@@ -446,31 +350,25 @@ __global__ __launch_bounds__(kCompositeLanes) void k_image_composite(const uint3
 
 void launch_image_composite(const uint32_t* backdrop, uint32_t w, uint32_t h, const uint32_t* source, uint32_t source_w, uint32_t source_h, int32_t x, int32_t y, uint32_t o, uint32_t mode,
                             uint32_t op, uint32_t* out, hipStream_t stream) {
-    const uint32_t v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
-    // (uint32_t)x % v is x mod v for a negative x as well: v divides 2^32
-    const uint32_t wide = v > 1u && source_w % v == 0u && (uint32_t)x % v == 0u ? 1u : 0u;
-    const uint32_t segments = (w + (uint32_t)kCompositeLanes * v - 1u) / ((uint32_t)kCompositeLanes * v); // <= 64
-    const dim3 grid(segments, std::min(h, std::max(1u, kCompositeBlocks / segments)));
+    const StreamGrid g = stream_grid(w, h, kStreamBlocks);
+    const uint32_t wide = stream_wide(g.v, source_w, x);
     const CompositeFactors f = composite_factors(op);
-    if (v == 4u) hipLaunchKernelGGL(k_image_composite<4>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, o, mode, f, out);
-    else if (v == 2u) hipLaunchKernelGGL(k_image_composite<2>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, o, mode, f, out);
-    else hipLaunchKernelGGL(k_image_composite<1>, grid, dim3(kCompositeLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, 0u, o, mode, f, out);
+#define CRH_COMPOSITE_LAUNCH(V) hipLaunchKernelGGL(k_image_composite<V>, g.grid, dim3(kStreamLanes), 0, stream, backdrop, w, h, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, o, mode, f, out)
+    CRH_STREAM_DISPATCH(g.v, CRH_COMPOSITE_LAUNCH);
+#undef CRH_COMPOSITE_LAUNCH
 }
 
 namespace {
 __device__ const UnpremultiplyTable k_unpremultiply{}; // color_filter.hpp's reciprocals, staged in LDS by every workgroup of the kernel below
 } // namespace
 
-// crh_image_color_filter. Streaming: 4 bytes read and 4 written per texel, k_image_composite's geometry with one input: a workgroup owns the
-// row segment blockIdx.x of 256 V texels and strides over the rows blockIdx.y, blockIdx.y + gridDim.y, ...; a lane owns V consecutive texels,
-// V = 4, 2 or 1 with w % V == 0, so that its group is one aligned load and one aligned store and lies wholly inside the row or wholly outside
-// it: every address is (row j < h) * w + (column i < w). The 16 coefficients and 4 biases are kernel arguments, wave-uniform (SGPRs); the
+// crh_image_color_filter. Streaming (image_geometry.hpp): 4 bytes read and 4 written per texel. The 16 coefficients and 4 biases are kernel arguments, wave-uniform (SGPRs); the
 // matrix stage is 16 signed 24-bit multiply-adds per texel. The unpremultiply's 256 reciprocals and, with TABLES, the four 256-byte tables
 // (as they are in memory: four byte planes, entry v of channel i at byte 256 i + v) are staged in LDS once per workgroup, one word per lane
 // each, and read per texel with data-dependent indices: one 4-byte read for the alpha's reciprocal, four 1-byte reads for the tables.
 // TABLES = false stages and reads no table and declares no LDS for one.
 template <int V, bool TABLES>
-__global__ __launch_bounds__(kCompositeLanes) void k_image_color_filter(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, ColorFilterCoefficients f,
+__global__ __launch_bounds__(kStreamLanes) void k_image_color_filter(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, ColorFilterCoefficients f,
                                                                          const uint32_t* __restrict__ tables, uint32_t* __restrict__ out) {
     typedef typename TexelGroup<V>::type Group;
     __shared__ uint32_t recip[256];
@@ -478,8 +376,8 @@ __global__ __launch_bounds__(kCompositeLanes) void k_image_color_filter(const ui
     recip[threadIdx.x] = k_unpremultiply.r[threadIdx.x];
     if (TABLES) lut[threadIdx.x] = tables[threadIdx.x];
     __syncthreads();
-    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
-    if (i >= w) return; // (w % V == 0 and i % V == 0: the whole group is outside)
+    const uint32_t i = stream_column<V>();
+    if (i >= w) return; // (the whole group is outside)
     for (uint32_t j = blockIdx.y; j < h; j += gridDim.y) {
         const size_t at = (size_t)j * w + i;
         const Group s = *reinterpret_cast<const Group*>(src + at);
@@ -491,19 +389,10 @@ __global__ __launch_bounds__(kCompositeLanes) void k_image_color_filter(const ui
 }
 
 void launch_image_color_filter(const uint32_t* src, uint32_t w, uint32_t h, const ColorFilterCoefficients& f, const uint32_t* tables, uint32_t* out, hipStream_t stream) {
-    const uint32_t v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
-    const uint32_t segments = (w + (uint32_t)kCompositeLanes * v - 1u) / ((uint32_t)kCompositeLanes * v); // <= 64
-    const dim3 grid(segments, std::min(h, std::max(1u, kCompositeBlocks / segments)));
-#define CRH_COLOR_FILTER_LAUNCH(V, TABLES) hipLaunchKernelGGL((k_image_color_filter<V, TABLES>), grid, dim3(kCompositeLanes), 0, stream, src, w, h, f, tables, out)
-    if (tables) {
-        if (v == 4u) CRH_COLOR_FILTER_LAUNCH(4, true);
-        else if (v == 2u) CRH_COLOR_FILTER_LAUNCH(2, true);
-        else CRH_COLOR_FILTER_LAUNCH(1, true);
-    } else {
-        if (v == 4u) CRH_COLOR_FILTER_LAUNCH(4, false);
-        else if (v == 2u) CRH_COLOR_FILTER_LAUNCH(2, false);
-        else CRH_COLOR_FILTER_LAUNCH(1, false);
-    }
+    const StreamGrid g = stream_grid(w, h, kStreamBlocks);
+#define CRH_COLOR_FILTER_LAUNCH(V, TABLES) hipLaunchKernelGGL((k_image_color_filter<V, TABLES>), g.grid, dim3(kStreamLanes), 0, stream, src, w, h, f, tables, out)
+    if (tables) CRH_STREAM_DISPATCH(g.v, CRH_COLOR_FILTER_LAUNCH, true);
+    else CRH_STREAM_DISPATCH(g.v, CRH_COLOR_FILTER_LAUNCH, false);
 #undef CRH_COLOR_FILTER_LAUNCH
 }
 
@@ -517,7 +406,7 @@ static_assert(kMorphApron == (int)kMorphologyMaxRadius, "the apron holds the lar
 } // namespace
 
 // Horizontal pass, by doubling in LDS. Grid (ceil(out_w / 256), src_h), 256 lanes: the workgroup stages the L = 256 + 2 radius texels its
-// segment of one row reads, wrapped or zero by the edge, each split into two words of two 16-bit fields (morphology.hpp). Lane l owns the
+// segment of one row reads, each split into two words of two 16-bit fields (morphology.hpp), by edge.hpp's rule. Lane l owns the
 // staged texels l, l + 256 and l + 512 and keeps them in registers. Step k turns m_k[i], the extreme of the 2^k texels from i on, into
 // m_{k+1}[i] = op(m_k[i], m_k[i + 2^k]): per owned texel one 8-byte LDS read at lane + const (consecutive lanes, consecutive banks), two
 // v_pk_min_u16 / v_pk_max_u16 and one 8-byte write into the other of two buffers, so a step needs one barrier. After p = floor(log2(2 radius + 1))
@@ -539,12 +428,7 @@ __global__ __launch_bounds__(kMorphSegment) void k_image_morph_h(const uint32_t*
     for (int t = 0; t < kMorphOwned; ++t) {
         const uint32_t at = lane + (uint32_t)(t * kMorphSegment);
         const int i = first + (int)at;
-        uint32_t texel = 0u;
-        if (at < staged) {
-            if (edge != 0u) texel = line[morphology_wrap(i, (int)src_w, edge)];
-            else if ((uint32_t)i < src_w) texel = line[i];
-        }
-        own[t] = morphology_split(texel);
+        own[t] = morphology_split(at < staged ? edge_load(line, i, (int)src_w, edge) : 0u);
         if (at < staged) spans[0][at] = make_uint2(own[t].rb, own[t].ga);
     }
     __syncthreads();
@@ -577,7 +461,7 @@ __global__ __launch_bounds__(kMorphSegment) void k_image_morph_h(const uint32_t*
 // v_pk_min_u16 / v_pk_max_u16), one LDS write and one LDS read per texel at every radius. ROWS = the rows of S the LDS holds, >= W (the launcher picks
 // the smallest of three instantiations, so a small radius does not pay the LDS of the largest). `in` has in_h rows of out_w texels;
 // `origin`: the input row under output row 0 is -origin. The row index is wave-uniform: the wrap is scalar arithmetic, and its one remainder is
-// taken at the pivot (morphology.hpp's phase). radius >= 1.
+// taken at the pivot (edge.hpp's phase). radius >= 1.
 template <bool DILATE, int ROWS>
 __global__ __launch_bounds__(kMorphColumns) void k_image_morph_v(const uint32_t* __restrict__ in, uint32_t in_h, uint32_t* __restrict__ out, uint32_t out_w, uint32_t out_h, uint32_t radius,
                                                                   uint32_t origin, uint32_t edge) {
@@ -590,21 +474,17 @@ __global__ __launch_bounds__(kMorphColumns) void k_image_morph_v(const uint32_t*
     const int c = (int)j0 - (int)origin + (int)radius;
     if (x >= out_w) return; // (no barrier below: a lane shares nothing with its neighbours)
     const uint32_t* column = in + x;
-    const int n = (int)in_h, period = morphology_period(n, edge);
-    // Row i of the lane's column, (0, 0, 0, 0) outside the image under TRANSPARENT: the address comes from the wrapped (or, for TRANSPARENT,
-    // clamped) row in every case and the load is unconditional, so the loads of an unrolled stretch are in flight together.
-    auto texel_of = [&](int i, int phase) {
-        const uint32_t texel = column[(size_t)morphology_wrap_at(i, phase, n, edge) * out_w];
-        return morphology_split(edge == 0u && (uint32_t)i >= in_h ? 0u : texel);
-    };
-    const int phase_c = morphology_phase(c, n, edge); // the walk's one division; from here the phase moves by one with the row
+    const int n = (int)in_h, period = edge_period(n, edge);
+    // Row i of the lane's column, (0, 0, 0, 0) outside the image under TRANSPARENT, by an unconditional load
+    auto texel_of = [&](int i, int phase) { return morphology_split(edge_load_select(column, i, phase, n, edge, out_w)); };
+    const int phase_c = edge_phase(c, n, edge); // the walk's one division; from here the phase moves by one with the row
     const MorphologyTexel centre = texel_of(c, phase_c);
     MorphologyTexel s = centre;
     suffix[0][lane] = morphology_merge(s);
     int phase = phase_c;
 #pragma unroll kAhead
     for (uint32_t k = 1u; k <= reach; ++k) {
-        phase = morphology_phase_before(phase, period);
+        phase = edge_phase_before(phase, period);
         s = morphology_extreme<DILATE>(s, texel_of(c - (int)k, phase));
         suffix[k][lane] = morphology_merge(s);
     }
@@ -614,7 +494,7 @@ __global__ __launch_bounds__(kMorphColumns) void k_image_morph_v(const uint32_t*
     phase = phase_c;
 #pragma unroll kAhead
     for (uint32_t m = 1u; m < rows; ++m) {
-        phase = morphology_phase_next(phase, period);
+        phase = edge_phase_next(phase, period);
         p = morphology_extreme<DILATE>(p, texel_of(c + (int)m, phase));
         out[(size_t)(j0 + m) * out_w + x] = morphology_merge(morphology_extreme<DILATE>(p, morphology_split(suffix[reach - m][lane])));
     }
@@ -643,16 +523,14 @@ void launch_image_morph_v(const uint32_t* in, uint32_t in_h, uint32_t* out, uint
 }
 
 namespace {
-constexpr int kConvolveTileW = 64;  // output columns per workgroup, one per lane of a wave
-constexpr int kConvolveWaves = 4;   // waves per workgroup
 #ifndef CRH_CONVOLVE_ROWS
 #define CRH_CONVOLVE_ROWS 4 // (a build with -DCRH_CONVOLVE_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the register blocking was measured)
 #endif
-constexpr int kConvolveRows = CRH_CONVOLVE_ROWS; // adjacent output rows per lane: a staged texel's bytes are extracted once for all of them
-constexpr int kConvolveTileH = kConvolveWaves * kConvolveRows;      // 16 output rows per workgroup
-constexpr int kConvolveHalo = (int)kConvolveMaxOrder - 1;           // 14: the most texels staged beyond the tile per axis
-constexpr int kConvolvePitch = kConvolveTileW + kConvolveHalo;      // 78 words per staged row
-constexpr int kConvolveStagedRows = kConvolveTileH + kConvolveHalo; // 30
+typedef Tile<CRH_CONVOLVE_ROWS> ConvolveTile; // adjacent output rows per lane: a staged texel's bytes are extracted once for all of them
+constexpr int kConvolveRows = ConvolveTile::Rows;
+constexpr int kConvolveHalo = (int)kConvolveMaxOrder - 1;              // 14: the most texels staged beyond the tile per axis
+constexpr int kConvolvePitch = ConvolveTile::W + kConvolveHalo;        // 78 words per staged row
+constexpr int kConvolveStagedRows = ConvolveTile::H + kConvolveHalo;   // 30
 constexpr int kConvolveTapRows = (int)kConvolveMaxOrder + 2 * (kConvolveRows - 1); // 21: the kernel's rows between kConvolveRows - 1 rows of zeros
 
 // The kernel matrix as k_image_convolve reads it: rotated, so that k[(dy + kConvolveRows - 1) * 15 + dx] multiplies the window's texel
@@ -664,20 +542,17 @@ struct ConvolveTaps {
 };
 } // namespace
 
-// crh_image_convolve: a 2-D stencil. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the workgroup produces the tile of 64 x 16 texels at
-// (i0, j0). It stages the (64 + order_x - 1) x (16 + order_y - 1) source texels its windows read in LDS, once: wave v takes the staged rows
-// v, v + 4, ... (a wave-uniform row: its wrap is scalar arithmetic), a lane the staged columns lane and lane + 64, whose wrap it computes
-// once; the edge rule (morphology.hpp's wrap, or zero under TRANSPARENT) and the load stage (the clamp to alpha and, with PRESERVE, the
-// unpremultiply) are applied here, so the tap loop has no wrap, no clamp and no division. Every source address is a wrapped or clamped row
-// below h times w plus a wrapped or clamped column below w. Then lane l of wave v produces the four outputs of column l, tile rows
-// 4 v .. 4 v + 3: for each of the order_y + 3 staged rows under them and each kernel column it reads one word at lane + const (consecutive
-// lanes, consecutive banks: no conflict at the pitch of 78), extracts its bytes once and adds it into the four outputs' sums with the
-// coefficients of four rows of the padded table — 16 (with PRESERVE, 12) signed 24-bit multiply-adds per read. The coefficients are a
-// kernel argument and every index into them is wave-uniform: scalar loads, scalar operands. LDS: 9360 B (+ 1 KiB of reciprocals with
-// PRESERVE), so registers and the 32-wave cap, not LDS, bound the occupancy. LDS indices: row 4 v + q <= 12 + order_y + 2 =
-// (16 + order_y - 1) - 1, column l + dx <= 63 + order_x - 1 <= 77.
+// crh_image_convolve: a 2-D stencil on a tile of 64 x 16 texels (image_geometry.hpp: Tile). The workgroup stages the (64 + order_x - 1) x
+// (16 + order_y - 1) source texels its windows read in LDS, once (stage_tile); the load stage (the clamp to alpha and, with PRESERVE, the
+// unpremultiply) is applied there, so the tap loop has no wrap, no clamp and no division. Then lane l of wave v produces the four outputs
+// of column l, tile rows 4 v .. 4 v + 3: for each of the order_y + 3 staged rows under them and each kernel column it reads one word at
+// lane + const (consecutive lanes, consecutive banks: no conflict at the pitch of 78), extracts its bytes once and adds it into the four
+// outputs' sums with the coefficients of four rows of the padded table — 16 (with PRESERVE, 12) signed 24-bit multiply-adds per read. The
+// coefficients are a kernel argument and every index into them is wave-uniform: scalar loads, scalar operands. LDS: 9360 B (+ 1 KiB of
+// reciprocals with PRESERVE), so registers and the 32-wave cap, not LDS, bound the occupancy. LDS indices: row 4 v + q <= 12 + order_y + 2
+// = (16 + order_y - 1) - 1, column l + dx <= 63 + order_x - 1 <= 77.
 template <bool PRESERVE>
-__global__ __launch_bounds__(kConvolveTileW* kConvolveWaves) void k_image_convolve(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, ConvolveTaps taps, uint32_t order_x, uint32_t order_y,
+__global__ __launch_bounds__(ConvolveTile::Lanes) void k_image_convolve(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, ConvolveTaps taps, uint32_t order_x, uint32_t order_y,
                                                                                     uint32_t target_x, uint32_t target_y, uint32_t edge, uint32_t* __restrict__ out) {
     __shared__ uint32_t staged[kConvolveStagedRows * kConvolvePitch];
     __shared__ uint32_t recip[PRESERVE ? 256 : 1];
@@ -685,32 +560,12 @@ __global__ __launch_bounds__(kConvolveTileW* kConvolveWaves) void k_image_convol
         recip[threadIdx.x] = k_unpremultiply.r[threadIdx.x];
         __syncthreads();
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int i0 = (int)(blockIdx.x * (uint32_t)kConvolveTileW), j0 = (int)(blockIdx.y * (uint32_t)kConvolveTileH);
-    const uint32_t staged_w = (uint32_t)kConvolveTileW + order_x - 1u, staged_h = (uint32_t)kConvolveTileH + order_y - 1u; // (orders <= 15: the host refuses more)
-    int column[2];
-    bool inside[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int x = i0 - (int)target_x + (int)lane + t * kConvolveTileW; // the source column of staged column lane + 64 t
-        column[t] = morphology_wrap(x, (int)w, edge);                      // (under TRANSPARENT: clamped, an address the lane may read)
-        inside[t] = edge != kConvolveTransparent || (uint32_t)x < w;
-    }
-    for (uint32_t q = wave; q < staged_h; q += (uint32_t)kConvolveWaves) {
-        const int y = j0 - (int)target_y + (int)q;
-        const uint32_t* line = src + (size_t)morphology_wrap(y, (int)h, edge) * w;
-        const bool row_inside = edge != kConvolveTransparent || (uint32_t)y < h;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const uint32_t s = lane + (uint32_t)(t * kConvolveTileW);
-            if (s < staged_w) {
-                const uint32_t texel = line[column[t]];
-                staged[q * (uint32_t)kConvolvePitch + s] = convolve_load<PRESERVE>(row_inside && inside[t] ? texel : 0u, recip);
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t y0 = wave * (uint32_t)kConvolveRows; // the tile row of the lane's first output
+    const ConvolveTile tile;
+    const uint32_t lane = tile.lane;
+    const int i0 = (int)tile.i0, j0 = (int)tile.j0; // (below: orders <= 15, the host refuses more)
+    stage_tile<kConvolvePitch>(staged, (uint32_t)ConvolveTile::W + order_x - 1u, (uint32_t)ConvolveTile::H + order_y - 1u, src, i0 - (int)target_x, j0 - (int)target_y, w, h, edge, lane,
+                               tile.wave, [&](uint32_t texel) { return convolve_load<PRESERVE>(texel, recip); });
+    const uint32_t y0 = tile.wave * (uint32_t)kConvolveRows; // the tile row of the lane's first output
     int32_t n[kConvolveRows][4];
 #pragma unroll
     for (int b = 0; b < kConvolveRows; ++b)
@@ -743,33 +598,27 @@ void launch_image_convolve(const uint32_t* src, uint32_t w, uint32_t h, const Co
         for (uint32_t dx = 0; dx < order_x; ++dx)
             taps.k[(dy + (uint32_t)(kConvolveRows - 1)) * kConvolveMaxOrder + dx] = f.k[(order_y - 1u - dy) * order_x + (order_x - 1u - dx)];
     taps.bias = f.bias;
-    const dim3 grid((w + (uint32_t)kConvolveTileW - 1u) / (uint32_t)kConvolveTileW, (h + (uint32_t)kConvolveTileH - 1u) / (uint32_t)kConvolveTileH); // <= 256 x 1024
-    const dim3 block(kConvolveTileW * kConvolveWaves);
+    const dim3 grid = ConvolveTile::grid(w, h), block(ConvolveTile::Lanes);
     if (preserve_alpha) hipLaunchKernelGGL(k_image_convolve<true>, grid, block, 0, stream, src, w, h, taps, order_x, order_y, target_x, target_y, edge, out);
     else hipLaunchKernelGGL(k_image_convolve<false>, grid, block, 0, stream, src, w, h, taps, order_x, order_y, target_x, target_y, edge, out);
 }
 
 namespace {
-constexpr int kLightingTileW = 64; // output columns per workgroup, one per lane of a wave
-constexpr int kLightingWaves = 4;  // waves per workgroup
 #ifndef CRH_LIGHTING_ROWS
 #define CRH_LIGHTING_ROWS 4 // (a build with -DCRH_LIGHTING_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the row blocking was measured)
 #endif
 #ifndef CRH_LIGHTING_FLAT_SKIP
 #define CRH_LIGHTING_FLAT_SKIP 1 // (-DCRH_LIGHTING_FLAT_SKIP=0: a distant light's arithmetic on every texel, the comparison of DESIGN.md)
 #endif
-constexpr int kLightingRows = CRH_LIGHTING_ROWS;                   // adjacent output rows per lane: the column sums of a staged row serve three of them
-constexpr int kLightingTileH = kLightingWaves * kLightingRows;     // 16 output rows per workgroup
-constexpr int kLightingPitch = kLightingTileW + 2;                 // 66 words per staged row: the tile and one texel of halo on each side
-constexpr int kLightingStagedRows = kLightingTileH + 2;            // 18
+typedef Tile<CRH_LIGHTING_ROWS> LightingTile; // adjacent output rows per lane: the column sums of a staged row serve three of them
+constexpr int kLightingRows = LightingTile::Rows;
+constexpr int kLightingPitch = LightingTile::W + 2;      // 66 words per staged row: the tile and one texel of halo on each side
+constexpr int kLightingStagedRows = LightingTile::H + 2; // 18
 } // namespace
 
-// crh_image_lighting: a 3 x 3 stencil on the alpha channel under binary64 arithmetic. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the
-// workgroup produces the tile of 64 x 16 texels at (i0, j0). It stages the 66 x 18 alpha codes its gradients read in LDS, one word each,
-// once: wave v takes the staged rows v, v + 4, ... (a wave-uniform row: its wrap is scalar arithmetic), a lane the staged columns lane and
-// (lanes 0 and 1) lane + 64, whose wrap it computes once; the edge rule (morphology.hpp's wrap, or zero under TRANSPARENT) is applied here,
-// so the arithmetic never branches on position. Only the alpha byte of a source texel is loaded (one byte load at texel * 4 + 3). Every
-// source address is a wrapped or clamped row below h times w plus a wrapped or clamped column below w. Then lane l of wave v produces the
+// crh_image_lighting: a 3 x 3 stencil on the alpha channel under binary64 arithmetic, on a tile of 64 x 16 texels (image_geometry.hpp:
+// Tile). The workgroup stages the 66 x 18 alpha codes its gradients read in LDS, one word each, once (stage_tile), so the arithmetic never
+// branches on position. Only the alpha byte of a source texel is loaded (one byte load at texel * 4 + 3). Then lane l of wave v produces the
 // four outputs of column l, tile rows 4 v .. 4 v + 3, walking down the staged rows 4 v .. 4 v + 5: of each it reads the three codes at lane,
 // lane + 1, lane + 2 (consecutive lanes, consecutive banks: no conflict at the pitch of 66) and keeps their difference (right - left) and
 // their sum (left + 2 mid + right) for the three output rows that use them, so an output costs 3 LDS reads, not 9. gx and gy are integer
@@ -778,34 +627,14 @@ constexpr int kLightingStagedRows = kLightingTileH + 2;            // 18
 // the host computed with the same function (f.flat); a wave in which every lane does skips the arithmetic. LDS: 4752 B, so registers and
 // the 32-wave cap, not LDS, bound the occupancy. LDS indices: row 4 v + b + 2 <= 12 + 3 + 2 = 17, column l + 2 <= 65.
 template <uint32_t OP, uint32_t LIGHT>
-__global__ __launch_bounds__(kLightingTileW* kLightingWaves) void k_image_lighting(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, LightingConstants f, uint32_t edge,
+__global__ __launch_bounds__(LightingTile::Lanes) void k_image_lighting(const uint8_t* __restrict__ src, uint32_t w, uint32_t h, LightingConstants f, uint32_t edge,
                                                                                     uint32_t* __restrict__ out) {
     __shared__ uint32_t staged[kLightingStagedRows * kLightingPitch];
-    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int i0 = (int)(blockIdx.x * (uint32_t)kLightingTileW), j0 = (int)(blockIdx.y * (uint32_t)kLightingTileH);
-    int column[2];
-    bool inside[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int x = i0 - 1 + (int)lane + t * kLightingTileW; // the source column of staged column lane + 64 t
-        column[t] = morphology_wrap(x, (int)w, edge);           // (under TRANSPARENT: clamped, an address the lane may read)
-        inside[t] = edge != kLightingTransparent || (uint32_t)x < w;
-    }
-    for (uint32_t q = wave; q < (uint32_t)kLightingStagedRows; q += (uint32_t)kLightingWaves) {
-        const int y = j0 - 1 + (int)q;
-        const uint8_t* line = src + (size_t)morphology_wrap(y, (int)h, edge) * w * 4u;
-        const bool row_inside = edge != kLightingTransparent || (uint32_t)y < h;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const uint32_t s = lane + (uint32_t)(t * kLightingTileW);
-            if (s < (uint32_t)kLightingPitch) {
-                const uint32_t alpha = line[(size_t)column[t] * 4u + 3u];
-                staged[q * (uint32_t)kLightingPitch + s] = row_inside && inside[t] ? alpha : 0u;
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t y0 = wave * (uint32_t)kLightingRows; // the tile row of the lane's first output
+    const LightingTile tile;
+    const uint32_t lane = tile.lane;
+    const int i0 = (int)tile.i0, j0 = (int)tile.j0;
+    stage_tile<kLightingPitch>(staged, (uint32_t)kLightingPitch, (uint32_t)kLightingStagedRows, src, i0 - 1, j0 - 1, w, h, edge, lane, tile.wave, [](uint32_t alpha) { return alpha; });
+    const uint32_t y0 = tile.wave * (uint32_t)kLightingRows; // the tile row of the lane's first output
     const uint32_t i = (uint32_t)i0 + lane;
     // the staged rows above and on the first output: their differences, sums and the code under the output
     const uint32_t* line = staged + y0 * (uint32_t)kLightingPitch + lane;
@@ -831,8 +660,7 @@ __global__ __launch_bounds__(kLightingTileW* kLightingWaves) void k_image_lighti
 }
 
 void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const LightingConstants& f, uint32_t op, uint32_t light, uint32_t edge, uint32_t* out, hipStream_t stream) {
-    const dim3 grid((w + (uint32_t)kLightingTileW - 1u) / (uint32_t)kLightingTileW, (h + (uint32_t)kLightingTileH - 1u) / (uint32_t)kLightingTileH); // <= 256 x 1024
-    const dim3 block(kLightingTileW * kLightingWaves);
+    const dim3 grid = LightingTile::grid(w, h), block(LightingTile::Lanes);
     const uint8_t* bytes = reinterpret_cast<const uint8_t*>(src);
 #define CRH_LIGHTING_LAUNCH(OP, LIGHT) hipLaunchKernelGGL((k_image_lighting<OP, LIGHT>), grid, block, 0, stream, bytes, w, h, f, edge, out)
     if (op == kLightingDiffuse) {
@@ -848,17 +676,15 @@ void launch_image_lighting(const uint32_t* src, uint32_t w, uint32_t h, const Li
 }
 
 namespace {
-constexpr int kTurbulenceTileW = 64; // output columns per workgroup, one per lane of a wave
-constexpr int kTurbulenceWaves = 4;  // waves per workgroup
 #ifndef CRH_TURBULENCE_ROWS
 #define CRH_TURBULENCE_ROWS 4 // (a build with -DCRH_TURBULENCE_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the row blocking is measured)
 #endif
-constexpr int kTurbulenceRows = CRH_TURBULENCE_ROWS;                   // adjacent output rows per lane: one column half serves them all
-constexpr int kTurbulenceTileH = kTurbulenceWaves * kTurbulenceRows;   // 16 output rows per workgroup
+typedef Tile<CRH_TURBULENCE_ROWS> TurbulenceTile; // adjacent output rows per lane: one column half serves them all
+constexpr int kTurbulenceRows = TurbulenceTile::Rows;
 } // namespace
 
-// crh_image_turbulence: procedural noise, bound by binary64 arithmetic and LDS gathers. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the
-// workgroup produces the tile of 64 x 16 texels at (i0, j0). It first copies the call's tables into LDS: the gradients of the channels it
+// crh_image_turbulence: procedural noise, bound by binary64 arithmetic and LDS gathers, on a tile of 64 x 16 texels (image_geometry.hpp:
+// Tile). The workgroup first copies the call's tables into LDS: the gradients of the channels it
 // evaluates, 16 bytes per (channel, lattice value) — 16 KB, or 12 KB when OPAQUE — and the 256 lattice bytes; lane t copies entry t of
 // every channel and (the first wave) word t of the lattice. Then lane l of wave v produces the four outputs of column l, tile rows
 // 4 v .. 4 v + 3. The octaves are the outer loop: per octave the lane computes its column's half of the cell once (floor, fractions,
@@ -869,12 +695,13 @@ constexpr int kTurbulenceTileH = kTurbulenceWaves * kTurbulenceRows;   // 16 out
 // every LDS index is masked to 8 bits — and does not store. Periods, their reciprocals and the ratio of octave o are the kernel
 // arguments of octave 0 shifted or halved o times, which is exact. The specialisation without STITCH carries no wrap at all.
 template <uint32_t KIND, bool OPAQUE, bool STITCH>
-__global__ __launch_bounds__(kTurbulenceTileW* kTurbulenceWaves) void k_image_turbulence(const TurbulenceTables* __restrict__ tables, uint32_t w, uint32_t h, TurbulenceConstants f,
+__global__ __launch_bounds__(TurbulenceTile::Lanes) void k_image_turbulence(const TurbulenceTables* __restrict__ tables, uint32_t w, uint32_t h, TurbulenceConstants f,
                                                                                           uint32_t* __restrict__ out) {
     constexpr int CH = OPAQUE ? 3 : 4;
     __shared__ __attribute__((aligned(16))) double gradient[CH * 512];
     __shared__ __attribute__((aligned(16))) uint8_t lattice[256];
-    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const TurbulenceTile tile;
+    const uint32_t lane = tile.lane, wave = tile.wave;
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
         const uint32_t e = ((uint32_t)k * 256u + threadIdx.x) * 2u;
@@ -882,8 +709,7 @@ __global__ __launch_bounds__(kTurbulenceTileW* kTurbulenceWaves) void k_image_tu
     }
     if (wave == 0u) reinterpret_cast<uint32_t*>(lattice)[lane] = reinterpret_cast<const uint32_t*>(tables->lattice)[lane];
     __syncthreads();
-    const uint32_t i = blockIdx.x * (uint32_t)kTurbulenceTileW + lane;
-    const uint32_t j0 = blockIdx.y * (uint32_t)kTurbulenceTileH + wave * (uint32_t)kTurbulenceRows;
+    const uint32_t i = tile.column(), j0 = tile.row();
     double vx = (f.ox + (double)i) * f.fx, vy[kTurbulenceRows];
 #pragma unroll
     for (int b = 0; b < kTurbulenceRows; ++b) vy[b] = (f.oy + (double)(j0 + (uint32_t)b)) * f.fy;
@@ -913,8 +739,7 @@ __global__ __launch_bounds__(kTurbulenceTileW* kTurbulenceWaves) void k_image_tu
 }
 
 void launch_image_turbulence(const TurbulenceTables* tables, uint32_t w, uint32_t h, const TurbulenceConstants& f, uint32_t kind, bool opaque, uint32_t* out, hipStream_t stream) {
-    const dim3 grid((w + (uint32_t)kTurbulenceTileW - 1u) / (uint32_t)kTurbulenceTileW, (h + (uint32_t)kTurbulenceTileH - 1u) / (uint32_t)kTurbulenceTileH); // <= 256 x 1024
-    const dim3 block(kTurbulenceTileW * kTurbulenceWaves);
+    const dim3 grid = TurbulenceTile::grid(w, h), block(TurbulenceTile::Lanes);
     const bool stitch = f.px != 0 || f.py != 0;
 #define CRH_TURBULENCE_LAUNCH(KIND, OPAQUE)                                                                                                 \
     do {                                                                                                                                    \
@@ -932,17 +757,15 @@ void launch_image_turbulence(const TurbulenceTables* tables, uint32_t w, uint32_
 }
 
 namespace {
-constexpr int kDisplaceTileW = 64; // output columns per workgroup, one per lane of a wave
-constexpr int kDisplaceWaves = 4;  // waves per workgroup
 #ifndef CRH_DISPLACE_ROWS
 #define CRH_DISPLACE_ROWS 4 // (a build with -DCRH_DISPLACE_ROWS=1, 2 or 8 is how DESIGN.md's comparison of the row blocking is measured)
 #endif
 #ifndef CRH_DISPLACE_EDGE_TEMPLATE
 #define CRH_DISPLACE_EDGE_TEMPLATE 0 // (a build with -DCRH_DISPLACE_EDGE_TEMPLATE=1 instantiates the kernel per wrapping edge: DESIGN.md's comparison)
 #endif
-constexpr int kDisplaceRows = CRH_DISPLACE_ROWS;                  // adjacent output rows per lane: their fetches are in flight together
-constexpr int kDisplaceTileH = kDisplaceWaves * kDisplaceRows;   // 16 output rows per workgroup
-constexpr uint32_t kDisplaceRuntimeEdge = 4;                     // EDGE of the kernel that takes its wrapping edge (1..3) from the constants
+typedef Tile<CRH_DISPLACE_ROWS> DisplaceTile; // adjacent output rows per lane: their fetches are in flight together
+constexpr int kDisplaceRows = DisplaceTile::Rows;
+constexpr uint32_t kDisplaceRuntimeEdge = 4; // EDGE of the kernel that takes its wrapping edge (1..3) from the constants
 
 // One index of a tap against its axis of n texels -> an index the lane may read, and whether the tap is the source's texel there: always
 // under a wrapping edge; under TRANSPARENT the index is clamped and the test says whether the value counts.
@@ -950,25 +773,24 @@ template <bool WRAPPED>
 __device__ __forceinline__ uint32_t displace_index(int i, int n, uint32_t edge, bool* inside) {
     if (WRAPPED) {
         *inside = true;
-        return (uint32_t)blur_wrap(i, n, edge);
+        return (uint32_t)edge_wrap_branching(i, n, edge);
     }
     *inside = (uint32_t)i < (uint32_t)n;
     return (uint32_t)(i < 0 ? 0 : i >= n ? n - 1 : i);
 }
 } // namespace
 
-// crh_image_displace: a data-dependent gather, bound by the latency of its fetches. Grid (ceil(w / 64), ceil(h / 16)), 256 lanes: the
-// workgroup produces the tile of 64 x 16 texels at (i0, j0); lane l of wave v the four outputs of column l, tile rows 4 v .. 4 v + 3, so
+// crh_image_displace: a data-dependent gather, bound by the latency of its fetches, on a tile of 64 x 16 texels (image_geometry.hpp: Tile):
 // a wave's map load and its store are 256 contiguous bytes per instruction and only the source read is a gather. No halo can be staged:
 // an offset reaches 512 texels either way. A lane works in four steps so that its loads are in flight together: (1) the map texels of
 // its rows; (2) per row the offsets by displace.hpp's rule (the unpremultiply's 256 reciprocals are in LDS, one word staged per lane),
-// the taps, and for each tap a texel index formed ONLY from wrapped (blur_wrap) or clamped indices, with under TRANSPARENT a bit that
+// the taps, and for each tap a texel index formed ONLY from wrapped (edge_wrap_branching) or clamped indices, with under TRANSPARENT a bit that
 // says whether the tap lies inside; (3) all fetches, 4 per row under LINEAR and 1 under NEAREST — 16 or 4 loads issued before the first
 // is consumed; (4) the taps outside zeroed, the blend, the store. A lane outside the image reads the map's last column or row, computes
 // like any other and does not store. Every index is below w h <= 2^28. EDGE = 0 is TRANSPARENT, 1..3 a wrapping edge as a constant,
-// kDisplaceRuntimeEdge the wrapping edge of the constants (wave-uniform: blur_wrap branches on an SGPR).
+// kDisplaceRuntimeEdge the wrapping edge of the constants (wave-uniform: the wrap branches on an SGPR).
 template <uint32_t FILTER, uint32_t EDGE>
-__global__ __launch_bounds__(kDisplaceTileW* kDisplaceWaves) void k_image_displace(const uint32_t* __restrict__ src, const uint32_t* __restrict__ map, uint32_t w, uint32_t h, DisplaceConstants f,
+__global__ __launch_bounds__(DisplaceTile::Lanes) void k_image_displace(const uint32_t* __restrict__ src, const uint32_t* __restrict__ map, uint32_t w, uint32_t h, DisplaceConstants f,
                                                                                     uint32_t* __restrict__ out) {
     constexpr int TAPS = FILTER == kDisplaceLinear ? 4 : 1;
     constexpr bool WRAPPED = EDGE != kDisplaceTransparent;
@@ -976,9 +798,8 @@ __global__ __launch_bounds__(kDisplaceTileW* kDisplaceWaves) void k_image_displa
     recip[threadIdx.x] = k_unpremultiply.r[threadIdx.x];
     __syncthreads();
     const uint32_t edge = EDGE == kDisplaceRuntimeEdge ? f.edge : EDGE;
-    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t i = blockIdx.x * (uint32_t)kDisplaceTileW + lane;
-    const uint32_t j0 = blockIdx.y * (uint32_t)kDisplaceTileH + wave * (uint32_t)kDisplaceRows;
+    const DisplaceTile tile;
+    const uint32_t i = tile.column(), j0 = tile.row();
     const uint32_t column = i < w ? i : w - 1u;
     uint32_t m[kDisplaceRows];
 #pragma unroll
@@ -1021,8 +842,7 @@ __global__ __launch_bounds__(kDisplaceTileW* kDisplaceWaves) void k_image_displa
 }
 
 void launch_image_displace(const uint32_t* src, const uint32_t* map, uint32_t w, uint32_t h, const DisplaceConstants& f, uint32_t* out, hipStream_t stream) {
-    const dim3 grid((w + (uint32_t)kDisplaceTileW - 1u) / (uint32_t)kDisplaceTileW, (h + (uint32_t)kDisplaceTileH - 1u) / (uint32_t)kDisplaceTileH); // <= 256 x 1024 with four rows per lane
-    const dim3 block(kDisplaceTileW * kDisplaceWaves);
+    const dim3 grid = DisplaceTile::grid(w, h), block(DisplaceTile::Lanes);
 #define CRH_DISPLACE_LAUNCH(EDGE)                                                                                                              \
     do {                                                                                                                                       \
         if (f.filter == kDisplaceLinear) hipLaunchKernelGGL((k_image_displace<kDisplaceLinear, EDGE>), grid, block, 0, stream, src, map, w, h, f, out); \
@@ -1056,7 +876,7 @@ static_assert(kDistanceApron == (int)kDistanceMaxSpread, "the apron holds the la
 // first row, counting again, over its own rows from the LDS bytes alone: g is the smaller of the two counts. ROWS + 2 (spread - 1) rows
 // read for ROWS outputs, at any ROWS; the launcher takes 32 rows for spreads up to 16 and 128 above. `origin`: the source texel
 // under result texel (0, 0) is (-origin, -origin) (the spread for a growing result, else 0). The row index is wave-uniform: the wrap is
-// scalar arithmetic, its one remainder per walk is taken at the walk's first row (morphology.hpp's phase), and the address always comes
+// scalar arithmetic, its one remainder per walk is taken at the walk's first row (edge.hpp's phase), and the address always comes
 // from a wrapped or clamped row and column, so the loads of an unrolled stretch are unconditional and in flight together.
 template <bool INSIDE, int ROWS>
 __global__ __launch_bounds__(kDistanceColumns) void k_image_distance_v(const uint32_t* __restrict__ src, uint32_t src_w, uint32_t src_h, uint8_t* __restrict__ g, uint32_t out_w, uint32_t out_h,
@@ -1068,35 +888,35 @@ __global__ __launch_bounds__(kDistanceColumns) void k_image_distance_v(const uin
     const uint32_t j0 = blockIdx.y * (uint32_t)ROWS;
     const uint32_t rows = out_h - j0 < (uint32_t)ROWS ? out_h - j0 : (uint32_t)ROWS; // (j0 < out_h by the grid): every LDS index is below ROWS
     const uint32_t reach = (f.spread < kDistanceMaxSpread ? f.spread : kDistanceMaxSpread) - 1u;
-    const int n = (int)src_h, period = morphology_period(n, f.edge);
+    const int n = (int)src_h, period = edge_period(n, f.edge);
     const int xs = (int)x - (int)origin;
     const bool in_x = f.edge != kDistanceTransparent || (uint32_t)xs < src_w;
-    const uint32_t* column = src + morphology_wrap(xs, (int)src_w, f.edge); // (TRANSPARENT clamps: an address the lane may read)
+    const uint32_t* column = src + edge_wrap(xs, (int)src_w, f.edge); // (TRANSPARENT clamps: an address the lane may read)
     auto target_of = [&](int i, int phase) {
-        const uint32_t texel = column[(size_t)morphology_wrap_at(i, phase, n, f.edge) * src_w];
+        const uint32_t texel = column[(size_t)edge_wrap_at(i, phase, n, f.edge) * src_w];
         const bool inside = distance_inside(texel, f) && (f.edge != kDistanceTransparent || ((uint32_t)i < src_h && in_x));
         return distance_target(inside, MODE);
     };
     const int first = (int)j0 - (int)origin, last = first + (int)rows - 1; // the source rows under the workgroup's first and last row
     uint32_t d = kDistanceNone;
-    int i = last + (int)reach, phase = morphology_phase(i, n, f.edge);
+    int i = last + (int)reach, phase = edge_phase(i, n, f.edge);
 #pragma unroll 8
     for (uint32_t k = 0u; k < reach; ++k, --i) {
         d = distance_step(d, target_of(i, phase));
-        phase = morphology_phase_before(phase, period);
+        phase = edge_phase_before(phase, period);
     }
 #pragma unroll 8
     for (uint32_t m = rows; m-- > 0u; --i) {
         d = distance_step(d, target_of(i, phase));
-        phase = morphology_phase_before(phase, period);
+        phase = edge_phase_before(phase, period);
         below[m][lane] = (uint8_t)d;
     }
     d = kDistanceNone;
-    i = first - (int)reach, phase = morphology_phase(i, n, f.edge);
+    i = first - (int)reach, phase = edge_phase(i, n, f.edge);
 #pragma unroll 8
     for (uint32_t k = 0u; k < reach; ++k, ++i) {
         d = distance_step(d, target_of(i, phase));
-        phase = morphology_phase_next(phase, period);
+        phase = edge_phase_next(phase, period);
     }
     for (uint32_t m = 0u; m < rows; ++m) {
         const uint32_t b = below[m][lane];
@@ -1133,7 +953,7 @@ __global__ __launch_bounds__(kDistanceSegment) void k_image_distance_h(const uin
         if (at < n_staged) {
             const int i = first + (int)at;
             uint32_t v = INSIDE ? 0u : kDistanceNone;
-            if (f.edge != kDistanceTransparent) v = row[morphology_wrap(i, (int)out_w, f.edge)];
+            if (f.edge != kDistanceTransparent) v = row[edge_wrap(i, (int)out_w, f.edge)];
             else if ((uint32_t)i < out_w) v = row[i];
             staged[at] = (uint8_t)v;
             any |= v != kDistanceNone;
@@ -1291,19 +1111,17 @@ void launch_image_resize_v(const void* tmp, uint32_t tmp_h, uint32_t* out, uint3
     hipLaunchKernelGGL(k_image_resize_v, grid, dim3(kResizeColumns * kResizeWaves), 0, stream, static_cast<const uint2*>(tmp), tmp_h, out, out_w, out_h, table, pairs);
 }
 
-// crh_image_crop and crh_image_create_from_frame_region. A copy: 4 bytes read (inside the source) and 4 written per texel, k_image_composite's
-// geometry without the backdrop: a workgroup owns the row segment blockIdx.x of 256 V texels of the RESULT and strides over its rows; a lane
-// owns V consecutive texels, V = 4, 2 or 1 with w % V == 0, one aligned store. The source's group is one load of 4 V bytes only where
-// `source_wide` says that its rows and the shift keep it aligned (source_w % V == 0 and x % V == 0: then a group is wholly inside the source
-// or wholly outside); otherwise V loads of 4 bytes. Every source address is formed behind region_source's range check (regions.hpp: the
+// crh_image_crop and crh_image_create_from_frame_region. A copy: 4 bytes read (inside the source) and 4 written per texel, streaming
+// (image_geometry.hpp) over the RESULT, one aligned store per group. The source's group is one load of 4 V bytes only where `source_wide`
+// says so (stream_wide); otherwise V loads of 4 bytes. Every source address is formed behind region_source's range check (regions.hpp: the
 // wrapped sum is below the source's size exactly when the true one is in range, for any int32 x and y), and every texel of the result is
 // written exactly once, the zeros outside the source included: nothing clears the result first.
 template <int V>
-__global__ __launch_bounds__(kCompositeLanes) void k_image_crop(const uint32_t* __restrict__ source, uint32_t source_w, uint32_t source_h, uint32_t x, uint32_t y, uint32_t source_wide,
+__global__ __launch_bounds__(kStreamLanes) void k_image_crop(const uint32_t* __restrict__ source, uint32_t source_w, uint32_t source_h, uint32_t x, uint32_t y, uint32_t source_wide,
                                                                  uint32_t* __restrict__ out, uint32_t w, uint32_t h) {
     typedef typename TexelGroup<V>::type Group;
-    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
-    if (i >= w) return; // (w % V == 0 and i % V == 0: the whole group is outside)
+    const uint32_t i = stream_column<V>();
+    if (i >= w) return; // (the whole group is outside)
     for (uint32_t j = blockIdx.y; j < h; j += gridDim.y) {
         Group r = 0u;
         uint32_t sj = 0u, si = 0u;
@@ -1322,31 +1140,27 @@ __global__ __launch_bounds__(kCompositeLanes) void k_image_crop(const uint32_t* 
 }
 
 void launch_image_crop(const uint32_t* source, uint32_t source_w, uint32_t source_h, int32_t x, int32_t y, uint32_t* out, uint32_t w, uint32_t h, hipStream_t stream) {
-    const uint32_t v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
-    // (uint32_t)x % v is x mod v for a negative x as well: v divides 2^32
-    const uint32_t wide = v > 1u && source_w % v == 0u && (uint32_t)x % v == 0u ? 1u : 0u;
-    const uint32_t segments = (w + (uint32_t)kCompositeLanes * v - 1u) / ((uint32_t)kCompositeLanes * v); // <= 64
-    const dim3 grid(segments, std::min(h, std::max(1u, kCompositeBlocks / segments)));
-    if (v == 4u) hipLaunchKernelGGL(k_image_crop<4>, grid, dim3(kCompositeLanes), 0, stream, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, out, w, h);
-    else if (v == 2u) hipLaunchKernelGGL(k_image_crop<2>, grid, dim3(kCompositeLanes), 0, stream, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, out, w, h);
-    else hipLaunchKernelGGL(k_image_crop<1>, grid, dim3(kCompositeLanes), 0, stream, source, source_w, source_h, (uint32_t)x, (uint32_t)y, 0u, out, w, h);
+    const StreamGrid g = stream_grid(w, h, kStreamBlocks);
+    const uint32_t wide = stream_wide(g.v, source_w, x);
+#define CRH_CROP_LAUNCH(V) hipLaunchKernelGGL(k_image_crop<V>, g.grid, dim3(kStreamLanes), 0, stream, source, source_w, source_h, (uint32_t)x, (uint32_t)y, wide, out, w, h)
+    CRH_STREAM_DISPATCH(g.v, CRH_CROP_LAUNCH);
+#undef CRH_CROP_LAUNCH
 }
 
 namespace {
-// crh_image_statistics' grid cap, chosen for it: every workgroup leaves a partial result of kStatsWords words (4116 bytes), so kCompositeBlocks
+// crh_image_statistics' grid cap, chosen for it: every workgroup leaves a partial result of kStatsWords words (4116 bytes), so kStreamBlocks
 // of them would write half of what a 4096^2 image holds. 512 = 256 CUs x 2 workgroups of eight waves, 256 lanes along the row by two rows;
 // a lane takes its rows two at a time, so that it has two loads in flight where k_image_color_filter has two workgroups on the SIMD. The
 // partials of a 4096^2 image are 2 MB written and read once: 3 % of its bytes.
 constexpr uint32_t kStatsBlocks = 512;
 constexpr int kStatsRows = 2;                                  // rows of lanes in a workgroup (threadIdx.y)
-constexpr int kStatsWaves = kStatsRows * kCompositeLanes / 64; // a histogram each: 32 KB of LDS
+constexpr int kStatsWaves = kStatsRows * kStreamLanes / 64; // a histogram each: 32 KB of LDS
 constexpr int kStatsMergeWords = 64, kStatsMergeSlices = 16; // k_image_stats_merge: words per workgroup, one per lane of a wave; partials in flight per word
 enum { kStatsPlain = 0, kStatsZeros = 1, kStatsRuns = 2 }; // what k_image_stats does about contention: DESIGN.md §7 "Regions and statistics" has the measurement
 } // namespace
 
-// crh_image_statistics, the pass over the texels. Streaming, 4 bytes read per texel: k_image_color_filter's geometry — a workgroup owns the row
-// segment blockIdx.x of 256 V texels; its lanes of threadIdx.y = s stride over the rows 2 blockIdx.y + s, + 2 gridDim.y, ..., two per turn; a
-// lane owns V consecutive texels, V = 4, 2 or 1 with w % V == 0: every address is (row j < h) * w + (column i < w). Histograms accumulate
+// crh_image_statistics, the pass over the texels. Streaming (image_geometry.hpp), 4 bytes read per texel, with two rows of lanes: the lanes
+// of threadIdx.y = s stride over the rows 2 blockIdx.y + s, + 2 gridDim.y, ..., two per turn. Histograms accumulate
 // in LDS, one of 4 x 256 words per wave (no wave contends with another; 32 KB per workgroup), by ds_add_u32 without return. A lane's columns are fixed, so the
 // bounds are kept per lane as a mask of its V columns that were hit, the first and last row with a hit, and the number of hits, joined
 // across the wave by shuffles at the end. What this does about the input the call is for — a layer that is almost all (0, 0, 0, 0), where
@@ -1358,17 +1172,17 @@ enum { kStatsPlain = 0, kStatsZeros = 1, kStatsRuns = 2 }; // what k_image_stats
 // Workgroups never wait for one another: each writes its partial result (regions.hpp's words, the bounds still in their "empty" form) to
 // its own slab; k_image_stats_merge below sums the slabs.
 template <int V, int M>
-__global__ __launch_bounds__(kCompositeLanes * kStatsRows) void k_image_stats(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, StatsConstants f, uint32_t* __restrict__ partial) {
+__global__ __launch_bounds__(kStreamLanes * kStatsRows) void k_image_stats(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, StatsConstants f, uint32_t* __restrict__ partial) {
     typedef typename TexelGroup<V>::type Group;
     __shared__ uint32_t hist[kStatsWaves][kStatsHistogramWords];
     __shared__ uint32_t edge[kStatsWaves][5];
-    const uint32_t lane = threadIdx.y * (uint32_t)kCompositeLanes + threadIdx.x; // of the workgroup
-    for (uint32_t k = lane; k < (uint32_t)kStatsWaves * kStatsHistogramWords; k += (uint32_t)(kCompositeLanes * kStatsRows)) (&hist[0][0])[k] = 0u;
+    const uint32_t lane = threadIdx.y * (uint32_t)kStreamLanes + threadIdx.x; // of the workgroup
+    for (uint32_t k = lane; k < (uint32_t)kStatsWaves * kStatsHistogramWords; k += (uint32_t)(kStreamLanes * kStatsRows)) (&hist[0][0])[k] = 0u;
     __syncthreads();
     const uint32_t wave = lane >> 6;
     uint32_t* mine = hist[wave];
-    const uint32_t i = (blockIdx.x * (uint32_t)kCompositeLanes + threadIdx.x) * (uint32_t)V;
-    const bool live = i < w; // (w % V == 0 and i % V == 0: the whole group is inside or outside)
+    const uint32_t i = stream_column<V>();
+    const bool live = i < w; // (the whole group is inside or outside)
     const uint64_t live_lanes = __ballot(live);
     uint32_t columns = 0u, row0 = 0xFFFFFFFFu, row1 = 0u, hits = 0u, zeros = 0u;
     uint32_t run_texel = 0u, run_length = 0u; // wave-uniform
@@ -1438,7 +1252,7 @@ __global__ __launch_bounds__(kCompositeLanes * kStatsRows) void k_image_stats(co
     if ((threadIdx.x & 63u) == 0u) edge[wave][0] = b.x0, edge[wave][1] = b.y0, edge[wave][2] = b.x1, edge[wave][3] = b.y1, edge[wave][4] = b.count;
     __syncthreads();
     uint32_t* slab = partial + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kStatsWords;
-    for (uint32_t at = lane; at < kStatsHistogramWords; at += (uint32_t)(kCompositeLanes * kStatsRows)) {
+    for (uint32_t at = lane; at < kStatsHistogramWords; at += (uint32_t)(kStreamLanes * kStatsRows)) {
         uint32_t sum = 0u;
 #pragma unroll
         for (int v = 0; v < kStatsWaves; ++v) sum += hist[v][at];
@@ -1488,42 +1302,25 @@ __global__ __launch_bounds__(kStatsMergeWords * kStatsMergeSlices) void k_image_
 }
 
 namespace {
-void stats_grid(uint32_t w, uint32_t h, uint32_t* v, dim3* grid) {
-    *v = w % 4u == 0u ? 4u : w % 2u == 0u ? 2u : 1u;
-    const uint32_t segments = (w + (uint32_t)kCompositeLanes * *v - 1u) / ((uint32_t)kCompositeLanes * *v); // <= 64
-    *grid = dim3(segments, std::min((h + (uint32_t)kStatsRows - 1u) / (uint32_t)kStatsRows, std::max(1u, kStatsBlocks / segments)));
-}
+StreamGrid stats_grid(uint32_t w, uint32_t h) { return stream_grid(w, (h + (uint32_t)kStatsRows - 1u) / (uint32_t)kStatsRows, kStatsBlocks); }
 } // namespace
 
 uint32_t image_stats_partials(uint32_t w, uint32_t h) {
-    uint32_t v;
-    dim3 grid;
-    stats_grid(w, h, &v, &grid);
-    return grid.x * grid.y;
+    const StreamGrid g = stats_grid(w, h);
+    return g.grid.x * g.grid.y;
 }
 
 void launch_image_stats(const uint32_t* src, uint32_t w, uint32_t h, const StatsConstants& f, uint32_t* partial, hipStream_t stream) {
-    uint32_t v;
-    dim3 grid;
-    stats_grid(w, h, &v, &grid);
+    const StreamGrid g = stats_grid(w, h);
     // CRH_STATS_VARIANT = 0 (a plain LDS histogram) or 1 (+ the zero texels in a register) builds the measurement's other arms; anything else is the default
     static const int variant = [] {
         const char* e = std::getenv("CRH_STATS_VARIANT");
         return e && (e[0] == '0' || e[0] == '1') && e[1] == 0 ? e[0] - '0' : (int)kStatsRuns;
     }();
-#define CRH_STATS_LAUNCH(V, M) hipLaunchKernelGGL((k_image_stats<V, M>), grid, dim3(kCompositeLanes, kStatsRows), 0, stream, src, w, h, f, partial)
-#define CRH_STATS_WIDTHS(M)                \
-    if (v == 4u) CRH_STATS_LAUNCH(4, M);   \
-    else if (v == 2u) CRH_STATS_LAUNCH(2, M); \
-    else CRH_STATS_LAUNCH(1, M)
-    if (variant == kStatsPlain) {
-        CRH_STATS_WIDTHS(kStatsPlain);
-    } else if (variant == kStatsZeros) {
-        CRH_STATS_WIDTHS(kStatsZeros);
-    } else {
-        CRH_STATS_WIDTHS(kStatsRuns);
-    }
-#undef CRH_STATS_WIDTHS
+#define CRH_STATS_LAUNCH(V, M) hipLaunchKernelGGL((k_image_stats<V, M>), g.grid, dim3(kStreamLanes, kStatsRows), 0, stream, src, w, h, f, partial)
+    if (variant == kStatsPlain) CRH_STREAM_DISPATCH(g.v, CRH_STATS_LAUNCH, kStatsPlain);
+    else if (variant == kStatsZeros) CRH_STREAM_DISPATCH(g.v, CRH_STATS_LAUNCH, kStatsZeros);
+    else CRH_STREAM_DISPATCH(g.v, CRH_STATS_LAUNCH, kStatsRuns);
 #undef CRH_STATS_LAUNCH
 }
 

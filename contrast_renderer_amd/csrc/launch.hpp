@@ -36,7 +36,8 @@ void launch_state_colors_from_image(const RasterParams& r, uint32_t samples, hip
 void launch_selftest_srgb(const float* x, uint8_t* codes, uint64_t n, float* decoded, hipStream_t stream);
 void launch_composite(const uint8_t* const* layers_dev, uint32_t n_layers, uint64_t n_pixels, uint8_t* dst, hipStream_t stream);
 
-// image_filter.hip: crh_image_blur's two passes (the kernels' comments state the two tap tables). `tmp` = four 16-bit values per texel, src_h rows
+// image_filter.hip (its header comment is the map of the kernels; edge.hpp holds the edge rule every `edge` below follows, image_geometry.hpp
+// the geometries the kernels share): crh_image_blur's two passes (the kernels' comments state the two tap tables). `tmp` = four 16-bit values per texel, src_h rows
 // of out_w; origin = the axis's radius for CRH_BLUR_EDGE_TRANSPARENT (the result grows), else 0; radius = 0 for an axis whose q[0] is 65536.
 constexpr uint32_t kBlurMaxRadius = 192; // CRH_MAX_BLUR_RADIUS
 constexpr uint32_t kBlurTapPad = 8;      // zero taps on either side of k_image_blur_v's table: the output rows a lane accumulates
@@ -50,7 +51,7 @@ void launch_image_composite(const uint32_t* backdrop, uint32_t w, uint32_t h, co
 // device (256 words), or nullptr for none (color_filter.hpp holds the rule).
 struct ColorFilterCoefficients;
 void launch_image_color_filter(const uint32_t* src, uint32_t w, uint32_t h, const ColorFilterCoefficients& f, const uint32_t* tables, uint32_t* out, hipStream_t stream);
-// image_filter.hip: crh_image_morphology's two passes (morphology.hpp holds the rule; op < 2, 1 <= radius <= 192, edge < 4). h: src_h rows of src_w
+// image_filter.hip: crh_image_morphology's two passes (morphology.hpp holds the rule, min and max; op < 2, 1 <= radius <= 192, edge < 4). h: src_h rows of src_w
 // texels -> src_h rows of out_w; v: in_h rows of out_w texels -> out_h rows of out_w. origin = the axis's radius where the result grows, else 0.
 void launch_image_morph_h(const uint32_t* src, uint32_t src_w, uint32_t src_h, uint32_t* out, uint32_t out_w, uint32_t op, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream);
 void launch_image_morph_v(const uint32_t* in, uint32_t in_h, uint32_t* out, uint32_t out_w, uint32_t out_h, uint32_t op, uint32_t radius, uint32_t origin, uint32_t edge, hipStream_t stream);

@@ -1,6 +1,6 @@
 // csrc/lighting.hpp — the lighting rule of crh_image_lighting (include/contrast_hip.h states it), written once: the per-call constants from
 // the caller's floats, the Sobel gradient of the height field and the lit texel. k_image_lighting (image_filter.hip) and
-// crh_lighting_texels (image.hip, on the host) both call lighting_prepare, lighting_gradient and lighting_texel; the wrap is morphology.hpp's.
+// crh_lighting_texels (image.hip, on the host) both call lighting_prepare, lighting_gradient and lighting_texel; the wrap is edge.hpp's.
 // All real arithmetic is IEEE binary64 in the written order and parenthesisation, with only + - * / sqrt and the functions of
 // include/crh_fmath.h, compiled without contraction (-ffp-contract=off), and one rounding to a code at the end: the same bytes on x86-64 and
 // on gfx950.
@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/crh_fmath.h"
-#include "morphology.hpp"
+#include "edge.hpp"
 
 namespace crh {
 
@@ -139,7 +139,7 @@ inline void lighting_run(const uint8_t* in, uint32_t w, uint32_t h, const Lighti
                 for (int dx = -1; dx <= 1; ++dx) {
                     const int x = (int)i + dx, y = (int)j + dy;
                     if (edge == kLightingTransparent) a[dy + 1][dx + 1] = (uint32_t)x < w && (uint32_t)y < h ? in[((size_t)y * w + (size_t)x) * 4u + 3u] : 0u;
-                    else a[dy + 1][dx + 1] = in[((size_t)morphology_wrap(y, (int)h, edge) * w + (size_t)morphology_wrap(x, (int)w, edge)) * 4u + 3u];
+                    else a[dy + 1][dx + 1] = in[((size_t)edge_wrap(y, (int)h, edge) * w + (size_t)edge_wrap(x, (int)w, edge)) * 4u + 3u];
                 }
             int gx, gy;
             lighting_gradient(a, &gx, &gy);

@@ -1,40 +1,20 @@
-// csrc/morphology.hpp — the morphology rule of crh_image_morphology (include/contrast_hip.h states it), written once: the wrap of an index by
-// an edge and the per-channel min / max of two packed RGBA8 texels. k_image_morph_h and k_image_morph_v (image_filter.hip) and
-// crh_morphology_texels (image.hip, on the host) all call morphology_wrap and morphology_extreme. Min and max do not round, so there is no
-// arithmetic to state beyond them: the values are the 8-bit codes as they are.
+// csrc/morphology.hpp — the morphology rule of crh_image_morphology (include/contrast_hip.h states it), written once: the per-channel
+// min / max of two packed RGBA8 texels. k_image_morph_h and k_image_morph_v (image_filter.hip) and crh_morphology_texels (image.hip, on the
+// host) all call morphology_extreme, and edge.hpp's wrap. Min and max do not round, so there is no arithmetic to state beyond them: the
+// values are the 8-bit codes as they are.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
 
+#include "edge.hpp"
+
 namespace crh {
 
 constexpr uint32_t kMorphologyMaxRadius = 192; // CRH_MAX_MORPHOLOGY_RADIUS
 constexpr uint32_t kMorphologyErode = 0, kMorphologyDilate = 1; // crh_morphology_op
 constexpr uint32_t kMorphologyTransparent = 0; // CRH_BLUR_EDGE_TRANSPARENT; 1, 2, 3 = PAD, REPEAT, REFLECT
-
-// The image-paint block's wrap(i, n) for edges 1..3 (PAD, REPEAT, REFLECT), any int32 i, 1 <= n <= 16384: -> [0, n), in two parts, so that
-// a walk along an axis pays the remainder once. |i| may be many times n (a radius of 192 on a one-texel axis), so REPEAT and REFLECT reduce
-// with a remainder, not a single fold: the phase of i is i mod the period (n for REPEAT, 2 n for REFLECT; 0 for the edges without a period).
-__host__ __device__ __forceinline__ int morphology_period(int n, uint32_t edge) { return edge == 2u ? n : edge == 3u ? 2 * n : 1; }
-__host__ __device__ __forceinline__ int morphology_phase(int i, int n, uint32_t edge) {
-    if (edge < 2u) return 0;
-    const int p = morphology_period(n, edge);
-    const int k = i % p;
-    return k < 0 ? k + p : k;
-}
-// the phase of i + 1 and of i - 1 from the phase of i: no division
-__host__ __device__ __forceinline__ int morphology_phase_next(int k, int period) { return k + 1 == period ? 0 : k + 1; }
-__host__ __device__ __forceinline__ int morphology_phase_before(int k, int period) { return k == 0 ? period - 1 : k - 1; }
-// wrap(i, n) from i and its phase k, without a branch or a division. PAD clamps i; REPEAT is the phase; REFLECT folds the phase's second half
-// back. Under TRANSPARENT (edge 0) it clamps as PAD does, which gives a caller that selects zero outside [0, n) an address it may still read.
-__host__ __device__ __forceinline__ int morphology_wrap_at(int i, int k, int n, uint32_t edge) {
-    const int clamped = i < 0 ? 0 : i >= n ? n - 1 : i;
-    const int folded = k < n ? k : 2 * n - 1 - k;
-    return edge < 2u ? clamped : folded;
-}
-__host__ __device__ __forceinline__ int morphology_wrap(int i, int n, uint32_t edge) { return morphology_wrap_at(i, morphology_phase(i, n, edge), n, edge); }
 
 // A texel r | g << 8 | b << 16 | a << 24 as two words of two 16-bit fields, rb = r | b << 16 and ga = g | a << 16 (k_image_blur_h's split):
 // the min or max of two such words per field is one v_pk_min_u16 / v_pk_max_u16 on the device, so a texel costs two instructions and is
@@ -77,7 +57,7 @@ inline void morphology_run(const uint8_t* in, uint32_t w, uint32_t h, uint32_t r
                 const int i = (int)o - ox + k;
                 uint32_t texel = 0u; // TRANSPARENT outside the source
                 if (edge != kMorphologyTransparent || (uint32_t)i < w) {
-                    const uint8_t* s = line + 4u * (size_t)(edge != kMorphologyTransparent ? morphology_wrap(i, (int)w, edge) : i);
+                    const uint8_t* s = line + 4u * (size_t)(edge != kMorphologyTransparent ? edge_wrap(i, (int)w, edge) : i);
                     texel = s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
                 }
                 m = k == -(int)rx ? morphology_split(texel) : morphology_extreme<DILATE>(m, morphology_split(texel));
@@ -91,7 +71,7 @@ inline void morphology_run(const uint8_t* in, uint32_t w, uint32_t h, uint32_t r
             for (int k = -(int)ry; k <= (int)ry; ++k) {
                 const int j = (int)o - oy + k;
                 uint32_t texel = 0u;
-                if (edge != kMorphologyTransparent) texel = rows[(size_t)morphology_wrap(j, (int)h, edge) * out_w + i];
+                if (edge != kMorphologyTransparent) texel = rows[(size_t)edge_wrap(j, (int)h, edge) * out_w + i];
                 else if ((uint32_t)j < h) texel = rows[(size_t)j * out_w + i];
                 m = k == -(int)ry ? morphology_split(texel) : morphology_extreme<DILATE>(m, morphology_split(texel));
             }

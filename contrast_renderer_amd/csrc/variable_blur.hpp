@@ -3,14 +3,14 @@
 // k_image_variable_blur_h and k_image_variable_blur_v (image_filter.hip) and crh_variable_blur_texels (image.hip, on the host, through
 // variable_blur_run) all read the tables through variable_blur_radius / variable_blur_offset and sum with variable_blur_mad. The taps
 // themselves are crh_blur_taps' (image.hip's blur_taps): this header invents no tap rule and takes the function as an argument. All
-// values are integers below 2^32: the same bytes on x86-64 and on gfx950. The host's wrap is morphology.hpp's.
+// values are integers below 2^32: the same bytes on x86-64 and on gfx950. The host's wrap is edge.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
 
-#include "morphology.hpp"
+#include "edge.hpp"
 
 namespace crh {
 
@@ -95,7 +95,7 @@ __host__ __device__ __forceinline__ uint32_t variable_blur_texel(const uint32_t 
 
 // The rule on a whole image on the host (crh_variable_blur_texels): w x h texels of `in` under the levels of `mask` (the same size) into
 // `out`, which is neither; the caller's bytes at any alignment. Under TRANSPARENT what lies outside is skipped (zero), otherwise the index
-// goes through morphology.hpp's wrap — every address is formed from a tested or wrapped index, every tap from offset + k, k <= radius.
+// goes through edge.hpp's wrap — every address is formed from a tested or wrapped index, every tap from offset + k, k <= radius.
 inline void variable_blur_run(const uint8_t* in, const uint8_t* mask, uint32_t w, uint32_t h, const VariableBlurAxis& ax, const VariableBlurAxis& ay, uint32_t channel, uint32_t edge, uint8_t* out) {
     std::vector<VariableBlurFields> t((size_t)w * h);
     const auto word = [](const uint8_t* s) { return s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24; };
@@ -111,7 +111,7 @@ inline void variable_blur_run(const uint8_t* in, const uint8_t* mask, uint32_t w
                 if (edge == kVariableBlurTransparent) {
                     if ((uint32_t)s >= w) continue;
                 } else {
-                    s = morphology_wrap(s, (int)w, edge);
+                    s = edge_wrap(s, (int)w, edge);
                 }
                 variable_blur_mad(acc, q[k < 0 ? -k : k], variable_blur_split(word(in + ((size_t)j * w + (size_t)s) * 4u)));
             }
@@ -129,7 +129,7 @@ inline void variable_blur_run(const uint8_t* in, const uint8_t* mask, uint32_t w
                 if (edge == kVariableBlurTransparent) {
                     if ((uint32_t)s >= h) continue;
                 } else {
-                    s = morphology_wrap(s, (int)h, edge);
+                    s = edge_wrap(s, (int)h, edge);
                 }
                 variable_blur_mad(acc, q[k < 0 ? -k : k], t[(size_t)s * w + i]);
             }

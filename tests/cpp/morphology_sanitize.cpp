@@ -1,8 +1,8 @@
 // Compiled as host code under the address and undefined-behaviour sanitizers and run once by tests/test_morphology_cpu.py: a stand-alone host
 // program around the rule of csrc/morphology.hpp, the code crh_morphology_texels runs (no library, no device). It puts images through both
 // operators and all four edges — radius 192 on 1-texel axes among them — in buffers that end exactly where the image does, at odd addresses,
-// and compares with a plain double loop over the window that wraps by its own arithmetic; and it walks the stepped wrap the vertical kernel
-// uses against the direct one. Exit status 0 = all equal.
+// and compares with a plain double loop over the window that wraps by its own arithmetic; and it walks csrc/edge.hpp's stepped wrap, the one
+// the vertical kernel uses, its direct one and its branching one against that arithmetic. Exit status 0 = all equal.
 #include <morphology.hpp>
 
 #include <cstdio>
@@ -79,12 +79,14 @@ int main() {
     for (int n : sizes)
         for (unsigned edge = 1; edge < 4; ++edge)
             for (int pivot : {-385, -1, 0, n - 1, n, 3 * n + 1}) {
-                const int period = morphology_period(n, edge);
-                int up = morphology_phase(pivot, n, edge), down = up;
+                const int period = edge_period(n, edge);
+                int up = edge_phase(pivot, n, edge), down = up;
                 for (int k = 0; k <= 400; ++k) {
-                    if (k) up = morphology_phase_before(up, period), down = morphology_phase_next(down, period);
-                    if (morphology_wrap_at(pivot - k, up, n, edge) != (int)wrap_plain(pivot - k, n, edge) || morphology_wrap(pivot - k, n, edge) != (int)wrap_plain(pivot - k, n, edge)) ++failures;
-                    if (morphology_wrap_at(pivot + k, down, n, edge) != (int)wrap_plain(pivot + k, n, edge) || morphology_wrap(pivot + k, n, edge) != (int)wrap_plain(pivot + k, n, edge)) ++failures;
+                    if (k) up = edge_phase_before(up, period), down = edge_phase_next(down, period);
+                    for (int side = 0; side < 2; ++side) {
+                        const int i = side ? pivot + k : pivot - k, expect = (int)wrap_plain(i, n, edge);
+                        if (edge_wrap_at(i, side ? down : up, n, edge) != expect || edge_wrap(i, n, edge) != expect || edge_wrap_branching(i, n, edge) != expect) ++failures;
+                    }
                 }
             }
     // the packed min / max: every pair of codes in every field

@@ -23,7 +23,7 @@ from test_gpu_blur import _blit
 
 pytestmark = pytest.mark.gpu
 
-# k_image_displace's tile is 64 x 16 texels (kDisplaceTileW x kDisplaceTileH in csrc/image_filter.hip): a lane per column, four rows per
+# k_image_displace's tile is 64 x 16 texels (DisplaceTile in csrc/image_filter.hip, Tile::W x Tile::H of csrc/image_geometry.hpp): a lane per column, four rows per
 # lane, four waves. (1, 1), (1, 7), (7, 1) and (33, 15) lie inside one tile; (64, 16) fills one exactly; (65, 16) crosses the first tile
 # border in x by one texel and (64, 17) the first in y by one: a wave's 64 columns and the rows-per-lane blocking. (129, 33) crosses the
 # second border of both axes by one; (300, 17) crosses the fourth in x by 44 and the first in y by one.

@@ -18,7 +18,7 @@ from test_gpu_blending import no_pins, stack  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-# k_image_lighting's tile is 64 x 16 texels (kLightingTileW x kLightingTileH in csrc/image_filter.hip) and its halo one texel on every side.
+# k_image_lighting's tile is 64 x 16 texels (LightingTile in csrc/image_filter.hip, Tile::W x Tile::H of csrc/image_geometry.hpp) and its halo one texel on every side.
 # (1, 1), (1, 7), (7, 1) and (3, 2) lie inside one tile, the first three narrower than the stencil, so the staged texels are wrapped ones;
 # (64, 16) fills one tile exactly. (65, 300) crosses the first tile border in x by one texel (the halo alone) and the 18th in y by 12;
 # (300, 17) crosses the fourth in x by 44 and the first in y by one; (129, 33) crosses the second border of both axes by one.

@@ -18,8 +18,8 @@ pytestmark = pytest.mark.gpu
 
 # Result widths of each group size: V = 4, 2, 1 texels per lane (the most that divides the width). A workgroup's row segment is 256 lanes.
 WIDTHS = {4: 8, 2: 6, 1: 5}
-# The grids' caps in csrc/image_filter.hip: kCompositeBlocks = 8192 workgroups of one row for k_image_crop; kStatsBlocks = 512 workgroups of
-# kStatsRows = 2 rows of lanes for k_image_stats, whose lanes take their rows two at a time. A one-segment image of more rows than a grid
+# The grids' caps: kStreamBlocks = 8192 (csrc/image_geometry.hpp) workgroups of one row for k_image_crop; kStatsBlocks = 512 (csrc/image_filter.hip)
+# workgroups of kStatsRows = 2 rows of lanes for k_image_stats, whose lanes take their rows two at a time. A one-segment image of more rows than a grid
 # covers at once — 8192, and 1024 — makes a row loop turn.
 CROP_ROWS, STATS_ROWS = 8192, 1024
 
