@@ -11,7 +11,7 @@ from .renderer import (BlendMode, BlurEdge, ColorMatrix, CompositeOp, ConvolveKe
                        MorphologyOp, Paint, PointLight, SpotLight, Spread, blur_taps, color_filter_texels, composite_texels, convolve_coefficients, convolve_texels,
                        lighting_texels, morphology_size, morphology_texels, TurbulenceKind, turbulence_tables, turbulence_texels, Channel, displace_offset, displace_texels,
                        DistanceMode, distance_code, distance_size, distance_texels, ResizeFilter, resize_taps, resize_texels, ImageStatistics, crop_texels, statistics_texels,
-                       variable_blur_sigma, variable_blur_texels)
+                       variable_blur_sigma, variable_blur_texels, TransformFilter, transform_fit, transform_position, transform_texels)
 
 __all__ = ["ContrastError", "PathBatch", "Cap", "CurveApproximation", "DashInterval", "DynamicStrokeOptions", "Join", "Path", "SegmentType",
            "StrokeOptions", "batch_from_shapes", "GradientStop", "Paint", "Spread", "Filter", "Image", "ImagePaint", "BlurEdge", "blur_taps",
@@ -22,4 +22,5 @@ __all__ = ["ContrastError", "PathBatch", "Cap", "CurveApproximation", "DashInter
            "DistanceMode", "distance_code", "distance_size", "distance_texels",
            "ResizeFilter", "resize_taps", "resize_texels",
            "ImageStatistics", "crop_texels", "statistics_texels",
-           "variable_blur_sigma", "variable_blur_texels"]
+           "variable_blur_sigma", "variable_blur_texels",
+           "TransformFilter", "transform_fit", "transform_position", "transform_texels"]

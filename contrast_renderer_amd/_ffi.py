@@ -261,6 +261,10 @@ class VariableBlurC(C.Structure):  # crh_variable_blur
     _fields_ = [("sigma_x", C.c_float * 2), ("sigma_y", C.c_float * 2), ("channel", C.c_uint32), ("edge", C.c_uint32)]
 
 
+class TransformC(C.Structure):  # crh_transform
+    _fields_ = [("matrix", C.c_double * 9), ("width", C.c_uint32), ("height", C.c_uint32), ("filter", C.c_uint32), ("edge", C.c_uint32)]
+
+
 class FontMetricsC(C.Structure):
     _fields_ = [("units_per_em", C.c_uint32), ("number_of_glyphs", C.c_uint32), ("ascender", C.c_int32), ("descender", C.c_int32),
                 ("line_gap", C.c_int32), ("height", C.c_int32), ("has_x_height", C.c_int32), ("x_height", C.c_int32),
@@ -380,6 +384,11 @@ def load_library():
         "crh_variable_blur_sigma": (C.c_int, [C.POINTER(VariableBlurC), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "crh_variable_blur_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, V, C.POINTER(VariableBlurC), V]),
         "crh_image_variable_blur": (C.c_int, [V, V, C.POINTER(VariableBlurC), C.POINTER(V)]),
+        "crh_transform_validate": (C.c_int, [C.POINTER(TransformC)]),
+        "crh_transform_fit": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.POINTER(TransformC), C.POINTER(C.c_int32)]),
+        "crh_transform_position": (C.c_int, [C.POINTER(TransformC), C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
+        "crh_transform_texels": (C.c_int, [C.c_uint32, C.c_uint32, V, C.POINTER(TransformC), V]),
+        "crh_image_transform": (C.c_int, [V, C.POINTER(TransformC), C.POINTER(V)]),
         "crh_image_paint_validate": (C.c_int, [C.POINTER(ImagePaintC)]),
         "crh_scene_set_paints_with_images": (C.c_int, [V, C.POINTER(PaintC), C.c_uint32, C.POINTER(ImagePaintC), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
         "crh_frame_upload": (C.c_int, [V, V]),

@@ -1,5 +1,5 @@
 // csrc/image.hip — the host half of crh_image behind the C ABI of include/contrast_hip.h: create, size, mipmaps, level download, the ten
-// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field, resize), crop, statistics and the variable blur, with their host rules (crh_*_texels) and validators.
+// filters (blur, composite, colour filter, morphology, convolve, lighting, turbulence, displace, distance field, resize), crop, statistics, the variable blur and the transform, with their host rules (crh_*_texels) and validators.
 // Host code only: the kernels are image_filter.hip's and raster.hip's (launch.hpp), the rules are the filters' headers. Of a renderer it
 // uses its device, its stream and "wait for every stream" (api_internal.hpp); what is about a frame or a paint table stays in api.hip.
 #include <hip/hip_runtime.h>
@@ -23,6 +23,7 @@
 #include "morphology.hpp"
 #include "regions.hpp"
 #include "resize.hpp"
+#include "transform.hpp"
 #include "turbulence.hpp"
 #include "variable_blur.hpp"
 
@@ -921,5 +922,116 @@ crh_status crh_image_variable_blur(const crh_image* src, const crh_image* mask, 
         void* tmp = static_cast<char*>(scratch) + tables_bytes;
         job.launch("k_image_variable_blur_h", [&] { launch_image_variable_blur_h(texels_of(src), texels_of(mask), w, h, tmp, table_x, ax.radius, shift, edge, job.stream); });
         job.launch("k_image_variable_blur_v", [&] { launch_image_variable_blur_v(tmp, texels_of(mask), job.texels(), w, h, table_y, shift, edge, job.stream); });
+    });
+}
+// ---- transform
+namespace {
+static_assert(CRH_TRANSFORM_NEAREST == kTransformNearest && CRH_TRANSFORM_LINEAR == kTransformLinear && CRH_TRANSFORM_CUBIC == kTransformCubic && CRH_MAX_TRANSFORM_ENTRY == kTransformMaxEntry &&
+                  CRH_BLUR_EDGE_TRANSPARENT == kTransformTransparent,
+              "transform.hpp's filters, limit and edge are the header's");
+constexpr const char* kTransform = "crh_transform_validate";
+// the rows of the validation that are about a matrix, a filter and an edge: crh_transform's own and crh_transform_fit's `forward`
+crh_status transform_check(const double* m, uint32_t filter, uint32_t edge) {
+    if (filter > CRH_TRANSFORM_CUBIC) return refuse(kTransform, "filter is above CRH_TRANSFORM_CUBIC");
+    if (edge > CRH_BLUR_EDGE_REFLECT) return refuse(kTransform, "edge is above CRH_BLUR_EDGE_REFLECT");
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(m[k])) return refuse(kTransform, "an entry of the matrix is not finite", CRH_ERR_NON_FINITE);
+    for (int k = 0; k < 9; ++k)
+        if (std::fabs(m[k]) > CRH_MAX_TRANSFORM_ENTRY) return refuse(kTransform, "an entry of the matrix is above 2^40 in magnitude");
+    return CRH_OK;
+}
+// validates the fields and prepares them: the one check of the entry points that take a crh_transform
+crh_status transform_constants(const crh_transform* how, TransformConstants* f) {
+    if (!how) return refuse(kTransform, "a null argument");
+    crh_status st = transform_check(how->matrix, how->filter, how->edge);
+    if (st == CRH_OK) st = check_size(kTransform, how->width, how->height);
+    if (st != CRH_OK) return st;
+    std::copy(how->matrix, how->matrix + 9, f->m);
+    f->filter = how->filter, f->edge = how->edge, f->projective = transform_is_affine(how->matrix) ? 0u : 1u;
+    return CRH_OK;
+}
+template <bool PROJECTIVE>
+void transform_run_filter(const uint8_t* in, uint32_t sw, uint32_t sh, const TransformConstants& f, uint32_t w, uint32_t h, uint8_t* out) {
+    if (f.filter == kTransformCubic) transform_run<kTransformCubic, PROJECTIVE>(in, sw, sh, f, w, h, out);
+    else if (f.filter == kTransformLinear) transform_run<kTransformLinear, PROJECTIVE>(in, sw, sh, f, w, h, out);
+    else transform_run<kTransformNearest, PROJECTIVE>(in, sw, sh, f, w, h, out);
+}
+} // namespace
+crh_status crh_transform_validate(const crh_transform* how) {
+    TransformConstants f;
+    return transform_constants(how, &f);
+}
+crh_status crh_transform_position(const crh_transform* how, uint32_t i, uint32_t j, int32_t position[2], uint32_t* visible) {
+    if (!position || !visible) return refuse(kTransform, "a null argument");
+    TransformConstants f;
+    const crh_status st = transform_constants(how, &f);
+    if (st != CRH_OK) return st;
+    if (i >= how->width || j >= how->height) return refuse(kTransform, "a texel is outside the result");
+    *visible = (f.projective ? transform_position<true>(f.m, i, j, &position[0], &position[1]) : transform_position<false>(f.m, i, j, &position[0], &position[1])) ? 1u : 0u;
+    return CRH_OK;
+}
+crh_status crh_transform_fit(uint32_t width, uint32_t height, const double forward[9], uint32_t filter, uint32_t edge, crh_transform* out, int32_t origin[2]) {
+    if (!forward || !out || !origin) return refuse(kTransform, "a null argument");
+    crh_status st = transform_check(forward, filter, edge);
+    if (st == CRH_OK) st = check_size(kTransform, width, height);
+    if (st != CRH_OK) return st;
+    const double a = forward[0], b = forward[1], c = forward[2], d = forward[3], e = forward[4], f = forward[5], g = forward[6], h = forward[7], i = forward[8];
+    const bool affine = transform_is_affine(forward);
+    // the four corners in the header's order, each min and max by comparisons
+    double lo[2] = {0.0, 0.0}, hi[2] = {0.0, 0.0};
+    for (int corner = 0; corner < 4; ++corner) {
+        const double x = corner & 1 ? (double)width : 0.0, y = corner & 2 ? (double)height : 0.0;
+        double p[2] = {(a * x + b * y) + c, (d * x + e * y) + f};
+        if (!affine) {
+            const double W = (g * x + h * y) + i;
+            if (!(W > 0.0)) return refuse(kTransform, "a corner is behind the horizon");
+            p[0] = p[0] / W, p[1] = p[1] / W;
+        }
+        for (int axis = 0; axis < 2; ++axis) {
+            if (corner == 0 || p[axis] < lo[axis]) lo[axis] = p[axis];
+            if (corner == 0 || p[axis] > hi[axis]) hi[axis] = p[axis];
+        }
+    }
+    const double x0 = std::floor(lo[0]), x1 = std::ceil(hi[0]), y0 = std::floor(lo[1]), y1 = std::ceil(hi[1]);
+    const double w = x1 - x0 < 1.0 ? 1.0 : x1 - x0, t = y1 - y0 < 1.0 ? 1.0 : y1 - y0;
+    if (!(w <= (double)kMaxImageSize) || !(t <= (double)kMaxImageSize)) return refuse(kTransform, "the result is outside [1, 16384]");
+    if (!(std::fabs(x0) <= 1073741824.0) || !(std::fabs(y0) <= 1073741824.0)) return refuse(kTransform, "the origin is beyond 2^30");
+    const double A[9] = {e * i - f * h, c * h - b * i, b * f - c * e, f * g - d * i, a * i - c * g, c * d - a * f, d * h - e * g, b * g - a * h, a * e - b * d};
+    const double det = (a * A[0] + b * A[3]) + c * A[6];
+    if (det == 0.0) return refuse(kTransform, "forward is singular");
+    crh_transform fitted = {};
+    for (int k = 0; k < 9; ++k) {
+        fitted.matrix[k] = A[k] / det;
+        if (!std::isfinite(fitted.matrix[k])) return refuse(kTransform, "forward is singular");
+    }
+    for (int row = 0; row < 3; ++row) fitted.matrix[3 * row + 2] = (fitted.matrix[3 * row] * x0 + fitted.matrix[3 * row + 1] * y0) + fitted.matrix[3 * row + 2];
+    fitted.width = (uint32_t)w, fitted.height = (uint32_t)t, fitted.filter = filter, fitted.edge = edge;
+    TransformConstants checked;
+    st = transform_constants(&fitted, &checked);
+    if (st != CRH_OK) return st;
+    *out = fitted;
+    origin[0] = (int32_t)-x0, origin[1] = (int32_t)-y0;
+    return CRH_OK;
+}
+crh_status crh_transform_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_transform* how, void* out_rgba8) {
+    if (!rgba8 || !out_rgba8) return refuse(kTransform, "a null argument");
+    TransformConstants f;
+    crh_status st = transform_constants(how, &f);
+    if (st == CRH_OK) st = check_size(kTransform, width, height);
+    if (st != CRH_OK) return st;
+    if (out_rgba8 == rgba8) return refuse(kTransform, "out_rgba8 is rgba8");
+    if (f.projective) transform_run_filter<true>(static_cast<const uint8_t*>(rgba8), width, height, f, how->width, how->height, static_cast<uint8_t*>(out_rgba8));
+    else transform_run_filter<false>(static_cast<const uint8_t*>(rgba8), width, height, f, how->width, how->height, static_cast<uint8_t*>(out_rgba8));
+    return CRH_OK;
+}
+crh_status crh_image_transform(const crh_image* src, const crh_transform* how, crh_image** out) {
+    if (!src || !out) return refuse(kTransform, "a null argument");
+    TransformConstants f;
+    crh_status st = transform_constants(how, &f); // (the fields before the image: a refused `how` does not look at it)
+    if (st == CRH_OK && !src->renderer) st = refuse(kTransform, "a null argument");
+    if (st == CRH_OK) st = check_size(kTransform, src->width, src->height);
+    if (st != CRH_OK) return st;
+    return filter_call("crh_image_transform", src->renderer, how->width, how->height, out, [&](FilterJob& job) {
+        job.launch("k_image_transform", [&] { launch_image_transform(texels_of(src), src->width, src->height, f, job.texels(), how->width, how->height, job.stream); });
     });
 }

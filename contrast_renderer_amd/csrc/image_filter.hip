@@ -6,6 +6,7 @@
 //   morphology                          k_image_morph_h / _v                                doubling in LDS; van Herk / Gil-Werman
 //   convolve, lighting                  k_image_convolve, k_image_lighting                  tile with a halo
 //   turbulence, displace                k_image_turbulence, k_image_displace                tile
+//   transform                           k_image_transform                                   block tile
 //   distance field                      k_image_distance_v / _h                             column walks; a scan in LDS
 //   resize                              k_image_resize_h / _v                               transposed chunks; row pairs from cache
 //   crop, frame regions, statistics     k_image_crop, k_image_stats, k_image_stats_merge    streaming; a merge of partials
@@ -25,6 +26,7 @@
 #include "morphology.hpp"
 #include "regions.hpp"
 #include "resize.hpp"
+#include "transform.hpp"
 #include "turbulence.hpp"
 #include "variable_blur.hpp"
 
@@ -857,6 +859,144 @@ void launch_image_displace(const uint32_t* src, const uint32_t* map, uint32_t w,
     else CRH_DISPLACE_LAUNCH(kDisplaceRuntimeEdge);
 #endif
 #undef CRH_DISPLACE_LAUNCH
+}
+
+namespace {
+#ifndef CRH_TRANSFORM_BLOCK
+#define CRH_TRANSFORM_BLOCK 8 // texels of one output row per wave instruction: 64 (the displace tile), 16 or 8 (a build with -DCRH_TRANSFORM_BLOCK=64 or 16 is how DESIGN.md's comparison of the lane mappings is measured)
+#endif
+#ifndef CRH_TRANSFORM_ROWS
+#define CRH_TRANSFORM_ROWS 4 // outputs per lane, BH rows apart: their fetches are in flight together under NEAREST and LINEAR
+#endif
+// Block tile. 256 lanes, four waves; a wave instruction covers BW x BH texels, BW BH = 64: lane l the texel (l % BW, l / BW) of the block, so
+// that the source footprint of a wave's fetch is compact under any angle: under a quarter turn 64 lanes of one output row read 64 source
+// rows, BW x BH lanes read BH segments of BW texels in BW rows. A lane produces ROWS outputs of one column, BH rows apart: a wave BW x BH ROWS
+// texels. The waves lie side by side while the tile is narrower than 64 texels and one below the other from there: BW = 64 is
+// image_geometry.hpp's Tile<ROWS> lane for lane, BW = 16 a tile of 64 x 4 ROWS, BW = 8 one of 32 x 8 ROWS. A wave's store is BH segments
+// of 4 BW bytes. The wave is in an SGPR.
+template <int BW, int ROWS>
+struct BlockTile {
+    static constexpr int BH = 64 / BW, WavesX = BW >= 64 ? 1 : 4, WavesY = 4 / WavesX, Rows = ROWS, W = BW * WavesX, H = BH * ROWS * WavesY, Lanes = 256;
+    static_assert(BW * BH == 64 && WavesX * WavesY == 4, "a wave instruction is one block; four waves");
+    uint32_t i, j0;
+    __device__ __forceinline__ BlockTile() {
+        const uint32_t lane = threadIdx.x & 63u, wave = wave_of_workgroup();
+        i = blockIdx.x * (uint32_t)W + (wave % (uint32_t)WavesX) * (uint32_t)BW + lane % (uint32_t)BW;
+        j0 = blockIdx.y * (uint32_t)H + (wave / (uint32_t)WavesX) * (uint32_t)(BH * ROWS) + lane / (uint32_t)BW;
+    }
+    __device__ __forceinline__ uint32_t column() const { return i; }                           // the lane's output column
+    __device__ __forceinline__ uint32_t row(int b) const { return j0 + (uint32_t)(b * BH); }   // its b-th output row
+    static dim3 grid(uint32_t w, uint32_t h) { return dim3((w + (uint32_t)W - 1u) / (uint32_t)W, (h + (uint32_t)H - 1u) / (uint32_t)H); } // <= 512 x 1024
+};
+typedef BlockTile<CRH_TRANSFORM_BLOCK, CRH_TRANSFORM_ROWS> TransformTile;
+constexpr int kTransformRows = TransformTile::Rows;
+__device__ const TransformCubicTable k_transform_cubic{}; // transform.hpp's weights, staged in LDS by every workgroup of the CUBIC kernel
+} // namespace
+
+// crh_image_transform: a gather bound by the latency of its fetches, like k_image_displace and in its four steps, on a block tile
+// (BlockTile above). No map is read: (1) a lane's positions, each computed from (i, j) alone by transform.hpp's rule — six binary64
+// multiply-adds, under PROJECTIVE three more and two divisions; no stepping from a neighbour, so every texel has the rule's bits; (2) the
+// taps, and for each tap a texel index formed ONLY from wrapped (edge_wrap_branching) or clamped indices of the SOURCE's axes, with under
+// TRANSPARENT a bit that says whether the tap lies inside; (3) all fetches — under NEAREST and LINEAR those of all the lane's rows, 4 or 16
+// loads, under CUBIC the 16 of one row at a time — issued before the first is consumed; (4) the taps outside zeroed, the blend
+// (displace_blend, or transform_cubic_blend with the weights of the two phases from the table in LDS, one 8-byte entry staged per lane),
+// zero for a texel behind the horizon, the store. A lane outside the result computes like any other (its position clamps, its indices are
+// wrapped or clamped) and does not store. Every index is below src_w src_h <= 2^28. EDGE as in k_image_displace.
+template <uint32_t FILTER, uint32_t EDGE, bool PROJECTIVE>
+__global__ __launch_bounds__(TransformTile::Lanes) void k_image_transform(const uint32_t* __restrict__ src, uint32_t sw, uint32_t sh, TransformConstants f, uint32_t* __restrict__ out, uint32_t w,
+                                                                                     uint32_t h) {
+    constexpr bool WRAPPED = EDGE != kTransformTransparent;
+    const uint32_t edge = EDGE == kDisplaceRuntimeEdge ? f.edge : EDGE;
+    const TransformTile tile;
+    const uint32_t i = tile.column();
+    if constexpr (FILTER == kTransformCubic) {
+        __shared__ uint2 cubic[256];
+        cubic[threadIdx.x] = reinterpret_cast<const uint2*>(k_transform_cubic.c)[threadIdx.x];
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < kTransformRows; ++b) {
+            const uint32_t j = tile.row(b);
+            int32_t X, Y;
+            const bool visible = transform_position<PROJECTIVE>(f.m, i, j, &X, &Y);
+            const TransformCubicTaps t = transform_cubic_taps(X, Y);
+            uint32_t x[4], y[4], inside = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                bool in_x, in_y;
+                x[k] = displace_index<WRAPPED>(t.i0 - 1 + k, (int)sw, edge, &in_x), y[k] = displace_index<WRAPPED>(t.j0 - 1 + k, (int)sh, edge, &in_y) * sw;
+                inside |= (in_x ? 1u : 0u) << k | (in_y ? 16u : 0u) << k;
+            }
+            uint32_t s[16];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s[4 * r + k] = src[y[r] + x[k]];
+            if (!WRAPPED) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s[4 * r + k] = (inside >> k) & (inside >> (4 + r)) & 1u ? s[4 * r + k] : 0u;
+            }
+            const uint2 px = cubic[t.fx], py = cubic[t.fy];
+            const int16_t cx[4] = {(int16_t)px.x, (int16_t)(px.x >> 16), (int16_t)px.y, (int16_t)(px.y >> 16)}, cy[4] = {(int16_t)py.x, (int16_t)(py.x >> 16), (int16_t)py.y, (int16_t)(py.y >> 16)};
+            const uint32_t value = transform_cubic_blend(s, cx, cy);
+            if (i < w && j < h) out[j * w + i] = visible ? value : 0u;
+        }
+    } else {
+        constexpr int TAPS = FILTER == kTransformLinear ? 4 : 1;
+        DisplaceTaps taps[kTransformRows];
+        uint32_t at[kTransformRows][TAPS], inside[kTransformRows];
+        bool visible[kTransformRows];
+#pragma unroll
+        for (int b = 0; b < kTransformRows; ++b) {
+            int32_t X, Y;
+            visible[b] = transform_position<PROJECTIVE>(f.m, i, tile.row(b), &X, &Y);
+            taps[b] = displace_taps<FILTER>(X, Y);
+            bool in_x0, in_y0;
+            const uint32_t x0 = displace_index<WRAPPED>(taps[b].i0, (int)sw, edge, &in_x0), y0 = displace_index<WRAPPED>(taps[b].j0, (int)sh, edge, &in_y0) * sw;
+            at[b][0] = y0 + x0, inside[b] = in_x0 && in_y0 ? 1u : 0u;
+            if constexpr (FILTER == kTransformLinear) {
+                bool in_x1, in_y1;
+                const uint32_t x1 = displace_index<WRAPPED>(taps[b].i0 + 1, (int)sw, edge, &in_x1), y1 = displace_index<WRAPPED>(taps[b].j0 + 1, (int)sh, edge, &in_y1) * sw;
+                at[b][1] = y0 + x1, at[b][2] = y1 + x0, at[b][3] = y1 + x1;
+                inside[b] |= (in_x1 && in_y0 ? 2u : 0u) | (in_x0 && in_y1 ? 4u : 0u) | (in_x1 && in_y1 ? 8u : 0u);
+            }
+        }
+        uint32_t s[kTransformRows][TAPS];
+#pragma unroll
+        for (int b = 0; b < kTransformRows; ++b)
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) s[b][t] = src[at[b][t]];
+        if (i >= w) return;
+#pragma unroll
+        for (int b = 0; b < kTransformRows; ++b) {
+            const uint32_t j = tile.row(b);
+            if (!WRAPPED) {
+#pragma unroll
+                for (int t = 0; t < TAPS; ++t) s[b][t] = (inside[b] >> t) & 1u ? s[b][t] : 0u;
+            }
+            if (j < h) out[j * w + i] = visible[b] ? displace_blend<FILTER>(s[b], taps[b]) : 0u;
+        }
+    }
+}
+
+void launch_image_transform(const uint32_t* src, uint32_t src_w, uint32_t src_h, const TransformConstants& f, uint32_t* out, uint32_t w, uint32_t h, hipStream_t stream) {
+    const dim3 grid = TransformTile::grid(w, h), block(TransformTile::Lanes);
+#define CRH_TRANSFORM_LAUNCH(FILTER, EDGE)                                                                                                             \
+    do {                                                                                                                                               \
+        if (f.projective) hipLaunchKernelGGL((k_image_transform<FILTER, EDGE, true>), grid, block, 0, stream, src, src_w, src_h, f, out, w, h);        \
+        else hipLaunchKernelGGL((k_image_transform<FILTER, EDGE, false>), grid, block, 0, stream, src, src_w, src_h, f, out, w, h);                    \
+    } while (0)
+#define CRH_TRANSFORM_LAUNCH_EDGE(FILTER)                                                      \
+    do {                                                                                       \
+        if (f.edge == kTransformTransparent) CRH_TRANSFORM_LAUNCH(FILTER, kTransformTransparent); \
+        else CRH_TRANSFORM_LAUNCH(FILTER, kDisplaceRuntimeEdge);                               \
+    } while (0)
+    if (f.filter == kTransformCubic) CRH_TRANSFORM_LAUNCH_EDGE(kTransformCubic);
+    else if (f.filter == kTransformLinear) CRH_TRANSFORM_LAUNCH_EDGE(kTransformLinear);
+    else CRH_TRANSFORM_LAUNCH_EDGE(kTransformNearest);
+#undef CRH_TRANSFORM_LAUNCH_EDGE
+#undef CRH_TRANSFORM_LAUNCH
 }
 
 namespace {

@@ -91,6 +91,10 @@ void launch_image_stats_merge(const uint32_t* partial, uint32_t n, uint32_t* out
 // of w texels; `tmp`: h rows of w texels of four 16-bit values; apron = the axis's largest radius <= 192; shift = 8 * the mask's channel; edge < 4. out is neither input.
 void launch_image_variable_blur_h(const uint32_t* src, const uint32_t* mask, uint32_t w, uint32_t h, void* tmp, const uint32_t* table, uint32_t apron, uint32_t shift, uint32_t edge, hipStream_t stream);
 void launch_image_variable_blur_v(const void* tmp, const uint32_t* mask, uint32_t* out, uint32_t w, uint32_t h, const uint32_t* table, uint32_t shift, uint32_t edge, hipStream_t stream);
+// image_filter.hip: crh_image_transform's kernel (transform.hpp holds the rule; f.filter < 3, f.edge < 4, f.projective = !transform_is_affine(f.m)). src: src_h rows of src_w texels;
+// out: h rows of w texels, each written once; 1 <= every size <= 16384. out is not the source.
+struct TransformConstants;
+void launch_image_transform(const uint32_t* src, uint32_t src_w, uint32_t src_h, const TransformConstants& f, uint32_t* out, uint32_t w, uint32_t h, hipStream_t stream);
 
 // bin_edges.hip: the plain Stencil + Color pass as boundary edges + backdrop (edge_slots.hpp), binned in one traversal; the slot ranges and scans around it
 void launch_clear_words(uint32_t* words, size_t n_words, hipStream_t stream); // zeroes n_words 32-bit words with single-wave workgroups (the clear in front of both passes' binning kernels)

@@ -949,6 +949,65 @@ def variable_blur_sigma(code, sigma, sigma_at_zero=0.0):
     return float(sx.value), float(sy.value)
 
 
+class TransformFilter(IntEnum):  # crh_transform_filter
+    Nearest = 0
+    Linear = 1
+    Cubic = 2  # Catmull-Rom over 4 x 4 texels
+
+
+MAX_TRANSFORM_ENTRY = 2.0 ** 40  # CRH_MAX_TRANSFORM_ENTRY
+
+
+def _matrix9(matrix):
+    """9 floats, row-major, or 6 (an affine matrix: the last row is 0 0 1) -> a C array of 9 doubles"""
+    m = [float(v) for v in np.asarray(matrix, dtype=np.float64).reshape(-1)]
+    if len(m) == 6:
+        m += [0.0, 0.0, 1.0]
+    if len(m) != 9:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"a transform matrix has 9 entries (or 6, affine), not {len(m)}")
+    return (C.c_double * 9)(*m)
+
+
+def _transform_arguments(matrix, width, height, filter, edge):
+    """-> TransformC"""
+    how = _ffi.TransformC()
+    how.matrix = _matrix9(matrix)
+    how.width, how.height, how.filter, how.edge = int(width) & 0xFFFFFFFF, int(height) & 0xFFFFFFFF, int(filter) & 0xFFFFFFFF, int(edge) & 0xFFFFFFFF
+    return how
+
+
+def transform_fit(width, height, forward, filter=TransformFilter.Linear, edge=BlurEdge.Transparent):
+    """crh_transform_fit (host only) -> (matrix, (result width, result height), origin): for a source of width x height and `forward`,
+    which maps SOURCE coordinates to the caller's target space (9 floats row-major, or 6 for an affine matrix), the result -> source
+    matrix as a (3, 3) float64 array and the size of the smallest result that holds the whole source, and where the target space's
+    (0, 0) lies in that result."""
+    how, origin = _ffi.TransformC(), (C.c_int32 * 2)()
+    check(_ffi.load_library().crh_transform_fit(int(width) & 0xFFFFFFFF, int(height) & 0xFFFFFFFF, _matrix9(forward), int(filter) & 0xFFFFFFFF, int(edge) & 0xFFFFFFFF, C.byref(how), origin))
+    return np.array(list(how.matrix), dtype=np.float64).reshape(3, 3), (int(how.width), int(how.height)), (int(origin[0]), int(origin[1]))
+
+
+def transform_position(matrix, width, height, i, j):
+    """crh_transform_position (host only) -> (X, Y, visible): where result texel (i, j) of a width x height result reads the source under
+    `matrix` (result -> source), in 1/256 texel, and whether the texel is visible (not behind the horizon of a projective matrix)."""
+    how = _transform_arguments(matrix, width, height, TransformFilter.Nearest, BlurEdge.Transparent)
+    position, visible = (C.c_int32 * 2)(), C.c_uint32()
+    check(_ffi.load_library().crh_transform_position(C.byref(how), int(i) & 0xFFFFFFFF, int(j) & 0xFFFFFFFF, position, C.byref(visible)))
+    return int(position[0]), int(position[1]), bool(visible.value)
+
+
+def transform_texels(pixels, matrix, width, height, filter=TransformFilter.Linear, edge=BlurEdge.Transparent):
+    """crh_transform_texels (host only): the rule of Image.resample on a (height', width', 4) uint8 array -> the (height, width, 4) uint8
+    result (include/contrast_hip.h crh_image_transform states the rule)."""
+    pixels = np.ascontiguousarray(pixels)
+    if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ContrastError(_ffi.ERR_INVALID_ARGUMENT, f"transform_texels takes a (height, width, 4) uint8 array, not {pixels.shape} {pixels.dtype}")
+    how = _transform_arguments(matrix, width, height, filter, edge)
+    legal = 1 <= how.width <= 16384 and 1 <= how.height <= 16384  # (a size the library refuses gets a texel's room and the library's status)
+    out = np.empty((how.height, how.width, 4) if legal else (1, 1, 4), dtype=np.uint8)
+    check(_ffi.load_library().crh_transform_texels(pixels.shape[1], pixels.shape[0], pixels.ctypes.data, C.byref(how), out.ctypes.data))
+    return out
+
+
 class Image:
     """crh_image: width x height texels of premultiplied RGBA8 on the device, row 0 = top — the bytes Frame.download() hands out. `pixels` is a
     [height, width, 4] uint8 array, copied before the constructor returns. One level until generate_mipmaps(): an image drawn much smaller than
@@ -1151,6 +1210,41 @@ class Image:
         handle = C.c_void_p()
         check(self.lib.crh_image_variable_blur(self.handle, mask.handle, C.byref(how), C.byref(handle)))
         return Image._adopt(self.renderer, handle, (self.width, self.height))
+
+    def resample(self, matrix, width, height, filter=TransformFilter.Linear, edge=BlurEdge.Transparent):
+        """crh_image_transform, the raw call -> a new Image of one level, width x height (each in [1, 16384]), origin (0, 0): this image
+        seen through `matrix`, which maps RESULT coordinates (x, y, 1) to coordinates of THIS image (9 floats row-major, or 6 for an
+        affine matrix; finite, |.| <= MAX_TRANSFORM_ENTRY; a singular one is legal). Positions in binary64 in a fixed order, then
+        integers: every byte is defined (include/contrast_hip.h states the rule). TransformFilter.Nearest and .Linear sample as
+        displace() does, .Cubic is Catmull-Rom over 4 x 4 texels; `edge` is what THIS image is outside itself; a texel behind the
+        horizon of a projective matrix is transparent. No prefilter: shrink by more than about 2 with resize() first. Built on the device
+        and complete when this returns (a synchronous call). This image is not modified."""
+        how = _transform_arguments(matrix, width, height, filter, edge)
+        handle = C.c_void_p()
+        check(self.lib.crh_image_transform(self.handle, C.byref(how), C.byref(handle)))
+        return Image._adopt(self.renderer, handle, (int(how.width), int(how.height)))
+
+    def transform(self, forward, filter=TransformFilter.Linear, edge=BlurEdge.Transparent):
+        """transform_fit, then resample: this image moved by `forward`, which maps its coordinates to the caller's target space (9 floats
+        row-major, or 6 for an affine matrix), in the smallest result that holds all of it. The result's `origin` is where the target
+        space's (0, 0) lies in it, by blur()'s and crop()'s convention: composite it at offset = (dx - origin[0], dy - origin[1]) to put
+        target point (0, 0) at (dx, dy). A corner behind the horizon, a singular `forward` and a result above 16384 are refused."""
+        matrix, (width, height), origin = transform_fit(self.width, self.height, forward, filter, edge)
+        image = self.resample(matrix, width, height, filter, edge)
+        image.origin = origin
+        return image
+
+    def rotate(self, degrees, center=None, filter=TransformFilter.Linear, edge=BlurEdge.Transparent):
+        """transform() by a rotation of `degrees`, clockwise on the screen (y points down, as CSS rotate() turns), about `center` (x, y) in
+        this image's coordinates, None = its middle. A multiple of 90 uses the entries 0 and +-1 exactly, so a quarter turn permutes the
+        texels. The result's `origin` is where this image's texel corner (0, 0) would lie had it not been turned."""
+        cx, cy = (self.width / 2.0, self.height / 2.0) if center is None else (float(center[0]), float(center[1]))
+        quarter = float(degrees) / 90.0
+        if quarter == int(quarter):
+            c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(quarter) % 4]
+        else:
+            c, s = math.cos(math.radians(float(degrees))), math.sin(math.radians(float(degrees)))
+        return self.transform((c, -s, cx - c * cx + s * cy, s, c, cy - s * cx - c * cy), filter, edge)
 
     def distance_field(self, spread, mode=DistanceMode.Outside, channel=Channel.A, threshold=128, edge=BlurEdge.Transparent):
         """crh_image_distance_field -> a new Image of one level: for every texel the exact Euclidean distance between texel centres to the

@@ -1136,6 +1136,81 @@ crh_status crh_variable_blur_validate(const crh_variable_blur* how);            
 crh_status crh_variable_blur_sigma(const crh_variable_blur* how, uint32_t code, float* sigma_x, float* sigma_y);              /* host only */
 crh_status crh_variable_blur_texels(uint32_t width, uint32_t height, const void* rgba8, const void* mask_rgba8, const crh_variable_blur* how, void* out_rgba8); /* host only: the rule */
 crh_status crh_image_variable_blur(const crh_image* src, const crh_image* mask, const crh_variable_blur* how, crh_image** out);
+/* Transform: a new image that is `src` seen through a 3 x 3 matrix — rotate, skew or tilt a layer (CSS transform, Canvas drawImage under a
+ * matrix, a card flip) in one call, with a result of any size, three filters and the four edges. The matrix maps RESULT coordinates to
+ * SOURCE coordinates (no inverse is taken; a singular matrix is legal), texel (i, j) covering [i, i + 1) x [j, j + 1).
+ * All real arithmetic below is IEEE binary64, exactly in the written order and parenthesisation, with no contraction, and uses only
+ * + * /, comparisons and floor; everything behind X and Y is integer. The tests check every byte.
+ *   position  of result texel (i, j): u = i + 0.5, v = j + 0.5; xs = (m0 u + m1 v) + m2, ys = (m3 u + m4 v) + m5, ws = (m6 u + m7 v) + m8.
+ *             The call is AFFINE when m6 == 0 && m7 == 0 && m8 == 1: then px = xs, py = ys. Otherwise a texel with !(ws > 0) is NOT
+ *             VISIBLE — its result is (0, 0, 0, 0) under every edge (it lies behind the horizon) — and for the others px = xs / ws,
+ *             py = ys / ws. Clamp by comparisons: p = p < -2097152 ? -2097152 : p > 2097152 ? 2097152 : p. With |m| <= 2^40 and
+ *             u, v < 2^15 every sum is finite, so no NaN can arise, and an infinite quotient clamps. X = (int32) floor(px * 256 + 0.5),
+ *             Y likewise: |X|, |Y| <= 2^29, in units of 1/256 texel. crh_transform_position hands out exactly these (visible 0 or 1;
+ *             the position of an invisible texel is (0, 0)).
+ *   NEAREST   and LINEAR: the value is crh_image_displace's NEAREST and LINEAR of the position (X, Y): S(X >> 8, Y >> 8), or the
+ *             2 x 2 blend around (X - 128, Y - 128) with one rounding. One function serves both calls.
+ *   CUBIC     Catmull-Rom over 4 x 4 texels. ax = X - 128, i0 = ax >> 8, F = ax & 255, the y axis the same. Exact integer weights over
+ *             2^25: W0 = -F^3 + 512 F^2 - 65536 F, W2 = -3 F^3 + 1024 F^2 + 65536 F, W3 = F^3 - 256 F^2, W1 = 2^25 - W0 - W2 - W3;
+ *             c_k = (W_k + 1024) >> 11 (arithmetic) for k = 0, 2, 3 and c_1 = 16384 - c_0 - c_2 - c_3, a 256 x 4 table that is a
+ *             constant of the library. Per channel and footprint row r = j0 - 1 .. j0 + 2:
+ *             h_r = (sum_k c_k(Fx) S(i0 - 1 + k, r) + 32) >> 6, then value = clamp((sum_r c_r(Fy) h_r + 2^21) >> 22, 0, 255), and at
+ *             the end rgb = min(rgb, a), as crh_image_resize does, because negative lobes do not keep rgb <= a. Over all 256 phases:
+ *             -1214 <= c_k <= 16384; the positive weights of a phase sum to at most 18432 and the negative ones to at most 2048 in
+ *             magnitude; -8161 <= h <= 73440; the second numerator is at most 1 372 456 960 < 2^31 in magnitude; a constant image
+ *             comes back exactly at every phase pair.
+ *   S(i, j)   crh_image_displace's S: the source's codes as they are, with no load clamp. Under PAD, REPEAT and REFLECT each index goes
+ *             separately through the image-paint block's wrap(i, n), any number of periods out; under TRANSPARENT the value is
+ *             (0, 0, 0, 0) when either index is outside. Every address is formed from a wrapped or tested index only.
+ * Hence: the identity at the source's size is a byte-for-byte copy under NEAREST and LINEAR and every edge, and under CUBIC a copy of a
+ * premultiplied source (F = 0 gives c = (0, 16384, 0, 0), and only min(rgb, a) can change a texel); an integer translation under
+ * TRANSPARENT is crh_image_crop's bytes; a quarter turn (entries 0 and +-1 and an integer offset) is an exact permutation of the texels
+ * under all three filters; rgb <= a survives every filter for a premultiplied source; an all-zero linear part reads one point.
+ * crh_transform_fit is the call for "rotate this layer by 30 degrees and keep all of it": `forward` maps SOURCE coordinates to the caller's
+ * target space, and the call writes to *out the result size and the result -> source matrix of the smallest result that holds the
+ * whole source, and to `origin` where the target space's (0, 0) lies in that result (blur's and crop's convention). In binary64, in
+ * this order, with (a b c; d e f; g h i) = forward: each corner (x, y) of (0, 0), (w, 0), (0, h), (w, h) gives X = (a x + b y) + c,
+ * Y = (d x + e y) + f, W = (g x + h y) + i; an affine forward (g == 0 && h == 0 && i == 1) takes (X, Y), any other refuses
+ * "a corner is behind the horizon" when !(W > 0) and takes (X / W, Y / W). x0 = floor(min x), x1 = ceil(max x), y likewise; the size is
+ * max(1, x1 - x0) by max(1, y1 - y0), refused as "the result is outside [1, 16384]" when it exceeds 16384 or is not finite, and
+ * "the origin is beyond 2^30" when |x0| or |y0| is; origin = (-x0, -y0). The adjugate, entry by entry:
+ *   A0 = e i - f h   A1 = c h - b i   A2 = b f - c e
+ *   A3 = f g - d i   A4 = a i - c g   A5 = c d - a f
+ *   A6 = d h - e g   A7 = b g - a h   A8 = a e - b d          det = (a A0 + b A3) + c A6
+ * "forward is singular" when det == 0 or a quotient n_k = A_k / det is not finite. The matrix is n composed with the translation by
+ * (x0, y0): entries 0, 1, 3, 4, 6, 7 are n's, and m2 = (n0 x0 + n1 y0) + n2, m5 = (n3 x0 + n4 y0) + n5, m8 = (n6 x0 + n7 y0) + n8; it
+ * is then validated like any other. An affine forward gives A6 = A7 = 0 and A8 = det, so the last row is exactly (0, 0, 1) and the
+ * call takes the affine path.
+ * crh_transform_validate, _fit, _position and crh_transform_texels (the rule on whole images in host memory: width * height * 4 bytes
+ * of the source in the order r g b a at any alignment, row 0 first, to how->width * how->height * 4 bytes) are host only: no renderer,
+ * no device.
+ * Every error is found before the device is touched, and a refused call writes nothing and leaves *out untouched, in this order: a null
+ * argument is CRH_ERR_INVALID_ARGUMENT; then a filter above CRH_TRANSFORM_CUBIC or an edge above CRH_BLUR_EDGE_REFLECT; then a non-finite
+ * entry is CRH_ERR_NON_FINITE; then an entry above CRH_MAX_TRANSFORM_ENTRY in magnitude, a result size (and the source's) outside
+ * [1, 16384], a texel outside the result in crh_transform_position, and out_rgba8 equal to the input in crh_transform_texels are
+ * CRH_ERR_INVALID_ARGUMENT, each with a crh_last_error text "crh_transform_validate: ...". crh_transform_fit checks `forward` by the same
+ * rows before its own refusals.
+ * crh_image_transform runs k_image_transform on the renderer's stream, specialised on the filter, on TRANSPARENT against the wrapping
+ * edges and on affine against projective; it allocates nothing but the result, which has one level (crh_image_generate_mipmaps works on
+ * it) and origin (0, 0); only level 0 of the source is read and it is not modified. A failed allocation or launch frees everything and
+ * returns CRH_ERR_HIP.
+ * Limits: no prefilter — a minification beyond about 2 x aliases: crh_image_resize or crh_image_generate_mipmaps first; the call is
+ * synchronous, like its siblings; the codes are used as they are, with no gamma handling; this is not a per-draw effect of the raster
+ * path. */
+typedef enum crh_transform_filter { CRH_TRANSFORM_NEAREST = 0, CRH_TRANSFORM_LINEAR = 1, CRH_TRANSFORM_CUBIC = 2 } crh_transform_filter;
+#define CRH_MAX_TRANSFORM_ENTRY 1099511627776.0 /* 2^40 */
+typedef struct crh_transform {
+    double matrix[9];       /* row-major 3 x 3: RESULT coordinates (x, y, 1) -> SOURCE coordinates; finite, |.| <= 2^40 */
+    uint32_t width, height; /* of the result, each in [1, 16384] */
+    uint32_t filter;        /* crh_transform_filter */
+    uint32_t edge;          /* crh_blur_edge: what the source is outside itself */
+} crh_transform;
+crh_status crh_transform_validate(const crh_transform* how);                                   /* host only */
+crh_status crh_transform_fit(uint32_t width, uint32_t height, const double forward[9], uint32_t filter, uint32_t edge,
+                             crh_transform* out, int32_t origin[2]);                          /* host only */
+crh_status crh_transform_position(const crh_transform* how, uint32_t i, uint32_t j, int32_t position[2], uint32_t* visible); /* host only */
+crh_status crh_transform_texels(uint32_t width, uint32_t height, const void* rgba8, const crh_transform* how, void* out_rgba8); /* host only */
+crh_status crh_image_transform(const crh_image* src, const crh_transform* how, crh_image** out);
 typedef struct crh_image_paint {
     const crh_image* image;
     uint32_t filter;             /* CRH_FILTER_NEAREST or _LINEAR, optionally | CRH_FILTER_MIPMAP */

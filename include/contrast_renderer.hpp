@@ -890,6 +890,63 @@ inline void variable_blur_validate(const VariableBlur& blur) {
     const crh_variable_blur how = blur.to_c();
     check(crh_variable_blur_validate(&how));
 }
+// Transform (include/contrast_hip.h crh_image_transform states the rule): an image seen through a 3 x 3 matrix, in a result of any size.
+enum class TransformFilter : uint32_t { Nearest = CRH_TRANSFORM_NEAREST, Linear = CRH_TRANSFORM_LINEAR, Cubic = CRH_TRANSFORM_CUBIC };
+// The fields of crh_transform: the matrix that maps RESULT coordinates (x, y, 1) to SOURCE coordinates, row-major (the identity by
+// default), the result's size, the filter and what the SOURCE is outside itself.
+struct Transform {
+    std::array<double, 9> matrix = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    uint32_t width = 1, height = 1;
+    TransformFilter filter = TransformFilter::Linear;
+    BlurEdge edge = BlurEdge::Transparent;
+    crh_transform to_c() const {
+        crh_transform how = {};
+        for (size_t k = 0; k < 9; ++k) how.matrix[k] = matrix[k];
+        how.width = width, how.height = height, how.filter = (uint32_t)filter, how.edge = (uint32_t)edge;
+        return how;
+    }
+};
+// What crh_transform_fit gives: the call that holds the whole source moved by `forward`, and where the target space's (0, 0) lies in its result
+struct TransformFit {
+    Transform transform;
+    std::array<int32_t, 2> origin = {0, 0};
+};
+// crh_transform_validate (host only): throws what Image::resample would refuse of the fields
+inline void transform_validate(const Transform& transform) {
+    const crh_transform how = transform.to_c();
+    check(crh_transform_validate(&how));
+}
+// crh_transform_fit (host only): `forward` maps the coordinates of a width x height source to the caller's target space
+inline TransformFit transform_fit(uint32_t width, uint32_t height, const std::array<double, 9>& forward, TransformFilter filter = TransformFilter::Linear, BlurEdge edge = BlurEdge::Transparent) {
+    crh_transform how = {};
+    TransformFit fit;
+    check(crh_transform_fit(width, height, forward.data(), (uint32_t)filter, (uint32_t)edge, &how, fit.origin.data()));
+    for (size_t k = 0; k < 9; ++k) fit.transform.matrix[k] = how.matrix[k];
+    fit.transform.width = how.width, fit.transform.height = how.height, fit.transform.filter = filter, fit.transform.edge = edge;
+    return fit;
+}
+// crh_transform_position (host only): where result texel (i, j) reads the source, in 1/256 texel, and whether it is visible
+struct TransformPosition {
+    std::array<int32_t, 2> position = {0, 0};
+    bool visible = false;
+};
+inline TransformPosition transform_position(const Transform& transform, uint32_t i, uint32_t j) {
+    const crh_transform how = transform.to_c();
+    TransformPosition at;
+    uint32_t visible = 0;
+    check(crh_transform_position(&how, i, j, at.position.data(), &visible));
+    at.visible = visible != 0u;
+    return at;
+}
+// crh_transform_texels (host only): the rule on the width * height * 4 bytes of a source -> the transform.width * transform.height * 4 bytes of the result
+inline std::vector<uint8_t> transform_texels(uint32_t width, uint32_t height, const std::vector<uint8_t>& texels, const Transform& transform) {
+    if (texels.size() != (size_t)width * height * 4u) throw Error(CRH_ERR_INVALID_ARGUMENT);
+    const crh_transform how = transform.to_c();
+    transform_validate(transform); // (the result's size before its room is taken)
+    std::vector<uint8_t> out((size_t)how.width * how.height * 4u);
+    check(crh_transform_texels(width, height, texels.data(), &how, out.data()));
+    return out;
+}
 // Distance fields (include/contrast_hip.h crh_image_distance_field states the rule): the exact Euclidean distance to a shape in 8 bits over a spread.
 enum class DistanceMode : uint32_t { Outside = CRH_DISTANCE_OUTSIDE, Inside = CRH_DISTANCE_INSIDE };
 // The fields of crh_distance: what the distance is measured to (Outside: the shape, 255 on it and 0 at the spread; Inside: what is not the
@@ -1100,6 +1157,38 @@ class Image {
         check(crh_image_displace(handle_, map.handle_, &how, &image.handle_));
         image.width_ = width_, image.height_ = height_;
         return image;
+    }
+    // crh_image_transform, the raw call -> a new Image of one level, transform.width x transform.height, origin (0, 0): this image seen through
+    // transform.matrix (result -> this image); positions in binary64 in a fixed order, then integers; complete on return (a synchronous call).
+    // This image is not modified.
+    Image resample(const Transform& transform) const {
+        const crh_transform how = transform.to_c();
+        Image image;
+        check(crh_image_transform(handle_, &how, &image.handle_));
+        image.width_ = how.width, image.height_ = how.height;
+        return image;
+    }
+    // transform_fit, then resample: this image moved by `forward` (its coordinates -> the caller's target space) in the smallest result that
+    // holds all of it; the result's origin is where the target space's (0, 0) lies in it (two's complement when negative, as a crop's).
+    Image transform(const std::array<double, 9>& forward, TransformFilter filter = TransformFilter::Linear, BlurEdge edge = BlurEdge::Transparent) const {
+        const TransformFit fit = transform_fit(width_, height_, forward, filter, edge);
+        Image image = resample(fit.transform);
+        image.origin_ = {(uint32_t)fit.origin[0], (uint32_t)fit.origin[1]};
+        return image;
+    }
+    // transform() by a rotation of `degrees`, clockwise on the screen (y points down), about (cx, cy) in this image's coordinates; a multiple
+    // of 90 uses the entries 0 and +-1 exactly.
+    Image rotate(double degrees, double cx, double cy, TransformFilter filter = TransformFilter::Linear, BlurEdge edge = BlurEdge::Transparent) const {
+        const double quarter = degrees / 90.0, radians = degrees * 3.14159265358979323846 / 180.0;
+        double c = std::cos(radians), s = std::sin(radians);
+        if (quarter == std::floor(quarter)) {
+            const int turn = (int)std::fmod(std::fmod(quarter, 4.0) + 4.0, 4.0);
+            c = turn == 0 ? 1.0 : turn == 2 ? -1.0 : 0.0, s = turn == 1 ? 1.0 : turn == 3 ? -1.0 : 0.0;
+        }
+        return transform({c, -s, cx - c * cx + s * cy, s, c, cy - s * cx - c * cy, 0.0, 0.0, 1.0}, filter, edge);
+    }
+    Image rotate(double degrees, TransformFilter filter = TransformFilter::Linear, BlurEdge edge = BlurEdge::Transparent) const {
+        return rotate(degrees, width_ / 2.0, height_ / 2.0, filter, edge);
     }
     // crh_image_variable_blur -> a new Image of one level, of this image's size under every edge, origin (0, 0): blur() with the taps of each
     // texel's own level, the stored code of `blur.channel` of `mask`, an image of the same size and renderer; integer and bit-exact,

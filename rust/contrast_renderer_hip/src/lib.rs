@@ -1156,6 +1156,64 @@ pub fn variable_blur_texels(width: u32, height: u32, texels: &[u8], mask: &[u8],
     status(unsafe { ffi::crh_variable_blur_texels(width, height, texels.as_ptr() as *const _, mask.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
     Ok(out)
 }
+/// `crh_transform_filter`
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum TransformFilter {
+    Nearest = 0,
+    Linear = 1,
+    /// Catmull-Rom over 4 x 4 texels
+    Cubic = 2,
+}
+/// The fields of `crh_transform` (include/contrast_hip.h, `crh_image_transform`, states the rule): the matrix that maps RESULT coordinates
+/// (x, y, 1) to SOURCE coordinates, row-major, the result's size, the filter and what the SOURCE is outside itself.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct Transform {
+    pub matrix: [f64; 9],
+    pub width: u32,
+    pub height: u32,
+    pub filter: TransformFilter,
+    pub edge: BlurEdge,
+}
+impl Default for Transform {
+    fn default() -> Transform {
+        Transform { matrix: [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0], width: 1, height: 1, filter: TransformFilter::Linear, edge: BlurEdge::Transparent }
+    }
+}
+impl Transform {
+    fn to_c(&self) -> ffi::crh_transform {
+        ffi::crh_transform { matrix: self.matrix, width: self.width, height: self.height, filter: self.filter as u32, edge: self.edge as u32 }
+    }
+}
+/// `crh_transform_validate` (host only): what `Image::resample` would refuse of the fields
+pub fn transform_validate(transform: &Transform) -> Result<(), Error> {
+    let how = transform.to_c();
+    status(unsafe { ffi::crh_transform_validate(&how) })
+}
+/// `crh_transform_fit` (host only): for a width x height source and `forward`, which maps SOURCE coordinates to the caller's target space,
+/// the call whose result holds the whole source, and where the target space's (0, 0) lies in that result
+pub fn transform_fit(width: u32, height: u32, forward: &[f64; 9], filter: TransformFilter, edge: BlurEdge) -> Result<(Transform, [i32; 2]), Error> {
+    let mut how = Transform::default().to_c();
+    let mut origin = [0i32; 2];
+    status(unsafe { ffi::crh_transform_fit(width, height, forward.as_ptr(), filter as u32, edge as u32, &mut how, origin.as_mut_ptr()) })?;
+    Ok((Transform { matrix: how.matrix, width: how.width, height: how.height, filter, edge }, origin))
+}
+/// `crh_transform_position` (host only) -> where result texel (i, j) reads the source, in 1/256 texel, and whether the texel is visible
+pub fn transform_position(transform: &Transform, i: u32, j: u32) -> Result<([i32; 2], bool), Error> {
+    let how = transform.to_c();
+    let mut position = [0i32; 2];
+    let mut visible = 0u32;
+    status(unsafe { ffi::crh_transform_position(&how, i, j, position.as_mut_ptr(), &mut visible) })?;
+    Ok((position, visible != 0))
+}
+/// `crh_transform_texels` (host only): the rule on the width * height * 4 bytes of a source -> the bytes of the result
+pub fn transform_texels(width: u32, height: u32, texels: &[u8], transform: &Transform) -> Result<Vec<u8>, Error> {
+    assert_eq!(texels.len(), width as usize * height as usize * 4);
+    transform_validate(transform)?;
+    let how = transform.to_c();
+    let mut out = vec![0u8; transform.width as usize * transform.height as usize * 4];
+    status(unsafe { ffi::crh_transform_texels(width, height, texels.as_ptr() as *const _, &how, out.as_mut_ptr() as *mut _) })?;
+    Ok(out)
+}
 /// `crh_distance_mode`: what the distance is measured to
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum DistanceMode {
@@ -1445,6 +1503,35 @@ impl Image {
         let mut raw = ptr::null_mut();
         status(unsafe { ffi::crh_image_displace(self.raw, map.raw, &how, &mut raw) })?;
         Ok(Image { raw, width: self.width, height: self.height, origin: (0, 0) })
+    }
+    /// `crh_image_transform`, the raw call -> a new `Image` of one level, `transform.width` x `transform.height`, origin (0, 0): this image
+    /// seen through `transform.matrix` (result -> this image); positions in binary64 in a fixed order, then integers; complete on return (a
+    /// synchronous call). This image is not modified.
+    pub fn resample(&self, transform: &Transform) -> Result<Image, Error> {
+        let how = transform.to_c();
+        let mut raw = ptr::null_mut();
+        status(unsafe { ffi::crh_image_transform(self.raw, &how, &mut raw) })?;
+        Ok(Image { raw, width: transform.width, height: transform.height, origin: (0, 0) })
+    }
+    /// `transform_fit`, then `resample`: this image moved by `forward` (its coordinates -> the caller's target space) in the smallest result
+    /// that holds all of it; the result's origin is where the target space's (0, 0) lies in it (two's complement when negative, as a crop's).
+    pub fn transform(&self, forward: &[f64; 9], filter: TransformFilter, edge: BlurEdge) -> Result<Image, Error> {
+        let (fitted, origin) = transform_fit(self.width, self.height, forward, filter, edge)?;
+        let mut image = self.resample(&fitted)?;
+        image.origin = (origin[0] as u32, origin[1] as u32);
+        Ok(image)
+    }
+    /// `transform` by a rotation of `degrees`, clockwise on the screen (y points down), about `center` in this image's coordinates, `None` =
+    /// its middle; a multiple of 90 uses the entries 0 and +-1 exactly.
+    pub fn rotate(&self, degrees: f64, center: Option<[f64; 2]>, filter: TransformFilter, edge: BlurEdge) -> Result<Image, Error> {
+        let [cx, cy] = center.unwrap_or([self.width as f64 / 2.0, self.height as f64 / 2.0]);
+        let quarter = degrees / 90.0;
+        let (c, s) = if quarter == quarter.floor() {
+            [(1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)][quarter.rem_euclid(4.0) as usize]
+        } else {
+            (degrees.to_radians().cos(), degrees.to_radians().sin())
+        };
+        self.transform(&[c, -s, cx - c * cx + s * cy, s, c, cy - s * cx - c * cy, 0.0, 0.0, 1.0], filter, edge)
     }
     /// `crh_image_variable_blur` -> a new `Image` of one level, of this image's size under every edge, origin (0, 0): `blur` with the taps
     /// of each texel's own level, the stored code of `blur.channel` of `mask`, an image of the same size and renderer; integer and
