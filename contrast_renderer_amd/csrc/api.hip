@@ -21,6 +21,7 @@
 #include "launch.hpp"
 #include "raster_params.hpp"
 #include "scene.hpp"
+#include "tess_streams.hpp"
 
 using namespace crh;
 
@@ -54,71 +55,43 @@ struct DevBuf {
     }
 };
 
-// Host -> device copies that must not stall the host: pageable memory makes hipMemcpyAsync wait for the stream, so the bytes are first
-// copied into one of two pinned staging buffers (the previous use of that buffer — two uploads ago — is waited for, normally long done)
-// and sent from there.
-struct PinnedUpload {
+// Host -> device copies that must not stall the host: pageable memory makes hipMemcpyAsync wait for the stream, so the bytes go through one
+// of two pinned staging slots, taken in turn. A slot is guarded by the event behind the copies that read it — its previous use, two takes ago and
+// normally long done, is waited for before it is handed out — so the call that filled it need not wait for them. Two ways to fill one: copy()
+// (memcpy, then send), or begin() / done() around a caller that writes in place (crh_scene_upload builds the element stream straight into it).
+// One object is used one way: done() records for the slot taken last, so a copy() between a begin() and its done() would leave that slot unguarded.
+struct PinnedPair {
     void* host[2] = {nullptr, nullptr};
     size_t cap[2] = {0, 0};
     hipEvent_t sent[2] = {nullptr, nullptr};
-    int next = 0;
-    hipError_t copy(void* dst, const void* src, size_t bytes, hipStream_t stream) {
-        if (bytes == 0) return hipSuccess;
-        const int k = next;
+    int next = 0, cur = 0;
+    // the next slot, at least `bytes` large: one that has to grow is allocated with `grown` bytes
+    hipError_t take(size_t bytes, size_t grown, uint8_t** out) {
+        const int k = cur = next;
         next ^= 1;
         hipError_t e;
         if (!sent[k] && (e = hipEventCreateWithFlags(&sent[k], hipEventDisableTiming)) != hipSuccess) return e;
         if (cap[k] && (e = hipEventSynchronize(sent[k])) != hipSuccess) return e;
         if (cap[k] < bytes) {
             if (host[k]) (void)hipHostFree(host[k]);
-            host[k] = nullptr;
-            cap[k] = 0;
-            if ((e = hipHostMalloc(&host[k], bytes, hipHostMallocDefault)) != hipSuccess) return e;
-            cap[k] = bytes;
-        }
-        memcpy(host[k], src, bytes);
-        if ((e = hipMemcpyAsync(dst, host[k], bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-        return hipEventRecord(sent[k], stream);
-    }
-    void release() {
-        for (int k = 0; k < 2; ++k) {
-            if (sent[k]) {
-                (void)hipEventSynchronize(sent[k]);
-                (void)hipEventDestroy(sent[k]);
-            }
-            if (host[k]) (void)hipHostFree(host[k]);
-            host[k] = nullptr;
-            sent[k] = nullptr;
-            cap[k] = 0;
-        }
-    }
-};
-
-// Pinned staging memory a caller fills in place (crh_scene_upload builds the element stream straight into it): two arenas in turn, each guarded
-// by the event behind the copies that read it, so the call that filled it need not wait for them.
-struct PinnedArena {
-    void* host[2] = {nullptr, nullptr};
-    size_t cap[2] = {0, 0};
-    hipEvent_t sent[2] = {nullptr, nullptr};
-    int next = 0, cur = 0;
-    hipError_t begin(size_t bytes, uint8_t** out) {
-        const int k = next;
-        next ^= 1;
-        cur = k;
-        hipError_t e;
-        if (!sent[k] && (e = hipEventCreateWithFlags(&sent[k], hipEventDisableTiming)) != hipSuccess) return e;
-        if (cap[k] && (e = hipEventSynchronize(sent[k])) != hipSuccess) return e; // (the copies out of it two uploads ago: long done)
-        if (cap[k] < bytes) {
-            if (host[k]) (void)hipHostFree(host[k]);
             host[k] = nullptr, cap[k] = 0;
-            const size_t want = bytes + bytes / 4 + 4096;
-            if ((e = hipHostMalloc(&host[k], want, hipHostMallocDefault)) != hipSuccess) return e;
-            cap[k] = want;
+            if ((e = hipHostMalloc(&host[k], grown, hipHostMallocDefault)) != hipSuccess) return e;
+            cap[k] = grown;
         }
         *out = static_cast<uint8_t*>(host[k]);
         return hipSuccess;
     }
+    hipError_t begin(size_t bytes, uint8_t** out) { return take(bytes, bytes + bytes / 4 + 4096, out); }
     hipError_t done(hipStream_t stream) { return hipEventRecord(sent[cur], stream); }
+    hipError_t copy(void* dst, const void* src, size_t bytes, hipStream_t stream) {
+        if (bytes == 0) return hipSuccess;
+        uint8_t* staged;
+        hipError_t e;
+        if ((e = take(bytes, bytes, &staged)) != hipSuccess) return e;
+        memcpy(staged, src, bytes);
+        if ((e = hipMemcpyAsync(dst, staged, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+        return done(stream);
+    }
     void release() {
         for (int k = 0; k < 2; ++k) {
             if (sent[k]) {
@@ -314,7 +287,7 @@ struct crh_frame {
     uint32_t items_total_slots = 0;
     DevBuf item_transforms_b, item_colors_b; // second set of instance data: a re-submitted pass writes the set its predecessor did not read
     int item_inst_cur = 0, item_inst_last = 0, item_projective_of[2] = {0, 0}, item_tame_of[2] = {0, 0};
-    PinnedUpload item_upload_t, item_upload_c;
+    PinnedPair item_upload_t, item_upload_c;
     InstanceSlot item_slot[2];
     uint32_t n_items = 0;
     int last_instances = 0;        // which of the scene's two instance buffers the last plain pass read
@@ -403,7 +376,49 @@ struct crh_frame {
     uint64_t triangle_pass_generation = 0; // ... of that Scene's geometry: a re-upload (or a new Scene at the same address) starts on the edge pass again
 };
 
-constexpr int kTessBufs = 33; // buffers a tessellation run writes (crh_scene::tess_bufs)
+namespace {
+// Everything a tessellation run writes, and what orders the run against its readers. It exists twice once a Scene is tessellated again (animated
+// paths, the benchmark step): the run for frame i + 1 fills the set that frame i does NOT read, so it overlaps frame i's binning instead of
+// waiting for it (with one set the chain tessellate -> bin of consecutive frames was serial and, not the raster kernel, set the frame rate).
+// A Scene holds both (crh_scene::tess_set) and the index of the current one; flip_tess_set() toggles it and re-binds the pointers of `d`.
+struct TessSet {
+    // scan state
+    DevBuf elem_scan, wg_total, wg_base, group_base, totals, shape_base, hull_count, hull_large, hull_sort, hull_chain, status;
+    // outputs: the eleven streams of tess_streams.hpp (kStream below) and what the kernels keep beside them
+    DevBuf line_v, joint_v, solid_v, iq_v, ic_v, rq_v, rc_v, hull_cand, hull_v, line_i, joint_i, solid_i, solid_flag, line_pair_cut, line_pair_mode, line_inc;
+    // binning: primitives and, for the edge pass, slots of the primitive heap per Shape (transform independent, so they belong to the tessellation)
+    DevBuf shape_ncand, shape_prim_begin, prim_scan_scratch, shape_nslots, shape_slot_begin, path_scan;
+    // frame pipelining: tessellation runs on its own stream; these events order it against the raster stream
+    hipEvent_t tess_done = nullptr;     // recorded on the tessellation stream after the last tessellation kernel
+    hipEvent_t vertices_free = nullptr; // recorded on the raster stream after k_prim_setup (last reader of the vertex streams and hulls)
+    hipEvent_t ranges_free = nullptr;   // recorded on the raster stream after the fill pass (last reader of the primitive ranges)
+    bool allocated = false;             // its buffers are sized for the uploaded structure (crh_scene_upload the current set, flip_tess_set the other one)
+    bool capacity_known = false, rendered_once = false;
+    bool last_render_one_event = false; // the last render that READ this set recorded ONE event (vertices_free) for everything behind its binning:
+                                        // the next tessellation into this set need not wait for ranges_free as well
+    uint32_t totals_host[NCH] = {};
+    uint32_t cap_host[NCH] = {};   // records every stream of this set holds (ensure_outputs: the totals + a sixteenth + 64) — what d.capacity says while it is current
+    uint64_t emitted_bytes = 0;
+
+    // THE list of the buffers: what release() frees and what flip_tess_set sizes the other set by, in this order
+    static constexpr DevBuf TessSet::*kBuffers[] = {
+        &TessSet::elem_scan, &TessSet::wg_total, &TessSet::wg_base, &TessSet::group_base, &TessSet::totals, &TessSet::shape_base, &TessSet::hull_count, &TessSet::hull_large,
+        &TessSet::hull_sort, &TessSet::hull_chain, &TessSet::status, &TessSet::line_v, &TessSet::joint_v, &TessSet::solid_v, &TessSet::iq_v, &TessSet::ic_v, &TessSet::rq_v,
+        &TessSet::rc_v, &TessSet::hull_cand, &TessSet::hull_v, &TessSet::line_i, &TessSet::joint_i, &TessSet::solid_i, &TessSet::solid_flag, &TessSet::line_pair_cut,
+        &TessSet::line_pair_mode, &TessSet::line_inc, &TessSet::shape_ncand, &TessSet::shape_prim_begin, &TessSet::prim_scan_scratch, &TessSet::shape_nslots,
+        &TessSet::shape_slot_begin, &TessSet::path_scan};
+    // the buffer of every stream of tess_streams.hpp's table
+    static constexpr DevBuf TessSet::*kStream[kTessStreams] = {&TessSet::line_v, &TessSet::joint_v, &TessSet::solid_v, &TessSet::iq_v, &TessSet::ic_v, &TessSet::rq_v,
+                                                              &TessSet::rc_v, &TessSet::hull_v, &TessSet::line_i, &TessSet::joint_i, &TessSet::solid_i};
+    void release() {
+        for (DevBuf TessSet::*b : kBuffers) (this->*b).release();
+        allocated = false;
+    }
+};
+// A count check, no more: the buffers are the leading members, so one declared in front of the events and left out of the list does not compile.
+// (A buffer listed twice in another's place, or declared behind the events, is not seen.)
+static_assert(sizeof(TessSet::kBuffers) / sizeof(*TessSet::kBuffers) * sizeof(DevBuf) == offsetof(TessSet, tess_done), "TessSet::kBuffers has as many entries as the set has buffers");
+} // namespace
 
 struct crh_scene {
     crh_renderer* renderer; // nullptr once the renderer has been destroyed (only crh_scene_destroy is valid then)
@@ -412,11 +427,12 @@ struct crh_scene {
     uint32_t n_segments = 0;
     bool has_stroke = false, big_shapes = false;
     uint64_t structure_hash = 0; // of shape_path_begin and path_segment_begin of the uploaded batch (crh_scene_upload: same_structure)
-    bool capacity_known = false;
     uint64_t instances_version = 0; // counts crh_scene_set_instances calls
-    uint64_t input_bytes = 0, emitted_bytes = 0;
-    uint32_t totals_host[NCH] = {};
-    uint32_t cap_host[NCH] = {};   // records every stream of the current set holds (ensure_outputs: the totals + a sixteenth + 64) — what d.capacity says
+    uint64_t input_bytes = 0;
+    TessSet tess_set[2]; // what a tessellation run writes: the set the latest run filled (the one `d` points into) and the one the run before it did
+    int tess_cur = 0;
+    TessSet& tess() { return tess_set[tess_cur]; }
+    TessSet& other_tess() { return tess_set[tess_cur ^ 1]; }
     // New paths of the SAME STRUCTURE (as many Shapes, paths, elements: an animation of control points) uploaded into a Scene whose streams
     // are sized: the capacities are kept and the tessellation runs without the host waiting for its totals (`optimistic`; until something
     // synchronises, totals_host holds the capacities — upper bounds). A run that does not fit raises the overflow code and emits nothing;
@@ -437,21 +453,16 @@ struct crh_scene {
     uint64_t bounds_generation = 0;  // ... of which upload (the same paths tessellate to the same hulls: once per upload, by the first pass with a slab)
     DevBuf geometry; // the uploaded element stream: ONE arena (the layout of crh_scene_upload's pinned staging arena), one copy
     DevBuf elem_cnt, run_base; // the one-pass tessellation: runs of Shapes, every element's packed counts, the runs' bases (scene.hpp) — per upload
-    // scan state
-    DevBuf elem_scan, wg_total, wg_base, group_base, totals, shape_base, hull_count, hull_large, hull_sort, hull_chain, status, path_scan;
-    // outputs
-    DevBuf line_v, joint_v, solid_v, iq_v, ic_v, rq_v, rc_v, hull_cand, hull_v, line_i, joint_i, solid_i, solid_flag, line_pair_cut, line_pair_mode, line_inc;
     // instances + binning
-    DevBuf transforms, colors, shape_ncand, shape_prim_begin, prim_scan_scratch;
-    DevBuf shape_nslots, shape_slot_begin; // the edge pass: slots of the primitive heap per Shape (transform independent, like shape_prim_begin)
+    DevBuf transforms, colors;
     DevBuf prim_rec[kPipelineDepth];    // set-up triangles, one buffer per frame in flight like the frame's binning buffers
     DevBuf prim_proj[kPipelineDepth];                // 1/w and z/w planes of the primitives of projective instances (allocated on first use)
     bool instances_projective = false;  // of the current instance buffer
     // Instance data is double-buffered: crh_scene_set_instances writes the buffer the latest frame did NOT use, so that frame — whose
     // deferred tile-list check may still ask for it to be drawn again — needs no wait; only a frame two updates old is settled first.
     DevBuf transforms_b, colors_b;
-    PinnedUpload upload_t, upload_c;
-    PinnedArena geometry_stage;          // crh_scene_upload's element stream on its way to the device
+    PinnedPair upload_t, upload_c;
+    PinnedPair geometry_stage;           // crh_scene_upload's element stream on its way to the device
     hipEvent_t geometry_ready = nullptr; // behind those copies (on the renderer's stream); the next tessellation waits for it once
     bool geometry_pending = false, tessellated_once_before_upload = false;
     UploadBuild pending_build = {}; // what the first tessellation behind an upload builds the element stream from (launch_build_elements)
@@ -461,8 +472,6 @@ struct crh_scene {
     bool instances_projective_of[2] = {false, false};
     bool instances_tame_of[2] = {false, false}; // all_colors_tame of that instance buffer
     hipEvent_t rec_raster_done[kPipelineDepth] = {};
-    bool last_render_one_event = false; // the last render that READ the current tessellation set recorded ONE event (vertices_free) for everything behind its binning:
-                                        // the next tessellation into this set need not wait for ranges_free as well. Per set: flip_tess_set swaps it with the shadow's
     uint64_t rec_raster_serial[kPipelineDepth] = {}; // the render call that recorded it (crh_renderer::render_serial)
     bool rec_used[kPipelineDepth] = {};
     bool rec_used_ever[kPipelineDepth] = {}; // rec_raster_done[k] has been recorded (crh_scene_upload orders its copy behind them: rec_used is reset by every upload)
@@ -481,22 +490,6 @@ struct crh_scene {
     std::vector<uint32_t> mip_paints;           // the association indices of those paints
     DevBuf image_paints;                        // [n_image_paints] ImagePaintRec
     std::vector<std::shared_ptr<ImagePixels>> image_pixels;
-    // frame pipelining: tessellation runs on its own stream; these events order it against the raster stream
-    hipEvent_t tess_done = nullptr;     // recorded on the tessellation stream after the last tessellation kernel
-    hipEvent_t vertices_free = nullptr; // recorded on the raster stream after k_prim_setup (last reader of the vertex streams and hulls)
-    hipEvent_t ranges_free = nullptr;   // recorded on the raster stream after the fill pass (last reader of the primitive ranges)
-    bool rendered_once = false;
-    // Everything a tessellation run writes exists twice once a Scene is tessellated again (animated paths, the benchmark step): the run
-    // for frame i + 1 fills the set that frame i does NOT read, so it overlaps frame i's binning instead of waiting for it (with one set
-    // the chain tessellate -> bin of consecutive frames was serial and, not the raster kernel, set the frame rate). The members above are
-    // the current set; flip_tess_set() swaps them with this one and re-binds the pointers of `d`.
-    struct TessShadow {
-        DevBuf buf[kTessBufs];
-        hipEvent_t tess_done = nullptr, vertices_free = nullptr, ranges_free = nullptr;
-        bool allocated = false, capacity_known = false, rendered_once = false, last_render_one_event = false;
-        uint32_t totals_host[NCH] = {}, cap_host[NCH] = {};
-        uint64_t emitted_bytes = 0;
-    } shadow;
     bool tessellated_once = false;
     uint64_t tess_runs = 0; // tessellation runs so far: two passes that draw the same run read the same set, and its vertices_free names the later one only (render_impl: such a pass is ordered)
     // Which formulation draws this Scene's plain passes — boundary edges + backdrops (bin_edges.hip, raster_edges.hip) or the reference's strip triangles
@@ -520,24 +513,13 @@ struct crh_scene {
     uint8_t pass_known[16] = {}; // choices already measured, by size class: a Scene drawn into a large frame and a thumbnail in turn measures twice, not for ever
     uint32_t pass_geometry = 0; // what the choices were measured on: (log2 of the Shape count, log2 of the segment count) — an upload of geometry of the same class keeps them
     float pass_ms[3] = {0.0f, 0.0f, 0.0f};
-    void tess_bufs(DevBuf* (&out)[kTessBufs]) {
-        DevBuf* all[kTessBufs] = {&elem_scan, &wg_total, &wg_base, &group_base, &totals, &shape_base, &hull_count, &hull_large, &hull_sort, &hull_chain, &status, &line_v, &joint_v,
-                                  &solid_v, &iq_v, &ic_v, &rq_v, &rc_v, &hull_cand, &hull_v, &line_i, &joint_i, &solid_i, &solid_flag, &line_pair_cut, &line_pair_mode,
-                                  &line_inc, &shape_ncand, &shape_prim_begin, &prim_scan_scratch, &shape_nslots, &shape_slot_begin, &path_scan};
-        for (int i = 0; i < kTessBufs; ++i) out[i] = all[i];
-    }
     // host copies for the parity taps
     std::vector<uint32_t> shape_base_host, hull_count_host;
     bool layout_valid = false;
 
     void release_all() {
-        DevBuf* all[] = {&geometry, &shape_bounds, &elem_cnt, &run_base, &path_scan,
-                         &elem_scan, &wg_total, &wg_base, &group_base, &totals, &shape_base, &hull_count, &hull_large, &hull_sort, &hull_chain, &status, &line_v, &joint_v,
-                         &solid_v, &iq_v, &ic_v, &rq_v, &rc_v, &hull_cand, &hull_v, &line_i, &joint_i, &solid_i, &solid_flag, &line_pair_cut,
-                         &line_pair_mode, &line_inc, &transforms, &colors, &transforms_b, &colors_b, &shape_ncand, &shape_prim_begin, &prim_scan_scratch, &shape_nslots, &shape_slot_begin};
-        for (DevBuf* b : all) b->release();
-        for (DevBuf& b : shadow.buf) b.release();
-        shadow.allocated = false;
+        for (DevBuf* b : {&geometry, &shape_bounds, &elem_cnt, &run_base, &transforms, &colors, &transforms_b, &colors_b}) b->release();
+        for (TessSet& t : tess_set) t.release();
         for (DevBuf& b : prim_rec) b.release();
         for (DevBuf& b : prim_proj) b.release();
         for (DevBuf& b : paint_items) b.release();
@@ -591,8 +573,7 @@ crh_status upload_vector(DevBuf& buf, const std::vector<T>& v, hipStream_t strea
     return CRH_OK;
 }
 
-crh_status decode_status(crh_scene* scene, uint32_t word) {
-    (void)scene;
+crh_status decode_status(uint32_t word) {
     if (word == 0xFFFFFFFFu) return CRH_OK;
     const uint32_t code = word & 0xFFu;
     if (code >= 0x80u) return CRH_ERR_UNSUPPORTED;
@@ -602,107 +583,87 @@ crh_status decode_status(crh_scene* scene, uint32_t word) {
 // the pointers of sc->d into the (current) set of tessellation buffers
 void bind_tess_pointers(crh_scene* sc) {
     SceneDev& d = sc->d;
-    d.elem_scan = sc->elem_scan.as<ElemScan>();
-    d.wg_total = sc->wg_total.as<uint32_t>();
-    d.wg_base = sc->wg_base.as<uint32_t>();
-    d.group_base = sc->group_base.as<uint32_t>();
-    d.totals = sc->totals.as<uint32_t>();
-    d.shape_base = sc->shape_base.as<uint32_t>();
-    d.path_scan = sc->path_scan.as<uint32_t>();
-    d.hull_count = sc->hull_count.as<uint32_t>();
-    d.hull_large_count = sc->hull_large.as<uint32_t>();
-    d.hull_large_list = sc->hull_large.as<uint32_t>() + 4;
-    d.status = sc->status.as<uint32_t>();
-    d.line_v = sc->line_v.as<Vertex2f1i>();
-    d.joint_v = sc->joint_v.as<Vertex3f1i>();
-    d.solid_v = sc->solid_v.as<Vertex0>();
-    d.iq_v = sc->iq_v.as<Vertex2f>();
-    d.ic_v = sc->ic_v.as<Vertex3f>();
-    d.rq_v = sc->rq_v.as<Vertex3f>();
-    d.rc_v = sc->rc_v.as<Vertex4f>();
-    d.hull_cand = sc->hull_cand.as<Vertex0>();
-    d.hull_v = sc->hull_v.as<Vertex0>();
-    d.hull_sort = sc->hull_sort.as<float2>();
-    d.hull_chain = sc->hull_chain.as<float2>();
-    d.line_i = sc->line_i.as<uint16_t>();
-    d.joint_i = sc->joint_i.as<uint16_t>();
-    d.solid_i = sc->solid_i.as<uint16_t>();
-    d.solid_flag = sc->solid_flag.as<uint8_t>();
-    d.line_pair_cut = sc->line_pair_cut.as<uint8_t>();
-    d.line_pair_mode = sc->line_pair_mode.as<uint8_t>();
-    d.line_inc = sc->line_inc.as<float>();
+    const TessSet& t = sc->tess();
+    d.elem_scan = t.elem_scan.as<ElemScan>();
+    d.wg_total = t.wg_total.as<uint32_t>();
+    d.wg_base = t.wg_base.as<uint32_t>();
+    d.group_base = t.group_base.as<uint32_t>();
+    d.totals = t.totals.as<uint32_t>();
+    d.shape_base = t.shape_base.as<uint32_t>();
+    d.path_scan = t.path_scan.as<uint32_t>();
+    d.hull_count = t.hull_count.as<uint32_t>();
+    d.hull_large_count = t.hull_large.as<uint32_t>();
+    d.hull_large_list = t.hull_large.as<uint32_t>() + 4;
+    d.status = t.status.as<uint32_t>();
+    d.line_v = t.line_v.as<Vertex2f1i>();
+    d.joint_v = t.joint_v.as<Vertex3f1i>();
+    d.solid_v = t.solid_v.as<Vertex0>();
+    d.iq_v = t.iq_v.as<Vertex2f>();
+    d.ic_v = t.ic_v.as<Vertex3f>();
+    d.rq_v = t.rq_v.as<Vertex3f>();
+    d.rc_v = t.rc_v.as<Vertex4f>();
+    d.hull_cand = t.hull_cand.as<Vertex0>();
+    d.hull_v = t.hull_v.as<Vertex0>();
+    d.hull_sort = t.hull_sort.as<float2>();
+    d.hull_chain = t.hull_chain.as<float2>();
+    d.line_i = t.line_i.as<uint16_t>();
+    d.joint_i = t.joint_i.as<uint16_t>();
+    d.solid_i = t.solid_i.as<uint16_t>();
+    d.solid_flag = t.solid_flag.as<uint8_t>();
+    d.line_pair_cut = t.line_pair_cut.as<uint8_t>();
+    d.line_pair_mode = t.line_pair_mode.as<uint8_t>();
+    d.line_inc = t.line_inc.as<float>();
 }
 
 // Before a repeated tessellation run: continue on the other set of buffers (allocated like the current one the first time).
 crh_status flip_tess_set(crh_scene* sc) {
-    crh_scene::TessShadow& o = sc->shadow;
-    DevBuf* cur[kTessBufs];
-    sc->tess_bufs(cur);
+    const TessSet& c = sc->tess();
+    TessSet& o = sc->other_tess();
     if (!o.allocated) {
-        for (int i = 0; i < kTessBufs; ++i)
-            if (cur[i]->cap) HIP_TRY(o.buf[i].ensure(cur[i]->cap));
+        for (DevBuf TessSet::*b : TessSet::kBuffers)
+            if ((c.*b).cap) HIP_TRY((o.*b).ensure((c.*b).cap));
         for (hipEvent_t* e : {&o.tess_done, &o.vertices_free, &o.ranges_free})
             if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
         // the same input gives the same totals: the sizes of the current set are right for this one (an overflow is caught as ever)
-        o.capacity_known = sc->capacity_known;
-        std::memcpy(o.totals_host, sc->totals_host, sizeof(o.totals_host));
-        std::memcpy(o.cap_host, sc->cap_host, sizeof(o.cap_host));
+        o.capacity_known = c.capacity_known;
+        std::memcpy(o.totals_host, c.totals_host, sizeof(o.totals_host));
+        std::memcpy(o.cap_host, c.cap_host, sizeof(o.cap_host));
         // (rows nobody has written yet must not send a pass anywhere: an optimistic run that does not fit leaves them as they are)
-        if (o.buf[5].p) HIP_TRY(hipMemsetAsync(o.buf[5].p, 0, o.buf[5].cap, sc->renderer->tessellation_stream()));
-        if (o.buf[6].p) HIP_TRY(hipMemsetAsync(o.buf[6].p, 0, o.buf[6].cap, sc->renderer->tessellation_stream()));
-        o.emitted_bytes = sc->emitted_bytes;
+        if (o.shape_base.p) HIP_TRY(hipMemsetAsync(o.shape_base.p, 0, o.shape_base.cap, sc->renderer->tessellation_stream()));
+        if (o.hull_count.p) HIP_TRY(hipMemsetAsync(o.hull_count.p, 0, o.hull_count.cap, sc->renderer->tessellation_stream()));
+        o.emitted_bytes = c.emitted_bytes;
         o.rendered_once = false;
         o.allocated = true;
     }
-    for (int i = 0; i < kTessBufs; ++i) std::swap(*cur[i], o.buf[i]);
-    std::swap(sc->tess_done, o.tess_done);
-    std::swap(sc->vertices_free, o.vertices_free);
-    std::swap(sc->ranges_free, o.ranges_free);
-    std::swap(sc->capacity_known, o.capacity_known);
-    std::swap(sc->rendered_once, o.rendered_once);
-    std::swap(sc->last_render_one_event, o.last_render_one_event);
-    std::swap(sc->emitted_bytes, o.emitted_bytes);
-    for (int c = 0; c < NCH; ++c) std::swap(sc->totals_host[c], o.totals_host[c]), std::swap(sc->cap_host[c], o.cap_host[c]);
-    for (int c = 0; c < NCH; ++c) sc->d.capacity[c] = sc->capacity_known ? sc->cap_host[c] : 0u;
+    sc->tess_cur ^= 1;
+    for (int ch = 0; ch < NCH; ++ch) sc->d.capacity[ch] = o.capacity_known ? o.cap_host[ch] : 0u;
     bind_tess_pointers(sc);
     return CRH_OK;
 }
 
 crh_status ensure_outputs(crh_scene* sc) {
+    TessSet& set = sc->tess();
     // (a sixteenth + 64 records beyond the totals: new paths of the same structure — crh_scene_upload into this Scene — then fit without a wait)
     uint32_t want[NCH];
-    for (int c = 0; c < NCH; ++c) want[c] = (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)sc->totals_host[c] + sc->totals_host[c] / 16u + 64u);
+    for (int c = 0; c < NCH; ++c) want[c] = (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)set.totals_host[c] + set.totals_host[c] / 16u + 64u);
     want[CH_LINE_V] &= ~1u; // (pairs)
     const uint32_t* t = want;
-    SceneDev& d = sc->d;
+    for (int k = 0; k < kTessStreams; ++k) HIP_TRY((set.*TessSet::kStream[k]).ensure(tess_stream_bytes(k, t)));
+    // what the kernels keep beside the streams
     const size_t pairs = t[CH_LINE_V] / 2 + 1;
-    HIP_TRY(sc->line_v.ensure((size_t)t[CH_LINE_V] * 20));
-    HIP_TRY(sc->line_i.ensure(((size_t)t[CH_LINE_V] + t[CH_LINE_CUT]) * 2));
-    HIP_TRY(sc->line_inc.ensure(pairs * 4));
-    HIP_TRY(sc->line_pair_cut.ensure(pairs));
-    HIP_TRY(sc->line_pair_mode.ensure(pairs));
-    HIP_TRY(sc->joint_v.ensure((size_t)t[CH_JOINT] * 5 * 24));
-    HIP_TRY(sc->joint_i.ensure((size_t)t[CH_JOINT] * 6 * 2));
-    HIP_TRY(sc->solid_v.ensure((size_t)t[CH_SOLID_V] * 8));
-    HIP_TRY(sc->solid_i.ensure(((size_t)t[CH_SOLID_V] + t[CH_SOLID_END]) * 2));
-    HIP_TRY(sc->solid_flag.ensure((size_t)t[CH_SOLID_V] + 2));
-    HIP_TRY(sc->iq_v.ensure((size_t)t[CH_IQ] * 3 * 16));
-    HIP_TRY(sc->ic_v.ensure((size_t)t[CH_IC_V] * 20));
-    HIP_TRY(sc->rq_v.ensure((size_t)t[CH_RQ] * 3 * 20));
-    HIP_TRY(sc->rc_v.ensure((size_t)t[CH_RC_V] * 24));
-    HIP_TRY(sc->hull_cand.ensure((size_t)t[CH_HULL] * 8));
-    HIP_TRY(sc->hull_v.ensure((size_t)t[CH_HULL] * 8));
+    HIP_TRY(set.line_inc.ensure(pairs * 4));
+    HIP_TRY(set.line_pair_cut.ensure(pairs));
+    HIP_TRY(set.line_pair_mode.ensure(pairs));
+    HIP_TRY(set.solid_flag.ensure((size_t)t[CH_SOLID_V] + 2));
+    HIP_TRY(set.hull_cand.ensure((size_t)t[CH_HULL] * 8));
     if (sc->big_shapes || sc->has_stroke) { // only Shapes beyond the LDS hull kernels (> 2048 candidates) use these — a stroked Shape reaches that with few
                                             // segments (every emitted line vertex is a hull candidate, stroke.rs:125); sized so that any Shape may
-        HIP_TRY(sc->hull_sort.ensure((size_t)t[CH_HULL] * 16 + 16));
-        HIP_TRY(sc->hull_chain.ensure((size_t)t[CH_HULL] * 16 + 16));
+        HIP_TRY(set.hull_sort.ensure((size_t)t[CH_HULL] * 16 + 16));
+        HIP_TRY(set.hull_chain.ensure((size_t)t[CH_HULL] * 16 + 16));
     }
-    for (int c = 0; c < NCH; ++c) d.capacity[c] = sc->cap_host[c] = t[c]; // (what THIS sizing guarantees; the buffers themselves only grow)
+    for (int c = 0; c < NCH; ++c) sc->d.capacity[c] = set.cap_host[c] = t[c]; // (what THIS sizing guarantees; the buffers themselves only grow)
     bind_tess_pointers(sc);
-    t = sc->totals_host;
-    sc->emitted_bytes = (uint64_t)t[CH_LINE_V] * 20 + ((uint64_t)t[CH_LINE_V] + t[CH_LINE_CUT]) * 2 + (uint64_t)t[CH_JOINT] * (5 * 24 + 6 * 2) +
-                        (uint64_t)t[CH_SOLID_V] * 8 + ((uint64_t)t[CH_SOLID_V] + t[CH_SOLID_END]) * 2 + (uint64_t)t[CH_IQ] * 48 + (uint64_t)t[CH_IC_V] * 20 +
-                        (uint64_t)t[CH_RQ] * 60 + (uint64_t)t[CH_RC_V] * 24;
+    set.emitted_bytes = tess_emitted_bytes(set.totals_host);
     return CRH_OK;
 }
 
@@ -714,13 +675,14 @@ crh_status run_tessellation(crh_scene* sc, bool again) {
         if (st != CRH_OK) return st;
     }
     sc->tessellated_once = true;
+    TessSet& set = sc->tess();
     sc->tess_runs += 1u;
     if (again) sc->bounds_generation = 0; // (boxes taken from the hulls of a run that did not fit are nobody's)
     if (again) sc->hull_queued_state = 0; // (the run that overflowed queued nothing: its hull kernels returned at once; the caller has synchronised)
     SceneDev& d = sc->d;
     const hipStream_t ts = r->tessellation_stream();
     // the previous frame's k_prim_setup must have consumed the vertex streams this run overwrites; its binning and raster may still run
-    if (sc->rendered_once) HIP_TRY(hipStreamWaitEvent(ts, sc->vertices_free, 0));
+    if (set.rendered_once) HIP_TRY(hipStreamWaitEvent(ts, set.vertices_free, 0));
     if (sc->geometry_pending) { // the batch of the last crh_scene_upload is still on its way (an asynchronous copy out of pinned staging memory)
         HIP_TRY(hipStreamWaitEvent(ts, sc->geometry_ready, 0));
         // ... and its element stream is built from it HERE, in front of the kernels that read it, on their stream. (On the upload stream the kernel had a
@@ -737,27 +699,27 @@ crh_status run_tessellation(crh_scene* sc, bool again) {
         if (d.n_shapes) HIP_TRY(hipMemsetAsync(d.shape_base, 0, (size_t)d.n_shapes * kShapeRow * 4, ts));
         if (d.n_shapes) HIP_TRY(hipMemsetAsync(d.hull_count, 0, (size_t)d.n_shapes * 4, ts));
     }
-    const uint64_t bytes[4] = {sc->input_bytes, 0, sc->input_bytes + sc->emitted_bytes, 0};
+    const uint64_t bytes[4] = {sc->input_bytes, 0, sc->input_bytes + set.emitted_bytes, 0};
     // (the one-pass path counts once per upload — elem_cnt, run_base —, the two-pass path every time)
-    if (!sc->capacity_known)
+    if (!set.capacity_known)
         for (int c = 0; c < NCH; ++c) d.capacity[c] = 0u; // (not known: the counting kernels must not take the streams' old sizes for a verdict — k_shape_rows)
     // CRH_TESS_COUNT_EVERY_RUN (read per run: bench.py's `recount` side block switches it inside one process): the counts and bases are not kept —
     // k_tess_count_runs and k_scan_runs run in front of every k_tess_runs, as they do for new paths
-    launch_tessellate(d, ts, r->mark_fn_tess(), r, bytes, sc->has_stroke, !sc->capacity_known || !sc->counts_valid || getenv("CRH_TESS_COUNT_EVERY_RUN") != nullptr);
+    launch_tessellate(d, ts, r->mark_fn_tess(), r, bytes, sc->has_stroke, !set.capacity_known || !sc->counts_valid || getenv("CRH_TESS_COUNT_EVERY_RUN") != nullptr);
     sc->counts_valid = true;
-    if (!sc->capacity_known) { // first run: the output sizes are data dependent, fetch the totals once and allocate
-        HIP_TRY(hipMemcpyAsync(sc->totals_host, d.totals, sizeof(uint32_t) * NCH, hipMemcpyDeviceToHost, ts));
+    if (!set.capacity_known) { // first run: the output sizes are data dependent, fetch the totals once and allocate
+        HIP_TRY(hipMemcpyAsync(set.totals_host, d.totals, sizeof(uint32_t) * NCH, hipMemcpyDeviceToHost, ts));
         // (the tessellation stream alone: it has waited for the consumers of this set's streams — vertices_free, above — before the count kernel, and
         // the frames before this one go on binning and rasterizing on their streams while the host waits here. Until round 4 this was a wait for
         // every stream: new paths every frame, bench.py --reupload, ran one frame at a time)
         HIP_TRY(hipStreamSynchronize(ts));
         crh_status st = ensure_outputs(sc);
         if (st != CRH_OK) return st;
-        sc->capacity_known = true;
+        set.capacity_known = true;
         sc->optimistic = false;
     }
-    if (sc->has_stroke) HIP_TRY(hipMemsetAsync(d.line_pair_cut, 0, sc->line_pair_cut.cap, ts));
-    const uint64_t bytes2[4] = {sc->input_bytes, 0, sc->input_bytes + sc->emitted_bytes, (uint64_t)sc->totals_host[CH_HULL] * 8};
+    if (sc->has_stroke) HIP_TRY(hipMemsetAsync(d.line_pair_cut, 0, set.line_pair_cut.cap, ts));
+    const uint64_t bytes2[4] = {sc->input_bytes, 0, sc->input_bytes + set.emitted_bytes, (uint64_t)set.totals_host[CH_HULL] * 8};
     if (sc->hull_queued_state == 1 && hipEventQuery(sc->hull_queued_ready) == hipSuccess) sc->hull_queued_state = 2;
     launch_emit(d, ts, r->mark_fn_tess(), r, bytes2, sc->has_stroke, sc->big_shapes, sc->hull_queued_state == 2 ? sc->hull_queued_host : nullptr);
     if (sc->hull_queued_state == 0 && (sc->has_stroke || sc->big_shapes)) {
@@ -769,11 +731,11 @@ crh_status run_tessellation(crh_scene* sc, bool again) {
     }
     // contiguous primitive ids per Shape, in draw order (transform independent, so it belongs to the tessellation); the previous
     // frame's tile walks read the old ranges until its fill pass is through
-    if (sc->rendered_once && !sc->last_render_one_event) HIP_TRY(hipStreamWaitEvent(ts, sc->ranges_free, 0)); // (one event stood for both: waited for above)
-    launch_plain_ranges(d, sc->shape_ncand.as<uint32_t>(), sc->shape_prim_begin.as<uint32_t>(), sc->shape_nslots.as<uint32_t>(), sc->shape_slot_begin.as<uint32_t>(),
-                        sc->prim_scan_scratch.as<uint32_t>(), sc->prim_scan_scratch.as<uint32_t>() + ((size_t)(d.n_shapes + 511) / 512 + 2), ts);
+    if (set.rendered_once && !set.last_render_one_event) HIP_TRY(hipStreamWaitEvent(ts, set.ranges_free, 0)); // (one event stood for both: waited for above)
+    launch_plain_ranges(d, set.shape_ncand.as<uint32_t>(), set.shape_prim_begin.as<uint32_t>(), set.shape_nslots.as<uint32_t>(), set.shape_slot_begin.as<uint32_t>(),
+                        set.prim_scan_scratch.as<uint32_t>(), set.prim_scan_scratch.as<uint32_t>() + ((size_t)(d.n_shapes + 511) / 512 + 2), ts);
     if (r->timing & 2u) crh_renderer::mark_cb_tess(r, "tess_prim_ranges", 0);
-    HIP_TRY(hipEventRecord(sc->tess_done, ts));
+    HIP_TRY(hipEventRecord(set.tess_done, ts));
     HIP_TRY(hipGetLastError());
     sc->layout_valid = false;
     return CRH_OK;
@@ -788,13 +750,13 @@ crh_status settle_tessellation(crh_scene* sc, uint32_t* status_word) {
         HIP_TRY(hipMemcpyAsync(&word, sc->d.status, 4, hipMemcpyDeviceToHost, r->tessellation_stream()));
         HIP_TRY(r->sync());
         if (word != 0xFFFFFFFFu && (word & 0xFFu) >= 0x80u && attempt == 0) {
-            sc->capacity_known = false, sc->optimistic = false;
+            sc->tess().capacity_known = false, sc->optimistic = false;
             crh_status st = run_tessellation(sc, true);
             if (st != CRH_OK) return st;
             continue;
         }
-        if (sc->optimistic && sc->capacity_known) { // the run fitted: the host may know its totals now (until here totals_host held the capacities)
-            HIP_TRY(hipMemcpy(sc->totals_host, sc->d.totals, sizeof(uint32_t) * NCH, hipMemcpyDeviceToHost));
+        if (sc->optimistic && sc->tess().capacity_known) { // the run fitted: the host may know its totals now (until here totals_host held the capacities)
+            HIP_TRY(hipMemcpy(sc->tess().totals_host, sc->d.totals, sizeof(uint32_t) * NCH, hipMemcpyDeviceToHost));
             sc->optimistic = false;
         }
         *status_word = word;
@@ -814,90 +776,35 @@ crh_status fetch_layout(crh_scene* sc) {
     if (sc->d.n_shapes) HIP_TRY(hipMemcpyAsync(sc->shape_base_host.data(), sc->d.shape_base, sc->shape_base_host.size() * 4, hipMemcpyDeviceToHost, r->stream));
     if (sc->d.n_shapes == 0) sc->shape_base_host.clear();
     if (sc->d.n_shapes) HIP_TRY(hipMemcpyAsync(sc->hull_count_host.data(), sc->d.hull_count, sc->hull_count_host.size() * 4, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipMemcpyAsync(sc->totals_host, sc->d.totals, sizeof(uint32_t) * NCH, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipMemcpyAsync(sc->tess().totals_host, sc->d.totals, sizeof(uint32_t) * NCH, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(r->sync());
     sc->layout_valid = true;
     return CRH_OK;
 }
 
-void shape_layout(const crh_scene* sc, uint32_t s, uint64_t vo[8], uint64_t io[3]) {
-    const uint32_t* a = &sc->shape_base_host[(size_t)s * kShapeRow]; // begin[NCH], end[NCH]
-    const uint32_t* b = a + NCH;
-    auto n = [&](int c) { return (uint64_t)(b[c] - a[c]); };
-    uint64_t v = 0;
-    v += n(CH_LINE_V) * 20;
-    vo[0] = v;
-    v += n(CH_JOINT) * 5 * 24;
-    vo[1] = v;
-    v += n(CH_SOLID_V) * 8;
-    vo[2] = v;
-    v += n(CH_IQ) * 3 * 16;
-    vo[3] = v;
-    v += n(CH_IC_V) * 20;
-    vo[4] = v;
-    v += n(CH_RQ) * 3 * 20;
-    vo[5] = v;
-    v += n(CH_RC_V) * 24;
-    vo[6] = v;
-    v += (uint64_t)sc->hull_count_host[s] * 8;
-    vo[7] = v;
-    uint64_t i = 0;
-    i += (n(CH_LINE_V) + n(CH_LINE_CUT)) * 2;
-    io[0] = i;
-    i += n(CH_JOINT) * 6 * 2;
-    io[1] = i;
-    i += (n(CH_SOLID_V) + n(CH_SOLID_END)) * 2;
-    io[2] = i;
-}
+// The parity taps: a Shape's slices of the eleven streams (tess_streams.hpp), from the host copies fetch_layout made of shape_base and hull_count
+void shape_layout(const crh_scene* sc, uint32_t s, uint64_t vo[8], uint64_t io[3]) { tess_shape_offsets(&sc->shape_base_host[(size_t)s * kShapeRow], sc->hull_count_host[s], vo, io); }
 
 struct HostCopy {
-    std::vector<uint8_t> line_v, joint_v, solid_v, iq_v, ic_v, rq_v, rc_v, hull_v, line_i, joint_i, solid_i;
+    std::vector<uint8_t> stream[kTessStreams];
 };
 crh_status fetch_outputs(crh_scene* sc, HostCopy& h) {
-    const uint32_t* t = sc->totals_host;
+    const TessSet& set = sc->tess();
     hipStream_t st = sc->renderer->stream;
-    auto get = [&](std::vector<uint8_t>& dst, const void* src, size_t bytes) -> crh_status {
-        dst.resize(bytes);
-        if (bytes) HIP_TRY(hipMemcpyAsync(dst.data(), src, bytes, hipMemcpyDeviceToHost, st));
-        return CRH_OK;
-    };
-    crh_status rc;
-    if ((rc = get(h.line_v, sc->d.line_v, (size_t)t[CH_LINE_V] * 20)) != CRH_OK) return rc;
-    if ((rc = get(h.joint_v, sc->d.joint_v, (size_t)t[CH_JOINT] * 120)) != CRH_OK) return rc;
-    if ((rc = get(h.solid_v, sc->d.solid_v, (size_t)t[CH_SOLID_V] * 8)) != CRH_OK) return rc;
-    if ((rc = get(h.iq_v, sc->d.iq_v, (size_t)t[CH_IQ] * 48)) != CRH_OK) return rc;
-    if ((rc = get(h.ic_v, sc->d.ic_v, (size_t)t[CH_IC_V] * 20)) != CRH_OK) return rc;
-    if ((rc = get(h.rq_v, sc->d.rq_v, (size_t)t[CH_RQ] * 60)) != CRH_OK) return rc;
-    if ((rc = get(h.rc_v, sc->d.rc_v, (size_t)t[CH_RC_V] * 24)) != CRH_OK) return rc;
-    if ((rc = get(h.hull_v, sc->d.hull_v, (size_t)t[CH_HULL] * 8)) != CRH_OK) return rc;
-    if ((rc = get(h.line_i, sc->d.line_i, ((size_t)t[CH_LINE_V] + t[CH_LINE_CUT]) * 2)) != CRH_OK) return rc;
-    if ((rc = get(h.joint_i, sc->d.joint_i, (size_t)t[CH_JOINT] * 12)) != CRH_OK) return rc;
-    if ((rc = get(h.solid_i, sc->d.solid_i, ((size_t)t[CH_SOLID_V] + t[CH_SOLID_END]) * 2)) != CRH_OK) return rc;
+    for (int k = 0; k < kTessStreams; ++k) {
+        const size_t bytes = tess_stream_bytes(k, set.totals_host);
+        h.stream[k].resize(bytes);
+        if (bytes) HIP_TRY(hipMemcpyAsync(h.stream[k].data(), (set.*TessSet::kStream[k]).p, bytes, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     return CRH_OK;
 }
 
 // the byte image of renderer.rs:198-209 for shape s, assembled from the scene-wide streams
 void assemble_shape(const crh_scene* sc, const HostCopy& h, uint32_t s, uint8_t* vb, uint8_t* ib) {
-    const uint32_t* a = &sc->shape_base_host[(size_t)s * kShapeRow]; // begin[NCH], end[NCH]
-    const uint32_t* b = a + NCH;
-    auto put = [](uint8_t*& dst, const std::vector<uint8_t>& src, size_t begin, size_t bytes) {
-        if (dst && bytes) {
-            std::memcpy(dst, src.data() + begin, bytes);
-            dst += bytes;
-        }
-    };
-    put(vb, h.line_v, (size_t)a[CH_LINE_V] * 20, (size_t)(b[CH_LINE_V] - a[CH_LINE_V]) * 20);
-    put(vb, h.joint_v, (size_t)a[CH_JOINT] * 120, (size_t)(b[CH_JOINT] - a[CH_JOINT]) * 120);
-    put(vb, h.solid_v, (size_t)a[CH_SOLID_V] * 8, (size_t)(b[CH_SOLID_V] - a[CH_SOLID_V]) * 8);
-    put(vb, h.iq_v, (size_t)a[CH_IQ] * 48, (size_t)(b[CH_IQ] - a[CH_IQ]) * 48);
-    put(vb, h.ic_v, (size_t)a[CH_IC_V] * 20, (size_t)(b[CH_IC_V] - a[CH_IC_V]) * 20);
-    put(vb, h.rq_v, (size_t)a[CH_RQ] * 60, (size_t)(b[CH_RQ] - a[CH_RQ]) * 60);
-    put(vb, h.rc_v, (size_t)a[CH_RC_V] * 24, (size_t)(b[CH_RC_V] - a[CH_RC_V]) * 24);
-    put(vb, h.hull_v, (size_t)a[CH_HULL] * 8, (size_t)sc->hull_count_host[s] * 8);
-    put(ib, h.line_i, ((size_t)a[CH_LINE_V] + a[CH_LINE_CUT]) * 2, ((size_t)(b[CH_LINE_V] - a[CH_LINE_V]) + (b[CH_LINE_CUT] - a[CH_LINE_CUT])) * 2);
-    put(ib, h.joint_i, (size_t)a[CH_JOINT] * 12, (size_t)(b[CH_JOINT] - a[CH_JOINT]) * 12);
-    put(ib, h.solid_i, ((size_t)a[CH_SOLID_V] + a[CH_SOLID_END]) * 2, ((size_t)(b[CH_SOLID_V] - a[CH_SOLID_V]) + (b[CH_SOLID_END] - a[CH_SOLID_END])) * 2);
+    const uint8_t* stream[kTessStreams];
+    for (int k = 0; k < kTessStreams; ++k) stream[k] = h.stream[k].data();
+    tess_assemble_shape(&sc->shape_base_host[(size_t)s * kShapeRow], sc->hull_count_host[s], stream, vb, ib);
 }
 
 // Tile-list capacity after an overflow: ov[1] = the pairs the pass needs, ov[5] = a region of the edge pass' pair stream filled up although
@@ -1129,7 +1036,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     }
     const bool recorded = f->n_items != 0; // crh_scene_render_draws stored a pass in the frame
     if (!recorded && !sc->instances_set) return CRH_ERR_INVALID_ARGUMENT;
-    if (!sc->capacity_known) return CRH_ERR_INVALID_ARGUMENT; // tessellate first
+    if (!sc->tess().capacity_known) return CRH_ERR_INVALID_ARGUMENT; // tessellate first
     if (f->carry && sc->optimistic) { // a pass into a frame that keeps its state cannot be drawn a second time: the tessellation it draws has to be known to fit
         uint32_t word = 0;
         const crh_status st = settle_tessellation(sc, &word);
@@ -1151,7 +1058,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     const hipStream_t bin = r->binning_stream();
     crh_frame::BinSet& set = f->sets[f->next_set];
     const int rec = sc->next_rec;
-    HIP_TRY(hipStreamWaitEvent(bin, sc->tess_done, 0)); // the tessellation this frame draws (a no-op when it finished long ago)
+    HIP_TRY(hipStreamWaitEvent(bin, sc->tess().tess_done, 0)); // the tessellation this frame draws (a no-op when it finished long ago)
     if (f->ext_read_set) HIP_TRY(hipStreamWaitEvent(bin, f->ext_read, 0)); // (the exchange reads the tile counts of the frame's passes: csrc/comm.hip)
     if (r->raster_exclusive && r->raster_events[0]) HIP_TRY(hipStreamWaitEvent(bin, r->raster_events[0], 0));
     // (each wait on another stream's event is a packet the binning lane — the critical one — spends 5 - 10 us on, satisfied or not: the
@@ -1195,8 +1102,8 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     p.tile_cursor = set.tile_count_cursor.as<uint32_t>();
     p.tile_count = set.tile_count_cursor.as<uint32_t>() + f->n_tiles;
     p.tile_offset = set.tile_offset.as<uint32_t>();
-    p.shape_ncand = sc->shape_ncand.as<uint32_t>();
-    p.shape_prim_begin = sc->shape_prim_begin.as<uint32_t>();
+    p.shape_ncand = sc->tess().shape_ncand.as<uint32_t>();
+    p.shape_prim_begin = sc->tess().shape_prim_begin.as<uint32_t>();
     HIP_TRY(set.scan_scratch.ensure(((size_t)(f->n_tiles + 511) / 512 + 2) * 4)); // (launch_tile_bases takes a sum per 512 tiles, the other scans one per 1 024)
     if (recorded) {
         // primitive ranges per draw item; a Shape may be drawn many times, so the record capacity comes from the scan's total
@@ -1225,7 +1132,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         p.shape_prim_begin = f->item_prim_begin.as<uint32_t>();
     } else {
         // every candidate triangle gets a record slot: an upper bound follows from the tessellation totals
-        const uint32_t* t = sc->totals_host;
+        const uint32_t* t = sc->tess().totals_host;
         const size_t prim_capacity = (size_t)t[CH_LINE_V] + 3u * (size_t)t[CH_JOINT] + t[CH_SOLID_V] + t[CH_IQ] + t[CH_IC_V] / 3u + t[CH_RQ] + t[CH_RC_V] / 3u + t[CH_HULL] + 64;
         // the edge pass: four slots per stroke / curve triangle, one per polygon vertex and hull vertex, the per-Shape cover slots
         const size_t slot_capacity = 4u * ((size_t)t[CH_LINE_V] + 3u * (size_t)t[CH_JOINT] + t[CH_IQ] + t[CH_IC_V] / 3u + t[CH_RQ] + t[CH_RC_V] / 3u) + t[CH_SOLID_V] + 4u * (size_t)t[CH_HULL] +
@@ -1234,10 +1141,10 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         HIP_TRY(sc->prim_rec[rec].ensure(std::max(prim_capacity * 128, slot_capacity * 32)));
         p.prim_capacity = (uint32_t)prim_capacity;
         p.slot_capacity = (uint32_t)slot_capacity;
-        p.slot_begin = sc->shape_slot_begin.as<uint32_t>();
+        p.slot_begin = sc->tess().shape_slot_begin.as<uint32_t>();
     }
     {   // totals of the scene's tessellation (hull vertices are at most the hull candidates; on the benchmark scene about half of them)
-        const uint32_t* t = sc->totals_host;
+        const uint32_t* t = sc->tess().totals_host;
         const uint64_t tris = (uint64_t)t[CH_LINE_V] + 3u * (uint64_t)t[CH_JOINT] + t[CH_IQ] + t[CH_IC_V] / 3u + t[CH_RQ] + t[CH_RC_V] / 3u, edges = (uint64_t)t[CH_SOLID_V] + t[CH_HULL] / 2u;
         const uint64_t per = std::max<uint64_t>(1, sc->d.n_shapes);
         p.hint_tris = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, tris * p.n_items / per), p.hint_edges = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, edges * p.n_items / per);
@@ -1389,9 +1296,9 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
                 launch_slab_items(p, set.item_elsewhere.as<uint8_t>(), bin);
                 p.item_elsewhere = set.item_elsewhere.as<uint8_t>();
             }
-            f->last_bin = launch_bin_edges(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
+            f->last_bin = launch_bin_edges(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->tess().vertices_free);
         } else {
-            launch_bin(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->vertices_free);
+            launch_bin(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->tess().vertices_free);
             if (painted) { // behind k_prim_setup, in front of the event that says the instance data has been read
                 HIP_TRY(sc->paint_items[rec].ensure((size_t)p.n_items * sizeof(PaintItem) + 64));
                 const PaintTable table = {sc->paint_items[rec].as<PaintItem>(), sc->paint_instance.as<int32_t>(), (uint32_t)sc->instance_paint.size()};
@@ -1460,8 +1367,8 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     // read", "the slot ranges are free" and "binned" are one point in time, and the event launch_bin_edges recorded there (the Scene's
     // vertices_free) stands for all four — three packets less on the critical lane.
     const bool one_event = direct;
-    sc->last_render_one_event = one_event;
-    const hipEvent_t vertices_free_now = sc->vertices_free; // (the handle: flip_tess_set swaps the Scene's two)
+    sc->tess().last_render_one_event = one_event;
+    const hipEvent_t vertices_free_now = sc->tess().vertices_free;
     if (one_event) {
         if (slot.read_done) slot.read_event = vertices_free_now, slot.was_read = true;
     } else if (slot.read_done) { // k_prim_setup, the only reader of the instance data, is behind us on this stream
@@ -1470,7 +1377,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
         slot.was_read = true;
     }
     if (edges) {
-        if (!one_event) HIP_TRY(hipEventRecord(sc->ranges_free, bin)); // k_bin_edges, the only reader of the slot ranges, is behind us
+        if (!one_event) HIP_TRY(hipEventRecord(sc->tess().ranges_free, bin)); // k_bin_edges, the only reader of the slot ranges, is behind us
         launch_scatter(p, bin, r->mark_fn_bin(), r);
         if (direct && f->places_instances != sc->instances_version) { // the places of the next pass into this frame, from this pass' counts: behind the event the raster kernel waits for, beside that kernel (resident instances: the same counts, the same places)
             f->places_instances = sc->instances_version;
@@ -1487,7 +1394,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
             f->base_cur ^= 1;
         }
     } else {
-        launch_fill(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->ranges_free);
+        launch_fill(sc->d, p, r->config.msaa_sample_count, bin, r->mark_fn_bin(), r, sc->tess().ranges_free);
     }
     if (!one_event) HIP_TRY(hipEventRecord(set.bin_done, bin));
     if (two_lanes) { // the end of this pass' work on its lane: what the next pass, on the other lane, waits for unless both are steady
@@ -1501,7 +1408,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     r->begin_marks(0);
     // algorithmic bytes of the raster step: every emitted byte read once + 64 B transform + 16 B colour per shape,
     // the framebuffer written once
-    const uint64_t raster_bytes = sc->emitted_bytes + (uint64_t)p.n_items * 80 + (uint64_t)f->image_bytes();
+    const uint64_t raster_bytes = sc->tess().emitted_bytes + (uint64_t)p.n_items * 80 + (uint64_t)f->image_bytes();
     if (f->carry && (!f->carry_valid || f->carry_recolor)) { // on the raster stream: behind every earlier pass into the frame, in front of this one
         const size_t n_samples = (size_t)f->width * f->height * r->config.msaa_sample_count;
         if (!f->carry_valid) {
@@ -1539,7 +1446,7 @@ crh_status render_impl(crh_scene* sc, crh_frame* f, bool again = false) {
     }
     set.used = true;
     sc->rec_used[rec] = true, sc->rec_used_ever[rec] = true;
-    sc->rendered_once = true;
+    sc->tess().rendered_once = true;
     HIP_TRY(hipGetLastError());
     f->last_set = f->next_set;
     if (r->pipeline) { // alternate the buffers; without pipelining everything is ordered on one stream anyway
@@ -1593,7 +1500,7 @@ crh_status settle_frame(crh_frame* f) {
     if (tess_overflow) { // the optimistic tessellation this pass drew did not fit its streams: size them from the totals, tessellate, and draw again
         if (getenv("CRH_PASS_VERBOSE")) std::fprintf(stderr, "[contrast-hip] the tessellation of re-uploaded paths outgrew the streams of the paths before them: sized again, the pass is drawn again\n");
         crh_scene* const sc = f->last_scene;
-        sc->capacity_known = false, sc->optimistic = false;
+        sc->tess().capacity_known = false, sc->optimistic = false;
         const crh_status st = run_tessellation(sc, true);
         if (st != CRH_OK) return st;
     }
@@ -1944,6 +1851,7 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
         phase("frames settled");
     }
     crh_scene* sc = existing ? existing : new crh_scene;
+    TessSet& tess = sc->tess(); // (an upload stays on the current set)
     // ---- the one-pass tessellation's runs ... (below) and: are these paths of the structure the Scene already holds?
     // ---- element stream: MOVE, segments..., END per path; pool = start point + records, -0 canonicalised (safe_float.rs:44-52) — built straight
     //      into pinned staging memory (one arena for all thirteen arrays; the copies to the device are asynchronous, the tessellation waits
@@ -2047,10 +1955,10 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
     sc->device = r->device;
     static std::atomic<uint64_t> next_generation{1}; // unique across scenes (and threads): a new Scene at a recycled address is not mistaken for the old one
     sc->generation = next_generation.fetch_add(1);
-    if (!sc->tess_done) {
-        if (!hip_ok(hipEventCreateWithFlags(&sc->tess_done, hipEventDisableTiming), "hipEventCreate") ||
-            !hip_ok(hipEventCreateWithFlags(&sc->vertices_free, hipEventDisableTiming), "hipEventCreate") ||
-            !hip_ok(hipEventCreateWithFlags(&sc->ranges_free, hipEventDisableTiming), "hipEventCreate")) {
+    if (!tess.tess_done) {
+        if (!hip_ok(hipEventCreateWithFlags(&tess.tess_done, hipEventDisableTiming), "hipEventCreate") ||
+            !hip_ok(hipEventCreateWithFlags(&tess.vertices_free, hipEventDisableTiming), "hipEventCreate") ||
+            !hip_ok(hipEventCreateWithFlags(&tess.ranges_free, hipEventDisableTiming), "hipEventCreate")) {
             if (!existing) delete sc;
             return CRH_ERR_HIP;
         }
@@ -2063,15 +1971,15 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
     // New paths of the structure the Scene holds (as many Shapes, paths, elements, the same tessellation path) and sized streams: the capacities
     // stay, no wait for the totals (crh_scene::optimistic). CRH_NO_OPTIMISTIC_UPLOAD: A/B runs and the tests of the other way.
     const uint32_t new_runs = (runs.empty() || n_elems == 0u) ? 0u : (uint32_t)runs.size() - 1u;
-    const bool same_structure = existing && sc->capacity_known && sc->d.n_elems == n_elems && sc->d.n_paths == b->n_paths && sc->d.n_shapes == b->n_shapes && sc->has_stroke == has_stroke &&
+    const bool same_structure = existing && tess.capacity_known && sc->d.n_elems == n_elems && sc->d.n_paths == b->n_paths && sc->d.n_shapes == b->n_shapes && sc->has_stroke == has_stroke &&
                                 sc->d.n_runs == new_runs && sc->d.run_block == run_block && n_elems != 0u && sc->structure_hash == structure_hash && std::getenv("CRH_NO_OPTIMISTIC_UPLOAD") == nullptr;
     sc->structure_hash = structure_hash;
-    sc->rendered_once = false;
-    sc->last_render_one_event = false;
-    if (sc->shadow.allocated && !same_structure) { // sized for the previous contents
+    tess.rendered_once = false;
+    tess.last_render_one_event = false;
+    TessSet& other = sc->other_tess();
+    if (other.allocated && !same_structure) { // sized for the previous contents
         if (!hip_ok(r->sync(), "sync")) return CRH_ERR_HIP;
-        for (DevBuf& buf : sc->shadow.buf) buf.release();
-        sc->shadow.allocated = false;
+        other.release();
     }
     sc->tessellated_once_before_upload = sc->tessellated_once;
     sc->tessellated_once = false;
@@ -2093,10 +2001,10 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
     for (bool& used : sc->rec_used) used = false;
     sc->n_segments = b->n_segments;
     sc->has_stroke = has_stroke;
-    sc->capacity_known = same_structure, sc->optimistic = same_structure, sc->counts_valid = false;
+    tess.capacity_known = same_structure, sc->optimistic = same_structure, sc->counts_valid = false;
     if (same_structure) {
-        std::memcpy(sc->totals_host, sc->cap_host, sizeof(sc->totals_host)); // (upper bounds, for what the host sizes from the totals)
-        if (sc->shadow.allocated) std::memcpy(sc->shadow.totals_host, sc->shadow.cap_host, sizeof(sc->shadow.totals_host));
+        std::memcpy(tess.totals_host, tess.cap_host, sizeof(tess.totals_host)); // (upper bounds, for what the host sizes from the totals)
+        if (other.allocated) std::memcpy(other.totals_host, other.cap_host, sizeof(other.totals_host));
     } else {
         sc->lineage = sc->generation;
     }
@@ -2124,7 +2032,7 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
     d.n_wg = (n_elems + kTessBlock - 1) / kTessBlock;
     d.n_runs = new_runs;
     d.run_block = run_block;
-    for (int c = 0; c < NCH; ++c) d.capacity[c] = same_structure ? sc->cap_host[c] : 0u;
+    for (int c = 0; c < NCH; ++c) d.capacity[c] = same_structure ? tess.cap_host[c] : 0u;
     // ONE asynchronous copy of the whole arena into a device arena of the same layout (round 5; until then fourteen copies into fourteen buffers on the
     // raster stream, in line behind the raster kernel of the frame in front). It runs on the upload stream, behind the last readers of the Scene's old
     // paths only: its tessellation and the raster kernels of the passes that drew it (their binning comes first on the way) — the frames in flight
@@ -2137,8 +2045,8 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
             goto fail;
         }
         bool ok = true;
-        if (existing && sc->tess_done && sc->tessellated_once_before_upload) ok = hip_ok(hipStreamWaitEvent(st, sc->tess_done, 0), "hipStreamWaitEvent"); // a tessellation of the old paths may still run
-        if (existing && sc->shadow.tess_done && sc->tessellated_once_before_upload) ok = ok && hip_ok(hipStreamWaitEvent(st, sc->shadow.tess_done, 0), "hipStreamWaitEvent");
+        if (existing && tess.tess_done && sc->tessellated_once_before_upload) ok = hip_ok(hipStreamWaitEvent(st, tess.tess_done, 0), "hipStreamWaitEvent"); // a tessellation of the old paths may still run
+        if (existing && other.tess_done && sc->tessellated_once_before_upload) ok = ok && hip_ok(hipStreamWaitEvent(st, other.tess_done, 0), "hipStreamWaitEvent");
         for (int k = 0; k < kPipelineDepth && ok; ++k)
             if (existing && sc->rec_used_ever[k]) ok = hip_ok(hipStreamWaitEvent(st, sc->rec_raster_done[k], 0), "hipStreamWaitEvent");
         // (the element offsets exist twice on the device when a path is stroked: k_stroke_records rewrites elem_off, elem_off0 stays)
@@ -2160,7 +2068,7 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
         }
         // the status word: cleared IN FRONT of geometry_ready — the tessellation stream waits for that event only, then clears the word itself and
         // lets its kernels write error codes; a memset enqueued behind the event would be unordered against those writes
-        if (ok) ok = hip_ok(sc->status.ensure(4), "hipMalloc") && hip_ok(hipMemsetAsync(sc->status.p, 0xFF, 4, st), "hipMemset");
+        if (ok) ok = hip_ok(tess.status.ensure(4), "hipMalloc") && hip_ok(hipMemsetAsync(tess.status.p, 0xFF, 4, st), "hipMemset");
         if (ok) ok = hip_ok(sc->geometry_stage.done(st), "hipEventRecord") && hip_ok(hipEventRecord(sc->geometry_ready, st), "hipEventRecord");
         if (!ok) {
             rc = CRH_ERR_HIP;
@@ -2169,19 +2077,20 @@ crh_status crh_scene_upload(crh_renderer* r, const crh_path_batch* b, crh_scene*
         sc->geometry_pending = true;
     }
     // (the scan state of the two-pass path — 40 B per element and the rows' totals — exists only for Scenes that take it)
-    if ((d.n_runs == 0u && (!hip_ok(sc->elem_scan.ensure((size_t)n_elems * sizeof(ElemScan)), "hipMalloc elem_scan") ||
-        !hip_ok(sc->wg_total.ensure((size_t)d.n_wg * NCH * 4), "hipMalloc") || !hip_ok(sc->wg_base.ensure((size_t)d.n_wg * NCH * 4), "hipMalloc") || !hip_ok(sc->group_base.ensure(((size_t)d.n_wg / 64 + 2) * NCH * 4), "hipMalloc"))) ||
+    if ((d.n_runs == 0u && (!hip_ok(tess.elem_scan.ensure((size_t)n_elems * sizeof(ElemScan)), "hipMalloc elem_scan") ||
+        !hip_ok(tess.wg_total.ensure((size_t)d.n_wg * NCH * 4), "hipMalloc") || !hip_ok(tess.wg_base.ensure((size_t)d.n_wg * NCH * 4), "hipMalloc") || !hip_ok(tess.group_base.ensure(((size_t)d.n_wg / 64 + 2) * NCH * 4), "hipMalloc"))) ||
         (d.n_runs != 0u && (!hip_ok(sc->elem_cnt.ensure((size_t)n_elems * 4), "hipMalloc") || !hip_ok(sc->run_base.ensure(((size_t)d.n_runs + 1) * NCH * 4), "hipMalloc"))) ||
-        (d.n_runs != 0u && has_stroke && !hip_ok(sc->path_scan.ensure((size_t)b->n_paths * 12), "hipMalloc")) ||
-        !hip_ok(sc->totals.ensure(NCH * 4), "hipMalloc") || !hip_ok(sc->shape_base.ensure((size_t)b->n_shapes * kShapeRow * 4), "hipMalloc") ||
-        !hip_ok(sc->hull_count.ensure((size_t)b->n_shapes * 4), "hipMalloc") || !hip_ok(sc->hull_large.ensure((3 * (size_t)b->n_shapes + 4) * 4), "hipMalloc") || !hip_ok(sc->status.ensure(4), "hipMalloc") ||
+        (d.n_runs != 0u && has_stroke && !hip_ok(tess.path_scan.ensure((size_t)b->n_paths * 12), "hipMalloc")) ||
+        !hip_ok(tess.totals.ensure(NCH * 4), "hipMalloc") || !hip_ok(tess.shape_base.ensure((size_t)b->n_shapes * kShapeRow * 4), "hipMalloc") ||
+        !hip_ok(tess.hull_count.ensure((size_t)b->n_shapes * 4), "hipMalloc") || !hip_ok(tess.hull_large.ensure((3 * (size_t)b->n_shapes + 4) * 4), "hipMalloc") || !hip_ok(tess.status.ensure(4), "hipMalloc") ||
         !hip_ok(sc->transforms.ensure((size_t)b->n_shapes * 64), "hipMalloc") || !hip_ok(sc->colors.ensure((size_t)b->n_shapes * 16), "hipMalloc") ||
-        !hip_ok(sc->shape_ncand.ensure((size_t)b->n_shapes * 4 + 4), "hipMalloc") || !hip_ok(sc->shape_prim_begin.ensure(((size_t)b->n_shapes + 1) * 4), "hipMalloc") ||
-        !hip_ok(sc->shape_nslots.ensure((size_t)b->n_shapes * 4 + 4), "hipMalloc") || !hip_ok(sc->shape_slot_begin.ensure(((size_t)b->n_shapes + 1) * 4), "hipMalloc") ||
-        !hip_ok(sc->prim_scan_scratch.ensure(((size_t)(b->n_shapes + 511) / 512 + 2) * 8), "hipMalloc")) { // (two scans side by side, a sum per 512 Shapes each)
+        !hip_ok(tess.shape_ncand.ensure((size_t)b->n_shapes * 4 + 4), "hipMalloc") || !hip_ok(tess.shape_prim_begin.ensure(((size_t)b->n_shapes + 1) * 4), "hipMalloc") ||
+        !hip_ok(tess.shape_nslots.ensure((size_t)b->n_shapes * 4 + 4), "hipMalloc") || !hip_ok(tess.shape_slot_begin.ensure(((size_t)b->n_shapes + 1) * 4), "hipMalloc") ||
+        !hip_ok(tess.prim_scan_scratch.ensure(((size_t)(b->n_shapes + 511) / 512 + 2) * 8), "hipMalloc")) { // (two scans side by side, a sum per 512 Shapes each)
         rc = CRH_ERR_HIP;
         goto fail;
     }
+    tess.allocated = true;
     {
         uint8_t* const g = static_cast<uint8_t*>(sc->geometry.p);
         auto at = [&](int k) { return g + part[k].at; };
@@ -2224,7 +2133,7 @@ crh_status crh_scene_status(crh_scene* sc) {
     uint32_t word = 0xFFFFFFFFu;
     crh_status st = settle_tessellation(sc, &word);
     if (st != CRH_OK) return st;
-    return decode_status(sc, word);
+    return decode_status(word);
 }
 void crh_scene_destroy(crh_scene* sc) {
     if (!sc) return;
@@ -2245,8 +2154,10 @@ void crh_scene_destroy(crh_scene* sc) {
     }
     sc->release_all();
     if (sc->geometry_ready) (void)hipEventSynchronize(sc->geometry_ready);
-    for (hipEvent_t e : {sc->tess_done, sc->vertices_free, sc->ranges_free, sc->shadow.tess_done, sc->shadow.vertices_free, sc->shadow.ranges_free, sc->geometry_ready})
-        if (e) (void)hipEventDestroy(e);
+    for (const TessSet& t : sc->tess_set)
+        for (hipEvent_t e : {t.tess_done, t.vertices_free, t.ranges_free})
+            if (e) (void)hipEventDestroy(e);
+    if (sc->geometry_ready) (void)hipEventDestroy(sc->geometry_ready);
     for (hipEvent_t e : sc->rec_raster_done)
         if (e) (void)hipEventDestroy(e);
     for (crh_scene::PassTrial& t : sc->pass_trial)
@@ -2322,7 +2233,7 @@ crh_status crh_scene_download_all(crh_scene* sc, void* vb, void* ib) {
 crh_status crh_scene_traffic(crh_scene* sc, uint64_t* bytes_read, uint64_t* bytes_written) {
     if (!sc) return CRH_ERR_INVALID_ARGUMENT;
     if (bytes_read) *bytes_read = sc->input_bytes;
-    if (bytes_written) *bytes_written = sc->emitted_bytes;
+    if (bytes_written) *bytes_written = sc->tess().emitted_bytes;
     return CRH_OK;
 }
 crh_status crh_scene_set_dynamic_stroke_options(crh_scene* sc, uint32_t shape, uint32_t group, const crh_dynamic_stroke_options* o) {
